@@ -4,6 +4,8 @@
     python bench.py --gpus N --steps K --warmup W        (N > 1: bench.py itself starts one rank per GPU, see _launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus 2 --launcher-selftest          (CPU only: the launcher and the rendezvous, no GPU work)
+    python bench.py ... --full                            (also every side figure and check, see below)
+    python bench.py ... --dump-outputs DIR                (the last timed step's cells and proofs as DIR/<name>.npy)
 
 A step = one pass of the hot path (blob bytes -> 128 cells + 128 proofs per blob) over one batch of
 synthetic blobs that is already resident in HBM, through the device-pointer C ABI
@@ -12,12 +14,16 @@ contiguous blob index with no data-path collective; with N > 1 each step ends wi
 all-gather of the proof vectors (48 B x 128 per blob) on the library's own communicator
 (eth_kzg_amd_all_gather), which is the only exchange north_star names.
 Weak scaling: the per-GPU batch is fixed (default 2048 blobs, batch-saturated as BASELINE.md section 3 asks); at N > 1
-the JSON also carries `configs_strong`: BASELINE configs 4 and 5 AS WRITTEN (512 / 256 blobs in total, split N ways,
+a --full run's JSON also carries `configs_strong`: BASELINE configs 4 and 5 AS WRITTEN (512 / 256 blobs in total, split N ways,
 gathered), timed outside the headline region next to the same total on one GPU -- the strong-scaling numbers.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline`, `cpu_baseline` and, at N = 1, a
-`configs` block: BASELINE.json's other configurations and the reference's own bench set
-(crates/eip7594/benches/benchmark-mt.rs:36-113) measured in the same process, outside the headline region.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it builds the context (the widest tables),
+warms up, times --steps steps, writes the outputs of the last step if --dump-outputs DIR is given, and prints `metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the configuration.  Everything else runs with --full:
+the correctness gate, the context-creation figures, `roofline`, per-stage times, the single-blob latency, `cpu_baseline`,
+and at N = 1 a `configs` block (BASELINE.json's other configurations and the reference's own bench set,
+crates/eip7594/benches/benchmark-mt.rs:36-113), at N > 1 the strong-scaling and device-list legs -- all measured in the
+same process, outside the headline region.  The --no-* options switch single legs of a --full run off.
 """
 import argparse
 import importlib
@@ -769,6 +775,24 @@ def kernel_sources_hash():
     return h.hexdigest()
 
 
+DUMP_BLOBS = {"cells": 32, "proofs": 1024}  # --dump-outputs: at most this many blobs per array (32 MB + 24 MB as float32)
+DUMP_SEED = 0x4B5A47
+
+
+def dump_outputs(dirname, d_cells, d_proofs, B):
+    """--dump-outputs DIR: what the last timed step handed its caller -- every blob's 128 cells and 128 proofs -- as
+    DIR/cells.npy (blobs x 128 x 2048) and DIR/proofs.npy (blobs x 128 x 48), byte values in float32 (exact).  A batch larger
+    than DUMP_BLOBS is sampled: the same seeded, sorted choice of blob indices for the same --blobs-per-gpu, every run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, d, per_blob in (("cells", d_cells, CELLS * BYTES_PER_CELL), ("proofs", d_proofs, CELLS * 48)):
+        k = DUMP_BLOBS[name]
+        idx = np.arange(B) if B <= k else np.sort(np.random.RandomState(DUMP_SEED).choice(B, k, replace=False))
+        rows = d.view(B, per_blob)[torch.from_numpy(idx).to(d.device)].cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), rows.reshape(len(idx), CELLS, -1).astype(np.float32))
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -877,12 +901,153 @@ def _launcher_selftest(args):
         print(json.dumps({"launcher_selftest": True, "n_gpus": world, "gpus_arg": args.gpus, "ranks": ranks}), flush=True)
 
 
+def context_creation_times(ctx, t_ctx0, t_ctx_new, build_probe):
+    """--full: context creation as the reference's "Initialize context" bench sees it (benchmark-mt.rs:103-113): the constructor
+    returned on small start tables (progressive start) t_ctx_new after t_ctx0; a first result is computed on them, then the wide
+    tables arrive.  Returns the figures once the wide tables are in use."""
+    start_width = ctx.window_bits()
+    first_blob = synth_blobs(1, seed=0x4B5A47)[0].tobytes()
+    first_out = ctx.compute_cells_and_kzg_proofs(first_blob)
+    t_ctx_first = time.perf_counter() - t_ctx0
+    _mark("first result computed")
+    # While the helper thread allocates (pieces of < 1 GB) and builds the wide tables, a caller keeps working: one
+    # compute_cells_and_kzg_proofs through the reference's entry point every 5 ms.  How long the slowest of them took is the
+    # stall a service sees during start-up (round 3: one 206 GB hipMalloc froze every HIP call of the process for 2-4.4 s).
+    waits, wait_at, half_s = [], [], None
+    while ctx.tables_ready(0) == 0 and build_probe:
+        t1 = time.perf_counter()
+        out_k = ctx.compute_cells_and_kzg_proofs(first_blob)
+        waits.append(time.perf_counter() - t1)
+        wait_at.append(t1 - t_ctx0)
+        assert out_k == first_out, "a call made while the wide tables were being built returned different bytes"
+        g = ctx.table_groups_ready()
+        if half_s is None and (g >= 64 or ctx.window_bits() != start_width):
+            half_s = time.perf_counter() - t_ctx0
+        time.sleep(0.005)
+    tables_state = ctx.tables_ready(-1)
+    t_ctx = time.perf_counter() - t_ctx0
+    _mark("wide tables ready")
+    assert ctx.compute_cells_and_kzg_proofs(first_blob) == first_out, "start tables and wide tables disagree"
+    ws = sorted(waits)
+    return {"constructor_returns_s": round(t_ctx_new, 3), "first_result_s": round(t_ctx_first, 3), "wide_tables_in_use_s": round(t_ctx, 2),
+            "half_of_the_fk20_groups_on_the_wide_table_s": round(half_s, 2) if half_s is not None else None,
+            "start_table_window_bits": start_width, "final_state": tables_state,
+            "table_allocation": dict(ctx.table_build_info(), note="hipMalloc of the wide tables' pieces (< 1 GB each). On an idle GPU a piece takes ~2 ms (206 GB: 0.4 s); "
+                                     "a piece that takes seconds is the driver wiping memory another process has just freed, and this process's GPU queues "
+                                     "stand still meanwhile -- that, not the library, is what the longest call during the build then shows"),
+            "calls_during_build": {"calls": len(ws), "calls_per_s": round(len(ws) / max(1e-9, t_ctx - t_ctx_first), 1) if ws else None,
+                                   "longest_ms": round(ws[-1] * 1e3, 2) if ws else None, "p99_ms": round(ws[int(0.99 * (len(ws) - 1))] * 1e3, 2) if ws else None,
+                                   "median_ms": round(ws[len(ws) // 2] * 1e3, 2) if ws else None,
+                                   "slowest_three_at_s_ms": [[round(a, 2), round(w * 1e3, 1)] for w, a in sorted(zip(waits, wait_at), reverse=True)[:3]],
+                                   "what": "eth_kzg_compute_cells_and_kzg_proofs of one blob every 5 ms from the calling thread while the helper thread "
+                                           "allocates and builds ~250 GB of window tables; bytes checked against the first result every time"}}
+
+
+def roofline_figures(stages, steps, B, value, window_bits, linmap):
+    """--full: the per-stage HIP-event times of the timed steps and the roofline views of their dominant kernel."""
+    # dominant kernel = the one with the largest accumulated HIP-event time
+    dom = max(stages, key=lambda s: stages[s][0])
+    dom_ms, dom_launches = stages[dom]
+    per_launch_s = dom_ms * 1e-3 / max(1, dom_launches)
+    # gathered additions per (scalar, base) of the FK20 table IN USE: 2 ceil(128 / w) for a GLV table of width w (both 128-bit
+    # halves over the same windows), ceil(255 / w) for a plain one
+    msm_adds = 2 * -(-128 // window_bits)
+    # algorithmic bytes per launch of each kernel family (DESIGN.md "kernels"):
+    alg_bytes = {
+        "blob_to_coeffs": B * (BYTES_PER_BLOB + 4096 * 32),
+        "coeffs_to_cells": B * (4096 * 32 * 2 + 8192 * 32),
+        "fk20_scalars": B * (4096 * 32 + 128 * 64 * 32),
+        # scalars in + one 96-B table entry per (scalar, window) + 128 Jacobian sums out
+        # (2 ceil(128 / w) packed 96-B entries per scalar: 16 at the widest table)
+        "msm_fixed": B * (128 * 64 * 32 + 128 * 64 * msm_adds * 96 + 128 * 168),
+        # one radix-2 layer: 64 butterflies x (2 points in, 2 points out) x 168 B per blob
+        "g1_ifft": B * 64 * 4 * 168,
+        "g1_fft": B * 64 * 4 * 168,
+        "compress": B * 128 * (168 + 48),
+        # compiled linear map: ~3.9 k point operations per blob (350 constant multiplications, 3.2 k additions, 0.4 k
+        # doubling runs), each reading one or two 168-B points and writing one, over its ~42 launches
+        "g1_linmap": B * (sum(linmap[:2]) + 400) * 3 * 168 // max(1, linmap[3]),
+    }[dom]
+    achieved = alg_bytes / per_launch_s / 1e9
+    # HBM traffic of the dominant kernel: NOT measured in this run (PMC passes need rocprofv3) -- taken from the newest
+    # committed profile of this round and labelled with its file name; valid only for the configuration it was collected on
+    traffic, traffic_source, insts_valu, insts_source = None, None, None, None
+    try:
+        import glob
+        files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*_pmc_b2048*.json")))
+        pmc_doc = json.load(open(files[-1]))
+        pm = pmc_doc["kernels"]
+        # the counters are only quoted for the build they were collected on: the profile records a hash of the dominant
+        # kernel's sources (tools/pmc_summary.py); a build whose sources differ gets traffic = null instead of stale numbers
+        if pmc_doc.get("msm_kernel_sources_sha256") != kernel_sources_hash():
+            raise RuntimeError("committed PMC profile belongs to another build of the kernel")
+        want = {"msm_fixed": ("k_msm_glv_chunked",), "g1_linmap": ("k_slp_mulc",)}.get(dom, ())
+        key = next((k for w_ in want for k in pm if w_ in k), None)  # the newest profile names the kernel the default schedule runs
+        if key in pm and B == 2048 and window_bits == 16:
+            # gfx950 correction (MI355X_MICROARCH.md, calibrated for this kernel's 16-B-per-lane gathers in
+            # profiles/r1f_calib_fetch.log): FETCH_SIZE tallies every 128-B line request at 64 B -> double it; WRITE_SIZE is exact
+            traffic = (2.0 * pm[key]["FETCH_SIZE_per_launch_max"] + pm[key]["WRITE_SIZE_per_launch_max"]) * 1024.0
+            traffic_source = os.path.relpath(files[-1], ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this command; not re-measured here)"
+            insts_valu = pm[key].get("SQ_INSTS_VALU_per_launch_max")
+            insts_source = os.path.relpath(files[-1], ROOT) + " (SQ_INSTS_VALU of the same build, rocprofv3 --pmc)"
+    except Exception:
+        pass
+    if insts_valu is None and dom == "msm_fixed":
+        # no counter file for this build: the static count of the kernel's hot loop (4,066 VALU instructions per gathered addition in
+        # the disassembly + the folds; 4,090 per addition measured by SQ_INSTS_VALU on round 5's build) x the additions of a launch
+        insts_valu = 4090.0 * B * 128 * 64 * msm_adds / 64.0
+        insts_source = "static count: 4,090 wave-instructions per gathered addition (profiles/r5c_pmc_sq_b2048_glv16.json) x additions per launch / 64 lanes"
+    stage_ms_per_step = {s: round(stages[s][0] / steps, 3) for s in stages}
+    # integer-VALU view (the bound that actually binds, SURVEY.md 8d)
+    mac_rate = value * 1.0e9 / 1e9  # reference-algorithm count: ~1.0e9 32x32 MACs per blob
+    li = linmap
+    mul_eq = fp_mul_eq_per_blob(window_bits, li[:3] if li[0] else (642, 14 * 64 * 1.5, 0), B)
+    mul_rate = value * mul_eq / 1e9
+    return {
+        # What binds the dominant kernel is integer-VALU issue (SURVEY 8d, VERDICT r4 item 9): achieved = wave-instructions x 64 lanes
+        # / launch time, peak = the measured issue ceiling of this kernel's own 12 : 4 multiply-add mix at the two waves per SIMD its
+        # 212 registers allow (34.4 T lane-ops/s at 2.4 GHz, profiles/r3_ubench_issue.log).  NOTE: under this kernel the chip does
+        # not hold 2.4 GHz -- the SMI reports ~2.0-2.1 GHz at ~1.27 kW (profiles/r5c_bench_clocks_power.log) -- so frac < 1 is mostly
+        # clock, not idle issue slots: GRBM_GUI_ACTIVE / launch time gives the clock, SQ_INSTS_VALU / GRBM cycles the issue rate.
+        "roofline": {"bound": "valu-int", "kernel": dom,
+                     "achieved": (insts_valu * 64.0 / per_launch_s / 1e12) if insts_valu else None, "peak": VALU_MIX_PEAK_TLOPS, "unit": "T lane-ops/s",
+                     "frac": (insts_valu * 64.0 / per_launch_s / 1e12 / VALU_MIX_PEAK_TLOPS) if insts_valu else None,
+                     "wave_instructions_per_launch": insts_valu, "instructions_source": insts_source,
+                     "traffic": traffic, "traffic_source": traffic_source,
+                     "avg_launch_ms": per_launch_s * 1e3, "launches_per_step": dom_launches // max(1, steps),
+                     "note": "integer-VALU issue is what binds (MFMA unused: no dense contraction); peak = measured issue ceiling of the kernel's "
+                             "multiply-add mix at 2 waves/SIMD and 2.4 GHz; the kernel runs at ~2.0-2.1 GHz (power), see roofline_hbm for the byte view"},
+        # the HBM view the contract names, kept as the secondary: both byte counts side by side -- the MANDATORY bytes of SURVEY 8(d)
+        # for this kernel (scalars in + sums out) and the bytes the design chooses to gather from its window table
+        "roofline_hbm": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "algorithmic_bytes_per_launch_gathered": alg_bytes,
+                         "algorithmic_bytes_per_launch_mandatory": B * (128 * 64 * 32 + 128 * 168) if dom == "msm_fixed" else alg_bytes,
+                         "frac_mandatory": (B * (128 * 64 * 32 + 128 * 168) if dom == "msm_fixed" else alg_bytes) / per_launch_s / 1e9 / HBM_PEAK_GBS,
+                         "whole_path_mandatory_bytes_per_blob": ALG_BYTES_PER_BLOB,
+                         "traffic": traffic, "traffic_source": traffic_source},
+        "roofline_valu": {"bound": "valu-int", "achieved": mul_rate, "peak": FP_MUL_PEAK_G, "unit": "G Fp-mul/s",
+                          "frac": mul_rate / FP_MUL_PEAK_G, "fp_mul_eq_per_blob": round(mul_eq),
+                          "reference_algorithm_mac_rate_G": mac_rate, "mac_issue_peak_G": VALU_INT_PEAK_GOPS,
+                          "note": "blobs/s x Fp-multiplication equivalents this build executes per blob / measured sustained "
+                                  "multiplication rate of the signed 13 x 30-bit field (tools/ubench_fp30 --sustained, 2 waves/SIMD); "
+                                  "reference_algorithm_mac_rate = blobs/s x 1.0e9 MACs (SURVEY 8d)"},
+        "whole_path_hbm_frac": value * ALG_BYTES_PER_BLOB / 1e9 / HBM_PEAK_GBS,
+        "stage_ms_per_step": stage_ms_per_step,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--blobs-per-gpu", type=int, default=int(os.environ.get("KZG_BENCH_BLOBS", "2048")))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the correctness gate, context-creation figures, per-stage times and roofline, the "
+                         "timing without stage events, the single-blob latency, the CPU baseline and the side configurations (N = 1), "
+                         "the exchange check and the strong-scaling and device-list legs (N > 1); the --no-* options below drop single legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's cells and proofs as DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the side configurations (BASELINE configs 3-5, ABI, context creation)")
     ap.add_argument("--no-latency-probe", action="store_true",
@@ -891,7 +1056,7 @@ def main():
                     help="do not issue single-blob calls while the wide tables are built (profiling runs: keeps those launches, slowed by the "
                          "table builder next to them, out of rocprofv3's per-kernel averages)")
     ap.add_argument("--strong-configs", action="store_true",
-                    help="also run the strong-scaling legs (configs 4 and 5 as written) at N = 1; they always run at N > 1")
+                    help="with --full: also run the strong-scaling legs (configs 4 and 5 as written) at N = 1; a --full run at N > 1 always has them")
     ap.add_argument("--launcher-selftest", action="store_true", help="CPU only: check the --gpus N launcher and the rendezvous, then exit")
     ap.add_argument("--no-device-list-leg", action="store_true",
                     help="skip the single-process leg: ONE context over the device list (N > 1: all N GPUs from rank 0 after the ranks "
@@ -904,6 +1069,10 @@ def main():
                          "on over torch.distributed's and SAYS SO in config.exchange and on stderr; library-required: fail instead), "
                          "or on torch.distributed's by choice")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.strong_configs and not args.full:
+        ap.error("--strong-configs is a leg of a --full run")
 
     # --gpus N is authoritative: without a launcher's environment bench.py starts the N ranks itself -- before torch or
     # the GPU is touched in this process
@@ -950,48 +1119,18 @@ def main():
 
     kzg = importlib.import_module("rust-eth-kzg_amd")
     sharding = importlib.import_module("rust-eth-kzg_amd.sharding")
-    # Context creation, as the reference's "Initialize context" bench sees it (benchmark-mt.rs:103-113): the constructor
-    # returns on small start tables (progressive start), a first result is computed on them, then the wide tables arrive.
+    # The constructor returns on small start tables (progressive start) while a helper thread builds the wide ones; --full
+    # times that start-up as a caller sees it (context_creation_times), a plain run just waits for the wide tables.
+    ctx_times = None
     t_ctx0 = time.perf_counter()
     ctx = kzg.DASContext(use_precomp=True, device=local_rank, wait_tables=False)  # no CPU fallback: raises/aborts without the HIP path
     t_ctx_new = time.perf_counter() - t_ctx0
     _mark("context constructed")
-    start_width = ctx.window_bits()
-    first_blob = synth_blobs(1, seed=0x4B5A47)[0].tobytes()
-    first_out = ctx.compute_cells_and_kzg_proofs(first_blob)
-    t_ctx_first = time.perf_counter() - t_ctx0
-    _mark("first result computed")
-    # While the helper thread allocates (pieces of < 1 GB) and builds the wide tables, a caller keeps working: one
-    # compute_cells_and_kzg_proofs through the reference's entry point every 5 ms.  How long the slowest of them took is the
-    # stall a service sees during start-up (round 3: one 206 GB hipMalloc froze every HIP call of the process for 2-4.4 s).
-    waits, wait_at, half_s = [], [], None
-    while ctx.tables_ready(0) == 0 and not args.no_build_probe:
-        t1 = time.perf_counter()
-        out_k = ctx.compute_cells_and_kzg_proofs(first_blob)
-        waits.append(time.perf_counter() - t1)
-        wait_at.append(t1 - t_ctx0)
-        assert out_k == first_out, "a call made while the wide tables were being built returned different bytes"
-        g = ctx.table_groups_ready()
-        if half_s is None and (g >= 64 or ctx.window_bits() != start_width):
-            half_s = time.perf_counter() - t_ctx0
-        time.sleep(0.005)
-    tables_state = ctx.tables_ready(-1)
-    t_ctx = time.perf_counter() - t_ctx0
-    _mark("wide tables ready")
-    assert ctx.compute_cells_and_kzg_proofs(first_blob) == first_out, "start tables and wide tables disagree"
-    ws = sorted(waits)
-    ctx_times = {"constructor_returns_s": round(t_ctx_new, 3), "first_result_s": round(t_ctx_first, 3), "wide_tables_in_use_s": round(t_ctx, 2),
-                 "half_of_the_fk20_groups_on_the_wide_table_s": round(half_s, 2) if half_s is not None else None,
-                 "start_table_window_bits": start_width, "final_state": tables_state,
-                 "table_allocation": dict(ctx.table_build_info(), note="hipMalloc of the wide tables' pieces (< 1 GB each). On an idle GPU a piece takes ~2 ms (206 GB: 0.4 s); "
-                                          "a piece that takes seconds is the driver wiping memory another process has just freed, and this process's GPU queues "
-                                          "stand still meanwhile -- that, not the library, is what the longest call during the build then shows"),
-                 "calls_during_build": {"calls": len(ws), "calls_per_s": round(len(ws) / max(1e-9, t_ctx - t_ctx_first), 1) if ws else None,
-                                        "longest_ms": round(ws[-1] * 1e3, 2) if ws else None, "p99_ms": round(ws[int(0.99 * (len(ws) - 1))] * 1e3, 2) if ws else None,
-                                        "median_ms": round(ws[len(ws) // 2] * 1e3, 2) if ws else None,
-                                        "slowest_three_at_s_ms": [[round(a, 2), round(w * 1e3, 1)] for w, a in sorted(zip(waits, wait_at), reverse=True)[:3]],
-                                        "what": "eth_kzg_compute_cells_and_kzg_proofs of one blob every 5 ms from the calling thread while the helper thread "
-                                                "allocates and builds ~250 GB of window tables; bytes checked against the first result every time"}}
+    if args.full:
+        ctx_times = context_creation_times(ctx, t_ctx0, t_ctx_new, build_probe=not args.no_build_probe)
+    else:
+        ctx.tables_ready(-1)  # the headline runs on the wide tables
+        _mark("wide tables ready")
 
     B = args.blobs_per_gpu
     blobs_h = synth_blobs(B, seed=0x4B5A47 + rank)
@@ -1050,31 +1189,35 @@ def main():
         torch.cuda.synchronize(dev)
         return t_local
 
-    # correctness gate on the first run (status + the data-in-first-half invariant, fk20/prover.rs:251-275)
-    st = ctx.compute_cells_and_kzg_proofs_device(B, d_blobs.data_ptr(), d_cells.data_ptr(), d_proofs.data_ptr(),
-                                                 want_status=True, stream=None)
-    assert st == [0] * B, "synthetic blobs rejected"
-    torch.cuda.synchronize(dev)
-    first_half = d_cells.view(B, 2, 64 * BYTES_PER_CELL)[:, 0, :]
-    assert torch.equal(first_half, d_blobs), "cells[0..63] != blob"
-
     gather_checked = None
-    if world > 1:  # the exchange itself, once, before timing: rank r's slab of the gathered vector must be rank r's proofs
-        step()
-        fence()
-        mine = d_proofs.view(-1, 8).view(torch.int64).sum().reshape(1)
-        sums = torch.empty(world, dtype=torch.int64, device=dev)
-        hz.all_gather_into(sums, mine)  # (torch's communicator: an independent path for the check)
-        got = d_all_proofs.view(world, -1, 8).view(torch.int64).sum(dim=(1, 2))
-        gather_checked = bool(torch.equal(sums, got)) and bool(torch.equal(d_all_proofs.view(world, -1)[rank], d_proofs))
-        flag = torch.tensor([1 if gather_checked else 0], dtype=torch.int32, device=dev)
-        hz.all_reduce(flag, dist.ReduceOp.MIN)
-        if not int(flag.item()):
-            raise SystemExit("bench.py: the all-gathered proof vector does not match the ranks' own proofs")
-    _mark("correctness gate passed; warm-up")
+    if args.full:
+        # correctness gate on the first run (status + the data-in-first-half invariant, fk20/prover.rs:251-275)
+        st = ctx.compute_cells_and_kzg_proofs_device(B, d_blobs.data_ptr(), d_cells.data_ptr(), d_proofs.data_ptr(),
+                                                     want_status=True, stream=None)
+        assert st == [0] * B, "synthetic blobs rejected"
+        torch.cuda.synchronize(dev)
+        first_half = d_cells.view(B, 2, 64 * BYTES_PER_CELL)[:, 0, :]
+        assert torch.equal(first_half, d_blobs), "cells[0..63] != blob"
+
+        if world > 1:  # the exchange itself, once, before timing: rank r's slab of the gathered vector must be rank r's proofs
+            step()
+            fence()
+            mine = d_proofs.view(-1, 8).view(torch.int64).sum().reshape(1)
+            sums = torch.empty(world, dtype=torch.int64, device=dev)
+            hz.all_gather_into(sums, mine)  # (torch's communicator: an independent path for the check)
+            got = d_all_proofs.view(world, -1, 8).view(torch.int64).sum(dim=(1, 2))
+            gather_checked = bool(torch.equal(sums, got)) and bool(torch.equal(d_all_proofs.view(world, -1)[rank], d_proofs))
+            flag = torch.tensor([1 if gather_checked else 0], dtype=torch.int32, device=dev)
+            hz.all_reduce(flag, dist.ReduceOp.MIN)
+            if not int(flag.item()):
+                raise SystemExit("bench.py: the all-gathered proof vector does not match the ranks' own proofs")
+        _mark("correctness gate passed")
+    _mark("warm-up")
     for _ in range(args.warmup):
         step()
     fence()
+    # the timed region, the same in a plain and a --full run (with the per-stage events it has always had, so that ms_per_step
+    # keeps its meaning; --full reports the stage times and the cost of the events)
     ctx.set_profiling(True)
     ctx.get_stage_times()
     t0 = time.perf_counter()
@@ -1084,12 +1227,16 @@ def main():
     dt = time.perf_counter() - t0
     stages = ctx.get_stage_times()
     ctx.set_profiling(False)
+    _mark("timed steps done")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_cells, d_proofs, B)
     dt_rank = t_local_end - t0  # without the wait for the slowest rank
     per_rank_ms, gather_ms = None, None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         hz.all_reduce(t, dist.ReduceOp.MAX)
         dt = float(t.item())
+    if world > 1 and args.full:
         # one line must be enough to diagnose a bad scaling curve: every rank's own time per step, and the all-gather alone
         mine = torch.tensor([dt_rank / args.steps * 1e3], dtype=torch.float64, device=dev)
         allr = torch.empty(world, dtype=torch.float64, device=dev)
@@ -1107,32 +1254,33 @@ def main():
         tgm = torch.tensor([(time.perf_counter() - tg) / args.steps * 1e3], dtype=torch.float64, device=dev)
         hz.all_reduce(tgm, dist.ReduceOp.MAX)
         gather_ms = round(float(tgm.item()), 3)
-    # the same K steps once more WITHOUT the per-stage events (they also keep the small-batch cells kernel on the main stream):
-    # what the instrumentation of the timed region costs, stated instead of assumed
-    fence()
-    t0u = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    dt_plain = time.perf_counter() - t0u
-    if world > 1:
-        t = torch.tensor([dt_plain], dtype=torch.float64, device=dev)
-        hz.all_reduce(t, dist.ReduceOp.MAX)
-        dt_plain = float(t.item())
+    dt_plain, lat = None, []
+    if args.full:
+        # the same K steps once more WITHOUT the per-stage events (they also keep the small-batch cells kernel on the main stream):
+        # what the instrumentation of the timed region costs, stated instead of assumed
+        fence()
+        t0u = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        dt_plain = time.perf_counter() - t0u
+        if world > 1:
+            t = torch.tensor([dt_plain], dtype=torch.float64, device=dev)
+            hz.all_reduce(t, dist.ReduceOp.MAX)
+            dt_plain = float(t.item())
 
-    # single-blob latency (BASELINE.json config 2), outside the timed region
-    lat = []
-    for _ in range(0 if args.no_latency_probe else 3):
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        with torch.cuda.stream(stream):
-            ctx.compute_cells_and_kzg_proofs_device(1, d_blobs.data_ptr(), d_cells.data_ptr(), d_proofs.data_ptr(),
-                                                    want_status=False, stream=stream.cuda_stream)
-        torch.cuda.synchronize(dev)
-        lat.append(time.perf_counter() - t1)
+        # single-blob latency (BASELINE.json config 2), outside the timed region
+        for _ in range(0 if args.no_latency_probe else 3):
+            torch.cuda.synchronize(dev)
+            t1 = time.perf_counter()
+            with torch.cuda.stream(stream):
+                ctx.compute_cells_and_kzg_proofs_device(1, d_blobs.data_ptr(), d_cells.data_ptr(), d_proofs.data_ptr(),
+                                                        want_status=False, stream=stream.cuda_stream)
+            torch.cuda.synchronize(dev)
+            lat.append(time.perf_counter() - t1)
 
     strong = None
-    if world > 1 or args.strong_configs:
+    if args.full and (world > 1 or args.strong_configs):
         try:
             strong = strong_configs(ctx, sharding, torch, dist, dev, world, rank, lib_comm, stream, hz)
         except SystemExit:
@@ -1143,7 +1291,7 @@ def main():
     # what the record quotes from the context (read now: at N > 1 the context is freed before the record is written)
     ctx_window_bits, ctx_table_bytes, ctx_linmap = ctx.window_bits(), ctx.table_bytes(), ctx.linmap_info()
     device_list = None
-    if world > 1 and not args.no_device_list_leg:
+    if world > 1 and args.full and not args.no_device_list_leg:
         # The process-per-GPU form is measured; now the form a drop-in host gets without launching anything: rank 0 alone, ONE context
         # over all N GPUs.  Every rank first frees its context (its tables would not leave room for a second set on its GPU), the
         # others wait at the barrier.  On the library's DEFAULT table budget (what such a host gets), per-GPU share = half the
@@ -1176,75 +1324,17 @@ def main():
     if rank == 0:
         total_blobs = B * world * args.steps
         value = total_blobs / dt
-        # dominant kernel = the one with the largest accumulated HIP-event time
-        dom = max(stages, key=lambda s: stages[s][0])
-        dom_ms, dom_launches = stages[dom]
-        per_launch_s = dom_ms * 1e-3 / max(1, dom_launches)
-        # gathered additions per (scalar, base) of the FK20 table IN USE: 2 ceil(128 / w) for a GLV table of width w (both 128-bit
-        # halves over the same windows), ceil(255 / w) for a plain one
         wbits = ctx_window_bits
-        msm_adds = 2 * -(-128 // wbits)
-        # algorithmic bytes per launch of each kernel family (DESIGN.md "kernels"):
-        alg_bytes = {
-            "blob_to_coeffs": B * (BYTES_PER_BLOB + 4096 * 32),
-            "coeffs_to_cells": B * (4096 * 32 * 2 + 8192 * 32),
-            "fk20_scalars": B * (4096 * 32 + 128 * 64 * 32),
-            # scalars in + one 96-B table entry per (scalar, window) + 128 Jacobian sums out
-            # (2 ceil(128 / w) packed 96-B entries per scalar: 16 at the widest table)
-            "msm_fixed": B * (128 * 64 * 32 + 128 * 64 * msm_adds * 96 + 128 * 168),
-            # one radix-2 layer: 64 butterflies x (2 points in, 2 points out) x 168 B per blob
-            "g1_ifft": B * 64 * 4 * 168,
-            "g1_fft": B * 64 * 4 * 168,
-            "compress": B * 128 * (168 + 48),
-            # compiled linear map: ~3.9 k point operations per blob (350 constant multiplications, 3.2 k additions, 0.4 k
-            # doubling runs), each reading one or two 168-B points and writing one, over its ~42 launches
-            "g1_linmap": B * (sum(ctx_linmap[:2]) + 400) * 3 * 168 // max(1, ctx_linmap[3]),
-        }[dom]
-        achieved = alg_bytes / per_launch_s / 1e9
-        # HBM traffic of the dominant kernel: NOT measured in this run (PMC passes need rocprofv3) -- taken from the newest
-        # committed profile of this round and labelled with its file name; valid only for the configuration it was collected on
-        traffic, traffic_source, insts_valu, insts_source = None, None, None, None
-        try:
-            import glob
-            files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9]*_pmc_b2048*.json")))
-            pmc_doc = json.load(open(files[-1]))
-            pm = pmc_doc["kernels"]
-            # the counters are only quoted for the build they were collected on: the profile records a hash of the dominant
-            # kernel's sources (tools/pmc_summary.py); a build whose sources differ gets traffic = null instead of stale numbers
-            if pmc_doc.get("msm_kernel_sources_sha256") != kernel_sources_hash():
-                raise RuntimeError("committed PMC profile belongs to another build of the kernel")
-            want = {"msm_fixed": ("k_msm_glv_chunked",), "g1_linmap": ("k_slp_mulc",)}.get(dom, ())
-            key = next((k for w_ in want for k in pm if w_ in k), None)  # the newest profile names the kernel the default schedule runs
-            if key in pm and B == 2048 and ctx_window_bits == 16:
-                # gfx950 correction (MI355X_MICROARCH.md, calibrated for this kernel's 16-B-per-lane gathers in
-                # profiles/r1f_calib_fetch.log): FETCH_SIZE tallies every 128-B line request at 64 B -> double it; WRITE_SIZE is exact
-                traffic = (2.0 * pm[key]["FETCH_SIZE_per_launch_max"] + pm[key]["WRITE_SIZE_per_launch_max"]) * 1024.0
-                traffic_source = os.path.relpath(files[-1], ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this command; not re-measured here)"
-                insts_valu = pm[key].get("SQ_INSTS_VALU_per_launch_max")
-                insts_source = os.path.relpath(files[-1], ROOT) + " (SQ_INSTS_VALU of the same build, rocprofv3 --pmc)"
-        except Exception:
-            pass
-        if insts_valu is None and dom == "msm_fixed":
-            # no counter file for this build: the static count of the kernel's hot loop (4,066 VALU instructions per gathered addition in
-            # the disassembly + the folds; 4,090 per addition measured by SQ_INSTS_VALU on round 5's build) x the additions of a launch
-            insts_valu = 4090.0 * B * 128 * 64 * msm_adds / 64.0
-            insts_source = "static count: 4,090 wave-instructions per gathered addition (profiles/r5c_pmc_sq_b2048_glv16.json) x additions per launch / 64 lanes"
-        stage_ms_per_step = {s: round(stages[s][0] / args.steps, 3) for s in stages}
-        # integer-VALU view (the bound that actually binds)
-        mac_rate = value * 1.0e9 / 1e9  # reference-algorithm count: ~1.0e9 32x32 MACs per blob
+        msm_adds = 2 * -(-128 // wbits)  # gathered additions per (scalar, base) of the FK20 table in use
         li = ctx_linmap
-        mul_eq = fp_mul_eq_per_blob(ctx_window_bits, li[:3] if li[0] else (642, 14 * 64 * 1.5, 0), args.blobs_per_gpu)
-        mul_rate = value * mul_eq / 1e9
         out = {
             "metric": "blobs/sec compute_cells_and_kzg_proofs (4096-pt blob)",
             "value": value, "unit": "blobs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "ms_per_step_without_stage_events": round(dt_plain / args.steps * 1e3, 3),
-            "ms_per_step_per_rank": per_rank_ms, "all_gather_ms_per_step": gather_ms,
             "vs_baseline": None, "dtype": "u32", "dtype_note": "381-bit Fp as 13 signed 30-bit digits (everything between the scalars and the proof bytes of this batch: MSM, the G1 linear map's multiplications and additions), 14x29-bit / 12x32-bit limbs in the latency paths, codecs and verification, 255-bit Fr as 8x32-bit (stored) and 9x29-bit (inside the transforms) limbs, Montgomery integers; exact arithmetic", "data": "synthetic",
             "config": {"workload": f"compute_cells_and_kzg_proofs on DEVICE-RESIDENT blobs (inputs and outputs stay in HBM; the "
                                    f"host-pointer ABI rate is configs.abi_host_pointer_batch), batch-saturated: {B} synthetic blobs "
-                                   f"per GPU per step (config 2's single blob is reported as single_blob_latency_ms)",
+                                   f"per GPU per step (config 2's single blob: single_blob_latency_ms of a --full run)",
                        "blobs_per_gpu": B, "use_precomp": True, "window_bits": ctx_window_bits,
                        "fk20_table": f"GLV: {msm_adds // 2} windows of {wbits} bits per 128-bit half scalar, packed 96-B entries, {msm_adds} gathered additions per base",
                        "table_GB": round(ctx_table_bytes / 1e9, 2),
@@ -1258,53 +1348,29 @@ def main():
                        "launcher": os.environ.get("KZG_BENCH_LAUNCHER", "external (torch.distributed.run)") if world > 1 else "none",
                        "rehearsal": "KZG_BENCH_REHEARSAL=1: all ranks share GPU 0, gloo for the harness, small tables -- a check of the N > 1 code paths, NOT a measurement" if rehearsal else None,
                        "gathered_proofs_checked": gather_checked},
-            # What binds the dominant kernel is integer-VALU issue: achieved = wave-instructions x 64 lanes
-            # / launch time, peak = the measured issue ceiling of this kernel's own 12 : 4 multiply-add mix at the two waves per SIMD its
-            # 212 registers allow (34.4 T lane-ops/s at 2.4 GHz, profiles/r3_ubench_issue.log).  NOTE: under this kernel the chip does
-            # not hold 2.4 GHz -- the SMI reports ~2.0-2.1 GHz at ~1.27 kW (profiles/r5c_bench_clocks_power.log) -- so frac < 1 is mostly
-            # clock, not idle issue slots: GRBM_GUI_ACTIVE / launch time gives the clock, SQ_INSTS_VALU / GRBM cycles the issue rate.
-            "roofline": {"bound": "valu-int", "kernel": dom,
-                         "achieved": (insts_valu * 64.0 / per_launch_s / 1e12) if insts_valu else None, "peak": VALU_MIX_PEAK_TLOPS, "unit": "T lane-ops/s",
-                         "frac": (insts_valu * 64.0 / per_launch_s / 1e12 / VALU_MIX_PEAK_TLOPS) if insts_valu else None,
-                         "wave_instructions_per_launch": insts_valu, "instructions_source": insts_source,
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "avg_launch_ms": per_launch_s * 1e3, "launches_per_step": dom_launches // max(1, args.steps),
-                         "note": "integer-VALU issue is what binds (MFMA unused: no dense contraction); peak = measured issue ceiling of the kernel's "
-                                 "multiply-add mix at 2 waves/SIMD and 2.4 GHz; the kernel runs at ~2.0-2.1 GHz (power), see roofline_hbm for the byte view"},
-            # the HBM view the contract names, kept as the secondary: both byte counts side by side -- the MANDATORY bytes of SURVEY 8(d)
-            # for this kernel (scalars in + sums out) and the bytes the design chooses to gather from its window table
-            "roofline_hbm": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                             "frac": achieved / HBM_PEAK_GBS, "algorithmic_bytes_per_launch_gathered": alg_bytes,
-                             "algorithmic_bytes_per_launch_mandatory": B * (128 * 64 * 32 + 128 * 168) if dom == "msm_fixed" else alg_bytes,
-                             "frac_mandatory": (B * (128 * 64 * 32 + 128 * 168) if dom == "msm_fixed" else alg_bytes) / per_launch_s / 1e9 / HBM_PEAK_GBS,
-                             "whole_path_mandatory_bytes_per_blob": ALG_BYTES_PER_BLOB,
-                             "traffic": traffic, "traffic_source": traffic_source},
-            "roofline_valu": {"bound": "valu-int", "achieved": mul_rate, "peak": FP_MUL_PEAK_G, "unit": "G Fp-mul/s",
-                              "frac": mul_rate / FP_MUL_PEAK_G, "fp_mul_eq_per_blob": round(mul_eq),
-                              "reference_algorithm_mac_rate_G": mac_rate, "mac_issue_peak_G": VALU_INT_PEAK_GOPS,
-                              "note": "blobs/s x Fp-multiplication equivalents this build executes per blob / measured sustained "
-                                      "multiplication rate of the signed 13 x 30-bit field (tools/ubench_fp30 --sustained, 2 waves/SIMD); "
-                                      "reference_algorithm_mac_rate = blobs/s x 1.0e9 MACs (SURVEY 8d)"},
-            "whole_path_hbm_frac": value * ALG_BYTES_PER_BLOB / 1e9 / HBM_PEAK_GBS,
-            "stage_ms_per_step": stage_ms_per_step,
-            "single_blob_latency_ms": (min(lat) * 1e3) if lat else None,
-            "context_creation_s": None,
         }
+        if args.full:
+            out.update(roofline_figures(stages, args.steps, B, value, ctx_window_bits, ctx_linmap))
+            out.update({"ms_per_step_without_stage_events": round(dt_plain / args.steps * 1e3, 3),
+                        "ms_per_step_per_rank": per_rank_ms, "all_gather_ms_per_step": gather_ms,
+                        "single_blob_latency_ms": (min(lat) * 1e3) if lat else None, "context_creation_s": None})
         if strong is not None:
             out["configs_strong"] = strong
         if device_list is not None:
             out["single_process_device_list"] = device_list
-        if world > 1:
+        if world > 1 and args.full:
             out["omitted_at_n_gpus_above_1"] = ["cpu_baseline", "configs (single-GPU side figures)", "blobs_per_s_vs_table_memory"]
+        side = args.full and world == 1  # the single-GPU side figures of a --full run
         extra = None
-        if not args.no_configs and world == 1:
+        if side and not args.no_configs:
             out["configs"], extra = side_configs(ctx, kzg, torch, dev, blobs_h, ctx_times)
-        out["context_creation_s"] = ctx_times
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out["context_creation_s"] = ctx_times
+        if side and not args.no_cpu_baseline:
             gpu_first = (bytes(d_cells[:CELLS * BYTES_PER_CELL].cpu().numpy()), bytes(d_proofs[:CELLS * 48].cpu().numpy()))
             out["cpu_baseline"] = cpu_baseline([bytes(blobs_h[i].tobytes()) for i in range(min(B, 32))], gpu_first=gpu_first, extra=extra)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        if not args.no_configs and world == 1:
+        if side and not args.no_configs:
             # blobs/s against window-table memory: the main context goes first (its 249 GB leave no room),
             # then one context per table size on the same resident batch.  UsePrecomp::Yes{width} is the reference's knob
             # (fixed_base_msm.rs:41-49).

@@ -5,7 +5,7 @@ REPO=$(cd "$(dirname "$0")/.." && pwd)
 for r in 1 2 3; do for V in base c2 c3; do
   lib=$REPO/rust-eth-kzg_amd/libc_eth_kzg.so; [ $V != base ] && lib=$REPO/rust-eth-kzg_amd/ab/libc_eth_kzg_$V.so
   for B in 3 4; do
-    ms=$(ETH_KZG_AMD_LIB=$lib python $REPO/bench.py --blobs-per-gpu $B --steps 40 --warmup 5 --no-cpu-baseline --no-latency-probe --no-configs --no-build-probe --no-device-list-leg 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step_without_stage_events'],3))")
+    ms=$(ETH_KZG_AMD_LIB=$lib python $REPO/bench.py --full --blobs-per-gpu $B --steps 40 --warmup 5 --no-cpu-baseline --no-latency-probe --no-configs --no-build-probe --no-device-list-leg 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step_without_stage_events'],3))")
     echo "round $r $V blobs=$B: $ms ms"
   done
 done; done

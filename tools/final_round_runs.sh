@@ -8,7 +8,7 @@ cd "$REPO"
 python -m pytest tests -m gpu -x -q > "$OUT/gpu_suite.log" 2>&1; echo "pytest rc=$?" >> "$OUT/gpu_suite.log"
 bash tools/collect_profiles.sh r6 > "$OUT/collect.log" 2>&1
 cd "$REPO"
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 bash tools/sweep_tiny_and_other.sh > "$OUT/sweep_tiny_and_other.log" 2>&1
 bash tools/sweep_small_batches.sh > "$OUT/sweep_small_batches.log" 2>&1
 bash tools/sweep_mid_batches.sh > "$OUT/sweep_mid_batches.log" 2>&1

@@ -3,7 +3,7 @@
 # (the point kernels are power-limited: the clock they get, not the instruction count alone, sets their time).
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${1:-$REPO/gpurun_out/clocks.log}
-python3 "$REPO/bench.py" --steps 400 --warmup 3 --no-cpu-baseline --no-latency-probe --no-configs --no-build-probe > "$OUT.bench.json" 2> /dev/null &
+python3 "$REPO/bench.py" --full --steps 400 --warmup 3 --no-cpu-baseline --no-latency-probe --no-configs --no-build-probe > "$OUT.bench.json" 2> /dev/null &
 PID=$!
 sleep 14
 for i in $(seq 1 40); do

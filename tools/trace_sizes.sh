@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/trace_sizes
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for B in "$@"; do
-  rocprofv3 --kernel-trace --stats -d "$OUT/t$B" -o t --output-format csv -- python3 "$REPO/bench.py" --blobs-per-gpu $B --steps 6 --warmup 2 --no-cpu-baseline --no-latency-probe --no-configs --no-build-probe --no-device-list-leg > "$OUT/bench_b$B.json" 2> "$OUT/t$B.err"
+  rocprofv3 --kernel-trace --stats -d "$OUT/t$B" -o t --output-format csv -- python3 "$REPO/bench.py" --full --blobs-per-gpu $B --steps 6 --warmup 2 --no-cpu-baseline --no-latency-probe --no-configs --no-build-probe --no-device-list-leg > "$OUT/bench_b$B.json" 2> "$OUT/t$B.err"
   cp "$(find "$OUT/t$B" -name '*kernel_stats.csv' | head -1)" "$OUT/kernel_stats_b$B.csv"
   rm -rf "$OUT/t$B"
   echo "== $B"; head -8 "$OUT/kernel_stats_b$B.csv" | cut -c1-150
