@@ -16,6 +16,13 @@ int eth_kzg_amd_test_g1_decompress(const DASContext *ctx, const uint8_t *in, int
 int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const uint8_t *b, uint8_t *out, int n,
                                int is_fp);
 
+/* One field or point operation of the kernels per element (csrc/k_test_ops.hip), on the raw words of the device structs.
+ * eth_kzg_amd_test_op_info: word counts per element of operation `op` (0, 1, ... until it returns -1), whether it exists on the
+ * device only (the pair / quad forms, the tree folds) and its name.  eth_kzg_amd_test_op: n elements of in_words each in, n of
+ * out_words each out; on_device = 0 runs the host pass of the same source (ctx may be NULL; an error for the device-only forms). */
+int eth_kzg_amd_test_op_info(int op, int32_t *in_words, int32_t *out_words, int32_t *device_only, const char **name);
+int eth_kzg_amd_test_op(const DASContext *ctx, int op, int n, const int32_t *in, int32_t *out, int on_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,7 +65,7 @@ EXPORTED_SYMBOLS = [
 # include/c_eth_kzg_test_hooks.h: stage-level hooks for tests/, not part of the drop-in ABI
 TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_fr_ntt4096", "eth_kzg_amd_test_g1_fft128", "eth_kzg_amd_test_fixed_msm",
-    "eth_kzg_amd_test_g1_decompress", "eth_kzg_amd_test_field_mul",
+    "eth_kzg_amd_test_g1_decompress", "eth_kzg_amd_test_field_mul", "eth_kzg_amd_test_op_info", "eth_kzg_amd_test_op",
 ]
 
 _lib = None
@@ -157,6 +157,8 @@ def load_library():
         "eth_kzg_amd_test_fixed_msm": [P, U8P, C.c_int, P],
         "eth_kzg_amd_test_g1_decompress": [P, U8P, C.c_int, C.c_int, P, P],
         "eth_kzg_amd_test_field_mul": [P, U8P, U8P, P, C.c_int, C.c_int],
+        "eth_kzg_amd_test_op_info": [C.c_int, P, P, P, C.POINTER(C.c_char_p)],
+        "eth_kzg_amd_test_op": [P, C.c_int, C.c_int, P, P, C.c_int],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args

@@ -198,6 +198,7 @@ public:
     int test_fixed_msm(const uint8_t* scalars_be, int n_msm, uint8_t* out_compressed);
     int test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out_recompressed);
     int test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp);
+    int test_op(int op, int n, const int32_t* in, int32_t* out);
 
     // ---- per-stage HIP-event timing (bench.py's roofline leg) ----
     enum Stage { ST_BLOB_TO_COEFFS = 0, ST_COEFFS_TO_CELLS, ST_FK20_SCALARS, ST_MSM_FIXED, ST_G1_IFFT, ST_G1_FFT,

@@ -136,4 +136,29 @@ int Engine::test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int
     return OK;
 }
 
+// one operation of k_test_ops.hip per element: n elements of the op's input words in, n of its output words out
+int Engine::test_op(int op, int n, const int32_t* in, int32_t* out) {
+    int in_w, out_w, dev_only;
+    const char* name;
+    if (launch::test_op_info(op, &in_w, &out_w, &dev_only, &name) != 0 || n <= 0) return ERR_INPUT;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        const size_t ni = (size_t)n * in_w * sizeof(int32_t), no = (size_t)n * out_w * sizeof(int32_t);
+        int32_t *di, *dout;
+        HIPCK(hipMalloc(&di, ni)); HIPCK(hipMalloc(&dout, no));
+        HIPCK(hipMemcpy(di, in, ni, hipMemcpyHostToDevice));
+        HIPCK(hipMemset(dout, 0, no));
+        launch::test_op_device(op, n, di, dout, stream_);
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(stream_));
+        HIPCK(hipMemcpy(out, dout, no, hipMemcpyDeviceToHost));
+        HIPCK(hipFree(di)); HIPCK(hipFree(dout));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 }  // namespace kzg

@@ -32,6 +32,10 @@ void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, con
 void test_ntt4096(const uint8_t* in, uint8_t* out, const void* w29, const Fr8& n_inv, int inverse_dit, hipStream_t st);
 void test_scalars_be(const uint8_t* in, void* out, size_t n, hipStream_t st);
 void test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp, hipStream_t st);
+// k_test_ops.hip (hooks library only): one field or point operation per element on raw words; the HD operations also on the host
+int test_op_info(int op, int* in_words, int* out_words, int* device_only, const char** name);
+int test_op_host(int op, int n, const int32_t* in, int32_t* out);
+int test_op_device(int op, int n, const int32_t* d_in, int32_t* d_out, hipStream_t st);
 
 // k_msm.hip
 // A window table as the kernels see it: a device array of block pointers -- two per group (blocks[2 group + upper]: the lower

@@ -529,32 +529,101 @@ def _blob_from_coefficients(coeffs):
     return b"".join(ev[32 * brp(k):32 * brp(k) + 32] for k in range(4096))
 
 
-def test_sparse_polynomials_hit_the_degenerate_point_operations(ctx, oracle):
-    """Polynomials with one or two non-zero coefficients: most of the 8192 FK20 scalars are zero, whole MSMs are the
-    identity, the additions and doublings of the compiled linear map meet identity operands, equal and opposite points
-    (their exact slow paths), and the constant multiplications meet the identity.  Batches of 12 (compiled map, windowed
-    MSM), and the same blobs alone (circulant path, flat MSM) must all give the oracle's bytes."""
-    def poly(*terms):
-        c = [0] * 4096
-        for idx, val in terms:
-            c[idx] = val
-        return c
-    polys = [poly((0, 1)), poly((63, 5)), poly((64, 1)), poly((65, synth.R - 1)), poly((4032, 7)), poly((4095, 1)),
-             poly((64, 1), (128, 1)), poly((64, 1), (128, synth.R - 1)), poly((100, 3), (4000, 9)), [1] * 4096,
-             poly(*[(64 * m, 1) for m in range(64)]), poly(*[(i, i + 1) for i in range(64)])]
-    blobs = [_blob_from_coefficients(c) for c in polys]
-    st, cells, proofs = ctx.compute_cells_and_kzg_proofs_batch(blobs)
-    assert st == [0] * len(blobs)
+def _sparse_poly(*terms):
+    c = [0] * 4096
+    for idx, val in terms:
+        c[idx] = val
+    return c
+
+
+# Polynomials with one or two non-zero coefficients (and two dense but structured ones): most of the 8192 FK20 scalars are zero,
+# whole MSMs are the identity, the additions and doublings of the compiled linear map meet identity operands, equal and opposite
+# points (their exact slow paths), and the constant multiplications meet the identity.
+SPARSE_POLYS = [_sparse_poly((0, 1)), _sparse_poly((63, 5)), _sparse_poly((64, 1)), _sparse_poly((65, synth.R - 1)),
+                _sparse_poly((4032, 7)), _sparse_poly((4095, 1)), _sparse_poly((64, 1), (128, 1)),
+                _sparse_poly((64, 1), (128, synth.R - 1)), _sparse_poly((100, 3), (4000, 9)), [1] * 4096,
+                _sparse_poly(*[(64 * m, 1) for m in range(64)]), _sparse_poly(*[(i, i + 1) for i in range(64)])]
+
+
+@pytest.fixture(scope="module")
+def sparse_expected(oracle):
+    """the 12 sparse polynomials' blobs and the oracle's cells and proofs, computed once for the module"""
+    blobs = [_blob_from_coefficients(c) for c in SPARSE_POLYS]
+    return blobs, [oracle.compute_cells_and_kzg_proofs(b) for b in blobs]
+
+
+def _sparse_positions(n):
+    """where the 12 sparse blobs go in a batch of n: the even and the odd lane of a pair, both edges of a 32-blob pair-form wave
+    and of a 16-blob quad-form wave, both sides of every 64-lane group boundary, the batch's last blob"""
+    if n <= 12:
+        return list(range(n))
+    want = [0, 1, 63, 64, n - 2, n - 1, 31, 32, 127, 128, 15, 16, 191, 192, 255, 256]
+    pos = []
+    for q in want:
+        if q < n and q not in pos and len(pos) < 12:
+            pos.append(q)
+    k = 2
+    while len(pos) < 12:  # small batches: fill with interior odd / even positions
+        if k not in pos and k < n:
+            pos.append(k)
+        k += 1
+    return sorted(pos[:12])
+
+
+def _sparse_batch_matches_oracle(ctx, sparse_expected, n):
+    """the 12 sparse polynomials at _sparse_positions(n) of a batch of n, random blobs around them: the sparse blobs must give the
+    oracle's bytes (n = 2: the 12 as six batches of two); returns (batch, positions, cells, proofs) for further checks"""
+    blobs, expected = sparse_expected
+    if n == 2:
+        for k in range(0, 12, 2):
+            st, cells, proofs = ctx.compute_cells_and_kzg_proofs_batch(blobs[k:k + 2])
+            assert st == [0, 0]
+            for j in range(2):
+                assert (cells[j], proofs[j]) == expected[k + j], f"polynomial {k + j} in a batch of 2"
+        return None
+    pos = _sparse_positions(n)
+    assert len(pos) == 12
+    rnd = _random_blobs(n, 5150 + n)
+    batch = [rnd[i].tobytes() for i in range(n)]
+    for k, q in enumerate(pos):
+        batch[q] = blobs[k]
+    st, cells, proofs = ctx.compute_cells_and_kzg_proofs_batch(batch)
+    assert st == [0] * n
+    for k, q in enumerate(pos):
+        ec, ep = expected[k]
+        assert cells[q] == ec and proofs[q] == ep, f"polynomial {k} at position {q} of {n}"
+    return batch, pos, cells, proofs
+
+
+def test_sparse_polynomials_hit_the_degenerate_point_operations(ctx, oracle, sparse_expected):
+    """The 12 sparse polynomials as one batch of 12 (compiled map in its quad forms, windowed MSM), each alone (circulant path,
+    flat MSM) and in a batch that fills lane groups unevenly (70 = 64 + 6 lanes) next to random blobs: all must give the oracle's
+    bytes.  The other batch-size regimes: test_sparse_polynomials_in_every_g1_schedule_regime."""
+    blobs, expected = sparse_expected
+    _, _, cells, proofs = _sparse_batch_matches_oracle(ctx, sparse_expected, 12)
     for b, blob in enumerate(blobs):
-        ec, ep = oracle.compute_cells_and_kzg_proofs(blob)
-        assert cells[b] == ec and proofs[b] == ep, f"polynomial {b} in the batch"
         c1, p1 = ctx.compute_cells_and_kzg_proofs(blob)
-        assert c1 == ec and p1 == ep, f"polynomial {b} alone"
-    # and in a batch that fills lane groups unevenly (70 = 64 + 6 lanes) next to random blobs
+        assert (c1, p1) == expected[b], f"polynomial {b} alone"
     rnd = _random_blobs(58, 4242)
     mixed = blobs + [rnd[i].tobytes() for i in range(58)]
     st, cells2, proofs2 = ctx.compute_cells_and_kzg_proofs_batch(mixed)
     assert st == [0] * 70 and cells2[:12] == cells and proofs2[:12] == proofs
+
+
+# 2: flat MSM + circulant transforms; 24: pair forms, the 712-multiplication compilation; 48: pair forms, the 456-multiplication
+# compilation in two waves; 150, 300, 350: three, five and six 64-lane groups
+@pytest.mark.parametrize("n", [2, 24, 48, 150, 300, 350])
+def test_sparse_polynomials_in_every_g1_schedule_regime(ctx, oracle, sparse_expected, n):
+    """The 12 sparse polynomials in the G1 schedule regimes on both sides of the 12-blob batch, placed on even and odd lanes of a
+    pair, at wave edges and across lane-group boundaries, their neighbours random blobs: the sparse blobs must give the oracle's
+    bytes, the random neighbours the single-blob path's."""
+    r = _sparse_batch_matches_oracle(ctx, sparse_expected, n)
+    if r is None:
+        return
+    batch, pos, cells, proofs = r
+    for q in sorted({pos[1] + 1, pos[-1] - 1, pos[6] - 1} - set(pos)):
+        c1, p1 = ctx.compute_cells_and_kzg_proofs(batch[q])
+        assert cells[q] == c1 and proofs[q] == p1, f"random blob at position {q} of {n}"
 
 
 def test_degenerate_blobs_inside_a_batch_that_fills_the_chip(ctx, oracle):
