@@ -491,9 +491,15 @@ void Engine::init_constants() {
 static linmap::Strategy slp_strategy(int id) {
     linmap::Strategy s;
     s.allow_toom8 = true;
+    {   // phi = [lambda] with the lambda the constants are GLV-recoded with: the device's beta was picked to match it (init_srs)
+        Fr lam = zero<FrParams>();
+        for (int i = 0; i < 4; i++) lam.v[i] = (uint32_t)(GLV_LAMBDA >> (32 * i));
+        s.lambda = to_mont(lam);
+    }
     auto fixed = [&](int k4, int k8, int k16, int k32) {
         s.tuned = false;
         s.balanced_lincomb = true;
+        s.phi = false;  // the real Toom-Cook points these depth-optimised programs were measured with
         s.hankel_split = {{2, 2}, {4, k4}, {8, k8}, {16, k16}, {32, k32}};
     };
     // (tools/linmap_explore.cpp lists every assignment of splits with its multiplication count and the latency of its cheap
@@ -503,7 +509,7 @@ static linmap::Strategy slp_strategy(int id) {
         case 3: fixed(4, 2, 4, 2); break;  // 456 multiplications, 18 levels, at most two doublings in front of an addition
         case 4: fixed(2, 2, 2, 4); break;  // 606 multiplications, 15 levels
         case 5: fixed(4, 2, 4, 8); break;  // 372 multiplications, 19 levels (8-way split of the 32-point products only)
-        default: break;                    // tuned by operation count: 350 multiplications
+        default: break;                    // tuned by operation count, Toom-Cook points on mu_6: 298 multiplications (16-way splits)
     }
     return s;
 }
@@ -584,6 +590,9 @@ const Engine::SlpProgram& Engine::slp_program(int id) {
 //   456            1.92  1.98  2.14  3.28  3.38  4.60  4.81  5.85  6.07  8.59  10.9
 //   606            1.78  1.85  3.08  3.20  4.43  4.56  5.83        7.16
 //   372            2.21  2.22  2.35  3.54  3.61  3.72  4.96  4.95  5.16  7.64  9.05  13.4
+// The tuned program is now the one on the mu_6 points (298 multiplications, 19 cheap launches; 2048 blobs: 14.73 -> 13.41 ms,
+// profiles/r7_phi/).  Programs 2-5 and these thresholds are unchanged; with phi their point sets would lose their doublings too
+// (tools/linmap_explore.cpp, phi = 1), which is not yet measured.
 int Engine::pick_slp_program(int lanes) const {
     if (slp_force_ >= 0) return slp_force_;
     const int groups = lanes / 64, simds = wave_slots_ / 2;

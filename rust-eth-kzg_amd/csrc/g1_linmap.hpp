@@ -41,16 +41,32 @@ namespace linmap {
 enum OpKind : uint8_t { OP_ADD = 0, OP_SUB = 1, OP_DBL = 2, OP_MULC = 3 };
 struct Op {
     OpKind kind;
-    int dst;  // value id (SSA)
-    int a;    // first operand (value id)
-    int b;    // ADD/SUB: second operand; DBL: number of doublings; MULC: constant id
+    int dst;      // value id (SSA)
+    int a;        // first operand (value id)
+    int b;        // ADD/SUB: second operand; DBL: number of doublings; MULC: constant id
+    int rot = 0;  // ADD/SUB: the second operand enters as phi^rot(b) (phi = [lambda], the curve's endomorphism of order 3)
 };
-// a signed reference to a value: (id, negative?).  id < 0: the identity (a term that is absent)
+// a reference to a value: +-phi^rot(v), (id, negative?, rot).  id < 0: the identity (a term that is absent).  phi(X : Y : Z) =
+// (beta X : Y : Z) = [lambda] P costs one product in Fp, so a rotation is an operand modifier like the sign, never an op of its own.
 struct Ref {
     int id = -1;
     bool neg = false;
+    int rot = 0;
     bool zero() const { return id < 0; }
 };
+
+// lambda of the GLV endomorphism, a primitive cube root of unity in Fr: phi(P) = [lambda] P on G1 (the value the engine recodes
+// its constants with), Montgomery form
+inline Fr glv_lambda() {
+    static const uint32_t w[8] = {0xffffffffu, 0x00000000u, 0x0001a402u, 0xac45a401u, 0, 0, 0, 0};
+    Fr a = zero<FrParams>();
+    for (int i = 0; i < 8; i++) a.v[i] = w[i];
+    return to_mont(a);
+}
+inline Fr lambda_pow(const Fr& lambda, int rot) {
+    rot = ((rot % 3) + 3) % 3;
+    return rot == 0 ? one<FrParams>() : rot == 1 ? lambda : sqr(lambda);
+}
 
 struct Plan {
     int n_in = 0;
@@ -58,6 +74,7 @@ struct Plan {
     std::vector<Op> ops;        // in dependency order
     std::vector<Ref> outputs;   // one per output
     std::vector<Fr> consts;     // MULC constants, Montgomery form
+    Fr lambda = glv_lambda();   // phi = [lambda] (Montgomery form)
     long count(OpKind k) const {
         long n = 0;
         for (auto& o : ops) n += o.kind == k;
@@ -68,10 +85,18 @@ struct Plan {
         for (auto& o : ops) n += o.kind == OP_DBL ? o.b : 0;
         return n;
     }
+    long rotations() const {  // operands that enter through phi or phi^2
+        long n = 0;
+        for (auto& o : ops) n += (o.kind == OP_ADD || o.kind == OP_SUB) && o.rot != 0;
+        return n;
+    }
 };
 
-// relative costs in VALU instructions (measured shapes of k_g1fft.hip / curve29.hpp)
-constexpr double COST_MULC = 690e3, COST_ADD = 8.3e3, COST_DBL = 3.1e3;
+// relative costs in VALU instructions of the signed 13 x 30-bit kernels (k_g1slp.hip, g1_mulc30.hpp, curve30.hpp).  A constant
+// multiplication: SQ_INSTS_VALU of k_slp_mulc_s, 6.313e9 x 64 lanes / (2048 blobs x 350) = 564 k.  The cheap operations from their
+// multiply-add counts at the same 1.37 instructions per multiply-add as that kernel (564 k / 413 k): a general addition 16 products
+// of ~318 multiply-adds, a halved doubling 2,054 multiply-adds, phi one product (351).
+constexpr double COST_MULC = 564e3, COST_ADD = 7.0e3, COST_DBL = 2.8e3, COST_PHI = 0.48e3;
 
 inline Fr fr_small(int64_t v) {
     Fr a = zero<FrParams>();
@@ -84,43 +109,50 @@ inline Fr fr_small(int64_t v) {
 
 class Builder {
 public:
-    explicit Builder(int n_in) {
+    explicit Builder(int n_in, const Fr& lambda = glv_lambda()) {
         plan_.n_in = n_in;
         plan_.n_values = n_in;
+        plan_.lambda = lambda;
     }
-    Ref input(int i) const { return Ref{i, false}; }
-    static Ref negate(Ref r) { return r.zero() ? r : Ref{r.id, !r.neg}; }
+    Ref input(int i) const { return Ref{i, false, 0}; }
+    static Ref negate(Ref r) { return r.zero() ? r : Ref{r.id, !r.neg, r.rot}; }
+    static Ref rotate(Ref r, int t) { return r.zero() ? r : Ref{r.id, r.neg, (((r.rot + t) % 3) + 3) % 3}; }
 
+    // +-phi^ra(a) +- phi^rb(b) = phi^ra(+-a +- phi^(rb - ra)(b)): the operation carries the relative rotation, the result the rest
     Ref add(Ref a, Ref b) {
         if (a.zero()) return b;
         if (b.zero()) return a;
-        if (a.id == b.id) return a.neg == b.neg ? dbl(a, 1) : Ref{};
-        if (!a.neg && !b.neg) return Ref{emit2(OP_ADD, a.id, b.id, true), false};
-        if (a.neg && b.neg) return Ref{emit2(OP_ADD, a.id, b.id, true), true};
-        if (!a.neg) return Ref{emit2(OP_SUB, a.id, b.id, false), false};  // a - b
-        return Ref{emit2(OP_SUB, b.id, a.id, false), false};              // b - a
+        if (a.id == b.id) {
+            if (a.rot == b.rot) return a.neg == b.neg ? dbl(a, 1) : Ref{};
+            if (a.neg == b.neg) return Ref{a.id, !a.neg, 3 - a.rot - b.rot};  // 1 + lambda + lambda^2 = 0
+        }
+        if (a.neg && !b.neg) std::swap(a, b);  // b - a
+        const int r = (b.rot - a.rot + 3) % 3;
+        if (a.neg == b.neg) return Ref{emit2(OP_ADD, a.id, b.id, true, r), a.neg, a.rot};
+        return Ref{emit2(OP_SUB, a.id, b.id, false, r), false, a.rot};  // a - b
     }
     Ref sub(Ref a, Ref b) { return add(a, negate(b)); }
     Ref dbl(Ref a, int t) {
         if (a.zero() || t == 0) return a;
         // fold chains: 2^t (2^s v) = 2^(t+s) v only if the inner value has no other use -- keep it simple, no folding
-        auto key = std::make_tuple((int)OP_DBL, a.id, t);
+        auto key = std::make_tuple((int)OP_DBL, a.id, t, 0);
         auto it = memo_.find(key);
-        if (it != memo_.end()) return Ref{it->second, a.neg};
+        if (it != memo_.end()) return Ref{it->second, a.neg, a.rot};
         int id = plan_.n_values++;
         plan_.ops.push_back(Op{OP_DBL, id, a.id, t});
         memo_[key] = id;
-        return Ref{id, a.neg};
+        return Ref{id, a.neg, a.rot};  // doubling commutes with phi
     }
-    Ref mulc(Ref a, const Fr& c) {  // c in Montgomery form
+    Ref mulc(Ref a, Fr c) {  // c in Montgomery form; a rotation of the operand goes into the constant
         if (a.zero() || is_zero(c)) return Ref{};
-        if (eq(c, one<FrParams>())) return a;
-        if (eq(c, neg(one<FrParams>()))) return negate(a);
+        c = mul(c, lambda_pow(plan_.lambda, a.rot));
+        if (eq(c, one<FrParams>())) return Ref{a.id, a.neg, 0};
+        if (eq(c, neg(one<FrParams>()))) return Ref{a.id, !a.neg, 0};
         int cid = (int)plan_.consts.size();
         plan_.consts.push_back(c);
         int id = plan_.n_values++;
         plan_.ops.push_back(Op{OP_MULC, id, a.id, cid});
-        return Ref{id, a.neg};
+        return Ref{id, a.neg, 0};
     }
     // sum_i coef_i * x_i with small integer coefficients: bit planes from the top, doublings merged
     Ref lincomb(const std::vector<std::pair<Ref, int64_t>>& terms) {
@@ -179,26 +211,35 @@ public:
         return std::move(plan_);
     }
     const Plan& plan() const { return plan_; }
-    double cost() const { return plan_.count(OP_MULC) * COST_MULC + (plan_.count(OP_ADD) + plan_.count(OP_SUB)) * COST_ADD + plan_.doublings() * COST_DBL; }
+    double cost() const { return plan_cost(plan_); }
+    static double plan_cost(const Plan& p) {
+        return p.count(OP_MULC) * COST_MULC + (p.count(OP_ADD) + p.count(OP_SUB)) * COST_ADD + p.doublings() * COST_DBL + p.rotations() * COST_PHI;
+    }
 
 private:
-    int emit2(OpKind k, int a, int b, bool commutative) {
-        if (commutative && a > b) std::swap(a, b);
-        auto key = std::make_tuple((int)k, a, b);
+    int emit2(OpKind k, int a, int b, bool commutative, int rot) {
+        if (commutative && rot == 0 && a > b) std::swap(a, b);
+        auto key = std::make_tuple((int)k, a, b, rot);
         auto it = memo_.find(key);
         if (it != memo_.end()) return it->second;
         int id = plan_.n_values++;
-        plan_.ops.push_back(Op{k, id, a, b});
+        plan_.ops.push_back(Op{k, id, a, b, rot});
         memo_[key] = id;
         return id;
     }
     Plan plan_;
-    std::map<std::tuple<int, int, int>, int> memo_;
+    std::map<std::tuple<int, int, int, int>, int> memo_;
 };
 
 // ---------------------------------------------------------------------------------------------------------------
-// Toom-Cook evaluation points for a k-way split, projective (a : b): E[r][J] = a^J b^(k-1-J).
-struct EvalPoint { int a, b; };
+// Toom-Cook evaluation points for a k-way split, projective (a zeta : b) with zeta = (-1)^zneg lambda^zr a sixth root of unity:
+// E[r][J] = a^J b^(k-1-J) zeta^J.  The factor zeta^J costs a sign and phi^(zr J), so the six points c mu_6 cost the doublings of
+// ONE point (see Compiler::hankel).
+struct EvalPoint {
+    int a, b;
+    int zr = 0;
+    bool zneg = false;
+};
 inline std::vector<EvalPoint> toom_points(int k) {
     switch (k) {
         case 2: return {{0, 1}, {1, 0}, {1, 1}};
@@ -208,19 +249,38 @@ inline std::vector<EvalPoint> toom_points(int k) {
         default: throw std::runtime_error("toom_points: unsupported split");
     }
 }
+// the same splits with the sixth roots of unity: 0, infinity, then whole classes c mu_6 for c = 1, 2, 1/2, 4, 1/4 as far as needed
+// (the last one partial).  Coefficients up to 2^7 for 8 ways instead of 8^7, and a 16-way split (31 points) within 4^15.
+inline std::vector<EvalPoint> toom_points_phi(int k) {
+    if (k == 2) return toom_points(2);
+    const int R = 2 * k - 1;
+    std::vector<EvalPoint> p = {{0, 1}, {1, 0}};
+    const int cls[][2] = {{1, 1}, {2, 1}, {1, 2}, {4, 1}, {1, 4}};
+    for (auto& c : cls)
+        for (int zr = 0; zr < 3; zr++)
+            for (int zn = 0; zn < 2; zn++)
+                if ((int)p.size() < R) p.push_back(EvalPoint{c[0], c[1], zr, zn != 0});
+    if ((int)p.size() != R) throw std::runtime_error("toom_points_phi: unsupported split");
+    return p;
+}
 inline int64_t ipow(int64_t b, int e) {
     int64_t r = 1;
     while (e-- > 0) r *= b;
     return r;
 }
-// U = (E2^T)^-1 with E2[r][s] = a^s b^(2k-2-s), r, s < 2k-1: U[r][D] multiplies Hankel block D for evaluation point r
-inline std::vector<std::vector<Fr>> toom_fixed_side(int k) {
-    const auto pts = toom_points(k);
+// E[r][J] of a point for a sum of degree deg, over Fr: a^J b^(deg-J) zeta^J
+inline Fr point_coef(const EvalPoint& p, int J, int deg, const Fr& lambda) {
+    Fr c = mul(fr_small(ipow(p.a, J) * ipow(p.b, deg - J)), lambda_pow(lambda, p.zr * J));
+    return (p.zneg && (J & 1)) ? neg(c) : c;
+}
+// U = (E2^T)^-1 with E2[r][s] = a^s b^(2k-2-s) zeta^s, r, s < 2k-1: U[r][D] multiplies Hankel block D for evaluation point r
+inline std::vector<std::vector<Fr>> toom_fixed_side(int k, bool phi = false, const Fr& lambda = glv_lambda()) {
+    const auto pts = phi ? toom_points_phi(k) : toom_points(k);
     const int R = 2 * k - 1;
     // solve E2^T U = I  <=>  for each column D of U: E2^T u = e_D.  Gauss-Jordan on [E2^T | I].
     std::vector<std::vector<Fr>> M(R, std::vector<Fr>(2 * R, zero<FrParams>()));
     for (int s = 0; s < R; s++) {
-        for (int r = 0; r < R; r++) M[s][r] = fr_small(ipow(pts[r].a, s) * ipow(pts[r].b, 2 * k - 2 - s));
+        for (int r = 0; r < R; r++) M[s][r] = point_coef(pts[r], s, 2 * k - 2, lambda);
         M[s][R + s] = one<FrParams>();
     }
     for (int col = 0; col < R; col++) {
@@ -252,6 +312,8 @@ public:
     std::map<int, bool> root_split;
     bool allow_toom8 = true;
     bool balanced_lincomb = false;  // evaluation / interpolation sums as balanced trees (Builder::lincomb_balanced)
+    bool phi = false;               // evaluation points on mu_6 (toom_points_phi) and 16-way splits; lambda: phi = [lambda]
+    Fr lambda = glv_lambda();
     Ref sum(Builder& B, const std::vector<std::pair<Ref, int64_t>>& t) const { return balanced_lincomb ? B.lincomb_balanced(t) : B.lincomb(t); }
 
     // y_i = sum_j h[i + j] x[j],  i, j < n;  h has 2n - 1 entries
@@ -261,6 +323,7 @@ public:
         if (n == 1) return {B.mulc(x[0], h[0])};
         const int k = hankel_split.count(n) ? hankel_split[n] : 2;
         if (n % k) throw std::runtime_error("hankel: split does not divide the size");
+        if (phi && k > 2) return hankel_mu6(B, x, h, k);
         const int m = n / k, R = 2 * k - 1;
         const auto pts = toom_points(k);
         const auto& U = fixed_side(k);
@@ -313,6 +376,83 @@ public:
                     if (partner[r] < 0) t.emplace_back(Z[r][i], coef);
                     else t.emplace_back((I & 1) ? Dm[r] : S[r], coef);
                 }
+                y[I * m + i] = sum(B, t);
+            }
+        }
+        return y;
+    }
+
+    // The same product on the points of toom_points_phi: the points come in classes c zeta, zeta = (-1)^e lambda^q in mu_6, and
+    // a class shares its work through a 6-point DFT that needs only additions, signs and phi:
+    //   evaluation     X(c zeta) = sum_s zeta^s A_s,   A_s = sum_{J = s mod 6} c^J x_J  (one small-integer sum per residue)
+    //                  = E_q + (-1)^e O_q,  E_q = A_0 + phi^2q A_2 + phi^q A_4,  O_q = phi^q A_1 + A_3 + phi^2q A_5
+    //   interpolation  y_I = sum_classes c^I W_(I mod 6),  W_s = sum_zeta zeta^s Z_zeta = sum_q phi^(q s) (Z_+q +- Z_-q)
+    // so the doublings of a class are those of one point (projective c = (a : b): a^J b^(k-1-J)).
+    std::vector<Ref> hankel_mu6(Builder& B, const std::vector<Ref>& x, const std::vector<Fr>& h, int k) {
+        const int n = (int)x.size(), m = n / k, R = 2 * k - 1;
+        const auto pts = toom_points_phi(k);
+        const auto& U = fixed_side(k);
+        struct Cls {
+            int a, b;
+            int member[3][2];  // point index of zeta = (-1)^e lambda^q, or -1
+        };
+        std::vector<Cls> cls;
+        for (int r = 0; r < R; r++) {
+            size_t c = 0;
+            while (c < cls.size() && !(cls[c].a == pts[r].a && cls[c].b == pts[r].b)) c++;
+            if (c == cls.size()) {
+                Cls nc{pts[r].a, pts[r].b, {{-1, -1}, {-1, -1}, {-1, -1}}};
+                cls.push_back(nc);
+            }
+            cls[c].member[pts[r].zr][pts[r].zneg ? 1 : 0] = r;
+        }
+        auto cf = [&](const Cls& c, int J) { return ipow(c.a, J) * ipow(c.b, k - 1 - J); };
+        std::vector<std::vector<Ref>> X(R, std::vector<Ref>(m));
+        for (auto& c : cls)
+            for (int i = 0; i < m; i++) {
+                Ref A[6];
+                for (int s = 0; s < 6 && s < k; s++) {
+                    std::vector<std::pair<Ref, int64_t>> t;
+                    for (int J = s; J < k; J += 6) t.emplace_back(x[J * m + i], cf(c, J));
+                    A[s] = sum(B, t);
+                }
+                for (int q = 0; q < 3; q++) {
+                    if (c.member[q][0] < 0 && c.member[q][1] < 0) continue;
+                    const Ref E = B.add(B.add(A[0], B.rotate(A[2], 2 * q)), B.rotate(A[4], q));
+                    const Ref O = B.add(B.add(B.rotate(A[1], q), A[3]), B.rotate(A[5], 2 * q));
+                    if (c.member[q][0] >= 0) X[c.member[q][0]][i] = B.add(E, O);
+                    if (c.member[q][1] >= 0) X[c.member[q][1]][i] = B.sub(E, O);
+                }
+            }
+        std::vector<std::vector<Ref>> Z(R);
+        for (int r = 0; r < R; r++) {
+            std::vector<Fr> hr(2 * m - 1, zero<FrParams>());
+            for (int D = 0; D < R; D++) {
+                if (is_zero(U[r][D])) continue;
+                for (int s = 0; s < 2 * m - 1; s++) hr[s] = add(hr[s], mul(U[r][D], h[D * m + s]));
+            }
+            Z[r] = hankel(B, X[r], hr);
+        }
+        std::vector<Ref> y(n);
+        for (int i = 0; i < m; i++) {
+            std::vector<std::vector<Ref>> W(cls.size(), std::vector<Ref>(6));
+            for (size_t ci = 0; ci < cls.size(); ci++) {
+                const Cls& c = cls[ci];
+                Ref S[3], D[3];
+                for (int q = 0; q < 3; q++) {
+                    const Ref zp = c.member[q][0] >= 0 ? Z[c.member[q][0]][i] : Ref{};
+                    const Ref zm = c.member[q][1] >= 0 ? Z[c.member[q][1]][i] : Ref{};
+                    S[q] = B.add(zp, zm);
+                    D[q] = B.sub(zp, zm);
+                }
+                for (int s = 0; s < 6 && s < k; s++) {
+                    const Ref* v = (s & 1) ? D : S;
+                    W[ci][s] = B.add(B.add(v[0], B.rotate(v[1], s)), B.rotate(v[2], 2 * s));
+                }
+            }
+            for (int I = 0; I < k; I++) {
+                std::vector<std::pair<Ref, int64_t>> t;
+                for (size_t ci = 0; ci < cls.size(); ci++) t.emplace_back(W[ci][I % 6], cf(cls[ci], I));
                 y[I * m + i] = sum(B, t);
             }
         }
@@ -397,10 +537,10 @@ public:
         for (int n = 2; n <= max_n; n *= 2) {
             double best = 0;
             int best_k = 0;
-            for (int k : {2, 4, 8}) {
-                if (n % k || (k == 8 && !allow_toom8)) continue;
+            for (int k : {2, 4, 8, 16}) {
+                if (n % k || (k == 8 && !allow_toom8) || (k == 16 && !phi)) continue;
                 hankel_split[n] = k;
-                Builder B(n);
+                Builder B(n, lambda);
                 std::vector<Ref> x(n);
                 for (int i = 0; i < n; i++) x[i] = B.input(i);
                 std::vector<Fr> h(2 * n - 1);
@@ -413,7 +553,7 @@ public:
             double cost[2];
             for (int split = 0; split < 2; split++) {
                 root_split[n] = split != 0;
-                Builder B(n);
+                Builder B(n, lambda);
                 std::vector<Ref> x(n);
                 for (int i = 0; i < n; i++) x[i] = B.input(i);
                 std::vector<Fr> c(n);
@@ -429,7 +569,7 @@ public:
 private:
     const std::vector<std::vector<Fr>>& fixed_side(int k) {
         auto it = fixed_.find(k);
-        if (it == fixed_.end()) it = fixed_.emplace(k, toom_fixed_side(k)).first;
+        if (it == fixed_.end()) it = fixed_.emplace(k, toom_fixed_side(k, phi && k > 2, lambda)).first;
         return it->second;
     }
     std::map<int, std::vector<std::vector<Fr>>> fixed_;
@@ -439,10 +579,11 @@ private:
 inline std::vector<Fr> run_over_fr(const Plan& p, const std::vector<Fr>& in) {
     std::vector<Fr> v(p.n_values, zero<FrParams>());
     for (int i = 0; i < p.n_in; i++) v[i] = in[i];
+    const Fr lp[3] = {one<FrParams>(), p.lambda, sqr(p.lambda)};
     for (auto& o : p.ops) {
         switch (o.kind) {
-            case OP_ADD: v[o.dst] = add(v[o.a], v[o.b]); break;
-            case OP_SUB: v[o.dst] = sub(v[o.a], v[o.b]); break;
+            case OP_ADD: v[o.dst] = add(v[o.a], mul(v[o.b], lp[o.rot])); break;
+            case OP_SUB: v[o.dst] = sub(v[o.a], mul(v[o.b], lp[o.rot])); break;
             case OP_DBL: { Fr t = v[o.a]; for (int k = 0; k < o.b; k++) t = add(t, t); v[o.dst] = t; break; }
             case OP_MULC: v[o.dst] = mul(v[o.a], p.consts[o.b]); break;
         }
@@ -450,7 +591,8 @@ inline std::vector<Fr> run_over_fr(const Plan& p, const std::vector<Fr>& in) {
     std::vector<Fr> out(p.outputs.size());
     for (size_t i = 0; i < out.size(); i++) {
         const Ref r = p.outputs[i];
-        out[i] = r.zero() ? zero<FrParams>() : (r.neg ? neg(v[r.id]) : v[r.id]);
+        const Fr t = r.zero() ? zero<FrParams>() : mul(v[r.id], lp[r.rot]);
+        out[i] = r.neg ? neg(t) : t;
     }
     return out;
 }
@@ -463,6 +605,8 @@ struct Strategy {
     std::map<int, int> hankel_split;
     std::map<int, bool> root_split;
     bool balanced_lincomb = false;
+    bool phi = true;            // Toom-Cook points on mu_6 and 16-way splits (Compiler::hankel_mu6)
+    Fr lambda = glv_lambda();   // phi = [lambda] on G1: the lambda the device's beta belongs to
 };
 // The FK20 map: in[j] = y_j / 2 (Fourier index j < 128, natural order), out[k] = proof at FFT index k (natural order).
 // w128[e] = omega_128^e in Montgomery form, e < 128.
@@ -473,12 +617,16 @@ inline Plan build_fk20_proofs_plan(const std::vector<Fr>& w128, const Strategy& 
             if (eq(z, w128[e])) { s = w128[e / 2]; return true; }
         return false;
     };
+    if (strat.phi && !is_zero(add(add(sqr(strat.lambda), strat.lambda), one<FrParams>())))
+        throw std::runtime_error("fk20 plan: lambda is not a primitive cube root of unity");
     Compiler C;
     C.allow_toom8 = strat.allow_toom8;
     C.balanced_lincomb = strat.balanced_lincomb;
+    C.phi = strat.phi;
+    C.lambda = strat.lambda;
     if (strat.tuned) C.tune(32);
     else { C.hankel_split = strat.hankel_split; C.root_split = strat.root_split; }
-    Builder B(128);
+    Builder B(128, strat.lambda);
     const Fr one_ = one<FrParams>(), inv32 = inv(fr_small(32));
     auto m_of = [&](int e) {  // (1/32) / (1 - w^e), e odd
         return mul(inv32, inv(sub(one_, w128[((e % 128) + 128) % 128])));
@@ -496,15 +644,15 @@ inline Plan build_fk20_proofs_plan(const std::vector<Fr>& w128, const Strategy& 
     }
     // outputs must be plain (positive) values produced by an operation, so that the executor can pin their slots
     for (auto& r : out)
-        if (r.zero() || r.neg || r.id < 128) throw std::runtime_error("fk20 plan: degenerate output");
+        if (r.zero() || r.neg || r.rot || r.id < 128) throw std::runtime_error("fk20 plan: degenerate output");
     Plan p = B.take(out);
     if (verbose) {
         fprintf(stderr, "[linmap] hankel splits:");
         for (auto& kv : C.hankel_split) fprintf(stderr, " %d->%d", kv.first, kv.second);
         fprintf(stderr, "  root splits:");
         for (auto& kv : C.root_split) fprintf(stderr, " %d:%d", kv.first, (int)kv.second);
-        fprintf(stderr, "\n[linmap] %ld constant multiplications, %ld additions, %ld doublings\n", p.count(OP_MULC),
-                p.count(OP_ADD) + p.count(OP_SUB), p.doublings());
+        fprintf(stderr, "\n[linmap] %ld constant multiplications, %ld additions, %ld doublings, %ld phi operands, cost %.1f M\n",
+                p.count(OP_MULC), p.count(OP_ADD) + p.count(OP_SUB), p.doublings(), p.rotations(), Builder::plan_cost(p) / 1e6);
     }
     return p;
 }
@@ -541,11 +689,12 @@ struct Launch {
 };
 struct Schedule {
     int n_slots = 0;             // arena slots; inputs occupy 0 .. n_in-1, outputs n_in .. n_in+n_out-1
-    std::vector<uint32_t> words;  // per operation: dst slot, a slot, b (slot | doublings | constant id), flags (1 = subtract, 2 = doubling run, 4 = a + b to dst and a - b to slot flags >> 16; bits 3-7: doublings of operand a first)
+    std::vector<uint32_t> words;  // per operation: dst slot, a slot, b (slot | doublings | constant id), flags (1 = subtract, 2 = doubling run, 4 = a + b to dst and a - b to slot flags >> 16; bits 3-7: doublings of operand a first; bits 8-9 / 10-11: operand a / b enters as phi^rot)
     std::vector<Launch> launches;
     long mulc_total = 0;
     long fused_pairs = 0;  // (a + b, a - b) pairs emitted as one operation
     long fused_runs = 0;   // doubling runs folded into the operation that consumes them
+    Fr lambda = glv_lambda();  // phi = [lambda]: what run_schedule_over_fr multiplies a rotated operand by
 };
 inline Schedule make_schedule(const Plan& p, bool fuse_add_sub = true, bool fuse_runs = true) {
     const int n_out = (int)p.outputs.size();
@@ -587,7 +736,9 @@ inline Schedule make_schedule(const Plan& p, bool fuse_add_sub = true, bool fuse
             if (u.size() == 1 && two(u[0]) && fits(p.ops[u[0]])) ok = true;
             if (fuse_add_sub && u.size() == 2 && two(u[0]) && two(u[1]) && p.ops[u[0]].kind != p.ops[u[1]].kind) {
                 const Op &x = p.ops[u[0]], &y = p.ops[u[1]];
-                if (std::min(x.a, x.b) == std::min(y.a, y.b) && std::max(x.a, x.b) == std::max(y.a, y.b) && fits(x) && fits(y)) ok = true;
+                if (std::min(x.a, x.b) == std::min(y.a, y.b) && std::max(x.a, x.b) == std::max(y.a, y.b) && x.rot == y.rot &&
+                    (x.rot == 0 || x.a == y.a) && fits(x) && fits(y))
+                    ok = true;
             }
             if (!ok) continue;
             run_of[o.dst] = o.b;
@@ -641,6 +792,7 @@ inline Schedule make_schedule(const Plan& p, bool fuse_add_sub = true, bool fuse
     }
     // slots: inputs and outputs pinned, temporaries from a free list; a slot freed at step s is reusable from step s+1
     Schedule S;
+    S.lambda = p.lambda;
     std::vector<int> slot(p.n_values, -1);
     for (int i = 0; i < p.n_in; i++) slot[i] = i;
     for (int k = 0; k < n_out; k++) {
@@ -664,15 +816,19 @@ inline Schedule make_schedule(const Plan& p, bool fuse_add_sub = true, bool fuse
         // and doubling runs together (they are independent of each other within a step; half as many small launches)
         // a + b and a - b of the same two values are ONE operation on the device (curve29.hpp: add_sub_* share all but the last
         // squaring and product pair): the subtraction carries the pair, the addition is dropped from the list
-        std::map<std::pair<int, int>, int> add_of;  // unordered operand pair -> index of the step's addition
+        // (operands: unordered without a rotation, a + phi^r b and a - phi^r b in that order with one)
+        auto pair_key = [&](const Op& o) {
+            return o.rot ? std::make_tuple(o.a, o.b, o.rot) : std::make_tuple(std::min(o.a, o.b), std::max(o.a, o.b), 0);
+        };
+        std::map<std::tuple<int, int, int>, int> add_of;  // operands -> index of the step's addition
         for (int i : step_ops[s])
-            if (p.ops[i].kind == OP_ADD) add_of[{std::min(p.ops[i].a, p.ops[i].b), std::max(p.ops[i].a, p.ops[i].b)}] = i;
+            if (p.ops[i].kind == OP_ADD) add_of[pair_key(p.ops[i])] = i;
         std::map<int, int> partner;  // subtraction -> its addition
         std::vector<char> fused_away(p.ops.size(), 0);
         if (fuse_add_sub)
             for (int i : step_ops[s]) {
                 if (p.ops[i].kind != OP_SUB) continue;
-                auto it = add_of.find({std::min(p.ops[i].a, p.ops[i].b), std::max(p.ops[i].a, p.ops[i].b)});
+                auto it = add_of.find(pair_key(p.ops[i]));
                 if (it == add_of.end() || fused_away[it->second]) continue;
                 partner[i] = it->second;
                 fused_away[it->second] = 1;
@@ -696,9 +852,9 @@ inline Schedule make_schedule(const Plan& p, bool fuse_add_sub = true, bool fuse
                 if ((pass == 0) != (o.kind == OP_MULC)) continue;
                 if (fused_away[i]) continue;
                 // an addition / subtraction with a folded run: that operand first, its doublings in bits 3-7 of the flags
-                int first = o.a, second = two ? o.b : 0;
-                if (two && run_of[o.b]) std::swap(first, second);  // additions only (see the folding rule above)
-                const uint32_t shifts = two ? (uint32_t)run_of[first] << 3 : 0u;
+                int first = o.a, second = two ? o.b : 0, rot_first = 0, rot_second = two ? o.rot : 0;
+                if (two && run_of[o.b]) { std::swap(first, second); std::swap(rot_first, rot_second); }  // additions only (see the folding rule above)
+                const uint32_t shifts = two ? ((uint32_t)run_of[first] << 3) | ((uint32_t)rot_first << 8) | ((uint32_t)rot_second << 10) : 0u;
                 if (two && run_of[first]) S.fused_runs++;
                 if (partner.count(i)) {  // words: slot of a + b, a, b, 4 | shifts | slot of a - b << 16
                     S.words.push_back((uint32_t)slot[p.ops[partner[i]].dst]);
@@ -728,6 +884,7 @@ inline Schedule make_schedule(const Plan& p, bool fuse_add_sub = true, bool fuse
 inline std::vector<Fr> run_schedule_over_fr(const Schedule& S, const std::vector<Fr>& consts, int n_in, int n_out, const std::vector<Fr>& in) {
     std::vector<Fr> arena(S.n_slots, zero<FrParams>());
     for (int i = 0; i < n_in; i++) arena[i] = in[i];
+    const Fr lp[4] = {one<FrParams>(), S.lambda, sqr(S.lambda), zero<FrParams>()};  // (rotation 3 is not a valid word)
     for (auto& L : S.launches) {
         std::vector<Fr> res(L.count), res2(L.count);
         for (int i = 0; i < L.count; i++) {
@@ -736,7 +893,7 @@ inline std::vector<Fr> run_schedule_over_fr(const Schedule& S, const std::vector
             if (L.kind == OP_MULC) res[i] = mul(a, consts[w[2]]);
             else if (w[3] & 2u) { Fr t = a; for (uint32_t k = 0; k < w[2]; k++) t = add(t, t); res[i] = t; }
             else {
-                Fr x = a, y = arena[w[2]];
+                Fr x = mul(a, lp[(w[3] >> 8) & 3u]), y = mul(arena[w[2]], lp[(w[3] >> 10) & 3u]);
                 for (uint32_t k = 0; k < ((w[3] >> 3) & 31u); k++) x = add(x, x);
                 if (w[3] & 4u) { res[i] = add(x, y); res2[i] = sub(x, y); }
                 else res[i] = (w[3] & 1u) ? sub(x, y) : add(x, y);

@@ -20,6 +20,20 @@ namespace kzg {
 
 static_assert(sizeof(JacS) == launch::SIZEOF_JACS && sizeof(JacQ) == launch::SIZEOF_JACQ, "the engine sizes and offsets the arena with these");
 
+// phi^rot of an operand of an addition (rot: bits 8-9 of the flags for the first operand, 10-11 for the second; wave-uniform):
+// phi(X : Y : Z) = (beta X : Y : Z) = [lambda] P, one product per application.  The program uses the sixth roots of unity as
+// Toom-Cook points (g1_linmap.hpp: Compiler::hankel_mu6); a constant multiplication's operand never carries a rotation (the host
+// folds it into the constant).
+__device__ __forceinline__ JacS slp_rotate(JacS p, uint32_t rot, const Fs<1, DC>& beta) {
+#pragma unroll 1
+    for (uint32_t k = 0; k < rot; k++) p = apply_phi(p, beta);
+    return p;
+}
+__device__ __forceinline__ JacQ slp_rotate(const JacQ& p, uint32_t rot, const Fs<1, DC>& beta) {
+    if (!rot) return p;
+    return jacq_from_jacs(slp_rotate(jacs_from_jacq(p), rot, beta));
+}
+
 // (a lane per blob on a 14 x 29-bit arena -- ETH_KZG_AMD_ARENA_SIGNED=0: the
 // multiplication runs in the signed 13 x 30-bit field, g1_mulc30.hpp; the point is converted on the way in and out)
 // n_active (every lane-per-blob kernel below): the blobs that are really there.  The lanes behind them (the batch is padded to a
@@ -81,20 +95,22 @@ __global__ __launch_bounds__(64, 2) void k_slp_mulc_coop2(JacQ* __restrict__ A, 
 // one cheap operation of the program on one lane: flags & 2: a run of b doublings; otherwise an addition (flags & 1: subtraction;
 // flags & 4: a + b to dst AND a - b to slot flags >> 16) whose FIRST operand is doubled (flags >> 3) & 31 times in registers
 // before the second one is read -- the schedule folds a doubling run into its only consumer (g1_linmap.hpp: make_schedule)
-__device__ __forceinline__ void slp_cheap_op(JacQ* __restrict__ A, int stride, int lane, uint32_t dst, uint32_t a, uint32_t b, uint32_t fl) {
-    JacQ r = A[(size_t)a * stride + lane];
+__device__ __forceinline__ void slp_cheap_op(JacQ* __restrict__ A, int stride, int lane, uint32_t dst, uint32_t a, uint32_t b, uint32_t fl,
+                                             const Fs<1, DC>& beta) {
+    const uint32_t rot_a = (fl & 2u) ? 0u : (fl >> 8) & 3u, rot_b = (fl & 2u) ? 0u : (fl >> 10) & 3u;
+    JacQ r = slp_rotate(A[(size_t)a * stride + lane], rot_a, beta);
     const uint32_t runs = (fl & 2u) ? b : (fl >> 3) & 31u;
 #pragma unroll 1
     for (uint32_t k = 0; k < runs; k++) r = dbl(r);
     bool degenerate = false;
     if (!(fl & 2u)) {
         if (fl & 4u) {  // the difference is stored before the sum is computed (curve29.hpp: add_sub_*)
-            const AddSubShared sh = add_sub_prepare(r, A[(size_t)b * stride + lane]);
+            const AddSubShared sh = add_sub_prepare(r, slp_rotate(A[(size_t)b * stride + lane], rot_b, beta));
             degenerate = sh.degenerate;  // (an identity, a = +-b: both results are redone below; what is stored here is overwritten)
             A[(size_t)(fl >> 16) * stride + lane] = add_sub_finish(sh, true);
             r = add_sub_finish(sh, false);
         } else {
-            r = add(r, A[(size_t)b * stride + lane], (fl & 1u) != 0);
+            r = add(r, slp_rotate(A[(size_t)b * stride + lane], rot_b, beta), (fl & 1u) != 0);
         }
     }
     A[(size_t)dst * stride + lane] = r;
@@ -102,10 +118,10 @@ __device__ __forceinline__ void slp_cheap_op(JacQ* __restrict__ A, int stride, i
     // path 33 spilled registers): the operands are read and doubled again.  Rare: all-zero / constant / two-valued blobs.
     if (degenerate) {
         asm volatile("" ::: "memory");
-        JacQ p2 = A[(size_t)a * stride + lane];
+        JacQ p2 = slp_rotate(A[(size_t)a * stride + lane], rot_a, beta);
 #pragma unroll 1
         for (uint32_t k = 0; k < runs; k++) p2 = dbl(p2);
-        const JacQ q2 = A[(size_t)b * stride + lane];
+        const JacQ q2 = slp_rotate(A[(size_t)b * stride + lane], rot_b, beta);
         const JacQ d = add_slow(p2, q2, true);
         A[(size_t)dst * stride + lane] = add_slow(p2, q2, false);
         A[(size_t)(fl >> 16) * stride + lane] = d;
@@ -114,39 +130,40 @@ __device__ __forceinline__ void slp_cheap_op(JacQ* __restrict__ A, int stride, i
 // additions, subtractions and runs of doublings of one step, one wave per operation.  Blocks are dealt in blockIdx order, x
 // fastest: x = lane group, y = operation, and the schedule lists a step's operations longest first (g1_linmap.hpp), so every
 // group's long operations start first and the launch ends on short ones.
-__global__ __launch_bounds__(64, 2) void k_slp_add(JacQ* __restrict__ A, int stride, const uint32_t* __restrict__ words, int n_active) {
+__global__ __launch_bounds__(64, 2) void k_slp_add(JacQ* __restrict__ A, int stride, const uint32_t* __restrict__ words, Fs<1, DC> beta, int n_active) {
     const uint32_t* w = words + (size_t)blockIdx.y * 4;
     const uint32_t dst = __builtin_amdgcn_readfirstlane(w[0]), a = __builtin_amdgcn_readfirstlane(w[1]),
                    b = __builtin_amdgcn_readfirstlane(w[2]), fl = __builtin_amdgcn_readfirstlane(w[3]);
     if ((int)(blockIdx.x * 64 + threadIdx.x) >= n_active) return;
-    slp_cheap_op(A, stride, blockIdx.x * 64 + threadIdx.x, dst, a, b, fl);
+    slp_cheap_op(A, stride, blockIdx.x * 64 + threadIdx.x, dst, a, b, fl, beta);
 }
 
 // The same operations on an arena in the signed 13 x 30-bit form (launch::FMT_JACS; curve30.hpp): add-1998-cmo-2 with the
 // subtractions fused into the reductions, the sum-and-difference pair with its shared part computed once (add_sub), doubling runs
 // in the halved form (dbl_half: (X / 4, Y / 8, Z / 2) is the same point).  Degenerate operands -- an identity, a = +-b -- leave by
 // add_slow inside add / add_sub (Z3 = Z1 Z2 H is a fresh product: zero iff its digits are).
-__global__ __launch_bounds__(64, 2) void k_slp_add_s(JacS* __restrict__ A, int stride, const uint32_t* __restrict__ words, int n_active) {
+__global__ __launch_bounds__(64, 2) void k_slp_add_s(JacS* __restrict__ A, int stride, const uint32_t* __restrict__ words, Fs<1, DC> beta, int n_active) {
     const uint32_t* w = words + (size_t)blockIdx.y * 4;
     const uint32_t dst = __builtin_amdgcn_readfirstlane(w[0]), a = __builtin_amdgcn_readfirstlane(w[1]),
                    b = __builtin_amdgcn_readfirstlane(w[2]), fl = __builtin_amdgcn_readfirstlane(w[3]);
     const int lane_of_thread = blockIdx.x * 64 + threadIdx.x;
     const bool keep = lane_of_thread < n_active;  // (padding lanes repeat the last blob's work and store nothing: see k_slp_mulc_s)
     const int lane = keep ? lane_of_thread : n_active - 1;
-    JacS r = A[(size_t)a * stride + lane];
+    const uint32_t rot_a = (fl & 2u) ? 0u : (fl >> 8) & 3u, rot_b = (fl & 2u) ? 0u : (fl >> 10) & 3u;
+    JacS r = slp_rotate(A[(size_t)a * stride + lane], rot_a, beta);
     const uint32_t runs = (fl & 2u) ? b : (fl >> 3) & 31u;
 #pragma unroll 1
     for (uint32_t k = 0; k < runs; k++) r = dbl_half(r);
     bool degenerate = false;
     if (!(fl & 2u)) {
         if (fl & 4u) {  // the difference is stored before the sum is computed
-            const AddSubSharedS sh = add_sub_prepare(r, A[(size_t)b * stride + lane]);
+            const AddSubSharedS sh = add_sub_prepare(r, slp_rotate(A[(size_t)b * stride + lane], rot_b, beta));
             degenerate = sh.degenerate;  // (an identity, a = +-b: both results are redone below; what is stored here is overwritten)
             const JacS df = add_sub_finish(sh, true);
             if (keep) A[(size_t)(fl >> 16) * stride + lane] = df;
             r = add_sub_finish(sh, false);
         } else {
-            r = add_unchecked(r, A[(size_t)b * stride + lane], (fl & 1u) != 0, degenerate);
+            r = add_unchecked(r, slp_rotate(A[(size_t)b * stride + lane], rot_b, beta), (fl & 1u) != 0, degenerate);
         }
     }
     if (keep) A[(size_t)dst * stride + lane] = r;
@@ -154,10 +171,10 @@ __global__ __launch_bounds__(64, 2) void k_slp_add_s(JacS* __restrict__ A, int s
     // them): the operands are read and doubled again.  Rare: all-zero / constant / two-valued / sparse blobs.
     if (degenerate && keep) {
         asm volatile("" ::: "memory");
-        JacS p2 = A[(size_t)a * stride + lane];
+        JacS p2 = slp_rotate(A[(size_t)a * stride + lane], rot_a, beta);
 #pragma unroll 1
         for (uint32_t k = 0; k < runs; k++) p2 = dbl_half(p2);
-        const JacS q2 = A[(size_t)b * stride + lane];
+        const JacS q2 = slp_rotate(A[(size_t)b * stride + lane], rot_b, beta);
         if (fl & 4u) {
             const JacS d = add_slow(p2, q2, true);
             A[(size_t)dst * stride + lane] = add_slow(p2, q2, false);
@@ -172,18 +189,19 @@ __global__ __launch_bounds__(64, 2) void k_slp_add_s(JacS* __restrict__ A, int s
 // (g1_coop.hpp): a level is then a few hundred waves on an idle chip, each a single addition -- 16.5 multiplication times for one
 // lane, 5.5 for a quad; a doubling run likewise 3.5 per doubling instead of 6.5.  The sum-and-difference pair is two
 // quad additions (11 against the shared form's 20).  16 blobs per wave; every lane of a quad stores the same result.
-__global__ __launch_bounds__(64, 2) void k_slp_add_coop(JacQ* __restrict__ A, int stride, const uint32_t* __restrict__ words, int lanes) {
+__global__ __launch_bounds__(64, 2) void k_slp_add_coop(JacQ* __restrict__ A, int stride, const uint32_t* __restrict__ words, Fs<1, DC> beta, int lanes) {
     const uint32_t* w = words + (size_t)blockIdx.y * 4;
     const uint32_t dst = __builtin_amdgcn_readfirstlane(w[0]), a = __builtin_amdgcn_readfirstlane(w[1]),
                    b = __builtin_amdgcn_readfirstlane(w[2]), fl = __builtin_amdgcn_readfirstlane(w[3]);
     const int lane = blockIdx.x * 16 + (threadIdx.x >> 2), quad = threadIdx.x & 3;
     if (lane >= lanes) return;
-    JacQ r = A[(size_t)a * stride + lane];
+    const uint32_t rot_a = (fl & 2u) ? 0u : (fl >> 8) & 3u, rot_b = (fl & 2u) ? 0u : (fl >> 10) & 3u;
+    JacQ r = slp_rotate(A[(size_t)a * stride + lane], rot_a, beta);
     const uint32_t runs = (fl & 2u) ? b : (fl >> 3) & 31u;
 #pragma unroll 1
     for (uint32_t k = 0; k < runs; k++) r = coop_dbl(r, quad);
     if (!(fl & 2u)) {
-        const JacQ q = A[(size_t)b * stride + lane];
+        const JacQ q = slp_rotate(A[(size_t)b * stride + lane], rot_b, beta);
         if (fl & 4u) {
             const JacQ d = coop_add(r, q, true, quad);
             A[(size_t)(fl >> 16) * stride + lane] = d;
@@ -213,19 +231,20 @@ __global__ __launch_bounds__(64, 2) void k_slp_mulc_coop_s(JacS* __restrict__ A,
 }
 // the cheap operations with four lanes per blob (k_slp_add_coop's schedule): a doubling run 3 reductions deep per doubling, an
 // addition 5, the sum-and-difference pair 4 levels + its two fused pairs.  Every lane of a quad stores the same result.
-__global__ __launch_bounds__(64, 2) void k_slp_add_coop_s(JacS* __restrict__ A, int stride, const uint32_t* __restrict__ words, int lanes) {
+__global__ __launch_bounds__(64, 2) void k_slp_add_coop_s(JacS* __restrict__ A, int stride, const uint32_t* __restrict__ words, Fs<1, DC> beta, int lanes) {
     const uint32_t* w = words + (size_t)blockIdx.y * 4;
     const uint32_t dst = __builtin_amdgcn_readfirstlane(w[0]), a = __builtin_amdgcn_readfirstlane(w[1]),
                    b = __builtin_amdgcn_readfirstlane(w[2]), fl = __builtin_amdgcn_readfirstlane(w[3]);
     const int lane_of_thread = blockIdx.x * 16 + (threadIdx.x >> 2), quad = threadIdx.x & 3;
     const bool keep = lane_of_thread < lanes;
     const int lane = keep ? lane_of_thread : lanes - 1;
-    JacS r = A[(size_t)a * stride + lane];
+    const uint32_t rot_a = (fl & 2u) ? 0u : (fl >> 8) & 3u, rot_b = (fl & 2u) ? 0u : (fl >> 10) & 3u;
+    JacS r = slp_rotate(A[(size_t)a * stride + lane], rot_a, beta);
     const uint32_t runs = (fl & 2u) ? b : (fl >> 3) & 31u;
 #pragma unroll 1
     for (uint32_t k = 0; k < runs; k++) r = coop4_dbl_half(r, quad);
     if (!(fl & 2u)) {
-        const JacS q = A[(size_t)b * stride + lane];
+        const JacS q = slp_rotate(A[(size_t)b * stride + lane], rot_b, beta);
         if (fl & 4u) {
             JacS d;
             coop4_add_sub(r, q, quad, r, d);
@@ -250,12 +269,12 @@ void g1_slp_launch(int kind, void* arena, int stride, const uint32_t* words, int
     if (lanes <= 0) lanes = stride;  // (a sub-range of the lanes: arena already points at its first lane, stride stays the arena's)
     if (n_active <= 0 || n_active > lanes) n_active = lanes;
     const dim3 grid((unsigned)count, (unsigned)(lanes / 64));
+    Fp b384;
+    for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
+    const Fs<1, DC> bs = fs_from_fp(b384);  // phi of a rotated operand (additions) and the constant multiplications' GLV halves
     if (fmt == FMT_JACS) {  // everything in the signed field (the engine's format unless ETH_KZG_AMD_ARENA_SIGNED=0)
         const bool coop = coop_points_max() > 0;
         if (kind == 3) {
-            Fp b384;
-            for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
-            const Fs<1, DC> bs = fs_from_fp(b384);
             // coop_lanes: the blobs that are really there when they are few enough for four lanes each (<= 16: one quad wave per
             // operation) or two (17 .. 64)
             if (coop_lanes > 16 && coop)
@@ -266,14 +285,12 @@ void g1_slp_launch(int kind, void* arena, int stride, const uint32_t* words, int
         } else {
             // one lane group and few enough operations for every quad wave to have a SIMD of its own: four lanes per blob
             if (lanes == 64 && count * 4 <= 1024 && coop)
-                k_slp_add_coop_s<<<dim3((unsigned)((n_active + 15) / 16), (unsigned)count), 64, 0, st>>>((JacS*)arena, stride, words, n_active);
-            else k_slp_add_s<<<dim3((unsigned)(lanes / 64), (unsigned)count), 64, 0, st>>>((JacS*)arena, stride, words, n_active);
+                k_slp_add_coop_s<<<dim3((unsigned)((n_active + 15) / 16), (unsigned)count), 64, 0, st>>>((JacS*)arena, stride, words, bs, n_active);
+            else k_slp_add_s<<<dim3((unsigned)(lanes / 64), (unsigned)count), 64, 0, st>>>((JacS*)arena, stride, words, bs, n_active);
         }
         return;
     }
     if (kind == 3) {
-        Fp b384;
-        for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
         // coop_lanes: the blobs that are really there when they are few enough for four lanes each (<= 16: one quad wave per operation)
         // or two (<= 32: still one wave per operation)
         if (coop_lanes > 16 && coop_points_max() > 0) {
@@ -283,12 +300,12 @@ void g1_slp_launch(int kind, void* arena, int stride, const uint32_t* words, int
         else if (coop_lanes > 0 && coop_points_max() > 0)
             k_slp_mulc_coop<<<dim3((unsigned)count, (unsigned)((coop_lanes + 15) / 16)), 64, 0, st>>>((JacQ*)arena, stride, words, (const uint32_t*)naf,
                                                                                                      fq_from_fp(b384), coop_lanes);
-        else k_slp_mulc<<<grid, 64, 0, st>>>((JacQ*)arena, stride, words, (const uint32_t*)naf, fs_from_fp(b384), n_active);
+        else k_slp_mulc<<<grid, 64, 0, st>>>((JacQ*)arena, stride, words, (const uint32_t*)naf, bs, n_active);
     } else {
         // one lane group and few enough operations for every quad wave to have a SIMD of its own: four lanes per blob
         if (lanes == 64 && count * 4 <= 1024 && coop_points_max() > 0)
-            k_slp_add_coop<<<dim3((unsigned)((n_active + 15) / 16), (unsigned)count), 64, 0, st>>>((JacQ*)arena, stride, words, n_active);
-        else k_slp_add<<<dim3((unsigned)(lanes / 64), (unsigned)count), 64, 0, st>>>((JacQ*)arena, stride, words, n_active);
+            k_slp_add_coop<<<dim3((unsigned)((n_active + 15) / 16), (unsigned)count), 64, 0, st>>>((JacQ*)arena, stride, words, bs, n_active);
+        else k_slp_add<<<dim3((unsigned)(lanes / 64), (unsigned)count), 64, 0, st>>>((JacQ*)arena, stride, words, bs, n_active);
     }
 }
 }  // namespace launch
