@@ -150,6 +150,48 @@ uint64_t eth_kzg_amd_context_devices(const DASContext *ctx, int32_t *out_ordinal
  * symbol's meaning changes or one is removed, so that an out-of-tree consumer can check at load time. */
 int eth_kzg_amd_abi_version(void);
 
+/* ---- a caller-supplied trusted setup ----
+ * Every other constructor builds the context on the mainnet ceremony file that is linked into the library.  Chains with a
+ * ceremony of their own, devnets and test suites (an insecure setup with a known secret) hand their points in here -- the
+ * reference's DASContext::new(&TrustedSetup, ..) with TrustedSetup::from_json / from_json_unchecked
+ * (crates/eip7594/src/lib.rs:81, crates/trusted_setup/src/lib.rs:88-124), c-kzg's load_trusted_setup.
+ *   g1_monomial   n_g1 = 4096 points [tau^i]_1, 48 bytes each, ZCash compressed (the JSON's "g1_monomial"; NOT "g1_lagrange")
+ *   g2_monomial   n_g2 = 65 points [tau^i]_2, 96 bytes each
+ *   flags         ETH_KZG_AMD_SETUP_*; 0 = what from_json does
+ *   device_ordinals / n_devices   a device list as for eth_kzg_amd_das_context_new_on_devices; NULL and 0: the devices
+ *                 eth_kzg_das_context_new would pick (ETH_KZG_AMD_DEVICES / ETH_KZG_AMD_DEVICE / GPU 0)
+ *   table_budget_gb   as eth_kzg_amd_das_context_try_new
+ * Never aborts: NULL and Err("ContextCreation(..)") otherwise.  The counts, the pointers and the flags are checked before a GPU is
+ * looked for ("InvalidInput: a trusted setup holds 4096 G1 and 65 G2 monomial points, got .."); other sizes are not supported.
+ * Validation of the points ("InvalidSetup: g1_monomial[2077] is not in the prime-order subgroup" -- the FIRST bad index is named):
+ *   - every point must be the canonical compressed encoding of a curve point; a point at infinity in g1_monomial is refused;
+ *   - every G1 point (on the GPU, endomorphism test) and every G2 point (on the host, psi-endomorphism test) must lie in the
+ *     subgroup of order r, unless ETH_KZG_AMD_SETUP_NO_SUBGROUP_CHECK (from_json_unchecked) is given.  Unchecked, g1_monomial[1]
+ *     must still be in the subgroup: the library calibrates its endomorphism on it;
+ *   - ETH_KZG_AMD_SETUP_CHECK_POWERS: g1_monomial[0] and g2_monomial[0] are the standard generators and both lists are
+ *     consecutive powers of one tau (two random-weight pairing checks; error 2^-128).  This is what catches a well-formed file
+ *     in the wrong basis or order -- Lagrange points passed as monomial ones pass every subgroup test and give wrong proofs.
+ *     Off by default (the reference has no such check); costs two 4096-point MSMs on the GPU and four pairings;
+ *   - a setup from which a base at infinity is derived is refused ("degenerate trusted setup"): an FK20 base, or the verification
+ *     base [tau^64 - h^64]_2 of a coset -- tau inside the evaluation domain (tau^8192 = 1; tau = 1 is the plain case), where
+ *     every proof for that coset's cell would verify.
+ * Everything else is as for the embedded setup: progressive start, table budget, use_precomp, device lists, serial lanes.  The
+ * window tables are shared between the contexts of a GPU that hold the SAME setup (equal eth_kzg_amd_setup_digest) and only
+ * those; the mainnet points handed in here give the same bytes as eth_kzg_das_context_new in every output and share its tables. */
+#define ETH_KZG_AMD_SETUP_NO_SUBGROUP_CHECK 1u
+#define ETH_KZG_AMD_SETUP_CHECK_POWERS 2u
+DASContext *eth_kzg_amd_das_context_new_with_setup(const uint8_t *g1_monomial, uint64_t n_g1, const uint8_t *g2_monomial,
+                                                   uint64_t n_g2, uint32_t flags, bool use_precomp,
+                                                   const int32_t *device_ordinals, uint64_t n_devices,
+                                                   double table_budget_gb, CResult *result);
+/* The same from ONE buffer in the flat layout of rust-eth-kzg_amd/data/trusted_setup_4096.bin:
+ * "KZGSRS01" | n_g1 (u32, little endian) | n_g2 (u32) | n_g1 * 48 bytes | n_g2 * 96 bytes.  Forwards to the constructor above. */
+DASContext *eth_kzg_amd_das_context_new_with_setup_file(const uint8_t *file, uint64_t file_length, uint32_t flags,
+                                                        bool use_precomp, const int32_t *device_ordinals,
+                                                        uint64_t n_devices, double table_budget_gb, CResult *result);
+/* Which setup a context holds: SHA-256 over the g1_monomial bytes followed by the g2_monomial bytes (32 bytes out). */
+void eth_kzg_amd_setup_digest(const DASContext *ctx, uint8_t *out_digest /* 32 */);
+
 /* Host-pointer batches: n blobs; out_cells[b] / out_proofs[b] are arrays of 128 pointers as in the
  * single-blob calls (either may be NULL to skip that output). */
 CResult eth_kzg_amd_compute_cells_and_kzg_proofs_batch(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs,

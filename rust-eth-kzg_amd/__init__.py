@@ -40,6 +40,11 @@ class CResult(C.Structure):
 
 # every symbol include/c_eth_kzg.h declares (tests assert the library exports all of them)
 VERIFY_PARTIAL_BYTES = 96
+# flags of eth_kzg_amd_das_context_new_with_setup
+SETUP_NO_SUBGROUP_CHECK = 1
+SETUP_CHECK_POWERS = 2
+SETUP_G1_POINTS = 4096
+SETUP_G2_POINTS = 65
 
 EXPORTED_SYMBOLS = [
     "eth_kzg_das_context_new", "eth_kzg_das_context_free", "eth_kzg_free_error_message",
@@ -50,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_verify_blob_kzg_proof", "eth_kzg_verify_blob_kzg_proof_batch",
     "eth_kzg_amd_das_context_new_on_device",
     "eth_kzg_amd_das_context_try_new", "eth_kzg_amd_das_context_new_on_devices", "eth_kzg_amd_context_devices",
+    "eth_kzg_amd_das_context_new_with_setup", "eth_kzg_amd_das_context_new_with_setup_file", "eth_kzg_amd_setup_digest",
     "eth_kzg_amd_abi_version", "eth_kzg_amd_window_count", "eth_kzg_amd_glv_table",
     "eth_kzg_amd_compute_cells_and_kzg_proofs_batch", "eth_kzg_amd_blob_to_kzg_commitment_batch",
     "eth_kzg_amd_recover_cells_and_proofs_batch", "eth_kzg_amd_recover_cells_and_proofs_device",
@@ -147,6 +153,13 @@ def load_library():
     lib.eth_kzg_amd_context_devices.restype = U64
     lib.eth_kzg_amd_context_devices.argtypes = [P, P, U64]
     lib.eth_kzg_amd_abi_version.restype = C.c_int
+    if hasattr(lib, "eth_kzg_amd_das_context_new_with_setup"):  # (an A/B build from before these symbols, via ETH_KZG_AMD_LIB, still loads; calling them there raises)
+        lib.eth_kzg_amd_das_context_new_with_setup.restype = P
+        lib.eth_kzg_amd_das_context_new_with_setup.argtypes = [P, U64, P, U64, C.c_uint32, C.c_bool, P, U64, C.c_double, C.POINTER(CResult)]
+        lib.eth_kzg_amd_das_context_new_with_setup_file.restype = P
+        lib.eth_kzg_amd_das_context_new_with_setup_file.argtypes = [P, U64, C.c_uint32, C.c_bool, P, U64, C.c_double, C.POINTER(CResult)]
+        lib.eth_kzg_amd_setup_digest.restype = None
+        lib.eth_kzg_amd_setup_digest.argtypes = [P, P]
     lib.eth_kzg_amd_window_count.argtypes = [P]
     lib.eth_kzg_amd_glv_table.argtypes = [P]
     # the stage-level test hooks exist in libc_eth_kzg_hooks.so only (what tests/ loads through ETH_KZG_AMD_LIB); the product
@@ -189,6 +202,37 @@ def present_masks(n, present):
         masks[2 * b] = m & 0xFFFFFFFFFFFFFFFF
         masks[2 * b + 1] = m >> 64
     return masks
+
+
+def parse_trusted_setup_json(text):
+    """The consensus-specs trusted-setup JSON -> (g1_monomial, g2_monomial) as lists of bytes (48 and 96 bytes each).
+    Every entry is a 0x-prefixed hex string; `g1_lagrange` is not needed and ignored, as in the reference
+    (crates/trusted_setup/src/lib.rs:111).  Raises KzgError on anything else; the point COUNTS are the constructor's business."""
+    import json
+    try:
+        doc = json.loads(text)
+    except ValueError as e:
+        raise KzgError(f"InvalidSetup: not JSON ({e})")
+    if not isinstance(doc, dict):
+        raise KzgError("InvalidSetup: the trusted setup JSON is an object with g1_monomial and g2_monomial")
+    out = []
+    for key, size in (("g1_monomial", 48), ("g2_monomial", 96)):
+        pts = doc.get(key)
+        if not isinstance(pts, list):
+            raise KzgError(f"InvalidSetup: {key} is missing")
+        dec = []
+        for i, h in enumerate(pts):
+            if not isinstance(h, str) or not h.startswith("0x"):
+                raise KzgError(f"InvalidSetup: {key}[{i}] is not a 0x-prefixed hex string")
+            try:
+                b = bytes.fromhex(h[2:])
+            except ValueError:
+                raise KzgError(f"InvalidSetup: {key}[{i}] is not hex")
+            if len(b) != size:
+                raise KzgError(f"InvalidSetup: {key}[{i}] has {len(b)} bytes, not {size}")
+            dec.append(b)
+        out.append(dec)
+    return out[0], out[1]
 
 
 def _ptr_array(bufs):
@@ -271,6 +315,64 @@ class DASContext:
             raise RuntimeError("eth_kzg_das_context_new returned NULL")
         if wait_tables:
             self.tables_ready(-1)
+
+    @classmethod
+    def from_trusted_setup(cls, g1_monomial, g2_monomial, *, subgroup_check=True, check_powers=False, use_precomp=True, devices=None,
+                           table_budget_gb=None, wait_tables=True):
+        """A context on the caller's trusted setup (eth_kzg_amd_das_context_new_with_setup; the reference's
+        DASContext::new(&TrustedSetup, ..)).  g1_monomial / g2_monomial: 4096 / 65 compressed points, each list a sequence of
+        48- / 96-byte strings or one flat bytes object.  subgroup_check=False is the reference's from_json_unchecked;
+        check_powers=True also proves that both lists are consecutive powers of one tau over the standard generators (catches
+        Lagrange points passed as monomial ones).  devices: a device list (None: what DASContext() picks).  Raises KzgError."""
+        def flat(pts, size):
+            if isinstance(pts, (bytes, bytearray, memoryview)):
+                raw = bytes(pts)
+                if len(raw) % size:
+                    raise KzgError(f"InvalidSetup: {len(raw)} bytes are not a whole number of {size}-byte points")
+                return raw, len(raw) // size
+            pts = [bytes(x) for x in pts]
+            for i, x in enumerate(pts):
+                if len(x) != size:
+                    raise KzgError(f"InvalidSetup: point {i} has {len(x)} bytes, not {size}")
+            return b"".join(pts), len(pts)
+        g1, n1 = flat(g1_monomial, 48)
+        g2, n2 = flat(g2_monomial, 96)
+        self = cls.__new__(cls)
+        self._lib = load_library()
+        self._ctx = C.c_void_p(None)
+        devs = np.array([int(d) for d in devices], dtype=np.int32) if devices is not None else None
+        self.device_index = int(devs[0]) if devs is not None and len(devs) else int(os.environ.get("ETH_KZG_AMD_DEVICE", "0"))
+        flags = (0 if subgroup_check else SETUP_NO_SUBGROUP_CHECK) | (SETUP_CHECK_POWERS if check_powers else 0)
+        res = CResult()
+        b1, b2 = C.create_string_buffer(g1, max(1, len(g1))), C.create_string_buffer(g2, max(1, len(g2)))
+        self._ctx = C.c_void_p(self._lib.eth_kzg_amd_das_context_new_with_setup(
+            C.addressof(b1), n1, C.addressof(b2), n2, flags, bool(use_precomp), _vp(devs) if devs is not None and len(devs) else None,
+            len(devs) if devs is not None else 0, float(table_budget_gb or 0.0), C.byref(res)))
+        if not self._ctx.value:
+            msg = C.cast(res.error_msg, C.c_char_p).value.decode() if res.error_msg else "unknown"
+            self._lib.eth_kzg_free_error_message(res.error_msg)
+            raise KzgError(msg)
+        if wait_tables:
+            self.tables_ready(-1)
+        return self
+
+    @classmethod
+    def from_trusted_setup_json(cls, text_or_path, *, check_powers=True, **kwargs):
+        """from_trusted_setup on the consensus-specs JSON (a JSON string, or the path of a file that holds one).  The structure
+        check is ON by default here: a JSON file is where a wrong basis comes from."""
+        text = text_or_path
+        if not str(text_or_path).lstrip().startswith("{"):
+            with open(text_or_path) as f:
+                text = f.read()
+        g1, g2 = parse_trusted_setup_json(text)
+        return cls.from_trusted_setup(g1, g2, check_powers=check_powers, **kwargs)
+
+    @property
+    def setup_digest(self):
+        """SHA-256 over the context's g1_monomial | g2_monomial bytes (eth_kzg_amd_setup_digest): which setup it holds."""
+        out = C.create_string_buffer(32)
+        self._lib.eth_kzg_amd_setup_digest(self._ctx, out)
+        return out.raw
 
     def devices(self):
         """The context's device list (eth_kzg_amd_context_devices)."""

@@ -88,7 +88,8 @@ void free_ctx(DASContext* c) {
 }
 // the one constructor: NULL + message when the context cannot be built (no usable GPU, not even the 3.7 GB start tables fit).
 // The engines of a device list are built side by side (a constructor is 0.1 - 2 s of set-up kernels and allocations per GPU).
-DASContext* try_make_ctx(bool use_precomp, const std::vector<int>& devices, double table_budget_gb, std::string* why) {
+DASContext* try_make_ctx(bool use_precomp, const std::vector<int>& devices, double table_budget_gb, std::string* why,
+                         const std::shared_ptr<const kzg::TrustedSetup>& setup = nullptr) {
     DASContext* c = nullptr;
     try {
         if (devices.empty() || devices.size() > 64) throw std::runtime_error("empty or oversized device list");
@@ -98,7 +99,7 @@ DASContext* try_make_ctx(bool use_precomp, const std::vector<int>& devices, doub
         std::vector<std::string> errs(D);
         auto make = [&](size_t d) {
             try {
-                c->engines[d] = new kzg::Engine(use_precomp, devices[d], nullptr, table_budget_gb);
+                c->engines[d] = new kzg::Engine(use_precomp, devices[d], nullptr, table_budget_gb, setup);
             } catch (const std::exception& e) {
                 errs[d] = e.what();
                 if (errs[d].empty()) errs[d] = "unknown failure";
@@ -185,6 +186,57 @@ DASContext* eth_kzg_amd_das_context_new_on_devices(bool use_precomp, const int32
     if (result) *result = c ? ok() : err("ContextCreation(" + why + ")");
     return c;
 }
+// A caller-supplied trusted setup.  Order of the checks: the arguments (no GPU needed, so a wrong count is reported as such on any
+// machine), the G2 points on the host (trusted_setup.cpp), then per device the G1 points on the GPU (engine.hip: init_srs), the
+// derived bases (engine_tables.hip: init_fk20) and, if asked for, the power structure (eip4844.hip: check_setup_powers).  Every
+// failure is NULL + a message; a constructor that fails late tears down what it had built (Engine::teardown).
+DASContext* eth_kzg_amd_das_context_new_with_setup(const uint8_t* g1_monomial, uint64_t n_g1, const uint8_t* g2_monomial, uint64_t n_g2,
+                                                   uint32_t flags, bool use_precomp, const int32_t* device_ordinals, uint64_t n_devices,
+                                                   double table_budget_gb, CResult* result) {
+    std::string why;
+    DASContext* c = nullptr;
+    constexpr uint32_t KNOWN = ETH_KZG_AMD_SETUP_NO_SUBGROUP_CHECK | ETH_KZG_AMD_SETUP_CHECK_POWERS;
+    if (n_g1 != kzg::TrustedSetup::N_G1 || n_g2 != kzg::TrustedSetup::N_G2)
+        why = "InvalidInput: a trusted setup holds 4096 G1 and 65 G2 monomial points, got " + std::to_string(n_g1) + " and " + std::to_string(n_g2);
+    else if (!g1_monomial || !g2_monomial) why = "InvalidInput: NULL point array (4096 G1 points of 48 bytes and 65 G2 points of 96 bytes are expected)";
+    else if (flags & ~KNOWN) why = "InvalidInput: unknown setup flags";
+    else if ((device_ordinals == nullptr) != (n_devices == 0) || n_devices > 64) why = "InvalidInput: the device list holds 1 to 64 ordinals (or NULL and 0)";
+    else {
+        try {
+            const auto setup = kzg::TrustedSetup::from_points(g1_monomial, g2_monomial, !(flags & ETH_KZG_AMD_SETUP_NO_SUBGROUP_CHECK),
+                                                              (flags & ETH_KZG_AMD_SETUP_CHECK_POWERS) != 0);
+            const std::vector<int> devices = n_devices ? std::vector<int>(device_ordinals, device_ordinals + n_devices) : env_device_list();
+            c = try_make_ctx(use_precomp, devices, table_budget_gb, &why, setup);
+        } catch (const std::exception& e) {  // (the point copies and the device list are allocations too)
+            why = std::string("InvalidSetup: ") + e.what();
+        } catch (...) {
+            why = "unknown failure";
+        }
+    }
+    if (result) *result = c ? ok() : err("ContextCreation(" + why + ")");
+    return c;
+}
+DASContext* eth_kzg_amd_das_context_new_with_setup_file(const uint8_t* file, uint64_t file_length, uint32_t flags, bool use_precomp,
+                                                        const int32_t* device_ordinals, uint64_t n_devices, double table_budget_gb,
+                                                        CResult* result) {
+    // "KZGSRS01" | n_g1 (u32 LE) | n_g2 (u32 LE) | g1 monomial (48 B each) | g2 monomial (96 B each)
+    uint32_t n1 = 0, n2 = 0;
+    const char* bad = nullptr;
+    if (!file) bad = "NULL file";
+    else if (file_length < 16 || memcmp(file, "KZGSRS01", 8)) bad = "no KZGSRS01 header";
+    else {
+        memcpy(&n1, file + 8, 4);
+        memcpy(&n2, file + 12, 4);
+        if (file_length != 16 + (uint64_t)n1 * 48 + (uint64_t)n2 * 96) bad = "the length does not match the counts in the header";
+    }
+    if (bad) {
+        if (result) *result = err(std::string("ContextCreation(InvalidInput: setup file: ") + bad + ")");
+        return nullptr;
+    }
+    return eth_kzg_amd_das_context_new_with_setup(file + 16, n1, file + 16 + (size_t)n1 * 48, n2, flags, use_precomp, device_ordinals, n_devices,
+                                                  table_budget_gb, result);
+}
+void eth_kzg_amd_setup_digest(const DASContext* ctx, uint8_t* out) { memcpy(out, eng(ctx)->setup().digest.data(), 32); }
 uint64_t eth_kzg_amd_context_devices(const DASContext* ctx, int32_t* out_ordinals, uint64_t capacity) {
     live(ctx);
     for (size_t d = 0; d < ctx->engines.size() && d < capacity && out_ordinals; d++) out_ordinals[d] = ctx->engines[d]->device();

@@ -180,6 +180,44 @@ int Engine::pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0
     return pairing::product_is_one(out, q, 2) ? 1 : 0;
 }
 
+
+// TrustedSetup::check_powers: subgroup tests pass for a well-formed file in the wrong basis or order (Lagrange points handed in
+// as monomial ones; two entries swapped) and every proof made on it is then wrong.  Both chains are checked to be consecutive
+// powers of ONE tau with random 128-bit weights rho_i derived from the setup's bytes:
+//   e(sum_i rho_i g1[i], [tau]_2)   == e(sum_i rho_i g1[i+1], [1]_2)     i = 0 .. 4094: the two sums are the verifier's bucket MSMs
+//   e(g1[0], sum_j rho'_j g2[j+1]) == e(g1[1], sum_j rho'_j g2[j])       j = 0 .. 63: 64-term sums on the host
+// (a chain that is not geometric passes with probability 2^-128).  That g1[0] and g2[0] are the standard generators was checked
+// on the bytes (trusted_setup.cpp).  Throws with a message that says which chain failed.
+void Engine::check_setup_powers() {
+    const TrustedSetup& ts = *setup_;
+    {
+        std::vector<uint32_t> w((size_t)(N_BLOB - 1) * 4);
+        ts.weights128(1, reinterpret_cast<uint32_t(*)[4]>(w.data()), N_BLOB - 1);
+        std::vector<Fr8> s0((size_t)N_BLOB - 1), s1((size_t)N_BLOB);  // canonical scalars: the weights are below 2^128 < r
+        memset(s0.data(), 0, s0.size() * sizeof(Fr8));
+        memset(s1.data(), 0, s1.size() * sizeof(Fr8));
+        for (int i = 0; i < N_BLOB - 1; i++) {
+            memcpy(s0[(size_t)i].v, &w[(size_t)i * 4], 16);      // job 0: sum rho_i g1[i], pairs with [tau]_2
+            memcpy(s1[(size_t)i + 1].v, &w[(size_t)i * 4], 16);  // job 1: sum rho_i g1[i+1], pairs with -[1]_2
+        }
+        if (!pairing_check_4844(d_srs_, s0, s1)) throw std::runtime_error("g1_monomial is not a sequence of consecutive powers of the tau of g2_monomial[1] (wrong basis or order?)");
+    }
+    {
+        constexpr int M = (int)TrustedSetup::N_G2 - 1;
+        std::vector<pairing::G2Affine> q(TrustedSetup::N_G2);
+        for (size_t j = 0; j < TrustedSetup::N_G2; j++)
+            if (!pairing::g2_decompress(q[j], ts.g2.data() + j * TrustedSetup::G2_BYTES)) throw std::runtime_error("trusted setup: G2 point failed to decompress");
+        uint32_t w[M][4];
+        ts.weights128(2, w, M);
+        const pairing::G2Prepared hi = pairing::prepare(pairing::g2_lincomb128(q.data() + 1, w, M));
+        const pairing::G2Prepared lo = pairing::prepare(pairing::g2_neg(pairing::g2_lincomb128(q.data(), w, M)));
+        G1Affine P[2];
+        HIPCK(hipMemcpy(P, d_srs_, sizeof P, hipMemcpyDeviceToHost));
+        const pairing::G2Prepared* qq[2] = {&hi, &lo};
+        if (!pairing::product_is_one(P, qq, 2)) throw std::runtime_error("g2_monomial is not a sequence of consecutive powers of the tau of g1_monomial[1]");
+    }
+}
+
 static Fr8 canon8(const Fr& mont) { Fr c = from_mont(mont); Fr8 r; memcpy(&r, &c, 32); return r; }
 
 // Verifier::verify_kzg_proof (kzg_single_open/src/verifier.rs:33-57): e(C - yG, -G2) e(pi, [tau - z]_2) == 1, evaluated as

@@ -209,7 +209,9 @@ Engine::SerialLease Engine::lease_serial() {
     });
 }
 
-Engine::Engine(bool use_precomp, int device, const Engine* primary, double table_budget_gb) : dev_(device), use_precomp_(use_precomp), primary_(primary), auxiliary_(primary != nullptr) {
+Engine::Engine(bool use_precomp, int device, const Engine* primary, double table_budget_gb, std::shared_ptr<const TrustedSetup> setup)
+    : dev_(device), use_precomp_(use_precomp), primary_(primary), auxiliary_(primary != nullptr) {
+    setup_ = primary ? primary->setup_ : setup ? std::move(setup) : TrustedSetup::mainnet();
     // every environment knob is read here, once (knobs.hpp); the auxiliary engines of a context copy their context's values
     knobs_ = primary ? primary->knobs_ : Knobs::from_env();
     if (knobs_.serial_lanes) max_lanes_ = knobs_.serial_lanes;
@@ -301,6 +303,10 @@ void Engine::construct() {
     init_verifier();
     HIPCK(hipStreamSynchronize(stream_));
     lap("verifier (G2 lines, cosets)");
+    if (setup_->check_powers && !primary_) {  // (a lane holds the setup its context has checked)
+        check_setup_powers();
+        lap("setup: powers of one tau");
+    }
     if (knobs_.fault == "constructor" && !primary_) throw std::runtime_error("injected fault (ETH_KZG_AMD_FAULT=constructor)");
     start_builder();  // last: nothing after it can throw
 }
@@ -623,31 +629,35 @@ void Engine::init_linmap(const Fr8* w8192_mont) {
 }
 
 void Engine::init_srs() {
-    // embedded trusted setup: "KZGSRS01" | n_g1 | n_g2 | g1 monomial (48 B each) | g2 monomial (96 B each)
-    const unsigned char* p = kzg_srs_begin;
-    size_t len = (size_t)(kzg_srs_end - kzg_srs_begin);
-    uint32_t n1, n2;
-    if (len < 16 || memcmp(p, "KZGSRS01", 8)) throw std::runtime_error("bad embedded SRS");
-    memcpy(&n1, p + 8, 4);
-    memcpy(&n2, p + 12, 4);
-    if (n1 != (uint32_t)N_BLOB || len != 16 + (size_t)n1 * 48 + (size_t)n2 * 96) throw std::runtime_error("bad embedded SRS size");
-    uint8_t* d_bytes;
-    int* d_st;
+    // The monomial G1 points of the setup.  The ceremony file of the library is decompressed without a subgroup test
+    // (trusted_setup/src/lib.rs:80-86); a caller's points take the endomorphism test unless the caller waived it
+    // (TrustedSetup::from_json against from_json_unchecked).  A lane's points were validated when its context was made.
+    const TrustedSetup& ts = *setup_;
+    if (ts.g1.size() != (size_t)N_BLOB * 48) throw std::runtime_error("trusted setup: wrong number of G1 points");
+    const bool checked = ts.subgroup_check && !ts.embedded && !primary_;
+    uint8_t* d_bytes = nullptr;
+    int* d_st = nullptr;
+    std::vector<int> st(N_BLOB);
+    struct Scratch {  // freed on every way out
+        uint8_t*& b;
+        int*& s;
+        ~Scratch() { if (b) (void)hipFree(b); if (s) (void)hipFree(s); }
+    } scratch{d_bytes, d_st};
     HIPCK(hipMalloc(&d_bytes, (size_t)N_BLOB * 48));
     HIPCK(hipMalloc(&d_st, N_BLOB * sizeof(int)));
     HIPCK(hipMalloc(&d_srs_, N_BLOB * sizeof(G1Affine)));
-    HIPCK(hipMemcpy(d_bytes, p + 16, (size_t)N_BLOB * 48, hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(d_bytes, ts.g1.data(), (size_t)N_BLOB * 48, hipMemcpyHostToDevice));
     {
         Fp12w nobeta{};
         launch::g1_decompress(d_bytes, d_srs_, d_st, N_BLOB, 0, nobeta, stream_);
     }
-    std::vector<int> st(N_BLOB);
     HIPCK(hipMemcpyAsync(st.data(), d_st, N_BLOB * sizeof(int), hipMemcpyDeviceToHost, stream_));
     HIPCK(hipStreamSynchronize(stream_));
-    for (int s : st)
-        if (s) throw std::runtime_error("embedded SRS point failed to decompress");
-    HIPCK(hipFree(d_bytes));
-    HIPCK(hipFree(d_st));
+    for (int i = 0; i < N_BLOB; i++) {
+        if (st[i]) throw std::runtime_error("g1_monomial[" + std::to_string(i) + "] is not the encoding of a curve point");
+        // [tau^i]_1 = O means tau = 0; the FK20 bases and the window tables have no form for an identity base
+        if ((ts.g1[(size_t)i * 48] >> 6) & 1) throw std::runtime_error("g1_monomial[" + std::to_string(i) + "] is the point at infinity");
+    }
     // beta: the cube root of unity in Fp with (beta x, y) = [lambda](x, y); pick it by testing on [tau]_1
     {
         G1Affine P;
@@ -657,13 +667,26 @@ void Engine::init_srs() {
         G1Affine Q = to_affine(scalar_mul<4>(to_jac(P), lam));
         Fp bx = mul(Q.x, inv(P.x));  // beta = x(lambda P) / x(P)
         Fp b3 = mul(sqr(bx), bx);
-        if (!eq(b3, one<FpParams>()) || eq(bx, one<FpParams>()) || !eq(Q.y, P.y)) throw std::runtime_error("GLV endomorphism check failed");
+        if (!eq(b3, one<FpParams>()) || eq(bx, one<FpParams>()) || !eq(Q.y, P.y)) {
+            // [lambda]P = (beta x, y) holds for every point of order r: a point it fails on is outside the subgroup
+            if (!ts.embedded) throw std::runtime_error("g1_monomial[1] is not in the prime-order subgroup (the endomorphism check failed on it)");
+            throw std::runtime_error("GLV endomorphism check failed");
+        }
         memcpy(&beta_, &bx, 48);
+    }
+    if (checked) {  // the same kernel in mode 1: decode + endomorphism subgroup test (status 2)
+        launch::g1_decompress(d_bytes, d_srs_, d_st, N_BLOB, 1, beta_, stream_);
+        HIPCK(hipMemcpyAsync(st.data(), d_st, N_BLOB * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        HIPCK(hipStreamSynchronize(stream_));
+        for (int i = 0; i < N_BLOB; i++) {
+            if (st[i] == 2) throw std::runtime_error("g1_monomial[" + std::to_string(i) + "] is not in the prime-order subgroup");
+            if (st[i]) throw std::runtime_error("g1_monomial[" + std::to_string(i) + "] is not the encoding of a curve point");
+        }
     }
 }
 
-// Window tables are immutable once built and depend only on (device, which bases, width), so the contexts of one
-// process share them: the second DASContext on a GPU costs neither another 206 GB nor another build
+// Window tables are immutable once built and depend only on (device, setup, which bases, width), so the contexts of one
+// process that hold the same setup share them: the second DASContext on a GPU costs neither another 206 GB nor another build
 // (the reference's Java test creates several contexts, LibEthKZGTest.java:32).  The last context to go frees the table.
 //
 }  // namespace kzg

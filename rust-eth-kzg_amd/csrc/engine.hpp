@@ -4,6 +4,7 @@
 #pragma once
 #include "knobs.hpp"
 #include "host_sync.hpp"
+#include "trusted_setup.hpp"
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
@@ -100,7 +101,11 @@ public:
     // window tables by reading through to its view -- no registry look-up, no builder thread, no lock shared with a build
     // table_budget_gb: > 0: upper bound for both window tables together; 0: $ETH_KZG_AMD_TABLE_GB, else DEFAULT_TABLE_BUDGET_GB;
     // < 0: whatever the HBM still holds
-    Engine(bool use_precomp, int device, const Engine* primary = nullptr, double table_budget_gb = 0);
+    // setup: the trusted setup the context is built on (trusted_setup.hpp); null: the mainnet ceremony file linked into the library.
+    // A lane takes its primary's.  Only what is a function of the setup is derived from it (the decompressed points, beta's
+    // self-test, the FK20 bases, the window tables, the prepared G2 points): twiddles, linear-map programs and NAF tables are not.
+    Engine(bool use_precomp, int device, const Engine* primary = nullptr, double table_budget_gb = 0,
+           std::shared_ptr<const TrustedSetup> setup = nullptr);
     // The default memory budget of the window tables: the nine-window GLV tables (nominal width 15: two windows of 15 bits and seven
     // of 14, 18 gathered additions per base) for FK20 (70.9 GB) and for the commitments (35.4 GB).  Measured on one box, same
     // resident 2048-blob batch: -8 % against the widest FK20 table (eight windows of 16 bits: 206 GB) at 43 % of the memory; the next
@@ -121,6 +126,7 @@ public:
     SerialLease lease_serial();
 
     int device() const { return dev_; }
+    const TrustedSetup& setup() const { return *setup_; }
     Comm* comm() const { return comm_; }       // RCCL communicator attached by eth_kzg_amd_comm_init (multi_gpu.cpp)
     void set_comm(Comm* c) { comm_ = c; }
     hipStream_t stream() const { return stream_; }
@@ -242,6 +248,7 @@ private:
     void init_constants();
     void init_linmap(const Fr8* w8192_mont);  // host copy of omega_8192^k
     void init_srs();
+    void check_setup_powers();  // TrustedSetup::check_powers: both chains of the setup are powers of one tau (eip4844.hip)
     void settle_streams();
     bool streams_overlap(hipStream_t a, hipStream_t b);
     void init_fk20();
@@ -313,6 +320,7 @@ private:
     std::mutex marks_mu_;
 
     int dev_ = 0;
+    std::shared_ptr<const TrustedSetup> setup_;  // never null once the constructor's first line has run
     Comm* comm_ = nullptr;
     bool use_precomp_ = true;
     Knobs knobs_;            // every environment knob, read once when the context is created (knobs.hpp)

@@ -17,9 +17,6 @@
 #include <stdexcept>
 #include <tuple>
 
-extern "C" const unsigned char kzg_srs_begin[];
-extern "C" const unsigned char kzg_srs_end[];
-
 namespace kzg {
 
 // a failed HIP call; `code` lets a caller tell an exhausted HBM (retry with a smaller sub-batch) from a broken device

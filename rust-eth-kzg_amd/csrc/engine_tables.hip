@@ -1,20 +1,33 @@
-// Window tables of a context: the process-wide registry (one table per GPU, kind and width, shared by contexts), the builder that
+// Window tables of a context: the process-wide registry (one table per GPU, setup, kind and width, shared by contexts), the builder that
 // allocates a table in pieces and fills it group by group, the views the MSM launches snapshot, the progressive start.
 // Replaces precompute_points / FixedBaseMSMPrecompWindow::new (crates/cryptography/bls12_381/src/fixed_base_msm_window.rs:69-82).
 #include "engine_internal.hpp"
 
 namespace kzg {
 
+// A table is a function of its bases, and the bases of the setup: the key carries the setup's digest (SHA-256 of its point bytes,
+// trusted_setup.hpp).  Two contexts of one GPU on the SAME setup share a table; a context on another setup never sees it --
+// without the digest it would pick up the first setup's tables and return well-formed proofs of the wrong setup.
+using Digest = TrustedSetup::Digest;
+using TableKey = std::tuple<int, Digest, int, int>;  // (device, setup digest, kind, width)
 static std::mutex g_tables_mu;  // the registry below: held for look-ups and inserts only, never across a build
-static std::map<std::tuple<int, int, int>, std::weak_ptr<Engine::SharedTable>> g_tables;  // (device, kind, width)
+static std::map<TableKey, std::weak_ptr<Engine::SharedTable>> g_tables;
 // one builder of WIDE tables at a time per GPU (the helper threads of several contexts of one device queue here; the contexts of a
-// device list -- c_api.cpp, ETH_KZG_AMD_DEVICES -- build side by side, one per device)
+// device list -- c_api.cpp, ETH_KZG_AMD_DEVICES -- build side by side, one per device).  Per GPU and NOT per setup: what the lock
+// rations is the GPU's memory -- fill_table decides from hipMemGetInfo whether a table fits, and two builders that both read
+// "fits" before either has allocated would each stop half-way -- so the builders of two setups on one GPU take turns as well.
+// The registry is IMMORTAL (allocated once, never deleted): a helper thread first calls this after start_builder() has
+// registered the exit handler, so function-local statics would be destroyed BEFORE that handler joins the builders, and a
+// builder still inside try_lock() / unlock() at process exit would touch a freed mutex.
 static std::mutex& build_mutex_of(int device) {
-    static std::mutex reg;
-    static std::map<int, std::unique_ptr<std::mutex>> mu;
-    std::lock_guard<std::mutex> lk(reg);
-    auto& m = mu[device];
-    if (!m) m.reset(new std::mutex);
+    struct Registry {
+        std::mutex reg;
+        std::map<int, std::mutex*> mu;
+    };
+    static Registry* const r = new Registry;
+    std::lock_guard<std::mutex> lk(r->reg);
+    std::mutex*& m = r->mu[device];
+    if (!m) m = new std::mutex;
     return *m;
 }
 
@@ -102,19 +115,19 @@ static bool fill_table(Engine::SharedTable& t, const void* bases, hipStream_t st
     return true;
 }
 
-// the live table of (device, kind, width) in the registry, whatever its state (null: none, or only an abandoned one)
-static std::shared_ptr<Engine::SharedTable> find_table(int dev, int kind, int w) {
+// the live table of (device, setup, kind, width) in the registry, whatever its state (null: none, or only an abandoned one)
+static std::shared_ptr<Engine::SharedTable> find_table(int dev, const Digest& setup, int kind, int w) {
     std::lock_guard<std::mutex> lk(g_tables_mu);
-    auto it = g_tables.find(std::make_tuple(dev, kind, w));
+    auto it = g_tables.find(TableKey(dev, setup, kind, w));
     if (it == g_tables.end()) return nullptr;
     auto t = it->second.lock();
     if (!t || t->state.load() == 2) return nullptr;
     return t;
 }
 // find_table, or a new (empty, state 0) table registered under the key; *created tells which
-static std::shared_ptr<Engine::SharedTable> find_or_create_table(int dev, int kind, int w, int n_groups, bool* created) {
+static std::shared_ptr<Engine::SharedTable> find_or_create_table(int dev, const Digest& setup, int kind, int w, int n_groups, bool* created) {
     std::lock_guard<std::mutex> lk(g_tables_mu);
-    auto& slot = g_tables[std::make_tuple(dev, kind, w)];
+    auto& slot = g_tables[TableKey(dev, setup, kind, w)];
     auto t = slot.lock();
     *created = false;
     if (t && t->state.load() != 2) return t;
@@ -124,16 +137,16 @@ static std::shared_ptr<Engine::SharedTable> find_or_create_table(int dev, int ki
     *created = true;
     return t;
 }
-// a COMPLETE table of (device, kind, width): found, awaited (another thread is building it) or built here; null if it does not fit
-static std::shared_ptr<Engine::SharedTable> obtain_table(int dev, int kind, int w, const void* bases, int n_groups, hipStream_t st,
+// a COMPLETE table of (device, setup, kind, width): found, awaited (another thread is building it) or built here; null if it does not fit
+static std::shared_ptr<Engine::SharedTable> obtain_table(int dev, const Digest& setup, int kind, int w, const void* bases, int n_groups, hipStream_t st,
                                                          bool only_if_live = false, const std::atomic<bool>* cancel = nullptr) {
     if (only_if_live) {
-        auto t = find_table(dev, kind, w);
+        auto t = find_table(dev, setup, kind, w);
         return t && t->state.load() == 1 ? t : nullptr;
     }
     if (cancel && cancel->load()) throw BuildCancelled{};
     bool created = false;
-    auto t = find_or_create_table(dev, kind, w, n_groups, &created);
+    auto t = find_or_create_table(dev, setup, kind, w, n_groups, &created);
     if (created) return fill_table(*t, bases, st, cancel) ? t : nullptr;
     while (t->state.load() == 0) {  // another context's thread is building it
         if (cancel && cancel->load()) throw BuildCancelled{};
@@ -197,9 +210,17 @@ void Engine::init_fk20() {
     launch::fk20_gather_bases(X, d_fk_bases_, stream_);
     HIPCK(hipStreamSynchronize(stream_));
     HIPCK(hipFree(X));
+    {   // A base that is the point at infinity has no table entries and no affine form the MSM kernels could add: never wrong
+        // bytes, so such a setup is refused here.  (tau = 1 does NOT give one -- a vector has 63 points, and sum_{k<63} omega^(m k) is
+        // never zero -- it is refused by init_verifier, where the base that vanishes for it lives.)  No honest setup has one.
+        std::vector<G1Affine> fk((size_t)128 * 64);
+        HIPCK(hipMemcpy(fk.data(), d_fk_bases_, fk.size() * sizeof(G1Affine), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < fk.size(); i++)
+            if (is_inf(fk[i])) throw std::runtime_error("degenerate trusted setup: a derived FK20 base (vector " + std::to_string(i >> 6) + ", position " + std::to_string(i & 63) + ") is the point at infinity");
+    }
     if (primary_) return;  // an engine lane: the tables are the context's (table_view reads through)
     if (!use_precomp_) {  // UsePrecomp::No: the sixteen-window tables (1.6 + 0.8 GB: what a use_precomp = true context STARTS on), nothing else to build
-        auto srs = obtain_table(dev_, 3, 8, d_srs_, 64, stream_), fk = obtain_table(dev_, 2, 8, d_fk_bases_, 128, stream_);
+        auto srs = obtain_table(dev_, setup_->digest, 3, 8, d_srs_, 64, stream_), fk = obtain_table(dev_, setup_->digest, 2, 8, d_fk_bases_, 128, stream_);
         if (!srs || !fk) throw std::runtime_error("not enough device memory for the window tables");
         publish(TAB_SRS, srs, nullptr);
         publish(TAB_FK, fk, nullptr);
@@ -218,11 +239,11 @@ void Engine::init_fk20() {
     {
         std::shared_ptr<SharedTable> fk, srs;
         for (int w : launch::GLV_WIDTHS)
-            if (!fk) fk = obtain_table(dev_, 2, w, nullptr, 128, stream_, /*only_if_live=*/true);
-        if (!fk) fk = obtain_table(dev_, 2, 8, d_fk_bases_, 128, stream_);
+            if (!fk) fk = obtain_table(dev_, setup_->digest, 2, w, nullptr, 128, stream_, /*only_if_live=*/true);
+        if (!fk) fk = obtain_table(dev_, setup_->digest, 2, 8, d_fk_bases_, 128, stream_);
         for (int w : launch::GLV_WIDTHS)
-            if (!srs) srs = obtain_table(dev_, 3, w, nullptr, 64, stream_, true);
-        if (!srs) srs = obtain_table(dev_, 3, 8, d_srs_, 64, stream_);
+            if (!srs) srs = obtain_table(dev_, setup_->digest, 3, w, nullptr, 64, stream_, true);
+        if (!srs) srs = obtain_table(dev_, setup_->digest, 3, 8, d_srs_, 64, stream_);
         if (!fk || !srs) throw std::runtime_error("not enough device memory for the start window tables");
         publish(TAB_FK, fk, nullptr);
         publish(TAB_SRS, srs, nullptr);
@@ -286,7 +307,7 @@ void Engine::build_final_tables() {
             return nullptr;
         }
         bool created = false;
-        auto t = find_or_create_table(dev_, kind, w, n_groups, &created);
+        auto t = find_or_create_table(dev_, setup_->digest, kind, w, n_groups, &created);
         const TableView cur = table_view(sel);
         const bool same_form = cur.main && cur.main->n_groups == t->n_groups;
         if (t->state.load() == 0 && same_form) publish(sel, cur.main, t);  // its ready groups serve at once
@@ -318,10 +339,10 @@ void Engine::build_final_tables() {
                 std::shared_ptr<SharedTable> growing;
                 if (sel == TAB_SRS) {
                     for (int w : launch::GLV_WIDTHS)
-                        if (!growing && w > cur.c) { auto t = find_table(dev_, 3, w); if (t && t->state.load() == 0) growing = t; }
+                        if (!growing && w > cur.c) { auto t = find_table(dev_, setup_->digest, 3, w); if (t && t->state.load() == 0) growing = t; }
                 } else {
                     for (int w : launch::GLV_WIDTHS)
-                        if (!growing && w > cur.c) { auto t = find_table(dev_, 2, w); if (t && t->state.load() == 0) growing = t; }
+                        if (!growing && w > cur.c) { auto t = find_table(dev_, setup_->digest, 2, w); if (t && t->state.load() == 0) growing = t; }
                 }
                 if (growing && growing->n_groups == cur.main->n_groups) publish(sel, cur.main, growing);
             }

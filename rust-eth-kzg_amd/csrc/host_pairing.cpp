@@ -285,5 +285,108 @@ bool final_exponentiation_is_one(const Fp12& f) {
     return is_one12(r);
 }
 
+// ---------------- G2 arithmetic for a caller-supplied setup ----------------
+// Jacobian coordinates over Fp2 (a = 0); used once per setup, never per call.
+struct G2Jac { Fp2 x, y, z; };
+static inline G2Jac g2j_inf() { return {one2(), one2(), zero2()}; }
+static inline G2Jac g2j_from(const G2Affine& a) { return a.inf ? g2j_inf() : G2Jac{a.x, a.y, one2()}; }
+static G2Jac g2j_dbl(const G2Jac& p) {
+    if (is_zero2(p.z)) return p;
+    const Fp2 A = sqr2(p.x), B = sqr2(p.y), Cc = sqr2(B);
+    Fp2 D = sqr2(p.x + B) - A - Cc;
+    D = D + D;
+    const Fp2 E = A + A + A, F = sqr2(E);
+    G2Jac r;
+    r.x = F - D - D;
+    Fp2 c8 = Cc + Cc;
+    c8 = c8 + c8;
+    c8 = c8 + c8;
+    r.y = E * (D - r.x) - c8;
+    const Fp2 yz = p.y * p.z;
+    r.z = yz + yz;
+    return r;
+}
+static G2Jac g2j_add(const G2Jac& p, const G2Jac& q) {
+    if (is_zero2(p.z)) return q;
+    if (is_zero2(q.z)) return p;
+    const Fp2 z1z1 = sqr2(p.z), z2z2 = sqr2(q.z);
+    const Fp2 u1 = p.x * z2z2, u2 = q.x * z1z1;
+    const Fp2 s1 = p.y * q.z * z2z2, s2 = q.y * p.z * z1z1;
+    if (eq2(u1, u2)) return eq2(s1, s2) ? g2j_dbl(p) : g2j_inf();
+    const Fp2 h = u2 - u1;
+    Fp2 i = h + h;
+    i = sqr2(i);
+    const Fp2 j = h * i;
+    Fp2 rr = s2 - s1;
+    rr = rr + rr;
+    const Fp2 v = u1 * i;
+    G2Jac r;
+    r.x = sqr2(rr) - j - v - v;
+    Fp2 s1j = s1 * j;
+    s1j = s1j + s1j;
+    r.y = rr * (v - r.x) - s1j;
+    r.z = (sqr2(p.z + q.z) - z1z1 - z2z2) * h;
+    return r;
+}
+static bool g2j_eq(const G2Jac& p, const G2Jac& q) {
+    const bool pi = is_zero2(p.z), qi = is_zero2(q.z);
+    if (pi || qi) return pi && qi;
+    const Fp2 z1z1 = sqr2(p.z), z2z2 = sqr2(q.z);
+    return eq2(p.x * z2z2, q.x * z1z1) && eq2(p.y * q.z * z2z2, q.y * p.z * z1z1);
+}
+static G2Affine g2j_to_affine(const G2Jac& p) {
+    if (is_zero2(p.z)) return {zero2(), zero2(), true};
+    const Fp2 zi = inv2(p.z), zi2 = sqr2(zi);
+    return {p.x * zi2, p.y * zi2 * zi, false};
+}
+static G2Jac g2j_mul(const G2Jac& p, const uint32_t* k, int nl) {
+    G2Jac acc = g2j_inf();
+    for (int i = 32 * nl - 1; i >= 0; i--) {
+        acc = g2j_dbl(acc);
+        if ((k[i >> 5] >> (i & 31)) & 1) acc = g2j_add(acc, p);
+    }
+    return acc;
+}
+bool g2_eq(const G2Affine& a, const G2Affine& b) {
+    if (a.inf || b.inf) return a.inf && b.inf;
+    return eq2(a.x, b.x) && eq2(a.y, b.y);
+}
+bool g2_killed_by_r(const G2Affine& q) { return is_zero2(g2j_mul(g2j_from(q), FrParams::MOD, 8).z); }
+// psi = twist . Frobenius . untwist: (x, y) -> (conj(x) / xi^((p-1)/3), conj(y) / xi^((p-1)/2)); on E'(Fp2) the points of order r
+// are exactly those with psi(Q) = [x]Q, x the (negative) BLS parameter (M. Scott, "A note on group membership tests for G1, G2
+// and GT on BLS pairing-friendly curves", 2021): a 64-bit multiplication instead of the 255-bit one of the definition.
+bool g2_in_subgroup(const G2Affine& q) {
+    if (q.inf) return true;
+    init();
+    const Fp2 cx = inv2(G2C), cy = inv2(G2C * G1C);
+    const G2Jac psi = {conj(q.x) * cx, conj(q.y) * cy, one2()};
+    const uint32_t xabs[2] = {(uint32_t)X_ABS, (uint32_t)(X_ABS >> 32)};
+    G2Jac xq = g2j_mul(g2j_from(q), xabs, 2);
+    xq.y = neg2(xq.y);  // x < 0
+    return g2j_eq(psi, xq);
+}
+G2Affine g2_mul(const G2Affine& q, const uint32_t* k, int n_limbs) { return g2j_to_affine(g2j_mul(g2j_from(q), k, n_limbs)); }
+G2Affine g2_lincomb128(const G2Affine* pts, const uint32_t (*k)[4], int n) {
+    G2Jac acc = g2j_inf();
+    std::vector<G2Jac> j((size_t)n);
+    for (int i = 0; i < n; i++) j[(size_t)i] = g2j_from(pts[i]);
+    for (int b = 127; b >= 0; b--) {  // the doublings are shared by all terms
+        acc = g2j_dbl(acc);
+        for (int i = 0; i < n; i++)
+            if ((k[i][b >> 5] >> (b & 31)) & 1) acc = g2j_add(acc, j[(size_t)i]);
+    }
+    return g2j_to_affine(acc);
+}
+// x^3 + 4 (1 + u) as a curve point with the lexicographically smaller y, if it is a square (the tests' source of points off the subgroup)
+bool g2_from_x(G2Affine& out, const Fp2& x) {
+    Fp four = zero<FpP>();
+    four.v[0] = 4;
+    four = to_mont(four);
+    Fp2 y;
+    if (!sqrt2(y, sqr2(x) * x + Fp2{four, four})) return false;
+    out = {x, y, false};
+    return true;
+}
+
 }  // namespace pairing
 }  // namespace kzg

@@ -22,6 +22,15 @@ struct G2Prepared { std::vector<Line> lines; bool inf = true; };
 void init();                                               // Frobenius constants (idempotent)
 bool g2_decompress(G2Affine& out, const uint8_t in[96]);   // ZCash encoding, on-curve check only
 G2Affine g2_neg(const G2Affine& q);
+// A caller-supplied setup (trusted_setup.hpp): membership of the order-r subgroup by the psi-endomorphism test (infinity passes,
+// as it does in the reference's checked parser) and by the definition [r]Q = O, equality, a multiple, a sum of 128-bit multiples,
+// and the curve point over an abscissa.  Once per setup, never per call.
+bool g2_in_subgroup(const G2Affine& q);
+bool g2_killed_by_r(const G2Affine& q);
+bool g2_eq(const G2Affine& a, const G2Affine& b);
+G2Affine g2_mul(const G2Affine& q, const uint32_t* k, int n_limbs);
+G2Affine g2_lincomb128(const G2Affine* pts, const uint32_t (*k)[4], int n);
+bool g2_from_x(G2Affine& out, const Fp2& x);
 G2Prepared prepare(const G2Affine& q);
 // prod_i e(P_i, Q_i) == 1 ?   P_i affine (Montgomery coordinates, identity = (0,0)).
 bool product_is_one(const G1Affine* P, const G2Prepared* const* Q, int n);

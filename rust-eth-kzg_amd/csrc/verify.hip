@@ -24,8 +24,6 @@
 #include <thread>
 #include <exception>
 
-extern "C" const unsigned char kzg_srs_begin[];
-
 namespace kzg {
 
 #define HIPCK(x)                                                                                              \
@@ -61,15 +59,30 @@ void Engine::init_verifier() {
     launch::init_attributes_verify();
     pairing::init();
     // G2 points of the verification key: [1]_2 = g2_monomial[0], [tau^64]_2 = g2_monomial[64]
-    const unsigned char* g2 = kzg_srs_begin + 16 + (size_t)N_BLOB * 48;
+    const unsigned char* g2 = setup_->g2.data();
     pairing::G2Affine gen, tau;
     if (!pairing::g2_decompress(gen, g2) || !pairing::g2_decompress(tau, g2 + 96 * CELL_LEN))
-        throw std::runtime_error("embedded SRS: G2 point failed to decompress");
+        throw std::runtime_error("trusted setup: G2 point failed to decompress");
     g2_tau_ = std::make_shared<pairing::G2Prepared>(pairing::prepare(tau));
     g2_neg_gen_ = std::make_shared<pairing::G2Prepared>(pairing::prepare(pairing::g2_neg(gen)));
     pairing::G2Affine tau1;
-    if (!pairing::g2_decompress(tau1, g2 + 96)) throw std::runtime_error("embedded SRS: [tau]_2 failed to decompress");
+    if (!pairing::g2_decompress(tau1, g2 + 96)) throw std::runtime_error("trusted setup: [tau]_2 failed to decompress");
     g2_tau1_ = std::make_shared<pairing::G2Prepared>(pairing::prepare(tau1));
+    if (!setup_->embedded && !primary_) {
+        // A tau inside the evaluation domain (tau^8192 = 1; tau = 1 is the plain case) makes tau^64 equal to h_k^64 for one of the 128
+        // cosets: the key [tau^64 - h_k^64]_2 that cell k's opening is checked against is the point at infinity and every "proof"
+        // for that cell verifies.  tau^8192 = 1 <=> tau^4096 = +-1 <=> e([tau^4095]_1, [tau]_2) = e([1]_1, [1]_2)^(+-1): two pairing
+        // checks on points the context holds anyway.  No honest setup is in this case; never wrong answers, so it is refused.
+        G1Affine P[2];
+        HIPCK(hipMemcpy(&P[0], (const G1Affine*)d_srs_ + (N_BLOB - 1), sizeof(G1Affine), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(&P[1], (const G1Affine*)d_srs_, sizeof(G1Affine), hipMemcpyDeviceToHost));
+        const pairing::G2Prepared gen_p = pairing::prepare(gen);
+        const pairing::G2Prepared* minus[2] = {g2_tau1_.get(), g2_neg_gen_.get()};  // tau^4096 = 1
+        const pairing::G2Prepared* plus[2] = {g2_tau1_.get(), &gen_p};              // tau^4096 = -1
+        if (pairing::product_is_one(P, minus, 2) || pairing::product_is_one(P, plus, 2))
+            throw std::runtime_error("degenerate trusted setup: tau is a root of unity of the evaluation domain (tau^8192 = 1), so a derived "
+                                     "verification base [tau^64 - h^64]_2 is the point at infinity");
+    }
     // coset shift tables 7^i, 7^-i
     std::vector<Fr> c(N_EXT), ci(N_EXT);
     Fr g = fr_u64(7), gi = inv(g);
