@@ -23,6 +23,31 @@ int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const ui
 int eth_kzg_amd_test_op_info(int op, int32_t *in_words, int32_t *out_words, int32_t *device_only, const char **name);
 int eth_kzg_amd_test_op(const DASContext *ctx, int op, int n, const int32_t *in, int32_t *out, int on_device);
 
+/* The window tables themselves.  A GLV table of nominal width c (launch.hpp): glv_windows(c) windows of mixed widths, two blocks per group
+ * (lower / upper windows), inside a block [window][base][digit], entry (base i, digit d) of a window of `bits` bits at
+ * (i << (bits - 1)) + d - 1, 1 <= d <= 2^(bits - 1), 96 bytes = 24 words each.
+ * kind: 0 the FK20 table (128 groups of 64 bases), 1 the commitment table (64 groups of 64).  which: 0 the complete table the next MSM
+ * launch would snapshot, 1 the wider table under construction next to it (its ready groups only), 2 the table a progressive start
+ * began on, while it is alive.  All return 0 on success, non-zero if there is no such table or an argument is out of range.
+ *
+ * eth_kzg_amd_test_table_info: out8 = nominal width, groups, bases per group, state (0 under construction, 1 complete, 2 abandoned),
+ *   ready groups, payload bytes (the entries: nothing else), groups per launch of the builder (they share its scratch), pieces;
+ *   piece_first_block[k] (up to max_pieces; may be NULL) = the first block, 2 * group + upper, of piece k (a piece holds whole blocks).
+ * eth_kzg_amd_test_table_audit: the exact audit (csrc/table_audit.hpp) of EVERY entry of the ready groups, on the GPU: *visited = entries
+ *   visited, *n_findings = entries with a finding, findings = the first max_findings of them as (group, window, base, d, reasons), sorted;
+ *   reasons: 1 encoding, 2 off the curve, 4 step T[d] != T[d-1] + T[1], 8 window link, 16 zero entry of a live row, 32 non-zero entry of
+ *   an identity row, 64 first entry of window 0 is not the base.  *ms (may be NULL) = the kernel's time.
+ * eth_kzg_amd_test_table_read: the stored words of entries d0 .. d0 + n - 1 of row (group, window, base) -> out[n][24].
+ * eth_kzg_amd_test_table_audit_buffer: the same audit of a caller's table -- its blocks one after the other ([group][lower | upper]) --
+ *   over bases[n_groups * nb] (96 bytes each: x, y as 12 little-endian words of the Montgomery form x 2^384 mod p; the identity is all
+ *   zero).  on_device = 0 runs the host pass of the same source (ctx may be NULL). */
+int eth_kzg_amd_test_table_info(const DASContext *ctx, int kind, int which, int64_t *out8, int32_t *piece_first_block, int max_pieces);
+int eth_kzg_amd_test_table_audit(const DASContext *ctx, int kind, int which, uint64_t *visited, uint64_t *n_findings, int32_t *findings,
+                                 int max_findings, double *ms);
+int eth_kzg_amd_test_table_read(const DASContext *ctx, int kind, int which, int group, int window, int base, int d0, int n, uint32_t *out);
+int eth_kzg_amd_test_table_audit_buffer(const DASContext *ctx, int c, int n_groups, int nb, const uint32_t *table, const uint8_t *bases,
+                                        int on_device, uint64_t *visited, uint64_t *n_findings, int32_t *findings, int max_findings);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = [
 TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_fr_ntt4096", "eth_kzg_amd_test_g1_fft128", "eth_kzg_amd_test_fixed_msm",
     "eth_kzg_amd_test_g1_decompress", "eth_kzg_amd_test_field_mul", "eth_kzg_amd_test_op_info", "eth_kzg_amd_test_op",
+    "eth_kzg_amd_test_table_info", "eth_kzg_amd_test_table_audit", "eth_kzg_amd_test_table_read", "eth_kzg_amd_test_table_audit_buffer",
 ]
 
 _lib = None
@@ -172,6 +173,10 @@ def load_library():
         "eth_kzg_amd_test_field_mul": [P, U8P, U8P, P, C.c_int, C.c_int],
         "eth_kzg_amd_test_op_info": [C.c_int, P, P, P, C.POINTER(C.c_char_p)],
         "eth_kzg_amd_test_op": [P, C.c_int, C.c_int, P, P, C.c_int],
+        "eth_kzg_amd_test_table_info": [P, C.c_int, C.c_int, P, P, C.c_int],
+        "eth_kzg_amd_test_table_audit": [P, C.c_int, C.c_int, P, P, P, C.c_int, P],
+        "eth_kzg_amd_test_table_read": [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
+        "eth_kzg_amd_test_table_audit_buffer": [P, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P, P, C.c_int],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args

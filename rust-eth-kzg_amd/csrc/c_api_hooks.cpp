@@ -4,8 +4,12 @@
 #include "c_ctx.hpp"
 #include "launch.hpp"
 
+#include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <vector>
 
 namespace {
 kzg::Engine* eng(const DASContext* ctx) {
@@ -51,6 +55,45 @@ int eth_kzg_amd_test_op(const DASContext* ctx, int op, int n, const int32_t* in,
     const char* nm;
     if (kzg::launch::test_op_info(op, &i, &o, &d, &nm) != 0 || d || n <= 0) return kzg::ERR_INPUT;  // device-only forms have no host pass
     return kzg::launch::test_op_host(op, n, in, out) == 0 ? 0 : kzg::ERR_INPUT;
+}
+
+static bool glv_shape_ok(int c, int n_groups, int nb) {
+    return kzg::launch::glv_width_supported(c) && n_groups >= 1 && n_groups <= 128 && nb >= 1 && nb <= 64;
+}
+int eth_kzg_amd_test_table_info(const DASContext* ctx, int kind, int which, int64_t* out8, int32_t* piece_first_block, int max_pieces) {
+    return eng(ctx)->test_table_info(kind, which, out8, piece_first_block, max_pieces);
+}
+int eth_kzg_amd_test_table_audit(const DASContext* ctx, int kind, int which, uint64_t* visited, uint64_t* n_findings, int32_t* findings,
+                                 int max_findings, double* ms) {
+    return eng(ctx)->test_table_audit(kind, which, visited, n_findings, findings, max_findings, ms);
+}
+int eth_kzg_amd_test_table_read(const DASContext* ctx, int kind, int which, int group, int window, int base, int d0, int n, uint32_t* out) {
+    return eng(ctx)->test_table_read(kind, which, group, window, base, d0, n, out);
+}
+int eth_kzg_amd_test_table_audit_buffer(const DASContext* ctx, int c, int n_groups, int nb, const uint32_t* table, const uint8_t* bases,
+                                        int on_device, uint64_t* visited, uint64_t* n_findings, int32_t* findings, int max_findings) {
+    if (!glv_shape_ok(c, n_groups, nb) || max_findings < 0) return kzg::ERR_INPUT;
+    if (on_device) return eng(ctx)->test_table_audit_buffer(c, n_groups, nb, table, bases, visited, n_findings, findings, max_findings);
+    // the host pass of the same source: no GPU, no context
+    const int WL = kzg::launch::glv_lower_windows(c), W = kzg::launch::glv_windows(c);
+    const size_t lower = kzg::launch::glv_entries_per_base(c, 0, WL) * (size_t)nb, upper = kzg::launch::glv_entries_per_base(c, WL, W) * (size_t)nb;
+    std::vector<const void*> blocks((size_t)2 * n_groups);
+    const char* t = (const char*)table;
+    for (int g = 0; g < n_groups; g++) {
+        blocks[2 * g] = t + (size_t)g * (lower + upper) * kzg::launch::SIZEOF_TABP;
+        blocks[2 * g + 1] = t + ((size_t)g * (lower + upper) + lower) * kzg::launch::SIZEOF_TABP;
+    }
+    unsigned long long v = 0, nf = 0;
+    kzg::launch::table_audit_host(blocks.data(), bases, c, n_groups, nb, &v, &nf, findings, max_findings);
+    std::vector<std::array<int32_t, 5>> f(std::min<unsigned long long>(nf, (unsigned long long)max_findings));
+    if (!f.empty()) {
+        memcpy(f.data(), findings, f.size() * sizeof(f[0]));
+        std::sort(f.begin(), f.end());
+        memcpy(findings, f.data(), f.size() * sizeof(f[0]));
+    }
+    *visited = v;
+    *n_findings = nf;
+    return 0;
 }
 
 }  // extern "C"

@@ -205,6 +205,14 @@ public:
     int test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out_recompressed);
     int test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp);
     int test_op(int op, int n, const int32_t* in, int32_t* out);
+    // the window tables themselves (engine_testhooks.hip).  kind: TableSel; which: 0 = the complete table the next MSM launch would
+    // snapshot (the view's main), 1 = the wider one under construction next to it (its ready groups), 2 = the table the context started on, while it is alive
+    std::shared_ptr<SharedTable> test_table(int kind, int which) const;
+    int test_table_info(int kind, int which, int64_t* out8, int32_t* piece_first_block, int max_pieces);
+    int test_table_audit(int kind, int which, uint64_t* visited, uint64_t* n_findings, int32_t* findings, int max_findings, double* ms);
+    int test_table_read(int kind, int which, int group, int window, int base, int d0, int n, uint32_t* out);
+    int test_table_audit_buffer(int c, int n_groups, int nb, const uint32_t* table, const uint8_t* bases, uint64_t* visited, uint64_t* n_findings,
+                                int32_t* findings, int max_findings);
 
     // ---- per-stage HIP-event timing (bench.py's roofline leg) ----
     enum Stage { ST_BLOB_TO_COEFFS = 0, ST_COEFFS_TO_CELLS, ST_FK20_SCALARS, ST_MSM_FIXED, ST_G1_IFFT, ST_G1_FFT,
@@ -328,6 +336,7 @@ private:
     double table_budget_gb_ = DEFAULT_TABLE_BUDGET_GB;  // upper bound for both tables together (constructor argument, ETH_KZG_AMD_TABLE_GB, or the default); <= 0: what the HBM holds
     mutable std::mutex tab_mu_;
     std::condition_variable tab_cv_;
+    std::weak_ptr<SharedTable> start_tab_[2];  // what a progressive start began on (introspection: alive until the wide tables have replaced it)
     Published<SharedTable> pub_[2];  // per table kind: main / next / retired (host_sync.hpp); start tables stay alive for kernels already in flight
     int tables_state_ = 0;  // 0 building, 1 final, 2 wide build failed (guarded by tab_mu_)
     std::string tables_error_;

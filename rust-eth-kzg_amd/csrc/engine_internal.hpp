@@ -65,6 +65,8 @@ struct Engine::SharedTable {
     size_t bytes = 0;                      // of all blocks
     size_t block_entries[2] = {0, 0};      // entries of a group's two blocks
     std::vector<void*> pieces;
+    std::vector<int> piece_first_block;    // per piece: its first block (2 group + upper); a piece holds whole blocks
+    int build_chunk = 0;                   // groups per builder launch: they share the builder's scratch (fill_table)
     std::vector<void*> h_blocks;           // host copy of the pointer array (entries of unallocated blocks are null)
     void** d_blocks = nullptr;             // device: [n_groups * halves]
     int blocks_allocated = 0;
@@ -81,7 +83,8 @@ struct Engine::SharedTable {
         bytes = 0;
         for (int b = 0; b < halves; b++) bytes += block_bytes(b) * (size_t)n_groups;
         h_blocks.assign((size_t)n_groups * halves, nullptr);
-        pieces.reserve((size_t)n_groups * halves);  // never reallocated: table_build_info reads its size from other threads while the builder appends
+        pieces.reserve((size_t)n_groups * halves);
+        piece_first_block.reserve((size_t)n_groups * halves);  // never reallocated: table_build_info reads its size from other threads while the builder appends
     }
     // time spent in hipMalloc for the pieces (microseconds: total, longest single call) and their count -- written by the builder thread,
     // read by eth_kzg_amd_table_build_info from caller threads while the build runs: atomics, not plain doubles
@@ -122,6 +125,7 @@ struct Engine::SharedTable {
             if ((uint64_t)(dt * 1e3) > alloc_us_max.load(std::memory_order_relaxed)) alloc_us_max.store((uint64_t)(dt * 1e3), std::memory_order_relaxed);
             if (dt > 100 && trace_allocs) fprintf(stderr, "[context] @%.0f ms: hipMalloc of table piece %zu (%.2f GB) took %.0f ms\n", trace_clock_ms(), pieces.size(), sz / 1e9, dt);
             if (e != hipSuccess) { (void)hipGetLastError(); why = std::string("hipMalloc of a table piece: ") + hipGetErrorString(e); return false; }
+            piece_first_block.push_back(blocks_allocated);
             pieces.push_back(p);
             piece_count.store(pieces.size(), std::memory_order_release);
             // the HIP runtime serialises allocations and other calls on locks that are not fair: a thread that allocates piece

@@ -49,6 +49,7 @@ static bool fill_table(Engine::SharedTable& t, const void* bases, hipStream_t st
     if (chunk < 1) chunk = 1;
     if (chunk > t.n_groups) chunk = t.n_groups;
     if (gentle) chunk = std::max(1, std::min(chunk, 512 / (nb * launch::glv_windows(c))));  // <= ~512 builder waves in flight (a wave per (base, window): 64 x W per group)
+    t.build_chunk = chunk;
     const size_t side_bytes = launch::table_glv_side_bytes(c, chunk, nb);
     void *scratch = nullptr, *side = nullptr;
     int* d_err = nullptr;
@@ -247,6 +248,8 @@ void Engine::init_fk20() {
         if (!fk || !srs) throw std::runtime_error("not enough device memory for the start window tables");
         publish(TAB_FK, fk, nullptr);
         publish(TAB_SRS, srs, nullptr);
+        start_tab_[TAB_FK] = fk;
+        start_tab_[TAB_SRS] = srs;
     }
     progressive_build_ = true;  // start_builder(), the constructor's LAST step, starts the helper thread
 }

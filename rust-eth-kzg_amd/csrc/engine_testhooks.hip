@@ -1,6 +1,8 @@
 // Stage-level test hooks of the engine (include/c_eth_kzg_test_hooks.h): single stages against the oracle.
 #include "engine_internal.hpp"
 
+#include <array>
+
 namespace kzg {
 
 // ---------------------------------------------------------------------------------------------
@@ -154,6 +156,144 @@ int Engine::test_op(int op, int n, const int32_t* in, int32_t* out) {
         HIPCK(hipStreamSynchronize(stream_));
         HIPCK(hipMemcpy(out, dout, no, hipMemcpyDeviceToHost));
         HIPCK(hipFree(di)); HIPCK(hipFree(dout));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the window tables themselves: introspection, raw entries, the exact audit of table_audit.hpp
+std::shared_ptr<Engine::SharedTable> Engine::test_table(int kind, int which) const {
+    if (primary_) return primary_->test_table(kind, which);
+    if (kind != TAB_FK && kind != TAB_SRS) return nullptr;
+    if (which == 2) return start_tab_[kind].lock();
+    const TableView v = table_view((TableSel)kind);
+    return which == 0 ? v.main : which == 1 ? v.next : nullptr;
+}
+
+// out8: nominal width, groups, bases per group, state, ready groups, payload bytes (all blocks, nothing else), groups per builder
+// launch (0: unknown), pieces; piece_first_block: the first block (2 group + upper) of each piece.  Returns ERR_INPUT if there is no such table.
+int Engine::test_table_info(int kind, int which, int64_t* out8, int32_t* piece_first_block, int max_pieces) {
+    const auto t = test_table(kind, which);
+    if (!t) return ERR_INPUT;
+    const int ready = t->state.load() == 1 ? t->n_groups : t->ready_groups.load(std::memory_order_acquire);
+    const int n_pieces = (int)t->piece_count.load(std::memory_order_acquire);
+    out8[0] = t->c; out8[1] = t->n_groups; out8[2] = t->nb; out8[3] = t->state.load(); out8[4] = ready;
+    out8[5] = (int64_t)t->bytes; out8[6] = t->build_chunk; out8[7] = n_pieces;
+    for (int k = 0; k < n_pieces && k < max_pieces && piece_first_block; k++) piece_first_block[k] = t->piece_first_block[k];
+    return OK;
+}
+
+static const void* table_bases(const void* fk, const void* srs, int kind) { return kind == 0 ? fk : srs; }
+
+// every entry of the table's ready groups through audit::audit_entry on the GPU; findings sorted by (group, window, base, d)
+int Engine::test_table_audit(int kind, int which, uint64_t* visited, uint64_t* n_findings, int32_t* findings, int max_findings, double* ms) {
+    const auto t = test_table(kind, which);
+    if (!t || max_findings < 0) return ERR_INPUT;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        const int groups = t->state.load() == 1 ? t->n_groups : t->ready_groups.load(std::memory_order_acquire);
+        const int FW = launch::TABLE_FINDING_WORDS;
+        char* d_out;
+        int32_t* d_find;
+        HIPCK(hipMalloc(&d_out, launch::SIZEOF_AUDIT_OUT));
+        HIPCK(hipMalloc(&d_find, (size_t)std::max(1, max_findings) * FW * sizeof(int32_t)));
+        struct { unsigned long long visited; unsigned int n, max; int32_t* f; } h = {0, 0, (unsigned)max_findings, d_find};
+        static_assert(sizeof(h) == launch::SIZEOF_AUDIT_OUT, "audit::Out");
+        HIPCK(hipMemcpy(d_out, &h, sizeof(h), hipMemcpyHostToDevice));
+        hipEvent_t e0, e1;
+        HIPCK(hipEventCreate(&e0)); HIPCK(hipEventCreate(&e1));
+        HIPCK(hipEventRecord(e0, stream_));
+        if (groups > 0) launch::table_audit_device(t->d_blocks, table_bases(d_fk_bases_, d_srs_, kind), t->c, groups, t->nb, d_out, stream_);
+        HIPCK(hipGetLastError());
+        HIPCK(hipEventRecord(e1, stream_));
+        HIPCK(hipStreamSynchronize(stream_));
+        float dt = 0;
+        HIPCK(hipEventElapsedTime(&dt, e0, e1));
+        HIPCK(hipEventDestroy(e0)); HIPCK(hipEventDestroy(e1));
+        HIPCK(hipMemcpy(&h, d_out, sizeof(h), hipMemcpyDeviceToHost));
+        const int kept = (int)std::min<unsigned>(h.n, (unsigned)max_findings);
+        std::vector<std::array<int32_t, 5>> f(kept);
+        if (kept) HIPCK(hipMemcpy(f.data(), d_find, (size_t)kept * FW * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::sort(f.begin(), f.end());
+        if (kept) memcpy(findings, f.data(), (size_t)kept * FW * sizeof(int32_t));
+        *visited = h.visited;
+        *n_findings = h.n;
+        if (ms) *ms = dt;
+        HIPCK(hipFree(d_out)); HIPCK(hipFree(d_find));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// the 24 words of the entries d0 .. d0 + n - 1 of row (group, window, base), as stored
+int Engine::test_table_read(int kind, int which, int group, int window, int base, int d0, int n, uint32_t* out) {
+    const auto t = test_table(kind, which);
+    if (!t) return ERR_INPUT;
+    const int c = t->c, W = launch::glv_windows(c), WL = launch::glv_lower_windows(c);
+    const int ready = t->state.load() == 1 ? t->n_groups : t->ready_groups.load(std::memory_order_acquire);
+    if (group < 0 || group >= ready || window < 0 || window >= W || base < 0 || base >= t->nb || d0 < 1 || n < 1) return ERR_INPUT;
+    const long T = 1l << (launch::glv_window_bits(c, window) - 1);
+    if ((long)d0 - 1 + n > T) return ERR_INPUT;
+    const int upper = window >= WL ? 1 : 0;
+    const size_t in_block = launch::glv_entries_per_base(c, upper ? WL : 0, window) * (size_t)t->nb + (size_t)base * T + (size_t)(d0 - 1);
+    const char* blk = (const char*)t->h_blocks[(size_t)group * t->halves + upper];
+    if (!blk || in_block + n > t->block_entries[upper]) return ERR_INPUT;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        HIPCK(hipMemcpy(out, blk + in_block * launch::SIZEOF_TABP, (size_t)n * launch::SIZEOF_TABP, hipMemcpyDeviceToHost));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// a caller's table (its blocks one after the other: [group][lower | upper], inside a block [window][base][digit]) and its n_groups x nb
+// bases (G1Affine), audited on the GPU
+int Engine::test_table_audit_buffer(int c, int n_groups, int nb, const uint32_t* table, const uint8_t* bases, uint64_t* visited, uint64_t* n_findings,
+                                    int32_t* findings, int max_findings) {
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        const int FW = launch::TABLE_FINDING_WORDS, WL = launch::glv_lower_windows(c), W = launch::glv_windows(c);
+        const size_t entries = launch::table_glv_entries(c, n_groups, nb), lower = launch::glv_entries_per_base(c, 0, WL) * (size_t)nb,
+                     upper = launch::glv_entries_per_base(c, WL, W) * (size_t)nb;
+        char *d_tab, *d_bases, *d_out;
+        void** d_blocks;
+        int32_t* d_find;
+        HIPCK(hipMalloc(&d_tab, entries * launch::SIZEOF_TABP));
+        HIPCK(hipMalloc(&d_bases, (size_t)n_groups * nb * sizeof(G1Affine)));
+        HIPCK(hipMalloc(&d_blocks, (size_t)2 * n_groups * sizeof(void*)));
+        HIPCK(hipMalloc(&d_out, launch::SIZEOF_AUDIT_OUT));
+        HIPCK(hipMalloc(&d_find, (size_t)std::max(1, max_findings) * FW * sizeof(int32_t)));
+        std::vector<void*> hb((size_t)2 * n_groups);
+        for (int g = 0; g < n_groups; g++) {
+            hb[2 * g] = d_tab + (size_t)g * (lower + upper) * launch::SIZEOF_TABP;
+            hb[2 * g + 1] = d_tab + ((size_t)g * (lower + upper) + lower) * launch::SIZEOF_TABP;
+        }
+        struct { unsigned long long visited; unsigned int n, max; int32_t* f; } h = {0, 0, (unsigned)max_findings, d_find};
+        HIPCK(hipMemcpy(d_tab, table, entries * launch::SIZEOF_TABP, hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_bases, bases, (size_t)n_groups * nb * sizeof(G1Affine), hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_blocks, hb.data(), hb.size() * sizeof(void*), hipMemcpyHostToDevice));
+        HIPCK(hipMemcpy(d_out, &h, sizeof(h), hipMemcpyHostToDevice));
+        launch::table_audit_device(d_blocks, d_bases, c, n_groups, nb, d_out, stream_);
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(stream_));
+        HIPCK(hipMemcpy(&h, d_out, sizeof(h), hipMemcpyDeviceToHost));
+        const int kept = (int)std::min<unsigned>(h.n, (unsigned)max_findings);
+        std::vector<std::array<int32_t, 5>> f(kept);
+        if (kept) HIPCK(hipMemcpy(f.data(), d_find, (size_t)kept * FW * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::sort(f.begin(), f.end());
+        if (kept) memcpy(findings, f.data(), (size_t)kept * FW * sizeof(int32_t));
+        *visited = h.visited;
+        *n_findings = h.n;
+        HIPCK(hipFree(d_tab)); HIPCK(hipFree(d_bases)); HIPCK(hipFree(d_blocks)); HIPCK(hipFree(d_out)); HIPCK(hipFree(d_find));
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;

@@ -36,6 +36,13 @@ void test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int
 int test_op_info(int op, int* in_words, int* out_words, int* device_only, const char** name);
 int test_op_host(int op, int n, const int32_t* in, int32_t* out);
 int test_op_device(int op, int n, const int32_t* d_in, int32_t* d_out, hipStream_t st);
+// k_table_audit.hip (hooks library only): table_audit.hpp over every entry of the groups [0, n_groups) behind `blocks` (two pointers
+// per group), bases = their n_groups x nb G1Affine.  Device: out = a device audit::Out (visited count, findings).  Host: the same source.
+constexpr int TABLE_FINDING_WORDS = 5;  // group, window, base, d, reasons (audit::R_*)
+constexpr size_t SIZEOF_AUDIT_OUT = 24;
+void table_audit_device(const void* const* blocks, const void* bases, int c, int n_groups, int nb, void* out, hipStream_t st);
+void table_audit_host(const void* const* blocks, const void* bases, int c, int n_groups, int nb, unsigned long long* visited,
+                      unsigned long long* n_findings, int32_t* findings, int max_findings);
 
 // k_msm.hip
 // A window table as the kernels see it: a device array of block pointers -- two per group (blocks[2 group + upper]: the lower

@@ -762,3 +762,180 @@ def fold_cases(name, rng, pts):
             tot = g_add(tot, a)
         refs.append(tot)
     return cases, refs
+
+
+# ---- GLV window tables: layout (csrc/launch.hpp), packed entries (curve30.hpp: TabS), the audit predicate -----------------------
+# A table of nominal width c: W = ceil(128 / c) windows of mixed widths covering the 128-bit half exactly; two blocks per group (the
+# lower ceil(W / 2) windows, the upper rest); inside a block [window][base][digit]; entry (base i, digit d) of a window of `bits`
+# bits at (i << (bits - 1)) + d - 1, 1 <= d <= 2^(bits - 1); 24 words per entry.  The entry is d 2^lo(w) B.
+def glv_windows(c):
+    return (128 + c - 1) // c
+
+
+def glv_lower_windows(c):
+    return (glv_windows(c) + 1) // 2
+
+
+def glv_window_bits(c, w):
+    W = glv_windows(c)
+    b = 128 // W
+    return b + (1 if w < 128 - W * b else 0)
+
+
+def glv_window_lo(c, w):
+    return sum(glv_window_bits(c, k) for k in range(w))
+
+
+def glv_entries_per_base(c, w0=0, w1=None):
+    return sum(1 << (glv_window_bits(c, w) - 1) for w in range(w0, glv_windows(c) if w1 is None else w1))
+
+
+def glv_table_entries(c, n_groups, nb):
+    return n_groups * nb * glv_entries_per_base(c)
+
+
+def glv_entry_index(c, nb, group, w, i, d):
+    """position (in entries) of entry (group, w, i, d) in a table whose blocks lie one after the other"""
+    WL = glv_lower_windows(c)
+    per_group = glv_entries_per_base(c) * nb
+    lower = glv_entries_per_base(c, 0, WL) * nb
+    upper = w >= WL
+    in_block = glv_entries_per_base(c, WL if upper else 0, w) * nb + (i << (glv_window_bits(c, w) - 1)) + d - 1
+    return group * per_group + (lower if upper else 0) + in_block
+
+
+def tabs_pack_value(v):
+    """12 words of an integer 0 <= v < 2^384 (the coordinate's Montgomery-390 value when it is canonical): word i = centred digit i's
+    low 30 bits | bits 2 i, 2 i + 1 of the top digit"""
+    d = fs_digits(v, DC)
+    assert 0 <= d[12] < (1 << 24), "not packable"
+    return [(d[i] & ((1 << 30) - 1)) | (((d[12] >> (2 * i)) & 3) << 30) for i in range(12)]
+
+
+def tabs_unpack_value(w):
+    """the integer 12 stored words stand for, whatever they hold"""
+    top, v = 0, 0
+    for i in range(12):
+        x = int(w[i]) & 0xFFFFFFFF
+        lo = x & 0x3FFFFFFF
+        if lo >= SHALF:
+            lo -= 1 << 30
+        v += lo << (30 * i)
+        top |= (x >> 30) << (2 * i)
+    return v + (top << 360)
+
+
+def tabs_pack(a):
+    """the 24 words tabs_pack_from_fq stores for the affine point a (None: the all-zero entry of an identity row)"""
+    if a is None:
+        return [0] * 24
+    return tabs_pack_value(a[0] * RS % P) + tabs_pack_value(a[1] * RS % P)
+
+
+def tabs_point(w):
+    """the affine point an entry holds (None: all zero), read without any check"""
+    if not any(int(x) for x in w):
+        return None
+    return tabs_unpack_value(w[:12]) * INV_RS % P, tabs_unpack_value(w[12:24]) * INV_RS % P
+
+
+def g1affine_words(a):
+    """G1Affine of curve.hpp: x, y as 12 little-endian words each of the Montgomery form x 2^384 mod p; the identity is all zero"""
+    if a is None:
+        return [0] * 24
+    out = []
+    for v in a:
+        m = v * (1 << 384) % P
+        out += [(m >> (32 * i)) & 0xFFFFFFFF for i in range(12)]
+    return out
+
+
+A_ENCODING, A_OFF_CURVE, A_STEP, A_LINK, A_ZERO, A_NONZERO_IDENTITY, A_ANCHOR = 1, 2, 4, 8, 16, 32, 64
+
+
+def _collinear(a, b, c):
+    """a + b == c for three affine points with a != +-b, by the line through a, b and -c and three different x"""
+    if a is None or b is None or c is None or len({a[0], b[0], c[0]}) != 3:
+        return False
+    return ((b[1] - a[1]) * (c[0] - a[0]) + (c[1] + a[1]) * (b[0] - a[0])) % P == 0
+
+
+def _tangent(a, c):
+    """2 a == c by the tangent in a through -c"""
+    if a is None or c is None or a[0] == c[0] or a[1] == 0:
+        return False
+    return ((c[1] + a[1]) * 2 * a[1] + 3 * a[0] * a[0] * (c[0] - a[0])) % P == 0
+
+
+def audit_row(row, bits_prev, prev_first, base, identity_row=False):
+    """The audit predicate (csrc/table_audit.hpp) over one row in plain integers: row = the 24 words of d = 1 .. T; prev_first = the
+    stored words of the first entry of the window below (None for window 0, where `base` -- the affine base -- anchors the row);
+    bits_prev = that window's width.  Returns {d: reasons}.  The words of a coordinate and the integer they stand for determine
+    each other (twelve 30-bit digits and a 24-bit top digit), so the encoding is the canonical one exactly when 0 <= value < p."""
+    out = {}
+    vals = [(tabs_unpack_value(w[:12]), tabs_unpack_value(w[12:24])) if any(int(x) for x in w) else None for w in row]
+    pts = [None if v is None else (v[0] * INV_RS % P, v[1] * INV_RS % P) for v in vals]
+    head_ok = None
+    for k in range(len(row)):
+        d, r, me = k + 1, 0, pts[k]
+        if identity_row:
+            if me is not None:
+                out[d] = A_NONZERO_IDENTITY
+            continue
+        if me is None:
+            out[d] = A_ZERO
+            continue
+        if not (0 <= vals[k][0] < P and 0 <= vals[k][1] < P):
+            r |= A_ENCODING
+        if (me[1] * me[1] - me[0] * me[0] * me[0] - 4) % P:
+            r |= A_OFF_CURVE
+        if d == 1:
+            if prev_first is None:
+                if me != base:
+                    r |= A_ANCHOR
+            else:
+                q = tabs_point(prev_first)
+                for _ in range(bits_prev):
+                    q = g_add(q, q)
+                if q is None or q != me:
+                    r |= A_LINK
+        elif d == 2:
+            if not _tangent(pts[0], me):
+                r |= A_STEP
+        elif not _collinear(pts[k - 1], pts[0], me):
+            if head_ok is None:
+                head_ok = _tangent(pts[0], pts[1])
+            if head_ok:  # a broken head is reported by d = 1, 2 themselves
+                r |= A_STEP
+        if r:
+            out[d] = r
+    return out
+
+
+def row_multiples_error(row, q):
+    """None, or the first d whose entry is not d q (q = 2^lo B, affine): the direct statement, by d - 1 additions (Jacobian, compared
+    by cross-multiplication: no inversion per entry; d = 2 is the doubling)"""
+    X, Y, Z = q[0], q[1], 1
+    qx, qy = q
+    for k, w in enumerate(row):
+        if k == 1:
+            X, Y = g_add(q, q)
+        elif k:
+            # (X, Y, Z) + q, mixed addition in plain integers (madd-2007-bl); d q != +-q for d < r, so H != 0
+            zz = Z * Z % P
+            h = (qx * zz - X) % P
+            rr = 2 * (qy * Z * zz - Y) % P
+            if h == 0:
+                return k + 1
+            i = 4 * h * h % P
+            j = h * i % P
+            v = X * i % P
+            X3 = (rr * rr - j - 2 * v) % P
+            Y = (rr * (v - X3) - 2 * Y * j) % P
+            Z = 2 * Z * h % P
+            X = X3
+        me = tabs_point(w)
+        zz = Z * Z % P
+        if me is None or (me[0] * zz - X) % P or (me[1] * zz * Z - Y) % P:
+            return k + 1
+    return None

@@ -408,6 +408,10 @@ def test_fixed_base_msm_stage_matches_oracle(oracle, monkeypatch, chunks, precom
             pts = b"".join(_fk20_base_column(i)[j] for i in range(64))
             scal = b"".join(sc[m][j * 64:(j + 1) * 64])
             assert got(m, j) == oracle_lib.g1_msm(pts, scal), (chunks, m, j)
+        for j in range(128):  # every group's rows are read by at least one compared MSM, in every schedule
+            m = 2 + j % 7
+            pts = b"".join(_fk20_base_column(i)[j] for i in range(64))
+            assert got(m, j) == oracle_lib.g1_msm(pts, b"".join(sc[m][j * 64:(j + 1) * 64])), (chunks, m, j)
     finally:
         c2.close()
 

@@ -109,6 +109,10 @@ def _msm_stage_check(ctx, tag):
         pts = b"".join(full._fk20_base_column(i)[j] for i in range(64))
         scal = b"".join(sc[m][j * 64:(j + 1) * 64])
         assert got(m, j) == oracle_lib.g1_msm(pts, scal), (tag, m, j)
+    for j in range(128):  # every group's rows are read by at least one compared MSM (tests/test_table_audit.py audits every entry)
+        m = 2 + j % 7
+        pts = b"".join(full._fk20_base_column(i)[j] for i in range(64))
+        assert got(m, j) == oracle_lib.g1_msm(pts, b"".join(sc[m][j * 64:(j + 1) * 64])), (tag, m, j)
 
 
 @pytest.mark.parametrize("width", [15, 14, 12, 8])
