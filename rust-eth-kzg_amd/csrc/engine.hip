@@ -225,7 +225,6 @@ Engine::Engine(bool use_precomp, int device, const Engine* primary, double table
         else if (knobs_.table_budget_gb != 0) table_budget_gb_ = knobs_.table_budget_gb;
     }
     vm_search_ = knobs_.vm_search;
-    arena_signed_ = knobs_.arena_signed;
     msm_split_ = knobs_.msm_split;
     if (knobs_.pip_shift_min >= 1) pip_shift_min_ = knobs_.pip_shift_min;
     // largest batch on the circulant form.  Its cost grows with every blob (1 blob 1.11 ms, 2: 1.36, 3: 1.78, 4: 1.87); the compiled

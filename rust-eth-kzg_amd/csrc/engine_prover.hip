@@ -60,7 +60,7 @@ void Engine::ensure_workspace(Work& w, int n, bool release) {
     HIPCK(hipMalloc(&w.coeffs, (size_t)cap * N_BLOB * sizeof(Fr)));
     if (&w == &work_[0]) HIPCK(hipMalloc(&w.canon, (size_t)cap * N_BLOB * sizeof(Fr)));  // canonical coefficients: commitment / EIP-4844 paths only
     HIPCK(hipMalloc(&w.scalars, (size_t)cap * 128 * 64 * sizeof(Fr)));
-    HIPCK(hipMalloc(&w.X, (size_t)cap * 128 * launch::SIZEOF_JACQ));
+    HIPCK(hipMalloc(&w.X, (size_t)cap * 128 * launch::SIZEOF_JACS));
     HIPCK(hipMalloc(&w.status, (size_t)cap * sizeof(int)));
     w.cap = cap;
 }
@@ -105,8 +105,8 @@ void Engine::launch_msm(const void* scalars, TableSel which, void* out, int n_gr
                         int brp_bits, hipStream_t st, int out_fmt) {
     launch_msm(scalars, table_view(which), false, out, n_groups, n_slices, out_stride, brp_bits, st, out_fmt);
 }
-// out_fmt: launch::FMT_JACQ (the default: 14 x 29-bit sums) or FMT_JACS (the signed 13 x 30-bit sums everything after the MSM computes
-// in); `out` addresses points of that format
+// out_fmt: launch::FMT_JACS (the signed 13 x 30-bit sums everything after the MSM computes in on the prover, recovery and commitment
+// paths) or FMT_JACQ (14 x 29-bit sums: the stage hook, the interpolation MSM of verify_many.hip); `out` addresses points of that format
 // tv: ONE snapshot of the table view (the builder thread may publish a wider table at any time); scalars_split: the producer
 // has stored the scalars as balanced GLV halves already (only meaningful for a GLV table).  While a wider table is under
 // construction its leading ready groups run on it and the rest on the complete table: two launches, one MSM stage.
@@ -195,7 +195,7 @@ void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream
         if (slp_force_ < 0 && bp == 64 && n > 32 && launch::coop_points_max() > 0) which = SLP_DEPTH_456;
         mulc_coop_lanes = n <= 32 ? n : (bp == 64 && which == SLP_DEPTH_456) ? n : 0;
         prog = &slp_program(which);
-        const size_t need = (size_t)prog->n_slots * bp * launch::SIZEOF_JACQ;  // (sized for the larger of the two point formats)
+        const size_t need = (size_t)prog->n_slots * bp * launch::SIZEOF_JACS;
         if (need > w.slp_arena_bytes) {
             if (w.slp_arena) { HIPCK(hipStreamSynchronize(st)); HIPCK(hipFree(w.slp_arena)); w.slp_arena = nullptr; w.slp_arena_bytes = 0; }
             HIPCK(hipMalloc(&w.slp_arena, need));
@@ -206,9 +206,9 @@ void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream
     // The arena's point format: every kernel between the scalars and the proofs' bytes -- MSM, constant multiplications, additions,
     // compression; a lane, two or four lanes per blob -- is a kernel of the signed 13 x 30-bit field, and the arena holds its points
     // (JacS, 156 B) as they are: ONE Fp representation under the whole path at every batch size, no conversions.
-    // The 14 x 29-bit field (JacQ) is the cross-check ETH_KZG_AMD_ARENA_SIGNED=0 (and what verification and EIP-4844 compute in).
-    const int fmt = arena_signed_ ? launch::FMT_JACS : launch::FMT_JACQ;
-    const size_t pt = fmt == launch::FMT_JACS ? launch::SIZEOF_JACS : launch::SIZEOF_JACQ;
+    // (The 14 x 29-bit field, JacQ, is what verification and the set-up compute in.)
+    constexpr int fmt = launch::FMT_JACS;
+    constexpr size_t pt = launch::SIZEOF_JACS;
     const TableView tv = tv_pre ? *tv_pre : table_view(TAB_FK);  // one snapshot for the scalars' form AND the MSM that reads them
     if (!tv_pre) {
         const int mk1 = mark_begin(ST_FK20_SCALARS, st);
@@ -237,7 +237,7 @@ void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream
         int n_launches = 0;
         for (auto& L : prog->launches)
             launch::g1_slp_launch(L.kind, w.slp_arena, bp, (const uint32_t*)prog->d_words + (size_t)L.first * 4, L.count, prog->d_naf, beta_, st, 0,
-                                  mulc_coop_lanes, fmt, n);
+                                  mulc_coop_lanes, n);
         n_launches = (int)prog->launches.size();
         mark_end(mk3, n_launches, st);
         const int mk4 = mark_begin(ST_COMPRESS, st);
@@ -248,7 +248,7 @@ void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream
     if (n <= circ_max_) {  // a handful of blobs: the two transforms as one circulant product (k_g1circ.hip)
         if (!w.circ_table) HIPCK(hipMalloc(&w.circ_table, launch::g1_circ_table_bytes(circ_max_, circ_T_)));
         const int mk5 = mark_begin(ST_G1_IFFT, st);
-        launch::g1_circ128(w.X, bp, n, segs, w.circ_table, circ_T_, d_circ_terms_, circ_per_lane_, beta_, st, fmt);
+        launch::g1_circ128(w.X, bp, n, segs, w.circ_table, circ_T_, d_circ_terms_, circ_per_lane_, beta_, st);
         mark_end(mk5, 2, st);
     } else throw std::logic_error("run_proofs_from_coeffs: a batch above the circulant form needs the compiled linear map");
     const int mk10 = mark_begin(ST_COMPRESS, st);
@@ -368,11 +368,10 @@ int Engine::blob_to_kzg_commitment_device(int n, const uint8_t* d_blobs, uint8_t
         // commit = MSM_4096(coeffs, g1_monomial)  (fk20/prover.rs:128-145, commit_key.rs:38-44):
         // 64 groups of 64 bases through the window-table kernel, then a fold over the groups.
         launch::blob_to_coeffs(n, d_blobs, d_coeffs_, d_canon_, d_status_, d_w29_, n_inv4096_, st);
-        const int fmt = arena_signed_ ? launch::FMT_JACS : launch::FMT_JACQ;  // (the points' form: run_proofs_from_coeffs)
-        launch::g1_set_inf(d_X_, (size_t)64 * bp, st, fmt);
-        launch_msm(d_canon_, TAB_SRS, d_X_, 64, n, bp, 0, st, fmt);
-        launch::g1_sum_positions(d_X_, 64, bp, n, st, fmt);
-        launch::g1_compress(d_X_, d_commitments, 1, bp, n, st, fmt);
+        launch::g1_set_inf(d_X_, (size_t)64 * bp, st, launch::FMT_JACS);  // (the points' form: run_proofs_from_coeffs)
+        launch_msm(d_canon_, TAB_SRS, d_X_, 64, n, bp, 0, st, launch::FMT_JACS);
+        launch::g1_sum_positions(d_X_, 64, bp, n, st);
+        launch::g1_compress(d_X_, d_commitments, 1, bp, n, st, launch::FMT_JACS);
         if (h_status) HIPCK(hipMemcpyAsync(h_status, d_status_, n * sizeof(int), hipMemcpyDeviceToHost, st));
         HIPCK(hipEventRecord(work_[0].done, st));
         HIPCK(hipGetLastError());

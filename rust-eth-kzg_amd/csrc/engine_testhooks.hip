@@ -42,7 +42,7 @@ int Engine::test_g1_fft128(const uint8_t* in, uint8_t* out, int n_lanes, int inv
         const size_t PS = launch::SIZEOF_JACQ;
         HIPCK(hipMalloc(&X, nx * PS));
         HIPCK(hipMemcpy(di, in, bytes, hipMemcpyHostToDevice));
-        launch::g1_set_inf(X, nx, stream_);
+        launch::g1_set_inf(X, nx, stream_, launch::FMT_JACQ);
         launch::test_load_points(di, X, n_lanes, stride, stream_);
         HIPCK(hipStreamSynchronize(stream_));
         std::vector<uint8_t> hx(nx * PS), hy(nx * PS);
@@ -56,7 +56,7 @@ int Engine::test_g1_fft128(const uint8_t* in, uint8_t* out, int n_lanes, int inv
         g1_fft128_full(X, stride, inverse, stream_);
         HIPCK(hipStreamSynchronize(stream_));
         if (!inverse) permute();  // DIF leaves bit-reversed output
-        launch::g1_compress(X, dout, 128, stride, n_lanes, stream_);
+        launch::g1_compress(X, dout, 128, stride, n_lanes, stream_, launch::FMT_JACQ);
         HIPCK(hipStreamSynchronize(stream_));
         HIPCK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
         HIPCK(hipFree(di)); HIPCK(hipFree(dout)); HIPCK(hipFree(X));
@@ -82,9 +82,9 @@ int Engine::test_fixed_msm(const uint8_t* scalars_be, int n_msm, uint8_t* out) {
         HIPCK(hipMalloc(&dout, (size_t)n_msm * 128 * 48));
         HIPCK(hipMemcpy(di, scalars_be, ns * 32, hipMemcpyHostToDevice));
         launch::test_scalars_be(di, sc, ns, stream_);
-        launch::g1_set_inf(X, (size_t)128 * stride, stream_);
-        launch_msm(sc, TAB_FK, X, 128, n_msm, stride, 0, stream_);
-        launch::g1_compress(X, dout, 128, stride, n_msm, stream_);
+        launch::g1_set_inf(X, (size_t)128 * stride, stream_, launch::FMT_JACQ);
+        launch_msm(sc, TAB_FK, X, 128, n_msm, stride, 0, stream_, launch::FMT_JACQ);
+        launch::g1_compress(X, dout, 128, stride, n_msm, stream_, launch::FMT_JACQ);
         HIPCK(hipStreamSynchronize(stream_));
         HIPCK(hipMemcpy(out, dout, (size_t)n_msm * 128 * 48, hipMemcpyDeviceToHost));
         HIPCK(hipFree(di)); HIPCK(hipFree(sc)); HIPCK(hipFree(X)); HIPCK(hipFree(dout));

@@ -1,8 +1,8 @@
 // Two (and, below, four) lanes per point operation in the signed 13 x 30-bit field (fp30.hpp / curve30.hpp): the chain forms of the constant
 // multiplication -- halved doubling and mixed addition with a table entry on the common Z (g1_mulc30.hpp) -- for batches of
 // 17 .. 64 blobs, where a constant multiplication of the G1 linear map is a dependent chain of 128 doublings and ~43 additions on a
-// SIMD that has nothing else to do (BASELINE configs 4 and 5: the per-GPU shares).  Same idea as g1_coop.hpp's pair forms in the
-// 14 x 29-bit field: the lanes 2b and 2b + 1 of a wave both hold blob b's operands, compute one level's independent products side by
+// SIMD that has nothing else to do (BASELINE configs 4 and 5: the per-GPU shares).  Same idea as g1_coop.hpp's quad forms in the
+// 14 x 29-bit field, with two lanes: the lanes 2b and 2b + 1 of a wave both hold blob b's operands, compute one level's independent products side by
 // side (operands picked by lane, ONE multiplication issued), exchange them with pair-broadcast DPP moves (13 per field element) and
 // run the linear steps and the last, fused reductions redundantly:
 //     doubling      X^2 | Y^2  ->  X Y^2 | Y Z  ->  H^2 - 2 M  ->  H (M - X3) - B^2            4 reductions deep (7 alone):  1,406 multiply-adds (2,054)

@@ -1,9 +1,9 @@
-// Multiplication of a G1 point by a PUBLIC constant that the host has recoded (engine.hip: recode_glv_wnaf):
-// shared by the radix-2 G1-FFT layers (k_g1fft.hip) and the straight-line executor of the FK20 proofs map (k_g1slp.hip).
+// Multiplication of a G1 point by a PUBLIC constant that the host has recoded (engine.hip: recode_glv_wnaf), in the 14 x 29-bit
+// field: what the radix-2 G1-FFT layers run (k_g1fft.hip).  The straight-line executor of the FK20 proofs map (k_g1slp.hip) runs
+// the same algorithm in the signed 13 x 30-bit field (g1_mulc30.hpp).
 #pragma once
 #include "kcommon.hpp"
 #include "curve29.hpp"
-#include "g1_coop.hpp"
 #include "launch.hpp"
 
 #ifndef G1_MULC_COZ
@@ -23,11 +23,7 @@ namespace kzg {
 // Every digit test is a scalar branch on wave-uniform data: no lane divergence.
 // tab[k][2][33] words = 2 x 132 signed bytes: digit t of half h is byte t of tab[k][h].
 // row: the 2 x TWIDDLE_WORDS digit words of the constant (wave-uniform address)
-// COOP = 4: the four lanes of a quad hold the same p and share the doublings and mixed additions of the digit loop (g1_coop.hpp:
-// 3.5 and 5.5 multiplication times instead of 6.5 and 10.5); COOP = 2: the two lanes of a pair (4 and 5.5); `quad` is the lane's
-// index in its quad / pair.  The table is built on every lane.
-template <int COOP = 0>
-__device__ __forceinline__ JacQ mul_by_recoded(const JacQ& p, const uint32_t* __restrict__ row, const Fq<1>& beta, int quad = -1) {
+__device__ __forceinline__ JacQ mul_by_recoded(const JacQ& p, const uint32_t* __restrict__ row, const Fq<1>& beta) {
     constexpr int NT = 1 << (launch::TWIDDLE_WNAF_W - 2);  // odd multiples P, 3P, .., (2 NT - 1) P
     // The table is brought to ONE common Z = prod z_j without an inversion: (X_j l_j^2, Y_j l_j^3) with l_j = Z / z_j are
     // the affine coordinates of the same points on the isomorphic curve y^2 = x^3 + 4 Z^6.  The group law for a = 0
@@ -113,11 +109,7 @@ __device__ __forceinline__ JacQ mul_by_recoded(const JacQ& p, const uint32_t* __
         if (!started && (w1 | w2) == 0) continue;
 #pragma unroll 1
         for (int q = 3; q >= 0; q--) {
-            if (started) {
-                if constexpr (COOP == 4) acc = coop_dbl(acc, quad);
-                else if constexpr (COOP == 2) acc = coop2_dbl(acc, quad);
-                else acc = dbl(acc);
-            }
+            if (started) acc = dbl(acc);
 #pragma unroll 1
             for (int h = 0; h < 2; h++) {
                 const int d = (int)(int8_t)((h ? w2 : w1) >> (8 * q));
@@ -130,9 +122,7 @@ __device__ __forceinline__ JacQ mul_by_recoded(const JacQ& p, const uint32_t* __
                     acc.y = d < 0 ? relax<XB>(neg(op.y)) : relax<XB>(op.y);
                     acc.z = relax<ZB>(fq_one());
                     started = true;
-                } else if constexpr (COOP == 4) acc = coop_add_mixed(acc, op, d < 0, quad);
-                else if constexpr (COOP == 2) acc = coop2_add_mixed(acc, op, d < 0, quad);
-                else acc = add_mixed(acc, op, d < 0);
+                } else acc = add_mixed(acc, op, d < 0);
             }
         }
     }

@@ -1,11 +1,10 @@
-// Multiplication of a G1 point by a PUBLIC, host-recoded constant in the signed 13 x 30-bit field: the form k_slp_mulc runs
+// Multiplication of a G1 point by a PUBLIC, host-recoded constant in the signed 13 x 30-bit field: the form k_slp_mulc_s runs
 // for batches that fill the chip (83 % of the G1 linear map's time).  Same algorithm as g1_mulc.hpp -- GLV halves in width-5
 // NAF over the 8 odd multiples, the table built by co-Z additions and brought to ONE common Z (the isomorphic curve
 // y^2 = x^3 + 4 Z^6) so that every addition of the digit loop is a mixed one -- with the chain written for fp30.hpp:
 //   * doublings in the halved form (curve30.hpp: dbl_half: 2,054 multiply-adds instead of 2,317, no constant multiples),
 //   * mixed additions with the subtractions fused into the reductions (3,497 instead of 3,941),
-//   * the point is read from and written to the arena as it is when the arena holds the signed form (batches of more than one
-//     lane group); an arena in the 14 x 29-bit form (JacQ) costs six products per multiplication for the way in and out.
+//   * the point is read from and written to the arena as it is: the arena holds the signed form.
 // Reference work being replaced: the blst scalar multiplication behind `b * twiddle` of fft.rs:164-177.
 #pragma once
 #include "kcommon.hpp"
@@ -108,11 +107,6 @@ __device__ __forceinline__ JacS mul_by_recoded30(const JacS& p, const uint32_t* 
     }
     acc.z = mul(acc.z, zc);  // back from the isomorphic curve
     return acc;
-}
-// the same on an arena in the 14 x 29-bit form: six products for the way in and out
-template <int COOP = 0>
-__device__ __forceinline__ JacQ mul_by_recoded30(const JacQ& pq, const uint32_t* __restrict__ row, const Fs<1, DC>& beta, int part = 0) {
-    return jacq_from_jacs(mul_by_recoded30<COOP>(jacs_from_jacq(pq), row, beta, part));
 }
 
 }  // namespace kzg

@@ -13,8 +13,6 @@
 // ~45x the additions of the radix-2 network per blob, but on SIMDs that would otherwise idle; used for <= CIRC_MAX blobs.
 #include "engine.hpp"
 #include "kcommon.hpp"
-#include "curve29.hpp"
-#include "g1_coop.hpp"
 #include "curve30.hpp"
 #include "g1_coop30.hpp"
 #include "launch.hpp"
@@ -22,40 +20,13 @@
 namespace kzg {
 using launch::CIRC_LANES;
 
-// The kernels below are written once for both point forms: JacS, the signed 13 x 30-bit field (launch::FMT_JACS: what the engine
-// runs -- with it the single-blob path, too, is in the prover's ONE Fp representation from the MSM's fold to the proof bytes; round 6),
-// and JacQ, the 14 x 29-bit field (ETH_KZG_AMD_ARENA_SIGNED=0, the cross-check).  A doubling of the signed form is the halved one:
-// (X / 4, Y / 8, Z / 2) is the same point, so the table holds 2^t u[j] all the same.
+// The points are JacS, the signed 13 x 30-bit field (curve30.hpp, g1_coop30.hpp): the single-blob path, too, is in the prover's ONE Fp
+// representation from the MSM's fold to the proof bytes (round 6).  A doubling is the halved one: (X / 4, Y / 8, Z / 2) is the same
+// point, so the table holds 2^t u[j] all the same.
+// The kernels were written for two point forms and are still templates over the point type with its operations in CircOps<Pt>; JacS is
+// the one instantiation left.  (Rewritten as plain functions they compile to the same instructions except that some integer additions
+// get their operands in the other order; they stay templates so that removing the 14-digit form changes no launched kernel at all.)
 template <class Pt> struct CircOps;
-template <> struct CircOps<JacQ> {
-    using Beta = Fq<1>;
-    static __device__ __forceinline__ JacQ dbl1(const JacQ& p) { return dbl(p); }
-    static __device__ __forceinline__ void set_phi_x(JacQ& q, const JacQ& p, const Beta& beta) { q.x = relax<XB>(mul(p.x, beta)); }
-    static __device__ __forceinline__ JacQ coop_add4(const JacQ& p, const JacQ& q, bool negq, int quad) { return coop_add(p, q, negq, quad); }
-    template <int NT> static __device__ __forceinline__ void fold(JacQ* red, int first_span, int tid) { coop_tree_fold<NT>(red, first_span, tid); }
-    // coop_dbl with the product beta X in lane 3 of its first level
-    static __device__ __forceinline__ JacQ coop_dbl_phi(const JacQ& p, int quad, const Beta& beta, JacQ& phi) {
-        const bool l0 = quad == 0, l1 = quad == 1, l3 = quad == 3;
-        const Fq<XB> bw = relax<XB>(beta);
-        const Fq<XB> a1 = select(l0 || l3, p.x, p.y);
-        const Fq<XB> b1 = select(l0, p.x, select(l1, p.y, select(l3, bw, relax<XB>(p.z))));
-        const Fq<2> r1 = mul(a1, b1);
-        const Fq<2> A = quad_bcast<0>(r1), B = quad_bcast<1>(r1), YZ = quad_bcast<2>(r1), bX = quad_bcast<3>(r1);
-        phi = p;
-        phi.x = relax<XB>(bX);
-        const Fq<6> E = add(dbl(A), A);
-        const Fq<2> r2 = mul(select(l0, p.x, relax<XB>(E)), select(l0, relax<XB>(B), relax<XB>(E)));
-        const Fq<2> XY2 = quad_bcast<0>(r2), F = quad_bcast<1>(r2);
-        const Fq<8> Dd = dbl2(XY2);
-        auto x3 = sub2(F, Dd);
-        auto y3 = mul_add(E, sub(Dd, x3), neg2(B), dbl2(B));
-        JacQ r;
-        r.x = relax<XB>(x3);
-        r.y = relax<XB>(y3);
-        r.z = dbl(YZ);
-        return r;
-    }
-};
 template <> struct CircOps<JacS> {
     using Beta = Fs<1, DC>;
     static __device__ __forceinline__ JacS dbl1(const JacS& p) { return dbl_half(p); }
@@ -121,7 +92,7 @@ __global__ __launch_bounds__(CIRC_LANES) void k_g1_circ_sum(const Pt* __restrict
     if (l == 0) X[(size_t)(__brev((unsigned)k) >> 25) * stride + b] = part[0];  // proofs leave in bit-reversed order
 }
 
-// The same two kernels with FOUR lanes per chain (g1_coop.hpp, g1_coop30.hpp): a handful of blobs leaves the chip idle, and both
+// The same two kernels with FOUR lanes per chain (g1_coop30.hpp): a handful of blobs leaves the chip idle, and both
 // kernels are dependent chains -- T / segs doublings, then ~30 general additions per lane of the sum.  The quad shares each doubling
 // (the beta X of the phi image rides in a lane the doubling leaves idle) and each addition.
 template <class Pt>
@@ -225,7 +196,7 @@ void preload_k_g1circ() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_g1_dbl_table<JacS>));
 }
-size_t g1_circ_table_bytes(int n, int T) { return (size_t)n * N_CELLS * 2 * (T + 1) * sizeof(JacQ); }  // + two partial sums per output (sized for the larger point form)
+size_t g1_circ_table_bytes(int n, int T) { return (size_t)n * N_CELLS * 2 * (T + 1) * sizeof(JacS); }  // + two partial sums per output
 template <class Pt>
 static void circ128(Pt* X, int stride, int n, int segs, Pt* D, int T, const uint32_t* terms, int per_lane, typename CircOps<Pt>::Beta bt, hipStream_t st) {
     // one blob: 1.47 -> 1.27 ms per call; from two blobs on the chip is busy enough for the quads' extra instructions to cost more than
@@ -241,12 +212,11 @@ static void circ128(Pt* X, int stride, int n, int segs, Pt* D, int T, const uint
     k_g1_dbl_table<Pt><<<(segs * n * N_CELLS + 63) / 64, 64, 0, st>>>(X, stride, n, segs, D, T, bt);
     k_g1_circ_sum<Pt><<<dim3(N_CELLS, n), CIRC_LANES, 0, st>>>(D, T, terms, per_lane, X, stride);
 }
-// X: [128][stride] MSM outputs (natural order) -> X: proofs (bit-reversed), for blobs 0 .. n-1; fmt: the point form of X (and of D)
-void g1_circ128(void* X, int stride, int n, int segs, void* D, int T, const void* terms, int per_lane, const Fp12w& beta, hipStream_t st, int fmt) {
+// X: [128][stride] MSM outputs (natural order) -> X: proofs (bit-reversed), for blobs 0 .. n-1; X and D hold JacS
+void g1_circ128(void* X, int stride, int n, int segs, void* D, int T, const void* terms, int per_lane, const Fp12w& beta, hipStream_t st) {
     Fp b384;
     for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
-    if (fmt == FMT_JACS) circ128<JacS>((JacS*)X, stride, n, segs, (JacS*)D, T, (const uint32_t*)terms, per_lane, fs_from_fp(b384), st);
-    else circ128<JacQ>((JacQ*)X, stride, n, segs, (JacQ*)D, T, (const uint32_t*)terms, per_lane, fq_from_fp(b384), st);
+    circ128<JacS>((JacS*)X, stride, n, segs, (JacS*)D, T, (const uint32_t*)terms, per_lane, fs_from_fp(b384), st);
 }
 }  // namespace launch
 }  // namespace kzg

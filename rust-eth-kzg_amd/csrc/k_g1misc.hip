@@ -12,12 +12,13 @@
 
 namespace kzg {
 
-// The batched point arrays X[pos * stride + lane] hold JacQ (unsaturated Montgomery-406 coordinates, 168 B).
+// The batched point arrays X[pos * stride + lane] hold JacS (launch::FMT_JACS: the prover, recovery and the commitments) or JacQ
+// (launch::FMT_JACQ, unsaturated Montgomery-406 coordinates, 168 B: the set-up, the stage hooks, verification).
 __global__ void k_g1_set_inf(JacQ* X, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) X[i] = jacq_inf();
 }
-__global__ void k_g1_set_inf_s(JacS* X, size_t n) {  // an array in the signed 13 x 30-bit form (launch::FMT_JACS)
+__global__ void k_g1_set_inf_s(JacS* X, size_t n) {  // an array in the signed 13 x 30-bit form
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) X[i] = jacs_inf();
 }
@@ -86,10 +87,10 @@ __global__ __launch_bounds__(64) void k_g1_compress(const Pt* __restrict__ X, ui
 // A block per slice, a lane per position, a six-level tree through LDS (its idle lanes sharing the additions): the lane-per-slice loop this replaces was a chain of 63
 // dependent additions -- 1.0 ms whatever the batch, two thirds of a single blob's commitment (round 4: 1.59 -> 0.7 ms), and
 // still the longer way at 2048 blobs (32 waves for 1.0 ms against 2048 short ones).  X[slice] (position 0) is read by its own
-// block only, so the sum may land there.
-__device__ __forceinline__ void sum_fold64(JacQ* T, int t) { coop_tree_fold<64>(T, 32, t); }    // four lanes per addition (g1_coop.hpp)
-__device__ __forceinline__ void sum_fold64(JacS* T, int t) { coop4_tree_fold<64>(T, 32, t); }   // ... in the signed field (g1_coop30.hpp)
-__device__ __forceinline__ void set_inf(JacQ& p) { p = jacq_inf(); }
+// block only, so the sum may land there.  X holds JacS: the commitments are the only caller.
+// (A template over the point type with JacS its one instantiation left: as a plain function it compiles to the same instructions
+// with the operands of some integer additions swapped, and removing the 14-digit form was to change no launched kernel at all.)
+__device__ __forceinline__ void sum_fold64(JacS* T, int t) { coop4_tree_fold<64>(T, 32, t); }   // four lanes per addition (g1_coop30.hpp)
 __device__ __forceinline__ void set_inf(JacS& p) { p = jacs_inf(); }
 template <class Pt>
 __global__ __launch_bounds__(64) void k_g1_sum_positions(Pt* __restrict__ X, int n_pos, int stride, int n_slices) {
@@ -323,10 +324,9 @@ void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slice
         else k_g1_compress<1, JacQ><<<g1, 64, 0, st>>>((const JacQ*)X, out, n_pos, stride, n_slices);
     }
 }
-void g1_sum_positions(void* X, int n_pos, int stride, int n_slices, hipStream_t st, int fmt) {
+void g1_sum_positions(void* X, int n_pos, int stride, int n_slices, hipStream_t st) {
     if (n_slices <= 0) return;
-    if (fmt == FMT_JACS) k_g1_sum_positions<JacS><<<n_slices, 64, 0, st>>>((JacS*)X, n_pos, stride, n_slices);
-    else k_g1_sum_positions<JacQ><<<n_slices, 64, 0, st>>>((JacQ*)X, n_pos, stride, n_slices);
+    k_g1_sum_positions<JacS><<<n_slices, 64, 0, st>>>((JacS*)X, n_pos, stride, n_slices);
 }
 void g1_decompress(const uint8_t* in, void* out, int* status, int n, int subgroup_check, const Fp12w& beta, hipStream_t st) {
     Fp b;

@@ -67,9 +67,9 @@ using MsmAcc = XyzzS;
 struct GlvScalar { uint32_t h[2][4]; };
 static_assert(sizeof(GlvScalar) == sizeof(Fr), "split in place");
 
-// Where an MSM's sum goes: out_fmt 0 = the 14 x 29-bit form (JacQ: the circulant form of <= 2 blobs, the commitment fold, the stage
-// hooks), 1 = the signed 13 x 30-bit form as it stands (JacS, 156 B: the G1 linear map computes in it -- k_g1slp.hip -- so nothing is
-// converted between the MSM and the proofs' compression).  `out` then addresses JacS.
+// Where an MSM's sum goes: out_fmt 0 = the 14 x 29-bit form (JacQ: the stage hook, the interpolation MSM of verify_many.hip), 1 = the
+// signed 13 x 30-bit form as it stands (JacS, 156 B: the prover, recovery and the commitments compute in it -- k_g1slp.hip,
+// k_g1circ.hip, k_g1misc.hip -- so nothing is converted between the MSM and the compression).  `out` then addresses JacS.
 __device__ __forceinline__ void store_sum(JacQ* __restrict__ out, size_t idx, const JacS& s, int out_fmt) {
     if (out_fmt) reinterpret_cast<JacS*>(out)[idx] = s;
     else out[idx] = jacq_from_jacs(s);

@@ -9,8 +9,8 @@
 //
 // The pair and quad forms map operation i onto lanes the way their callers do: COOP consecutive lanes per operation, whole
 // 64-lane waves; in the signed field the padding lanes of the last wave repeat the last operation and store nothing
-// (k_slp_mulc_coop_s, k_slp_add_coop_s), in the 14 x 29-bit field whole groups beyond the last operation leave (k_slp_add_coop,
-// k_verify_many.hip).  Every lane of a group writes its own copy of the result, so a lane that ends with a different value shows.
+// (k_slp_mulc_coop_s, k_slp_add_coop_s), in the 14 x 29-bit field whole groups beyond the last operation leave
+// (k_verify_many.hip).  Every lane of a group writes its own copy of the result, so a lane that ends with a different value shows.
 // The tree folds take one block per fold with the callers' block size and first span.
 #include "g1_coop.hpp"
 #include "g1_coop30.hpp"
@@ -193,17 +193,6 @@ OP_HD(jacq_from_jacs, JS, JQ, st_jacq(out, jacq_from_jacs(ld_jacs(in))))
 OP_HD(jacq_add, 2 * JQ + 1, JQ, st_jacq(out, add(ld_jacq(in), ld_jacq(in + JQ), in[2 * JQ] != 0)))
 OP_HD(jacq_add_mixed, JQ + AQ + 1, JQ, st_jacq(out, add_mixed(ld_jacq(in), ld_affq(in + JQ), in[JQ + AQ] != 0)))
 OP_HD(jacq_dbl, JQ, JQ, st_jacq(out, dbl(ld_jacq(in))))
-// sum, difference, degenerate flag (the finish is not for degenerate operands: then only the flag is meaningful)
-OP_HD(jacq_add_sub, 2 * JQ, 2 * JQ + 1, {
-    const AddSubShared sh = add_sub_prepare(ld_jacq(in), ld_jacq(in + JQ));
-    out[2 * JQ] = sh.degenerate ? 1 : 0;
-    if (!sh.degenerate) {
-        st_jacq(out, add_sub_finish(sh, false));
-        st_jacq(out + JQ, add_sub_finish(sh, true));
-    } else {
-        for (int i = 0; i < 2 * JQ; i++) out[i] = 0;
-    }
-})
 #undef OP_HD
 
 // ---- device-only forms: COOP lanes per operation ---------------------------------------------------------------------------
@@ -238,8 +227,6 @@ OP_COOP(coop4_add_sub, 4, 2 * JS, 2 * JS, {
 OP_COOPQ(q_coop_dbl, 4, JQ, JQ, st_jacq(out, coop_dbl(ld_jacq(in), sub)))
 OP_COOPQ(q_coop_add_mixed, 4, JQ + AQ + 1, JQ, st_jacq(out, coop_add_mixed(ld_jacq(in), ld_affq(in + JQ), in[JQ + AQ] != 0, sub)))
 OP_COOPQ(q_coop_add, 4, 2 * JQ + 1, JQ, st_jacq(out, coop_add(ld_jacq(in), ld_jacq(in + JQ), in[2 * JQ] != 0, sub)))
-OP_COOPQ(q_coop2_dbl, 2, JQ, JQ, st_jacq(out, coop2_dbl(ld_jacq(in), sub)))
-OP_COOPQ(q_coop2_add_mixed, 2, JQ + AQ + 1, JQ, st_jacq(out, coop2_add_mixed(ld_jacq(in), ld_affq(in + JQ), in[JQ + AQ] != 0, sub)))
 #undef OP_COOP
 #undef OP_COOPQ
 
@@ -251,11 +238,11 @@ struct FoldOp {
     static constexpr int PW = SIGNED ? JS : JQ;
     static constexpr int IN = 2 * SPAN * PW, OUT = PW, COOP = 0, FOLD = NT;
 };
-using op_fold30_64 = FoldOp<JacS, 64, 32>;     // sum_fold64 (k_g1misc.hip)
+using op_fold30_64 = FoldOp<JacS, 64, 32>;     // k_g1_sum_positions (k_g1misc.hip)
 using op_fold30_256 = FoldOp<JacS, 256, 128>;  // the circulant form's sums (k_g1circ.hip: CIRC_LANES / 2)
-using op_fold29_64 = FoldOp<JacQ, 64, 32>;     // sum_fold64
+using op_fold29_64 = FoldOp<JacQ, 64, 32>;     // one wave: the two-round first level never runs
 using op_fold29_128 = FoldOp<JacQ, 128, 64>;   // k_ps_buckets (PS_LANES / 2)
-using op_fold29_256 = FoldOp<JacQ, 256, 128>;  // the bucket sums of verification (PIP_B / 2), the circulant form (CIRC_LANES / 2)
+using op_fold29_256 = FoldOp<JacQ, 256, 128>;  // the bucket sums of verification (PIP_B / 2)
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------
 template <class O>
@@ -268,7 +255,7 @@ template <class O>
 __global__ __launch_bounds__(64) void k_test_op_coop(const int32_t* __restrict__ in, int32_t* __restrict__ out, int n) {
     constexpr int C = O::COOP;
     const int op_of_thread = blockIdx.x * (64 / C) + (int)threadIdx.x / C, sub = (int)threadIdx.x % C;
-    if (!O::SIGNED && op_of_thread >= n) return;  // whole groups leave (k_slp_add_coop, k_verify_many.hip)
+    if (!O::SIGNED && op_of_thread >= n) return;  // whole groups leave (k_verify_many.hip)
     const bool keep = op_of_thread < n;           // padding lanes repeat the last operation and store nothing (k_slp_add_coop_s)
     const int op = keep ? op_of_thread : n - 1;
     int32_t r[O::OUT / C];
@@ -306,9 +293,9 @@ __global__ __launch_bounds__(NT) void k_test_fold(const int32_t* __restrict__ in
     X(fq_mul) X(fq_mul_wide) X(fq_sqr) X(fq_mul_add) X(fq_is_zero) X(fq_product_is_zero)                                      \
     X(fr_mul) X(fr_reduce_once) X(fr_partial_reduce) X(fr_add) X(fr_sub2r)                                                    \
     X(xyzz_add_mixed) X(xyzz_to_jacs) X(jacs_dbl_half) X(jacs_add_mixed) X(jacs_add) X(jacs_add_sub) X(jacs_dbl)              \
-    X(jacs_apply_phi) X(jacs_from_jacq) X(jacq_from_jacs) X(jacq_add) X(jacq_add_mixed) X(jacq_dbl) X(jacq_add_sub)            \
+    X(jacs_apply_phi) X(jacs_from_jacq) X(jacq_from_jacs) X(jacq_add) X(jacq_add_mixed) X(jacq_dbl)                            \
     X(coop2_dbl_half) X(coop2_add_mixed) X(coop4_dbl_half) X(coop4_dbl_half_phi) X(coop4_add_mixed) X(coop4_add)              \
-    X(coop4_add_sub) X(q_coop_dbl) X(q_coop_add_mixed) X(q_coop_add) X(q_coop2_dbl) X(q_coop2_add_mixed)                                \
+    X(coop4_add_sub) X(q_coop_dbl) X(q_coop_add_mixed) X(q_coop_add)                                                            \
     X(fold30_64) X(fold30_256) X(fold29_64) X(fold29_128) X(fold29_256)
 
 struct OpInfo {

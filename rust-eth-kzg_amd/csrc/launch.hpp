@@ -75,12 +75,13 @@ constexpr size_t glv_entries_per_base(int c, int w0, int w1) {
 constexpr int GLV_WIDTHS[] = {16, 15, 14, 12, 8};  // widest first: the order the engine tries them in
 bool glv_width_supported(int c);
 void glv_split(void* scalars, size_t n, hipStream_t st);
-// Point arrays between the G1 stages come in two formats (FMT_*): the signed 13 x 30-bit form (JacS, 156 B: the MSM sums, the linear
-// map's arena, the circulant form, the commitment's fold and the input of the compression -- one field under the whole prover, recovery
-// and commitment path) and the 14 x 29-bit form (JacQ, 168 B: set-up, verification, the stage hooks, ETH_KZG_AMD_ARENA_SIGNED=0).
+// The prover, recovery and the commitments keep their points in the signed 13 x 30-bit form (JacS, 156 B) from the MSM sums through the
+// linear map's arena, the circulant form and the commitment's fold to the compression: their launchers take JacS and nothing else.
+// Set-up, verification and the stage hooks compute in the 14 x 29-bit form (JacQ, 168 B).  The three launchers both sides share --
+// msm_glv, g1_set_inf, g1_compress -- are told the format of their point array (FMT_*) at every call.
 constexpr int FMT_JACQ = 0, FMT_JACS = 1;
 void msm_glv(int c, int mode, const void* scalars, const TabBlocks& table, void* out /*JacQ or JacS by out_fmt*/, int n_groups, int n_slices, int nb, int out_stride,
-             int brp_bits, const Fp12w& beta, hipStream_t st, int out_fmt = FMT_JACQ);
+             int brp_bits, const Fp12w& beta, hipStream_t st, int out_fmt);
 // k_table.hip
 #ifdef TABS_STRIDE_128
 constexpr size_t SIZEOF_TABP = 128;   // EXPERIMENT: a GLV table entry on a line of its own (curve30.hpp)
@@ -97,19 +98,18 @@ bool build_table_glv(int c, const void* bases, void* const* blocks, void* scratc
 void g1_fft_layer(void* X, int stride, int half, int tw_step, int inverse, int mode, const void* tw, const Fp12w& beta,
                   hipStream_t st);
 
-// k_g1slp.hip: one launch of the straight-line program of the FK20 proofs map (g1_linmap.hpp); kind = linmap::OpKind
+// k_g1slp.hip: one launch of the straight-line program of the FK20 proofs map (g1_linmap.hpp) on an arena of JacS; kind = linmap::OpKind
 void g1_slp_launch(int kind, void* arena, int stride, const uint32_t* words, int count, const void* naf, const Fp12w& beta,
                    hipStream_t st, int lanes = 0 /* lanes to run (a multiple of 64, from the arena pointer on); 0: all `stride` of them */,
                    int coop_lanes = 0 /* > 0: the batch has this many blobs (<= 64): the constant multiplications take four (<= 16) or two lanes per blob */,
-                   int fmt = FMT_JACQ /* the arena's point format; FMT_JACS: the kernels of the signed field */,
                    int n_active = 0 /* blobs that are really there (0: all `lanes`): the padding lanes behind them are skipped */);
 
 // k_g1misc.hip
-void g1_set_inf(void* X, size_t n, hipStream_t st, int fmt = FMT_JACQ);
+void g1_set_inf(void* X, size_t n, hipStream_t st, int fmt);
 int coop_points_max();  // largest launch (points) that takes the four-lanes-per-point kernels (k_g1misc.hip)
 void spin(uint64_t wall_clock_ticks, hipStream_t st);  // one wave, resident for that many ticks of the constant-rate device clock
-void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slices, hipStream_t st, int fmt = FMT_JACQ);
-void g1_sum_positions(void* X, int n_pos, int stride, int n_slices, hipStream_t st, int fmt = FMT_JACQ);
+void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slices, hipStream_t st, int fmt);
+void g1_sum_positions(void* X /*JacS*/, int n_pos, int stride, int n_slices, hipStream_t st);
 // subgroup_check: 0 none, 1 endomorphism test, 2 definitional [r]P == O
 void g1_decompress(const uint8_t* in, void* out /*G1Affine*/, int* status, int n, int subgroup_check, const Fp12w& beta,
                    hipStream_t st);
@@ -131,7 +131,7 @@ constexpr int TWIDDLE_WORDS = 33;   // 132 signed digit bytes per 128-bit half
 // k_g1circ.hip
 constexpr int CIRC_LANES = 256;
 size_t g1_circ_table_bytes(int n, int T);
-void g1_circ128(void* X, int stride, int n, int segs, void* D, int T, const void* terms, int per_lane, const Fp12w& beta, hipStream_t st, int fmt = FMT_JACQ);
+void g1_circ128(void* X /*JacS*/, int stride, int n, int segs, void* D, int T, const void* terms, int per_lane, const Fp12w& beta, hipStream_t st);
 // k_verify.hip
 void init_attributes_verify();
 // slot_of: destination cell slot per input cell (null = identity); status_of: status word per input cell (null = word 0)

@@ -369,7 +369,7 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             } else {
                 launch::vm_mul(d_pts, db + off_s1, db + off_s2, db + off_w, db + off_prod, n, m, beta_, st);
                 // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
-                launch_msm(db + off_isc, TAB_SRS, db + off_icm, 1, Bc, Bc, 0, st);
+                launch_msm(db + off_isc, TAB_SRS, db + off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
                 launch::vm_reduce(db + off_prod, db + off_icm, d_cs, d_rs, db + off_out, n, Bc, st);
             }
             if (folded) {

@@ -21,12 +21,12 @@ static Knobs with(const char* name, const char* value) {
 static bool list_is(const Knobs& k, std::initializer_list<int> want) { return k.devices == std::vector<int>(want); }
 
 int main() {
-    for (const char* v : {"ETH_KZG_AMD_DEVICES", "ETH_KZG_AMD_DEVICE", "ETH_KZG_AMD_TABLE_GB", "ETH_KZG_AMD_DEVICE_BATCH_MAX", "ETH_KZG_AMD_ARENA_SIGNED",
+    for (const char* v : {"ETH_KZG_AMD_DEVICES", "ETH_KZG_AMD_DEVICE", "ETH_KZG_AMD_TABLE_GB", "ETH_KZG_AMD_DEVICE_BATCH_MAX",
                           "ETH_KZG_AMD_FAULT", "ETH_KZG_AMD_GLV_WINDOW", "ETH_KZG_AMD_PROGRESSIVE"})
         unsetenv(v);
     {
         const Knobs k = Knobs::from_env();  // nothing set: the defaults
-        expect(k.devices.empty() && k.device == 0 && k.table_budget_gb == 0 && k.progressive && k.arena_signed && k.fault.empty() &&
+        expect(k.devices.empty() && k.device == 0 && k.table_budget_gb == 0 && k.progressive && k.fault.empty() &&
                k.device_batch_max == 0 && k.glv_window == 0, "defaults");
     }
     expect(list_is(with("ETH_KZG_AMD_DEVICES", "0"), {0}), "one device");
@@ -49,7 +49,6 @@ int main() {
                with("ETH_KZG_AMD_TABLE_GB", "0").table_budget_gb == 0 && with("ETH_KZG_AMD_TABLE_GB", "-3").table_budget_gb == 0 &&
                with("ETH_KZG_AMD_TABLE_GB", "lots").table_budget_gb == 0, "table budget");
     expect(with("ETH_KZG_AMD_DEVICE_BATCH_MAX", "128").device_batch_max == 128 && with("ETH_KZG_AMD_DEVICE_BATCH_MAX", "3").device_batch_max == 0, "device batch bound (>= 64)");
-    expect(!with("ETH_KZG_AMD_ARENA_SIGNED", "0").arena_signed && with("ETH_KZG_AMD_ARENA_SIGNED", "1").arena_signed, "arena format");
     expect(!with("ETH_KZG_AMD_PROGRESSIVE", "0").progressive, "blocking constructor");
     expect(with("ETH_KZG_AMD_GLV_WINDOW", "15").glv_window == 15 && with("ETH_KZG_AMD_GLV_WINDOW", "99").glv_window == 0, "table width");
     {

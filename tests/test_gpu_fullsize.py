@@ -171,70 +171,68 @@ def test_six_thousand_blobs_in_one_device_resident_call(ctx, oracle):
     assert _verify_every_proof(ctx, blobs[3584:4608], cells[3584:4608], proofs[3584:4608]) == [True] * 1024
 
 
-def test_signed_and_unsigned_arena_give_identical_bytes(ctx, oracle, monkeypatch):
-    """Round 6: above the circulant form (> 2 blobs) the G1 linear map's arena holds signed 13 x 30-bit points -- MSM sums (one block
-    per MSM with its quad fold, windowed, chunked), constant multiplications (four, two or one lane per blob), additions / pairs /
-    halved doubling runs (four lanes or one) and the compression's input all in csrc/fp30.hpp, g1_coop30.hpp: no conversions;
-    ETH_KZG_AMD_ARENA_SIGNED=0 keeps the 14 x 29-bit arena and kernels of rounds 2-5.  Same bytes from both, at sizes on both sides
-    of every schedule threshold (flat / windowed / chunked MSM, quad / pair / lane multiplications, the fused-pair schedule of
-    >= 1024 lanes), with degenerate blobs inside -- the zero polynomial, a constant, sparse polynomials (identity operands, equal and
-    opposite points meet the exact slow paths of add, add_sub and their quad forms) -- and through recovery."""
-    monkeypatch.setenv("ETH_KZG_AMD_ARENA_SIGNED", "0")
-    old = kzg.DASContext(use_precomp=True)  # shares ctx's tables; everything of the G1 linear map in the 14-digit field, as in rounds 2-5
-    try:
-        # up to 64 blobs: one lane group -- the several-lanes-per-blob kernels of the two fields (g1_coop30.hpp against g1_coop.hpp)
-        for n in (6, 9, 16, 17, 20, 33, 64, 65, 129, 300, 1100):
-            blobs = _random_blobs(n, 9100 + n)
-            blobs[1] = 0
-            blobs[2] = np.frombuffer((b"\x00" * 31 + b"\x05") * 4096, dtype=np.uint8).reshape(4096, 32)
-            blobs[3] = np.frombuffer(_blob_from_coefficients([0] * 4095 + [11]), dtype=np.uint8).reshape(4096, 32)
-            blobs[n // 2] = np.frombuffer(_blob_from_coefficients([3] + [0] * 63 + [9] + [0] * 4031), dtype=np.uint8).reshape(4096, 32)
-            blobs[n - 1] = np.frombuffer(synth.dummy_blob(), dtype=np.uint8).reshape(4096, 32)
-            a, b = _compute_on_device(ctx, blobs), _compute_on_device(old, blobs)
-            assert a[0] == b[0] == [0] * n
-            assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), n
-            _check_sample_against_oracle(oracle, blobs, a[1], a[2], [0, 1, 2, 3, n // 2, n - 1])
-        # one and two blobs: the circulant form (k_g1circ.hip) on both point forms, the one-block MSM with its quad fold before it
-        for n in (1, 2):
-            for kind in ("random", "degenerate"):
-                blobs = _random_blobs(n, 9300 + n)
-                if kind == "degenerate":
-                    blobs[0] = np.frombuffer(_blob_from_coefficients([0] * 64 + [1] + [0] * 4031), dtype=np.uint8).reshape(4096, 32)
-                    blobs[n - 1] = 0 if n == 1 else np.frombuffer((b"\x00" * 31 + b"\x05") * 4096, dtype=np.uint8).reshape(4096, 32)
-                a, b = _compute_on_device(ctx, blobs), _compute_on_device(old, blobs)
-                assert a[0] == b[0] == [0] * n
-                assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), (n, kind)
-                _check_sample_against_oracle(oracle, blobs, a[1], a[2], list(range(n)))
-        # commitments (MSM on the commitment table, fold over the 64 groups, compression) and the EIP-4844 proof, which is the same path
-        for n in (1, 3, 70):
-            cb = [bytes(x.tobytes()) for x in _random_blobs(n, 9400 + n)]
-            cb[0] = bytes(131072)
-            cb[n - 1] = synth.dummy_blob()
-            ca, co = ctx.blob_to_kzg_commitment_batch(cb), old.blob_to_kzg_commitment_batch(cb)
-            assert ca == co and ca[0] == [0] * n, n
-            assert ca[1][n - 1] == oracle.blob_to_kzg_commitment(cb[n - 1]) and (n == 1 or ca[1][0] == b"\xc0" + bytes(47))
-        z = (12345).to_bytes(32, "big")
-        pr = ctx.compute_kzg_proof(cb[1], z)  # (the EIP-4844 vectors pin it; here: the same bytes from both point forms, and it verifies)
-        assert pr == old.compute_kzg_proof(cb[1], z) and ctx.verify_kzg_proof(ca[1][1], z, pr[1], pr[0]) is True
-        # recovery of 80 half-erased blobs runs the same map from coefficients
-        import torch
-        n = 80
-        blobs = _random_blobs(n, 9200)
+def test_one_point_form_through_every_schedule_threshold(ctx, oracle):
+    """The prover's, recovery's and the commitments' G1 points are signed 13 x 30-bit points from the MSM sums -- one block per MSM with
+    its quad fold, windowed, chunked -- through the constant multiplications (four, two or one lane per blob), the additions / pairs /
+    halved doubling runs (four lanes or one) or the circulant form, to the compression's input (csrc/fp30.hpp, g1_coop30.hpp).  Sizes
+    on both sides of every schedule threshold (flat / windowed / chunked MSM, circulant form / compiled map, quad / pair / lane
+    multiplications, the fused-pair schedule of >= 1024 lanes), with degenerate blobs inside -- the zero polynomial, a constant, sparse
+    polynomials (identity operands, equal and opposite points meet the exact slow paths of add, add_sub and their quad forms) -- and
+    through recovery.  EVERY proof of every blob is verified against its cell and commitment by the verifier, which computes in the
+    other field (csrc/fp29.hpp): a proof is the canonical encoding of a unique group element, so a proof that verifies is the right
+    bytes.  Cells 0-63 are the blob; a sample goes against the oracle byte for byte; every commitment and the EIP-4844 (proof, y) too
+    (the oracle exposes compute_kzg_proof)."""
+    def check(blobs, sample):
+        n = blobs.shape[0]
         st, cells, proofs = _compute_on_device(ctx, blobs)
-        ext = torch.from_numpy(np.ascontiguousarray(cells)).cuda().view(n, 128, 2048).clone()
-        ext[:, 1::2, :] = 0xEE
-        outs = []
-        for c in (ctx, old):
-            d_c = torch.zeros(n * 128 * 2048, dtype=torch.uint8, device="cuda")
-            d_p = torch.zeros(n * 128 * 48, dtype=torch.uint8, device="cuda")
-            st = c.recover_cells_and_kzg_proofs_device(n, ext.data_ptr(), [list(range(0, 128, 2))] * n, d_c.data_ptr(), d_p.data_ptr())
-            torch.cuda.synchronize()
-            assert st == [0] * n
-            outs.append((d_c.cpu().numpy().reshape(n, -1), d_p.cpu().numpy().reshape(n, -1)))
-        assert np.array_equal(outs[0][0], cells) and np.array_equal(outs[0][1], proofs)
-        assert np.array_equal(outs[1][0], cells) and np.array_equal(outs[1][1], proofs)
-    finally:
-        old.close()
+        assert st == [0] * n
+        assert np.array_equal(cells[:, :131072], blobs.reshape(n, 131072)), "cells 0..63 must be the blob itself"
+        assert _verify_every_proof(ctx, blobs, cells, proofs) == [True] * n, n
+        _check_sample_against_oracle(oracle, blobs, cells, proofs, sample)
+    # up to 64 blobs: one lane group -- the several-lanes-per-blob kernels (g1_coop30.hpp)
+    for n in (6, 9, 16, 17, 20, 33, 64, 65, 129, 300, 1100):
+        blobs = _random_blobs(n, 9100 + n)
+        blobs[1] = 0
+        blobs[2] = np.frombuffer((b"\x00" * 31 + b"\x05") * 4096, dtype=np.uint8).reshape(4096, 32)
+        blobs[3] = np.frombuffer(_blob_from_coefficients([0] * 4095 + [11]), dtype=np.uint8).reshape(4096, 32)
+        blobs[n // 2] = np.frombuffer(_blob_from_coefficients([3] + [0] * 63 + [9] + [0] * 4031), dtype=np.uint8).reshape(4096, 32)
+        blobs[n - 1] = np.frombuffer(synth.dummy_blob(), dtype=np.uint8).reshape(4096, 32)
+        check(blobs, [0, 1, 2, 3, n // 2, n - 1])
+    # one and two blobs: the circulant form (k_g1circ.hip), the one-block MSM with its quad fold before it
+    for n in (1, 2):
+        for kind in ("random", "degenerate"):
+            blobs = _random_blobs(n, 9300 + n)
+            if kind == "degenerate":
+                blobs[0] = np.frombuffer(_blob_from_coefficients([0] * 64 + [1] + [0] * 4031), dtype=np.uint8).reshape(4096, 32)
+                blobs[n - 1] = 0 if n == 1 else np.frombuffer((b"\x00" * 31 + b"\x05") * 4096, dtype=np.uint8).reshape(4096, 32)
+            check(blobs, list(range(n)))
+    # commitments (MSM on the commitment table, fold over the 64 groups, compression) and the EIP-4844 proof, which is the same path
+    for n in (1, 3, 70):
+        cb = [bytes(x.tobytes()) for x in _random_blobs(n, 9400 + n)]
+        cb[0] = bytes(131072)
+        cb[n - 1] = synth.dummy_blob()
+        ca = ctx.blob_to_kzg_commitment_batch(cb)
+        assert ca[0] == [0] * n, n
+        for b in range(n):
+            assert ca[1][b] == oracle.blob_to_kzg_commitment(cb[b]), (n, b)
+        assert n == 1 or ca[1][0] == b"\xc0" + bytes(47)
+    z = (12345).to_bytes(32, "big")
+    pr = ctx.compute_kzg_proof(cb[1], z)  # (proof, y): the oracle's bytes (the EIP-4844 vectors pin it too), and it verifies
+    assert tuple(pr) == oracle.compute_kzg_proof(cb[1], z)
+    assert ctx.verify_kzg_proof(ca[1][1], z, pr[1], pr[0]) is True
+    # recovery of 80 half-erased blobs runs the same map from coefficients
+    import torch
+    n = 80
+    blobs = _random_blobs(n, 9200)
+    st, cells, proofs = _compute_on_device(ctx, blobs)
+    ext = torch.from_numpy(np.ascontiguousarray(cells)).cuda().view(n, 128, 2048).clone()
+    ext[:, 1::2, :] = 0xEE
+    d_c = torch.zeros(n * 128 * 2048, dtype=torch.uint8, device="cuda")
+    d_p = torch.zeros(n * 128 * 48, dtype=torch.uint8, device="cuda")
+    st = ctx.recover_cells_and_kzg_proofs_device(n, ext.data_ptr(), [list(range(0, 128, 2))] * n, d_c.data_ptr(), d_p.data_ptr())
+    torch.cuda.synchronize()
+    assert st == [0] * n
+    assert np.array_equal(d_c.cpu().numpy().reshape(n, -1), cells) and np.array_equal(d_p.cpu().numpy().reshape(n, -1), proofs)
 
 
 def test_compute_512_through_the_host_batch_abi(ctx, oracle):

@@ -444,7 +444,7 @@ def test_every_batch_size_regime_matches_oracle(ctx, oracle, n):
     number of 64-blob lane groups: 712 constant multiplications for one group, 456 for two, 606 for three, 456 for four, 372 for
     five, the 350 of the operation-count optimum from six; inside one lane group the map's constant multiplications take four
     lanes per blob up to 16 blobs, two from 17 to 64 -- and from 33 the 456-multiplication compilation, two waves each -- and its
-    cheap levels four (g1_coop.hpp); one blob takes the four-lanes-per-chain circulant kernels;
+    cheap levels four (g1_coop30.hpp); one blob takes the four-lanes-per-chain circulant kernels;
     MSM: flat <= 8 (and for a small overflow beyond one round of wave slots), windowed below 256 blobs, chunked above).  Every regime and both sides of every threshold
     must give the oracle's bytes; blobs not checked against the oracle are checked against the single-blob path."""
     import numpy as np
