@@ -279,6 +279,47 @@ CResult eth_kzg_amd_compute_cells_and_kzg_proofs_device(const DASContext *ctx, u
 CResult eth_kzg_amd_blob_to_kzg_commitment_device(const DASContext *ctx, uint64_t n, const uint8_t *d_blobs,
                                                   uint8_t *d_out, int32_t *status, void *hip_stream);
 
+/* The EIP-4844 proofs for MANY blobs in one call -- the throughput forms of eth_kzg_compute_kzg_proof and
+ * eth_kzg_compute_blob_kzg_proof (bindings/c/src/lib.rs:423-480 -> crates/eip4844/src/prover.rs:37-92), which prove one blob per call
+ * with an upload, a launch set and a synchronisation each.  Per blob they compute what the single calls compute, byte for byte.
+ * status[b] follows the single call's order of checks: 1 = the blob holds a field element >= r, else 1 = z is not canonical
+ * (compute_kzg_proof) or 2 = the commitment is not a valid point of the subgroup (compute_blob_kzg_proof; it is only validated,
+ * prover.rs:73-75), else 0.  The outputs of a blob whose status is not 0 are unspecified (host forms: left untouched).
+ *
+ * Host-pointer forms: n pointers each -- blobs[b] 131072 bytes, commitments[b] / out_proofs[b] 48, zs[b] / out_ys[b] 32 (big-endian,
+ * as in the single call).  The blobs are gathered into pinned memory and the Fiat-Shamir challenges
+ * z_b = H("FSBLOBVERIFY_V1_" | 4096 | blob_b | commitment_b) (crates/eip4844/src/verifier.rs:155-196) hashed by host threads in
+ * parallel (the bytes are on the host already), then every 256 blobs are one upload and one set of launches.  status may be NULL. */
+CResult eth_kzg_amd_compute_blob_kzg_proof_batch(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs,
+                                                 const uint8_t *const *commitments, uint8_t *const *out_proofs,
+                                                 int32_t *status);
+CResult eth_kzg_amd_compute_kzg_proof_batch(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs,
+                                            const uint8_t *const *zs, uint8_t *const *out_proofs, uint8_t *const *out_ys,
+                                            int32_t *status);
+/* Device-resident forms: flat arrays in this GPU's HBM -- d_blobs n * 131072 bytes, d_commitments / d_out_proofs n * 48, d_zs /
+ * d_out_ys n * 32 big-endian (4-byte aligned) -- for pipelines that already hold their blobs there (commitments from
+ * eth_kzg_amd_blob_to_kzg_commitment_device): nothing but the status words crosses the link.  The challenges of the blob proofs
+ * are hashed ON THE GPU, one lane per blob (csrc/k_sha256.hip): the 131 KB of a blob do not come down for a 32-byte answer.  That
+ * hash is serial inside a blob and takes a few milliseconds whatever n is: for a handful of blobs the
+ * host-pointer form or the single call is the faster one.  status, hip_stream, ordering behind the caller's queued work and
+ * asynchronous use exactly as eth_kzg_amd_blob_to_kzg_commitment_device above (status NULL and a stream given: the call returns
+ * without synchronising). */
+CResult eth_kzg_amd_compute_blob_kzg_proof_device(const DASContext *ctx, uint64_t n, const uint8_t *d_blobs,
+                                                  const uint8_t *d_commitments, uint8_t *d_out_proofs, int32_t *status,
+                                                  void *hip_stream);
+CResult eth_kzg_amd_compute_kzg_proof_device(const DASContext *ctx, uint64_t n, const uint8_t *d_blobs, const uint8_t *d_zs,
+                                             uint8_t *d_out_proofs, uint8_t *d_out_ys, int32_t *status, void *hip_stream);
+/* eth_kzg_verify_blob_kzg_proof_batch (bindings/c/src/lib.rs:530-566 -> crates/eip4844/src/verifier.rs:80-196) on flat arrays in this
+ * GPU's HBM: n * 131072 blob bytes, n * 48 commitment bytes, n * 48 proof bytes.  Challenges (GPU hash) and evaluations y_b are
+ * computed where the blobs lie, commitments and proofs are decompressed in place; the n * (48 + 32 + 32 + 48) bytes of the
+ * "RCKZGBATCH___V1_" transcript come down and the weight r is hashed on the host (one short serial message), then the two bucket
+ * MSMs and the pairing check as in the host form.  Synchronous; work already queued on `hip_stream` (NULL: the default stream)
+ * that produces the inputs is waited for.  Verdict and errors as the host form: Err for a non-canonical blob element, else a bad
+ * commitment, else a bad proof; n = 0 verifies.  ONE random linear combination over the whole batch: never cut over a device list. */
+CResult eth_kzg_amd_verify_blob_kzg_proof_batch_device(const DASContext *ctx, uint64_t n, const uint8_t *d_blobs,
+                                                       const uint8_t *d_commitments, const uint8_t *d_proofs, bool *verified,
+                                                       void *hip_stream);
+
 /* verify_cell_kzg_proof_batch on flat arrays in this GPU's HBM: n * 48 commitment bytes (one per cell, NOT deduplicated, as in
  * the host form), n indices, n * 2048 cell bytes, n * 48 proof bytes.  The GPU's part reads cells and proofs where they are;
  * the transcript hash runs on a host core, so its bytes come down (in chunks, under the hash) and the call is synchronous;

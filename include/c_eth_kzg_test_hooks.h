@@ -16,6 +16,13 @@ int eth_kzg_amd_test_g1_decompress(const DASContext *ctx, const uint8_t *in, int
 int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const uint8_t *b, uint8_t *out, int n,
                                int is_fp);
 
+/* The many-message SHA-256 kernel (csrc/k_sha256.hip) on its own: n messages, message i = prefix[prefix_len] (HOST memory) |
+ * (d_body + i * body_stride)[body_len] | (d_tail + i * tail_stride)[tail_len] (device memory; a part of length 0 may be NULL), digest i
+ * -> d_out + 32 i (device).  Synchronous; returns 0 on success. */
+int eth_kzg_amd_test_sha256_many(const DASContext *ctx, uint64_t n, const uint8_t *prefix, uint64_t prefix_len, const uint8_t *d_body,
+                                 uint64_t body_stride, uint64_t body_len, const uint8_t *d_tail, uint64_t tail_stride, uint64_t tail_len,
+                                 uint8_t *d_out);
+
 /* One field or point operation of the kernels per element (csrc/k_test_ops.hip), on the raw words of the device structs.
  * eth_kzg_amd_test_op_info: word counts per element of operation `op` (0, 1, ... until it returns -1), whether it exists on the
  * device only (the pair / quad forms, the tree folds) and its name.  eth_kzg_amd_test_op: n elements of in_words each in, n of

@@ -62,6 +62,9 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_cell_kzg_proof_batch_partial", "eth_kzg_amd_verify_cell_kzg_proof_batch_combine",
     "eth_kzg_amd_compute_cells_and_kzg_proofs_device", "eth_kzg_amd_blob_to_kzg_commitment_device",
     "eth_kzg_amd_verify_cell_kzg_proof_batch_device", "eth_kzg_amd_verify_cell_kzg_proof_batch_many",
+    "eth_kzg_amd_compute_blob_kzg_proof_batch", "eth_kzg_amd_compute_kzg_proof_batch",
+    "eth_kzg_amd_compute_blob_kzg_proof_device", "eth_kzg_amd_compute_kzg_proof_device",
+    "eth_kzg_amd_verify_blob_kzg_proof_batch_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
     "eth_kzg_amd_set_profiling", "eth_kzg_amd_get_stage_times",
     "eth_kzg_amd_comm_probe", "eth_kzg_amd_comm_unique_id", "eth_kzg_amd_comm_init", "eth_kzg_amd_comm_info",
@@ -73,6 +76,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_fr_ntt4096", "eth_kzg_amd_test_g1_fft128", "eth_kzg_amd_test_fixed_msm",
     "eth_kzg_amd_test_g1_decompress", "eth_kzg_amd_test_field_mul", "eth_kzg_amd_test_op_info", "eth_kzg_amd_test_op",
     "eth_kzg_amd_test_table_info", "eth_kzg_amd_test_table_audit", "eth_kzg_amd_test_table_read", "eth_kzg_amd_test_table_audit_buffer",
+    "eth_kzg_amd_test_sha256_many",
 ]
 
 _lib = None
@@ -119,6 +123,11 @@ def load_library():
         "eth_kzg_amd_blob_to_kzg_commitment_device": [P, U64, P, P, P, P],
         "eth_kzg_amd_verify_cell_kzg_proof_batch_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_verify_cell_kzg_proof_batch_many": [P, U64, P, P, P, P, P, P, P, P, P, P],
+        "eth_kzg_amd_compute_blob_kzg_proof_batch": [P, U64, P, P, P, P],
+        "eth_kzg_amd_compute_kzg_proof_batch": [P, U64, P, P, P, P, P],
+        "eth_kzg_amd_compute_blob_kzg_proof_device": [P, U64, P, P, P, P, P],
+        "eth_kzg_amd_compute_kzg_proof_device": [P, U64, P, P, P, P, P, P],
+        "eth_kzg_amd_verify_blob_kzg_proof_batch_device": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_comm_unique_id": [P],
         "eth_kzg_amd_comm_probe": [P, P, U64],
         "eth_kzg_amd_comm_info": [P, P, P],
@@ -177,6 +186,7 @@ def load_library():
         "eth_kzg_amd_test_table_audit": [P, C.c_int, C.c_int, P, P, P, C.c_int, P],
         "eth_kzg_amd_test_table_read": [P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P],
         "eth_kzg_amd_test_table_audit_buffer": [P, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P, P, C.c_int],
+        "eth_kzg_amd_test_sha256_many": [P, U64, P, U64, P, U64, U64, P, U64, U64, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -741,6 +751,64 @@ class DASContext:
         self._check(self._lib.eth_kzg_amd_blob_to_kzg_commitment_device(
             self._ctx, n, C.c_void_p(d_blobs), C.c_void_p(d_out), st, C.c_void_p(stream) if stream else None))
         return list(st)[:n] if want_status else None
+
+    # ---- EIP-4844 proofs for many blobs (eth_kzg_amd_compute_*_kzg_proof_batch / _device) ----
+    def compute_blob_kzg_proof_batch(self, blobs, commitments):
+        """Lists of blobs and commitments -> (status list, proofs): compute_blob_kzg_proof for every pair in one call.  status[b]: 0 ok,
+        1 the blob holds a non-canonical field element, 2 the commitment is not a valid point (the proof of such a blob is 48 zero bytes)."""
+        n = len(blobs)
+        if len(commitments) != n or any(len(b) != BYTES_PER_BLOB for b in blobs) or any(len(c) != 48 for c in commitments):
+            raise KzgError("InvalidLength")
+        ba, _kb = _flat_ptrs(blobs, BYTES_PER_BLOB)
+        ca, _kc = _flat_ptrs(commitments, 48)
+        out = np.zeros(max(1, n) * 48, dtype=np.uint8)
+        oa = np.uint64(out.ctypes.data) + np.arange(max(1, n), dtype=np.uint64) * np.uint64(48)
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_compute_blob_kzg_proof_batch(self._ctx, n, _vp(ba), _vp(ca), _vp(oa), st))
+        raw = out.tobytes()
+        return list(st)[:n], [raw[48 * b:48 * b + 48] for b in range(n)]
+
+    def compute_kzg_proof_batch(self, blobs, zs):
+        """Lists of blobs and 32-byte evaluation points -> (status list, proofs, ys): compute_kzg_proof for every pair in one call.
+        status[b]: 0 ok, 1 the blob or z holds a non-canonical field element (outputs of such a blob are zero bytes)."""
+        n = len(blobs)
+        if len(zs) != n or any(len(b) != BYTES_PER_BLOB for b in blobs) or any(len(z) != 32 for z in zs):
+            raise KzgError("InvalidLength")
+        ba, _kb = _flat_ptrs(blobs, BYTES_PER_BLOB)
+        za, _kz = _flat_ptrs(zs, 32)
+        proofs, ys = np.zeros(max(1, n) * 48, dtype=np.uint8), np.zeros(max(1, n) * 32, dtype=np.uint8)
+        pa = np.uint64(proofs.ctypes.data) + np.arange(max(1, n), dtype=np.uint64) * np.uint64(48)
+        ya = np.uint64(ys.ctypes.data) + np.arange(max(1, n), dtype=np.uint64) * np.uint64(32)
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_compute_kzg_proof_batch(self._ctx, n, _vp(ba), _vp(za), _vp(pa), _vp(ya), st))
+        rp, ry = proofs.tobytes(), ys.tobytes()
+        return list(st)[:n], [rp[48 * b:48 * b + 48] for b in range(n)], [ry[32 * b:32 * b + 32] for b in range(n)]
+
+    def compute_blob_kzg_proof_device(self, n, d_blobs, d_commitments, d_out_proofs, want_status=True, stream=None):
+        """Device-resident flat buffers (integer device addresses): n * 131072 blob bytes, n * 48 commitment bytes -> n * 48 proof
+        bytes; the Fiat-Shamir challenges are hashed on the GPU.  Returns the status list (None with want_status=False: then, with
+        a stream, the call does not synchronise)."""
+        st = (C.c_int32 * max(1, n))() if want_status else None
+        self._check(self._lib.eth_kzg_amd_compute_blob_kzg_proof_device(
+            self._ctx, n, C.c_void_p(d_blobs), C.c_void_p(d_commitments), C.c_void_p(d_out_proofs), st, C.c_void_p(stream) if stream else None))
+        return list(st)[:n] if want_status else None
+
+    def compute_kzg_proof_device(self, n, d_blobs, d_zs, d_out_proofs, d_out_ys, want_status=True, stream=None):
+        """Device-resident compute_kzg_proof: n * 32 big-endian z bytes in, n * 48 proof and n * 32 y bytes out."""
+        st = (C.c_int32 * max(1, n))() if want_status else None
+        self._check(self._lib.eth_kzg_amd_compute_kzg_proof_device(
+            self._ctx, n, C.c_void_p(d_blobs), C.c_void_p(d_zs), C.c_void_p(d_out_proofs), C.c_void_p(d_out_ys), st,
+            C.c_void_p(stream) if stream else None))
+        return list(st)[:n] if want_status else None
+
+    def verify_blob_kzg_proof_batch_device(self, n, d_blobs, d_commitments, d_proofs, stream=None):
+        """verify_blob_kzg_proof_batch on flat arrays in HBM (integer device addresses); synchronous.  Raises KzgError for
+        malformed input, as the host form."""
+        ok = C.c_bool(False)
+        self._check(self._lib.eth_kzg_amd_verify_blob_kzg_proof_batch_device(
+            self._ctx, int(n), C.c_void_p(d_blobs), C.c_void_p(d_commitments), C.c_void_p(d_proofs), C.byref(ok),
+            C.c_void_p(stream) if stream else None))
+        return bool(ok.value)
 
     STAGES = ["blob_to_coeffs", "coeffs_to_cells", "fk20_scalars", "msm_fixed", "g1_ifft", "g1_fft", "compress", "g1_linmap"]
 

@@ -549,6 +549,92 @@ CResult eth_kzg_amd_blob_to_kzg_commitment_device(const DASContext* ctx, uint64_
     if (status) for (uint64_t i = 0; i < n; i++) status[i] = status[i] ? kzg::ERR_SCALAR : 0;
     return ok();
 }
+// ---------------------------------------------------------------------------------------------
+// EIP-4844 proofs for many blobs (eip4844.hip).  Host-pointer forms: contiguous slices over the device list; device-resident forms:
+// the engine that owns d_blobs; the device verifier is ONE random combination over the whole batch and is never cut.
+CResult eth_kzg_amd_compute_blob_kzg_proof_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* commitments,
+                                                 uint8_t* const* out_proofs, int32_t* status) {
+    if (n > MAX_BATCH) return err("InvalidInput");
+    live(ctx);
+    if (n == 0) return ok();
+    if (!blobs || !commitments || !out_proofs) return err("InvalidInput");
+    try {
+        std::vector<int> st(n);
+        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
+            auto lane = ctx->engines[(size_t)d]->lease_serial();
+            kzg::Engine* e = lane.e;
+            return e->compute_blob_kzg_proof_batch_host((int)(hi - lo), blobs + lo, commitments + lo, out_proofs + lo, st.data() + lo) ? device_text(e)
+                                                                                                                                     : std::string();
+        });
+        if (r.first >= 0) return slices_result(ctx, r);
+        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
+        return ok();
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+CResult eth_kzg_amd_compute_kzg_proof_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* zs,
+                                            uint8_t* const* out_proofs, uint8_t* const* out_ys, int32_t* status) {
+    if (n > MAX_BATCH) return err("InvalidInput");
+    live(ctx);
+    if (n == 0) return ok();
+    if (!blobs || !zs || !out_proofs || !out_ys) return err("InvalidInput");
+    try {
+        std::vector<int> st(n);
+        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
+            auto lane = ctx->engines[(size_t)d]->lease_serial();
+            kzg::Engine* e = lane.e;
+            return e->compute_kzg_proof_batch_host((int)(hi - lo), blobs + lo, zs + lo, out_proofs + lo, out_ys + lo, st.data() + lo) ? device_text(e)
+                                                                                                                                      : std::string();
+        });
+        if (r.first >= 0) return slices_result(ctx, r);
+        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
+        return ok();
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+CResult eth_kzg_amd_compute_blob_kzg_proof_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments,
+                                                  uint8_t* d_out_proofs, int32_t* status, void* hip_stream) {
+    if (n > MAX_BATCH) return err("InvalidInput");
+    kzg::Engine* owner = engine_of_pointer(ctx, d_blobs);
+    if (!owner) return err("InvalidInput: the buffers are on no device of this context");
+    if (n == 0) return ok();
+    if (!d_blobs || !d_commitments || !d_out_proofs) return err("InvalidInput");
+    auto lane = owner->lease_serial();
+    kzg::Engine* e = lane.e;
+    static_assert(sizeof(int32_t) == sizeof(int), "status array");
+    const bool sync = hip_stream == nullptr;
+    if (e->compute_blob_kzg_proof_device((int)n, d_blobs, d_commitments, d_out_proofs, (int*)status, (hipStream_t)hip_stream, sync)) return device_err(e);
+    return ok();
+}
+CResult eth_kzg_amd_compute_kzg_proof_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_zs, uint8_t* d_out_proofs,
+                                             uint8_t* d_out_ys, int32_t* status, void* hip_stream) {
+    if (n > MAX_BATCH) return err("InvalidInput");
+    kzg::Engine* owner = engine_of_pointer(ctx, d_blobs);
+    if (!owner) return err("InvalidInput: the buffers are on no device of this context");
+    if (n == 0) return ok();
+    if (!d_blobs || !d_zs || !d_out_proofs || !d_out_ys) return err("InvalidInput");
+    auto lane = owner->lease_serial();
+    kzg::Engine* e = lane.e;
+    const bool sync = hip_stream == nullptr;
+    if (e->compute_kzg_proof_device((int)n, d_blobs, d_zs, d_out_proofs, d_out_ys, (int*)status, (hipStream_t)hip_stream, sync)) return device_err(e);
+    return ok();
+}
+CResult eth_kzg_amd_verify_blob_kzg_proof_batch_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments,
+                                                       const uint8_t* d_proofs, bool* verified, void* hip_stream) {
+    if (n > MAX_BATCH) return err("InvalidInput");
+    kzg::Engine* owner = engine_of_pointer(ctx, d_blobs);
+    if (!owner) return err("InvalidInput: the buffers are on no device of this context");
+    if (n == 0) { *verified = true; return ok(); }
+    if (!d_blobs || !d_commitments || !d_proofs) return err("InvalidInput");
+    auto lane = owner->lease_serial();
+    kzg::Engine* e = lane.e;
+    int ver = 0;
+    const int st = e->verify_blob_kzg_proof_batch_device(n, d_blobs, d_commitments, d_proofs, &ver, (hipStream_t)hip_stream);
+    if (!st) *verified = ver != 0;
+    return finish(e, st);
+}
 void eth_kzg_amd_set_profiling(const DASContext* ctx, int on) { eng(ctx)->set_profiling(on != 0); }
 int eth_kzg_amd_get_stage_times(const DASContext* ctx, double* ms, uint64_t* launches, int n) {
     double m[kzg::Engine::ST_COUNT];

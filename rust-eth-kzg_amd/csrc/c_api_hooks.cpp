@@ -39,6 +39,13 @@ int eth_kzg_amd_test_g1_decompress(const DASContext* ctx, const uint8_t* in, int
 int eth_kzg_amd_test_field_mul(const DASContext* ctx, const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp) {
     return eng(ctx)->test_field_mul(a, b, out, n, is_fp);
 }
+int eth_kzg_amd_test_sha256_many(const DASContext* ctx, uint64_t n, const uint8_t* prefix, uint64_t prefix_len, const uint8_t* d_body,
+                                 uint64_t body_stride, uint64_t body_len, const uint8_t* d_tail, uint64_t tail_stride, uint64_t tail_len,
+                                 uint8_t* d_out) {
+    if (n > (1u << 24) || (prefix_len | body_len | tail_len) >> 31) return kzg::ERR_INPUT;
+    return eng(ctx)->test_sha256_many((int)n, prefix, (uint32_t)prefix_len, d_body, body_stride, (uint32_t)body_len, d_tail, tail_stride,
+                                      (uint32_t)tail_len, d_out);
+}
 int eth_kzg_amd_test_op_info(int op, int32_t* in_words, int32_t* out_words, int32_t* device_only, const char** name) {
     int i, o, d;
     const char* nm;

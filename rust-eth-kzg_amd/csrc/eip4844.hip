@@ -11,9 +11,11 @@
 #include "launch.hpp"
 #include "sha256.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace kzg {
 
@@ -76,28 +78,34 @@ static Fr fs_challenge(const uint8_t* blob, const uint8_t* commitment) {
     return reduce_be32_4844(dig);
 }
 
-// blobs -> (status, y_i canonical, optionally proof_i = commit(quotient_i)); z_i Montgomery.
-// Shared by compute_kzg_proof / compute_blob_kzg_proof (want_proofs) and the blob verifiers (y only).
-int Engine::open_blobs_at(int n, const uint8_t* const* blobs, const Fr8* z_mont, bool want_proofs, uint8_t* h_proofs,
-                          Fr8* h_y_canon, int* h_status) {
-    hipStream_t st = stream_;
-    ensure_workspace(n);
+// The device-resident core of every opening: blobs and Montgomery z_i in HBM -> y_i canonical and, if asked for, proof_i =
+// commit(quotient_i), left on the device; per-blob status words in d_status_ (non-zero: a non-canonical element).
+void Engine::open_blobs_core(int n, const uint8_t* d_blobs, const void* d_z_mont, void* d_y, uint8_t* d_proofs, hipStream_t st) {
     const int bp = ((n + 63) / 64) * 64;
-    PoolBuf d_blobs(*this, (size_t)n * BYTES_PER_BLOB), d_z(*this, (size_t)n * 32), d_y(*this, (size_t)n * 32), d_pr(*this, (size_t)n * 48);
-    for (int b = 0; b < n; b++)
-        HIPCK(hipMemcpyAsync((uint8_t*)d_blobs.p + (size_t)b * BYTES_PER_BLOB, blobs[b], BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
-    HIPCK(hipMemcpyAsync(d_z.p, z_mont, (size_t)n * 32, hipMemcpyHostToDevice, st));
     HIPCK(hipMemsetAsync(d_status_, 0, n * sizeof(int), st));
-    launch::blob_to_coeffs(n, (const uint8_t*)d_blobs.p, d_coeffs_, nullptr, d_status_, d_w29_, n_inv4096_, st);
-    launch::quotient_by_linear(n, d_coeffs_, d_z.p, d_canon_, d_y.p, st);
-    if (want_proofs) {
+    launch::blob_to_coeffs(n, d_blobs, d_coeffs_, nullptr, d_status_, d_w29_, n_inv4096_, st);
+    launch::quotient_by_linear(n, d_coeffs_, d_z_mont, d_canon_, d_y, st);
+    if (d_proofs) {
         // proof = g1_lincomb(g1s[..4095], quotient) (kzg_single_open/src/prover.rs:40-43): the commitment MSM path
         launch::g1_set_inf(d_X_, (size_t)64 * bp, st, launch::FMT_JACS);
         launch_msm(d_canon_, TAB_SRS, d_X_, 64, n, bp, 0, st, launch::FMT_JACS);
         launch::g1_sum_positions(d_X_, 64, bp, n, st);
-        launch::g1_compress(d_X_, (uint8_t*)d_pr.p, 1, bp, n, st, launch::FMT_JACS);
-        HIPCK(hipMemcpyAsync(h_proofs, d_pr.p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+        launch::g1_compress(d_X_, d_proofs, 1, bp, n, st, launch::FMT_JACS);
     }
+}
+
+// blobs -> (status, y_i canonical, optionally proof_i = commit(quotient_i)); z_i Montgomery.  The upload step in front of the core
+// and the download behind it: shared by compute_kzg_proof / compute_blob_kzg_proof (want_proofs) and the blob verifiers (y only).
+int Engine::open_blobs_at(int n, const uint8_t* const* blobs, const Fr8* z_mont, bool want_proofs, uint8_t* h_proofs,
+                          Fr8* h_y_canon, int* h_status) {
+    hipStream_t st = stream_;
+    ensure_workspace(n);
+    PoolBuf d_blobs(*this, (size_t)n * BYTES_PER_BLOB), d_z(*this, (size_t)n * 32), d_y(*this, (size_t)n * 32), d_pr(*this, (size_t)n * 48);
+    for (int b = 0; b < n; b++)
+        HIPCK(hipMemcpyAsync((uint8_t*)d_blobs.p + (size_t)b * BYTES_PER_BLOB, blobs[b], BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_z.p, z_mont, (size_t)n * 32, hipMemcpyHostToDevice, st));
+    open_blobs_core(n, (const uint8_t*)d_blobs.p, d_z.p, d_y.p, want_proofs ? (uint8_t*)d_pr.p : nullptr, st);
+    if (want_proofs) HIPCK(hipMemcpyAsync(h_proofs, d_pr.p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
     HIPCK(hipMemcpyAsync(h_y_canon, d_y.p, (size_t)n * 32, hipMemcpyDeviceToHost, st));
     HIPCK(hipMemcpyAsync(h_status, d_status_, n * sizeof(int), hipMemcpyDeviceToHost, st));
     SYNC_CHECKED(st);
@@ -250,6 +258,50 @@ int Engine::verify_kzg_proof_host(const uint8_t* commitment, const uint8_t* z_by
     return OK;
 }
 
+// The second half of verify_blob_kzg_proof_batch, shared by the host and the device-resident form: the challenges z_i (Montgomery)
+// and evaluations y_i (canonical) are known, d_points = [proofs n | commitments n | room for G] holds the decoded points.
+// Hashes the weight r on the host (one short message), forms the two scalar lists and runs the bucket MSMs + pairing.  Returns 1 / 0.
+int Engine::finish_verify_blob_batch(int n, const Fr8* z_mont, const Fr8* y_canon, const uint8_t* const* commitments,
+                                     const uint8_t* const* proofs, const void* d_points) {
+    void* d_pts = const_cast<void*>(d_points);
+    launch::copy_affine(d_srs_, (G1Affine*)d_pts + 2 * n, 1, stream_);
+    // compute_r_powers_for_verify_kzg_proof_batch (verifier.rs:201-262)
+    Sha256 sh;
+    uint8_t hdr[32];
+    memcpy(hdr, "RCKZGBATCH___V1_", 16);
+    for (int b = 0; b < 8; b++) { hdr[16 + b] = (uint8_t)((uint64_t)N_BLOB >> (56 - 8 * b)); hdr[24 + b] = (uint8_t)((uint64_t)n >> (56 - 8 * b)); }
+    sh.update(hdr, 32);
+    std::vector<Fr> zs(n);
+    for (int i = 0; i < n; i++) {
+        memcpy(&zs[i], &z_mont[i], 32);
+        uint8_t zy[64];
+        fr_to_be(zy, from_mont(zs[i]));
+        Fr yc;
+        memcpy(&yc, &y_canon[i], 32);
+        fr_to_be(zy + 32, yc);
+        sh.update(commitments[i], 48);
+        sh.update(zy, 64);
+        sh.update(proofs[i], 48);
+    }
+    uint8_t dig[32];
+    sh.finish(dig);
+    Fr r = reduce_be32_4844(dig);
+    // lhs = sum r^i C_i - (sum r^i y_i) G + sum r^i z_i pi_i ; rhs = sum r^i pi_i   (kzg_single_open/src/verifier.rs:76-99)
+    std::vector<Fr8> s0(n), s1(2 * n + 1);
+    Fr cur = one<FrParams>(), ysum = zero<FrParams>();
+    for (int i = 0; i < n; i++) {
+        Fr yc;
+        memcpy(&yc, &y_canon[i], 32);
+        s0[i] = canon8(cur);
+        s1[i] = canon8(mul(cur, zs[i]));
+        s1[n + i] = s0[i];
+        ysum = add(ysum, mul(cur, to_mont(yc)));
+        cur = mul(cur, r);
+    }
+    s1[2 * n] = canon8(neg(ysum));
+    return pairing_check_4844(d_pts, s0, s1);
+}
+
 int Engine::verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* const* blobs, uint64_t n_commitments,
                                              const uint8_t* const* commitments, uint64_t n_proofs, const uint8_t* const* proofs,
                                              int* verified) {
@@ -260,10 +312,9 @@ int Engine::verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* co
     try {
         HIPCK(hipSetDevice(dev_));
         // challenges z_i and evaluations y_i = p_i(z_i)
-        std::vector<Fr> zs(n);
         std::vector<Fr8> z8(n), y8(n);
         std::vector<int> bst(n);
-        for (int i = 0; i < n; i++) { zs[i] = fs_challenge(blobs[i], commitments[i]); memcpy(&z8[i], &zs[i], 32); }
+        for (int i = 0; i < n; i++) { const Fr z = fs_challenge(blobs[i], commitments[i]); memcpy(&z8[i], &z, 32); }
         if (n) open_blobs_at(n, blobs, z8.data(), false, nullptr, y8.data(), bst.data());
         for (int i = 0; i < n; i++) if (bst[i]) return ERR_SCALAR;          // blobs first,
         // point array [proofs n | commitments n | G]
@@ -274,40 +325,7 @@ int Engine::verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* co
         if (n) check_points(this, pb.data(), 2 * n, d_pts.p, pst.data(), stream_, beta_);
         for (int i = 0; i < n; i++) if (pst[n + i]) return ERR_G1;          // then commitments,
         for (int i = 0; i < n; i++) if (pst[i]) return ERR_G1;              // then proofs (verifier.rs:97-113)
-        launch::copy_affine(d_srs_, (G1Affine*)d_pts.p + 2 * n, 1, stream_);
-        // compute_r_powers_for_verify_kzg_proof_batch (verifier.rs:201-262)
-        Sha256 sh;
-        uint8_t hdr[32];
-        memcpy(hdr, "RCKZGBATCH___V1_", 16);
-        for (int b = 0; b < 8; b++) { hdr[16 + b] = (uint8_t)((uint64_t)N_BLOB >> (56 - 8 * b)); hdr[24 + b] = (uint8_t)((uint64_t)n >> (56 - 8 * b)); }
-        sh.update(hdr, 32);
-        for (int i = 0; i < n; i++) {
-            uint8_t zy[64];
-            fr_to_be(zy, from_mont(zs[i]));
-            Fr yc;
-            memcpy(&yc, &y8[i], 32);
-            fr_to_be(zy + 32, yc);
-            sh.update(commitments[i], 48);
-            sh.update(zy, 64);
-            sh.update(proofs[i], 48);
-        }
-        uint8_t dig[32];
-        sh.finish(dig);
-        Fr r = reduce_be32_4844(dig);
-        // lhs = sum r^i C_i - (sum r^i y_i) G + sum r^i z_i pi_i ; rhs = sum r^i pi_i   (kzg_single_open/src/verifier.rs:76-99)
-        std::vector<Fr8> s0(n), s1(2 * n + 1);
-        Fr cur = one<FrParams>(), ysum = zero<FrParams>();
-        for (int i = 0; i < n; i++) {
-            Fr yc;
-            memcpy(&yc, &y8[i], 32);
-            s0[i] = canon8(cur);
-            s1[i] = canon8(mul(cur, zs[i]));
-            s1[n + i] = s0[i];
-            ysum = add(ysum, mul(cur, to_mont(yc)));
-            cur = mul(cur, r);
-        }
-        s1[2 * n] = canon8(neg(ysum));
-        *verified = pairing_check_4844(d_pts.p, s0, s1);
+        *verified = finish_verify_blob_batch(n, z8.data(), y8.data(), commitments, proofs, d_pts.p);
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;
@@ -343,6 +361,270 @@ int Engine::verify_blob_kzg_proof_host(const uint8_t* blob, const uint8_t* commi
     fr_to_be(yb, y);
     st = verify_kzg_proof_host(commitment, zb, yb, proof, verified);
     return st;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched and device-resident forms (include/c_eth_kzg.h: eth_kzg_amd_compute_*_kzg_proof_batch / _device,
+// eth_kzg_amd_verify_blob_kzg_proof_batch_device).  One opening core per (sub-)batch instead of one per blob.
+
+// the engine-owned scratch of these forms, carved from one allocation: [32-byte Fiat-Shamir header | per blob: digest, z, y,
+// decoded commitment, proof, four status words].  Grown under mu_; a call that may still use the old block on another stream
+// has recorded work_[0].done, and hipFree waits for the device.
+Engine::Scratch4844 Engine::scratch_4844(int n) {
+    constexpr size_t HDR = 256;  // keeps every array 16-byte aligned
+    if (n > cap_4844_) {
+        const int cap = ((n + 63) / 64) * 64;
+        if (d_4844_) { HIPCK(hipFree(d_4844_)); d_4844_ = nullptr; cap_4844_ = 0; }
+        HIPCK(hipMalloc(&d_4844_, HDR + (size_t)cap * (32 + 32 + 32 + sizeof(G1Affine) + 48 + 4 * sizeof(int))));
+        uint8_t hdr[32];  // compute_fiat_shamir_challenge's domain separator and degree (fs_challenge above)
+        memcpy(hdr, "FSBLOBVERIFY_V1_", 16);
+        memset(hdr + 16, 0, 16);
+        hdr[16 + 14] = 0x10;
+        HIPCK(hipMemcpy(d_4844_, hdr, 32, hipMemcpyHostToDevice));
+        cap_4844_ = cap;
+    }
+    const size_t cap = (size_t)cap_4844_;
+    uint8_t* p = (uint8_t*)d_4844_ + HDR;
+    Scratch4844 s;
+    s.dig = p; p += cap * 32;
+    s.z = p; p += cap * 32;
+    s.y = p; p += cap * 32;
+    s.aff = p; p += cap * sizeof(G1Affine);
+    s.proofs = p; p += cap * 48;
+    s.blob_bad = (int*)p; p += cap * sizeof(int);
+    s.z_bad = (int*)p; p += cap * sizeof(int);
+    s.g1_bad = (int*)p; p += cap * sizeof(int);
+    s.status = (int*)p;
+    return s;
+}
+// z_i = H("FSBLOBVERIFY_V1_" | 4096 | blob_i | commitment_i) mod r for blobs and commitments in HBM: one lane per blob hashes
+// (k_sha256.hip), one lane per digest reduces (k_4844.hip); s.z then feeds k_quotient_by_linear without a host round trip
+void Engine::fs_challenges_device(int n, const uint8_t* d_blobs, const uint8_t* d_commitments, const Scratch4844& s, hipStream_t st) {
+    launch::sha256_many(n, (const uint8_t*)d_4844_, 32, d_blobs, BYTES_PER_BLOB, BYTES_PER_BLOB, d_commitments, 48, 48, s.dig, st);
+    launch::fr_from_be32(n, s.dig, s.z, nullptr, /*reduce=*/true, st);
+}
+
+int Engine::compute_blob_kzg_proof_device(int n, const uint8_t* d_blobs, const uint8_t* d_commitments, uint8_t* d_out_proofs, int* h_status,
+                                          hipStream_t st, bool sync) {
+    if (n <= 0) return OK;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    if (n > device_batch_max_) {  // sub-batches (0.5 MB of scratch per blob), as blob_to_kzg_commitment_device
+        for (int b0 = 0; b0 < n; b0 += device_batch_max_) {
+            const int nb = std::min(device_batch_max_, n - b0);
+            const int rc = compute_blob_kzg_proof_device(nb, d_blobs + (size_t)b0 * BYTES_PER_BLOB, d_commitments + (size_t)b0 * 48,
+                                                         d_out_proofs + (size_t)b0 * 48, h_status ? h_status + b0 : nullptr, st, sync);
+            if (rc) return rc;
+        }
+        return OK;
+    }
+    try {
+        HIPCK(hipSetDevice(dev_));
+        if (!st) {  // NULL: the library's stream, ordered behind whatever the caller has queued on the default stream so far
+            st = stream_;
+            HIPCK(hipEventRecord(work_[0].ev_in, nullptr));
+            HIPCK(hipStreamWaitEvent(st, work_[0].ev_in, 0));
+        }
+        ensure_workspace(n);
+        const Scratch4844 s = scratch_4844(n);
+        HIPCK(hipStreamWaitEvent(st, work_[0].done, 0));  // an earlier asynchronous call on another stream may still use the workspace
+        fs_challenges_device(n, d_blobs, d_commitments, s, st);
+        open_blobs_core(n, d_blobs, s.z, s.y, d_out_proofs, st);
+        if (h_status) {  // the commitment is only validated (prover.rs:73-75): without a status array there is nobody to tell
+            launch::g1_decompress(d_commitments, s.aff, s.g1_bad, n, 1, beta_, st);
+            launch::status_4844(n, d_status_, nullptr, s.g1_bad, s.status, st);
+            HIPCK(hipMemcpyAsync(h_status, s.status, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        }
+        HIPCK(hipEventRecord(work_[0].done, st));
+        HIPCK(hipGetLastError());
+        if (sync || h_status) HIPCK(hipStreamSynchronize(st));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+int Engine::compute_kzg_proof_device(int n, const uint8_t* d_blobs, const uint8_t* d_z, uint8_t* d_out_proofs, uint8_t* d_out_y, int* h_status,
+                                     hipStream_t st, bool sync) {
+    if (n <= 0) return OK;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    if (n > device_batch_max_) {
+        for (int b0 = 0; b0 < n; b0 += device_batch_max_) {
+            const int nb = std::min(device_batch_max_, n - b0);
+            const int rc = compute_kzg_proof_device(nb, d_blobs + (size_t)b0 * BYTES_PER_BLOB, d_z + (size_t)b0 * 32, d_out_proofs + (size_t)b0 * 48,
+                                                    d_out_y + (size_t)b0 * 32, h_status ? h_status + b0 : nullptr, st, sync);
+            if (rc) return rc;
+        }
+        return OK;
+    }
+    try {
+        HIPCK(hipSetDevice(dev_));
+        if (!st) {
+            st = stream_;
+            HIPCK(hipEventRecord(work_[0].ev_in, nullptr));
+            HIPCK(hipStreamWaitEvent(st, work_[0].ev_in, 0));
+        }
+        ensure_workspace(n);
+        const Scratch4844 s = scratch_4844(n);
+        HIPCK(hipStreamWaitEvent(st, work_[0].done, 0));
+        launch::fr_from_be32(n, d_z, s.z, s.z_bad, /*reduce=*/false, st);  // canonicity is checked on the device; a bad z opens at 0
+        open_blobs_core(n, d_blobs, s.z, s.y, d_out_proofs, st);
+        launch::fr_to_be32(n, s.y, d_out_y, st);
+        if (h_status) {
+            launch::status_4844(n, d_status_, s.z_bad, nullptr, s.status, st);  // the blob's own check first, then z: the single call's order
+            HIPCK(hipMemcpyAsync(h_status, s.status, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        }
+        HIPCK(hipEventRecord(work_[0].done, st));
+        HIPCK(hipGetLastError());
+        if (sync || h_status) HIPCK(hipStreamSynchronize(st));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// The two host-pointer forms.  Per sub-batch of 256 blobs: the helper threads gather the blobs into pinned memory and, the bytes
+// being in their cache anyway, hash the challenge (a SHA-NI core is faster per message than a GPU lane) or parse z; one upload, one
+// core, one download.  commitments != null: compute_blob_kzg_proof; zs != null: compute_kzg_proof.
+int Engine::proofs_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* commitments, const uint8_t* const* zs,
+                              uint8_t* const* out_proofs, uint8_t* const* out_ys, int* h_status) {
+    constexpr int SUB = 256;
+    HostPool* pool = n >= 4 ? ensure_host_pool() : nullptr;  // a couple of blobs: everything on the calling thread
+    for (int b0 = 0; b0 < n; b0 += SUB) {
+        const int nb = std::min(SUB, n - b0);
+        PoolBuf h_in(*this, (size_t)nb * BYTES_PER_BLOB, /*pinned_host=*/true);
+        std::vector<Fr8> z8(nb);
+        std::vector<int> z_ok(nb, 1), bst(nb), cst(nb, 0);
+        std::vector<uint8_t> cm(commitments ? (size_t)nb * 48 : 0), pr((size_t)nb * 48);
+        std::vector<Fr8> y8(nb);
+        parallel_for(nb, pool ? pool->threads() + 1 : 1, pool, [&](int i) {
+            uint8_t* dst = (uint8_t*)h_in.p + (size_t)i * BYTES_PER_BLOB;
+            memcpy(dst, blobs[b0 + i], BYTES_PER_BLOB);
+            Fr z;
+            if (commitments) {
+                memcpy(&cm[(size_t)i * 48], commitments[b0 + i], 48);
+                z = fs_challenge(dst, &cm[(size_t)i * 48]);
+            } else if (!fr_from_be_canonical(z, zs[b0 + i])) {
+                z_ok[i] = 0;
+                z = zero<FrParams>();
+            }
+            memcpy(&z8[i], &z, 32);
+        });
+        open_staged_blobs(nb, (const uint8_t*)h_in.p, z8.data(), commitments ? cm.data() : nullptr, pr.data(), y8.data(), bst.data(), cst.data());
+        for (int i = 0; i < nb; i++) {
+            const int st = bst[i] ? ERR_SCALAR : !z_ok[i] ? ERR_SCALAR : cst[i] ? ERR_G1 : OK;  // the single call's order
+            if (h_status) h_status[b0 + i] = st;
+            if (st) continue;
+            memcpy(out_proofs[b0 + i], &pr[(size_t)i * 48], 48);
+            if (out_ys) {
+                Fr y;
+                memcpy(&y, &y8[i], 32);
+                fr_to_be(out_ys[b0 + i], y);
+            }
+        }
+    }
+    return OK;
+}
+
+// one sub-batch of the host forms on stream_: pinned blobs up, core, (commitments validated,) results down
+void Engine::open_staged_blobs(int nb, const uint8_t* h_blobs_pinned, const Fr8* z_mont, const uint8_t* h_commitments, uint8_t* h_proofs,
+                               Fr8* h_y, int* h_blob_status, int* h_g1_status) {
+    hipStream_t st = stream_;
+    ensure_workspace(nb);
+    PoolBuf d_in(*this, (size_t)nb * BYTES_PER_BLOB), d_z(*this, (size_t)nb * 32), d_y(*this, (size_t)nb * 32), d_pr(*this, (size_t)nb * 48);
+    PoolBuf d_cm(*this, (size_t)nb * 48), d_aff(*this, (size_t)nb * sizeof(G1Affine)), d_cst(*this, (size_t)nb * sizeof(int));
+    HIPCK(hipMemcpyAsync(d_in.p, h_blobs_pinned, (size_t)nb * BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(d_z.p, z_mont, (size_t)nb * 32, hipMemcpyHostToDevice, st));
+    open_blobs_core(nb, (const uint8_t*)d_in.p, d_z.p, d_y.p, (uint8_t*)d_pr.p, st);
+    if (h_commitments) {
+        HIPCK(hipMemcpyAsync(d_cm.p, h_commitments, (size_t)nb * 48, hipMemcpyHostToDevice, st));
+        launch::g1_decompress((const uint8_t*)d_cm.p, d_aff.p, (int*)d_cst.p, nb, 1, beta_, st);  // only validated (prover.rs:73-75)
+        HIPCK(hipMemcpyAsync(h_g1_status, d_cst.p, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    HIPCK(hipMemcpyAsync(h_proofs, d_pr.p, (size_t)nb * 48, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(h_y, d_y.p, (size_t)nb * 32, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(h_blob_status, d_status_, nb * sizeof(int), hipMemcpyDeviceToHost, st));
+    SYNC_CHECKED(st);
+}
+
+int Engine::compute_blob_kzg_proof_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* commitments, uint8_t* const* out_proofs,
+                                              int* h_status) {
+    if (n <= 0) return OK;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        proofs_batch_host(n, blobs, commitments, nullptr, out_proofs, nullptr, h_status);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+int Engine::compute_kzg_proof_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* zs, uint8_t* const* out_proofs,
+                                         uint8_t* const* out_ys, int* h_status) {
+    if (n <= 0) return OK;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        proofs_batch_host(n, blobs, nullptr, zs, out_proofs, out_ys, h_status);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// verify_blob_kzg_proof_batch on flat arrays in HBM.  GPU: challenges (hash + reduction), y_i = p_i(z_i) through the core in
+// sub-batches, commitments and proofs decompressed where they lie.  Down: z, y, the status words and the 96 n point bytes the
+// weights' transcript hashes.  Then exactly the host form's second half.
+int Engine::verify_blob_kzg_proof_batch_device(uint64_t n64, const uint8_t* d_blobs, const uint8_t* d_commitments, const uint8_t* d_proofs,
+                                               int* verified, hipStream_t user_stream) {
+    *verified = 0;
+    if (n64 == 0) { *verified = 1; return OK; }  // an empty batch verifies, as in the host form
+    if (n64 > (1u << 24)) return ERR_INPUT;
+    const int n = (int)n64;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        std::vector<Fr8> z8(n), y8(n);  // inside the try: allocations must not unwind through the C ABI
+        std::vector<int> bst(n), pst(2 * (size_t)n);
+        std::vector<uint8_t> pb((size_t)2 * n * 48);
+        std::vector<const uint8_t*> cp(n), pp(n);
+        HIPCK(hipSetDevice(dev_));
+        hipStream_t st = stream_;
+        if (user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
+            HIPCK(hipEventRecord(v_decoded_, user_stream));
+            HIPCK(hipStreamWaitEvent(st, v_decoded_, 0));
+        }
+        const int sub = std::min(n, device_batch_max_);
+        ensure_workspace(sub);
+        const Scratch4844 s = scratch_4844(n);
+        fs_challenges_device(n, d_blobs, d_commitments, s, st);
+        for (int b0 = 0; b0 < n; b0 += sub) {
+            const int nb = std::min(sub, n - b0);
+            open_blobs_core(nb, d_blobs + (size_t)b0 * BYTES_PER_BLOB, (const uint8_t*)s.z + (size_t)b0 * 32, (uint8_t*)s.y + (size_t)b0 * 32, nullptr, st);
+            HIPCK(hipMemcpyAsync(s.blob_bad + b0, d_status_, nb * sizeof(int), hipMemcpyDeviceToDevice, st));
+        }
+        // point array [proofs n | commitments n | G], decoded and subgroup-checked from where the bytes lie
+        PoolBuf d_pts(*this, (size_t)(2 * n + 1) * sizeof(G1Affine)), d_pst(*this, (size_t)2 * n * sizeof(int));
+        launch::g1_decompress2(d_proofs, d_pts.p, (int*)d_pst.p, n, d_commitments, (G1Affine*)d_pts.p + n, (int*)d_pst.p + n, n, beta_, st);
+        HIPCK(hipMemcpyAsync(z8.data(), s.z, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(y8.data(), s.y, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(bst.data(), s.blob_bad, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(pst.data(), d_pst.p, (size_t)2 * n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(pb.data(), d_proofs, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(pb.data() + (size_t)n * 48, d_commitments, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+        SYNC_CHECKED(st);
+        for (int i = 0; i < n; i++) if (bst[i]) return ERR_SCALAR;          // blobs first,
+        for (int i = 0; i < n; i++) if (pst[n + i]) return ERR_G1;          // then commitments,
+        for (int i = 0; i < n; i++) if (pst[i]) return ERR_G1;              // then proofs (verifier.rs:97-113)
+        for (int i = 0; i < n; i++) { pp[i] = pb.data() + (size_t)i * 48; cp[i] = pb.data() + (size_t)(n + i) * 48; }
+        *verified = finish_verify_blob_batch(n, z8.data(), y8.data(), cp.data(), pp.data(), d_pts.p);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
 }
 
 }  // namespace kzg

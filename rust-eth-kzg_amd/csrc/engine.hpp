@@ -188,6 +188,26 @@ public:
     int verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* const* blobs, uint64_t n_commitments,
                                          const uint8_t* const* commitments, uint64_t n_proofs, const uint8_t* const* proofs,
                                          int* verified);
+    // ---- EIP-4844 proofs for MANY blobs (eip4844.hip; crates/eip4844/src/prover.rs:37-92 per blob) ----
+    // Device-resident: d_blobs n * 131072 B, d_commitments / d_out_proofs n * 48 B, d_z / d_out_y n * 32 B big-endian (4-byte aligned);
+    // h_status: n ints on the host or null.  status per blob in the single call's order: 1 the blob holds a non-canonical element,
+    // else 1 z is not canonical (compute_kzg_proof) / 2 the commitment is not a valid subgroup point (compute_blob_kzg_proof), else 0.
+    // Stream, event and status == null rules as blob_to_kzg_commitment_device.  The Fiat-Shamir challenges of the blob proofs are
+    // hashed on the GPU (k_sha256.hip): the blobs do not come down.
+    int compute_blob_kzg_proof_device(int n, const uint8_t* d_blobs, const uint8_t* d_commitments, uint8_t* d_out_proofs, int* h_status,
+                                      hipStream_t stream, bool sync);
+    int compute_kzg_proof_device(int n, const uint8_t* d_blobs, const uint8_t* d_z, uint8_t* d_out_proofs, uint8_t* d_out_y, int* h_status,
+                                 hipStream_t stream, bool sync);
+    // host pointers: blobs gathered into pinned memory and challenges hashed by the helper threads, one upload and one opening per
+    // sub-batch of 256 blobs; outputs of a blob whose status is not 0 are left untouched
+    int compute_blob_kzg_proof_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* commitments, uint8_t* const* out_proofs,
+                                          int* h_status);
+    int compute_kzg_proof_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* zs, uint8_t* const* out_proofs,
+                                     uint8_t* const* out_ys, int* h_status);
+    // verify_blob_kzg_proof_batch (verifier.rs:80-196) on flat arrays in HBM: challenges and evaluations on the GPU, points decompressed
+    // where they lie; the n * 160 bytes of the weights' transcript come down.  Synchronous; verdict and error split of the host form.
+    int verify_blob_kzg_proof_batch_device(uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments, const uint8_t* d_proofs,
+                                           int* verified, hipStream_t stream);
 
     // device-resident recovery: flat [R][128][2048] cells in HBM + a 128-bit presence mask per blob (host); see verify.hip
     int recover_cells_and_kzg_proofs_device(int R, const uint8_t* d_cells, const uint64_t* present_masks, uint8_t* d_out_cells,
@@ -205,6 +225,9 @@ public:
     int test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out_recompressed);
     int test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp);
     int test_op(int op, int n, const int32_t* in, int32_t* out);
+    // launch::sha256_many on its own: prefix on the host, every other buffer in HBM
+    int test_sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* d_body, size_t body_stride, uint32_t body_len,
+                         const uint8_t* d_tail, size_t tail_stride, uint32_t tail_len, uint8_t* d_out);
     // the window tables themselves (engine_testhooks.hip).  kind: TableSel; which: 0 = the complete table the next MSM launch would
     // snapshot (the view's main), 1 = the wider one under construction next to it (its ready groups), 2 = the table the context started on, while it is alive
     std::shared_ptr<SharedTable> test_table(int kind, int which) const;
@@ -263,6 +286,29 @@ private:
     void init_verifier();
     int open_blobs_at(int n, const uint8_t* const* blobs, const Fr8* z_mont, bool want_proofs, uint8_t* h_proofs, Fr8* h_y_canon,
                       int* h_status);
+    // the device-resident core of every opening: blobs in HBM, z_i Montgomery in HBM -> y_i canonical (d_y) and, if d_proofs is not
+    // null, proof_i = commit(quotient_i) compressed, all left on the device; the per-blob status words are work_[0]'s (d_status_).
+    // Enqueues on st and returns; the caller holds mu_ and has called ensure_workspace(n).
+    void open_blobs_core(int n, const uint8_t* d_blobs, const void* d_z_mont, void* d_y, uint8_t* d_proofs, hipStream_t st);
+    // scratch of the batched EIP-4844 forms, owned by the engine (grow-only, guarded by mu_; ordered by work_[0].done like the
+    // work set): per blob a digest, z, y, the decoded commitment, a proof and three status words
+    struct Scratch4844 {
+        uint8_t *dig = nullptr, *proofs = nullptr;
+        void *z = nullptr, *y = nullptr, *aff = nullptr;
+        int *blob_bad = nullptr, *z_bad = nullptr, *g1_bad = nullptr, *status = nullptr;
+    };
+    Scratch4844 scratch_4844(int n);
+    void fs_challenges_device(int n, const uint8_t* d_blobs, const uint8_t* d_commitments, const Scratch4844& s, hipStream_t st);
+    int finish_verify_blob_batch(int n, const Fr8* z_mont, const Fr8* y_canon, const uint8_t* const* commitments, const uint8_t* const* proofs,
+                                 const void* d_points);
+    // the two host-pointer batch forms (commitments: blob proofs; zs: proofs at given points) and one staged sub-batch of them
+    int proofs_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* commitments, const uint8_t* const* zs,
+                          uint8_t* const* out_proofs, uint8_t* const* out_ys, int* h_status);
+    void open_staged_blobs(int nb, const uint8_t* h_blobs_pinned, const Fr8* z_mont, const uint8_t* h_commitments, uint8_t* h_proofs, Fr8* h_y,
+                           int* h_blob_status, int* h_g1_status);
+    HostPool* ensure_host_pool();  // the memcpy / hash helper threads of the host-pointer batch forms (engine_prover.hip)
+    void* d_4844_ = nullptr;       // Scratch4844's arena + the 32-byte Fiat-Shamir header in front of it
+    int cap_4844_ = 0;
     int pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0, const std::vector<Fr8>& sc1);
     // dsrc (device-resident form): the cells and proofs already sit in HBM -- they are copied device to device into the arena
     // instead of being gathered on the host and uploaded; the pointer arrays then address their pinned host mirror, which the

@@ -383,6 +383,19 @@ int Engine::blob_to_kzg_commitment_device(int n, const uint8_t* d_blobs, uint8_t
     return OK;
 }
 
+HostPool* Engine::ensure_host_pool() {
+    std::call_once(host_pool_once_, [this] {
+        // memcpy helpers: the gather of 2048 blobs is 268 MB and the MSMs cannot start before its last byte is uploaded,
+        // so its bandwidth is exposed time (4 threads: ~10 ms, 8: ~5 ms).  ETH_KZG_AMD_HOST_THREADS overrides.
+        int t = 8;
+        const unsigned hw = std::thread::hardware_concurrency();
+        if (hw && (int)hw < 2 * t) t = (int)hw / 2 > 1 ? (int)hw / 2 : 1;
+        if (knobs_.host_threads) t = knobs_.host_threads;
+        host_pool_.reset(new HostPool(t, [d = dev_] { (void)hipSetDevice(d); }));
+    });
+    return host_pool_.get();
+}
+
 // ---------------------------------------------------------------------------------------------
 // host-buffer entry points: stage through device buffers owned by the engine
 // The reference's entry point (bindings/c/src/lib.rs:226-236) and its batched form: host pointers in, 256 caller
@@ -425,16 +438,7 @@ int Engine::compute_cells_and_kzg_proofs_host(int n, const uint8_t* const* blobs
     auto drain = [&]() { while (outstanding.load(std::memory_order_acquire) > 0) nap(); };
     try {
         HIPCK(hipSetDevice(dev_));
-        if (threaded)
-            std::call_once(host_pool_once_, [this] {
-                // memcpy helpers: the gather of 2048 blobs is 268 MB and the MSMs cannot start before its last byte is uploaded,
-                // so its bandwidth is exposed time (4 threads: ~10 ms, 8: ~5 ms).  ETH_KZG_AMD_HOST_THREADS overrides.
-                int t = 8;
-                const unsigned hw = std::thread::hardware_concurrency();
-                if (hw && (int)hw < 2 * t) t = (int)hw / 2 > 1 ? (int)hw / 2 : 1;
-                if (knobs_.host_threads) t = knobs_.host_threads;
-                host_pool_.reset(new HostPool(t, [d = dev_] { (void)hipSetDevice(d); }));
-            });
+        if (threaded) ensure_host_pool();
         Work& w = lease_work(1, NW - 1);
         held = &w;
         step();

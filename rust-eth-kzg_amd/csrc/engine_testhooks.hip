@@ -27,6 +27,23 @@ int Engine::test_fr_ntt4096(const uint8_t* in_be, uint8_t* out_be, int inverse_d
     return OK;
 }
 
+int Engine::test_sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* d_body, size_t body_stride, uint32_t body_len,
+                             const uint8_t* d_tail, size_t tail_stride, uint32_t tail_len, uint8_t* d_out) {
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        PoolBuf d_prefix(*this, prefix_len);
+        if (prefix_len) HIPCK(hipMemcpyAsync(d_prefix.p, prefix, prefix_len, hipMemcpyHostToDevice, stream_));
+        launch::sha256_many(n, (const uint8_t*)d_prefix.p, prefix_len, d_body, body_stride, body_len, d_tail, tail_stride, tail_len, d_out, stream_);
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(stream_));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 // in/out: [lane][128][48 B]; both directions natural in -> natural out (inverse is unscaled)
 int Engine::test_g1_fft128(const uint8_t* in, uint8_t* out, int n_lanes, int inverse) {
     std::lock_guard<std::recursive_mutex> lk(mu_);

@@ -185,6 +185,17 @@ void vm_fold_ranges(const void* prod, const int* ranges /*[n_ranges][2], device*
 
 // k_4844.hip
 void quotient_by_linear(int n, const void* coeffs, const void* z_mont, void* quotient, void* y_out, hipStream_t st);
+// n x 32 big-endian bytes -> Montgomery Fr.  reduce: the value mod r (a digest becomes a challenge; bad is not touched); otherwise a
+// value >= r gives bad[i] = 1 and the point 0
+void fr_from_be32(int n, const uint8_t* in, void* out_mont, int* bad, bool reduce, hipStream_t st);
+void fr_to_be32(int n, const void* canon /*Fr*/, uint8_t* out, hipStream_t st);
+// out[i] = 1 if blob_bad[i], else 1 if z_bad[i], else 2 if g1_bad[i], else 0 (z_bad / g1_bad may be null)
+void status_4844(int n, const int* blob_bad, const int* z_bad, const int* g1_bad, int* out, hipStream_t st);
+
+// k_sha256.hip: SHA-256 of n independent messages, one lane each; message i = prefix[prefix_len] | (body + i * body_stride)[body_len] |
+// (tail + i * tail_stride)[tail_len], all device pointers (a part of length 0 may be null); digest i -> out + 32 i
+void sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* body, size_t body_stride, uint32_t body_len,
+                 const uint8_t* tail, size_t tail_stride, uint32_t tail_len, uint8_t* out, hipStream_t st);
 
 constexpr size_t SIZEOF_FR = 32, SIZEOF_G1AFFINE = 96, SIZEOF_G1JAC = 144;
 constexpr size_t SIZEOF_JACS = 156;  // signed 13 x 30-bit Jacobian point (curve30.hpp)
