@@ -23,6 +23,16 @@ int eth_kzg_amd_test_sha256_many(const DASContext *ctx, uint64_t n, const uint8_
                                  uint64_t body_stride, uint64_t body_len, const uint8_t *d_tail, uint64_t tail_stride, uint64_t tail_len,
                                  uint8_t *d_out);
 
+/* The verifier's two-job bucket MSM on its own.  points: n_pts compressed G1 points (host); job 0 = sum_{i<n0} sc0[i] P_i, job 1 =
+ * sum_{i<n1} sc1[i] P_i, 1 <= n0 <= n1 <= n_pts, scalars canonical big-endian < r (host).  out: the two sums, compressed (96 bytes).
+ * form: 0 windowed (msm_pippenger2); 1 byte-shifted after pip_shift_prepare (one lane per point); 2 byte-shifted after
+ * pip_shift_prepare_and_subgroup exactly as verify.hip launches it (quad form below coop_points_max, one-lane form above), with
+ * status0/status1 over the first n0 / the remaining points; sub_status (n_pts ints, may be NULL) receives them (forms 0 and 1: the
+ * status words of the production decompression, same values: 0 good, 1 bad encoding or off the curve, 2 outside the subgroup).
+ * Synchronous.  Returns 0 on success, the library's status codes otherwise (a scalar >= r: 1; counts out of range: 3). */
+int eth_kzg_amd_test_verify_msm(const DASContext *ctx, int form, const uint8_t *points, int n_pts, const uint8_t *sc0, int n0,
+                                const uint8_t *sc1, int n1, uint8_t *out96, int32_t *sub_status);
+
 /* One field or point operation of the kernels per element (csrc/k_test_ops.hip), on the raw words of the device structs.
  * eth_kzg_amd_test_op_info: word counts per element of operation `op` (0, 1, ... until it returns -1), whether it exists on the
  * device only (the pair / quad forms, the tree folds) and its name.  eth_kzg_amd_test_op: n elements of in_words each in, n of

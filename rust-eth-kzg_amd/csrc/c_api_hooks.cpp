@@ -46,6 +46,11 @@ int eth_kzg_amd_test_sha256_many(const DASContext* ctx, uint64_t n, const uint8_
     return eng(ctx)->test_sha256_many((int)n, prefix, (uint32_t)prefix_len, d_body, body_stride, (uint32_t)body_len, d_tail, tail_stride,
                                       (uint32_t)tail_len, d_out);
 }
+int eth_kzg_amd_test_verify_msm(const DASContext* ctx, int form, const uint8_t* points, int n_pts, const uint8_t* sc0, int n0,
+                                const uint8_t* sc1, int n1, uint8_t* out96, int32_t* sub_status) {
+    if (!points || !sc0 || !sc1 || !out96) return kzg::ERR_INPUT;
+    return eng(ctx)->test_verify_msm(form, points, n_pts, sc0, n0, sc1, n1, out96, sub_status);
+}
 int eth_kzg_amd_test_op_info(int op, int32_t* in_words, int32_t* out_words, int32_t* device_only, const char** name) {
     int i, o, d;
     const char* nm;

@@ -228,6 +228,10 @@ public:
     // launch::sha256_many on its own: prefix on the host, every other buffer in HBM
     int test_sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* d_body, size_t body_stride, uint32_t body_len,
                          const uint8_t* d_tail, size_t tail_stride, uint32_t tail_len, uint8_t* d_out);
+    // the verifier's two-job bucket MSM on its own (k_verify.hip).  form: 0 windowed, 1 byte-shifted after pip_shift_prepare, 2 byte-shifted
+    // after pip_shift_prepare_and_subgroup as verify.hip launches it; h_status (n_pts ints, may be null): the points' status words
+    int test_verify_msm(int form, const uint8_t* points, int n_pts, const uint8_t* sc0_be, int n0, const uint8_t* sc1_be, int n1,
+                        uint8_t* out96, int32_t* h_status);
     // the window tables themselves (engine_testhooks.hip).  kind: TableSel; which: 0 = the complete table the next MSM launch would
     // snapshot (the view's main), 1 = the wider one under construction next to it (its ready groups), 2 = the table the context started on, while it is alive
     std::shared_ptr<SharedTable> test_table(int kind, int which) const;

@@ -1,5 +1,6 @@
 // Stage-level test hooks of the engine (include/c_eth_kzg_test_hooks.h): single stages against the oracle.
 #include "engine_internal.hpp"
+#include "curve29.hpp"
 
 #include <array>
 
@@ -173,6 +174,84 @@ int Engine::test_op(int op, int n, const int32_t* in, int32_t* out) {
         HIPCK(hipStreamSynchronize(stream_));
         HIPCK(hipMemcpy(out, dout, no, hipMemcpyDeviceToHost));
         HIPCK(hipFree(di)); HIPCK(hipFree(dout));
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// The two-job bucket MSM of a verification on its own (k_verify.hip; verify.hip: verify_cells_partial runs it behind the challenge).
+// points: n_pts compressed; job 0 = sum_{i < n0} sc0[i] P_i, job 1 = sum_{i < n1} sc1[i] P_i over the same array; out96: both sums, compressed.
+// form 0: msm_pippenger2.  form 1: pip_shift_prepare + msm_pippenger2_shifted.  form 2: the decode without the subgroup tests, then
+// pip_shift_prepare_and_subgroup (statuses of the first n0 points | of the rest) + msm_pippenger2_shifted, as a verification launches them.
+// The shifted forms leave two Jacobian sums that the host normalises, as verify.hip does.  h_status: the n_pts status words.
+int Engine::test_verify_msm(int form, const uint8_t* points, int n_pts, const uint8_t* sc0_be, int n0, const uint8_t* sc1_be, int n1,
+                            uint8_t* out96, int32_t* h_status) {
+    if (form < 0 || form > 2 || n0 < 1 || n1 < n0 || n_pts < n1 || n_pts > (1 << 20)) return ERR_INPUT;
+    std::vector<Fr> sc((size_t)n0 + n1);
+    for (int j = 0; j < n0 + n1; j++) {  // canonical big-endian -> canonical words
+        const uint8_t* b = j < n0 ? sc0_be + (size_t)j * 32 : sc1_be + (size_t)(j - n0) * 32;
+        Fr& x = sc[j];
+        for (int i = 0; i < 8; i++)
+            x.v[7 - i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
+        if (geq_mod<FrParams>(x.v)) return ERR_SCALAR;
+    }
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    struct DevBuf {  // (freed on every way out)
+        void* p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } d_in, d_pts, d_st, d_sc, d_ws, d_out;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        const bool shifted = form != 0;
+        HIPCK(hipMalloc(&d_in.p, (size_t)n_pts * 48));
+        HIPCK(hipMalloc(&d_pts.p, (size_t)n_pts * sizeof(G1Affine)));
+        HIPCK(hipMalloc(&d_st.p, (size_t)n_pts * sizeof(int)));
+        HIPCK(hipMalloc(&d_sc.p, sc.size() * sizeof(Fr)));
+        HIPCK(hipMalloc(&d_ws.p, shifted ? launch::pip_shift_workspace_bytes(n_pts) : launch::pip_workspace_bytes(n_pts)));
+        HIPCK(hipMalloc(&d_out.p, 512));  // two affine points, or two Jacobian sums (shifted form)
+        hipStream_t st = stream_;
+        HIPCK(hipMemcpyAsync(d_in.p, points, (size_t)n_pts * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(d_sc.p, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, st));
+        HIPCK(hipMemsetAsync(d_st.p, 0xff, (size_t)n_pts * sizeof(int), st));  // poisoned like a verification's arena: stale contents fail closed
+        HIPCK(hipMemsetAsync(d_out.p, 0xff, 512, st));
+        const uint8_t* in0 = (const uint8_t*)d_in.p;
+        G1Affine* p0 = (G1Affine*)d_pts.p;
+        int* st0 = (int*)d_st.p;
+        const int rest = n_pts - n0;
+        const Fr *s0 = (const Fr*)d_sc.p, *s1 = s0 + n0;
+        G1Affine out[2];
+        if (form == 2) {
+            launch::g1_decode2(in0, p0, st0, n0, in0 + (size_t)n0 * 48, p0 + n0, st0 + n0, rest, beta_, st);
+            launch::pip_shift_prepare_and_subgroup(p0, n_pts, n_pts, d_ws.p, p0, st0, n0, p0 + n0, st0 + n0, rest, beta_, st);
+        } else {
+            launch::g1_decompress2(in0, p0, st0, n0, in0 + (size_t)n0 * 48, p0 + n0, st0 + n0, rest, beta_, st);
+            if (form == 1) launch::pip_shift_prepare(p0, n_pts, n_pts, d_ws.p, beta_, st);
+        }
+        std::vector<int32_t> status(n_pts);
+        HIPCK(hipMemcpyAsync(status.data(), d_st.p, (size_t)n_pts * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (shifted) {
+            launch::msm_pippenger2_shifted(s0, n0, s1, n1, n_pts, d_ws.p, d_out.p, st);
+            JacQ sums[2];
+            static_assert(sizeof(sums) <= 512 && sizeof(JacQ) == launch::SIZEOF_JACQ, "result slot");
+            HIPCK(hipMemcpyAsync(sums, d_out.p, sizeof sums, hipMemcpyDeviceToHost, st));
+            HIPCK(hipGetLastError());
+            HIPCK(hipStreamSynchronize(st));
+            for (int i = 0; i < 2; i++) {
+                if (sums[i].x.v[0] == 0xffffffffu && sums[i].z.v[0] == 0xffffffffu) throw std::runtime_error("verification MSM left no result");
+                out[i] = to_affine(jac_from_jacq(sums[i]));
+            }
+        } else {
+            launch::msm_pippenger2(p0, s0, n0, s1, n1, d_ws.p, d_out.p, beta_, st);
+            HIPCK(hipMemcpyAsync(out, d_out.p, 2 * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+            HIPCK(hipGetLastError());
+            HIPCK(hipStreamSynchronize(st));
+        }
+        for (int i = 0; i < 2; i++)  // the poison pattern (or anything else that is not a reduced coordinate) is a device failure
+            if (out[i].x.v[11] > FpParams::MOD[11] || out[i].y.v[11] > FpParams::MOD[11]) throw std::runtime_error("verification MSM left no result");
+        if (h_status) memcpy(h_status, status.data(), (size_t)n_pts * sizeof(int32_t));
+        for (int i = 0; i < 2; i++) g1_compress(out96 + 48 * i, out[i]);
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;

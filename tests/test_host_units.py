@@ -23,9 +23,10 @@ def _build_and_run(tmp_path, name, *args):
 
 @pytest.mark.timeout(600)
 def test_binary_gcd_inversion_matches_fermat(tmp_path):
-    """csrc/inverse.hpp (used by the Jacobian -> affine step) against a^(p-2), 3000 values per field incl. edge cases."""
+    """csrc/inverse.hpp (used by the Jacobian -> affine step, the host normalisation of the verifier's sums) against a^(p-2): 3000
+    draws per field from the whole of [1, m), and 1, 2, m - 2, m - 1, (m +- 1) / 2 and 2^(BITS - 1)."""
     out = _build_and_run(tmp_path, "test_inverse")
-    assert "0 mismatches" in out
+    assert out.count(", 0 mismatches") == 2, out
 
 
 @pytest.mark.timeout(600)
