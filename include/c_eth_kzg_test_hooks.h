@@ -33,6 +33,24 @@ int eth_kzg_amd_test_sha256_many(const DASContext *ctx, uint64_t n, const uint8_
 int eth_kzg_amd_test_verify_msm(const DASContext *ctx, int form, const uint8_t *points, int n_pts, const uint8_t *sc0, int n0,
                                 const uint8_t *sc1, int n1, uint8_t *out96, int32_t *sub_status);
 
+/* What the batch verifiers hand to their pairing checks, as bytes (tests/test_verify_inputs.py compares them with an independent
+ * statement in exact integers: the Fiat-Shamir challenge, its powers, the weights, the coset factors and the interpolation sums all
+ * show in them; a verdict shows none of that for valid inputs).  Synchronous; return 0 on success, the library's status codes otherwise.
+ *
+ * eth_kzg_amd_test_verify_cells_partial_device: the device-resident form of eth_kzg_amd_verify_cell_kzg_proof_batch_partial -- the flat
+ *   arrays of eth_kzg_amd_verify_cell_kzg_proof_batch_device (n >= 1 entries, device memory), the cells [lo, hi) evaluated under the
+ *   challenge of the whole batch, out96 (host) = compress(sum r^k pi_k) | compress(the second pairing input).  It runs the set-up
+ *   eth_kzg_amd_verify_cell_kzg_proof_batch_device runs: the pinned host mirror that arrives in chunks behind events, the device source.
+ * eth_kzg_amd_test_verify_blob_batch_inputs: eth_kzg_verify_blob_kzg_proof_batch (on_device = 0: blobs / commitments / proofs are arrays
+ *   of n host pointers) or eth_kzg_amd_verify_blob_kzg_proof_batch_device (on_device = 1: flat arrays in device memory), n >= 1, with the
+ *   two sums the pairing check pairs handed out: out96 (host) = compress(sum r^i pi_i) | compress(sum r^i C_i - (sum r^i y_i) G +
+ *   sum r^i z_i pi_i), paired with [tau]_2 and -[1]_2; *verified = the verdict of that check. */
+int eth_kzg_amd_test_verify_cells_partial_device(const DASContext *ctx, uint64_t n, const uint8_t *d_commitments,
+                                                 const uint64_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs, uint64_t lo,
+                                                 uint64_t hi, uint8_t *out96);
+int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext *ctx, uint64_t n, int on_device, const void *blobs, const void *commitments,
+                                              const void *proofs, uint8_t *out96, int32_t *verified);
+
 /* One field or point operation of the kernels per element (csrc/k_test_ops.hip), on the raw words of the device structs.
  * eth_kzg_amd_test_op_info: word counts per element of operation `op` (0, 1, ... until it returns -1), whether it exists on the
  * device only (the pair / quad forms, the tree folds) and its name.  eth_kzg_amd_test_op: n elements of in_words each in, n of

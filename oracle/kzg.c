@@ -484,11 +484,15 @@ int oracle_compute_cells(const oracle_ctx *c, const uint8_t *blob, uint8_t *cell
 }
 
 /* ------------------------------------------------------------------ */
-/* verify_cell_kzg_proof_batch (eip7594/src/verifier.rs:72-164, fk20/verifier.rs:129-384) */
-int oracle_verify_cell_kzg_proof_batch(const oracle_ctx *c, size_t n_commitments, const uint8_t *commitments,
-                                       size_t n_indices, const uint64_t *cell_indices, size_t n_cells,
-                                       const uint8_t *cells, size_t n_proofs, const uint8_t *proofs, int *verified) {
-    *verified = 0;
+/* verify_cell_kzg_proof_batch (eip7594/src/verifier.rs:72-164, fk20/verifier.rs:129-384) up to the pairing check: the Fiat-Shamir
+   challenge r and the two normalised G1 pairing inputs, aff[0] = sum r^k pi_k (paired with [tau^64]_2) and aff[1] = sum w_row C_row -
+   commit(I) + sum r^k h_k^64 pi_k (paired with -[1]_2).  *empty: the batch has no cells (verifier.rs:90-93; nothing else is set).
+   Both exports below go through this one function, so the bytes one hands out are the ones the other pairs. */
+static int cell_batch_pairing_inputs(const oracle_ctx *c, size_t n_commitments, const uint8_t *commitments,
+                                     size_t n_indices, const uint64_t *cell_indices, size_t n_cells,
+                                     const uint8_t *cells, size_t n_proofs, const uint8_t *proofs,
+                                     fr_t *r_out, g1a_t aff[2], int *empty) {
+    *empty = 0;
     /* deduplicate_with_indices (verifier.rs:49-65): by byte equality, first-occurrence order */
     uint8_t *uniq = malloc(n_commitments * 48 + 1);
     uint64_t *row = malloc((n_commitments + 1) * sizeof(uint64_t));
@@ -504,7 +508,7 @@ int oracle_verify_cell_kzg_proof_batch(const oracle_ctx *c, size_t n_commitments
     if (!(n_commitments == n_indices && n_commitments == n_cells && n_commitments == n_proofs)) rc = ORACLE_ERR_INPUT;
     if (rc == ORACLE_OK) for (size_t i = 0; i < n_indices; i++) if (cell_indices[i] >= N_CELLS) { rc = ORACLE_ERR_INPUT; break; }
     size_t n = n_cells;
-    if (rc != ORACLE_OK || n == 0) { if (rc == ORACLE_OK) *verified = 1; free(uniq); free(row); return rc; }
+    if (rc != ORACLE_OK || n == 0) { if (rc == ORACLE_OK) *empty = 1; free(uniq); free(row); return rc; }
 
     g1a_t *comm = malloc(m * sizeof(g1a_t)), *prf = malloc(n * sizeof(g1a_t));
     fr_t *evals = malloc(n * CELL_LEN * sizeof(fr_t));
@@ -536,6 +540,7 @@ int oracle_verify_cell_kzg_proof_batch(const oracle_ctx *c, size_t n_commitments
         }
         uint8_t dig[32]; sha256(dig, hin, hlen);
         fr_t r; fr_from_be_reduce(&r, dig);
+        *r_out = r;
         fr_t cur = FR_ONE;                               /* compute_powers (verifier.rs:333-343) */
         for (size_t k = 0; k < n; k++) { rp[k] = cur; fr_mul(&cur, &cur, &r); }
     }
@@ -557,15 +562,41 @@ int oracle_verify_cell_kzg_proof_batch(const oracle_ctx *c, size_t n_commitments
         }
         g1_msm(&comm_interp, c->g1s, acc, CELL_LEN);   /* VerificationKey::commit_g1: first 65 SRS points */
     }
-    {   /* step 6: pairing check (verifier.rs:242-259) */
+    {   /* step 6, first half: the pairing inputs (verifier.rs:237-248) */
         g1_t pin; g1_sub(&pin, &sum_comm, &comm_interp); g1_add(&pin, &pin, &wsum_proofs);
-        g1_t both[2] = {sum_proofs, pin}; g1a_t aff[2];
+        g1_t both[2] = {sum_proofs, pin};
         g1_batch_normalize(aff, both, 2);
-        g2a_t q[2] = {c->tau_pow_n, c->neg_g2_gen};
-        *verified = pairing_product_is_one(aff, q, 2);
     }
 done:
     free(hin); free(comm); free(prf); free(evals); free(rp); free(wrp); free(weights); free(uniq); free(row);
+    return rc;
+}
+/* step 6, second half: the pairing check (verifier.rs:250-259) */
+static int cell_batch_pairing(const oracle_ctx *c, const g1a_t aff[2]) {
+    g2a_t q[2] = {c->tau_pow_n, c->neg_g2_gen};
+    return pairing_product_is_one(aff, q, 2);
+}
+int oracle_verify_cell_kzg_proof_batch(const oracle_ctx *c, size_t n_commitments, const uint8_t *commitments,
+                                       size_t n_indices, const uint64_t *cell_indices, size_t n_cells,
+                                       const uint8_t *cells, size_t n_proofs, const uint8_t *proofs, int *verified) {
+    fr_t r; g1a_t aff[2]; int empty;
+    *verified = 0;
+    int rc = cell_batch_pairing_inputs(c, n_commitments, commitments, n_indices, cell_indices, n_cells, cells, n_proofs, proofs, &r, aff, &empty);
+    if (rc == ORACLE_OK) *verified = empty || cell_batch_pairing(c, aff);
+    return rc;
+}
+int oracle_verify_cell_kzg_proof_batch_inputs(const oracle_ctx *c, size_t n_commitments, const uint8_t *commitments,
+                                              size_t n_indices, const uint64_t *cell_indices, size_t n_cells,
+                                              const uint8_t *cells, size_t n_proofs, const uint8_t *proofs,
+                                              uint8_t *r_be32, uint8_t *out96, int *verified) {
+    fr_t r = FR_ZERO; g1a_t aff[2]; int empty;
+    *verified = 0;
+    int rc = cell_batch_pairing_inputs(c, n_commitments, commitments, n_indices, cell_indices, n_cells, cells, n_proofs, proofs, &r, aff, &empty);
+    if (rc != ORACLE_OK) return rc;
+    if (empty) { aff[0].inf = aff[1].inf = 1; aff[0].x = aff[0].y = aff[1].x = aff[1].y = FP_ZERO; }
+    fr_to_be(r_be32, &r);
+    g1_compress(out96, &aff[0]); g1_compress(out96 + 48, &aff[1]);
+    *verified = empty || cell_batch_pairing(c, aff);
     return rc;
 }
 
@@ -719,10 +750,11 @@ int oracle_verify_blob_kzg_proof(const oracle_ctx *c, const uint8_t *blob, const
     free(v);
     return rc;
 }
-/* verify_blob_kzg_proof_batch (eip4844/src/verifier.rs:81-143, :201-262; kzg_single_open/src/verifier.rs:59-108) */
-int oracle_verify_blob_kzg_proof_batch(const oracle_ctx *c, size_t n_blobs, const uint8_t *blobs, size_t n_commitments,
-                                       const uint8_t *commitments, size_t n_proofs, const uint8_t *proofs, int *verified) {
-    *verified = 0;
+/* verify_blob_kzg_proof_batch (eip4844/src/verifier.rs:81-143, :201-262; kzg_single_open/src/verifier.rs:59-108) up to the pairing
+   check: the weight challenge r and the two normalised sums, aff[0] = rhs = sum r^i pi_i (paired with [tau]_2) and aff[1] = lhs =
+   sum r^i C_i - (sum r^i y_i) G + sum r^i z_i pi_i (paired with -[1]_2).  Both exports below go through this one function. */
+static int blob_batch_pairing_inputs(const oracle_ctx *c, size_t n_blobs, const uint8_t *blobs, size_t n_commitments,
+                                     const uint8_t *commitments, size_t n_proofs, const uint8_t *proofs, fr_t *r_out, g1a_t aff[2]) {
     if (!(n_blobs == n_commitments && n_blobs == n_proofs)) return ORACLE_ERR_INPUT;
     size_t n = n_blobs;
     int rc = ORACLE_OK;
@@ -752,6 +784,7 @@ int oracle_verify_blob_kzg_proof_batch(const oracle_ctx *c, size_t n_blobs, cons
         }
         uint8_t dig[32]; sha256(dig, hin, hlen); free(hin);
         fr_t r; fr_from_be_reduce(&r, dig);
+        *r_out = r;
         /* lhs = sum r^i C_i - (sum r^i y_i) G + sum r^i z_i pi_i ; rhs = sum r^i pi_i */
         g1a_t *pts = malloc((2 * n + 1) * sizeof(g1a_t)); fr_t *sc = malloc((2 * n + 1) * sizeof(fr_t));
         fr_t cur = FR_ONE, ysum = FR_ZERO;
@@ -763,14 +796,36 @@ int oracle_verify_blob_kzg_proof_batch(const oracle_ctx *c, size_t n_blobs, cons
         }
         pts[n] = c->g1s[0]; fr_neg(&sc[n], &ysum);
         g1_t both[2];
-        g1_msm(&both[0], pts, sc, 2 * n + 1);
-        g1_msm(&both[1], pi, sc, n);   /* sc[0..n) = r^i */
-        g1a_t aff[2]; g1_batch_normalize(aff, both, 2);
-        g2a_t q[2] = {c->neg_g2_gen, c->tau_g2};
-        *verified = pairing_product_is_one(aff, q, 2);
+        g1_msm(&both[0], pi, sc, n);   /* sc[0..n) = r^i */
+        g1_msm(&both[1], pts, sc, 2 * n + 1);
+        g1_batch_normalize(aff, both, 2);
         free(pts); free(sc);
     }
     free(polys); free(cm); free(pi); free(zs); free(ys);
+    return rc;
+}
+static int blob_batch_pairing(const oracle_ctx *c, const g1a_t aff[2]) {
+    g2a_t q[2] = {c->tau_g2, c->neg_g2_gen};
+    return pairing_product_is_one(aff, q, 2);
+}
+int oracle_verify_blob_kzg_proof_batch(const oracle_ctx *c, size_t n_blobs, const uint8_t *blobs, size_t n_commitments,
+                                       const uint8_t *commitments, size_t n_proofs, const uint8_t *proofs, int *verified) {
+    fr_t r; g1a_t aff[2];
+    *verified = 0;
+    int rc = blob_batch_pairing_inputs(c, n_blobs, blobs, n_commitments, commitments, n_proofs, proofs, &r, aff);
+    if (rc == ORACLE_OK) *verified = blob_batch_pairing(c, aff);
+    return rc;
+}
+int oracle_verify_blob_kzg_proof_batch_inputs(const oracle_ctx *c, size_t n_blobs, const uint8_t *blobs, size_t n_commitments,
+                                              const uint8_t *commitments, size_t n_proofs, const uint8_t *proofs,
+                                              uint8_t *r_be32, uint8_t *out96, int *verified) {
+    fr_t r; g1a_t aff[2];
+    *verified = 0;
+    int rc = blob_batch_pairing_inputs(c, n_blobs, blobs, n_commitments, commitments, n_proofs, proofs, &r, aff);
+    if (rc != ORACLE_OK) return rc;
+    fr_to_be(r_be32, &r);
+    g1_compress(out96, &aff[0]); g1_compress(out96 + 48, &aff[1]);
+    *verified = blob_batch_pairing(c, aff);
     return rc;
 }
 

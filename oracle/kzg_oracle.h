@@ -44,6 +44,14 @@ int oracle_verify_cell_kzg_proof_batch(const oracle_ctx *ctx, size_t n_commitmen
                                        size_t n_indices, const uint64_t *cell_indices,
                                        size_t n_cells, const uint8_t *cells,
                                        size_t n_proofs, const uint8_t *proofs, int *verified);
+/* The same verification, also handing out what it pairs: r_be32 = the Fiat-Shamir challenge (32 bytes, big-endian, reduced), out96 =
+   compress(sum r^k pi_k) | compress(sum w_row C_row - commit(I) + sum r^k h_k^64 pi_k), the points paired with [tau^64]_2 and -[1]_2.
+   Computed by the function oracle_verify_cell_kzg_proof_batch takes its verdict from.  An empty batch: r = 0, two identities, verified. */
+int oracle_verify_cell_kzg_proof_batch_inputs(const oracle_ctx *ctx, size_t n_commitments, const uint8_t *commitments,
+                                              size_t n_indices, const uint64_t *cell_indices,
+                                              size_t n_cells, const uint8_t *cells,
+                                              size_t n_proofs, const uint8_t *proofs,
+                                              uint8_t *r_be32, uint8_t *out96, int *verified);
 int oracle_recover_cells_and_kzg_proofs(const oracle_ctx *ctx, size_t n_cells, const uint8_t *cells,
                                         size_t n_indices, const uint64_t *cell_indices,
                                         uint8_t *out_cells, uint8_t *out_proofs);
@@ -55,6 +63,11 @@ int oracle_verify_kzg_proof(const oracle_ctx *ctx, const uint8_t *commitment, co
 int oracle_verify_blob_kzg_proof(const oracle_ctx *ctx, const uint8_t *blob, const uint8_t *commitment, const uint8_t *proof, int *verified);
 int oracle_verify_blob_kzg_proof_batch(const oracle_ctx *ctx, size_t n_blobs, const uint8_t *blobs, size_t n_commitments,
                                        const uint8_t *commitments, size_t n_proofs, const uint8_t *proofs, int *verified);
+/* ... also handing out what it pairs: r_be32 = the weights' challenge, out96 = compress(sum r^i pi_i) | compress(sum r^i C_i -
+   (sum r^i y_i) G + sum r^i z_i pi_i), the points paired with [tau]_2 and -[1]_2; same function as the verdict above. */
+int oracle_verify_blob_kzg_proof_batch_inputs(const oracle_ctx *ctx, size_t n_blobs, const uint8_t *blobs, size_t n_commitments,
+                                              const uint8_t *commitments, size_t n_proofs, const uint8_t *proofs,
+                                              uint8_t *r_be32, uint8_t *out96, int *verified);
 
 /* ---- stage-level entry points used by the kernel parity tests (canonical encodings) ---- */
 /* Fr NTT over n = 2^k elements given as 32-byte big-endian canonical scalars.

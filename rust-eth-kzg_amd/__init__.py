@@ -77,6 +77,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_g1_decompress", "eth_kzg_amd_test_field_mul", "eth_kzg_amd_test_op_info", "eth_kzg_amd_test_op",
     "eth_kzg_amd_test_table_info", "eth_kzg_amd_test_table_audit", "eth_kzg_amd_test_table_read", "eth_kzg_amd_test_table_audit_buffer",
     "eth_kzg_amd_test_sha256_many", "eth_kzg_amd_test_verify_msm",
+    "eth_kzg_amd_test_verify_cells_partial_device", "eth_kzg_amd_test_verify_blob_batch_inputs",
 ]
 
 _lib = None
@@ -188,6 +189,8 @@ def load_library():
         "eth_kzg_amd_test_table_audit_buffer": [P, C.c_int, C.c_int, C.c_int, P, P, C.c_int, P, P, P, C.c_int],
         "eth_kzg_amd_test_sha256_many": [P, U64, P, U64, P, U64, U64, P, U64, U64, P],
         "eth_kzg_amd_test_verify_msm": [P, C.c_int, U8P, C.c_int, U8P, C.c_int, U8P, C.c_int, P, P],
+        "eth_kzg_amd_test_verify_cells_partial_device": [P, U64, P, P, P, P, U64, U64, P],
+        "eth_kzg_amd_test_verify_blob_batch_inputs": [P, U64, C.c_int, P, P, P, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args

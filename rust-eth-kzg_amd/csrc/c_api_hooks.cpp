@@ -51,6 +51,19 @@ int eth_kzg_amd_test_verify_msm(const DASContext* ctx, int form, const uint8_t* 
     if (!points || !sc0 || !sc1 || !out96) return kzg::ERR_INPUT;
     return eng(ctx)->test_verify_msm(form, points, n_pts, sc0, n0, sc1, n1, out96, sub_status);
 }
+int eth_kzg_amd_test_verify_cells_partial_device(const DASContext* ctx, uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices,
+                                                 const uint8_t* d_cells, const uint8_t* d_proofs, uint64_t lo, uint64_t hi, uint8_t* out96) {
+    if (!d_commitments || !d_cell_indices || !d_cells || !d_proofs || !out96) return kzg::ERR_INPUT;
+    return eng(ctx)->test_verify_cells_partial_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, lo, hi, out96);
+}
+int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext* ctx, uint64_t n, int on_device, const void* blobs, const void* commitments,
+                                              const void* proofs, uint8_t* out96, int32_t* verified) {
+    if (!blobs || !commitments || !proofs || !out96 || !verified) return kzg::ERR_INPUT;
+    int v = 0;
+    const int rc = eng(ctx)->test_verify_blob_batch_inputs(n, on_device, blobs, commitments, proofs, out96, &v);
+    *verified = v;
+    return rc;
+}
 int eth_kzg_amd_test_op_info(int op, int32_t* in_words, int32_t* out_words, int32_t* device_only, const char** name) {
     int i, o, d;
     const char* nm;

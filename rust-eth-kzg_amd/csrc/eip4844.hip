@@ -172,7 +172,7 @@ int Engine::compute_blob_kzg_proof_host(const uint8_t* blob, const uint8_t* comm
 
 // e(sum_i a_i P_i, -[1]_2) * e(sum_i b_i Q_i, [tau]_2) == 1 with the two sums done as bucket MSMs on the GPU.
 // d_points: [n_total] affine (job 0 = first n0 with sc0, job 1 = all n1 with sc1).  Returns 1 / 0.
-int Engine::pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0, const std::vector<Fr8>& sc1) {
+int Engine::pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0, const std::vector<Fr8>& sc1, G1Affine* sums2) {
     hipStream_t st = stream_;
     const int n0 = (int)sc0.size(), n1 = (int)sc1.size();
     PoolBuf d_s0(*this, (size_t)n0 * 32), d_s1(*this, (size_t)n1 * 32), d_ws(*this, launch::pip_workspace_bytes(n1 > n0 ? n1 : n0)), d_out(*this, 2 * sizeof(G1Affine));
@@ -183,6 +183,7 @@ int Engine::pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0
     HIPCK(hipMemcpyAsync(out, d_out.p, sizeof out, hipMemcpyDeviceToHost, st));
     SYNC_CHECKED(st);
     // out[0] = rhs (pairs with [tau]_2), out[1] = lhs (pairs with -[1]_2)
+    if (sums2) { sums2[0] = out[0]; sums2[1] = out[1]; }
     const pairing::G2Prepared* q[2] = {g2_tau1_.get(), g2_neg_gen_.get()};
     return pairing::product_is_one(out, q, 2) ? 1 : 0;
 }
@@ -262,7 +263,7 @@ int Engine::verify_kzg_proof_host(const uint8_t* commitment, const uint8_t* z_by
 // and evaluations y_i (canonical) are known, d_points = [proofs n | commitments n | room for G] holds the decoded points.
 // Hashes the weight r on the host (one short message), forms the two scalar lists and runs the bucket MSMs + pairing.  Returns 1 / 0.
 int Engine::finish_verify_blob_batch(int n, const Fr8* z_mont, const Fr8* y_canon, const uint8_t* const* commitments,
-                                     const uint8_t* const* proofs, const void* d_points) {
+                                     const uint8_t* const* proofs, const void* d_points, G1Affine* sums2) {
     void* d_pts = const_cast<void*>(d_points);
     launch::copy_affine(d_srs_, (G1Affine*)d_pts + 2 * n, 1, stream_);
     // compute_r_powers_for_verify_kzg_proof_batch (verifier.rs:201-262)
@@ -299,12 +300,12 @@ int Engine::finish_verify_blob_batch(int n, const Fr8* z_mont, const Fr8* y_cano
         cur = mul(cur, r);
     }
     s1[2 * n] = canon8(neg(ysum));
-    return pairing_check_4844(d_pts, s0, s1);
+    return pairing_check_4844(d_pts, s0, s1, sums2);
 }
 
 int Engine::verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* const* blobs, uint64_t n_commitments,
                                              const uint8_t* const* commitments, uint64_t n_proofs, const uint8_t* const* proofs,
-                                             int* verified) {
+                                             int* verified, G1Affine* sums2) {
     *verified = 0;
     if (!(n_blobs == n_commitments && n_blobs == n_proofs)) return ERR_INPUT;  // eip4844/src/verifier.rs:87-95
     const int n = (int)n_blobs;
@@ -325,7 +326,7 @@ int Engine::verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* co
         if (n) check_points(this, pb.data(), 2 * n, d_pts.p, pst.data(), stream_, beta_);
         for (int i = 0; i < n; i++) if (pst[n + i]) return ERR_G1;          // then commitments,
         for (int i = 0; i < n; i++) if (pst[i]) return ERR_G1;              // then proofs (verifier.rs:97-113)
-        *verified = finish_verify_blob_batch(n, z8.data(), y8.data(), commitments, proofs, d_pts.p);
+        *verified = finish_verify_blob_batch(n, z8.data(), y8.data(), commitments, proofs, d_pts.p, sums2);
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;
@@ -579,7 +580,7 @@ int Engine::compute_kzg_proof_batch_host(int n, const uint8_t* const* blobs, con
 // sub-batches, commitments and proofs decompressed where they lie.  Down: z, y, the status words and the 96 n point bytes the
 // weights' transcript hashes.  Then exactly the host form's second half.
 int Engine::verify_blob_kzg_proof_batch_device(uint64_t n64, const uint8_t* d_blobs, const uint8_t* d_commitments, const uint8_t* d_proofs,
-                                               int* verified, hipStream_t user_stream) {
+                                               int* verified, hipStream_t user_stream, G1Affine* sums2) {
     *verified = 0;
     if (n64 == 0) { *verified = 1; return OK; }  // an empty batch verifies, as in the host form
     if (n64 > (1u << 24)) return ERR_INPUT;
@@ -619,7 +620,7 @@ int Engine::verify_blob_kzg_proof_batch_device(uint64_t n64, const uint8_t* d_bl
         for (int i = 0; i < n; i++) if (pst[n + i]) return ERR_G1;          // then commitments,
         for (int i = 0; i < n; i++) if (pst[i]) return ERR_G1;              // then proofs (verifier.rs:97-113)
         for (int i = 0; i < n; i++) { pp[i] = pb.data() + (size_t)i * 48; cp[i] = pb.data() + (size_t)(n + i) * 48; }
-        *verified = finish_verify_blob_batch(n, z8.data(), y8.data(), cp.data(), pp.data(), d_pts.p);
+        *verified = finish_verify_blob_batch(n, z8.data(), y8.data(), cp.data(), pp.data(), d_pts.p, sums2);
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;

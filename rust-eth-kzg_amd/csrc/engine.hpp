@@ -185,9 +185,10 @@ public:
     int compute_blob_kzg_proof_host(const uint8_t* blob, const uint8_t* commitment, uint8_t* out_proof);
     int verify_kzg_proof_host(const uint8_t* commitment, const uint8_t* z, const uint8_t* y, const uint8_t* proof, int* verified);
     int verify_blob_kzg_proof_host(const uint8_t* blob, const uint8_t* commitment, const uint8_t* proof, int* verified);
+    // sums2 (here and in the device form; null in every product call): receives the two sums the pairing check pairs, rhs then lhs
     int verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* const* blobs, uint64_t n_commitments,
                                          const uint8_t* const* commitments, uint64_t n_proofs, const uint8_t* const* proofs,
-                                         int* verified);
+                                         int* verified, G1Affine* sums2 = nullptr);
     // ---- EIP-4844 proofs for MANY blobs (eip4844.hip; crates/eip4844/src/prover.rs:37-92 per blob) ----
     // Device-resident: d_blobs n * 131072 B, d_commitments / d_out_proofs n * 48 B, d_z / d_out_y n * 32 B big-endian (4-byte aligned);
     // h_status: n ints on the host or null.  status per blob in the single call's order: 1 the blob holds a non-canonical element,
@@ -207,7 +208,7 @@ public:
     // verify_blob_kzg_proof_batch (verifier.rs:80-196) on flat arrays in HBM: challenges and evaluations on the GPU, points decompressed
     // where they lie; the n * 160 bytes of the weights' transcript come down.  Synchronous; verdict and error split of the host form.
     int verify_blob_kzg_proof_batch_device(uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments, const uint8_t* d_proofs,
-                                           int* verified, hipStream_t stream);
+                                           int* verified, hipStream_t stream, G1Affine* sums2 = nullptr);
 
     // device-resident recovery: flat [R][128][2048] cells in HBM + a 128-bit presence mask per blob (host); see verify.hip
     int recover_cells_and_kzg_proofs_device(int R, const uint8_t* d_cells, const uint64_t* present_masks, uint8_t* d_out_cells,
@@ -232,6 +233,13 @@ public:
     // after pip_shift_prepare_and_subgroup as verify.hip launches it; h_status (n_pts ints, may be null): the points' status words
     int test_verify_msm(int form, const uint8_t* points, int n_pts, const uint8_t* sc0_be, int n0, const uint8_t* sc1_be, int n1,
                         uint8_t* out96, int32_t* h_status);
+    // the two pairing inputs of the cells [lo, hi) of a device-resident batch, compressed: verify_cells_partial behind the set-up of
+    // verify_cell_kzg_proof_batch_device (verify_cells_partial_device: the pinned mirror in chunks, the device source)
+    int test_verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
+                                         const uint8_t* d_proofs, uint64_t lo, uint64_t hi, uint8_t* out96);
+    // the two sums verify_blob_kzg_proof_batch pairs (rhs | lhs, compressed) and its verdict; on_device: flat arrays in HBM, else host pointers
+    int test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs, uint8_t* out96,
+                                      int* verified);
     // the window tables themselves (engine_testhooks.hip).  kind: TableSel; which: 0 = the complete table the next MSM launch would
     // snapshot (the view's main), 1 = the wider one under construction next to it (its ready groups), 2 = the table the context started on, while it is alive
     std::shared_ptr<SharedTable> test_table(int kind, int which) const;
@@ -304,7 +312,7 @@ private:
     Scratch4844 scratch_4844(int n);
     void fs_challenges_device(int n, const uint8_t* d_blobs, const uint8_t* d_commitments, const Scratch4844& s, hipStream_t st);
     int finish_verify_blob_batch(int n, const Fr8* z_mont, const Fr8* y_canon, const uint8_t* const* commitments, const uint8_t* const* proofs,
-                                 const void* d_points);
+                                 const void* d_points, G1Affine* sums2 = nullptr);
     // the two host-pointer batch forms (commitments: blob proofs; zs: proofs at given points) and one staged sub-batch of them
     int proofs_batch_host(int n, const uint8_t* const* blobs, const uint8_t* const* commitments, const uint8_t* const* zs,
                           uint8_t* const* out_proofs, uint8_t* const* out_ys, int* h_status);
@@ -313,7 +321,7 @@ private:
     HostPool* ensure_host_pool();  // the memcpy / hash helper threads of the host-pointer batch forms (engine_prover.hip)
     void* d_4844_ = nullptr;       // Scratch4844's arena + the 32-byte Fiat-Shamir header in front of it
     int cap_4844_ = 0;
-    int pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0, const std::vector<Fr8>& sc1);
+    int pairing_check_4844(const void* d_points, const std::vector<Fr8>& sc0, const std::vector<Fr8>& sc1, G1Affine* sums2 = nullptr);
     // dsrc (device-resident form): the cells and proofs already sit in HBM -- they are copied device to device into the arena
     // instead of being gathered on the host and uploaded; the pointer arrays then address their pinned host mirror, which the
     // transcript hash reads, and whose cells arrive in chunks (an event per chunk)
@@ -335,6 +343,10 @@ private:
                              const uint64_t* cell_indices, uint64_t n_cells, const uint8_t* const* cells, uint64_t n_proofs,
                              const uint8_t* const* proofs, uint64_t lo, uint64_t hi, G1Affine* out2, bool* empty,
                              const VerifyDeviceSource* dsrc = nullptr, VerifyScratch* vs = nullptr);
+    // the device-resident form's set-up in front of verify_cells_partial: commitments, indices and proofs down into the pinned mirror,
+    // the cells behind them in chunks with an event each, the pointer arrays over the mirror, the device source.  The CALLER holds mu_ (the mirror is the context's).
+    int verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
+                                    const uint8_t* d_proofs, uint64_t lo, uint64_t hi, G1Affine* out2, bool* empty, hipStream_t user_stream);
     bool verify_cells_pairing(const G1Affine* pts2) const;
     // the same check with the second pair's Miller loop on a thread of the staging pool (the latency path of a single verification)
     bool verify_cells_pairing_split(const G1Affine* pts2);

@@ -259,6 +259,35 @@ int Engine::test_verify_msm(int form, const uint8_t* points, int n_pts, const ui
     return OK;
 }
 
+// What the batch verifiers hand to their pairing checks, as bytes.  The device-resident cell verifier: the product's own set-up
+// (verify.hip: verify_cells_partial_device) with a range; an empty range gives two identities, as the host form's partial call.
+int Engine::test_verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
+                                             const uint8_t* d_proofs, uint64_t lo, uint64_t hi, uint8_t* out96) {
+    if (n < 1 || n > MAX_CELLS_PER_VERIFICATION || lo > hi || hi > n) return ERR_INPUT;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    G1Affine pts[2];
+    bool empty = false;
+    const int rc = verify_cells_partial_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, lo, hi, pts, &empty, nullptr);
+    if (rc) return rc;
+    g1_compress(out96, pts[0]);
+    g1_compress(out96 + 48, pts[1]);
+    return OK;
+}
+// The blob batch verifier, host or device-resident form: the product's call with the out-pointer of pairing_check_4844 set.
+int Engine::test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs,
+                                          uint8_t* out96, int* verified) {
+    if (n < 1 || n > (1u << 24)) return ERR_INPUT;  // (an empty batch verifies without a pairing check: there are no sums)
+    G1Affine sums[2] = {aff_inf(), aff_inf()};
+    const int rc = on_device ? verify_blob_kzg_proof_batch_device(n, (const uint8_t*)blobs, (const uint8_t*)commitments, (const uint8_t*)proofs, verified,
+                                                                  nullptr, sums)
+                             : verify_blob_kzg_proof_batch_host(n, (const uint8_t* const*)blobs, n, (const uint8_t* const*)commitments, n,
+                                                                (const uint8_t* const*)proofs, verified, sums);
+    if (rc) return rc;
+    g1_compress(out96, sums[0]);
+    g1_compress(out96 + 48, sums[1]);
+    return OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the window tables themselves: introspection, raw entries, the exact audit of table_audit.hpp
 std::shared_ptr<Engine::SharedTable> Engine::test_table(int kind, int which) const {

@@ -407,6 +407,16 @@ int Engine::verify_cell_kzg_proof_batch_device(uint64_t n, const uint8_t* d_comm
     std::lock_guard<std::recursive_mutex> lk(mu_);  // the pinned mirror is the context's (grow-only, reused by every call)
     G1Affine pts[2];
     bool empty = false;
+    const int rc = verify_cells_partial_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, 0, n, pts, &empty, user_stream);
+    if (rc) return rc;
+    *verified = (empty || verify_cells_pairing_split(pts)) ? 1 : 0;
+    return OK;
+}
+
+// 1 <= n <= MAX_CELLS_PER_VERIFICATION; the two partial points of the cells [lo, hi) as verify_cells_partial leaves them.
+// The caller holds mu_ (the product call above through its pairing check; the test hook for the call).
+int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
+                                        const uint8_t* d_proofs, uint64_t lo, uint64_t hi, G1Affine* pts, bool* empty, hipStream_t user_stream) {
     int rc = OK;
     try {
         std::vector<const uint8_t*> cp(n), lp(n), pp(n);  // inside the try: a bogus n must not unwind through the C ABI
@@ -444,15 +454,13 @@ int Engine::verify_cell_kzg_proof_batch_device(uint64_t n, const uint8_t* d_comm
             pp[k] = pin_p + k * 48;
         }
         const VerifyDeviceSource src{d_cells, d_proofs, vd_events_, chunk_cells, n_chunks};
-        rc = verify_cells_partial(n, cp.data(), n, reinterpret_cast<const uint64_t*>(pin_i), n, lp.data(), n, pp.data(), 0, n, pts, &empty, &src);
-        if (rc != OK) (void)hipStreamSynchronize(st);  // (an early error return: the copies into the mirror must not outlive the call)
+        rc = verify_cells_partial(n, cp.data(), n, reinterpret_cast<const uint64_t*>(pin_i), n, lp.data(), n, pp.data(), lo, hi, pts, empty, &src);
+        if (rc != OK || lo == hi) (void)hipStreamSynchronize(st);  // (an early return, error or empty range: the copies into the mirror must not outlive the call)
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;
     }
-    if (rc) return rc;
-    *verified = (empty || verify_cells_pairing_split(pts)) ? 1 : 0;
-    return OK;
+    return rc;
 }
 
 int Engine::verify_cell_kzg_proof_batch_host(uint64_t n_commitments, const uint8_t* const* commitments, uint64_t n_indices,

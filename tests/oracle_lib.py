@@ -75,6 +75,18 @@ class Oracle:
             C.c_size_t(len(cells)), b"".join(cells), C.c_size_t(len(proofs)), b"".join(proofs), C.byref(ok)))
         return bool(ok.value)
 
+    def verify_cell_kzg_proof_batch_inputs(self, commitments, cell_indices, cells, proofs):
+        """-> (r as 32 big-endian bytes, the two pairing inputs compressed (96 bytes), verdict): what verify_cell_kzg_proof_batch pairs"""
+        if any(len(c) != 48 for c in commitments) or any(len(p) != 48 for p in proofs) or \
+                any(len(c) != BYTES_PER_CELL for c in cells):
+            raise OracleError(3)
+        idx = (C.c_uint64 * max(1, len(cell_indices)))(*cell_indices)
+        ok, r, out = C.c_int(0), C.create_string_buffer(32), C.create_string_buffer(96)
+        self._chk(self.lib.oracle_verify_cell_kzg_proof_batch_inputs(
+            self.ctx, C.c_size_t(len(commitments)), b"".join(commitments), C.c_size_t(len(cell_indices)), idx,
+            C.c_size_t(len(cells)), b"".join(cells), C.c_size_t(len(proofs)), b"".join(proofs), r, out, C.byref(ok)))
+        return r.raw, out.raw, bool(ok.value)
+
     def recover_cells_and_kzg_proofs(self, cell_indices, cells):
         if any(len(c) != BYTES_PER_CELL for c in cells):
             raise OracleError(3)
@@ -195,8 +207,20 @@ def _o_verify_blob_kzg_proof_batch(self, blobs, commitments, proofs):
     return bool(ok.value)
 
 
+def _o_verify_blob_kzg_proof_batch_inputs(self, blobs, commitments, proofs):
+    """-> (r as 32 big-endian bytes, rhs | lhs compressed (96 bytes), verdict): what verify_blob_kzg_proof_batch pairs"""
+    if any(len(b) != BYTES_PER_BLOB for b in blobs) or any(len(c) != 48 for c in commitments) or any(len(p) != 48 for p in proofs):
+        raise OracleError(3)
+    ok, r, out = C.c_int(0), C.create_string_buffer(32), C.create_string_buffer(96)
+    self._chk(self.lib.oracle_verify_blob_kzg_proof_batch_inputs(
+        self.ctx, C.c_size_t(len(blobs)), b"".join(blobs), C.c_size_t(len(commitments)), b"".join(commitments),
+        C.c_size_t(len(proofs)), b"".join(proofs), r, out, C.byref(ok)))
+    return r.raw, out.raw, bool(ok.value)
+
+
 Oracle.compute_kzg_proof = _o_compute_kzg_proof
 Oracle.compute_blob_kzg_proof = _o_compute_blob_kzg_proof
 Oracle.verify_kzg_proof = _o_verify_kzg_proof
 Oracle.verify_blob_kzg_proof = _o_verify_blob_kzg_proof
 Oracle.verify_blob_kzg_proof_batch = _o_verify_blob_kzg_proof_batch
+Oracle.verify_blob_kzg_proof_batch_inputs = _o_verify_blob_kzg_proof_batch_inputs
