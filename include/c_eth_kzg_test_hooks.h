@@ -51,6 +51,16 @@ int eth_kzg_amd_test_verify_cells_partial_device(const DASContext *ctx, uint64_t
 int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext *ctx, uint64_t n, int on_device, const void *blobs, const void *commitments,
                                               const void *proofs, uint8_t *out96, int32_t *verified);
 
+/* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode, exactly the launches recovery runs).  R >= 1 blobs; blob r has
+ * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
+ * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat
+ * 128 x 2048 bytes of the extended blob, absent cells holding junk (the device-resident form's source).  Outputs, host, canonical
+ * big-endian, each may be NULL: status[R] (0, 1 non-canonical cell element, 4 inconsistent), deg[R], zp[R][65][32] (coefficients of Z',
+ * ascending), zeval[R][128][32], zcinv[R][128][32] (cell order), coeffs[R][4096][32].  Synchronous. */
+int eth_kzg_amd_test_rs_decode(const DASContext *ctx, int R, const uint64_t *n_cells, const uint64_t *const *cell_indices,
+                               const uint8_t *const *const *cells, int flat_source, int32_t *status, int32_t *deg,
+                               uint8_t *zp, uint8_t *zeval, uint8_t *zcinv, uint8_t *coeffs);
+
 /* One field or point operation of the kernels per element (csrc/k_test_ops.hip), on the raw words of the device structs.
  * eth_kzg_amd_test_op_info: word counts per element of operation `op` (0, 1, ... until it returns -1), whether it exists on the
  * device only (the pair / quad forms, the tree folds) and its name.  eth_kzg_amd_test_op: n elements of in_words each in, n of

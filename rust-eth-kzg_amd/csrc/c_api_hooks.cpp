@@ -64,6 +64,20 @@ int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext* ctx, uint64_t n,
     *verified = v;
     return rc;
 }
+int eth_kzg_amd_test_rs_decode(const DASContext* ctx, int R, const uint64_t* n_cells, const uint64_t* const* cell_indices,
+                               const uint8_t* const* const* cells, int flat_source, int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval,
+                               uint8_t* zcinv, uint8_t* coeffs) {
+    // every count and index before anything is launched: k_rec_vanishing_poly is defined for at most 64 roots, the scatter for slots < 128
+    if (R < 1 || R > 4096 || !n_cells || !cell_indices || !cells || (flat_source != 0 && flat_source != 1)) return kzg::ERR_INPUT;
+    for (int r = 0; r < R; r++) {
+        if (n_cells[r] < 64 || n_cells[r] > 128 || !cell_indices[r] || !cells[r]) return kzg::ERR_INPUT;
+        for (uint64_t k = 0; k < n_cells[r]; k++) {
+            if (cell_indices[r][k] >= 128 || (k && cell_indices[r][k - 1] >= cell_indices[r][k])) return kzg::ERR_INPUT;
+            if (!cells[r][flat_source ? 0 : k]) return kzg::ERR_INPUT;
+        }
+    }
+    return eng(ctx)->test_rs_decode(R, n_cells, cell_indices, cells, flat_source, status, deg, zp, zeval, zcinv, coeffs);
+}
 int eth_kzg_amd_test_op_info(int op, int32_t* in_words, int32_t* out_words, int32_t* device_only, const char** name) {
     int i, o, d;
     const char* nm;

@@ -240,6 +240,10 @@ public:
     // the two sums verify_blob_kzg_proof_batch pairs (rhs | lhs, compressed) and its verdict; on_device: flat arrays in HBM, else host pointers
     int test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs, uint8_t* out96,
                                       int* verified);
+    // the Reed-Solomon decoder of recovery on its own: rs_decode (verify.hip) with its tap set, behind the staging of recover_batch_to_coeffs
+    // (flat_source = 0) or of recover_cells_and_kzg_proofs_device (1); outputs canonical big-endian on the host, each may be null
+    int test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,
+                       int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval, uint8_t* zcinv, uint8_t* coeffs);
     // the window tables themselves (engine_testhooks.hip).  kind: TableSel; which: 0 = the complete table the next MSM launch would
     // snapshot (the view's main), 1 = the wider one under construction next to it (its ready groups), 2 = the table the context started on, while it is alive
     std::shared_ptr<SharedTable> test_table(int kind, int which) const;
@@ -350,8 +354,11 @@ private:
     bool verify_cells_pairing(const G1Affine* pts2) const;
     // the same check with the second pair's Miller loop on a thread of the staging pool (the latency path of a single verification)
     bool verify_cells_pairing_split(const G1Affine* pts2);
+    // tap (null in every product call; the stage hook test_rs_decode sets it): host arrays that receive what the decoder's stages left,
+    // in the kernels' Montgomery words, before their pool buffers are released -- deg[R], zp[R][65], zeval[R][128], zcinv[R][128]; each may be null
+    struct RsDecodeTap { int* deg = nullptr; Fr8 *zp = nullptr, *zeval = nullptr, *zcinv = nullptr; };
     int rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
-                  const std::vector<uint32_t>& present, int* st_out);
+                  const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap = nullptr);
     int recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_t* const* const* cells,
                                 const uint64_t* const* cell_indices, int* st_out);
     void ensure_workspace(int n);  // work_[0]; also makes stream_ wait for the last asynchronous call that used it

@@ -288,6 +288,70 @@ int Engine::test_verify_blob_batch_inputs(uint64_t n, int on_device, const void*
     return OK;
 }
 
+// The Reed-Solomon decoder of recovery on its own: the masks, slots and cell bytes staged as recover_batch_to_coeffs (list form) or
+// recover_cells_and_kzg_proofs_device (flat form) stage them, then rs_decode with its tap.  The caller (c_api_hooks.cpp) has validated
+// the counts and indices.  Outputs canonical big-endian.
+static int brp7(int v) { int r = 0; for (int i = 0; i < 7; i++) r |= ((v >> i) & 1) << (6 - i); return r; }
+static void fr_mont_to_be(uint8_t* out, const uint32_t* mont) {
+    Fr x;
+    for (int i = 0; i < 8; i++) x.v[i] = mont[i];
+    x = from_mont(x);
+    for (int i = 0; i < 8; i++) {
+        const uint32_t w = x.v[7 - i];
+        out[4 * i] = (uint8_t)(w >> 24); out[4 * i + 1] = (uint8_t)(w >> 16); out[4 * i + 2] = (uint8_t)(w >> 8); out[4 * i + 3] = (uint8_t)w;
+    }
+}
+int Engine::test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,
+                           int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval, uint8_t* zcinv, uint8_t* coeffs) {
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        ensure_workspace(R);
+        std::vector<uint32_t> present((size_t)R * 4, 0);
+        std::vector<int> slot, stof, st_out(R, OK);
+        size_t total_cells = 0;
+        for (int r = 0; r < R; r++) total_cells += n_cells[r];
+        const size_t src_bytes = (flat_source ? (size_t)R * N_CELLS : total_cells) * BYTES_PER_CELL;
+        PoolBuf h_src(*this, src_bytes, true), d_src(*this, src_bytes);
+        uint8_t* h = (uint8_t*)h_src.p;
+        size_t pos = 0;
+        for (int r = 0; r < R; r++) {
+            if (flat_source) memcpy(h + (size_t)r * N_CELLS * BYTES_PER_CELL, cells[r][0], (size_t)N_CELLS * BYTES_PER_CELL);
+            for (uint64_t k = 0; k < n_cells[r]; k++) {
+                const int c = (int)cell_indices[r][k], i = brp7(c);
+                present[(size_t)r * 4 + (i >> 5)] |= 1u << (i & 31);
+                if (!flat_source) memcpy(h + pos * BYTES_PER_CELL, cells[r][k], BYTES_PER_CELL);
+                slot.push_back(r * N_CELLS + c);
+                stof.push_back(r);
+                pos++;
+            }
+        }
+        HIPCK(hipMemcpyAsync(d_src.p, h, src_bytes, hipMemcpyHostToDevice, stream_));
+        std::vector<int> h_deg(R);
+        std::vector<Fr8> h_zp((size_t)R * 65), h_zeval((size_t)R * N_CELLS), h_zcinv((size_t)R * N_CELLS);
+        RsDecodeTap tap;
+        tap.deg = h_deg.data(); tap.zp = h_zp.data(); tap.zeval = h_zeval.data(); tap.zcinv = h_zcinv.data();
+        const int rc = rs_decode(R, (const uint8_t*)d_src.p, flat_source != 0, slot, stof, present, st_out.data(), &tap);
+        if (rc) return rc;
+        for (int r = 0; r < R; r++) {
+            if (status) status[r] = st_out[r];
+            if (deg) deg[r] = h_deg[r];
+        }
+        for (size_t i = 0; i < h_zp.size() && zp; i++) fr_mont_to_be(zp + 32 * i, h_zp[i].v);
+        for (size_t i = 0; i < h_zeval.size() && zeval; i++) fr_mont_to_be(zeval + 32 * i, h_zeval[i].v);
+        for (size_t i = 0; i < h_zcinv.size() && zcinv; i++) fr_mont_to_be(zcinv + 32 * i, h_zcinv[i].v);
+        if (coeffs) {
+            std::vector<Fr8> h_c((size_t)R * N_BLOB);
+            HIPCK(hipMemcpy(h_c.data(), d_coeffs_, h_c.size() * sizeof(Fr8), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < h_c.size(); i++) fr_mont_to_be(coeffs + 32 * i, h_c[i].v);
+        }
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // the window tables themselves: introspection, raw entries, the exact audit of table_audit.hpp
 std::shared_ptr<Engine::SharedTable> Engine::test_table(int kind, int which) const {

@@ -555,7 +555,7 @@ int Engine::recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_
 // list entry) and `present` (domain-order masks); the cell bytes are read from d_cells at list position k, or at
 // slot[k] when the caller's buffer is the flat [R][128][2048] layout.  Leaves the coefficients in d_coeffs_.
 int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
-                      const std::vector<uint32_t>& present, int* st_out) {
+                      const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap) {
     hipStream_t st = stream_;
     const int n = (int)slot.size();
     Fr seven64 = fr_u64(7);
@@ -582,6 +582,12 @@ int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std
     launch::rec_dit_last(R, d_T.p, d_coset_inv_, n_inv8192_, nullptr, d_coeffs_, (int*)d_st.p, d_w8192_, 1, st);  // ... * 7^-i
     std::vector<int> hst(R);
     HIPCK(hipMemcpyAsync(hst.data(), d_st.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (tap) {  // the stage hook: what the stages left, while the pool still holds it
+        if (tap->deg) HIPCK(hipMemcpyAsync(tap->deg, d_deg.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (tap->zp) HIPCK(hipMemcpyAsync(tap->zp, d_zp.p, (size_t)R * 65 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (tap->zeval) HIPCK(hipMemcpyAsync(tap->zeval, d_zeval.p, (size_t)R * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (tap->zcinv) HIPCK(hipMemcpyAsync(tap->zcinv, d_zcinv.p, (size_t)R * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    }
     SYNC_CHECKED(st);
     for (int r = 0; r < R; r++) {
         if (st_out[r] != OK) continue;
