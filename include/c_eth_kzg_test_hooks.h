@@ -51,7 +51,7 @@ int eth_kzg_amd_test_verify_cells_partial_device(const DASContext *ctx, uint64_t
 int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext *ctx, uint64_t n, int on_device, const void *blobs, const void *commitments,
                                               const void *proofs, uint8_t *out96, int32_t *verified);
 
-/* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode, exactly the launches recovery runs).  R >= 1 blobs; blob r has
+/* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode in recover.hip, exactly the launches recovery runs).  R >= 1 blobs; blob r has
  * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
  * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat
  * 128 x 2048 bytes of the extended blob, absent cells holding junk (the device-resident form's source).  Outputs, host, canonical

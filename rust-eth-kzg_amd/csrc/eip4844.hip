@@ -5,78 +5,10 @@
 // GPU: blob -> coefficients (k_blob_to_coeffs), quotient by (X - z) (k_quotient_by_linear), MSM against the
 // monomial SRS window table, decompression with subgroup checks, bucket MSMs of the verification equation.
 // Host: SHA-256 transcripts, the handful of Fr products of the batch weights, the 2-pairing check.
-#include "engine.hpp"
-#include "curve.hpp"
+#include "engine_internal.hpp"
 #include "host_pairing.hpp"
-#include "launch.hpp"
-#include "sha256.hpp"
-
-#include <algorithm>
-#include <cstring>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
 namespace kzg {
-
-#define HIPCK(x)                                                                                              \
-    do {                                                                                                      \
-        hipError_t e_ = (x);                                                                                  \
-        if (e_ != hipSuccess)                                                                                 \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + __FILE__ + ":" + \
-                                     std::to_string(__LINE__));                                               \
-    } while (0)
-// Kernel launches report failures only through the thread's last-error slot: look at it before trusting anything that
-// is read back after the synchronisation (a stale status word or result point must never pass for a fresh one).
-#define SYNC_CHECKED(stream)                 \
-    do {                                     \
-        HIPCK(hipGetLastError());            \
-        HIPCK(hipStreamSynchronize(stream)); \
-        HIPCK(hipGetLastError());            \
-    } while (0)
-
-static constexpr int N_BLOB = 4096, BYTES_PER_BLOB = 131072;
-
-
-static bool fr_from_be_canonical(Fr& out_mont, const uint8_t* b) {  // deserialize_bytes_to_scalar (serialization/src/lib.rs:50-63)
-    Fr x;
-    for (int i = 0; i < 8; i++)
-        x.v[7 - i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    if (geq_mod<FrParams>(x.v)) return false;
-    out_mont = to_mont(x);
-    return true;
-}
-static void fr_to_be(uint8_t* o, const Fr& canon) {
-    for (int i = 0; i < 8; i++) {
-        uint32_t w = canon.v[7 - i];
-        o[4 * i] = (uint8_t)(w >> 24); o[4 * i + 1] = (uint8_t)(w >> 16); o[4 * i + 2] = (uint8_t)(w >> 8); o[4 * i + 3] = (uint8_t)w;
-    }
-}
-static Fr reduce_be32_4844(const uint8_t* b) {  // reduce_bytes_to_scalar_bias
-    Fr x;
-    for (int i = 0; i < 8; i++)
-        x.v[7 - i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    while (geq_mod<FrParams>(x.v)) {
-        uint32_t t[8];
-        sub_limbs<8>(t, x.v, FrParams::MOD);
-        memcpy(x.v, t, 32);
-    }
-    return to_mont(x);
-}
-// compute_fiat_shamir_challenge (eip4844/src/verifier.rs:155-196)
-static Fr fs_challenge(const uint8_t* blob, const uint8_t* commitment) {
-    Sha256 sh;
-    uint8_t hdr[32];
-    memcpy(hdr, "FSBLOBVERIFY_V1_", 16);
-    memset(hdr + 16, 0, 16);
-    hdr[16 + 14] = 0x10;  // u128 big-endian 4096
-    sh.update(hdr, 32);
-    sh.update(blob, BYTES_PER_BLOB);
-    sh.update(commitment, 48);
-    uint8_t dig[32];
-    sh.finish(dig);
-    return reduce_be32_4844(dig);
-}
 
 // The device-resident core of every opening: blobs and Montgomery z_i in HBM -> y_i canonical and, if asked for, proof_i =
 // commit(quotient_i), left on the device; per-blob status words in d_status_ (non-zero: a non-canonical element).
@@ -119,17 +51,14 @@ int Engine::compute_kzg_proof_host(const uint8_t* blob, const uint8_t* z_bytes, 
         Fr z;
         bool z_ok = fr_from_be_canonical(z, z_bytes);
         if (!z_ok) z = zero<FrParams>();
-        Fr8 z8, y8;
-        memcpy(&z8, &z, 32);
+        Fr8 z8 = to8(z), y8;
         int st = 0;
         uint8_t proof[48];
         const uint8_t* bl[1] = {blob};
         open_blobs_at(1, bl, &z8, true, proof, &y8, &st);
         if (st || !z_ok) return ERR_SCALAR;  // blob elements are checked first in the reference, then z
         memcpy(out_proof, proof, 48);
-        Fr y;
-        memcpy(&y, &y8, 32);
-        fr_to_be(out_y, y);
+        fr_to_be(out_y, from8(y8));
     } catch (const std::exception& e) {
         set_error(e);
         return ERR_DEVICE;
@@ -151,9 +80,8 @@ int Engine::compute_blob_kzg_proof_host(const uint8_t* blob, const uint8_t* comm
     std::lock_guard<std::recursive_mutex> lk(mu_);
     try {
         HIPCK(hipSetDevice(dev_));
-        Fr z = fs_challenge(blob, commitment);
-        Fr8 z8, y8;
-        memcpy(&z8, &z, 32);
+        Fr z = blob_challenge(blob, commitment);
+        Fr8 z8 = to8(z), y8;
         int st = 0, cst = 0;
         uint8_t proof[48];
         const uint8_t* bl[1] = {blob};
@@ -226,7 +154,7 @@ void Engine::check_setup_powers() {
     }
 }
 
-static Fr8 canon8(const Fr& mont) { Fr c = from_mont(mont); Fr8 r; memcpy(&r, &c, 32); return r; }
+static Fr8 canon8(const Fr& mont) { return to8(from_mont(mont)); }
 
 // Verifier::verify_kzg_proof (kzg_single_open/src/verifier.rs:33-57): e(C - yG, -G2) e(pi, [tau - z]_2) == 1, evaluated as
 // e(C - yG + z pi, -G2) e(pi, [tau]_2) == 1 (bilinearity; the shape the reference's batch verifier uses, :76-107).
@@ -266,37 +194,17 @@ int Engine::finish_verify_blob_batch(int n, const Fr8* z_mont, const Fr8* y_cano
                                      const uint8_t* const* proofs, const void* d_points, G1Affine* sums2) {
     void* d_pts = const_cast<void*>(d_points);
     launch::copy_affine(d_srs_, (G1Affine*)d_pts + 2 * n, 1, stream_);
-    // compute_r_powers_for_verify_kzg_proof_batch (verifier.rs:201-262)
-    Sha256 sh;
-    uint8_t hdr[32];
-    memcpy(hdr, "RCKZGBATCH___V1_", 16);
-    for (int b = 0; b < 8; b++) { hdr[16 + b] = (uint8_t)((uint64_t)N_BLOB >> (56 - 8 * b)); hdr[24 + b] = (uint8_t)((uint64_t)n >> (56 - 8 * b)); }
-    sh.update(hdr, 32);
-    std::vector<Fr> zs(n);
-    for (int i = 0; i < n; i++) {
-        memcpy(&zs[i], &z_mont[i], 32);
-        uint8_t zy[64];
-        fr_to_be(zy, from_mont(zs[i]));
-        Fr yc;
-        memcpy(&yc, &y_canon[i], 32);
-        fr_to_be(zy + 32, yc);
-        sh.update(commitments[i], 48);
-        sh.update(zy, 64);
-        sh.update(proofs[i], 48);
-    }
-    uint8_t dig[32];
-    sh.finish(dig);
-    Fr r = reduce_be32_4844(dig);
+    std::vector<Fr> zs(n), ys(n);
+    for (int i = 0; i < n; i++) { zs[i] = from8(z_mont[i]); ys[i] = from8(y_canon[i]); }
+    const Fr r = blob_batch_weight(n, commitments, zs.data(), ys.data(), proofs);
     // lhs = sum r^i C_i - (sum r^i y_i) G + sum r^i z_i pi_i ; rhs = sum r^i pi_i   (kzg_single_open/src/verifier.rs:76-99)
     std::vector<Fr8> s0(n), s1(2 * n + 1);
     Fr cur = one<FrParams>(), ysum = zero<FrParams>();
     for (int i = 0; i < n; i++) {
-        Fr yc;
-        memcpy(&yc, &y_canon[i], 32);
         s0[i] = canon8(cur);
         s1[i] = canon8(mul(cur, zs[i]));
         s1[n + i] = s0[i];
-        ysum = add(ysum, mul(cur, to_mont(yc)));
+        ysum = add(ysum, mul(cur, to_mont(ys[i])));
         cur = mul(cur, r);
     }
     s1[2 * n] = canon8(neg(ysum));
@@ -315,7 +223,7 @@ int Engine::verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* co
         // challenges z_i and evaluations y_i = p_i(z_i)
         std::vector<Fr8> z8(n), y8(n);
         std::vector<int> bst(n);
-        for (int i = 0; i < n; i++) { const Fr z = fs_challenge(blobs[i], commitments[i]); memcpy(&z8[i], &z, 32); }
+        for (int i = 0; i < n; i++) z8[i] = to8(blob_challenge(blobs[i], commitments[i]));
         if (n) open_blobs_at(n, blobs, z8.data(), false, nullptr, y8.data(), bst.data());
         for (int i = 0; i < n; i++) if (bst[i]) return ERR_SCALAR;          // blobs first,
         // point array [proofs n | commitments n | G]
@@ -344,14 +252,13 @@ int Engine::verify_blob_kzg_proof_host(const uint8_t* blob, const uint8_t* commi
         std::lock_guard<std::recursive_mutex> lk(mu_);
         try {
             HIPCK(hipSetDevice(dev_));
-            z = fs_challenge(blob, commitment);
-            Fr8 z8, y8;
-            memcpy(&z8, &z, 32);
+            z = blob_challenge(blob, commitment);
+            Fr8 z8 = to8(z), y8;
             int bst = 0;
             const uint8_t* bl[1] = {blob};
             open_blobs_at(1, bl, &z8, false, nullptr, &y8, &bst);
             if (bst) return ERR_SCALAR;
-            memcpy(&y, &y8, 32);
+            y = from8(y8);
         } catch (const std::exception& e) {
             set_error(e);
             return ERR_DEVICE;
@@ -377,10 +284,8 @@ Engine::Scratch4844 Engine::scratch_4844(int n) {
         const int cap = ((n + 63) / 64) * 64;
         if (d_4844_) { HIPCK(hipFree(d_4844_)); d_4844_ = nullptr; cap_4844_ = 0; }
         HIPCK(hipMalloc(&d_4844_, HDR + (size_t)cap * (32 + 32 + 32 + sizeof(G1Affine) + 48 + 4 * sizeof(int))));
-        uint8_t hdr[32];  // compute_fiat_shamir_challenge's domain separator and degree (fs_challenge above)
-        memcpy(hdr, "FSBLOBVERIFY_V1_", 16);
-        memset(hdr + 16, 0, 16);
-        hdr[16 + 14] = 0x10;
+        uint8_t hdr[32];  // compute_fiat_shamir_challenge's domain separator and degree, as the host's blob_challenge hashes them
+        blob_challenge_header(hdr);
         HIPCK(hipMemcpy(d_4844_, hdr, 32, hipMemcpyHostToDevice));
         cap_4844_ = cap;
     }
@@ -398,7 +303,7 @@ Engine::Scratch4844 Engine::scratch_4844(int n) {
     s.status = (int*)p;
     return s;
 }
-// z_i = H("FSBLOBVERIFY_V1_" | 4096 | blob_i | commitment_i) mod r for blobs and commitments in HBM: one lane per blob hashes
+// z_i = H(blob_challenge_header | blob_i | commitment_i) mod r for blobs and commitments in HBM: one lane per blob hashes
 // (k_sha256.hip), one lane per digest reduces (k_4844.hip); s.z then feeds k_quotient_by_linear without a host round trip
 void Engine::fs_challenges_device(int n, const uint8_t* d_blobs, const uint8_t* d_commitments, const Scratch4844& s, hipStream_t st) {
     launch::sha256_many(n, (const uint8_t*)d_4844_, 32, d_blobs, BYTES_PER_BLOB, BYTES_PER_BLOB, d_commitments, 48, 48, s.dig, st);
@@ -505,12 +410,12 @@ int Engine::proofs_batch_host(int n, const uint8_t* const* blobs, const uint8_t*
             Fr z;
             if (commitments) {
                 memcpy(&cm[(size_t)i * 48], commitments[b0 + i], 48);
-                z = fs_challenge(dst, &cm[(size_t)i * 48]);
+                z = blob_challenge(dst, &cm[(size_t)i * 48]);
             } else if (!fr_from_be_canonical(z, zs[b0 + i])) {
                 z_ok[i] = 0;
                 z = zero<FrParams>();
             }
-            memcpy(&z8[i], &z, 32);
+            z8[i] = to8(z);
         });
         open_staged_blobs(nb, (const uint8_t*)h_in.p, z8.data(), commitments ? cm.data() : nullptr, pr.data(), y8.data(), bst.data(), cst.data());
         for (int i = 0; i < nb; i++) {
@@ -518,11 +423,7 @@ int Engine::proofs_batch_host(int n, const uint8_t* const* blobs, const uint8_t*
             if (h_status) h_status[b0 + i] = st;
             if (st) continue;
             memcpy(out_proofs[b0 + i], &pr[(size_t)i * 48], 48);
-            if (out_ys) {
-                Fr y;
-                memcpy(&y, &y8[i], 32);
-                fr_to_be(out_ys[b0 + i], y);
-            }
+            if (out_ys) fr_to_be(out_ys[b0 + i], from8(y8[i]));
         }
     }
     return OK;

@@ -248,14 +248,7 @@ Engine::Engine(bool use_precomp, int device, const Engine* primary, double table
 }
 
 void Engine::construct() {
-    const bool trace = knobs_.trace;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!trace) return;
-        auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[context] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    };
+    TraceLap lap{knobs_.trace, "context"};
     HIPCK(hipSetDevice(dev_));
     {
         int cus = 0;

@@ -1,10 +1,13 @@
 // Shared by the translation units of the engine (engine.hip: context life cycle and constants; engine_tables.hip: window tables,
-// their registry and builder; engine_prover.hip: the prover paths; engine_testhooks.hip: stage-level test hooks).  Not installed.
+// their registry and builder; engine_prover.hip: the prover paths; verify.hip, verify_many.hip, recover.hip, eip4844.hip: the other entry points;
+// engine_testhooks.hip: stage-level test hooks).  Not installed, and not for the kernel files (k_*.hip keep to kcommon.hpp).
 #pragma once
 #include "engine.hpp"
 #include "curve.hpp"
 #include "g1_linmap.hpp"
+#include "hip_check.hpp"
 #include "launch.hpp"
+#include "verify_host.hpp"  // the geometry constants (N_BLOB ... BYTES_PER_CELL)
 
 #include <algorithm>
 #include <chrono>
@@ -19,20 +22,6 @@
 
 namespace kzg {
 
-// a failed HIP call; `code` lets a caller tell an exhausted HBM (retry with a smaller sub-batch) from a broken device
-struct HipError : std::runtime_error {
-    hipError_t code;
-    HipError(hipError_t c, const std::string& what) : std::runtime_error(what), code(c) {}
-    bool out_of_memory() const { return code == hipErrorOutOfMemory || code == hipErrorMemoryAllocation; }
-};
-#define HIPCK(x)                                                                                              \
-    do {                                                                                                      \
-        hipError_t e_ = (x);                                                                                  \
-        if (e_ != hipSuccess)                                                                                 \
-            throw HipError(e_, std::string("HIP error: ") + hipGetErrorString(e_) + " at " + __FILE__ + ":" + \
-                                   std::to_string(__LINE__));                                                 \
-    } while (0)
-
 // batches up to this many lanes (blobs rounded up to 64) use the direct 8 x 16 G1 transforms (k_g1fft.hip)
 // up to how many blobs the MSM stage runs one block per MSM (k_msm_glv_flat) instead of two lanes per window: measured on one box
 // (tools/ab_flat_msm_max.sh, profiles/r6_ab_flat_msm_max.log).  With one lane per addition in the windowed kernel's tree the cross-over
@@ -42,9 +31,61 @@ struct HipError : std::runtime_error {
 #endif
 static constexpr int FLAT_MSM_MAX_SLICES = KZG_FLAT_MSM_MAX_SLICES;
 static constexpr int SIDE_CELLS_MAX = 256;  // batches up to this size compute their cells on the work set's second stream, next to the proof stages (64 blobs: 0.08 of 3.7 ms)
-static constexpr int N_BLOB = 4096, N_EXT = 8192, N_CELLS = 128, CELL_LEN = 64, BYTES_PER_BLOB = 131072, BYTES_PER_CELL = 2048;
 static_assert(sizeof(Fr) == launch::SIZEOF_FR && sizeof(G1Affine) == launch::SIZEOF_G1AFFINE && sizeof(G1Jac) == launch::SIZEOF_G1JAC, "layout");
 
+inline Fr fr_u64(uint64_t v) {  // a small integer in Montgomery form
+    Fr a = zero<FrParams>();
+    a.v[0] = (uint32_t)v;
+    a.v[1] = (uint32_t)(v >> 32);
+    return to_mont(a);
+}
+inline Fr8 to8(const Fr& a) { Fr8 r; memcpy(&r, &a, 32); return r; }
+inline Fr from8(const Fr8& a) { Fr r; memcpy(&r, &a, 32); return r; }
+
+// The scratch of the verifiers is grow-only: a block that is too small is replaced by one a quarter larger than what is asked for.
+// `busy` is the stream whose queued work may still use the old device block.  Pointer and capacity are cleared before the
+// allocation, so a failed one leaves an empty buffer and not a dangling one.
+inline void grow_device(void*& p, size_t& cap, size_t bytes, hipStream_t busy) {
+    if (bytes <= cap) return;
+    if (p) { HIPCK(hipStreamSynchronize(busy)); HIPCK(hipFree(p)); }
+    p = nullptr;
+    cap = 0;
+    HIPCK(hipMalloc(&p, bytes + (bytes >> 2)));
+    cap = bytes + (bytes >> 2);
+}
+inline void grow_pinned(uint8_t*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return;
+    if (p) HIPCK(hipHostFree(p));
+    p = nullptr;
+    cap = 0;
+    HIPCK(hipHostMalloc((void**)&p, bytes + (bytes >> 2), hipHostMallocDefault));
+    cap = bytes + (bytes >> 2);
+}
+// the layout of such a block: take `bytes`, get their offset, stay 256-byte aligned
+struct Carve {
+    size_t end = 0;
+    constexpr size_t take(size_t bytes) {
+        const size_t at = end;
+        end += (bytes + 255) & ~(size_t)255;
+        return at;
+    }
+};
+constexpr size_t carve_end(size_t first, size_t second) { Carve c; c.take(first); c.take(second); return c.end; }
+static_assert(carve_end(0, 0) == 0 && carve_end(1, 0) == 256 && carve_end(256, 1) == 512 && carve_end(257, 512) == 1024,
+              "an array of no bytes takes no room; every other one ends on the next multiple of 256");
+
+// ETH_KZG_AMD_TRACE: one line per step of a call, with the time since the step before
+struct TraceLap {
+    const bool on;
+    const char* tag;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void operator()(const char* what) {
+        if (!on) return;
+        const auto t1 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[%s] %-28s %8.3f ms\n", tag, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = t1;
+    }
+};
 double trace_clock_ms();  // milliseconds since the library first asked (ETH_KZG_AMD_TRACE lines of different threads on one time line)
 
 // A table is NOT one allocation.  Mapping 200+ GB with one hipMalloc takes the driver seconds during which every other HIP

@@ -291,7 +291,6 @@ int Engine::test_verify_blob_batch_inputs(uint64_t n, int on_device, const void*
 // The Reed-Solomon decoder of recovery on its own: the masks, slots and cell bytes staged as recover_batch_to_coeffs (list form) or
 // recover_cells_and_kzg_proofs_device (flat form) stage them, then rs_decode with its tap.  The caller (c_api_hooks.cpp) has validated
 // the counts and indices.  Outputs canonical big-endian.
-static int brp7(int v) { int r = 0; for (int i = 0; i < 7; i++) r |= ((v >> i) & 1) << (6 - i); return r; }
 static void fr_mont_to_be(uint8_t* out, const uint32_t* mont) {
     Fr x;
     for (int i = 0; i < 8; i++) x.v[i] = mont[i];

@@ -1,59 +1,16 @@
-// verify_cell_kzg_proof_batch and recover_cells_and_kzg_proofs: host orchestration.
+// verify_cell_kzg_proof_batch: host orchestration.
 // Reference: DASContext::verify_cell_kzg_proof_batch (crates/eip7594/src/verifier.rs:49-164),
 // FK20Verifier::{new, verify_multi_opening} (crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:58-260),
-// compute_fiat_shamir_challenge (:269-328), recover_polynomial_coeff (crates/eip7594/src/recovery.rs:22-151),
-// ReedSolomon::{construct_vanishing_poly_from_block_erasures, recover_polynomial_coefficient}
-// (crates/cryptography/erasure_codes/src/reed_solomon.rs:220-262,332-384).
-// Work split: all G1 / Fr batch arithmetic on the GPU; the sequential SHA-256 transcript and the
-// constant-size 2-pairing check on the host.
-#include "engine.hpp"
-#include <condition_variable>
-#include <mutex>
+// compute_fiat_shamir_challenge (:269-328).
+// Work split: all G1 / Fr batch arithmetic on the GPU; the sequential SHA-256 transcript (verify_host.hpp) and the
+// constant-size 2-pairing check on the host.  Recovery: recover.hip.
+#include "engine_internal.hpp"
 #include "curve29.hpp"
 #include "host_pairing.hpp"
-#include "launch.hpp"
-#include "sha256.hpp"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <exception>
 
 namespace kzg {
 
-#define HIPCK(x)                                                                                              \
-    do {                                                                                                      \
-        hipError_t e_ = (x);                                                                                  \
-        if (e_ != hipSuccess)                                                                                 \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + __FILE__ + ":" + \
-                                     std::to_string(__LINE__));                                               \
-    } while (0)
-// Kernel launches report failures only through the thread's last-error slot: look at it before trusting anything that
-// is read back after the synchronisation (a stale status word or result point must never pass for a fresh one).
-#define SYNC_CHECKED(stream)                 \
-    do {                                     \
-        HIPCK(hipGetLastError());            \
-        HIPCK(hipStreamSynchronize(stream)); \
-        HIPCK(hipGetLastError());            \
-    } while (0)
-
-static constexpr int N_BLOB = 4096, N_EXT = 8192, N_CELLS = 128, CELL_LEN = 64, BYTES_PER_CELL = 2048;
-
-static Fr fr_u64(uint64_t v) {
-    Fr a = zero<FrParams>();
-    a.v[0] = (uint32_t)v;
-    a.v[1] = (uint32_t)(v >> 32);
-    return to_mont(a);
-}
-static Fr8 to8(const Fr& a) { Fr8 r; memcpy(&r, &a, 32); return r; }
-static Fr from8(const Fr8& a) { Fr r; memcpy(&r, &a, 32); return r; }
-static int brp7(int v) { int r = 0; for (int i = 0; i < 7; i++) r |= ((v >> i) & 1) << (6 - i); return r; }
-
+static_assert(INPUT_VALID == OK && INPUT_INVALID == ERR_INPUT && INPUT_MAX_CELLS == MAX_CELLS_PER_VERIFICATION, "verify_host.hpp states engine.hpp's codes");
 
 void Engine::init_verifier() {
     launch::init_attributes_verify();
@@ -96,18 +53,192 @@ void Engine::init_verifier() {
     n_inv8192_ = to8(inv(fr_u64(N_EXT)));
 }
 
-// reduce_bytes_to_scalar_bias (crates/cryptography/bls12_381/src/lib.rs:128-140): 256-bit big-endian integer mod r
-static Fr reduce_be32(const uint8_t* b) {
-    Fr x;
-    for (int i = 0; i < 8; i++)
-        x.v[7 - i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    while (geq_mod<FrParams>(x.v)) {  // 2^256 < 3r: at most two subtractions
-        uint32_t t[8];
-        sub_limbs<8>(t, x.v, FrParams::MOD);
-        memcpy(x.v, t, 32);
+namespace {
+
+// Where one call's arrays lie.  Device arena: [inputs, uploaded in ONE copy | device only]; the pinned slab holds the same inputs
+// and, behind them, the read-backs.  n cells of this shard, m unique commitments of the batch.
+struct Layout {
+    const int n, m;
+    const bool shifted;  // the byte-shifted lincombs (k_verify.hip): point copies and per-cell interpolation polynomials are built behind the hash
+    const size_t npts = (size_t)n + m + 64;  // one point array [proofs n | commitments m | 64 SRS points] so that the second lincomb is a single MSM
+    const int ib = n < 256 ? n : 256;
+    const size_t sz_c = (size_t)m * 48, sz_p = (size_t)n * 48, sz_cells = (size_t)n * BYTES_PER_CELL, sz_i = (size_t)n * sizeof(int);
+    Carve d;  // (members are initialised in the order they stand here)
+    const size_t off_c = d.take(sz_c), off_p = d.take(sz_p), off_cells = d.take(sz_cells), off_idx = d.take(sz_i), off_row = d.take(sz_i), in_bytes = d.end;
+    Carve h = d;  // pinned read-back area behind the inputs: statuses (m + n + 1 ints) and room for the two result points
+    const size_t n_status = (size_t)m + n + 1, off_hst = h.take(n_status * sizeof(int)), pin_bytes = (h.take(256), h.end);
+    const size_t off_pts = d.take(npts * sizeof(G1Affine)), off_evals = d.take((size_t)n * CELL_LEN * sizeof(Fr)), off_stc = d.take((size_t)m * sizeof(int)),
+                 off_stp = d.take(sz_i), off_ste = d.take(sizeof(int)), off_rp = d.take((size_t)n * sizeof(Fr)), off_s1 = d.take((size_t)n * sizeof(Fr)),
+                 off_sB = d.take(npts * sizeof(Fr)), off_part = d.take((size_t)ib * 64 * sizeof(Fr)),
+                 off_ws = d.take(shifted ? launch::pip_shift_workspace_bytes((int)npts) : launch::pip_workspace_bytes((int)npts)),
+                 off_coef = d.take(shifted ? (size_t)n * CELL_LEN * sizeof(Fr) : 0),
+                 off_out = d.take(512),  // two affine points, or two Jacobian sums (shifted form)
+                 dev_bytes = d.end;
+    Layout(int n_, int m_, bool shifted_) : n(n_), m(m_), shifted(shifted_) {}
+};
+
+// the end of a staging task, seen from the frame whose locals the task uses
+struct StageDone {
+    std::mutex mu;
+    std::condition_variable cv;
+    bool done = false;
+    std::exception_ptr error;  // the task's; read after wait()
+    void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return done; }); }
+    void signal() { std::lock_guard<std::mutex> lk(mu); done = true; cv.notify_all(); }
+};
+
+// One call of Engine::verify_cells_partial: what its steps share, as plain values (the member function fills them in).
+struct CellPass {
+    const Layout L;
+    explicit CellPass(const Layout& l) : L(l) {}
+    int k0 = 0;  // this shard: cells k0 .. k0 + n, global exponents r^(k0 + k)
+    int dev = 0;
+    hipStream_t st = nullptr;
+    uint8_t *hb = nullptr, *db = nullptr;  // pinned slab, device arena
+    // the caller's batch
+    const uint8_t* const* uniq = nullptr;
+    const int* row = nullptr;
+    const uint64_t* cell_indices = nullptr;
+    const uint8_t* const* cells = nullptr;
+    const uint8_t* const* proofs = nullptr;
+    // device-resident form (src_cells != null): cells and proofs move inside HBM; `cells` is their pinned mirror, arriving in chunks
+    const uint8_t *src_cells = nullptr, *src_proofs = nullptr;
+    hipEvent_t* chunk_events = nullptr;
+    int chunk_cells = 0, n_chunks = 0;
+    // the engine's constants
+    const void *d_srs = nullptr, *d_w8192 = nullptr;
+    Fp12w beta;
+    Fr8 inv64;
+    hipStream_t side = nullptr;  // round 3's form (ETH_KZG_AMD_VERIFY_SIDE_STREAM=1): the subgroup tests on this second stream; null: one stream
+    hipEvent_t decoded = nullptr, checked = nullptr;
+
+    int* h_status() const { return (int*)(hb + L.off_hst); }  // pinned: [commitments m | proofs n | cells 1]; the read-backs do not block
+    G1Affine* d_proofs_aff() const { return (G1Affine*)(db + L.off_pts); }
+    G1Affine* d_commitments_aff() const { return d_proofs_aff() + L.n; }
+
+    // ---- staging, upload and deserialisation: the pool task, while the calling thread hashes the transcript
+    void stage_and_decode() const {
+        const int n = L.n, m = L.m;
+        HIPCK(hipSetDevice(dev));
+        uint8_t *hc = hb + L.off_c, *hp = hb + L.off_p, *hcells = hb + L.off_cells;
+        int *hidx = (int*)(hb + L.off_idx), *hrow = (int*)(hb + L.off_row);
+        // gather the caller's scattered buffers into ONE pinned host slab, one async copy to a persistent device arena
+        for (int i = 0; i < m; i++) memcpy(hc + (size_t)i * 48, uniq[i], 48);
+        for (int k = 0; k < n; k++) {
+            if (!src_cells) {
+                memcpy(hp + (size_t)k * 48, proofs[k0 + k], 48);
+                memcpy(hcells + (size_t)k * BYTES_PER_CELL, cells[k0 + k], BYTES_PER_CELL);
+            }
+            hidx[k] = (int)cell_indices[k0 + k];
+            hrow[k] = row[k0 + k];
+        }
+        int *d_stc = (int*)(db + L.off_stc), *d_stp = (int*)(db + L.off_stp), *d_ste = (int*)(db + L.off_ste);
+        // stale contents of the persistent arena must fail closed: poison every status word and the result slot
+        // (device side and pinned read-back side) before anything is launched
+        memset(h_status(), 0xff, L.n_status * sizeof(int));
+        HIPCK(hipMemsetAsync(d_stc, 0xff, (size_t)m * sizeof(int), st));
+        HIPCK(hipMemsetAsync(d_stp, 0xff, (size_t)n * sizeof(int), st));
+        HIPCK(hipMemsetAsync(db + L.off_out, 0xff, 512, st));
+        if (!src_cells) {
+            HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
+        } else {  // device-resident form: only the small host-made parts go up; cells and proofs move inside HBM
+            HIPCK(hipMemcpyAsync(db + L.off_c, hb + L.off_c, L.sz_c, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_idx, hb + L.off_idx, L.in_bytes - L.off_idx, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_p, src_proofs + (size_t)k0 * 48, L.sz_p, hipMemcpyDeviceToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_cells, src_cells + (size_t)k0 * BYTES_PER_CELL, L.sz_cells, hipMemcpyDeviceToDevice, st));
+        }
+        HIPCK(hipMemsetAsync(d_ste, 0, sizeof(int), st));
+        // deserialisation with on-curve + subgroup checks (serialization/src/lib.rs:69-99), on the GPU
+        const uint8_t *d_cb = db + L.off_c, *d_pb = db + L.off_p, *d_cellb = db + L.off_cells;
+        G1Affine *d_prf_p = d_proofs_aff(), *d_comm_p = d_commitments_aff();
+        void* d_evals = db + L.off_evals;
+        if (L.shifted) {
+            // decode on this stream; the subgroup tests (126 dependent doublings per point) next to everything that needs only
+            // the coordinates and not the challenge: the byte-shifted point copies (120 dependent doublings per point) and
+            // the per-cell interpolation polynomials
+            launch::g1_decode2(d_pb, d_prf_p, d_stp, n, d_cb, d_comm_p, d_stc, m, beta, st);
+            launch::copy_affine(d_srs, d_comm_p + m, 64, st);  // vk.g1s: the first 64 SRS points (verification_key.rs:66-70)
+            launch::cells_to_fr(d_cellb, d_evals, nullptr, d_ste, nullptr, nullptr, n, st);
+            if (side) {
+                HIPCK(hipEventRecord(decoded, st));
+                HIPCK(hipStreamWaitEvent(side, decoded, 0));
+                launch::g1_subgroup2(d_prf_p, d_stp, n, d_comm_p, d_stc, m, beta, side);
+                HIPCK(hipEventRecord(checked, side));
+                launch::pip_shift_prepare(d_prf_p, (int)L.npts, (int)L.npts, db + L.off_ws, beta, st);
+            } else {
+                launch::pip_shift_prepare_and_subgroup(d_prf_p, (int)L.npts, (int)L.npts, db + L.off_ws, d_prf_p, d_stp, n, d_comm_p, d_stc, m, beta, st);
+            }
+            launch::interp_cells(d_evals, (const int*)(db + L.off_idx), d_w8192, inv64, db + L.off_coef, n, st);
+            if (side) HIPCK(hipStreamWaitEvent(st, checked, 0));
+        } else {
+            launch::g1_decompress2(d_pb, d_prf_p, d_stp, n, d_cb, d_comm_p, d_stc, m, beta, st);
+            launch::copy_affine(d_srs, d_comm_p + m, 64, st);  // vk.g1s: the first 64 SRS points (verification_key.rs:66-70)
+            launch::cells_to_fr(d_cellb, d_evals, nullptr, d_ste, nullptr, nullptr, n, st);
+        }
+        int* stc = h_status();
+        HIPCK(hipMemcpyAsync(stc, d_stc, m * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(stc + m, d_stp, n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(stc + m + n, d_ste, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipGetLastError());  // launch failures are per thread: this thread's would be lost with it
     }
-    return to_mont(x);
-}
+
+    // ---- the Fiat-Shamir challenge, hashed straight from the caller's buffers while the GPU decompresses.  The transcript always
+    // covers the whole batch (n_all cells), whatever the shard.
+    Fr challenge(int n_all) const {
+        CellBatchTranscript t(L.m, n_all, uniq);
+        int chunks_in = 0;  // (device-resident form) chunks of the cells' host mirror that have arrived
+        for (int k = 0; k < n_all; k++) {
+            while (chunks_in < n_chunks && k >= chunks_in * chunk_cells) HIPCK(hipEventSynchronize(chunk_events[chunks_in++]));
+            t.absorb(row[k], cell_indices[k], cells[k], proofs[k]);
+        }
+        return t.finish();
+    }
+
+    // ---- what the decoding found, in the order of the reference: commitments, proofs, cells
+    int read_verdicts() const {
+        const int *stc = h_status(), *stp = stc + L.m, *ste = stp + L.n;
+        for (int i = 0; i < L.m; i++) if (stc[i]) return ERR_G1;
+        for (int i = 0; i < L.n; i++) if (stp[i]) return ERR_G1;
+        return *ste ? ERR_SCALAR : OK;
+    }
+
+    // ---- the scalars from the challenge, then the four lincombs (verifier.rs:186,200,224,235) as two bucket MSMs over the shared
+    // point array:   out[0] = sum r^k pi_k;   out[1] = sum r^k h^64 pi_k + sum w_row C_row - commit(interpolation poly)
+    void scalars_and_lincombs(const Fr& r, G1Affine* out) const {
+        const int n = L.n, m = L.m;
+        Fr8 tab[24];
+        Fr cur = r;
+        for (int i = 0; i < 24; i++) { tab[i] = to8(cur); cur = sqr(cur); }
+        const int* d_idx = (const int*)(db + L.off_idx);
+        void *d_rp = db + L.off_rp, *d_s1 = db + L.off_s1, *d_sB = db + L.off_sB, *d_part = db + L.off_part;
+        Fr* d_s2 = (Fr*)d_sB;
+        Fr* d_w = d_s2 + n;
+        Fr* d_interp = d_w + m;
+        launch::verify_scalars(tab, k0, d_idx, d_w8192, d_rp, d_s1, d_s2, n, st);
+        launch::verify_weights(d_rp, (const int*)(db + L.off_row), d_w, n, m, st);
+        if (L.shifted) launch::interp_sum(db + L.off_coef, d_rp, d_part, L.ib, d_interp, n, st);
+        else launch::interp(db + L.off_evals, d_idx, d_rp, d_w8192, inv64, d_part, L.ib, d_interp, n, st);
+        void *d_ws = db + L.off_ws, *d_out = db + L.off_out;
+        if (L.shifted) {
+            launch::msm_pippenger2_shifted(d_s1, n, d_sB, n + m + 64, (int)L.npts, d_ws, d_out, st);
+            JacQ sums[2];
+            HIPCK(hipMemcpyAsync(sums, d_out, sizeof sums, hipMemcpyDeviceToHost, st));
+            SYNC_CHECKED(st);
+            for (int i = 0; i < 2; i++) {
+                if (sums[i].x.v[0] == 0xffffffffu && sums[i].z.v[0] == 0xffffffffu) throw std::runtime_error("verification MSM left no result");
+                out[i] = to_affine(jac_from_jacq(sums[i]));
+            }
+        } else {
+            launch::msm_pippenger2(d_proofs_aff(), d_s1, n, d_sB, n + m + 64, d_ws, d_out, beta, st);
+            HIPCK(hipMemcpyAsync(out, d_out, 2 * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+            SYNC_CHECKED(st);
+        }
+        for (int i = 0; i < 2; i++)  // the poison pattern (or anything else that is not a reduced coordinate) is a device failure
+            if (out[i].x.v[11] > FpParams::MOD[11] || out[i].y.v[11] > FpParams::MOD[11]) throw std::runtime_error("verification MSM left no result");
+    }
+};
+
+}  // namespace
 
 // The verification equation is linear in the cells: with the challenge r taken over the WHOLE batch, the two G1
 // pairing inputs are sums of per-cell terms, so a shard [lo, hi) of the cell list yields two partial points and the
@@ -119,237 +250,55 @@ int Engine::verify_cells_partial(uint64_t n_commitments, const uint8_t* const* c
                                  G1Affine* out, bool* empty, const VerifyDeviceSource* dsrc, VerifyScratch* vs) {
     *empty = false;
     out[0] = out[1] = aff_inf();
-    // deduplicate_with_indices (verifier.rs:49-65): byte equality, first-occurrence order
-    std::vector<const uint8_t*> uniq;
-    std::vector<int> row(n_commitments);
-    {
-        std::map<std::string, int> seen;
-        for (uint64_t i = 0; i < n_commitments; i++) {
-            std::string key((const char*)commitments[i], 48);
-            auto it = seen.find(key);
-            if (it == seen.end()) { it = seen.emplace(key, (int)uniq.size()).first; uniq.push_back(commitments[i]); }
-            row[i] = it->second;
-        }
-    }
-    // validation (verifier.rs:123-164)
-    if (!(n_commitments == n_indices && n_commitments == n_cells && n_commitments == n_proofs)) return ERR_INPUT;
-    if (n_cells > MAX_CELLS_PER_VERIFICATION) return ERR_INPUT;  // (engine.hpp: the 24-entry power table, 32-bit positions)
-    for (uint64_t i = 0; i < n_indices; i++)
-        if (cell_indices[i] >= (uint64_t)N_CELLS) return ERR_INPUT;
+    if (validate_cell_batch(n_commitments, n_indices, n_cells, n_proofs, cell_indices) != OK) return ERR_INPUT;
     if (lo > hi || hi > n_cells) return ERR_INPUT;
-    const int n_all = (int)n_cells, m = (int)uniq.size();
+    const int n_all = (int)n_cells;
     if (n_all == 0) { *empty = true; return OK; }  // verifier.rs:90-93
     if (lo == hi) return OK;                       // an empty shard contributes the identity twice
-    const int n = (int)(hi - lo), k0 = (int)lo;    // this shard: cells k0 .. k0+n, global exponents r^(k0+k)
-
-    // the engine's own scratch under its lock, or a pass slot's (its holder called)
     std::unique_lock<std::recursive_mutex> lk(mu_, std::defer_lock);
-    if (!vs) lk.lock();
-    void*& a_dev = vs ? vs->dev : v_dev_;
-    size_t& a_dev_cap = vs ? vs->dev_cap : v_dev_cap_;
-    uint8_t*& a_pin = vs ? vs->pin : v_pin_;
-    size_t& a_pin_cap = vs ? vs->pin_cap : v_pin_cap_;
-    const bool two_streams = v_two_streams_ && !vs;
-    const bool trace = knobs_.trace;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!trace) return;
-        auto t1 = std::chrono::steady_clock::now();
-        fprintf(stderr, "[verify] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    };
     try {
+        std::vector<const uint8_t*> uniq;
+        std::vector<int> row;
+        dedup_commitments(n_commitments, commitments, uniq, row);  // (before the lock: it is the caller's data, and concurrent callers overlap here)
+        if (!vs) lk.lock();  // the engine's own scratch under its lock, or a pass slot's (its holder called)
+        TraceLap lap{knobs_.trace, "verify"};
         HIPCK(hipSetDevice(dev_));
         hipStream_t st = vs ? vs->stream : stream_;
-        // ---- stage inputs: gather the caller's scattered buffers into ONE pinned host slab, one async copy to a
-        // persistent device arena (no per-call hipMalloc)
-        const size_t sz_c = (size_t)m * 48, sz_p = (size_t)n * 48, sz_cells = (size_t)n * BYTES_PER_CELL, sz_i = (size_t)n * sizeof(int);
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t off_c = 0, off_p = off_c + up(sz_c), off_cells = off_p + up(sz_p), off_idx = off_cells + up(sz_cells),
-                     off_row = off_idx + up(sz_i), in_bytes = off_row + up(sz_i);
-        // pinned read-back area behind the inputs: statuses (m + n + 1 ints) and the two result points
-        const size_t off_hst = in_bytes, pin_bytes = off_hst + up(((size_t)m + n + 1) * sizeof(int)) + 256;
-        const size_t npts = (size_t)n + m + 64;
-        const int ib = n < 256 ? n : 256;
-        size_t o = up(in_bytes);
-        const size_t off_pts = o; o += up(npts * sizeof(G1Affine));
-        const size_t off_evals = o; o += up((size_t)n * CELL_LEN * sizeof(Fr));
-        const size_t off_stc = o; o += up((size_t)m * sizeof(int));
-        const size_t off_stp = o; o += up(sz_i);
-        const size_t off_ste = o; o += 256;
-        const size_t off_rp = o; o += up((size_t)n * sizeof(Fr));
-        const size_t off_s1 = o; o += up((size_t)n * sizeof(Fr));
-        const size_t off_sB = o; o += up(npts * sizeof(Fr));
-        const size_t off_part = o; o += up((size_t)ib * 64 * sizeof(Fr));
-        // large batches take the byte-shifted lincombs (k_verify.hip): point copies and per-cell interpolation polynomials
-        // are built behind the hash, so only the cheap half waits for the challenge
-        const bool shifted = n >= pip_shift_min_;
-        const size_t off_ws = o; o += up(shifted ? launch::pip_shift_workspace_bytes((int)npts) : launch::pip_workspace_bytes((int)npts));
-        const size_t off_coef = o; o += shifted ? up((size_t)n * CELL_LEN * sizeof(Fr)) : 0;
-        const size_t off_out = o; o += 512;  // two affine points, or two Jacobian sums (shifted form)
-        if (o > a_dev_cap) {
-            if (a_dev) { HIPCK(hipStreamSynchronize(st)); HIPCK(hipFree(a_dev)); }
-            a_dev = nullptr;
-            a_dev_cap = 0;
-            HIPCK(hipMalloc(&a_dev, o + (o >> 2)));
-            a_dev_cap = o + (o >> 2);
+        const int n = (int)(hi - lo);
+        const Layout L(n, (int)uniq.size(), n >= pip_shift_min_);
+        grow_device(vs ? vs->dev : v_dev_, vs ? vs->dev_cap : v_dev_cap_, L.dev_bytes, st);  // (no per-call hipMalloc)
+        grow_pinned(vs ? vs->pin : v_pin_, vs ? vs->pin_cap : v_pin_cap_, L.pin_bytes);
+        CellPass pass(L);
+        pass.k0 = (int)lo; pass.dev = dev_; pass.st = st;
+        pass.hb = vs ? vs->pin : v_pin_; pass.db = (uint8_t*)(vs ? vs->dev : v_dev_);
+        pass.uniq = uniq.data(); pass.row = row.data(); pass.cell_indices = cell_indices; pass.cells = cells; pass.proofs = proofs;
+        if (dsrc) {
+            pass.src_cells = dsrc->d_cells; pass.src_proofs = dsrc->d_proofs;
+            pass.chunk_events = dsrc->chunk_events; pass.chunk_cells = dsrc->chunk_cells; pass.n_chunks = dsrc->n_chunks;
         }
-        if (pin_bytes > a_pin_cap) {
-            if (a_pin) HIPCK(hipHostFree(a_pin));
-            a_pin = nullptr;
-            a_pin_cap = 0;
-            HIPCK(hipHostMalloc((void**)&a_pin, pin_bytes + (pin_bytes >> 2), hipHostMallocDefault));
-            a_pin_cap = pin_bytes + (pin_bytes >> 2);
-        }
-        uint8_t* hb = a_pin;
-        uint8_t* db = (uint8_t*)a_dev;
-        uint8_t *hc = hb + off_c, *hp = hb + off_p, *hcells = hb + off_cells;
-        int* hidx = (int*)(hb + off_idx);
-        int* hrow = (int*)(hb + off_row);
-        struct View { void* p; };
-        View d_cb{db + off_c}, d_pb{db + off_p}, d_cellb{db + off_cells}, d_idx{db + off_idx}, d_row{db + off_row};
-        View d_pts{db + off_pts}, d_evals{db + off_evals}, d_stc{db + off_stc}, d_stp{db + off_stp}, d_ste{db + off_ste};
-        // one point array [proofs n | commitments m | 64 SRS points] so that the second lincomb is a single MSM
-        G1Affine* d_prf_p = (G1Affine*)d_pts.p;
-        G1Affine* d_comm_p = d_prf_p + n;
-        int* stc = (int*)(hb + off_hst);  // pinned: the read-backs do not block
-        int* stp = stc + m;
-        int* ste_p = stp + n;
-        // ---- staging, upload and deserialisation run on a helper thread while this one hashes the transcript straight from
-        // the caller's buffers (the hash is the longest sequential piece of a verification)
-        std::exception_ptr stage_error;
+        pass.d_srs = d_srs_; pass.d_w8192 = d_w8192_; pass.beta = beta_; pass.inv64 = inv64_;
+        if (v_two_streams_ && !vs) pass.side = v_side_;
+        pass.decoded = v_decoded_; pass.checked = v_checked_;
         // (a worker of the engine's small persistent pool: starting and joining a fresh thread per call was 50-100 us of a 3.3 ms call)
         std::call_once(stage_pool_once_, [this] { stage_pool_.reset(new HostPool(primary_ ? 1 : 4, [d = dev_] { (void)hipSetDevice(d); })); });
-        struct StageDone {
-            std::mutex mu;
-            std::condition_variable cv;
-            bool done = false;
-            void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return done; }); }
-        } staged;
-        stage_pool_->submit([&]() {
-            struct Signal { StageDone& s; ~Signal() { std::lock_guard<std::mutex> lk(s.mu); s.done = true; s.cv.notify_all(); } } signal{staged};
+        StageDone staged;
+        stage_pool_->submit([&pass, &staged]() {
+            struct Signal { StageDone& s; ~Signal() { s.signal(); } } signal{staged};
             try {
-                HIPCK(hipSetDevice(dev_));
-                for (int i = 0; i < m; i++) memcpy(hc + (size_t)i * 48, uniq[i], 48);
-                for (int k = 0; k < n; k++) {
-                    if (!dsrc) {
-                        memcpy(hp + (size_t)k * 48, proofs[k0 + k], 48);
-                        memcpy(hcells + (size_t)k * BYTES_PER_CELL, cells[k0 + k], BYTES_PER_CELL);
-                    }
-                    hidx[k] = (int)cell_indices[k0 + k];
-                    hrow[k] = row[k0 + k];
-                }
-                // stale contents of the persistent arena must fail closed: poison every status word and the result slot
-                // (device side and pinned read-back side) before anything is launched
-                memset(stc, 0xff, ((size_t)m + n + 1) * sizeof(int));
-                HIPCK(hipMemsetAsync(d_stc.p, 0xff, (size_t)m * sizeof(int), st));
-                HIPCK(hipMemsetAsync(d_stp.p, 0xff, (size_t)n * sizeof(int), st));
-                HIPCK(hipMemsetAsync(db + off_out, 0xff, 512, st));
-                if (!dsrc) {
-                    HIPCK(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, st));
-                } else {  // device-resident form: only the small host-made parts go up; cells and proofs move inside HBM
-                    HIPCK(hipMemcpyAsync(db + off_c, hb + off_c, sz_c, hipMemcpyHostToDevice, st));
-                    HIPCK(hipMemcpyAsync(db + off_idx, hb + off_idx, in_bytes - off_idx, hipMemcpyHostToDevice, st));
-                    HIPCK(hipMemcpyAsync(db + off_p, dsrc->d_proofs + (size_t)k0 * 48, sz_p, hipMemcpyDeviceToDevice, st));
-                    HIPCK(hipMemcpyAsync(db + off_cells, dsrc->d_cells + (size_t)k0 * BYTES_PER_CELL, sz_cells, hipMemcpyDeviceToDevice, st));
-                }
-                HIPCK(hipMemsetAsync(d_ste.p, 0, sizeof(int), st));
-                // deserialisation with on-curve + subgroup checks (serialization/src/lib.rs:69-99), on the GPU
-                if (shifted) {
-                    // decode on this stream; the subgroup tests (126 dependent doublings per point) on a second stream, next to
-                    // everything that needs only the coordinates and not the challenge: the byte-shifted point copies (120
-                    // dependent doublings per point) and the per-cell interpolation polynomials
-                    launch::g1_decode2((const uint8_t*)d_pb.p, d_prf_p, (int*)d_stp.p, n, (const uint8_t*)d_cb.p, d_comm_p, (int*)d_stc.p, m, beta_, st);
-                    launch::copy_affine(d_srs_, d_comm_p + m, 64, st);  // vk.g1s: the first 64 SRS points (verification_key.rs:66-70)
-                    launch::cells_to_fr((const uint8_t*)d_cellb.p, d_evals.p, nullptr, (int*)d_ste.p, nullptr, nullptr, n, st);
-                    if (two_streams) {  // round 3's form: the subgroup tests on a second stream (ETH_KZG_AMD_VERIFY_SIDE_STREAM=1)
-                        HIPCK(hipEventRecord(v_decoded_, st));
-                        HIPCK(hipStreamWaitEvent(v_side_, v_decoded_, 0));
-                        launch::g1_subgroup2(d_prf_p, (int*)d_stp.p, n, d_comm_p, (int*)d_stc.p, m, beta_, v_side_);
-                        HIPCK(hipEventRecord(v_checked_, v_side_));
-                        launch::pip_shift_prepare(d_pts.p, (int)npts, (int)npts, db + off_ws, beta_, st);
-                    } else {
-                        launch::pip_shift_prepare_and_subgroup(d_pts.p, (int)npts, (int)npts, db + off_ws, d_prf_p, (int*)d_stp.p, n, d_comm_p,
-                                                               (int*)d_stc.p, m, beta_, st);
-                    }
-                    launch::interp_cells(d_evals.p, (const int*)d_idx.p, d_w8192_, inv64_, db + off_coef, n, st);
-                    if (two_streams) HIPCK(hipStreamWaitEvent(st, v_checked_, 0));
-                } else {
-                    launch::g1_decompress2((const uint8_t*)d_pb.p, d_prf_p, (int*)d_stp.p, n, (const uint8_t*)d_cb.p, d_comm_p, (int*)d_stc.p, m, beta_, st);
-                    launch::copy_affine(d_srs_, d_comm_p + m, 64, st);  // vk.g1s: the first 64 SRS points (verification_key.rs:66-70)
-                    launch::cells_to_fr((const uint8_t*)d_cellb.p, d_evals.p, nullptr, (int*)d_ste.p, nullptr, nullptr, n, st);
-                }
-                HIPCK(hipMemcpyAsync(stc, d_stc.p, m * sizeof(int), hipMemcpyDeviceToHost, st));
-                HIPCK(hipMemcpyAsync(stp, d_stp.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
-                HIPCK(hipMemcpyAsync(ste_p, d_ste.p, sizeof(int), hipMemcpyDeviceToHost, st));
-                HIPCK(hipGetLastError());  // launch failures are per thread: this thread's would be lost with it
+                pass.stage_and_decode();
             } catch (...) {
-                stage_error = std::current_exception();
+                staged.error = std::current_exception();
             }
         });
         struct Joiner { StageDone& s; ~Joiner() { s.wait(); } } joiner{staged};  // whatever happens below, the task has left this frame first
-        // ---- Fiat-Shamir challenge on the host while the GPU decompresses (verifier.rs:269-328).
-        // Valid inputs are canonical encodings, so the transcript is the input bytes themselves.
-        Sha256 sh;
-        auto be64 = [](uint64_t v, uint8_t* o) { for (int b = 0; b < 8; b++) o[b] = (uint8_t)(v >> (56 - 8 * b)); };
-        uint8_t hdr[16 + 32];
-        memcpy(hdr, "RCKZGCBATCH__V1_", 16);
-        be64(N_BLOB, hdr + 16); be64(CELL_LEN, hdr + 24); be64((uint64_t)m, hdr + 32); be64((uint64_t)n_all, hdr + 40);
-        sh.update(hdr, sizeof hdr);
-        for (int i = 0; i < m; i++) sh.update(uniq[i], 48);
-        int chunks_in = 0;  // (device-resident form) chunks of the cells' host mirror that have arrived
-        for (int k = 0; k < n_all; k++) {  // the transcript always covers the whole batch, whatever the shard
-            while (dsrc && chunks_in < dsrc->n_chunks && k >= chunks_in * dsrc->chunk_cells) HIPCK(hipEventSynchronize(dsrc->chunk_events[chunks_in++]));
-            uint8_t ix[16];
-            be64((uint64_t)row[k], ix); be64(cell_indices[k], ix + 8);
-            sh.update(ix, 16);
-            sh.update(cells[k], BYTES_PER_CELL);
-            sh.update(proofs[k], 48);
-        }
-        uint8_t dig[32];
-        sh.finish(dig);
-        Fr r = reduce_be32(dig);
+        const Fr r = pass.challenge(n_all);
         lap("sha256 transcript (host)");
         staged.wait();
-        if (stage_error) std::rethrow_exception(stage_error);
+        if (staged.error) std::rethrow_exception(staged.error);
         SYNC_CHECKED(st);
         lap("wait decompress/deserialise");
-        for (int i = 0; i < m; i++) if (stc[i]) return ERR_G1;  // order of the reference: commitments, proofs, cells
-        for (int i = 0; i < n; i++) if (stp[i]) return ERR_G1;
-        if (*ste_p) return ERR_SCALAR;
-
-        // ---- scalars
-        Fr8 tab[24];
-        Fr cur = r;
-        for (int i = 0; i < 24; i++) { tab[i] = to8(cur); cur = sqr(cur); }
-        View d_rp{db + off_rp}, d_s1{db + off_s1}, d_sB{db + off_sB};
-        Fr* d_s2 = (Fr*)d_sB.p;
-        Fr* d_w = d_s2 + n;
-        Fr* d_interp = d_w + m;
-        launch::verify_scalars(tab, k0, (const int*)d_idx.p, d_w8192_, d_rp.p, d_s1.p, d_s2, n, st);
-        launch::verify_weights(d_rp.p, (const int*)d_row.p, d_w, n, m, st);
-        View d_part{db + off_part};
-        if (shifted) launch::interp_sum(db + off_coef, d_rp.p, d_part.p, ib, d_interp, n, st);
-        else launch::interp(d_evals.p, (const int*)d_idx.p, d_rp.p, d_w8192_, inv64_, d_part.p, ib, d_interp, n, st);
-        // ---- the four lincombs (verifier.rs:186,200,224,235) as two bucket MSMs over the shared point array:
-        //   out[0] = sum r^k pi_k;   out[1] = sum r^k h^64 pi_k + sum w_row C_row - commit(interpolation poly)
-        View d_ws{db + off_ws}, d_out{db + off_out};
-        if (shifted) {
-            launch::msm_pippenger2_shifted(d_s1.p, n, d_sB.p, n + m + 64, (int)npts, d_ws.p, d_out.p, st);
-            JacQ sums[2];
-            HIPCK(hipMemcpyAsync(sums, d_out.p, sizeof sums, hipMemcpyDeviceToHost, st));
-            SYNC_CHECKED(st);
-            for (int i = 0; i < 2; i++) {
-                if (sums[i].x.v[0] == 0xffffffffu && sums[i].z.v[0] == 0xffffffffu) throw std::runtime_error("verification MSM left no result");
-                out[i] = to_affine(jac_from_jacq(sums[i]));
-            }
-        } else {
-            launch::msm_pippenger2(d_pts.p, d_s1.p, n, d_sB.p, n + m + 64, d_ws.p, d_out.p, beta_, st);
-            HIPCK(hipMemcpyAsync(out, d_out.p, 2 * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
-            SYNC_CHECKED(st);
-        }
-        for (int i = 0; i < 2; i++)  // the poison pattern (or anything else that is not a reduced coordinate) is a device failure
-            if (out[i].x.v[11] > FpParams::MOD[11] || out[i].y.v[11] > FpParams::MOD[11]) throw std::runtime_error("verification MSM left no result");
+        if (const int verdict = pass.read_verdicts()) return verdict;
+        pass.scalars_and_lincombs(r, out);
         lap("scalars+interp+lincombs (GPU)");
     } catch (const std::exception& e) {
         set_error(e);
@@ -423,11 +372,7 @@ int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments
         HIPCK(hipSetDevice(dev_));
         const size_t sz_c = n * 48, sz_i = n * sizeof(uint64_t), sz_l = n * (size_t)BYTES_PER_CELL, sz_p = n * 48;
         const size_t need = sz_c + sz_i + sz_l + sz_p;
-        if (need > vd_pin_cap_) {
-            if (vd_pin_) { HIPCK(hipHostFree(vd_pin_)); vd_pin_ = nullptr; vd_pin_cap_ = 0; }
-            HIPCK(hipHostMalloc((void**)&vd_pin_, need + (need >> 2), hipHostMallocDefault));
-            vd_pin_cap_ = need + (need >> 2);
-        }
+        grow_pinned(vd_pin_, vd_pin_cap_, need);
         for (hipEvent_t& e : vd_events_)
             if (!e) HIPCK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         uint8_t* pin = vd_pin_;
@@ -472,11 +417,9 @@ int Engine::verify_cell_kzg_proof_batch_host(uint64_t n_commitments, const uint8
     int st = verify_cells_partial(n_commitments, commitments, n_indices, cell_indices, n_cells, cells, n_proofs, proofs, 0,
                                   n_cells, pts, &empty);
     if (st) return st;
-    const auto t0 = std::chrono::steady_clock::now();
+    TraceLap lap{knobs_.trace, "verify"};
     *verified = (empty || verify_cells_pairing_split(pts)) ? 1 : 0;
-    if (knobs_.trace)
-        fprintf(stderr, "[verify] %-28s %8.3f ms\n", "pairing check (host)",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    lap("pairing check (host)");
     return OK;
 }
 
@@ -510,216 +453,6 @@ int Engine::verify_cell_kzg_proof_batch_combine_host(uint64_t n_partials, const 
     // no cells anywhere => both sums are the identity and the product of pairings is 1, as the reference's early return
     *verified = verify_cells_pairing(pts) ? 1 : 0;
     return OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Recovery of R blobs at once.  Per blob: validated cell list -> coefficients in d_coeffs_[r].
-// Returns per-blob statuses in `st_out`; blobs that fail validation / decoding are skipped by the caller.
-int Engine::recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_t* const* const* cells,
-                                    const uint64_t* const* cell_indices, int* st_out) {
-    hipStream_t st = stream_;
-    ensure_workspace(R);
-    // host: presence masks (domain order) and the flattened cell list; the vanishing polynomials are built on the GPU
-    std::vector<uint32_t> present((size_t)R * 4, 0xffffffffu);  // a blob that failed validation has nothing missing
-    std::vector<int> slot, stof;
-    size_t total_cells = 0;
-    for (int r = 0; r < R; r++) total_cells += st_out[r] == OK ? n_cells[r] : 0;
-    PoolBuf hcells_buf(*this, total_cells * BYTES_PER_CELL, true);  // pinned staging: the H2D copy below runs at link speed
-    uint8_t* hcells = (uint8_t*)hcells_buf.p;
-    const size_t hcells_bytes = total_cells * BYTES_PER_CELL;
-    slot.reserve(total_cells);
-    stof.reserve(total_cells);
-    size_t pos = 0;
-    for (int r = 0; r < R; r++) {
-        if (st_out[r] != OK) continue;
-        // domain-order index of a cell = bit-reversed cell index (cosets.rs:186-195); missing = complement (recovery.rs:69-75)
-        uint32_t* m = &present[(size_t)r * 4];
-        m[0] = m[1] = m[2] = m[3] = 0;
-        for (uint64_t k = 0; k < n_cells[r]; k++) {
-            const int i = brp7((int)cell_indices[r][k]);
-            m[i >> 5] |= 1u << (i & 31);
-        }
-        for (uint64_t k = 0; k < n_cells[r]; k++) {
-            memcpy(&hcells[pos * BYTES_PER_CELL], cells[r][k], BYTES_PER_CELL);
-            slot.push_back(r * N_CELLS + (int)cell_indices[r][k]);  // scatter into blob r's 128 cell slots (cosets.rs:170-175)
-            stof.push_back(r);
-            pos++;
-        }
-    }
-    PoolBuf d_cellb(*this, hcells_bytes);
-    if (total_cells) HIPCK(hipMemcpyAsync(d_cellb.p, hcells, hcells_bytes, hipMemcpyHostToDevice, st));
-    return rs_decode(R, (const uint8_t*)d_cellb.p, /*source index = list position*/ false, slot, stof, present, st_out);
-}
-
-// Reed-Solomon decode of R blobs whose present cells are listed in `slot` (blob * 128 + cell index), `stof` (blob of each
-// list entry) and `present` (domain-order masks); the cell bytes are read from d_cells at list position k, or at
-// slot[k] when the caller's buffer is the flat [R][128][2048] layout.  Leaves the coefficients in d_coeffs_.
-int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
-                      const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap) {
-    hipStream_t st = stream_;
-    const int n = (int)slot.size();
-    Fr seven64 = fr_u64(7);
-    for (int i = 0; i < 6; i++) seven64 = sqr(seven64);
-    PoolBuf d_slot(*this, (size_t)n * sizeof(int)), d_stof(*this, (size_t)n * sizeof(int));
-    PoolBuf d_E(*this, (size_t)R * N_EXT * sizeof(Fr)), d_T(*this, (size_t)R * N_EXT * sizeof(Fr)), d_U(*this, (size_t)R * N_EXT * sizeof(Fr));
-    PoolBuf d_zp(*this, (size_t)R * 65 * sizeof(Fr)), d_deg(*this, R * sizeof(int)), d_present(*this, present.size() * 4);
-    PoolBuf d_zeval(*this, (size_t)R * N_CELLS * sizeof(Fr)), d_zcinv(*this, (size_t)R * N_CELLS * sizeof(Fr)), d_st(*this, R * sizeof(int));
-    if (n) {
-        HIPCK(hipMemcpyAsync(d_slot.p, slot.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(d_stof.p, stof.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
-    }
-    HIPCK(hipMemcpyAsync(d_present.p, present.data(), present.size() * 4, hipMemcpyHostToDevice, st));
-    launch::rec_vanishing_poly((const uint32_t*)d_present.p, d_w8192_, d_zp.p, (int*)d_deg.p, R, st);
-    HIPCK(hipMemsetAsync(d_E.p, 0, (size_t)R * N_EXT * sizeof(Fr), st));
-    HIPCK(hipMemsetAsync(d_st.p, 0, R * sizeof(int), st));
-    if (n) launch::cells_to_fr(d_cells, d_E.p, (const int*)d_slot.p, (int*)d_st.p, (const int*)d_stof.p,
-                               flat_source ? (const int*)d_slot.p : nullptr, n, st);  // E in cell order
-    launch::rec_vanishing(d_zp.p, (const int*)d_deg.p, d_w8192_, to8(seven64), d_zeval.p, d_zcinv.p, R, st);
-    launch::rec_dit_half(R, d_E.p, d_zeval.p, d_T.p, d_w8192_, st);                                      // (E*Z) -> IFFT ...
-    launch::rec_dit_last(R, d_T.p, d_coset_, n_inv8192_, d_U.p, nullptr, nullptr, d_w8192_, 0, st);      // ... * 7^i
-    launch::rec_dif_half(R, d_U.p, d_zcinv.p, d_E.p, d_w8192_, st);                                      // coset FFT, / Z
-    launch::rec_dit_half(R, d_E.p, nullptr, d_T.p, d_w8192_, st);                                        // coset IFFT ...
-    launch::rec_dit_last(R, d_T.p, d_coset_inv_, n_inv8192_, nullptr, d_coeffs_, (int*)d_st.p, d_w8192_, 1, st);  // ... * 7^-i
-    std::vector<int> hst(R);
-    HIPCK(hipMemcpyAsync(hst.data(), d_st.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (tap) {  // the stage hook: what the stages left, while the pool still holds it
-        if (tap->deg) HIPCK(hipMemcpyAsync(tap->deg, d_deg.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (tap->zp) HIPCK(hipMemcpyAsync(tap->zp, d_zp.p, (size_t)R * 65 * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        if (tap->zeval) HIPCK(hipMemcpyAsync(tap->zeval, d_zeval.p, (size_t)R * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        if (tap->zcinv) HIPCK(hipMemcpyAsync(tap->zcinv, d_zcinv.p, (size_t)R * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
-    }
-    SYNC_CHECKED(st);
-    for (int r = 0; r < R; r++) {
-        if (st_out[r] != OK) continue;
-        if (hst[r] & 1) st_out[r] = ERR_SCALAR;
-        else if (hst[r] & 4) st_out[r] = ERR_RECOVERY;
-    }
-    return OK;
-}
-
-// Device-resident form: d_cells is the flat [R][128][2048] extended-blob layout in HBM, present_masks[2 r .. 2 r + 1] the
-// 128-bit set of cells that hold data (bit c of word c / 64); missing cells are never read.  Outputs as in the
-// device-resident prover call; status[r] per blob, outputs of a failed blob are unspecified.
-int Engine::recover_cells_and_kzg_proofs_device(int R, const uint8_t* d_cells, const uint64_t* present_masks, uint8_t* d_out_cells,
-                                                uint8_t* d_out_proofs, int* status, hipStream_t user_stream) {
-    if (R <= 0) return OK;
-    std::lock_guard<std::recursive_mutex> lk(mu_);
-    if (R > device_batch_max_) {  // sub-batches on the same streams (the scratch of one pass is 0.9 MB per blob): see compute_cells_and_kzg_proofs_device
-        for (int r0 = 0; r0 < R; r0 += device_batch_max_) {
-            const int nr = std::min(device_batch_max_, R - r0);
-            const int rc = recover_cells_and_kzg_proofs_device(nr, d_cells + (size_t)r0 * N_CELLS * BYTES_PER_CELL, present_masks + 2 * (size_t)r0,
-                                                               d_out_cells ? d_out_cells + (size_t)r0 * N_CELLS * BYTES_PER_CELL : nullptr,
-                                                               d_out_proofs ? d_out_proofs + (size_t)r0 * N_CELLS * 48 : nullptr, status + r0, user_stream);
-            if (rc) return rc;
-        }
-        return OK;
-    }
-    try {
-        HIPCK(hipSetDevice(dev_));
-        ensure_workspace(R);  // also orders stream_ behind the previous asynchronous call that used the workspace
-        {   // the decode runs on the library's stream: it must see what the caller's stream (NULL: the default stream) wrote into d_cells
-            HIPCK(hipEventRecord(work_[0].ev_in, user_stream));
-            HIPCK(hipStreamWaitEvent(stream_, work_[0].ev_in, 0));
-        }
-        std::vector<uint32_t> present((size_t)R * 4, 0xffffffffu);
-        std::vector<int> slot, stof;
-        for (int r = 0; r < R; r++) {
-            const uint64_t m0 = present_masks[2 * r], m1 = present_masks[2 * r + 1];
-            const int cnt = __builtin_popcountll(m0) + __builtin_popcountll(m1);
-            status[r] = cnt < N_CELLS / 2 ? ERR_INPUT : OK;  // recovery.rs:90-146: at least half of the cells
-            if (status[r] != OK) continue;
-            uint32_t* m = &present[(size_t)r * 4];
-            m[0] = m[1] = m[2] = m[3] = 0;
-            for (int c = 0; c < N_CELLS; c++) {
-                if (!(((c < 64 ? m0 : m1) >> (c & 63)) & 1)) continue;
-                const int i = brp7(c);
-                m[i >> 5] |= 1u << (i & 31);
-                slot.push_back(r * N_CELLS + c);
-                stof.push_back(r);
-            }
-        }
-        int rc = rs_decode(R, d_cells, /*flat_source=*/true, slot, stof, present, status);
-        if (rc) return rc;
-        hipStream_t st = user_stream ? user_stream : stream_;
-        if (d_out_cells) launch::coeffs_to_cells(R, d_coeffs_, d_out_cells, d_w29_, st);
-        if (d_out_proofs) run_proofs_from_coeffs(R, d_out_proofs, st);
-        HIPCK(hipEventRecord(work_[0].done, st));  // the next user of the workspace waits for these kernels (ensure_workspace)
-        HIPCK(hipGetLastError());
-        if (!user_stream) SYNC_CHECKED(st);
-    } catch (const std::exception& e) {
-        set_error(e);
-        return ERR_DEVICE;
-    }
-    return OK;
-}
-
-// validate_recovery_inputs (recovery.rs:90-146)
-static int validate_recovery(uint64_t n_cells, uint64_t n_indices, const uint64_t* cell_indices) {
-    if (n_indices != n_cells) return ERR_INPUT;
-    for (uint64_t i = 0; i < n_indices; i++)
-        if (cell_indices[i] >= (uint64_t)N_CELLS) return ERR_INPUT;
-    for (uint64_t i = 1; i < n_indices; i++)
-        if (!(cell_indices[i - 1] < cell_indices[i])) return ERR_INPUT;
-    if (n_indices < (uint64_t)N_CELLS / 2 || n_indices > (uint64_t)N_CELLS) return ERR_INPUT;
-    return OK;
-}
-
-int Engine::recover_cells_and_kzg_proofs_batch_host(int R, const uint64_t* n_cells, const uint8_t* const* const* cells,
-                                                    const uint64_t* n_indices, const uint64_t* const* cell_indices,
-                                                    uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs,
-                                                    int* status) {
-    if (R <= 0) return OK;
-    for (int r = 0; r < R; r++) status[r] = validate_recovery(n_cells[r], n_indices[r], cell_indices[r]);
-    std::lock_guard<std::recursive_mutex> lk(mu_);
-    try {
-        HIPCK(hipSetDevice(dev_));
-        const bool trace = knobs_.trace;
-        auto t0 = std::chrono::steady_clock::now();
-        auto lap = [&](const char* what) {
-            if (!trace) return;
-            auto t1 = std::chrono::steady_clock::now();
-            fprintf(stderr, "[recover] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-            t0 = t1;
-        };
-        int rc = recover_batch_to_coeffs(R, n_cells, cells, cell_indices, status);
-        if (rc) return rc;
-        lap("stage in + RS decode");
-        // compute_multi_opening_proofs(Input::PolyCoeff) = stages C..I (prover.rs:164-170) for the whole batch
-        PoolBuf d_c(*this, (size_t)R * N_CELLS * BYTES_PER_CELL), d_p(*this, (size_t)R * N_CELLS * 48);
-        launch::coeffs_to_cells(R, d_coeffs_, (uint8_t*)d_c.p, d_w29_, stream_);
-        run_proofs_from_coeffs(R, (uint8_t*)d_p.p, stream_);
-        PoolBuf hc_buf(*this, (size_t)R * N_CELLS * BYTES_PER_CELL, true), hp_buf(*this, (size_t)R * N_CELLS * 48, true);
-        const uint8_t* hc = (const uint8_t*)hc_buf.p;
-        const uint8_t* hp = (const uint8_t*)hp_buf.p;
-        HIPCK(hipMemcpyAsync(hc_buf.p, d_c.p, (size_t)R * N_CELLS * BYTES_PER_CELL, hipMemcpyDeviceToHost, stream_));
-        HIPCK(hipMemcpyAsync(hp_buf.p, d_p.p, (size_t)R * N_CELLS * 48, hipMemcpyDeviceToHost, stream_));
-        SYNC_CHECKED(stream_);
-        lap("cells + proofs + D2H");
-        for (int r = 0; r < R; r++) {
-            if (status[r] != OK) continue;
-            for (int k = 0; k < N_CELLS; k++) {
-                memcpy(out_cells[r][k], &hc[((size_t)r * N_CELLS + k) * BYTES_PER_CELL], BYTES_PER_CELL);
-                memcpy(out_proofs[r][k], &hp[((size_t)r * N_CELLS + k) * 48], 48);
-            }
-        }
-        lap("scatter to caller buffers");
-    } catch (const std::exception& e) {
-        set_error(e);
-        return ERR_DEVICE;
-    }
-    return OK;
-}
-
-int Engine::recover_cells_and_kzg_proofs_host(uint64_t n_cells, const uint8_t* const* cells, uint64_t n_indices,
-                                              const uint64_t* cell_indices, uint8_t* const* out_cells,
-                                              uint8_t* const* out_proofs) {
-    int st = OK;
-    const uint8_t* const* cl[1] = {cells};
-    const uint64_t* ix[1] = {cell_indices};
-    uint8_t* const* oc[1] = {out_cells};
-    uint8_t* const* op[1] = {out_proofs};
-    int rc = recover_cells_and_kzg_proofs_batch_host(1, &n_cells, cl, &n_indices, ix, oc, op, &st);
-    return rc ? rc : st;
 }
 
 }  // namespace kzg

@@ -1,0 +1,174 @@
+// The host's share of verification and recovery that is pure computation over bytes: input validation, de-duplication, the scalar
+// codecs and the four Fiat-Shamir transcripts, each stated ONCE for verify.hip, verify_many.hip, eip4844.hip and recover.hip.
+// No HIP call in here, everything inline: tests/c/test_verify_host.cpp runs it on the CPU against hashlib.
+// Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
+// crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
+#pragma once
+#include "field.hpp"
+#include "sha256.hpp"
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+namespace kzg {
+
+// the geometry of a blob on the host side (the kernels' copy: kcommon.hpp)
+constexpr int N_BLOB = 4096, N_EXT = 8192, N_CELLS = 128, CELL_LEN = 64, BYTES_PER_BLOB = 131072, BYTES_PER_CELL = 2048;
+// what the validations return: Status OK / ERR_INPUT and the bound MAX_CELLS_PER_VERIFICATION of engine.hpp (verify.hip asserts the three)
+constexpr int INPUT_VALID = 0, INPUT_INVALID = 3;
+constexpr uint64_t INPUT_MAX_CELLS = (1u << 24) - 1;
+
+inline void be64(uint64_t v, uint8_t* o) { for (int b = 0; b < 8; b++) o[b] = (uint8_t)(v >> (56 - 8 * b)); }
+inline int brp7(int v) { int r = 0; for (int i = 0; i < 7; i++) r |= ((v >> i) & 1) << (6 - i); return r; }
+
+// ---- scalars: 32 big-endian bytes <-> Fr
+inline Fr fr_words_from_be(const uint8_t* b) {  // the integer as it stands: neither reduced nor Montgomery
+    Fr x;
+    for (int i = 0; i < 8; i++)
+        x.v[7 - i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
+    return x;
+}
+// reduce_bytes_to_scalar_bias (crates/cryptography/bls12_381/src/lib.rs:128-140): 256-bit big-endian integer mod r, Montgomery
+inline Fr fr_from_digest(const uint8_t* b) {
+    Fr x = fr_words_from_be(b);
+    while (geq_mod<FrParams>(x.v)) {  // 2^256 < 3r: at most two subtractions
+        uint32_t t[8];
+        sub_limbs<8>(t, x.v, FrParams::MOD);
+        memcpy(x.v, t, 32);
+    }
+    return to_mont(x);
+}
+inline bool fr_from_be_canonical(Fr& out_mont, const uint8_t* b) {  // deserialize_bytes_to_scalar (serialization/src/lib.rs:50-63)
+    const Fr x = fr_words_from_be(b);
+    if (geq_mod<FrParams>(x.v)) return false;
+    out_mont = to_mont(x);
+    return true;
+}
+inline void fr_to_be(uint8_t* o, const Fr& canon) {
+    for (int i = 0; i < 8; i++) {
+        uint32_t w = canon.v[7 - i];
+        o[4 * i] = (uint8_t)(w >> 24); o[4 * i + 1] = (uint8_t)(w >> 16); o[4 * i + 2] = (uint8_t)(w >> 8); o[4 * i + 3] = (uint8_t)w;
+    }
+}
+
+// ---- the cell verifier's inputs
+// validation (verifier.rs:123-164), before anything is sized by a count or read through a pointer array
+inline int validate_cell_batch(uint64_t n_commitments, uint64_t n_indices, uint64_t n_cells, uint64_t n_proofs, const uint64_t* cell_indices) {
+    if (!(n_commitments == n_indices && n_commitments == n_cells && n_commitments == n_proofs)) return INPUT_INVALID;
+    if (n_cells > INPUT_MAX_CELLS) return INPUT_INVALID;  // (engine.hpp: the 24-entry power table, 32-bit positions)
+    for (uint64_t i = 0; i < n_indices; i++)
+        if (cell_indices[i] >= (uint64_t)N_CELLS) return INPUT_INVALID;
+    return INPUT_VALID;
+}
+// deduplicate_with_indices (verifier.rs:49-65): byte equality, first-occurrence order -> the unique commitments, the row of every entry
+inline void dedup_commitments(uint64_t n, const uint8_t* const* commitments, std::vector<const uint8_t*>& uniq, std::vector<int>& row) {
+    uniq.clear();
+    row.resize(n);
+    std::map<std::string, int> seen;
+    for (uint64_t i = 0; i < n; i++) {
+        std::string key((const char*)commitments[i], 48);
+        auto it = seen.find(key);
+        if (it == seen.end()) { it = seen.emplace(key, (int)uniq.size()).first; uniq.push_back(commitments[i]); }
+        row[i] = it->second;
+    }
+}
+// validate_recovery_inputs (recovery.rs:90-146)
+inline int validate_recovery(uint64_t n_cells, uint64_t n_indices, const uint64_t* cell_indices) {
+    if (n_indices != n_cells) return INPUT_INVALID;
+    for (uint64_t i = 0; i < n_indices; i++)
+        if (cell_indices[i] >= (uint64_t)N_CELLS) return INPUT_INVALID;
+    for (uint64_t i = 1; i < n_indices; i++)
+        if (!(cell_indices[i - 1] < cell_indices[i])) return INPUT_INVALID;
+    if (n_indices < (uint64_t)N_CELLS / 2 || n_indices > (uint64_t)N_CELLS) return INPUT_INVALID;
+    return INPUT_VALID;
+}
+
+// ---- compute_fiat_shamir_challenge of the cell verifier (fk20/verifier.rs:269-328), cell by cell: valid inputs are canonical
+// encodings, so the transcript is the input bytes themselves.  It always covers the WHOLE batch (n_all cells, m unique commitments).
+class CellBatchTranscript {
+public:
+    CellBatchTranscript(int m, int n_all, const uint8_t* const* uniq) {
+        uint8_t hdr[16 + 32];
+        memcpy(hdr, "RCKZGCBATCH__V1_", 16);
+        be64(N_BLOB, hdr + 16); be64(CELL_LEN, hdr + 24); be64((uint64_t)m, hdr + 32); be64((uint64_t)n_all, hdr + 40);
+        sh_.update(hdr, sizeof hdr);
+        for (int i = 0; i < m; i++) sh_.update(uniq[i], 48);
+    }
+    void absorb(int row, uint64_t index, const uint8_t* cell, const uint8_t* proof) {
+        uint8_t ix[16];
+        be64((uint64_t)row, ix); be64(index, ix + 8);
+        sh_.update(ix, 16);
+        sh_.update(cell, BYTES_PER_CELL);
+        sh_.update(proof, 48);
+    }
+    Fr finish() {  // the challenge r, Montgomery
+        sh_.finish(digest_);
+        return fr_from_digest(digest_);
+    }
+    const uint8_t* digest() const { return digest_; }  // after finish(): the 32 bytes r was reduced from
+private:
+    Sha256 sh_;
+    uint8_t digest_[32];
+};
+
+// ---- compute_fiat_shamir_challenge of EIP-4844 (eip4844/src/verifier.rs:155-196): H(header | blob | commitment) mod r
+inline void blob_challenge_header(uint8_t hdr[32]) {
+    memcpy(hdr, "FSBLOBVERIFY_V1_", 16);
+    memset(hdr + 16, 0, 16);
+    hdr[16 + 14] = 0x10;  // u128 big-endian 4096
+}
+inline Fr blob_challenge(const uint8_t* blob, const uint8_t* commitment) {
+    Sha256 sh;
+    uint8_t hdr[32], dig[32];
+    blob_challenge_header(hdr);
+    sh.update(hdr, 32);
+    sh.update(blob, BYTES_PER_BLOB);
+    sh.update(commitment, 48);
+    sh.finish(dig);
+    return fr_from_digest(dig);
+}
+// compute_r_powers_for_verify_kzg_proof_batch (eip4844/src/verifier.rs:201-262) -> r, Montgomery; z_i Montgomery, y_i canonical
+inline Fr blob_batch_weight(int n, const uint8_t* const* commitments, const Fr* z_mont, const Fr* y_canon, const uint8_t* const* proofs) {
+    Sha256 sh;
+    uint8_t hdr[32];
+    memcpy(hdr, "RCKZGBATCH___V1_", 16);
+    be64(N_BLOB, hdr + 16); be64((uint64_t)n, hdr + 24);
+    sh.update(hdr, 32);
+    for (int i = 0; i < n; i++) {
+        uint8_t zy[64];
+        fr_to_be(zy, from_mont(z_mont[i]));
+        fr_to_be(zy + 32, y_canon[i]);
+        sh.update(commitments[i], 48);
+        sh.update(zy, 64);
+        sh.update(proofs[i], 48);
+    }
+    uint8_t dig[32];
+    sh.finish(dig);
+    return fr_from_digest(dig);
+}
+
+// ---- folding weights of a many-verification pass: rho_i = SHA-256(seed | i) truncated to 127 bits, seed = SHA-256 over ALL the
+// challenges' digests of the pass (so no weight can be predicted before every input byte is fixed)
+inline void fold_seed(const uint8_t* digests, size_t bytes, uint8_t seed[32]) {
+    Sha256 sh;
+    sh.update((const uint8_t*)"RCKZGCBATCHFOLD1", 16);
+    sh.update(digests, bytes);
+    sh.finish(seed);
+}
+inline void fold_weight(const uint8_t seed[32], uint64_t i, uint32_t out4[4]) {
+    Sha256 sh;
+    uint8_t ix[8], dg[32];
+    be64(i, ix);
+    sh.update(seed, 32);
+    sh.update(ix, 8);
+    sh.finish(dg);
+    memcpy(out4, dg, 16);
+    out4[3] &= 0x7fffffffu;
+    if ((out4[0] | out4[1] | out4[2] | out4[3]) == 0) out4[0] = 1;  // a weight of zero would drop its problem from the check
+}
+
+}  // namespace kzg

@@ -16,42 +16,11 @@
 // Three pass slots, each with its own lock, device arena and pinned slab, on the streams of the prover's three work sets (HIP maps
 // a process's streams onto four hardware queues): passes run side by side, a large call is cut into three concurrent parts, and a
 // "pass" of one problem is the single path on the slot.  Nothing here takes the context's big lock.
-#include "engine.hpp"
+#include "engine_internal.hpp"
 #include "curve29.hpp"
 #include "host_pairing.hpp"
-#include "launch.hpp"
-#include "sha256.hpp"
-
-#include <atomic>
-#include <condition_variable>
-#include <memory>
-#include <mutex>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <exception>
-#include <map>
-#include <stdexcept>
-#include <string>
-#include <thread>
 
 namespace kzg {
-
-#define HIPCK(x)                                                                                              \
-    do {                                                                                                      \
-        hipError_t e_ = (x);                                                                                  \
-        if (e_ != hipSuccess)                                                                                 \
-            throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e_) + " at " + __FILE__ + ":" + \
-                                     std::to_string(__LINE__));                                               \
-    } while (0)
-#define SYNC_CHECKED(stream)                 \
-    do {                                     \
-        HIPCK(hipGetLastError());            \
-        HIPCK(hipStreamSynchronize(stream)); \
-        HIPCK(hipGetLastError());            \
-    } while (0)
-
-static constexpr int N_BLOB = 4096, N_CELLS = 128, CELL_LEN = 64, BYTES_PER_CELL = 2048;
 
 namespace {
 int host_threads(const Knobs& k) {
@@ -61,23 +30,215 @@ int host_threads(const Knobs& k) {
     if (k.host_threads) t = k.host_threads;
     return t;
 }
-// reduce_bytes_to_scalar_bias (crates/cryptography/bls12_381/src/lib.rs:128-140): 256-bit big-endian integer mod r
-Fr reduce_be32(const uint8_t* b) {
-    Fr x;
-    for (int i = 0; i < 8; i++)
-        x.v[7 - i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    while (geq_mod<FrParams>(x.v)) {
-        uint32_t t[8];
-        sub_limbs<8>(t, x.v, FrParams::MOD);
-        memcpy(x.v, t, 32);
-    }
-    return to_mont(x);
-}
 struct Problem {  // one verification of the call, after validation
     std::vector<const uint8_t*> uniq;  // de-duplicated commitments, first-occurrence order (verifier.rs:49-65)
     std::vector<int> row;              // per cell: index into uniq
     int n = 0, m = 0;                  // cells, unique commitments (0, 0 when the problem is skipped)
 };
+
+// Where a pass's arrays lie: n cells and m unique commitments of Bc problems.  Device arena: [inputs, uploaded in one copy |
+// power tables and folding weights, uploaded after the hashes | device only]; the pinned slab holds both uploads and the read-backs.
+struct PassLayout {
+    const int n, m, Bc;
+    const bool small;
+    const int max_ranges = std::min(Bc, 2048);  // probes per level of the search for wrong proofs
+    static constexpr size_t JACQ = launch::SIZEOF_JACQ;
+    Carve d;  // (members are initialised in the order they stand here)
+    const size_t off_p = d.take((size_t)n * 48), off_c = d.take((size_t)m * 48), off_cells = d.take((size_t)n * BYTES_PER_CELL),
+                 off_idx = d.take((size_t)n * 4), off_row = d.take((size_t)n * 4), off_bat = d.take((size_t)n * 4), off_pos = d.take((size_t)n * 4),
+                 off_rowb = d.take((size_t)m * 4), off_cs = d.take((size_t)(Bc + 1) * 4), off_rs = d.take((size_t)(Bc + 1) * 4), in_bytes = d.end;
+    const size_t off_pow = d.take((size_t)Bc * 24 * sizeof(Fr)),  // second upload (after the hashes)
+                 off_rho = d.take((size_t)Bc * 16),               // folding weights, 128 bits per problem
+                 in2_bytes = d.end;
+    Carve h = d;  // pinned read-backs behind the inputs
+    const size_t poff_st = h.take((size_t)(n + m + Bc) * 4), poff_out = h.take((size_t)2 * Bc * JACQ), poff_fold = h.take((size_t)2 * JACQ),
+                 poff_rng = h.take((size_t)max_ranges * 8), poff_rsum = h.take((size_t)2 * max_ranges * JACQ), pin_bytes = h.end;
+    // device only
+    const size_t off_pts = d.take((size_t)(n + m) * sizeof(G1Affine)), off_evals = d.take((size_t)n * CELL_LEN * sizeof(Fr)),
+                 off_coef = d.take((size_t)n * CELL_LEN * sizeof(Fr)),
+                 off_stp = d.take((size_t)(n + m) * 4),  // [proofs n | commitments m]
+                 off_ste = d.take((size_t)Bc * 4), off_rp = d.take((size_t)n * sizeof(Fr)), off_s1 = d.take((size_t)n * sizeof(Fr)),
+                 off_s2 = d.take((size_t)n * sizeof(Fr)), off_w = d.take((size_t)m * sizeof(Fr)), off_isc = d.take((size_t)Bc * 64 * sizeof(Fr)),
+                 off_icm = d.take((size_t)Bc * JACQ), off_prod = d.take((size_t)(2 * n + m + (small ? 64 * Bc : 0)) * JACQ),
+                 off_out = d.take((size_t)2 * Bc * JACQ), off_fprod = d.take((size_t)2 * Bc * JACQ), off_fold = d.take((size_t)2 * JACQ),
+                 off_rng = d.take((size_t)max_ranges * 8), off_rsum = d.take((size_t)2 * max_ranges * JACQ), dev_bytes = d.end;
+    PassLayout(int n_, int m_, int Bc_, bool small_) : n(n_), m(m_), Bc(Bc_), small(small_) {}
+};
+
+// the pairing check of two sums read back (verifier.rs:242-259; vk = [tau^64]_2, -[1]_2): 1 / 0, or -1 where the poison of the result
+// slots is still there (a device failure)
+bool poisoned(const JacQ& s) { return s.x.v[0] == 0xffffffffu && s.z.v[0] == 0xffffffffu; }
+int check_pair(const JacQ* two, const pairing::G2Prepared* const* vk) {
+    G1Affine pts[2];
+    for (int j = 0; j < 2; j++) {
+        if (poisoned(two[j])) return -1;
+        pts[j] = to_affine(jac_from_jacq(two[j]));
+    }
+    return pairing::product_is_one(pts, vk, 2) ? 1 : 0;
+}
+
+// The host's side of one pass: problems b0 .. b0 + Bc of the call (the inputs are the call's arrays from b0 on), n cells and m unique
+// commitments in all, staged into the pinned slab hb as L lays it out.  Nothing in here touches the GPU.
+struct PassHost {
+    const PassLayout& L;
+    const Problem* pr;
+    const uint64_t* const* cell_indices;
+    const uint8_t* const* const* cells;
+    const uint8_t* const* const* proofs;
+    uint8_t* hb;
+    int T;
+    HostPool* pool;
+    const pairing::G2Prepared* vk[2];        // [tau^64]_2, -[1]_2
+    int* verified;                           // verified[i] belongs to problem i of the pass
+    std::atomic<int> device_fault{0};
+    std::vector<int> cell_start, row_start;  // first cell / first unique commitment of each problem
+    std::vector<uint8_t> digests;            // of the challenges: the fold seed hashes them
+    std::vector<char> live;                  // problems that decoded without an error
+    const JacQ* sums() const { return (const JacQ*)(hb + L.poff_out); }  // the problems' two sums read back
+    int* h_status() const { return (int*)(hb + L.poff_st); }  // read-backs: [proofs n | commitments m | cells, per problem]
+
+    // gather the problems into the slab; stale contents of the persistent slab must fail closed: status words and result slots are poisoned
+    void stage() {
+        cell_start.assign(L.Bc + 1, 0); row_start.assign(L.Bc + 1, 0);
+        for (int i = 0; i < L.Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[i].n; row_start[i + 1] = row_start[i] + pr[i].m; }
+        memcpy(hb + L.off_cs, cell_start.data(), (size_t)(L.Bc + 1) * 4);
+        memcpy(hb + L.off_rs, row_start.data(), (size_t)(L.Bc + 1) * 4);
+        int *h_idx = (int*)(hb + L.off_idx), *h_row = (int*)(hb + L.off_row), *h_bat = (int*)(hb + L.off_bat), *h_pos = (int*)(hb + L.off_pos),
+            *h_rowb = (int*)(hb + L.off_rowb);
+        parallel_for(L.Bc, T, pool, [&](int i) {
+            const Problem& p = pr[i];
+            const int c0 = cell_start[i], r0 = row_start[i];
+            for (int j = 0; j < p.m; j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
+            for (int k = 0; k < p.n; k++) {
+                memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, proofs[i][k], 48);
+                memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, cells[i][k], BYTES_PER_CELL);
+                h_idx[c0 + k] = (int)cell_indices[i][k];
+                h_row[c0 + k] = r0 + p.row[k];
+                h_bat[c0 + k] = i;
+                h_pos[c0 + k] = k;
+            }
+        });
+        memset(h_status(), 0xff, (size_t)(L.n + L.m + L.Bc) * 4);
+        memset(hb + L.poff_out, 0xff, (size_t)2 * L.Bc * launch::SIZEOF_JACQ);
+        memset(hb + L.poff_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ);
+    }
+    // the Fiat-Shamir challenges on the host threads (verify_host.hpp: CellBatchTranscript), then the table r^(2^i) per problem
+    void hash_challenges() {
+        Fr* h_pow = (Fr*)(hb + L.off_pow);
+        digests.assign((size_t)L.Bc * 32, 0);
+        parallel_for(L.Bc, T, pool, [&](int i) {
+            const Problem& p = pr[i];
+            Fr* tab = h_pow + (size_t)i * 24;
+            if (p.n == 0) { for (int j = 0; j < 24; j++) tab[j] = one<FrParams>(); return; }
+            CellBatchTranscript t(p.m, p.n, p.uniq.data());
+            for (int k = 0; k < p.n; k++) t.absorb(p.row[k], cell_indices[i][k], cells[i][k], proofs[i][k]);
+            Fr cur = t.finish();
+            memcpy(&digests[(size_t)i * 32], t.digest(), 32);
+            for (int j = 0; j < 24; j++) { tab[j] = cur; cur = sqr(cur); }
+        });
+    }
+    // decoding verdicts per problem (order of the reference: commitments, proofs, cells) -> live problems; the others take no further part
+    int judge(int* status) {
+        const int* h_st = h_status();
+        live.assign(L.Bc, 0);
+        int n_live = 0;
+        for (int i = 0; i < L.Bc; i++) {
+            const Problem& p = pr[i];
+            if (p.n == 0) continue;
+            const int c0 = cell_start[i], r0 = row_start[i];
+            int bad = OK;
+            for (int j = 0; j < p.m && !bad; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
+            for (int k = 0; k < p.n && !bad; k++) if (h_st[c0 + k]) bad = ERR_G1;
+            if (!bad && h_st[L.n + L.m + i]) bad = ERR_SCALAR;
+            status[i] = bad;
+            if (!bad) { live[i] = 1; n_live++; }
+        }
+        return n_live;
+    }
+    void check_single(int i) {  // one problem's own pairing check
+        const int v = check_pair(sums() + 2 * (size_t)i, vk);
+        if (v < 0) device_fault.store(1);
+        else verified[i] = v;
+    }
+    // folding weights (verify_host.hpp: fold_seed, fold_weight); 0 for problems that are out
+    void fold_weights() {
+        uint32_t* h_rho = (uint32_t*)(hb + L.off_rho);
+        uint8_t seed[32];
+        fold_seed(digests.data(), digests.size(), seed);
+        parallel_for(L.Bc, T, pool, [&](int i) {
+            uint32_t* r4 = h_rho + 4 * (size_t)i;
+            if (live[i]) fold_weight(seed, (uint64_t)i, r4);
+            else r4[0] = r4[1] = r4[2] = r4[3] = 0;
+        });
+    }
+};
+
+// Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM (off_fprod): SEARCH for the wrong ones by
+// folding sub-ranges (k_vm_fold_ranges: one small launch per level) and checking each with one pairing on a host
+// thread -- a range whose fold passes holds only valid proofs (the same 2^-127 argument, the weights were fixed
+// after every input byte), a single problem whose weighted pair fails is wrong EXACTLY (rho_b != 0 and the
+// pairing group has prime order).  Ranges are split K ways with K chosen so that a level's probes fill the
+// host threads once: one wrong proof among 1024 costs ~36 pairings in 3 rounds instead of 1024 in 64 (round 3:
+// 85 ms per call against 29.6 ms for an all-valid one).  When wrong proofs are many the search stops paying:
+// from a quarter of the live problems suspect, the rest is checked one by one as before.
+void search_wrong_proofs(PassHost& V, int n_live, uint8_t* db, hipStream_t st) {
+    const PassLayout& L = V.L;
+    const int Bc = L.Bc, T = V.T;
+    HostPool* const pool = V.pool;
+    uint8_t* const hb = V.hb;
+    std::vector<std::pair<int, int>> suspects{{0, Bc}};
+    int* h_rng = (int*)(hb + L.poff_rng);
+    const JacQ* h_rsum = (const JacQ*)(hb + L.poff_rsum);
+    while (!suspects.empty()) {
+        long suspect_problems = 0;
+        for (auto& sr : suspects) suspect_problems += sr.second - sr.first;
+        if ((long)suspects.size() * 4 >= n_live || suspect_problems <= 2 * T) {  // few problems left, or wrong proofs everywhere
+            std::vector<int> todo;
+            for (auto& sr : suspects)
+                for (int i = sr.first; i < sr.second; i++)
+                    if (V.live[i]) todo.push_back(i);
+            parallel_for((int)todo.size(), T, pool, [&](int q) { V.check_single(todo[q]); });
+            break;
+        }
+        int K = T / (int)suspects.size();
+        K = K < 2 ? 2 : K > 16 ? 16 : K;
+        std::vector<std::pair<int, int>> probes;
+        for (auto& sr : suspects) {
+            const int len = sr.second - sr.first, parts = std::min(K, len);
+            for (int q = 0; q < parts; q++) probes.emplace_back(sr.first + (int)((long)len * q / parts), sr.first + (int)((long)len * (q + 1) / parts));
+        }
+        // a level may need more probes than the range buffers hold (max_ranges = min(Bc, 2048): e.g. > 4096 small problems
+        // with > 1024 scattered wrong proofs): it then runs in batches over the same buffers -- never an error, the
+        // valid problems of the pass keep their verdicts
+        std::vector<char> fails(probes.size(), 0);
+        for (size_t q0 = 0; q0 < probes.size() && !V.device_fault.load(); q0 += (size_t)L.max_ranges) {
+            const size_t cnt = std::min(probes.size() - q0, (size_t)L.max_ranges);
+            for (size_t q = 0; q < cnt; q++) { h_rng[2 * q] = probes[q0 + q].first; h_rng[2 * q + 1] = probes[q0 + q].second; }
+            memset(hb + L.poff_rsum, 0xff, cnt * 2 * launch::SIZEOF_JACQ);
+            HIPCK(hipMemcpyAsync(db + L.off_rng, h_rng, cnt * 8, hipMemcpyHostToDevice, st));
+            launch::vm_fold_ranges(db + L.off_fprod, (const int*)(db + L.off_rng), db + L.off_rsum, (int)cnt, st);
+            HIPCK(hipMemcpyAsync(hb + L.poff_rsum, db + L.off_rsum, cnt * 2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
+            SYNC_CHECKED(st);
+            parallel_for((int)cnt, T, pool, [&](int q) {
+                const int v = check_pair(h_rsum + 2 * (size_t)q, V.vk);
+                if (v < 0) V.device_fault.store(1);
+                else fails[q0 + q] = v ? 0 : 1;
+            });
+        }
+        if (V.device_fault.load()) break;
+        suspects.clear();
+        for (size_t q = 0; q < probes.size(); q++) {
+            const int lo = probes[q].first, hi = probes[q].second;
+            if (!fails[q]) {
+                for (int i = lo; i < hi; i++) if (V.live[i]) V.verified[i] = 1;
+            } else if (hi - lo == 1) {
+                V.verified[lo] = 0;  // exact: its own weighted pair fails the check
+            } else {
+                suspects.emplace_back(lo, hi);
+            }
+        }
+    }
+}
 }  // namespace
 
 int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint64_t* n_commitments,
@@ -145,21 +306,12 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
         // ---- per problem: validation (verifier.rs:123-164) and de-duplication
         std::vector<Problem> pr(B);
         parallel_for(B, T, pool, [&](int b) {
-            const uint64_t nc = n_commitments[b];
-            if (!(nc == n_indices[b] && nc == n_cells[b] && nc == n_proofs[b]) || nc > MAX_CELLS_PER_VERIFICATION) { status[b] = ERR_INPUT; return; }
-            for (uint64_t i = 0; i < nc; i++)
-                if (cell_indices[b][i] >= (uint64_t)N_CELLS) { status[b] = ERR_INPUT; return; }
-            if (nc == 0) { verified[b] = 1; return; }  // verifier.rs:90-93
+            status[b] = validate_cell_batch(n_commitments[b], n_indices[b], n_cells[b], n_proofs[b], cell_indices[b]);
+            if (status[b] != OK) return;
+            if (n_cells[b] == 0) { verified[b] = 1; return; }  // verifier.rs:90-93
             Problem& p = pr[b];
-            p.row.resize(nc);
-            std::map<std::string, int> seen;
-            for (uint64_t i = 0; i < nc; i++) {
-                std::string key((const char*)commitments[b][i], 48);
-                auto it = seen.find(key);
-                if (it == seen.end()) { it = seen.emplace(key, (int)p.uniq.size()).first; p.uniq.push_back(commitments[b][i]); }
-                p.row[i] = it->second;
-            }
-            p.n = (int)nc;
+            dedup_commitments(n_commitments[b], commitments[b], p.uniq, p.row);
+            p.n = (int)n_cells[b];
             p.m = (int)p.uniq.size();
         });
         // ---- chunks of problems: at most CHUNK_CELLS cells per pass (the pinned slab and the arena stay bounded)
@@ -176,306 +328,78 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             // (k_vm_mul_small), no fold (its 128-bit multiplication per problem is a 1.4 ms chain; <= 2 T pairing checks are one or
             // two rounds of the host threads) -- decode 0.45 + products 1.7 + sums 0.2 ms of GPU instead of ~6
             const bool small = vm_small_max_ != 0 && Bc <= (vm_small_max_ > 0 ? vm_small_max_ : 2 * T);
-            std::vector<int> cell_start(Bc + 1, 0), row_start(Bc + 1, 0);
-            for (int i = 0; i < Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[b0 + i].n; row_start[i + 1] = row_start[i] + pr[b0 + i].m; }
-            // ---- layout: [inputs, uploaded in one copy][device-only]; pinned slab = inputs + read-backs
-            auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-            size_t o = 0;
-            const size_t off_p = o; o += up((size_t)n * 48);
-            const size_t off_c = o; o += up((size_t)m * 48);
-            const size_t off_cells = o; o += up((size_t)n * BYTES_PER_CELL);
-            const size_t off_idx = o; o += up((size_t)n * 4);
-            const size_t off_row = o; o += up((size_t)n * 4);
-            const size_t off_bat = o; o += up((size_t)n * 4);
-            const size_t off_pos = o; o += up((size_t)n * 4);
-            const size_t off_rowb = o; o += up((size_t)m * 4);
-            const size_t off_cs = o; o += up((size_t)(Bc + 1) * 4);
-            const size_t off_rs = o; o += up((size_t)(Bc + 1) * 4);
-            const size_t in_bytes = o;
-            const size_t off_pow = o; o += up((size_t)Bc * 24 * sizeof(Fr));  // second upload (after the hashes)
-            const size_t off_rho = o; o += up((size_t)Bc * 16);               // folding weights, 128 bits per problem
-            const size_t in2_bytes = o;
-            // device only
-            const size_t off_pts = o; o += up((size_t)(n + m) * sizeof(G1Affine));
-            const size_t off_evals = o; o += up((size_t)n * CELL_LEN * sizeof(Fr));
-            const size_t off_coef = o; o += up((size_t)n * CELL_LEN * sizeof(Fr));
-            const size_t off_stp = o; o += up((size_t)(n + m) * 4);  // [proofs n | commitments m]
-            const size_t off_ste = o; o += up((size_t)Bc * 4);
-            const size_t off_rp = o; o += up((size_t)n * sizeof(Fr));
-            const size_t off_s1 = o; o += up((size_t)n * sizeof(Fr));
-            const size_t off_s2 = o; o += up((size_t)n * sizeof(Fr));
-            const size_t off_w = o; o += up((size_t)m * sizeof(Fr));
-            const size_t off_isc = o; o += up((size_t)Bc * 64 * sizeof(Fr));
-            const size_t off_icm = o; o += up((size_t)Bc * launch::SIZEOF_JACQ);
-            const size_t off_prod = o; o += up((size_t)(2 * n + m + (small ? 64 * Bc : 0)) * launch::SIZEOF_JACQ);
-            const size_t off_out = o; o += up((size_t)2 * Bc * launch::SIZEOF_JACQ);
-            const size_t off_fprod = o; o += up((size_t)2 * Bc * launch::SIZEOF_JACQ);
-            const size_t off_fold = o; o += up((size_t)2 * launch::SIZEOF_JACQ);
-            const int max_ranges = std::min(Bc, 2048);  // probes per level of the search for wrong proofs
-            const size_t off_rng = o; o += up((size_t)max_ranges * 8);
-            const size_t off_rsum = o; o += up((size_t)2 * max_ranges * launch::SIZEOF_JACQ);
-            const size_t dev_bytes = o;
-            // pinned read-backs behind the inputs
-            size_t po = in2_bytes;
-            const size_t poff_st = po; po += up((size_t)(n + m + Bc) * 4);
-            const size_t poff_out = po; po += up((size_t)2 * Bc * launch::SIZEOF_JACQ);
-            const size_t poff_fold = po; po += up((size_t)2 * launch::SIZEOF_JACQ);
-            const size_t poff_rng = po; po += up((size_t)max_ranges * 8);
-            const size_t poff_rsum = po; po += up((size_t)2 * max_ranges * launch::SIZEOF_JACQ);
-            const size_t pin_bytes = po;
-            if (dev_bytes > slot->dev_cap) {
-                if (slot->dev) { HIPCK(hipStreamSynchronize(st)); HIPCK(hipFree(slot->dev)); slot->dev = nullptr; slot->dev_cap = 0; }
-                HIPCK(hipMalloc(&slot->dev, dev_bytes + (dev_bytes >> 2)));
-                slot->dev_cap = dev_bytes + (dev_bytes >> 2);
-            }
-            if (pin_bytes > slot->pin_cap) {
-                if (slot->pin) { HIPCK(hipHostFree(slot->pin)); slot->pin = nullptr; slot->pin_cap = 0; }
-                HIPCK(hipHostMalloc((void**)&slot->pin, pin_bytes + (pin_bytes >> 2), hipHostMallocDefault));
-                slot->pin_cap = pin_bytes + (pin_bytes >> 2);
-            }
-            uint8_t* hb = slot->pin;
-            uint8_t* db = (uint8_t*)slot->dev;
-            int* h_idx = (int*)(hb + off_idx);
-            int* h_row = (int*)(hb + off_row);
-            int* h_bat = (int*)(hb + off_bat);
-            int* h_pos = (int*)(hb + off_pos);
-            int* h_rowb = (int*)(hb + off_rowb);
-            memcpy(hb + off_cs, cell_start.data(), (size_t)(Bc + 1) * 4);
-            memcpy(hb + off_rs, row_start.data(), (size_t)(Bc + 1) * 4);
-            // ---- staging (parallel over problems)
-            parallel_for(Bc, T, pool, [&](int i) {
-                const int b = b0 + i;
-                const Problem& p = pr[b];
-                const int c0 = cell_start[i], r0 = row_start[i];
-                for (int j = 0; j < p.m; j++) { memcpy(hb + off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
-                for (int k = 0; k < p.n; k++) {
-                    memcpy(hb + off_p + (size_t)(c0 + k) * 48, proofs[b][k], 48);
-                    memcpy(hb + off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, cells[b][k], BYTES_PER_CELL);
-                    h_idx[c0 + k] = (int)cell_indices[b][k];
-                    h_row[c0 + k] = r0 + p.row[k];
-                    h_bat[c0 + k] = i;
-                    h_pos[c0 + k] = k;
-                }
-            });
-            // stale contents of the persistent arena must fail closed: poison the status words and the result slots
-            int* h_st = (int*)(hb + poff_st);
-            memset(h_st, 0xff, (size_t)(n + m + Bc) * 4);
-            memset(hb + poff_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ);
-            memset(hb + poff_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ);
-            HIPCK(hipMemsetAsync(db + off_stp, 0xff, (size_t)(n + m) * 4, st));
-            HIPCK(hipMemsetAsync(db + off_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ, st));
-            HIPCK(hipMemsetAsync(db + off_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ, st));
-            HIPCK(hipMemsetAsync(db + off_ste, 0, (size_t)Bc * 4, st));
-            HIPCK(hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, st));
+            const PassLayout L(n, m, Bc, small);
+            grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
+            grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
+            uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
+            PassHost H{L, pr.data() + b0, cell_indices + b0, cells + b0, proofs + b0, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, verified + b0};
+            H.stage();
+            int* h_st = H.h_status();
+            HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)(n + m) * 4, st));
+            HIPCK(hipMemsetAsync(db + L.off_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ, st));
+            HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ, st));
+            HIPCK(hipMemsetAsync(db + L.off_ste, 0, (size_t)Bc * 4, st));
+            HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
             // ---- challenge-free GPU work: decode (on curve) + subgroup tests of [proofs | commitments], cells, interpolation
-            G1Affine* d_pts = (G1Affine*)(db + off_pts);
-            int* d_stp = (int*)(db + off_stp);
-            launch::g1_decode2(db + off_p, d_pts, d_stp, n, db + off_c, d_pts + n, d_stp + n, m, beta_, st);
+            G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
+            int* d_stp = (int*)(db + L.off_stp);
+            launch::g1_decode2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, m, beta_, st);
             if (!small) launch::g1_subgroup2(d_pts, d_stp, n, d_pts + n, d_stp + n, m, beta_, st);  // (small: inside k_vm_mul_small)
-            launch::cells_to_fr(db + off_cells, db + off_evals, nullptr, (int*)(db + off_ste), (const int*)(db + off_bat), nullptr, n, st);
-            launch::interp_cells(db + off_evals, (const int*)(db + off_idx), d_w8192_, inv64_, db + off_coef, n, st);
+            launch::cells_to_fr(db + L.off_cells, db + L.off_evals, nullptr, (int*)(db + L.off_ste), (const int*)(db + L.off_bat), nullptr, n, st);
+            launch::interp_cells(db + L.off_evals, (const int*)(db + L.off_idx), d_w8192_, inv64_, db + L.off_coef, n, st);
             HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(h_st + n + m, db + off_ste, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(h_st + n + m, db + L.off_ste, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
             HIPCK(hipGetLastError());
-            // ---- Fiat-Shamir challenges on the host threads meanwhile (verifier.rs:269-328): valid inputs are canonical
-            // encodings, so the transcript is the input bytes themselves; then the table r^(2^i) per problem
-            Fr* h_pow = (Fr*)(hb + off_pow);
-            std::vector<uint8_t> digests((size_t)Bc * 32, 0);
-            parallel_for(Bc, T, pool, [&](int i) {
-                const int b = b0 + i;
-                const Problem& p = pr[b];
-                Fr* tab = h_pow + (size_t)i * 24;
-                if (p.n == 0) { for (int j = 0; j < 24; j++) tab[j] = one<FrParams>(); return; }
-                Sha256 sh;
-                auto be64 = [](uint64_t v, uint8_t* out) { for (int q = 0; q < 8; q++) out[q] = (uint8_t)(v >> (56 - 8 * q)); };
-                uint8_t hdr[16 + 32];
-                memcpy(hdr, "RCKZGCBATCH__V1_", 16);
-                be64(N_BLOB, hdr + 16); be64(CELL_LEN, hdr + 24); be64((uint64_t)p.m, hdr + 32); be64((uint64_t)p.n, hdr + 40);
-                sh.update(hdr, sizeof hdr);
-                for (int j = 0; j < p.m; j++) sh.update(p.uniq[j], 48);
-                for (int k = 0; k < p.n; k++) {
-                    uint8_t ix[16];
-                    be64((uint64_t)p.row[k], ix); be64(cell_indices[b][k], ix + 8);
-                    sh.update(ix, 16);
-                    sh.update(cells[b][k], BYTES_PER_CELL);
-                    sh.update(proofs[b][k], 48);
-                }
-                uint8_t* dig = &digests[(size_t)i * 32];
-                sh.finish(dig);
-                Fr cur = reduce_be32(dig);
-                for (int j = 0; j < 24; j++) { tab[j] = cur; cur = sqr(cur); }
-            });
-            // ---- decoding verdicts per problem (order of the reference: commitments, proofs, cells): the challenge-free GPU work
-            // has long finished under the hashes, so this wait is short; a problem with an error takes no part in what follows
-            SYNC_CHECKED(st);
-            // (order of the reference: commitments, proofs, cells)
-            std::vector<char> live(Bc, 0);
-            auto judge = [&]() {
-                for (int i = 0; i < Bc; i++) {
-                    const int b = b0 + i;
-                    const Problem& p = pr[b];
-                    live[i] = 0;
-                    if (p.n == 0) continue;
-                    const int c0 = cell_start[i], r0 = row_start[i];
-                    int bad = OK;
-                    for (int j = 0; j < p.m && !bad; j++) if (h_st[n + r0 + j]) bad = ERR_G1;
-                    for (int k = 0; k < p.n && !bad; k++) if (h_st[c0 + k]) bad = ERR_G1;
-                    if (!bad && h_st[n + m + i]) bad = ERR_SCALAR;
-                    status[b] = bad;
-                    if (!bad) live[i] = 1;
-                }
-            };
-            judge();  // (a small pass judges again once its subgroup tests are in)
-            // ---- folding weights: rho_b = SHA-256(seed || b) truncated to 127 bits, seed = SHA-256 over ALL challenges' digests of the
-            // pass (so no weight can be predicted before every input byte is fixed); 0 for problems that are out
-            uint32_t* h_rho = (uint32_t*)(hb + off_rho);
-            int n_live = 0;
-            for (int i = 0; i < Bc; i++) n_live += live[i];
+            H.hash_challenges();  // meanwhile, on the host threads
+            SYNC_CHECKED(st);     // (the challenge-free GPU work has long finished under the hashes: a short wait)
+            int n_live = H.judge(status + b0);  // (a small pass judges again once its subgroup tests are in)
             const bool folded = fold && n_live >= 2 && !small;
-            if (folded) {
-                uint8_t seed[32];
-                {
-                    Sha256 sh;
-                    sh.update((const uint8_t*)"RCKZGCBATCHFOLD1", 16);
-                    sh.update(digests.data(), digests.size());
-                    sh.finish(seed);
-                }
-                parallel_for(Bc, T, pool, [&](int i) {
-                    uint32_t* r4 = h_rho + 4 * (size_t)i;
-                    if (!live[i]) { r4[0] = r4[1] = r4[2] = r4[3] = 0; return; }
-                    Sha256 sh;
-                    uint8_t ix[8], dg[32];
-                    for (int q = 0; q < 8; q++) ix[q] = (uint8_t)((uint64_t)i >> (56 - 8 * q));
-                    sh.update(seed, 32);
-                    sh.update(ix, 8);
-                    sh.finish(dg);
-                    memcpy(r4, dg, 16);
-                    r4[3] &= 0x7fffffffu;
-                    if ((r4[0] | r4[1] | r4[2] | r4[3]) == 0) r4[0] = 1;
-                });
-            }
-            HIPCK(hipMemcpyAsync(db + off_pow, hb + off_pow, in2_bytes - off_pow, hipMemcpyHostToDevice, st));  // power tables + weights
+            if (folded) H.fold_weights();
+            HIPCK(hipMemcpyAsync(db + L.off_pow, hb + L.off_pow, L.in2_bytes - L.off_pow, hipMemcpyHostToDevice, st));  // power tables + weights
             // ---- per-problem scalars, weights, interpolation sums; every scalar multiplication; the two sums per problem
-            const int* d_cs = (const int*)(db + off_cs);
-            const int* d_rs = (const int*)(db + off_rs);
-            launch::vm_scalars(db + off_pow, (const int*)(db + off_bat), (const int*)(db + off_pos), (const int*)(db + off_idx), d_w8192_,
-                               db + off_rp, db + off_s1, db + off_s2, n, st);
-            launch::vm_weights(db + off_rp, (const int*)(db + off_row), (const int*)(db + off_rowb), d_cs, db + off_w, m, st);
-            launch::vm_interp_sum(db + off_coef, db + off_rp, d_cs, db + off_isc, Bc, st);
+            const int *d_cs = (const int*)(db + L.off_cs), *d_rs = (const int*)(db + L.off_rs);
+            launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_w8192_,
+                               db + L.off_rp, db + L.off_s1, db + L.off_s2, n, st);
+            launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), (const int*)(db + L.off_rowb), d_cs, db + L.off_w, m, st);
+            launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
             if (small) {
-                launch::vm_mul_small(d_pts, db + off_s1, db + off_s2, db + off_w, db + off_isc, d_srs_, db + off_prod, n, m, Bc, d_stp, beta_, st);
-                launch::vm_reduce_small(db + off_prod, d_cs, d_rs, db + off_out, n, m, Bc, st);
+                launch::vm_mul_small(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_isc, d_srs_, db + L.off_prod, n, m, Bc, d_stp, beta_, st);
+                launch::vm_reduce_small(db + L.off_prod, d_cs, d_rs, db + L.off_out, n, m, Bc, st);
                 HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
             } else {
-                launch::vm_mul(d_pts, db + off_s1, db + off_s2, db + off_w, db + off_prod, n, m, beta_, st);
+                launch::vm_mul(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_prod, n, m, beta_, st);
                 // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
-                launch_msm(db + off_isc, TAB_SRS, db + off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
-                launch::vm_reduce(db + off_prod, db + off_icm, d_cs, d_rs, db + off_out, n, Bc, st);
+                launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
+                launch::vm_reduce(db + L.off_prod, db + L.off_icm, d_cs, d_rs, db + L.off_out, n, Bc, st);
             }
             if (folded) {
-                launch::vm_fold(db + off_out, (const uint32_t*)(db + off_rho), db + off_fprod, db + off_fold, Bc, beta_, st);
-                HIPCK(hipMemcpyAsync(hb + poff_fold, db + off_fold, (size_t)2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
+                launch::vm_fold(db + L.off_out, (const uint32_t*)(db + L.off_rho), db + L.off_fprod, db + L.off_fold, Bc, beta_, st);
+                HIPCK(hipMemcpyAsync(hb + L.poff_fold, db + L.off_fold, (size_t)2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
             }
-            HIPCK(hipMemcpyAsync(hb + poff_out, db + off_out, (size_t)2 * Bc * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(hb + L.poff_out, db + L.off_out, (size_t)2 * Bc * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
             SYNC_CHECKED(st);
-            if (small) judge();
+            if (small) n_live = H.judge(status + b0);
             // ---- verdicts: ONE pairing check of the folded sums; only if that fails (some problem's proof is wrong) one per problem
-            const JacQ* sums = (const JacQ*)(hb + poff_out);
-            std::atomic<int> device_fault{0};
-            auto poisoned = [](const JacQ& s) { return s.x.v[0] == 0xffffffffu && s.z.v[0] == 0xffffffffu; };
             bool all_true = false;
             if (folded) {
-                const JacQ* f2 = (const JacQ*)(hb + poff_fold);
-                if (poisoned(f2[0]) || poisoned(f2[1])) throw std::runtime_error("many-verification pass left no folded result");
-                G1Affine pts[2] = {to_affine(jac_from_jacq(f2[0])), to_affine(jac_from_jacq(f2[1]))};
-                all_true = verify_cells_pairing(pts);
+                const int v = check_pair((const JacQ*)(hb + L.poff_fold), H.vk);
+                if (v < 0) throw std::runtime_error("many-verification pass left no folded result");
+                all_true = v == 1;
             }
-            auto check_single = [&](int i) {  // one problem's own pairing check on the sums read back
-                G1Affine pts[2];
-                for (int j = 0; j < 2; j++) {
-                    const JacQ& s = sums[2 * (size_t)i + j];
-                    if (poisoned(s)) { device_fault.store(1); return; }
-                    pts[j] = to_affine(jac_from_jacq(s));
-                }
-                verified[b0 + i] = verify_cells_pairing(pts) ? 1 : 0;
-            };
             if (all_true) {
                 for (int i = 0; i < Bc; i++)
-                    if (live[i]) {
-                        if (poisoned(sums[2 * (size_t)i]) || poisoned(sums[2 * (size_t)i + 1])) { device_fault.store(1); break; }
+                    if (H.live[i]) {
+                        if (poisoned(H.sums()[2 * (size_t)i]) || poisoned(H.sums()[2 * (size_t)i + 1])) { H.device_fault.store(1); break; }
                         verified[b0 + i] = 1;
                     }
             } else if (folded && vm_search_) {
-                // Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM: SEARCH for the wrong ones by
-                // folding sub-ranges (k_vm_fold_ranges: one small launch per level) and checking each with one pairing on a host
-                // thread -- a range whose fold passes holds only valid proofs (the same 2^-127 argument, the weights were fixed
-                // after every input byte), a single problem whose weighted pair fails is wrong EXACTLY (rho_b != 0 and the
-                // pairing group has prime order).  Ranges are split K ways with K chosen so that a level's probes fill the
-                // host threads once: one wrong proof among 1024 costs ~36 pairings in 3 rounds instead of 1024 in 64 (round 3:
-                // 85 ms per call against 29.6 ms for an all-valid one).  When wrong proofs are many the search stops paying:
-                // from a quarter of the live problems suspect, the rest is checked one by one as before.
-                std::vector<std::pair<int, int>> suspects{{0, Bc}};
-                int* h_rng = (int*)(hb + poff_rng);
-                const JacQ* h_rsum = (const JacQ*)(hb + poff_rsum);
-                while (!suspects.empty()) {
-                    long suspect_problems = 0;
-                    for (auto& sr : suspects) suspect_problems += sr.second - sr.first;
-                    if ((long)suspects.size() * 4 >= n_live || suspect_problems <= 2 * T) {  // few problems left, or wrong proofs everywhere
-                        std::vector<int> todo;
-                        for (auto& sr : suspects)
-                            for (int i = sr.first; i < sr.second; i++)
-                                if (live[i]) todo.push_back(i);
-                        parallel_for((int)todo.size(), T, pool, [&](int q) { check_single(todo[q]); });
-                        break;
-                    }
-                    int K = T / (int)suspects.size();
-                    K = K < 2 ? 2 : K > 16 ? 16 : K;
-                    std::vector<std::pair<int, int>> probes;
-                    for (auto& sr : suspects) {
-                        const int len = sr.second - sr.first, parts = std::min(K, len);
-                        for (int q = 0; q < parts; q++) probes.emplace_back(sr.first + (int)((long)len * q / parts), sr.first + (int)((long)len * (q + 1) / parts));
-                    }
-                    // a level may need more probes than the range buffers hold (max_ranges = min(Bc, 2048): e.g. > 4096 small problems
-                    // with > 1024 scattered wrong proofs): it then runs in batches over the same buffers -- never an error, the
-                    // valid problems of the pass keep their verdicts
-                    std::vector<char> fails(probes.size(), 0);
-                    for (size_t q0 = 0; q0 < probes.size() && !device_fault.load(); q0 += (size_t)max_ranges) {
-                        const size_t cnt = std::min(probes.size() - q0, (size_t)max_ranges);
-                        for (size_t q = 0; q < cnt; q++) { h_rng[2 * q] = probes[q0 + q].first; h_rng[2 * q + 1] = probes[q0 + q].second; }
-                        memset(hb + poff_rsum, 0xff, cnt * 2 * launch::SIZEOF_JACQ);
-                        HIPCK(hipMemcpyAsync(db + off_rng, h_rng, cnt * 8, hipMemcpyHostToDevice, st));
-                        launch::vm_fold_ranges(db + off_fprod, (const int*)(db + off_rng), db + off_rsum, (int)cnt, st);
-                        HIPCK(hipMemcpyAsync(hb + poff_rsum, db + off_rsum, cnt * 2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
-                        SYNC_CHECKED(st);
-                        parallel_for((int)cnt, T, pool, [&](int q) {
-                            G1Affine pts[2];
-                            for (int j = 0; j < 2; j++) {
-                                const JacQ& sj = h_rsum[2 * (size_t)q + j];
-                                if (poisoned(sj)) { device_fault.store(1); return; }
-                                pts[j] = to_affine(jac_from_jacq(sj));
-                            }
-                            fails[q0 + q] = verify_cells_pairing(pts) ? 0 : 1;
-                        });
-                    }
-                    if (device_fault.load()) break;
-                    suspects.clear();
-                    for (size_t q = 0; q < probes.size(); q++) {
-                        const int lo = probes[q].first, hi = probes[q].second;
-                        if (!fails[q]) {
-                            for (int i = lo; i < hi; i++) if (live[i]) verified[b0 + i] = 1;
-                        } else if (hi - lo == 1) {
-                            verified[b0 + lo] = 0;  // exact: its own weighted pair fails the check
-                        } else {
-                            suspects.emplace_back(lo, hi);
-                        }
-                    }
-                }
+                search_wrong_proofs(H, n_live, db, st);
             } else {
                 parallel_for(Bc, T, pool, [&](int i) {
-                    if (live[i]) check_single(i);
+                    if (H.live[i]) H.check_single(i);
                 });
             }
-            if (device_fault.load()) throw std::runtime_error("many-verification pass left no result");
+            if (H.device_fault.load()) throw std::runtime_error("many-verification pass left no result");
             b0 = b1;
         }
     } catch (const std::exception& e) {

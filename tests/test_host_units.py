@@ -114,3 +114,149 @@ def test_signed_13_digit_group_law_matches_saturated_formulas(tmp_path):
     the folds, exact slow paths, the packed table entry, conversions to and from the 14 x 29-bit form) against csrc/curve.hpp."""
     out = _build_and_run(tmp_path, "test_curve30")
     assert "0 mismatches" in out
+
+
+# ---- csrc/verify_host.hpp: the host statements the verifiers share, on the CPU against tests/verify_transcript.py -------------------------
+def _verify_host_cases():
+    """-> [(command line of the case file, expected output line)]: a plain function of the seeds.  The transcripts treat their inputs
+    as opaque bytes, so seeded random bytes serve (no curve material)."""
+    import hashlib
+    import random
+
+    import verify_transcript as T
+
+    rng = random.Random("verify-host:1")
+    rb = lambda n: bytes(rng.getrandbits(8) for _ in range(n))  # noqa: E731
+    R = T.R
+    out = []
+
+    def cell_case(comm, idx):
+        cells, proofs = [rb(T.BYTES_PER_CELL) for _ in idx], [rb(48) for _ in idx]
+        h = hashlib.sha256()  # the digest next to the challenge: the many path's fold seed hashes it
+        uniq, row = T.dedup(comm)
+        h.update(b"RCKZGCBATCH__V1_" + T.be64(T.N_BLOB) + T.be64(T.CELL_LEN) + T.be64(len(uniq)) + T.be64(len(idx)) + b"".join(uniq))
+        for k in range(len(idx)):
+            h.update(T.be64(row[k]) + T.be64(idx[k]) + cells[k] + proofs[k])
+        assert T.reduce_digest(h.digest()) == T.cell_challenge(comm, idx, cells, proofs)
+        line = "cell %d " % len(idx) + " ".join("%s %d %s %s" % (c.hex(), i, l.hex(), p.hex()) for c, i, l, p in zip(comm, idx, cells, proofs))
+        out.append((line, "cell %s %s" % (T.fr_be(T.cell_challenge(comm, idx, cells, proofs)).hex(), h.hexdigest())))
+        out.append(("dedup %d " % len(comm) + " ".join(c.hex() for c in comm),
+                    "dedup %d %s %s" % (len(uniq), ",".join(map(str, row)), b"".join(uniq).hex())))
+
+    a, b, c = rb(48), rb(48), rb(48)
+    cell_case([a], [5])                                   # n = 1
+    cell_case([b, b, b], [0, 127, 64])                    # all commitments equal: m = 1
+    cell_case([a, b, a, c, b], [9, 9, 10, 127, 0])        # rows 0 1 0 2 1: first-occurrence order, not byte order
+    assert T.dedup([a, b, a, c, b])[1] == [0, 1, 0, 2, 1]
+    many = [rb(48) for _ in range(7)]
+    cell_case([rng.choice(many) for _ in range(130)], list(range(128)) + [3, 3])  # 128 distinct indices plus repeats
+
+    for counts, idx, want in (((3, 3, 3, 3), [0, 64, 127], 0), ((2, 3, 3, 3), [0, 1, 2], 3), ((3, 2, 3, 3), [0, 1], 3), ((3, 3, 2, 3), [0, 1, 2], 3),
+                              ((3, 3, 3, 2), [0, 1, 2], 3), ((3, 3, 3, 3), [0, 128, 1], 3), ((0, 0, 0, 0), [], 0), ((1, 1, 1, 1), [1 << 40], 3)):
+        out.append(("validate %d %d %d %d %d %s" % (*counts, len(idx), " ".join(map(str, idx))), "validate %d" % want))
+
+    assert 2 * R < 1 << 256 < 3 * R  # so the digests below take the zero-, one- and two-subtraction paths
+    for v in (0, R - 1, R, 2 * R - 1, 2 * R, (1 << 256) - 1):
+        d = v.to_bytes(32, "big")
+        out.append(("reduce " + d.hex(), "reduce " + T.fr_be(T.reduce_digest(d)).hex()))
+    out.append(("canonical " + R.to_bytes(32, "big").hex(), "canonical 0 -"))
+    out.append(("canonical " + (R - 1).to_bytes(32, "big").hex(), "canonical 1 " + (R - 1).to_bytes(32, "big").hex()))
+    out.append(("canonical " + bytes(32).hex(), "canonical 1 " + bytes(32).hex()))
+
+    for _ in range(2):
+        blob, comm = rb(131072), rb(48)
+        out.append(("blob %s %s" % (blob.hex(), comm.hex()), "blob " + T.fr_be(T.blob_challenge(blob, comm)).hex()))
+    for n in (1, 3):
+        cs, ps = [rb(48) for _ in range(n)], [rb(48) for _ in range(n)]
+        zs, ys = [rng.randrange(R) for _ in range(n)], [rng.randrange(R) for _ in range(n)]
+        zs[0], ys[-1] = R - 1, 0
+        line = "blobbatch %d " % n + " ".join("%s %s %s %s" % (c_.hex(), T.fr_be(z).hex(), T.fr_be(y).hex(), p.hex()) for c_, z, y, p in zip(cs, zs, ys, ps))
+        out.append((line, "blobbatch " + T.fr_be(T.blob_batch_challenge(cs, zs, ys, ps)).hex()))
+
+    digests = rb(32 * 256)  # the challenges' digests of a pass of 256 problems
+    seed = hashlib.sha256(b"RCKZGCBATCHFOLD1" + digests).digest()
+    for i in (0, 1, 255):
+        w = int.from_bytes(hashlib.sha256(seed + T.be64(i)).digest()[:16], "little") & ((1 << 127) - 1)  # 127 bits of the digest's first 16 bytes
+        assert w != 0
+        words = [(w >> (32 * j)) & 0xffffffff for j in range(4)]
+        assert words[3] >> 31 == 0
+        out.append(("fold %s %d" % (digests.hex(), i), "fold %s %s" % (seed.hex(), " ".join("%08x" % x for x in words))))
+    out.append(("brp7", "brp7 " + ",".join(str(T.brp(v, 7)) for v in range(128))))
+    return out
+
+
+@pytest.fixture(scope="module")
+def verify_host_cases():
+    return _verify_host_cases()
+
+
+# the same stand-alone program twice: as the other host units are built, and with AddressSanitizer + UBSan (its own main, run
+# directly: nothing is preloaded and nothing is loaded into Python)
+VERIFY_HOST_BUILDS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
+
+
+@pytest.fixture(scope="module", params=list(VERIFY_HOST_BUILDS))
+def verify_host_output(request, tmp_path_factory, verify_host_cases):
+    """-> {command word: [(expected line, printed line)]} of one build of tests/c/test_verify_host.cpp run over the case file"""
+    tmp = tmp_path_factory.mktemp("verify_host_" + request.param)
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    exe, cases = str(tmp / "test_verify_host"), str(tmp / "cases.txt")
+    subprocess.check_call([hipcc, *VERIFY_HOST_BUILDS[request.param], "-std=c++17", "-x", "hip", "--cuda-host-only", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "c", "test_verify_host.cpp"), "-o", exe])
+    with open(cases, "w") as f:
+        f.write("".join(line + "\n" for line, _ in verify_host_cases))
+    run = subprocess.run([exe, cases], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0 and run.stderr == "", run.stdout[-2000:] + run.stderr[-4000:]
+    printed = run.stdout.splitlines()
+    assert len(printed) == len(verify_host_cases), run.stdout[-2000:]
+    by_command = {}
+    for (line, want), got in zip(verify_host_cases, printed):
+        by_command.setdefault(line.split()[0], []).append((want, got))
+    return by_command
+
+
+def _same(pairs, count):
+    assert len(pairs) == count
+    for want, got in pairs:
+        assert got == want
+
+
+@pytest.mark.timeout(600)
+def test_cell_batch_transcript_matches_hashlib(verify_host_output):
+    """CellBatchTranscript, the ONE statement of the cell verifiers' challenge (single, sharded, device-resident and many paths), and
+    dedup_commitments under it: n = 1; three equal commitments; A B A C B (rows and first-occurrence order); 130 cells over all 128
+    indices with repeats.  Challenge and raw digest against tests/verify_transcript.py."""
+    _same(verify_host_output["cell"], 4)
+    _same(verify_host_output["dedup"], 4)
+
+
+@pytest.mark.timeout(600)
+def test_cell_batch_validation_codes(verify_host_output):
+    """validate_cell_batch: a valid batch, each of the four length mismatches, an index of 128, an index far beyond 32 bits, n = 0"""
+    _same(verify_host_output["validate"], 8)
+
+
+@pytest.mark.timeout(600)
+def test_digest_reduction_and_canonical_scalars(verify_host_output):
+    """fr_from_digest on 0, r - 1, r, 2r - 1, 2r, 2^256 - 1 (no, one and two subtractions); fr_from_be_canonical rejects r and accepts
+    r - 1 and 0, and fr_to_be gives the bytes back; brp7 on every cell index"""
+    _same(verify_host_output["reduce"], 6)
+    _same(verify_host_output["canonical"], 3)
+    _same(verify_host_output["brp7"], 1)
+
+
+@pytest.mark.timeout(600)
+def test_blob_transcripts_match_hashlib(verify_host_output):
+    """blob_challenge on two random 131072-byte blobs (blob_challenge_header is also what the GPU hashes in front of every blob);
+    blob_batch_weight for n = 1 and n = 3, z = r - 1 and y = 0 among the values"""
+    _same(verify_host_output["blob"], 2)
+    _same(verify_host_output["blobbatch"], 2)
+
+
+@pytest.mark.timeout(600)
+def test_fold_weights_match_hashlib(verify_host_output):
+    """fold_seed and fold_weight for problems 0, 1 and 255 of a pass of 256: SHA-256(seed | i), its first 16 bytes as four little-endian
+    words, 127 bits kept -- the top bit of word 3 is clear"""
+    _same(verify_host_output["fold"], 3)
+    for _, got in verify_host_output["fold"]:
+        assert int(got.split()[-1], 16) >> 31 == 0

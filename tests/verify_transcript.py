@@ -1,6 +1,6 @@
 """An independent statement of what the batch verifiers pair, and the cases it is compared on (tests/test_verify_inputs.py).
 
-Written from the reference's source, not from oracle/kzg.c and not from csrc/verify.hip:
+Written from the reference's source, not from oracle/kzg.c and not from csrc/verify_host.hpp or csrc/verify.hip:
   crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:49-65    deduplicate_with_indices (the caller's side: eip7594/src/verifier.rs)
                                                           :129-260  verify_multi_opening: the four lincombs and the two pairing inputs
                                                           :269-384  compute_fiat_shamir_challenge, compute_powers, compute_sum_interpolation_poly
