@@ -16,6 +16,16 @@ int eth_kzg_amd_test_g1_decompress(const DASContext *ctx, const uint8_t *in, int
 int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const uint8_t *b, uint8_t *out, int n,
                                int is_fp);
 
+/* The scalars the prover hands to its fixed-base MSMs.  compute_cells_and_kzg_proofs' own schedule on n blobs (host, 1 <= n <= 4096,
+ * both outputs asked for), then what it left for eth_kzg_amd_test_fixed_msm's stage, word for word: scalars[seg][blob][j < 128][i < 64][8]
+ * little-endian words, each scalar as its two balanced GLV halves (sign in bit 127 of a half); seg < 4 for one or two blobs, < 2 for
+ * three or four (copies scaled by 2^32, 2^64, 2^96 / by 2^64), one otherwise.  *n_words = words written (<= max_words, else 3).
+ * cells[n][128][2048], proofs[n][128][48], status[n] (0, or 1: an element >= r): the call's outputs.  *fused_launches = launches of
+ * k_coeffs_to_cells_scalars by this call: 1 where the scalars came from the cells' transform, 0 where k_fk20_scalars wrote them
+ * (ETH_KZG_AMD_FUSED_SCALARS = 0 | 1 forces either at every batch size).  Synchronous. */
+int eth_kzg_amd_test_prover_scalars(const DASContext *ctx, int n, const uint8_t *blobs, uint32_t *scalars, uint64_t max_words,
+                                    uint64_t *n_words, uint8_t *cells, uint8_t *proofs, int32_t *status, int32_t *fused_launches);
+
 /* The many-message SHA-256 kernel (csrc/k_sha256.hip) on its own: n messages, message i = prefix[prefix_len] (HOST memory) |
  * (d_body + i * body_stride)[body_len] | (d_tail + i * tail_stride)[tail_len] (device memory; a part of length 0 may be NULL), digest i
  * -> d_out + 32 i (device).  Synchronous; returns 0 on success. */

@@ -78,6 +78,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_table_info", "eth_kzg_amd_test_table_audit", "eth_kzg_amd_test_table_read", "eth_kzg_amd_test_table_audit_buffer",
     "eth_kzg_amd_test_sha256_many", "eth_kzg_amd_test_verify_msm",
     "eth_kzg_amd_test_verify_cells_partial_device", "eth_kzg_amd_test_verify_blob_batch_inputs", "eth_kzg_amd_test_rs_decode",
+    "eth_kzg_amd_test_prover_scalars",
 ]
 
 _lib = None
@@ -192,6 +193,7 @@ def load_library():
         "eth_kzg_amd_test_verify_cells_partial_device": [P, U64, P, P, P, P, U64, U64, P],
         "eth_kzg_amd_test_verify_blob_batch_inputs": [P, U64, C.c_int, P, P, P, P, P],
         "eth_kzg_amd_test_rs_decode": [P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, P],
+        "eth_kzg_amd_test_prover_scalars": [P, C.c_int, P, P, U64, P, P, P, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args

@@ -32,6 +32,11 @@ int eth_kzg_amd_test_g1_fft128(const DASContext* ctx, const uint8_t* in, uint8_t
 int eth_kzg_amd_test_fixed_msm(const DASContext* ctx, const uint8_t* scalars, int n_msm, uint8_t* out) {
     return eng(ctx)->test_fixed_msm(scalars, n_msm, out);
 }
+int eth_kzg_amd_test_prover_scalars(const DASContext* ctx, int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words,
+                                    uint8_t* cells, uint8_t* proofs, int32_t* status, int32_t* fused_launches) {
+    if (!blobs || !scalars || !n_words || !cells || !proofs || !status || !fused_launches) return kzg::ERR_INPUT;
+    return eng(ctx)->test_prover_scalars(n, blobs, scalars, max_words, n_words, cells, proofs, status, fused_launches);
+}
 int eth_kzg_amd_test_g1_decompress(const DASContext* ctx, const uint8_t* in, int n, int subgroup_check, int32_t* status,
                                    uint8_t* out) {
     return eng(ctx)->test_g1_decompress(in, n, subgroup_check, status, out);

@@ -226,6 +226,7 @@ Engine::Engine(bool use_precomp, int device, const Engine* primary, double table
     }
     vm_search_ = knobs_.vm_search;
     msm_split_ = knobs_.msm_split;
+    fused_scalars_ = knobs_.fused_scalars;
     if (knobs_.pip_shift_min >= 1) pip_shift_min_ = knobs_.pip_shift_min;
     // largest batch on the circulant form.  Its cost grows with every blob (1 blob 1.11 ms, 2: 1.36, 3: 1.78, 4: 1.87); the compiled
     // map with four lanes per blob and the flat MSM is flat (3 .. 8 blobs: 1.65 .. 1.86 ms).  Round 3's cross-over was 8 blobs, round
@@ -369,7 +370,7 @@ void Engine::teardown() noexcept {
     host_pool_.reset();  // joins the helper threads before anything they might touch goes away
     vm_pool_.reset();
     stage_pool_.reset();
-    void* ptrs[] = {d_w8192_, d_w29_, d_naf_, d_srs_, d_fk_bases_, d_in_, d_cells_, d_proofs_, d_coset_, d_coset_inv_, d_circ_terms_, d_4844_};
+    void* ptrs[] = {d_w8192_, d_w29_, d_tapk_, d_naf_, d_srs_, d_fk_bases_, d_in_, d_cells_, d_proofs_, d_coset_, d_coset_inv_, d_circ_terms_, d_4844_};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (SlpProgram& P : slp_prog_) {
@@ -482,6 +483,11 @@ void Engine::init_constants() {
     Fr i4096 = inv(fr_from_u64(N_BLOB)), i128 = inv(fr_from_u64(128));
     memcpy(&n_inv4096_, &i4096, 32);
     memcpy(&inv128_, &i128, 32);
+    // the tap constants of k_coeffs_to_cells_scalars, one half per scale fk20_scalars is given (half_: init_linmap above)
+    HIPCK(hipMalloc(&d_tapk_, (size_t)2 * N_EXT * launch::SIZEOF_FR29));
+    launch::fk20_tap_consts(d_w29_, half_, d_tapk_, stream_);
+    launch::fk20_tap_consts(d_w29_, inv128_, (char*)d_tapk_ + (size_t)N_EXT * launch::SIZEOF_FR29, stream_);
+    HIPCK(hipGetLastError());
 }
 
 // The two G1 transforms of the prover as one straight-line program of point operations (g1_linmap.hpp): built, checked

@@ -223,6 +223,9 @@ public:
     int test_fr_ntt4096(const uint8_t* in_be, uint8_t* out_be, int inverse_dit);
     int test_g1_fft128(const uint8_t* in_compressed, uint8_t* out_compressed, int n_lanes, int inverse);
     int test_fixed_msm(const uint8_t* scalars_be, int n_msm, uint8_t* out_compressed);
+    // enqueue_compute on n blobs (host), then the MSM scalars it left in the work set: segs x n x 8192 x 8 words, as launch_msm reads them
+    int test_prover_scalars(int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words, uint8_t* cells, uint8_t* proofs,
+                            int32_t* status, int32_t* fused_launches);
     int test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out_recompressed);
     int test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp);
     int test_op(int op, int n, const int32_t* in, int32_t* out);
@@ -372,6 +375,7 @@ private:
                                 int msm_cut = 0);
     void enqueue_compute(Work& w, int n, const uint8_t* d_blobs, uint8_t* d_cells, uint8_t* d_proofs, hipStream_t st,
                          hipEvent_t after_cells);
+    int fk20_segs(int n) const;  // scaled copies of the scalars the MSM stage of n blobs wants (run_proofs_from_coeffs)
     Work& lease_work(int first, int last);  // locks and returns a free set among work_[first..last] (waits for whichever frees first)
     void release_work(Work& w);
     std::mutex lease_mu_;
@@ -416,6 +420,8 @@ private:
     int wave_slots_ = 2048;  // CUs x 4 SIMDs x 2 waves: what one round of a ~240-VGPR point kernel occupies
     int device_batch_max_ = 4096;  // a device-resident prover call runs as sub-batches of at most this many blobs (ETH_KZG_AMD_DEVICE_BATCH_MAX)
     int msm_chunks_ = -1;    // -1: pick per launch (launch_msm); otherwise forced by ETH_KZG_AMD_MSM_CHUNKS
+    int fused_scalars_ = -1;  // -1: k_coeffs_to_cells_scalars where enqueue_compute's conditions hold; ETH_KZG_AMD_FUSED_SCALARS=0: never, 1: at every batch size
+    std::atomic<uint64_t> fused_launches_{0};  // launches of k_coeffs_to_cells_scalars so far (the parity test asks which path ran)
     bool msm_split_ = true;  // small batches: two lanes per MSM window where they still fit one round of the wave slots (ETH_KZG_AMD_MSM_SPLIT=0: off)
     hipStream_t stream_ = nullptr;
     std::recursive_mutex mu_;  // the verification / recovery / EIP-4844 / commitment paths and work_[0]: one call at a time
@@ -432,6 +438,7 @@ private:
     void* d_srs_ = nullptr;       // G1Affine[4096] monomial SRS
     void* d_fk_bases_ = nullptr;  // G1Affine[128][64] FFT'd SRS vectors (batch_toeplitz.rs:46-61)
     BufferPool dev_pool_{false}, pin_pool_{true};
+    void* d_tapk_ = nullptr;      // Fr29[2][2][4096]: the constants of k_coeffs_to_cells_scalars' tap for the scales 1/2 (linear-map mode) and 1/128, built from d_w29_
     Fr8 n_inv4096_, inv128_;
 
     // verifier / recovery constants

@@ -176,11 +176,12 @@ void Engine::g1_fft128_full(void* X, int stride, int inverse, hipStream_t st) {
 // stages C..G of SURVEY 3.2 from coefficients already in w.coeffs
 // tv_pre: the scalars of all n blobs are in w.scalars already, computed in the form of THIS view (the host-pointer path does it
 // sub-batch by sub-batch under the uploads)
+// one or two blobs: the MSM also delivers 2^32 u, 2^64 u, 2^96 u (scaled copies of the scalars, same tables), which
+// cuts the doubling chain of the circulant form into four parallel quarters (needs 32 * 4 >= T - 1 doublings)
+int Engine::fk20_segs(int n) const { return (n > circ_max_ || circ_T_ > 129) ? 1 : n <= 2 ? 4 : n <= 4 ? 2 : 1; }
 void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream_t st, const TableView* tv_pre, ProofsPhase phase, int msm_cut) {
     const int bp = ((n + 63) / 64) * 64;
-    // one or two blobs: the MSM also delivers 2^32 u, 2^64 u, 2^96 u (scaled copies of the scalars, same tables), which
-    // cuts the doubling chain of the circulant form into four parallel quarters (needs 32 * 4 >= T - 1 doublings)
-    const int segs = (n > circ_max_ || circ_T_ > 129) ? 1 : n <= 2 ? 4 : n <= 4 ? 2 : 1;
+    const int segs = fk20_segs(n);
     const Fr8 two_segments[3] = {seg_shift_[1], seg_shift_[1], seg_shift_[1]};  // 2^64
     // beyond the small-batch circulant kernel the two transforms run as one compiled linear map (g1_linmap.hpp), which wants
     // the MSM outputs halved instead of divided by 128 and in natural Fourier order in the first 128 arena slots
@@ -274,6 +275,26 @@ void Engine::enqueue_compute(Work& w, int n, const uint8_t* d_blobs, uint8_t* d_
     if (side && n > FLAT_MSM_MAX_SLICES) {
         const long simds = wave_slots_ / 2, waves = msm_waves(128L * n, table_view(TAB_FK).c);
         if (waves > simds * 4 / 5 && waves <= simds) side = false;
+    }
+    // Cells and proofs in one call: the FK20 scalars are an intermediate of the cells' transform, so one kernel writes both, and cells
+    // 0..63 of an accepted blob are copied from its bytes (k_coeffs_to_cells_scalars).  Not where the cells run beside the proof stages
+    // on the second stream, and not with segment copies (one or two blobs: those are side-stream batches anyway) -- unless the test
+    // knob forces the kernel there too.  The scalars' form and the MSM that reads them follow ONE snapshot of the table view.
+    const int segs = fk20_segs(n);
+    const bool fused = d_cells && d_proofs && fused_scalars_ != 0 && (fused_scalars_ == 1 || (!side && segs == 1));
+    if (fused) {
+        const bool linmap_mode = n > circ_max_;  // (run_proofs_from_coeffs: which scale the scalars carry)
+        const Fr8 two_segments[3] = {seg_shift_[1], seg_shift_[1], seg_shift_[1]};
+        const TableView tv = table_view(TAB_FK);
+        const int mk = mark_begin(ST_COEFFS_TO_CELLS, st);
+        launch::coeffs_to_cells_scalars(n, w.coeffs, d_cells, w.scalars, d_blobs, w.status, d_w29_,
+                                        (const char*)d_tapk_ + (linmap_mode ? 0 : (size_t)N_EXT * launch::SIZEOF_FR29), segs,
+                                        segs == 2 ? two_segments : seg_shift_, st);
+        mark_end(mk, 1, st);
+        fused_launches_.fetch_add(1, std::memory_order_relaxed);
+        if (after_cells) HIPCK(hipEventRecord(after_cells, st));
+        run_proofs_from_coeffs(w, n, d_proofs, st, &tv);
+        return;
     }
     if (side) {
         HIPCK(hipEventRecord(w.ev_coeffs, st));

@@ -113,6 +113,47 @@ int Engine::test_fixed_msm(const uint8_t* scalars_be, int n_msm, uint8_t* out) {
     return OK;
 }
 
+// The prover's own schedule (enqueue_compute, both outputs asked for) on n blobs, then the MSM scalars it left in the work set, word for
+// word: which kernels wrote them is the context's ETH_KZG_AMD_FUSED_SCALARS; *fused_launches = launches of k_coeffs_to_cells_scalars.
+int Engine::test_prover_scalars(int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words, uint8_t* cells,
+                                uint8_t* proofs, int32_t* status, int32_t* fused_launches) {
+    if (n < 1 || n > 4096) return ERR_INPUT;
+    const uint64_t words = (uint64_t)fk20_segs(n) * n * N_EXT * 8;
+    if (words > max_words) return ERR_INPUT;
+    struct DevBuf {  // (freed on every way out)
+        void* p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } d_in, d_cells, d_proofs;
+    Work* held = nullptr;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        Work& w = lease_work(1, NW - 1);
+        held = &w;
+        HIPCK(hipMalloc(&d_in.p, (size_t)n * BYTES_PER_BLOB));
+        HIPCK(hipMalloc(&d_cells.p, (size_t)n * N_CELLS * BYTES_PER_CELL));
+        HIPCK(hipMalloc(&d_proofs.p, (size_t)n * N_CELLS * 48));
+        HIPCK(hipMemcpyAsync(d_in.p, blobs, (size_t)n * BYTES_PER_BLOB, hipMemcpyHostToDevice, w.stream));
+        const uint64_t before = fused_launches_.load();
+        enqueue_compute(w, n, (const uint8_t*)d_in.p, (uint8_t*)d_cells.p, (uint8_t*)d_proofs.p, w.stream, nullptr);
+        HIPCK(hipEventRecord(w.done, w.stream));
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(w.stream));
+        *fused_launches = (int32_t)(fused_launches_.load() - before);
+        *n_words = words;
+        HIPCK(hipMemcpy(scalars, w.scalars, words * 4, hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(cells, d_cells.p, (size_t)n * N_CELLS * BYTES_PER_CELL, hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(proofs, d_proofs.p, (size_t)n * N_CELLS * 48, hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(status, w.status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        release_work(w);
+        held = nullptr;
+    } catch (const std::exception& e) {
+        if (held) { (void)hipStreamSynchronize(held->stream); (void)hipStreamSynchronize(held->copy); release_work(*held); }
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 int Engine::test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out) {
     std::lock_guard<std::recursive_mutex> lk(mu_);
     try {

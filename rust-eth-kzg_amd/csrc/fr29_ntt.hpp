@@ -49,4 +49,28 @@ HD void ntt4096_ct_forward_unit(const Elems& m, const Fr29* __restrict__ w29, in
     m.store(i0 + 3 * h, fr29_sub2r<true>(a2, tb1));
 }
 
+// THE FK20 TAP.  The forward network is a remainder tree: after the passes h = 1024, 256, 64 (every layer with half >= 64) the
+// 64-element block q holds x(X) mod (X^64 - omega_64^brp6(q)), i.e. position e = 64 q + c holds sum_m x[64 m + c] omega_64^(brp6(q) m).
+// k_coeffs_to_cells_scalars transforms x[e] = a[e] omega_8192^(e h) for the half h of the extended domain, so with
+// F_c(y) = sum_{m<64} a[64 m + c] y^m that position holds omega_8192^(c h) F_c(omega_128^j), j = 2 brp6(q) + h.
+// The circulant-column vector of k_fk20_scalars for i = 63 - c is v[(65 + m) mod 128] = a[64 m + c], whose transform is
+// NTT_128(v)[j] = omega_128^(65 j) F_c(omega_128^j): the scalar (j, i) is the tapped value times scale omega_8192^(64 65 j - c h).
+HD int fk20_tap_row(int e, int h) {  // j of position e in half h
+    const int q = e >> 6;
+    int rb = 0;
+    for (int b = 0; b < 6; b++) rb |= ((q >> b) & 1) << (5 - b);
+    return 2 * rb + h;
+}
+HD int fk20_tap_column(int e) { return 63 - (e & 63); }  // i
+HD int fk20_tap_exponent(int e, int h) { return (64 * 65 * fk20_tap_row(e, h) + NTT_W - (e & 63) * h) & (NTT_W - 1); }
+// entry idx = h 4096 + e of the constant table: scale omega_8192^exponent as a plain canonical integer (scale_plain: the scale as one),
+// so that the product with the tapped value (Montgomery form, < 44 r after six layers) is the plain scalar, < 2r
+HD Fr29 fk20_tap_const(const Fr29* __restrict__ w29, const Fr29& scale_plain, int idx) {
+    return fr29_reduce_once(fr29_mul(w29[fk20_tap_exponent(idx & (NTT_N - 1), idx >> 12)], scale_plain));
+}
+template <class Elems>
+HD Fr29 fk20_tap_scalar(const Elems& m, const Fr29* __restrict__ tapk, int e, int h) {
+    return fr29_mul(m.load(e), tapk[h * NTT_N + e]);
+}
+
 }  // namespace kzg

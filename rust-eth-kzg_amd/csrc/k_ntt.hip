@@ -73,13 +73,19 @@ __device__ __forceinline__ void ntt4096_dit_inverse(uint32_t* s, const Fr29* __r
 __device__ __forceinline__ void ct_forward_pass(uint32_t* s, const Fr29* __restrict__ w29, int h, int log_m) {
     ntt4096_ct_forward_unit(LdsElems{s}, w29, h, log_m, (int)threadIdx.x);
 }
-__device__ __forceinline__ void ntt4096_ct_forward(uint32_t* s, const Fr29* __restrict__ w29) {  // input stored by thread e mod 1024
+// The transform in two parts, so that k_coeffs_to_cells_scalars can read the FK20 scalars between them (fr29_ntt.hpp, THE FK20 TAP).
+// After the head, thread tid's own stores of pass h = 64 are the elements (tid / 64) * 256 + (tid mod 64) + {0, 64, 128, 192}: the tap
+// reads exactly those, what the same thread wrote, so it needs NO barrier of its own (a wave's LDS operations execute in program
+// order), and it writes nothing to LDS: the wave barrier in front of the tail stands as it did between the passes h = 64 and h = 16.
+__device__ __forceinline__ void ntt4096_ct_forward_head(uint32_t* s, const Fr29* __restrict__ w29) {  // input stored by thread e mod 1024
     __builtin_amdgcn_wave_barrier();
     ct_forward_pass(s, w29, 1024, 0);
     __syncthreads();
     ct_forward_pass(s, w29, 256, 2);
     __syncthreads();
     ct_forward_pass(s, w29, 64, 4);
+}
+__device__ __forceinline__ void ntt4096_ct_forward_tail(uint32_t* s, const Fr29* __restrict__ w29) {
     __builtin_amdgcn_wave_barrier();
     ct_forward_pass(s, w29, 16, 6);
     __builtin_amdgcn_wave_barrier();
@@ -88,10 +94,24 @@ __device__ __forceinline__ void ntt4096_ct_forward(uint32_t* s, const Fr29* __re
     ct_forward_pass(s, w29, 1, 10);
     __syncthreads();
 }
+__device__ __forceinline__ void ntt4096_ct_forward(uint32_t* s, const Fr29* __restrict__ w29) {
+    ntt4096_ct_forward_head(s, w29);
+    ntt4096_ct_forward_tail(s, w29);
+}
 __device__ __forceinline__ Fr fr_words_of(const Fr29& canonical) {
     Fr r;
     fr29_to_words(r.v, canonical);
     return r;
+}
+// An MSM scalar leaves as its balanced GLV halves k = k1 + k2 lambda (glv.hpp), the form the window tables' kernels extract their
+// digits from.  x: the plain value, < 2r, normalised limbs.
+__device__ __forceinline__ void store_split_scalar(Fr* __restrict__ at, const Fr29& x) {
+    Fr k = fr_words_of(fr29_reduce_once(x));
+    uint32_t h[8];
+    glv_split_balanced(k, h);
+#pragma unroll
+    for (int l = 0; l < 8; l++) k.v[l] = h[l];
+    *at = k;
 }
 
 // Stage A+B of compute_cells_and_kzg_proofs: blob bytes -> monomial coefficients.
@@ -203,12 +223,7 @@ __global__ __launch_bounds__(256) void k_fk20_scalars(const Fr* __restrict__ coe
     // position q holds NTT[brp7(q)].  The scalar leaves already split k = k1 + k2 lambda for the GLV window tables (what the separate
     // k_glv_split pass of round 2 did in place: 0.19 ms of reading and writing 0.5 GB at 2048 blobs)
     auto emit = [&](size_t at, const Fr29& x) {  // x: the plain value, < 16 r (or < 2r: a segment's product)
-        Fr k = fr_words_of(fr29_reduce_once(fr29_partial_reduce(x)));
-        uint32_t h[8];
-        glv_split_balanced(k, h);
-#pragma unroll
-        for (int l = 0; l < 8; l++) k.v[l] = h[l];
-        scalars[at] = k;
+        store_split_scalar(&scalars[at], fr29_partial_reduce(x));
     };
     for (int q = lane; q < 128; q += 64) {
         Fr29 x;
@@ -219,6 +234,53 @@ __global__ __launch_bounds__(256) void k_fk20_scalars(const Fr* __restrict__ coe
         for (int sg = 1; sg < segs; sg++)  // (x sh) is this form again
             emit(((size_t)(sg * n + b) * 128 + j) * 64 + i, fr29_mul(x, sh.p[sg - 1]));  // plain x times the Montgomery form of the shift: plain
     }
+}
+
+// Stages H+I and C in one launch: k_coeffs_to_cells that also emits the FK20 scalars of its half of the extended domain, read from
+// the transform's LDS image after the third pass (fr29_ntt.hpp, THE FK20 TAP: block h holds every scalar with j = h mod 2 up to one
+// constant factor; barriers: ntt4096_ct_forward_head).  Same grid, LDS layout and passes as k_coeffs_to_cells; the scalars' layout and
+// form are k_fk20_scalars' (segment copies included), bit for bit.  tapk: launch::fk20_tap_consts for the wanted scale.
+// Cells 0..63 are the blob (the transform of half 0 inverts k_blob_to_coeffs): with `blobs` given and blob b accepted (status 0: every
+// element canonical, so its bytes ARE the canonical encoding), block h = 0 stops after its scalars and copies the 128 KiB across.  A
+// rejected blob, and a caller without the blob's bytes (blobs = null), finish the transform.
+__global__ __launch_bounds__(1024) void k_coeffs_to_cells_scalars(const Fr* __restrict__ coeffs, uint8_t* __restrict__ cells,
+                                                                 Fr* __restrict__ scalars, const uint8_t* __restrict__ blobs,
+                                                                 const int* __restrict__ status, const Fr29* __restrict__ w29,
+                                                                 const Fr29* __restrict__ tapk, int n, int segs, SegShifts sh) {
+    extern __shared__ uint32_t s[];
+    const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
+    for (int e = tid; e < N_BLOB; e += 1024) {
+        Fr29 c = fr29_from_fr_mont(coeffs[(size_t)b * N_BLOB + e]);  // < 32 r
+        if (h && e) c = fr29_mul(c, w29[e]);                          // < 2 r
+        lds_store(s, e, c);
+    }
+    __syncthreads();
+    ntt4096_ct_forward_head(s, w29);  // < 32 + 12 = 44 r
+    const int e0 = ((tid >> 6) << 8) + (tid & 63);  // this thread's unit of pass h = 64
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {
+        const int e = e0 + 64 * k;
+        const Fr29 x = fk20_tap_scalar(LdsElems{s}, tapk, e, h);  // (< 44 r) x (< r): the plain scalar, < 2r
+        const size_t at = (size_t)fk20_tap_row(e, h) * 64 + fk20_tap_column(e);
+        store_split_scalar(&scalars[(size_t)b * N_EXT + at], x);
+        for (int sg = 1; sg < segs; sg++)  // plain x times the Montgomery form of the shift: plain (k_fk20_scalars)
+            store_split_scalar(&scalars[(size_t)(sg * n + b) * N_EXT + at], fr29_mul(x, sh.p[sg - 1]));
+    }
+    uint8_t* out = cells + ((size_t)b * N_EXT + (size_t)h * N_BLOB) * 32;
+    if (h == 0 && blobs && status[b] == 0) {  // uniform over the block: no barrier follows
+        const uint4* src = reinterpret_cast<const uint4*>(blobs + (size_t)b * BYTES_PER_BLOB);
+        uint4* dst = reinterpret_cast<uint4*>(out);
+        for (int k = tid; k < BYTES_PER_BLOB / 16; k += 1024) dst[k] = src[k];
+        return;
+    }
+    ntt4096_ct_forward_tail(s, w29);  // < 56 r
+    const Fr29 one_plain = fr29_const(r29::ONE_PLAIN);
+    for (int e = tid; e < N_BLOB; e += 1024)
+        store_fr_be(out + 32 * e, fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), one_plain))));  // X / 2^261 = the value
+}
+__global__ void k_fk20_tap_consts(const Fr29* __restrict__ w29, Fr29 scale_plain, Fr29* __restrict__ out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < 2 * N_BLOB) out[idx] = fk20_tap_const(w29, scale_plain, idx);
 }
 
 #ifdef KZG_TEST_HOOKS  // stage-level test kernels: compiled into libc_eth_kzg_hooks.so only (csrc/Makefile)
@@ -272,6 +334,7 @@ constexpr size_t LDS_NTT29 = (size_t)N_BLOB * RL * 4;  // 144 KiB: one 4096-poin
 void init_attributes() {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_coeffs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
 #ifdef KZG_TEST_HOOKS
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_test_ntt4096), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
 #endif
@@ -313,6 +376,21 @@ void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, con
     SegShifts sh;
     for (int i = 0; i < 3; i++) sh.p[i] = fr29_mont_of(seg_shifts[i]);
     k_fk20_scalars<<<n * 16, 256, 0, st>>>((const Fr*)coeffs, (Fr*)scalars, (const Fr29*)w29, fr29_int32x_of(inv128), n, segs, sh);
+}
+void fk20_tap_consts(const void* w29, const Fr8& scale, void* out, hipStream_t st) {
+    k_fk20_tap_consts<<<2 * N_BLOB / 256, 256, 0, st>>>((const Fr29*)w29, fr29_from_plain(from_mont(as_fr(scale))), (Fr29*)out);
+}
+void coeffs_to_cells_scalars(int n, const void* coeffs, uint8_t* cells, void* scalars, const uint8_t* blobs, const int* status, const void* w29,
+                             const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st) {
+    // the 16-byte copy of an accepted blob wants both ends aligned and apart (a caller may hand in any byte address, and cells that
+    // overlap the blobs were fine while every blob was read before the first cell was written): otherwise every block transforms
+    const uintptr_t pb = (uintptr_t)blobs, pc = (uintptr_t)cells;
+    const bool apart = pb + (size_t)n * BYTES_PER_BLOB <= pc || pc + (size_t)n * N_EXT * 32 <= pb;
+    if (!status || ((pb | pc) & 15) || !apart) blobs = nullptr;
+    SegShifts sh;
+    for (int i = 0; i < 3; i++) sh.p[i] = fr29_mont_of(seg_shifts[i]);
+    k_coeffs_to_cells_scalars<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, cells, (Fr*)scalars, blobs, status, (const Fr29*)w29,
+                                                                   (const Fr29*)tapk, n, segs, sh);
 }
 #ifdef KZG_TEST_HOOKS
 void test_ntt4096(const uint8_t* in, uint8_t* out, const void* w29, const Fr8& n_inv, int inverse_dit, hipStream_t st) {

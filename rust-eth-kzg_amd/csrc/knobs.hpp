@@ -23,6 +23,8 @@
 //   ETH_KZG_AMD_VM_FOLD=0           many-verification: one pairing per problem instead of one folded check per pass
 //   ETH_KZG_AMD_VERIFY_COMBINE=0    concurrent single verifications are not combined into passes
 //   ETH_KZG_AMD_MSM_SPLIT=0         batches of <= 32 blobs: a lane per MSM window (rounds 2-5) instead of two (A/B runs, the tests' cross-check)
+//   ETH_KZG_AMD_FUSED_SCALARS=0|1   0: k_coeffs_to_cells + k_fk20_scalars at every batch size (the pair the fused kernel replaces: the parity
+//                                   test's other side, A/B runs of one build), 1: k_coeffs_to_cells_scalars wherever cells and proofs are both asked for
 //   ETH_KZG_AMD_DEVICE_BATCH_MAX=<n> a device-resident prover call is cut into sub-batches of at most n blobs (default 4096)
 //   ETH_KZG_AMD_FAULT=constructor   the context's constructor throws after its last step but one (tests: try_new returns NULL + a
 //                                   message, nothing leaks, the next context works)
@@ -45,7 +47,7 @@ struct Knobs {
     int host_threads = 0;  // 0: chosen from the core count
     int serial_lanes = 0;  // 0: the engine's default
     bool trace = false;
-    int msm_chunks = -1, slp_program = -1, pip_shift_min = 0;
+    int msm_chunks = -1, slp_program = -1, pip_shift_min = 0, fused_scalars = -1;
     bool vm_search = true, vm_fold = true, verify_combine = true, msm_split = true;
     std::string fault;  // ETH_KZG_AMD_FAULT (a copy: the environment may change under a long-lived context)
     int device_batch_max = 0;
@@ -87,6 +89,7 @@ struct Knobs {
         flag("ETH_KZG_AMD_VM_FOLD", k.vm_fold);
         flag("ETH_KZG_AMD_VERIFY_COMBINE", k.verify_combine);
         flag("ETH_KZG_AMD_MSM_SPLIT", k.msm_split);
+        num("ETH_KZG_AMD_FUSED_SCALARS", 0, 1, k.fused_scalars);
         if (const char* s = getenv("ETH_KZG_AMD_FAULT")) k.fault = s;
         num("ETH_KZG_AMD_DEVICE_BATCH_MAX", 64, 1 << 20, k.device_batch_max);
         return k;

@@ -29,6 +29,12 @@ void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29,
 // every scalar leaves as its balanced GLV halves (what launch::glv_split would make of it)
 void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, const Fr8& inv128, int segs, const Fr8* seg_shifts,
                   hipStream_t st);
+// coeffs_to_cells and fk20_scalars in one launch (k_coeffs_to_cells_scalars: the scalars are an intermediate of the cells' transform).
+// tapk: one half (2 x 4096 x 36 B) of the table fk20_tap_consts builds for the scale fk20_scalars would have been given; blobs + status
+// (both may be null): cells 0..63 of a blob with status 0 are copied from its bytes instead of being transformed back.
+void fk20_tap_consts(const void* w29, const Fr8& scale, void* out /*8192 x 36 B*/, hipStream_t st);
+void coeffs_to_cells_scalars(int n, const void* coeffs, uint8_t* cells, void* scalars, const uint8_t* blobs, const int* status, const void* w29,
+                             const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st);
 void test_ntt4096(const uint8_t* in, uint8_t* out, const void* w29, const Fr8& n_inv, int inverse_dit, hipStream_t st);
 void test_scalars_be(const uint8_t* in, void* out, size_t n, hipStream_t st);
 void test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp, hipStream_t st);
