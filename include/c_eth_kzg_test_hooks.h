@@ -61,6 +61,28 @@ int eth_kzg_amd_test_verify_cells_partial_device(const DASContext *ctx, uint64_t
 int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext *ctx, uint64_t n, int on_device, const void *blobs, const void *commitments,
                                               const void *proofs, uint8_t *out96, int32_t *verified);
 
+/* ONE pass of eth_kzg_amd_verify_cell_kzg_proof_batch_many with what it pairs handed out (tests/test_verify_inputs.py compares every byte
+ * with the statement of tests/verify_transcript.py: per-problem power tables, positions, row weights, sums, the folding weights, the fold
+ * and the search's probes all show in them; a verdict shows none of that).  The arguments of the public call (host pointers), and exactly its
+ * launches: the engine's pass fills a tap from the pinned read-backs it makes anyway, nothing is added on the device; points are compressed
+ * on the host.  The hook serves one pass: a call the engine would cut -- into parts from 192 problems with 24576 cells, into chunks above
+ * 131072 cells -- returns 3 before anything is launched, as does a NULL buffer (probe buffers may be NULL when max_probes is 0).
+ *   verified[B], status[B]: as the public call gives them.
+ *   form4: short-chain form (1 / 0), folded (1 / 0), the search ran (1 / 0), the folded check's verdict (1 / 0; -1 when not folded).
+ *   sums96[B][96]: compress(A_b) | compress(B_b), the two sums of problem b that pair with [tau^64]_2 and -[1]_2; unspecified for a problem
+ *     that is empty or whose status is not 0.
+ *   rho[B][4]: the folding weights, little-endian words as uploaded (folded passes; 0 for a problem that takes no part).
+ *   fold96: compress(S_0) | compress(S_1), S_j = sum_b rho_b sums[b][j] (folded passes).
+ *   probe_ranges[i] = (lo, hi, passed), probe_sums96[i] = the pair summed over problems lo <= b < hi with the same weights: the probes of the
+ *     search for the wrong problems, in the order they were made, the first max_probes of them; *n_probes = how many were made.
+ * Synchronous; returns 0 on success, the library's status codes otherwise. */
+int eth_kzg_amd_test_verify_many_sums(const DASContext *ctx, uint64_t n_batches, const uint64_t *commitments_lengths,
+                                      const uint8_t *const *const *commitments, const uint64_t *cell_indices_lengths,
+                                      const uint64_t *const *cell_indices, const uint64_t *cells_lengths, const uint8_t *const *const *cells,
+                                      const uint64_t *proofs_lengths, const uint8_t *const *const *proofs, int32_t *verified, int32_t *status,
+                                      int32_t *form4, uint8_t *sums96, uint32_t *rho, uint8_t *fold96, int32_t *probe_ranges,
+                                      uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes);
+
 /* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode in recover.hip, exactly the launches recovery runs).  R >= 1 blobs; blob r has
  * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
  * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat

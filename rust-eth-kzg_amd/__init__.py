@@ -78,7 +78,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_table_info", "eth_kzg_amd_test_table_audit", "eth_kzg_amd_test_table_read", "eth_kzg_amd_test_table_audit_buffer",
     "eth_kzg_amd_test_sha256_many", "eth_kzg_amd_test_verify_msm",
     "eth_kzg_amd_test_verify_cells_partial_device", "eth_kzg_amd_test_verify_blob_batch_inputs", "eth_kzg_amd_test_rs_decode",
-    "eth_kzg_amd_test_prover_scalars",
+    "eth_kzg_amd_test_prover_scalars", "eth_kzg_amd_test_verify_many_sums",
 ]
 
 _lib = None
@@ -194,6 +194,7 @@ def load_library():
         "eth_kzg_amd_test_verify_blob_batch_inputs": [P, U64, C.c_int, P, P, P, P, P],
         "eth_kzg_amd_test_rs_decode": [P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, P],
         "eth_kzg_amd_test_prover_scalars": [P, C.c_int, P, P, U64, P, P, P, P, P],
+        "eth_kzg_amd_test_verify_many_sums": [P, U64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, U64, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -501,6 +502,21 @@ class DASContext:
         eth_kzg_amd_verify_cell_kzg_proof_batch_many ONCE and return a zero-argument callable that runs the call and
         returns (verified list[bool], status list[int]) -- status 0 ok, 1 bad field element, 2 bad G1 point, 3 invalid
         lengths / indices: what the single form raises as KzgError."""
+        nb, lens, tabs, keep = self._marshal_many(problems)
+        ver = (C.c_bool * max(1, nb))()
+        st = (C.c_int32 * max(1, nb))()
+
+        def run(_keep=keep):
+            self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_many(
+                self._ctx, nb, _vp(lens[0]), _vp(tabs[0]), _vp(lens[1]), _vp(tabs[1]), _vp(lens[2]), _vp(tabs[2]), _vp(lens[3]), _vp(tabs[3]),
+                ver, st))
+            return [bool(v) for v in ver][:nb], list(st)[:nb]
+        return run
+
+    @staticmethod
+    def _marshal_many(problems):
+        """-> (count, lens[4][count], tabs[4][count], keep-alive): the length and pointer tables of the many-verification's arguments, in
+        the order commitments, cell indices, cells, proofs"""
         nb = len(problems)
         keep, lens = [], np.zeros((4, max(1, nb)), dtype=np.uint64)
         tabs = [np.zeros(max(1, nb), dtype=np.uint64) for _ in range(4)]  # per problem: commitments**, indices*, cells**, proofs**
@@ -517,16 +533,7 @@ class DASContext:
             keep += [ca, k1, cla, k2, pa, k3, idx]
             lens[:, b] = (len(commitments), len(cell_indices), len(cells), len(proofs))
             tabs[0][b], tabs[1][b], tabs[2][b], tabs[3][b] = ca.ctypes.data, idx.ctypes.data, cla.ctypes.data, pa.ctypes.data
-        lens = np.ascontiguousarray(lens)
-        ver = (C.c_bool * max(1, nb))()
-        st = (C.c_int32 * max(1, nb))()
-
-        def run(_keep=keep):
-            self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_many(
-                self._ctx, nb, _vp(lens[0]), _vp(tabs[0]), _vp(lens[1]), _vp(tabs[1]), _vp(lens[2]), _vp(tabs[2]), _vp(lens[3]), _vp(tabs[3]),
-                ver, st))
-            return [bool(v) for v in ver][:nb], list(st)[:nb]
-        return run
+        return nb, np.ascontiguousarray(lens), tabs, keep
 
     def verify_cell_kzg_proof_batch_many(self, problems):
         """Many independent verify_cell_kzg_proof_batch problems in one call (see prepare_verify_cell_kzg_proof_batch_many)."""

@@ -69,6 +69,19 @@ int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext* ctx, uint64_t n,
     *verified = v;
     return rc;
 }
+int eth_kzg_amd_test_verify_many_sums(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths,
+                                      const uint8_t* const* const* commitments, const uint64_t* cell_indices_lengths,
+                                      const uint64_t* const* cell_indices, const uint64_t* cells_lengths, const uint8_t* const* const* cells,
+                                      const uint64_t* proofs_lengths, const uint8_t* const* const* proofs, int32_t* verified, int32_t* status,
+                                      int32_t* form4, uint8_t* sums96, uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96,
+                                      uint64_t max_probes, uint64_t* n_probes) {
+    if (!commitments_lengths || !commitments || !cell_indices_lengths || !cell_indices || !cells_lengths || !cells || !proofs_lengths || !proofs ||
+        !verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || (max_probes && (!probe_ranges || !probe_sums96)))
+        return kzg::ERR_INPUT;
+    return eng(ctx)->test_verify_many_sums(n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells,
+                                           proofs_lengths, proofs, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes,
+                                           n_probes);
+}
 int eth_kzg_amd_test_rs_decode(const DASContext* ctx, int R, const uint64_t* n_cells, const uint64_t* const* cell_indices,
                                const uint8_t* const* const* cells, int flat_source, int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval,
                                uint8_t* zcinv, uint8_t* coeffs) {

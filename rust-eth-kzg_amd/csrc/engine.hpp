@@ -31,6 +31,22 @@ struct Fp12w { uint32_t v[12]; };
 // (k_verify.hip: k_verify_scalars, k_verify_many.hip: k_vm_scalars) and positions are 32-bit on the device.  2^24 cells are 34 GB
 // of input; longer lists are rejected as invalid input by every verification entry point.
 constexpr uint64_t MAX_CELLS_PER_VERIFICATION = (1u << 24) - 1;
+// How verify_cell_kzg_proof_batch_many_host divides a call (verify_many.hip): a call of at least VM_SPLIT_MIN_PROBLEMS problems and
+// VM_SPLIT_MIN_CELLS cells is cut into concurrent parts, and a pass holds at most VM_CHUNK_CELLS cells (1024 verifications of 128
+// cells: 275 MB of pinned staging, ~1 GB of device arena)
+constexpr int VM_SPLIT_MIN_PROBLEMS = 192, VM_SPLIT_MIN_CELLS = 24576, VM_CHUNK_CELLS = 131072;
+// Tap of a many-verification pass (null in every product call; the stage hook test_verify_many_sums sets it): copies of what the pass's
+// pinned read-backs held after the syncs the pass makes anyway, in the kernels' own words (JacQ = launch::SIZEOF_JACQ bytes).
+struct VerifyManyTap {
+    int passes = 0;                                  // passes the call ran (the hook serves calls of one pass)
+    int small = 0, folded = 0, searched = 0;         // the form of the pass
+    int fold_verdict = -1;                           // of the folded check (folded passes)
+    std::vector<uint8_t> sums;                       // [Bc][2] JacQ: the problems' two sums
+    std::vector<uint32_t> rho;                       // [Bc][4]: the folding weights as uploaded
+    std::vector<uint8_t> fold;                       // [2] JacQ: the folded pair
+    std::vector<int> probes;                         // the search's probes in order: lo, hi, passed
+    std::vector<uint8_t> probe_sums;                 // [probe][2] JacQ
+};
 
 enum Status : int {
     OK = 0,
@@ -159,7 +175,7 @@ public:
     int verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint64_t* n_commitments, const uint8_t* const* const* commitments,
                                               const uint64_t* n_indices, const uint64_t* const* cell_indices, const uint64_t* n_cells,
                                               const uint8_t* const* const* cells, const uint64_t* n_proofs,
-                                              const uint8_t* const* const* proofs, int* verified, int* status);
+                                              const uint8_t* const* const* proofs, int* verified, int* status, VerifyManyTap* tap = nullptr);
     // verify_cell_kzg_proof_batch as the reference's users call it -- one problem per call, from many threads on one context
     // (bindings/node/src/lib.rs:92-299) -- WITHOUT asking them to batch: the first callers take the latency-optimised path
     // (verify_cell_kzg_proof_batch_host, one per engine lane); callers that arrive while every lane is verifying
@@ -243,6 +259,13 @@ public:
     // the two sums verify_blob_kzg_proof_batch pairs (rhs | lhs, compressed) and its verdict; on_device: flat arrays in HBM, else host pointers
     int test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs, uint8_t* out96,
                                       int* verified);
+    // one pass of verify_cell_kzg_proof_batch_many_host with its tap set: verdicts and statuses as the call gives them, form = small, folded,
+    // searched, folded verdict; sums96[B] and fold96 compressed on the host from the sums read back, rho[B][4], the search's probes
+    // (probe_ranges[i] = lo, hi, passed; probe_sums96[i]) up to max_probes of them, *n_probes = how many there were
+    int test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
+                              const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells, const uint64_t* n_proofs,
+                              const uint8_t* const* const* proofs, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho,
+                              uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes);
     // the Reed-Solomon decoder of recovery on its own: rs_decode (verify.hip) with its tap set, behind the staging of recover_batch_to_coeffs
     // (flat_source = 0) or of recover_cells_and_kzg_proofs_device (1); outputs canonical big-endian on the host, each may be null
     int test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,

@@ -329,6 +329,60 @@ int Engine::test_verify_blob_batch_inputs(uint64_t n, int on_device, const void*
     return OK;
 }
 
+// One pass of the many-verification with its tap set (verify_many.hip): the launches are the public call's, the tap copies the pinned
+// read-backs after the pass's own syncs, and the points are compressed here, on the host.  The caller (c_api_hooks.cpp) has refused
+// null buffers; a call the engine would cut into parts or chunks is refused before anything is launched.
+int Engine::test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
+                                  const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells,
+                                  const uint64_t* n_proofs, const uint8_t* const* const* proofs, int32_t* verified, int32_t* status, int32_t* form4,
+                                  uint8_t* sums96, uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes,
+                                  uint64_t* n_probes) {
+    if (n_batches < 1 || n_batches > (1u << 20)) return ERR_INPUT;
+    uint64_t total_cells = 0;
+    for (uint64_t b = 0; b < n_batches; b++) {
+        if (n_cells[b] > (uint64_t)VM_CHUNK_CELLS) return ERR_INPUT;
+        total_cells += n_cells[b];
+    }
+    if (total_cells > (uint64_t)VM_CHUNK_CELLS) return ERR_INPUT;                                                        // chunks
+    if (n_batches >= (uint64_t)VM_SPLIT_MIN_PROBLEMS && total_cells >= (uint64_t)VM_SPLIT_MIN_CELLS) return ERR_INPUT;  // parts
+    const int B = (int)n_batches;
+    std::vector<int> ver(B), st(B);
+    VerifyManyTap tap;
+    const int rc = verify_cell_kzg_proof_batch_many_host(n_batches, n_commitments, commitments, n_indices, cell_indices, n_cells, cells, n_proofs, proofs,
+                                                         ver.data(), st.data(), &tap);
+    if (rc) return rc;
+    if (tap.passes > 1) return ERR_INPUT;  // (cannot happen behind the checks above)
+    static_assert(sizeof(JacQ) == launch::SIZEOF_JACQ, "the tap holds JacQ words");
+    auto compress2 = [](uint8_t* out96, const uint8_t* two) {  // a slot that still holds its poison comes out as 0xff bytes
+        for (int j = 0; j < 2; j++) {
+            JacQ s;
+            memcpy(&s, two + (size_t)j * sizeof(JacQ), sizeof(JacQ));
+            if (s.x.v[0] == 0xffffffffu && s.z.v[0] == 0xffffffffu) memset(out96 + 48 * j, 0xff, 48);
+            else g1_compress(out96 + 48 * j, to_affine(jac_from_jacq(s)));
+        }
+    };
+    for (int b = 0; b < B; b++) {
+        verified[b] = st[b] == OK && ver[b] != 0;
+        status[b] = st[b];
+        memset(sums96 + 96 * (size_t)b, 0, 96);
+        rho[4 * b] = rho[4 * b + 1] = rho[4 * b + 2] = rho[4 * b + 3] = 0;
+    }
+    form4[0] = tap.small; form4[1] = tap.folded; form4[2] = tap.searched; form4[3] = tap.fold_verdict;
+    memset(fold96, 0, 96);
+    *n_probes = tap.probes.size() / 3;
+    if (tap.passes == 0) return OK;  // no cell in the whole call: nothing was launched
+    for (int b = 0; b < B; b++) {
+        if (st[b] == OK && n_cells[b] > 0) compress2(sums96 + 96 * (size_t)b, tap.sums.data() + (size_t)2 * b * sizeof(JacQ));
+        for (int j = 0; j < 4; j++) rho[4 * b + j] = tap.rho[4 * (size_t)b + j];
+    }
+    if (tap.folded) compress2(fold96, tap.fold.data());
+    for (uint64_t q = 0; q < *n_probes && q < max_probes; q++) {
+        for (int j = 0; j < 3; j++) probe_ranges[3 * q + j] = tap.probes[3 * q + j];
+        compress2(probe_sums96 + 96 * q, tap.probe_sums.data() + (size_t)2 * q * sizeof(JacQ));
+    }
+    return OK;
+}
+
 // The Reed-Solomon decoder of recovery on its own: the masks, slots and cell bytes staged as recover_batch_to_coeffs (list form) or
 // recover_cells_and_kzg_proofs_device (flat form) stage them, then rs_decode with its tap.  The caller (c_api_hooks.cpp) has validated
 // the counts and indices.  Outputs canonical big-endian.

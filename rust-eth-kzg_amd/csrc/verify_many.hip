@@ -94,6 +94,7 @@ struct PassHost {
     std::vector<int> cell_start, row_start;  // first cell / first unique commitment of each problem
     std::vector<uint8_t> digests;            // of the challenges: the fold seed hashes them
     std::vector<char> live;                  // problems that decoded without an error
+    VerifyManyTap* tap = nullptr;            // (null in the product) receives copies of the read-backs
     const JacQ* sums() const { return (const JacQ*)(hb + L.poff_out); }  // the problems' two sums read back
     int* h_status() const { return (int*)(hb + L.poff_st); }  // read-backs: [proofs n | commitments m | cells, per problem]
 
@@ -224,6 +225,14 @@ void search_wrong_proofs(PassHost& V, int n_live, uint8_t* db, hipStream_t st) {
                 if (v < 0) V.device_fault.store(1);
                 else fails[q0 + q] = v ? 0 : 1;
             });
+            if (V.tap && !V.device_fault.load()) {
+                V.tap->searched = 1;
+                for (size_t q = 0; q < cnt; q++) {
+                    const int rec[3] = {probes[q0 + q].first, probes[q0 + q].second, fails[q0 + q] ? 0 : 1};
+                    V.tap->probes.insert(V.tap->probes.end(), rec, rec + 3);
+                }
+                V.tap->probe_sums.insert(V.tap->probe_sums.end(), hb + L.poff_rsum, hb + L.poff_rsum + cnt * 2 * launch::SIZEOF_JACQ);
+            }
         }
         if (V.device_fault.load()) break;
         suspects.clear();
@@ -245,7 +254,7 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
                                                   const uint8_t* const* const* commitments, const uint64_t* n_indices,
                                                   const uint64_t* const* cell_indices, const uint64_t* n_cells,
                                                   const uint8_t* const* const* cells, const uint64_t* n_proofs,
-                                                  const uint8_t* const* const* proofs, int* verified, int* status) {
+                                                  const uint8_t* const* const* proofs, int* verified, int* status, VerifyManyTap* tap) {
     const int B = (int)n_batches;
     for (int b = 0; b < B; b++) { verified[b] = 0; status[b] = OK; }
     if (B == 0) return OK;
@@ -255,10 +264,10 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
     // pairing check (one pass, round 3's form: 28.4-28.9 ms against 24.6-26.2 for 1024 problems).
     static thread_local bool in_part = false;
     constexpr int max_parts = VM_SLOTS < 3 ? (int)VM_SLOTS : 3;
-    if (!in_part && max_parts > 1 && B >= 192) {
+    if (!in_part && max_parts > 1 && B >= VM_SPLIT_MIN_PROBLEMS) {
         uint64_t total_cells = 0;
         for (int b = 0; b < B; b++) total_cells += n_cells[b];
-        if (total_cells >= 24576) {
+        if (total_cells >= (uint64_t)VM_SPLIT_MIN_CELLS) {
             const int parts = max_parts;
             std::vector<int> cut{0};
             uint64_t acc = 0;
@@ -315,7 +324,7 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             p.m = (int)p.uniq.size();
         });
         // ---- chunks of problems: at most CHUNK_CELLS cells per pass (the pinned slab and the arena stay bounded)
-        constexpr int CHUNK_CELLS = 131072;  // 1024 verifications of 128 cells: 275 MB of pinned staging, ~1 GB of device arena
+        constexpr int CHUNK_CELLS = VM_CHUNK_CELLS;
         bool fold = true;  // one folded pairing check per pass instead of one per problem (falls back to per-problem checks when it fails)
         if (!knobs_.vm_fold) fold = false;  // (test hook: one pairing per problem)
         for (int b0 = 0; b0 < B;) {
@@ -333,6 +342,7 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
             uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
             PassHost H{L, pr.data() + b0, cell_indices + b0, cells + b0, proofs + b0, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, verified + b0};
+            H.tap = tap;
             H.stage();
             int* h_st = H.h_status();
             HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)(n + m) * 4, st));
@@ -379,12 +389,20 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             HIPCK(hipMemcpyAsync(hb + L.poff_out, db + L.off_out, (size_t)2 * Bc * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
             SYNC_CHECKED(st);
             if (small) n_live = H.judge(status + b0);
+            if (tap) {
+                tap->passes++;
+                tap->small = small; tap->folded = folded;
+                tap->sums.assign(hb + L.poff_out, hb + L.poff_out + (size_t)2 * Bc * launch::SIZEOF_JACQ);
+                tap->rho.assign((const uint32_t*)(hb + L.off_rho), (const uint32_t*)(hb + L.off_rho) + 4 * (size_t)Bc);
+                if (folded) tap->fold.assign(hb + L.poff_fold, hb + L.poff_fold + (size_t)2 * launch::SIZEOF_JACQ);
+            }
             // ---- verdicts: ONE pairing check of the folded sums; only if that fails (some problem's proof is wrong) one per problem
             bool all_true = false;
             if (folded) {
                 const int v = check_pair((const JacQ*)(hb + L.poff_fold), H.vk);
                 if (v < 0) throw std::runtime_error("many-verification pass left no folded result");
                 all_true = v == 1;
+                if (tap) tap->fold_verdict = v;
             }
             if (all_true) {
                 for (int i = 0; i < Bc; i++)

@@ -11,7 +11,10 @@ Written from the reference's source, not from oracle/kzg.c and not from csrc/ver
 Everything in Fr is hashlib and Python integers.  Only the final sums in G1 go through oracle_lib.g1_msm, which tests/test_verify_msm.py
 and tests/test_oracle_units.py pin on their own.  A verdict is one bit that does not depend on the challenge for valid inputs; the 96
 bytes of the two pairing inputs depend on every byte of the transcript, every power of r, every weight and every interpolation
-coefficient."""
+coefficient.
+
+The many-verification's fold (its weights, the folded pair, the probes of its search) is stated in its own section below, and
+many_cases() holds the passes it is compared on."""
 import hashlib
 import os
 import random
@@ -80,8 +83,8 @@ def dedup(commitments):
     return uniq, row
 
 
-def cell_challenge(commitments, indices, cells, proofs):
-    """compute_fiat_shamir_challenge (verifier.rs:269-328) -> r.  The transcript covers the whole batch whatever range is evaluated."""
+def cell_digest(commitments, indices, cells, proofs):
+    """the raw SHA-256 of the cell transcript (verifier.rs:269-328), before it is reduced: 32 bytes"""
     uniq, row = dedup(commitments)
     n = len(indices)
     h = hashlib.sha256()
@@ -91,7 +94,12 @@ def cell_challenge(commitments, indices, cells, proofs):
         h.update(be64(row[k]) + be64(indices[k]))
         h.update(cells[k])
         h.update(proofs[k])
-    return reduce_digest(h.digest())
+    return h.digest()
+
+
+def cell_challenge(commitments, indices, cells, proofs):
+    """compute_fiat_shamir_challenge (verifier.rs:269-328) -> r.  The transcript covers the whole batch whatever range is evaluated."""
+    return reduce_digest(cell_digest(commitments, indices, cells, proofs))
 
 
 _interp_cache = {}
@@ -152,6 +160,37 @@ def cell_partial(commitments, indices, cells, proofs, lo, hi, r=None):
     b = oracle_lib.g1_msm(pi + b"".join(uniq) + b"".join(setup_g1_first64()),
                           b"".join(fr_be(s) for s in s2) + b"".join(fr_be(s) for s in w) + b"".join(fr_be(-s) for s in interp))
     return a + b
+
+
+# ---- the many-verification's fold ------------------------------------------------------------------------------------------------------
+# One pairing check stands for all problems of a pass (csrc/verify_host.hpp: "folding weights of a many-verification pass", DESIGN.md
+# section 4, `k_vm_*`): with sum_b = the two pairing inputs of problem b, S_j = sum_b rho_b sum_b[j].  The weights hang on every input byte of the
+# pass through the problems' transcript digests.  Written from that definition, not by calling the library.
+FOLD_DOMAIN = b"RCKZGCBATCHFOLD1"
+
+
+def fold_weights(digests, takes_part):
+    """digests[i]: the raw 32-byte transcript digest of problem i of the pass (32 zero bytes for a problem that was skipped before it was
+    hashed); takes_part[i]: the problem is neither empty nor refused.  seed = SHA-256(domain | all digests in order); rho_i = the first 16
+    bytes of SHA-256(seed | be64(i)) as a little-endian integer mod 2^127, 0 -> 1, with i the position in the PASS; rho_i = 0 for a problem
+    that takes no part."""
+    assert len(digests) == len(takes_part) and all(len(d) == 32 for d in digests)
+    seed = hashlib.sha256(FOLD_DOMAIN + b"".join(digests)).digest()
+    out = []
+    for i, on in enumerate(takes_part):
+        v = int.from_bytes(hashlib.sha256(seed + be64(i)).digest()[:16], "little") % (1 << 127)
+        out.append((v or 1) if on else 0)
+    return out
+
+
+def fold_pair(sums, rho, lo, hi):
+    """compress(S_0) | compress(S_1) over the problems lo <= b < hi: S_j = sum_b rho_b sums[b][j] (sums[b] = the problem's 96 bytes; the
+    whole pass is the folded pair, a sub-range is a probe of the search).  Problems of weight 0 take no part, whatever their sums."""
+    part = [b for b in range(lo, hi) if rho[b]]
+    if not part:
+        return INF + INF
+    sc = b"".join(fr_be(rho[b]) for b in part)
+    return oracle_lib.g1_msm(b"".join(sums[b][:48] for b in part), sc) + oracle_lib.g1_msm(b"".join(sums[b][48:] for b in part), sc)
 
 
 # ---- the blob batch verifier -----------------------------------------------------------------------------------------------------------
@@ -327,6 +366,193 @@ def cell_cases(seed=SEED):
     # k in [8190, 8200) sets bits 1 .. 13 and, with [4090, 4100), bit 0: table entries 0 .. 13; 4095 -> 4096 carries across bit 12
     out.append(CellCase("exponents-to-2^13", rnd(N_BIG), BIG_RANGES, n=N_BIG, bits=(1 << 14) - 1, carry=12))
     assert len({c.name for c in out}) == len(out)
+    return out
+
+
+# ---- the passes of the many-verification -------------------------------------------------------------------------------------------------
+_off_subgroup = None
+
+
+def off_subgroup_point():
+    """a compressed point on the curve and outside the subgroup: the smallest x >= 5 that gives one (the oracle says which)"""
+    global _off_subgroup
+    x = 5
+    while _off_subgroup is None:
+        cand = bytearray(x.to_bytes(48, "big"))
+        cand[0] |= 0x80
+        if oracle_lib.g1_validate(bytes(cand), False) == 0 and oracle_lib.g1_validate(bytes(cand), True) != 0:
+            _off_subgroup = bytes(cand)
+        x += 1
+    return _off_subgroup
+
+
+class ManyProblem:
+    """One problem of a pass: a CellCase as it stands ("valid"), or changed into
+      "empty"         no cells: verified without a check, takes no part in the fold (status 0)
+      "swapped"       two proofs exchanged (entries `swap`): everything decodes, the sums are exact MSMs, the verdict is False
+      "bad-index"     a cell index of 128: refused at validation, before anything is hashed (status 3)
+      "bad-scalar"    a cell element r: refused by the decoder (status 1)
+      "off-subgroup"  a proof on the curve and outside the subgroup: refused by the subgroup test (status 2)"""
+    STATUS = {"valid": 0, "empty": 0, "swapped": 0, "bad-scalar": 1, "off-subgroup": 2, "bad-index": 3}
+
+    def __init__(self, case, kind="valid", swap=None):
+        self.case, self.kind, self.swap = case, kind, swap
+        self.name = case.name if kind == "valid" else "empty" if kind == "empty" else "%s:%s" % (case.name, kind)
+        self.status = self.STATUS[kind]
+        self.live = kind in ("valid", "swapped")            # takes part in the sums, the fold and the search
+        self.hashed = kind not in ("empty", "bad-index")    # its transcript was hashed (decoding verdicts arrive behind the hashes)
+        self.verdict = kind in ("valid", "empty")           # what the public call reports as verified
+
+    def args(self, mat):
+        if self.kind == "empty":
+            return [], [], [], []
+        comm, idx, cells, proofs = (list(col) for col in self.case.args(mat))
+        last = len(idx) - 1
+        if self.kind == "swapped":
+            i, j = self.swap
+            assert proofs[i] != proofs[j], self.name
+            proofs[i], proofs[j] = proofs[j], proofs[i]
+        elif self.kind == "bad-index":
+            idx[last] = N_CELLS
+        elif self.kind == "bad-scalar":
+            cells[last] = cells[last][:-32] + R.to_bytes(32, "big")
+        elif self.kind == "off-subgroup":
+            proofs[last] = off_subgroup_point()
+        return comm, idx, cells, proofs
+
+
+class ManyPass:
+    def __init__(self, name, problems, small, folded, searched=False, **expect):
+        self.name, self.problems, self.small, self.folded, self.searched, self.expect = name, problems, small, folded, searched, expect
+
+    def cells(self):
+        """n cells and m unique commitments of the pass as the engine counts them: problems refused at validation hold none"""
+        n = m = 0
+        for q in self.problems:
+            if q.kind not in ("empty", "bad-index"):
+                n += len(q.case.entries)
+                m += len({b for b, _ in q.case.entries})
+        return n, m
+
+    def shares(self, i, j):
+        """problems i and j both hold cells and carry a commitment in common (entries name blobs; the material's commitments are distinct)"""
+        if not (0 <= i < len(self.problems) and 0 <= j < len(self.problems)) or i == j:
+            return False
+        a, b = self.problems[i], self.problems[j]
+        if a.kind in ("empty", "bad-index") or b.kind in ("empty", "bad-index"):
+            return False
+        return bool({x for x, _ in a.case.entries} & {x for x, _ in b.case.entries})
+
+    def check(self, host_threads, coop_points_max):
+        """the pass is one pass, takes the form it is meant to take under `host_threads` helper threads and holds what it is named for
+        (the thresholds are csrc/verify_many.hip's expressions)"""
+        B = len(self.problems)
+        n, m = self.cells()
+        live = [q.live for q in self.problems]
+        assert n <= 131072 and not (B >= 192 and n >= 24576), self.name                       # neither chunks nor parts
+        assert self.small == (B <= 2 * host_threads), (self.name, B)                          # the short-chain form
+        assert self.folded == (not self.small and sum(live) >= 2), self.name                  # one folded check
+        assert self.searched == (self.folded and not all(q.verdict for q in self.problems if q.live)), self.name
+        assert self.problems[0].kind not in ("empty", "bad-index"), self.name                 # problem 0 holds cells: later positions are > 0
+        e = self.expect
+        if "one_lane" in e:  # k_vm_mul_small_coop up to 2 * coop_points_max() products and subgroup tests, k_vm_mul_small above
+            assert self.small and e["one_lane"] == (3 * n + 2 * m + 64 * B > 2 * coop_points_max), (self.name, n, m, B)
+        if "kinds" in e:
+            assert sorted(q.kind for q in self.problems) == sorted(e["kinds"]), self.name
+        if "wrong" in e:
+            assert [i for i, q in enumerate(self.problems) if q.live and not q.verdict] == e["wrong"], self.name
+        if "n_problems" in e:
+            assert B == e["n_problems"], self.name
+        if e.get("sharing_is_adjacent"):  # a problem that shares a commitment with any problem of the pass shares one with a neighbour
+            for i in range(B):
+                anywhere = any(self.shares(i, j) for j in range(B))
+                assert anywhere == (self.shares(i, i - 1) or self.shares(i, i + 1)), (self.name, i)
+            assert sum(self.shares(i, i + 1) for i in range(B - 1)) >= e.get("adjacent_pairs", 1), self.name
+        if "lonely" in e:  # problems that share no commitment with anyone: they must stay put under a weight that looks next door
+            assert [i for i in range(B) if not any(self.shares(i, j) for j in range(B)) and self.problems[i].live] == e["lonely"], self.name
+        if "hole_before_live" in e:
+            dead = [i for i, q in enumerate(self.problems) if not q.live]
+            assert e["hole_before_live"] == bool(dead and any(live[dead[0]:])), self.name
+
+
+def search_plan(live, verdicts, host_threads):
+    """the probes of the search for the wrong problems of a pass, level by level, in the order they are made -- csrc/verify_many.hip's
+    expressions: suspects are handed to per-problem checks when they are at most 2 T problems or a quarter of the live ones are suspect
+    ranges, else every suspect range is cut K = clamp(T / ranges, 2, 16) ways.  -> [(lo, hi, passes)]"""
+    T, B, n_live = host_threads, len(live), sum(live)
+    suspects, out = [(0, B)], []
+    while suspects:
+        if len(suspects) * 4 >= n_live or sum(hi - lo for lo, hi in suspects) <= 2 * T:
+            break
+        K = min(16, max(2, T // len(suspects)))
+        probes = []
+        for lo, hi in suspects:
+            parts = min(K, hi - lo)
+            probes += [(lo + (hi - lo) * q // parts, lo + (hi - lo) * (q + 1) // parts) for q in range(parts)]
+        suspects = []
+        for lo, hi in probes:
+            ok = all(verdicts[b] for b in range(lo, hi) if live[b])
+            out.append((lo, hi, ok))
+            if not ok and hi - lo > 1:
+                suspects.append((lo, hi))
+    return out
+
+
+MANY_HOST_THREADS = 2  # of the context the passes run on: short-chain up to 4 problems, two-way splits, per-problem checks from 4 suspects
+SEARCH_WRONG = [0, 150, 299]
+SEARCH_EMPTY, SEARCH_REFUSED = 40, 200
+LARGE_ORDER = ["len-2", "len-63", "len-1", "len-64", "len-65", "len-255", "len-256", "len-257", "one-commitment", "row-of-280-next-to-row-of-1",
+               "all-128-indices", "constant-polynomial", "one-index", "cells-of-r-minus-1", "identity-commitment-only"]
+
+# pass -> kernels of csrc/k_verify_many.hip it reaches (k_vm_scalars, k_vm_weights and k_vm_interp_sum run in every pass)
+#   short-four-lanes    k_vm_mul_small_coop (products, the 64 interpolation terms per problem, subgroup blocks), k_vm_reduce_small
+#   short-holes         the same with an empty problem, a refused one and zero cells between exact neighbours
+#   short-one-lane      k_vm_mul_small (3 n + 2 m + 64 B > 2 coop_points_max()), k_vm_reduce_small's 128-stride loops, table entries 0 .. 13
+#   large-folded        k_vm_mul, the commitment window table's MSM, k_vm_reduce, k_vm_fold_mul_coop, k_vm_fold_sum (B < 128)
+#   large-one-live      k_vm_mul, k_vm_reduce; no fold below two live problems
+#   search              k_vm_fold_sum's stride loop (B > 128), k_vm_fold_ranges at widths above and below 128
+#   folded-ten          with the four-lane kernels switched off (a process of its own): k_vm_fold_mul; short-four-lanes there: k_vm_mul_small
+#                       and the one-lane subgroup blocks
+
+
+def many_cases(seed=SEED):
+    """every pass of the many-verification; a plain function of the seed.  Problems are the cell cases, or tiny ones of their kind."""
+    cc = {c.name: c for c in cell_cases(seed)}
+    rng = random.Random(seed + ":many")
+    rnd = lambda n, blobs=(0, 1, 2): [(rng.choice(blobs), rng.randrange(N_CELLS)) for _ in range(n)]  # noqa: E731
+    V = lambda name: ManyProblem(cc[name])  # noqa: E731
+    tiny = lambda name, n: CellCase(name, rnd(n), n=n)  # noqa: E731
+    empty = ManyProblem(CellCase("empty", []), "empty")
+    out = [ManyPass("short-four-lanes", [V("len-1"), V("len-65"), V("four-interleaved"), V("identity-commitment-mixed")], True, False, one_lane=False),
+           ManyPass("short-holes", [V("len-2"), empty, ManyProblem(tiny("five", 5), "off-subgroup"), V("zero-cells")], True, False, one_lane=False,
+                    kinds=["valid", "empty", "off-subgroup", "valid"], hole_before_live=True),
+           ManyPass("short-one-lane", [V("exponents-to-2^13")], True, False, one_lane=True),
+           ManyPass("large-folded", [V(name) for name in LARGE_ORDER], False, True, n_problems=15, sharing_is_adjacent=True, adjacent_pairs=13,
+                    lonely=[14], hole_before_live=False),
+           ManyPass("large-one-live", [ManyProblem(tiny("three", 3), "bad-scalar"), empty, V("len-63"), ManyProblem(tiny("four", 4), "bad-index"),
+                                       ManyProblem(tiny("six", 6), "off-subgroup")], False, False,
+                    kinds=["bad-scalar", "empty", "valid", "bad-index", "off-subgroup"])]
+    # the search: 300 problems of one to three cells; every problem's first cell is of the blob its predecessor ended on, so that
+    # neighbours share commitment bytes; the wrong ones have two different proofs to exchange
+    probs, prev = [], rng.choice((0, 1, 2))
+    for i in range(300):
+        if i == SEARCH_EMPTY:
+            probs.append(empty)
+            continue
+        n = rng.randrange(2, 4) if i in SEARCH_WRONG else rng.randrange(1, 4)
+        entries = [(prev, rng.randrange(N_CELLS))] + rnd(n - 1)
+        while i in SEARCH_WRONG and entries[0] == entries[-1]:
+            entries[-1] = rnd(1)[0]
+        prev = entries[-1][0]
+        case = CellCase("tiny-%d" % i, entries, n=n)
+        probs.append(ManyProblem(case, "swapped", (0, n - 1)) if i in SEARCH_WRONG else ManyProblem(case, "off-subgroup") if i == SEARCH_REFUSED
+                     else ManyProblem(case))
+    out.append(ManyPass("search", probs, False, True, True, n_problems=300, wrong=SEARCH_WRONG, sharing_is_adjacent=True, adjacent_pairs=290,
+                        lonely=[], hole_before_live=True))
+    out.append(ManyPass("folded-ten", [V("len-1"), V("len-2"), empty, V("len-63"), V("zero-cells"), V("len-64"), V("identity-commitment-mixed"),
+                                       V("len-65"), V("constant-polynomial"), V("four-interleaved")], False, True, n_problems=10,
+                        hole_before_live=True))
+    assert len({p.name for p in out}) == len(out)
     return out
 
 
