@@ -26,6 +26,24 @@ int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const ui
 int eth_kzg_amd_test_prover_scalars(const DASContext *ctx, int n, const uint8_t *blobs, uint32_t *scalars, uint64_t max_words,
                                     uint64_t *n_words, uint8_t *cells, uint8_t *proofs, int32_t *status, int32_t *fused_launches);
 
+/* The prover's G1 stage on its own: from the 128 sums per blob its fixed-base MSMs leave to the 128 proofs' bytes, by the launches
+ * compute_cells_and_kzg_proofs makes behind the MSM (the engine's one statement of them) -- the compiled linear map (k_g1slp.hip) or, for
+ * one or two blobs, the circulant form (k_g1circ.hip), then the compression.  n blobs (lanes), 1 <= n <= 256.  program: -1 = the engine's
+ * own choice for n, 0 .. 5 = that compilation of the linear map at this n (refused with 3 where n takes the circulant form).
+ * sums_words (host): raw words of the device's signed 13 x 30-bit Jacobian points (X, Y, Z: 13 words each), any digit pattern the type
+ * admits.  Linear-map mode: [128][n]; slot j holds what the MSM leaves there, y_j / 2 in natural Fourier order.  Circulant mode:
+ * [128][segs * n], segs = 4 for one or two blobs; lane seg * n + b holds 2^(128 seg / segs) u_j of blob b (u_j = y_j / 128), the scaled
+ * copies the MSM produces from k_fk20_scalars' segment copies.  The padding lanes hold the identity.  out_proofs[n][128][48] (host).
+ * Synchronous; returns 0, or the library's status codes.
+ *
+ * eth_kzg_amd_test_linmap_program: what the context uploaded for compilation `program`: words (4 per operation: dst slot, a slot, b,
+ * flags -- csrc/g1_linmap.hpp: Schedule), launches[i] = (kind, first operation, count), *n_slots, consts[i] = constant i as canonical
+ * big-endian bytes.  The counts come back in *n_words, *n_launches, *n_consts; a buffer that is too small: 3, with the counts set. */
+int eth_kzg_amd_test_proofs_from_sums(const DASContext *ctx, int program, int n, const int32_t *sums_words, uint8_t *out_proofs);
+int eth_kzg_amd_test_linmap_program(const DASContext *ctx, int program, uint32_t *words, uint64_t max_words, uint64_t *n_words,
+                                    int32_t *launches, uint64_t max_launches, uint64_t *n_launches, int32_t *n_slots, uint8_t *consts,
+                                    uint64_t max_consts, uint64_t *n_consts);
+
 /* The many-message SHA-256 kernel (csrc/k_sha256.hip) on its own: n messages, message i = prefix[prefix_len] (HOST memory) |
  * (d_body + i * body_stride)[body_len] | (d_tail + i * tail_stride)[tail_len] (device memory; a part of length 0 may be NULL), digest i
  * -> d_out + 32 i (device).  Synchronous; returns 0 on success. */

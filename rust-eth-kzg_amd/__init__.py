@@ -79,6 +79,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_sha256_many", "eth_kzg_amd_test_verify_msm",
     "eth_kzg_amd_test_verify_cells_partial_device", "eth_kzg_amd_test_verify_blob_batch_inputs", "eth_kzg_amd_test_rs_decode",
     "eth_kzg_amd_test_prover_scalars", "eth_kzg_amd_test_verify_many_sums",
+    "eth_kzg_amd_test_proofs_from_sums", "eth_kzg_amd_test_linmap_program",
 ]
 
 _lib = None
@@ -195,6 +196,8 @@ def load_library():
         "eth_kzg_amd_test_rs_decode": [P, C.c_int, P, P, P, C.c_int, P, P, P, P, P, P],
         "eth_kzg_amd_test_prover_scalars": [P, C.c_int, P, P, U64, P, P, P, P, P],
         "eth_kzg_amd_test_verify_many_sums": [P, U64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, U64, P],
+        "eth_kzg_amd_test_proofs_from_sums": [P, C.c_int, C.c_int, P, P],
+        "eth_kzg_amd_test_linmap_program": [P, C.c_int, P, U64, P, P, U64, P, P, P, U64, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args

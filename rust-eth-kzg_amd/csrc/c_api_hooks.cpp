@@ -37,6 +37,16 @@ int eth_kzg_amd_test_prover_scalars(const DASContext* ctx, int n, const uint8_t*
     if (!blobs || !scalars || !n_words || !cells || !proofs || !status || !fused_launches) return kzg::ERR_INPUT;
     return eng(ctx)->test_prover_scalars(n, blobs, scalars, max_words, n_words, cells, proofs, status, fused_launches);
 }
+int eth_kzg_amd_test_proofs_from_sums(const DASContext* ctx, int program, int n, const int32_t* sums_words, uint8_t* out_proofs) {
+    if (!sums_words || !out_proofs) return kzg::ERR_INPUT;
+    return eng(ctx)->test_proofs_from_sums(program, n, sums_words, out_proofs);
+}
+int eth_kzg_amd_test_linmap_program(const DASContext* ctx, int program, uint32_t* words, uint64_t max_words, uint64_t* n_words, int32_t* launches,
+                                    uint64_t max_launches, uint64_t* n_launches, int32_t* n_slots, uint8_t* consts, uint64_t max_consts,
+                                    uint64_t* n_consts) {
+    if (!words || !n_words || !launches || !n_launches || !n_slots || !consts || !n_consts) return kzg::ERR_INPUT;
+    return eng(ctx)->test_linmap_program(program, words, max_words, n_words, launches, max_launches, n_launches, n_slots, consts, max_consts, n_consts);
+}
 int eth_kzg_amd_test_g1_decompress(const DASContext* ctx, const uint8_t* in, int n, int subgroup_check, int32_t* status,
                                    uint8_t* out) {
     return eng(ctx)->test_g1_decompress(in, n, subgroup_check, status, out);

@@ -492,49 +492,15 @@ void Engine::init_constants() {
 
 // The two G1 transforms of the prover as one straight-line program of point operations (g1_linmap.hpp): built, checked
 // against the definition of the map over Fr (plan and scheduled slot program), constants recoded, uploaded.
-static linmap::Strategy slp_strategy(int id) {
-    linmap::Strategy s;
-    s.allow_toom8 = true;
-    {   // phi = [lambda] with the lambda the constants are GLV-recoded with: the device's beta was picked to match it (init_srs)
-        Fr lam = zero<FrParams>();
-        for (int i = 0; i < 4; i++) lam.v[i] = (uint32_t)(GLV_LAMBDA >> (32 * i));
-        s.lambda = to_mont(lam);
-    }
-    auto fixed = [&](int k4, int k8, int k16, int k32) {
-        s.tuned = false;
-        s.balanced_lincomb = true;
-        s.phi = false;  // the real Toom-Cook points these depth-optimised programs were measured with
-        s.hankel_split = {{2, 2}, {4, k4}, {8, k8}, {16, k16}, {32, k32}};
-    };
-    // (tools/linmap_explore.cpp lists every assignment of splits with its multiplication count and the latency of its cheap
-    // levels; these are points of that Pareto front)
-    switch (id) {
-        case 2: fixed(2, 2, 2, 2); break;  // Karatsuba throughout: 712 multiplications, 13 levels of single additions
-        case 3: fixed(4, 2, 4, 2); break;  // 456 multiplications, 18 levels, at most two doublings in front of an addition
-        case 4: fixed(2, 2, 2, 4); break;  // 606 multiplications, 15 levels
-        case 5: fixed(4, 2, 4, 8); break;  // 372 multiplications, 19 levels (8-way split of the 32-point products only)
-        default: break;                    // tuned by operation count, Toom-Cook points on mu_6: 298 multiplications (16-way splits)
-    }
-    return s;
-}
 void Engine::build_slp_program(int id) {
     const Fr* w128p = reinterpret_cast<const Fr*>(w128_.data());
     const std::vector<Fr> w128(w128p, w128p + 128);
     const bool verbose = knobs_.trace;
-    linmap::Plan plan = linmap::build_fk20_proofs_plan(w128, slp_strategy(id), verbose);
-    {   // the executor leaves output p in arena slot 128 + p, and the proofs are wanted in bit-reversed FFT order
-        std::vector<linmap::Ref> perm(128);
-        for (int p = 0; p < 128; p++) {
-            int k = 0;
-            for (int b = 0; b < 7; b++) k |= ((p >> b) & 1) << (6 - b);
-            perm[p] = plan.outputs[k];
-        }
-        plan.outputs = perm;
-    }
-    // a + b / a - b pairs as ONE operation only in the large-batch schedule: for batches that leave the chip part empty a
-    // step lasts as long as its longest operation, and the fused pair is 15 % longer than an addition (64 blobs: 2.65 against
-    // 2.73 ms for the map; 2048 blobs: 16.15 against 16.0 ms -- fewer, fuller rounds win there)
-    const linmap::Schedule sched = linmap::make_schedule(plan, /*fuse_add_sub=*/id == SLP_TUNED_FUSED);
+    static_assert(SLP_TUNED_FUSED == 0 && SLP_COUNT == linmap::SLP_PROGRAM_COUNT, "g1_linmap_programs.hpp numbers the programs as SlpProgramId does");
+    // the strategy, the order of the outputs and the form of the schedule: g1_linmap_programs.hpp (shared with the tests' host dump)
+    const linmap::SlpCompiled compiled = linmap::compile_slp_program(w128, id, verbose);
+    const linmap::Plan& plan = compiled.plan;
+    const linmap::Schedule& sched = compiled.sched;
     // self-check: definition of the map vs the plan vs the scheduled slot program, over Fr
     uint64_t st = 0x853c49e6748fea9bull + (uint64_t)id;
     for (int it = 0; it < 2; it++) {
@@ -559,6 +525,7 @@ void Engine::build_slp_program(int id) {
         Fr lam = zero<FrParams>();
         for (int i = 0; i < 4; i++) lam.v[i] = (uint32_t)(GLV_LAMBDA >> (32 * i));
         const Fr lm = to_mont(lam);
+        if (!eq(lm, plan.lambda)) throw std::runtime_error("FK20 proofs map: the plan's lambda is not the one its constants are recoded with");
         constexpr int TWW = launch::TWIDDLE_WORDS;
         std::vector<uint32_t> naf(plan.consts.size() * 2 * TWW);
         for (size_t c = 0; c < plan.consts.size(); c++) recode_glv_wnaf(plan.consts[c], lm, &naf[c * 2 * TWW]);
@@ -571,6 +538,9 @@ void Engine::build_slp_program(int id) {
     P.launches.clear();
     for (auto& L : sched.launches) P.launches.push_back(SlpLaunch{(int)L.kind, L.first, L.count});
     P.n_slots = sched.n_slots;
+    P.n_words = sched.words.size();
+    P.consts.resize(plan.consts.size());  // (host copy of what was recoded: the stage hooks hand it out)
+    if (!plan.consts.empty()) memcpy(P.consts.data(), plan.consts.data(), plan.consts.size() * sizeof(Fr8));
     P.info[0] = (int)plan.count(linmap::OP_MULC);
     P.info[1] = (int)(plan.count(linmap::OP_ADD) + plan.count(linmap::OP_SUB));
     P.info[2] = (int)plan.doublings();

@@ -242,6 +242,11 @@ public:
     // enqueue_compute on n blobs (host), then the MSM scalars it left in the work set: segs x n x 8192 x 8 words, as launch_msm reads them
     int test_prover_scalars(int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words, uint8_t* cells, uint8_t* proofs,
                             int32_t* status, int32_t* fused_launches);
+    // the G1 stage alone: prepare_g1_stage / run_g1_stage (engine_prover.hip) around sums the caller gives as raw JacS words
+    int test_proofs_from_sums(int program, int n, const int32_t* sums_words, uint8_t* out_proofs);
+    // what was uploaded for a compilation of the linear map: its words (read back from the device), launches, slots, constants
+    int test_linmap_program(int program, uint32_t* words, uint64_t max_words, uint64_t* n_words, int32_t* launches3, uint64_t max_launches,
+                            uint64_t* n_launches, int32_t* n_slots, uint8_t* consts_be, uint64_t max_consts, uint64_t* n_consts);
     int test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out_recompressed);
     int test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp);
     int test_op(int op, int n, const int32_t* in, int32_t* out);
@@ -398,6 +403,17 @@ private:
                                 int msm_cut = 0);
     void enqueue_compute(Work& w, int n, const uint8_t* d_blobs, uint8_t* d_cells, uint8_t* d_proofs, hipStream_t st,
                          hipEvent_t after_cells);
+    // the G1 stage behind the MSM (engine_prover.hip): its program, lanes and point array; then its launches down to the proof bytes
+    struct SlpProgram;
+    struct G1Stage {
+        int bp = 0, segs = 1;
+        bool linmap_mode = false;
+        const SlpProgram* prog = nullptr;
+        int mulc_coop_lanes = 0;  // > 0: so few blobs that the constant multiplications take several lanes per blob (launch::g1_slp_launch)
+        void* X = nullptr;        // where the MSM leaves its sums: the linear map's arena, or the work set's point array
+    };
+    G1Stage prepare_g1_stage(Work& w, int n, hipStream_t st, int force_program = -1);
+    void run_g1_stage(Work& w, const G1Stage& g, int n, uint8_t* d_proofs, hipStream_t st);
     int fk20_segs(int n) const;  // scaled copies of the scalars the MSM stage of n blobs wants (run_proofs_from_coeffs)
     Work& lease_work(int first, int last);  // locks and returns a free set among work_[first..last] (waits for whichever frees first)
     void release_work(Work& w);
@@ -541,6 +557,8 @@ private:
         void *d_words = nullptr, *d_naf = nullptr;  // d_naf may be shared with another program of the same plan (owns_naf)
         bool owns_naf = false, ready = false;
         int n_slots = 0;
+        size_t n_words = 0;          // words behind d_words (4 per operation)
+        std::vector<Fr8> consts;     // the constants d_naf was recoded from, Montgomery form
         int info[4] = {0, 0, 0, 0};  // constant multiplications, additions, doublings, launches
     };
     SlpProgram slp_prog_[SLP_COUNT];

@@ -5,6 +5,7 @@
 #include "engine.hpp"
 #include "curve.hpp"
 #include "g1_linmap.hpp"
+#include "g1_linmap_programs.hpp"
 #include "hip_check.hpp"
 #include "launch.hpp"
 #include "verify_host.hpp"  // the geometry constants (N_BLOB ... BYTES_PER_CELL)

@@ -173,37 +173,76 @@ void Engine::g1_fft128_full(void* X, int stride, int inverse, hipStream_t st) {
     }
 }
 
-// stages C..G of SURVEY 3.2 from coefficients already in w.coeffs
-// tv_pre: the scalars of all n blobs are in w.scalars already, computed in the form of THIS view (the host-pointer path does it
-// sub-batch by sub-batch under the uploads)
 // one or two blobs: the MSM also delivers 2^32 u, 2^64 u, 2^96 u (scaled copies of the scalars, same tables), which
 // cuts the doubling chain of the circulant form into four parallel quarters (needs 32 * 4 >= T - 1 doublings)
 int Engine::fk20_segs(int n) const { return (n > circ_max_ || circ_T_ > 129) ? 1 : n <= 2 ? 4 : n <= 4 ? 2 : 1; }
-void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream_t st, const TableView* tv_pre, ProofsPhase phase, int msm_cut) {
-    const int bp = ((n + 63) / 64) * 64;
-    const int segs = fk20_segs(n);
-    const Fr8 two_segments[3] = {seg_shift_[1], seg_shift_[1], seg_shift_[1]};  // 2^64
+// The G1 stage of n blobs -- from the MSM's 128 sums per blob to the proof bytes -- in two steps: what it runs and where its points
+// lie (before the MSM, which writes there), then its launches.  The stage hook eth_kzg_amd_test_proofs_from_sums runs the same two
+// functions around sums of its own; force_program >= 0 (that hook only) takes the place of the program picked for the batch.
+Engine::G1Stage Engine::prepare_g1_stage(Work& w, int n, hipStream_t st, int force_program) {
+    G1Stage g;
+    g.bp = ((n + 63) / 64) * 64;
+    g.segs = fk20_segs(n);
     // beyond the small-batch circulant kernel the two transforms run as one compiled linear map (g1_linmap.hpp), which wants
     // the MSM outputs halved instead of divided by 128 and in natural Fourier order in the first 128 arena slots
-    const bool linmap_mode = n > circ_max_;
-    void* X = w.X;
-    const SlpProgram* prog = nullptr;
-    int mulc_coop_lanes = 0;  // > 0: so few blobs that the constant multiplications take several lanes per blob (launch::g1_slp_launch)
-    if (linmap_mode) {
+    g.linmap_mode = n > circ_max_;
+    g.X = w.X;
+    if (g.linmap_mode) {
+        const int bp = g.bp;
         int which = pick_slp_program(bp);
         // 33 .. 64 blobs: the constant multiplications run with two lanes per blob = two waves per operation (k_g1slp.hip), so the
         // compilation with 456 of them (912 waves, one per SIMD) replaces the one with 712 that a lane per blob takes
         if (slp_force_ < 0 && bp == 64 && n > 32 && launch::coop_points_max() > 0) which = SLP_DEPTH_456;
-        mulc_coop_lanes = n <= 32 ? n : (bp == 64 && which == SLP_DEPTH_456) ? n : 0;
-        prog = &slp_program(which);
-        const size_t need = (size_t)prog->n_slots * bp * launch::SIZEOF_JACS;
+        if (force_program >= 0) which = force_program;
+        g.mulc_coop_lanes = n <= 32 ? n : (bp == 64 && which == SLP_DEPTH_456) ? n : 0;
+        g.prog = &slp_program(which);
+        const size_t need = (size_t)g.prog->n_slots * bp * launch::SIZEOF_JACS;
         if (need > w.slp_arena_bytes) {
             if (w.slp_arena) { HIPCK(hipStreamSynchronize(st)); HIPCK(hipFree(w.slp_arena)); w.slp_arena = nullptr; w.slp_arena_bytes = 0; }
             HIPCK(hipMalloc(&w.slp_arena, need));
             w.slp_arena_bytes = need;
         }
-        X = w.slp_arena;
+        g.X = w.slp_arena;
     }
+    return g;
+}
+void Engine::run_g1_stage(Work& w, const G1Stage& g, int n, uint8_t* d_proofs, hipStream_t st) {
+    constexpr int fmt = launch::FMT_JACS;
+    constexpr size_t pt = launch::SIZEOF_JACS;
+    const int bp = g.bp;
+    if (g.linmap_mode) {
+        const SlpProgram* prog = g.prog;
+        const int mk3 = mark_begin(ST_G1_LINMAP, st);
+        int n_launches = 0;
+        for (auto& L : prog->launches)
+            launch::g1_slp_launch(L.kind, w.slp_arena, bp, (const uint32_t*)prog->d_words + (size_t)L.first * 4, L.count, prog->d_naf, beta_, st, 0,
+                                  g.mulc_coop_lanes, n);
+        n_launches = (int)prog->launches.size();
+        mark_end(mk3, n_launches, st);
+        const int mk4 = mark_begin(ST_COMPRESS, st);
+        launch::g1_compress((const char*)w.slp_arena + (size_t)128 * bp * pt, d_proofs, 128, bp, n, st, fmt);
+        mark_end(mk4, 1, st);
+        return;
+    }
+    if (n <= circ_max_) {  // a handful of blobs: the two transforms as one circulant product (k_g1circ.hip)
+        if (!w.circ_table) HIPCK(hipMalloc(&w.circ_table, launch::g1_circ_table_bytes(circ_max_, circ_T_)));
+        const int mk5 = mark_begin(ST_G1_IFFT, st);
+        launch::g1_circ128(w.X, bp, n, g.segs, w.circ_table, circ_T_, d_circ_terms_, circ_per_lane_, beta_, st);
+        mark_end(mk5, 2, st);
+    } else throw std::logic_error("run_proofs_from_coeffs: a batch above the circulant form needs the compiled linear map");
+    const int mk10 = mark_begin(ST_COMPRESS, st);
+    launch::g1_compress(w.X, d_proofs, 128, bp, n, st, fmt);
+    mark_end(mk10, 1, st);
+}
+// stages C..G of SURVEY 3.2 from coefficients already in w.coeffs
+// tv_pre: the scalars of all n blobs are in w.scalars already, computed in the form of THIS view (the host-pointer path does it
+// sub-batch by sub-batch under the uploads)
+void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream_t st, const TableView* tv_pre, ProofsPhase phase, int msm_cut) {
+    const G1Stage g1 = prepare_g1_stage(w, n, st);
+    const int bp = g1.bp, segs = g1.segs;
+    const Fr8 two_segments[3] = {seg_shift_[1], seg_shift_[1], seg_shift_[1]};  // 2^64
+    const bool linmap_mode = g1.linmap_mode;
+    void* X = g1.X;
     // The arena's point format: every kernel between the scalars and the proofs' bytes -- MSM, constant multiplications, additions,
     // compression; a lane, two or four lanes per blob -- is a kernel of the signed 13 x 30-bit field, and the arena holds its points
     // (JacS, 156 B) as they are: ONE Fp representation under the whole path at every batch size, no conversions.
@@ -233,28 +272,7 @@ void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream
     const int mk2 = mark_begin(ST_MSM_FIXED, st);
     if (phase == PROOFS_ALL) launch_msm(w.scalars, tv, true, X, 128, segs * n, bp, 0, st, fmt);
     mark_end(mk2, 1, st);
-    if (linmap_mode) {
-        const int mk3 = mark_begin(ST_G1_LINMAP, st);
-        int n_launches = 0;
-        for (auto& L : prog->launches)
-            launch::g1_slp_launch(L.kind, w.slp_arena, bp, (const uint32_t*)prog->d_words + (size_t)L.first * 4, L.count, prog->d_naf, beta_, st, 0,
-                                  mulc_coop_lanes, n);
-        n_launches = (int)prog->launches.size();
-        mark_end(mk3, n_launches, st);
-        const int mk4 = mark_begin(ST_COMPRESS, st);
-        launch::g1_compress((const char*)w.slp_arena + (size_t)128 * bp * pt, d_proofs, 128, bp, n, st, fmt);
-        mark_end(mk4, 1, st);
-        return;
-    }
-    if (n <= circ_max_) {  // a handful of blobs: the two transforms as one circulant product (k_g1circ.hip)
-        if (!w.circ_table) HIPCK(hipMalloc(&w.circ_table, launch::g1_circ_table_bytes(circ_max_, circ_T_)));
-        const int mk5 = mark_begin(ST_G1_IFFT, st);
-        launch::g1_circ128(w.X, bp, n, segs, w.circ_table, circ_T_, d_circ_terms_, circ_per_lane_, beta_, st);
-        mark_end(mk5, 2, st);
-    } else throw std::logic_error("run_proofs_from_coeffs: a batch above the circulant form needs the compiled linear map");
-    const int mk10 = mark_begin(ST_COMPRESS, st);
-    launch::g1_compress(w.X, d_proofs, 128, bp, n, st, fmt);
-    mark_end(mk10, 1, st);
+    run_g1_stage(w, g1, n, d_proofs, st);
 }
 
 // the kernels of one prover call on `st`, scratch from `w`; optionally records `after_cells` once the cells are written

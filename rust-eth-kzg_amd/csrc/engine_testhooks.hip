@@ -154,6 +154,75 @@ int Engine::test_prover_scalars(int n, const uint8_t* blobs, uint32_t* scalars, 
     return OK;
 }
 
+// The G1 stage of the prover on sums of the caller's: the words go where the MSM would have left them (stride bp, the identity in the
+// padding lanes, as g1_set_inf leaves them in front of the MSM), then run_g1_stage -- the launches run_proofs_from_coeffs makes.
+// sums_words: [128][lanes][39], lanes = n in linear-map mode, fk20_segs(n) * n (lane seg * n + b) in the circulant mode.
+int Engine::test_proofs_from_sums(int program, int n, const int32_t* sums_words, uint8_t* out_proofs) {
+    if (n < 1 || n > 256 || program < -1 || program >= SLP_COUNT) return ERR_INPUT;
+    if (program >= 0 && n <= circ_max_) return ERR_INPUT;  // the circulant form runs no program
+    struct DevBuf {  // (freed on every way out)
+        void* p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } d_proofs;
+    Work* held = nullptr;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        Work& w = lease_work(1, NW - 1);
+        held = &w;
+        hipStream_t st = w.stream;
+        ensure_workspace(w, n);
+        HIPCK(hipStreamWaitEvent(st, w.done, 0));
+        HIPCK(hipMalloc(&d_proofs.p, (size_t)n * N_CELLS * 48));
+        const G1Stage g = prepare_g1_stage(w, n, st, program);
+        constexpr size_t pt = launch::SIZEOF_JACS;
+        static_assert(pt == 39 * sizeof(int32_t), "the hook's callers give 39 words per point");
+        const size_t lanes = (size_t)(g.linmap_mode ? 1 : g.segs) * n;
+        if (lanes > (size_t)g.bp) throw std::logic_error("test_proofs_from_sums: more lanes than the stride holds");
+        launch::g1_set_inf(g.X, (size_t)128 * g.bp, st, launch::FMT_JACS);
+        HIPCK(hipMemcpy2DAsync(g.X, (size_t)g.bp * pt, sums_words, lanes * pt, lanes * pt, 128, hipMemcpyHostToDevice, st));
+        run_g1_stage(w, g, n, (uint8_t*)d_proofs.p, st);
+        HIPCK(hipEventRecord(w.done, st));
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(st));
+        HIPCK(hipMemcpy(out_proofs, d_proofs.p, (size_t)n * N_CELLS * 48, hipMemcpyDeviceToHost));
+        release_work(w);
+        held = nullptr;
+    } catch (const std::exception& e) {
+        if (held) { (void)hipStreamSynchronize(held->stream); (void)hipStreamSynchronize(held->copy); release_work(*held); }
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+static void fr_mont_to_be(uint8_t* out, const uint32_t* mont);
+// What the engine uploaded for compilation `program` of the linear map: the words as the device holds them, the launches as (kind,
+// first, count), the arena's slot count, the constants (canonical big-endian) the recoded digits were made from.
+int Engine::test_linmap_program(int program, uint32_t* words, uint64_t max_words, uint64_t* n_words, int32_t* launches3, uint64_t max_launches,
+                                uint64_t* n_launches, int32_t* n_slots, uint8_t* consts_be, uint64_t max_consts, uint64_t* n_consts) {
+    if (program < 0 || program >= SLP_COUNT) return ERR_INPUT;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        const SlpProgram& P = slp_program(program);
+        *n_words = P.n_words;
+        *n_launches = P.launches.size();
+        *n_consts = P.consts.size();
+        *n_slots = P.n_slots;
+        if (P.n_words > max_words || P.launches.size() > max_launches || P.consts.size() > max_consts) return ERR_INPUT;
+        HIPCK(hipMemcpy(words, P.d_words, P.n_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < P.launches.size(); i++) {
+            launches3[3 * i] = P.launches[i].kind;
+            launches3[3 * i + 1] = P.launches[i].first;
+            launches3[3 * i + 2] = P.launches[i].count;
+        }
+        for (size_t i = 0; i < P.consts.size(); i++) fr_mont_to_be(consts_be + 32 * i, P.consts[i].v);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 int Engine::test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out) {
     std::lock_guard<std::recursive_mutex> lk(mu_);
     try {

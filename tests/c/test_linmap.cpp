@@ -90,7 +90,7 @@ int main() {
             }
         }
     }
-    // the depth-optimised compilations the engine uses for batches that do not fill the chip (engine.hip: slp_strategy): fixed
+    // the depth-optimised compilations the engine uses for batches that do not fill the chip (g1_linmap_programs.hpp: slp_strategy): fixed
     // splits per size, small-integer sums as balanced trees.  Each against the definition, as a plan and as its slot program.
     const int fixed_splits[][4] = {{2, 2, 2, 2}, {4, 2, 4, 2}, {2, 2, 2, 4}, {4, 2, 4, 8}, {4, 4, 4, 4}, {4, 8, 8, 8}};
     for (auto& f : fixed_splits) {

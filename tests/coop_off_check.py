@@ -1,6 +1,7 @@
 """Run by tests/test_gpu_parity.py in a process of its own with ETH_KZG_AMD_COOP_POINTS=0 (the limit is read once per process):
 the one-lane-per-point forms of the verification kernels -- which small inputs no longer reach by default -- on the
-single path, a small many-verification pass and the EIP-4844 verifier, valid and tampered."""
+single path, a small many-verification pass and the EIP-4844 verifier, valid and tampered; and the prover's G1 stage with a lane per
+blob where twelve blobs would take four (eth_kzg_amd_test_proofs_from_sums on the planned degenerate lanes of tests/linmap_model.py)."""
 import importlib, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,6 +47,11 @@ def main():
     proof, y = ctx.compute_kzg_proof(blobs[0], z)
     assert ctx.verify_kzg_proof(comms[0], z, y, proof) is True
     assert ctx.verify_kzg_proof(comms[1], z, y, proof) is False
+    # the linear map's one-lane-per-blob kernels on twelve lanes (k_slp_mulc_s, k_slp_add_s: with the quad kernels on, twelve blobs
+    # never reach them): program 2 on its planned degenerate, generic and all-identity lanes, byte for byte against the definition
+    import g1_stage_cases
+    for k, (batch, vectors) in enumerate(g1_stage_cases.linmap_batches(2, 12)):
+        g1_stage_cases.check_linmap_batch(kzg.load_library(), ctx.handle, 2, 2, 12, batch, vectors, seed=1000 * 2 + 10 * 12 + k)
     ctx.close()
     print("coop-off ok")
 
