@@ -16,6 +16,18 @@ int eth_kzg_amd_test_g1_decompress(const DASContext *ctx, const uint8_t *in, int
 int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const uint8_t *b, uint8_t *out, int n,
                                int is_fp);
 
+/* One stated schedule of the fixed-base MSM (csrc/k_msm_glv.inc) on either window table.  table_kind: 0 = the FK20 table (128 groups of 64
+ * bases), 1 = the commitment table (64 groups; the output is then the 64 group sums of a slice, before the commitment's fold).  mode: -1 =
+ * what the engine picks for n_slices (launch_msm_range; its two-launch overflow form included), 0 = a block per MSM (flat), 1 = a lane per
+ * window, 3 = two lanes per window, 2 = four chunks per MSM.  scalar_form: 0 = canonical big-endian scalars (32 B), split on the device as
+ * eth_kzg_amd_test_fixed_msm splits them; 1 = the two balanced GLV halves themselves, 8 little-endian 32-bit words per scalar: |k1| in words
+ * 0 .. 3, |k2| in words 4 .. 7, each below 2^127 with its sign in bit 127 -- word for word what the prover's Fr kernels leave
+ * (eth_kzg_amd_test_prover_scalars), read through the overload the prover calls.  scalars[n_slices][groups][64] (host, 1 <= n_slices <= 4096),
+ * out[n_slices][groups][48] (host).  modes[5]: modes[0] = launches made, modes[1 ..] = the mode of each (-1 behind the last).  Always the
+ * context's complete table.  Synchronous; returns 0, or the library's status codes. */
+int eth_kzg_amd_test_fixed_msm_ex(const DASContext *ctx, int table_kind, int mode, int scalar_form, const uint8_t *scalars, int n_slices,
+                                  uint8_t *out, int32_t *modes);
+
 /* The scalars the prover hands to its fixed-base MSMs.  compute_cells_and_kzg_proofs' own schedule on n blobs (host, 1 <= n <= 4096,
  * both outputs asked for), then what it left for eth_kzg_amd_test_fixed_msm's stage, word for word: scalars[seg][blob][j < 128][i < 64][8]
  * little-endian words, each scalar as its two balanced GLV halves (sign in bit 127 of a half); seg < 4 for one or two blobs, < 2 for

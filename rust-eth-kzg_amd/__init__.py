@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = [
 ]
 # include/c_eth_kzg_test_hooks.h: stage-level hooks for tests/, not part of the drop-in ABI
 TEST_HOOK_SYMBOLS = [
-    "eth_kzg_amd_test_fr_ntt4096", "eth_kzg_amd_test_g1_fft128", "eth_kzg_amd_test_fixed_msm",
+    "eth_kzg_amd_test_fr_ntt4096", "eth_kzg_amd_test_g1_fft128", "eth_kzg_amd_test_fixed_msm", "eth_kzg_amd_test_fixed_msm_ex",
     "eth_kzg_amd_test_g1_decompress", "eth_kzg_amd_test_field_mul", "eth_kzg_amd_test_op_info", "eth_kzg_amd_test_op",
     "eth_kzg_amd_test_table_info", "eth_kzg_amd_test_table_audit", "eth_kzg_amd_test_table_read", "eth_kzg_amd_test_table_audit_buffer",
     "eth_kzg_amd_test_sha256_many", "eth_kzg_amd_test_verify_msm",
@@ -181,6 +181,7 @@ def load_library():
         "eth_kzg_amd_test_fr_ntt4096": [P, U8P, P, C.c_int],
         "eth_kzg_amd_test_g1_fft128": [P, U8P, P, C.c_int, C.c_int],
         "eth_kzg_amd_test_fixed_msm": [P, U8P, C.c_int, P],
+        "eth_kzg_amd_test_fixed_msm_ex": [P, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P],
         "eth_kzg_amd_test_g1_decompress": [P, U8P, C.c_int, C.c_int, P, P],
         "eth_kzg_amd_test_field_mul": [P, U8P, U8P, P, C.c_int, C.c_int],
         "eth_kzg_amd_test_op_info": [C.c_int, P, P, P, C.POINTER(C.c_char_p)],

@@ -32,6 +32,11 @@ int eth_kzg_amd_test_g1_fft128(const DASContext* ctx, const uint8_t* in, uint8_t
 int eth_kzg_amd_test_fixed_msm(const DASContext* ctx, const uint8_t* scalars, int n_msm, uint8_t* out) {
     return eng(ctx)->test_fixed_msm(scalars, n_msm, out);
 }
+int eth_kzg_amd_test_fixed_msm_ex(const DASContext* ctx, int table_kind, int mode, int scalar_form, const uint8_t* scalars, int n_slices,
+                                  uint8_t* out, int32_t* modes) {
+    if (!scalars || !out || !modes) return kzg::ERR_INPUT;
+    return eng(ctx)->test_fixed_msm_ex(table_kind, mode, scalar_form, scalars, n_slices, out, modes);
+}
 int eth_kzg_amd_test_prover_scalars(const DASContext* ctx, int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words,
                                     uint8_t* cells, uint8_t* proofs, int32_t* status, int32_t* fused_launches) {
     if (!blobs || !scalars || !n_words || !cells || !proofs || !status || !fused_launches) return kzg::ERR_INPUT;

@@ -239,6 +239,8 @@ public:
     int test_fr_ntt4096(const uint8_t* in_be, uint8_t* out_be, int inverse_dit);
     int test_g1_fft128(const uint8_t* in_compressed, uint8_t* out_compressed, int n_lanes, int inverse);
     int test_fixed_msm(const uint8_t* scalars_be, int n_msm, uint8_t* out_compressed);
+    // one stated schedule of the fixed-base MSM on either window table (engine_testhooks.hip); modes5: the launches made, then their modes
+    int test_fixed_msm_ex(int table_kind, int mode, int scalar_form, const uint8_t* scalars, int n_slices, uint8_t* out_compressed, int32_t* modes5);
     // enqueue_compute on n blobs (host), then the MSM scalars it left in the work set: segs x n x 8192 x 8 words, as launch_msm reads them
     int test_prover_scalars(int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words, uint8_t* cells, uint8_t* proofs,
                             int32_t* status, int32_t* fused_launches);
@@ -422,10 +424,13 @@ private:
     void set_error(const std::exception& e);
     void launch_msm(const void* scalars, TableSel table, void* out, int n_groups, int n_slices, int out_stride,
                     int brp_bits, hipStream_t st, int out_fmt /* launch::FMT_* */);
+    // the stage hook's tap: force >= 0 takes the place of the mode launch_msm_range picks (and of its two-launch overflow form);
+    // modes[0 .. n): the mode of every launch::msm_glv call made, in order
+    struct MsmTap { int force = -1; int n = 0; int modes[4] = {0, 0, 0, 0}; };
     void launch_msm(const void* scalars, const TableView& tv, bool scalars_split, void* out, int n_groups, int n_slices, int out_stride,
-                    int brp_bits, hipStream_t st, int out_fmt /* launch::FMT_* */);
+                    int brp_bits, hipStream_t st, int out_fmt /* launch::FMT_* */, MsmTap* tap = nullptr);
     void launch_msm_range(const void* scalars, const SharedTable& t, int g0, int gcnt, void* out, int n_groups, int n_slices, int out_stride,
-                          int brp_bits, hipStream_t st, int out_fmt);
+                          int brp_bits, hipStream_t st, int out_fmt, MsmTap* tap = nullptr);
     long msm_waves(long msms, int c) const;  // waves of the MSM launch launch_msm_range would issue (the side-stream decision of enqueue_compute)
     void build_final_tables();  // the wide tables: on the helper thread (progressive start) or inline
     void publish(TableSel which, const std::shared_ptr<SharedTable>& main, const std::shared_ptr<SharedTable>& next);

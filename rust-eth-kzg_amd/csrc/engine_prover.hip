@@ -111,14 +111,14 @@ void Engine::launch_msm(const void* scalars, TableSel which, void* out, int n_gr
 // has stored the scalars as balanced GLV halves already (only meaningful for a GLV table).  While a wider table is under
 // construction its leading ready groups run on it and the rest on the complete table: two launches, one MSM stage.
 void Engine::launch_msm(const void* scalars, const TableView& tv, bool scalars_split, void* out, int n_groups, int n_slices,
-                        int out_stride, int brp_bits, hipStream_t st, int out_fmt) {
+                        int out_stride, int brp_bits, hipStream_t st, int out_fmt, MsmTap* tap) {
     const SharedTable* main = tv.main.get();
     const SharedTable* next = tv.next.get();
     int ready = 0;
     if (next) ready = std::min(n_groups, next->ready_groups.load(std::memory_order_acquire));
     if (!scalars_split) launch::glv_split(const_cast<void*>(scalars), (size_t)n_groups * n_slices * 64, st);  // in place: they feed nothing else
-    if (ready > 0) launch_msm_range(scalars, *next, 0, ready, out, n_groups, n_slices, out_stride, brp_bits, st, out_fmt);
-    if (ready < n_groups) launch_msm_range(scalars, *main, ready, n_groups - ready, out, n_groups, n_slices, out_stride, brp_bits, st, out_fmt);
+    if (ready > 0) launch_msm_range(scalars, *next, 0, ready, out, n_groups, n_slices, out_stride, brp_bits, st, out_fmt, tap);
+    if (ready < n_groups) launch_msm_range(scalars, *main, ready, n_groups - ready, out, n_groups, n_slices, out_stride, brp_bits, st, out_fmt, tap);
 }
 // waves of the MSM launch over `msms` MSMs on a table of nominal width c, as launch_msm_range will schedule it (flat launches aside)
 long Engine::msm_waves(long msms, int c) const {
@@ -129,12 +129,15 @@ long Engine::msm_waves(long msms, int c) const {
 }
 // groups [g0, g0 + gcnt) of every slice on table t
 void Engine::launch_msm_range(const void* scalars, const SharedTable& t, int g0, int gcnt, void* out, int n_groups, int n_slices,
-                              int out_stride, int brp_bits, hipStream_t st, int out_fmt) {
+                              int out_stride, int brp_bits, hipStream_t st, int out_fmt, MsmTap* tap) {
     const launch::TabBlocks tb{(const void* const*)t.d_blocks, g0, gcnt};
     const int c = t.c;
     const long msms = (long)gcnt * n_slices;
+    const bool forced = tap && tap->force >= 0;  // (the stage hook eth_kzg_amd_test_fixed_msm_ex only)
+    auto note = [&](int m) { if (tap && tap->n < 4) tap->modes[tap->n++] = m; };
     int mode = 1;  // a lane per (MSM, window)
-    if (n_slices <= FLAT_MSM_MAX_SLICES && circ_max_ > 0) mode = 0;  // a handful of blobs: one block per MSM
+    if (forced) mode = tap->force;
+    else if (n_slices <= FLAT_MSM_MAX_SLICES && circ_max_ > 0) mode = 0;  // a handful of blobs: one block per MSM
     else if (msm_chunks_ >= 0) mode = msm_chunks_ == 0 ? 1 : 2;  // tests: 0 = the windowed kernel, anything else = four chunks per MSM
     else if (msm_split_ && (msms * 4 * launch::glv_windows(c) + 63) / 64 <= (long)wave_slots_ / 2) mode = 3;  // <= 16 blobs on eight windows: two lanes per window while that still leaves a SIMD per wave -- the chain of dependent additions is halved (16 blobs: 0.70 -> 0.49 ms; with two waves per SIMD, 17 .. 32 blobs, it was measured 0.05 ms SLOWER)
     else if ((msms * 4 + 63) / 64 >= (long)wave_slots_) {
@@ -142,7 +145,7 @@ void Engine::launch_msm_range(const void* scalars, const SharedTable& t, int g0,
         // half -- no folds, no barriers, exact rounds of long waves -- were measured 1-2 % SLOWER in rounds 3 and 4 and are gone.)
         mode = 2;
     }
-    if (mode == 1 && msm_chunks_ < 0 && msm_split_) {
+    if (mode == 1 && msm_chunks_ < 0 && msm_split_ && !forced) {
         // A lane per window fills one round of wave slots with 64 blobs on eight windows -- and with 56 on nine (the default tables):
         // the blobs beyond that used to open a second round of full-length waves on a nearly empty chip (64 blobs on the default
         // tables: MSM 1.66 ms against 1.13 on eight windows).  An overflow of at most a quarter round runs as its own launch: a block per
@@ -153,12 +156,15 @@ void Engine::launch_msm_range(const void* scalars, const SharedTable& t, int g0,
         if (lanes > slots && lanes * 4 <= slots * 5 && n_a >= 1 && n_a < n_slices) {
             const size_t pt = out_fmt == launch::FMT_JACS ? launch::SIZEOF_JACS : launch::SIZEOF_JACQ;
             launch::msm_glv(c, 1, scalars, tb, out, n_groups, n_a, 64, out_stride, brp_bits, beta_, st, out_fmt);
-            const int n_b = n_slices - n_a;
-            launch::msm_glv(c, (n_b <= FLAT_MSM_MAX_SLICES && circ_max_ > 0) ? 0 : 3, (const char*)scalars + (size_t)n_a * n_groups * 64 * sizeof(Fr), tb,
+            const int n_b = n_slices - n_a, mode_b = (n_b <= FLAT_MSM_MAX_SLICES && circ_max_ > 0) ? 0 : 3;
+            note(1);
+            note(mode_b);
+            launch::msm_glv(c, mode_b, (const char*)scalars + (size_t)n_a * n_groups * 64 * sizeof(Fr), tb,
                             (char*)out + (size_t)n_a * pt, n_groups, n_b, 64, out_stride, brp_bits, beta_, st, out_fmt);
             return;
         }
     }
+    note(mode);
     launch::msm_glv(c, mode, scalars, tb, out, n_groups, n_slices, 64, out_stride, brp_bits, beta_, st, out_fmt);
 }
 

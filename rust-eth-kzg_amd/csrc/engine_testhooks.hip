@@ -113,6 +113,56 @@ int Engine::test_fixed_msm(const uint8_t* scalars_be, int n_msm, uint8_t* out) {
     return OK;
 }
 
+// One stated schedule of the fixed-base MSM.  table_kind: TAB_FK (128 groups) or TAB_SRS (64 groups: the group sums of a commitment, before its
+// fold).  mode: -1 = what launch_msm_range picks for n_slices (its two-launch overflow form included), else the mode handed to launch::msm_glv
+// (0 flat, 1 a lane per window, 3 two lanes per window, 2 four chunks).  scalar_form 0: canonical big-endian scalars, split by
+// launch::glv_split; 1: the balanced halves themselves, 8 little-endian words per scalar (|k1|, |k2|, the sign in bit 127 of a half) as the
+// prover's Fr kernels leave them -- launch_msm's scalars_split overload, which the prover calls.  scalars [n_slices][groups][64] ->
+// out [n_slices][groups][48]; modes5[0] = launches made, modes5[1 ..] their modes.  The complete table only (a wider one still being built is
+// left alone: one table per call).
+int Engine::test_fixed_msm_ex(int table_kind, int mode, int scalar_form, const uint8_t* scalars, int n_slices, uint8_t* out, int32_t* modes5) {
+    if ((table_kind != TAB_FK && table_kind != TAB_SRS) || mode < -1 || mode > 3 || (scalar_form != 0 && scalar_form != 1) || n_slices < 1 || n_slices > 4096)
+        return ERR_INPUT;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    struct DevBuf {  // (freed on every way out)
+        void* p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } d_in, d_sc, d_X, d_out;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        TableView tv = table_view((TableSel)table_kind);
+        if (!tv.main) return ERR_INPUT;
+        tv.next.reset();
+        const int n_groups = tv.main->n_groups, stride = ((n_slices + 63) / 64) * 64;
+        const size_t ns = (size_t)n_slices * n_groups * 64;
+        HIPCK(hipMalloc(&d_sc.p, ns * sizeof(Fr)));
+        HIPCK(hipMalloc(&d_X.p, (size_t)n_groups * stride * launch::SIZEOF_JACQ));
+        HIPCK(hipMalloc(&d_out.p, (size_t)n_slices * n_groups * 48));
+        if (scalar_form == 0) {
+            HIPCK(hipMalloc(&d_in.p, ns * 32));
+            HIPCK(hipMemcpy(d_in.p, scalars, ns * 32, hipMemcpyHostToDevice));
+            launch::test_scalars_be((const uint8_t*)d_in.p, d_sc.p, ns, stream_);
+        } else {
+            static_assert(sizeof(Fr) == 32, "a split scalar takes the place of the scalar");
+            HIPCK(hipMemcpy(d_sc.p, scalars, ns * sizeof(Fr), hipMemcpyHostToDevice));
+        }
+        MsmTap tap;
+        tap.force = mode;
+        launch::g1_set_inf(d_X.p, (size_t)n_groups * stride, stream_, launch::FMT_JACQ);
+        launch_msm(d_sc.p, tv, scalar_form == 1, d_X.p, n_groups, n_slices, stride, 0, stream_, launch::FMT_JACQ, &tap);
+        launch::g1_compress(d_X.p, (uint8_t*)d_out.p, n_groups, stride, n_slices, stream_, launch::FMT_JACQ);
+        HIPCK(hipGetLastError());
+        HIPCK(hipStreamSynchronize(stream_));
+        HIPCK(hipMemcpy(out, d_out.p, (size_t)n_slices * n_groups * 48, hipMemcpyDeviceToHost));
+        modes5[0] = tap.n;
+        for (int i = 0; i < 4; i++) modes5[1 + i] = i < tap.n ? tap.modes[i] : -1;
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 // The prover's own schedule (enqueue_compute, both outputs asked for) on n blobs, then the MSM scalars it left in the work set, word for
 // word: which kernels wrote them is the context's ETH_KZG_AMD_FUSED_SCALARS; *fused_launches = launches of k_coeffs_to_cells_scalars.
 int Engine::test_prover_scalars(int n, const uint8_t* blobs, uint32_t* scalars, uint64_t max_words, uint64_t* n_words, uint8_t* cells,

@@ -63,12 +63,10 @@ def _windows(w):
     return out
 
 
-def _msm_stage_check(ctx, tag):
-    """128 fixed-base MSM_64 per scalar set through the stage hook against oracle_g1_msm (edge scalars included)."""
-    lib = kzg.load_library()
-    n_msm = 9
+def _stage_scalars(w, n_msm=9):
+    """n_msm sets of 128 x 64 scalars for the MSM stage on a table of nominal width w: seeded ones, the recoding's edges in the first
+    192 places of set 0, zeros in set 1."""
     sc = [synth.seeded_scalars(128 * 64, b"tab%d" % m) for m in range(n_msm)]
-    w = ctx.window_bits()
     lam = 0xac45a4010001a40200000000ffffffff
     edge = [0, 1, synth.R - 1, 1 << (w - 1), (1 << (w - 1)) + 1, (1 << w) - 1, (1 << 254), (1 << (w * 3)) - (1 << (w - 1)),
             lam, lam - 1, lam + 1, (lam - 1) // 2, (lam + 1) // 2, (lam + 1) // 2 + 1, lam * ((lam + 1) // 2), synth.R - lam,
@@ -100,6 +98,14 @@ def _msm_stage_check(ctx, tag):
     for k, v in enumerate(edge):
         sc[0][k] = (v % synth.R).to_bytes(32, "big")
     sc[1] = [bytes(32)] * (128 * 64)
+    return sc
+
+
+def _msm_stage_check(ctx, tag):
+    """128 fixed-base MSM_64 per scalar set through the stage hook against oracle_g1_msm (edge scalars included)."""
+    lib = kzg.load_library()
+    n_msm = 9
+    sc = _stage_scalars(ctx.window_bits(), n_msm)
     flat = b"".join(b"".join(s) for s in sc)
     out = C.create_string_buffer(n_msm * 128 * 48)
     assert lib.eth_kzg_amd_test_fixed_msm(ctx.handle, flat, n_msm, out) == 0
