@@ -328,6 +328,40 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device(const DASContext *ctx, ui
                                                        const uint64_t *d_cell_indices, const uint8_t *d_cells,
                                                        const uint8_t *d_proofs, bool *verified, void *hip_stream);
 
+/* ---- cell verification with a leaf-hashed challenge ----
+ * The reference's Fiat-Shamir transcript is ONE SHA-256 over every byte of the batch: serial by construction, and for a large batch
+ * the time of the whole call is the time of that hash on one host core (8192 cells: 17.6 MB).  Only the verdict crosses this ABI --
+ * the challenge r never does -- so the two calls below take, when asked to, a challenge that binds the same bytes through a
+ * two-level hash whose first level runs on the GPU, one lane per cell (csrc/k_sha256.hip):
+ *   LEAF_k = SHA-256("RCKZGCBATCHLEAF1" | be64(k) | be64(cell_indices[k]) | commitments[k] | proofs[k] | cells[k])
+ *   ROOT   = SHA-256("RCKZGCBATCHROOT1" | be64(4096) | be64(64) | be64(n) | LEAF_0 | .. | LEAF_{n-1})
+ *   r      = ROOT as a 256-bit big-endian integer mod r
+ * (k: the position in the caller's list; commitments[k]: the caller's 48 bytes of entry k, not de-duplicated.)
+ * Soundness: r is a hash of every input byte -- the leaves bind the contents, the root binds their order, and the argument rests on
+ * the collision resistance of SHA-256.  The batch equation is the reference's: a batch that holds a wrong proof passes only if r is
+ * a root of a non-zero polynomial of degree below n over Fr.  Valid batches verify under any r, and whether a call is Err or
+ * Ok(false) does not depend on r: validation, the order in which errors are reported (commitments, proofs, cells) and the
+ * pairing check are those of the unflagged calls.
+ *   flags = 0                                    exactly eth_kzg_verify_cell_kzg_proof_batch / eth_kzg_amd_verify_cell_kzg_proof_batch_device
+ *   flags = ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT   the challenge above.  In the device-resident form neither cells nor proofs are
+ *                                                copied to the host: the commitments and the indices come down (validation and
+ *                                                de-duplication), and the n * 32 digest bytes
+ *   any other bit                                Err("InvalidInput..."), returned with the count checks, before the context is touched
+ * On a device-list context the host form routes like any single-problem call, the device form by the owner of the pointers.
+ * Not covered: eth_kzg_amd_verify_cell_kzg_proof_batch_partial / _combine, _many and the combining of concurrent calls of
+ * eth_kzg_verify_cell_kzg_proof_batch keep the reference's transcript; no environment setting moves the reference's own symbol
+ * onto this challenge.  When the flag pays: INTEGRATION.md. */
+#define ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT 1u
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_ex(const DASContext *ctx, uint64_t commitments_length,
+                                                   const uint8_t *const *commitments, uint64_t cell_indices_length,
+                                                   const uint64_t *cell_indices, uint64_t cells_length,
+                                                   const uint8_t *const *cells, uint64_t proofs_length,
+                                                   const uint8_t *const *proofs, uint32_t flags, bool *verified);
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(const DASContext *ctx, uint64_t n, const uint8_t *d_commitments,
+                                                          const uint64_t *d_cell_indices, const uint8_t *d_cells,
+                                                          const uint8_t *d_proofs, uint32_t flags, bool *verified,
+                                                          void *hip_stream);
+
 /* Introspection used by bench.py / DESIGN.md: bytes of both window tables resident in HBM; nominal window width w of the FK20
  * table in use (a GLV table: ceil(128 / w) windows over the two 128-bit halves of each scalar, packed 96-byte entries: 16
  * gathered additions per base at w = 16, 32 at w = 8 -- the start tables, and all there is with use_precomp = false). */

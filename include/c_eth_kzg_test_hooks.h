@@ -91,6 +91,23 @@ int eth_kzg_amd_test_verify_cells_partial_device(const DASContext *ctx, uint64_t
 int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext *ctx, uint64_t n, int on_device, const void *blobs, const void *commitments,
                                               const void *proofs, uint8_t *out96, int32_t *verified);
 
+/* The leaf-hashed challenge of the cell verifier (c_eth_kzg.h: ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT; tests/test_gpu_leaf_transcript.py).
+ * eth_kzg_amd_test_cell_leaf_digests: the leaf kernel (csrc/k_sha256.hip: k_sha256_cell_leaves) behind the staging and the launch of the
+ *   flagged verification -- de-duplicated commitments, the row array, 32-bit indices, the arena's offsets.  Flat HOST arrays of n >= 1
+ *   entries: commitments n * 48 bytes, cell_indices n uint64 (each below 128, else 3), cells n * 2048, proofs n * 48; any bytes will do
+ *   (the call returns behind the digests, before a decoding verdict is read).  out_digests (host): n * 32 bytes, LEAF_0 .. LEAF_{n-1}.
+ * eth_kzg_amd_test_verify_cells_inputs_ex: the whole batch through eth_kzg_amd_verify_cell_kzg_proof_batch_ex (on_device = 0:
+ *   commitments / cells / proofs are arrays of n host pointers, cell_indices n uint64 on the host) or ..._device_ex (on_device = 1: the four
+ *   flat arrays in device memory), n >= 1, flags as the public calls take them.  root32 (host) = the 32 digest bytes the challenge was
+ *   reduced from (flags = 0: of the reference's transcript; leaf flag: ROOT), out96 (host) = compress(sum r^k pi_k) | compress(the second
+ *   pairing input) over all n cells.
+ * Synchronous; return 0 on success, the library's status codes otherwise (a NULL buffer or an unknown flag: 3). */
+int eth_kzg_amd_test_cell_leaf_digests(const DASContext *ctx, uint64_t n, const uint8_t *commitments, const uint64_t *cell_indices,
+                                       const uint8_t *cells, const uint8_t *proofs, uint8_t *out_digests);
+int eth_kzg_amd_test_verify_cells_inputs_ex(const DASContext *ctx, uint64_t n, int on_device, const void *commitments,
+                                            const void *cell_indices, const void *cells, const void *proofs, uint32_t flags, uint8_t *root32,
+                                            uint8_t *out96);
+
 /* ONE pass of eth_kzg_amd_verify_cell_kzg_proof_batch_many with what it pairs handed out (tests/test_verify_inputs.py compares every byte
  * with the statement of tests/verify_transcript.py: per-problem power tables, positions, row weights, sums, the folding weights, the fold
  * and the search's probes all show in them; a verdict shows none of that).  The arguments of the public call (host pointers), and exactly its

@@ -45,6 +45,8 @@ SETUP_NO_SUBGROUP_CHECK = 1
 SETUP_CHECK_POWERS = 2
 SETUP_G1_POINTS = 4096
 SETUP_G2_POINTS = 65
+# flags of eth_kzg_amd_verify_cell_kzg_proof_batch_ex / _device_ex
+VERIFY_LEAF_TRANSCRIPT = 1
 
 EXPORTED_SYMBOLS = [
     "eth_kzg_das_context_new", "eth_kzg_das_context_free", "eth_kzg_free_error_message",
@@ -62,6 +64,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_cell_kzg_proof_batch_partial", "eth_kzg_amd_verify_cell_kzg_proof_batch_combine",
     "eth_kzg_amd_compute_cells_and_kzg_proofs_device", "eth_kzg_amd_blob_to_kzg_commitment_device",
     "eth_kzg_amd_verify_cell_kzg_proof_batch_device", "eth_kzg_amd_verify_cell_kzg_proof_batch_many",
+    "eth_kzg_amd_verify_cell_kzg_proof_batch_ex", "eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex",
     "eth_kzg_amd_compute_blob_kzg_proof_batch", "eth_kzg_amd_compute_kzg_proof_batch",
     "eth_kzg_amd_compute_blob_kzg_proof_device", "eth_kzg_amd_compute_kzg_proof_device",
     "eth_kzg_amd_verify_blob_kzg_proof_batch_device",
@@ -80,6 +83,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_verify_cells_partial_device", "eth_kzg_amd_test_verify_blob_batch_inputs", "eth_kzg_amd_test_rs_decode",
     "eth_kzg_amd_test_prover_scalars", "eth_kzg_amd_test_verify_many_sums",
     "eth_kzg_amd_test_proofs_from_sums", "eth_kzg_amd_test_linmap_program",
+    "eth_kzg_amd_test_cell_leaf_digests", "eth_kzg_amd_test_verify_cells_inputs_ex",
 ]
 
 _lib = None
@@ -173,6 +177,13 @@ def load_library():
         lib.eth_kzg_amd_das_context_new_with_setup_file.argtypes = [P, U64, C.c_uint32, C.c_bool, P, U64, C.c_double, C.POINTER(CResult)]
         lib.eth_kzg_amd_setup_digest.restype = None
         lib.eth_kzg_amd_setup_digest.argtypes = [P, P]
+    for name, args in {
+        "eth_kzg_amd_verify_cell_kzg_proof_batch_ex": [P, U64, P, U64, P, U64, P, U64, P, C.c_uint32, P],
+        "eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex": [P, U64, P, P, P, P, C.c_uint32, P, P],
+    }.items():
+        if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
+            getattr(lib, name).restype = CResult
+            getattr(lib, name).argtypes = args
     lib.eth_kzg_amd_window_count.argtypes = [P]
     lib.eth_kzg_amd_glv_table.argtypes = [P]
     # the stage-level test hooks exist in libc_eth_kzg_hooks.so only (what tests/ loads through ETH_KZG_AMD_LIB); the product
@@ -199,6 +210,8 @@ def load_library():
         "eth_kzg_amd_test_verify_many_sums": [P, U64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, U64, P],
         "eth_kzg_amd_test_proofs_from_sums": [P, C.c_int, C.c_int, P, P],
         "eth_kzg_amd_test_linmap_program": [P, C.c_int, P, U64, P, P, U64, P, P, P, U64, P],
+        "eth_kzg_amd_test_cell_leaf_digests": [P, U64, P, P, P, P, P],
+        "eth_kzg_amd_test_verify_cells_inputs_ex": [P, U64, C.c_int, P, P, P, P, C.c_uint32, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -468,7 +481,9 @@ class DASContext:
         self._check(self._lib.eth_kzg_compute_cells(self._ctx, bytes(blob), ca))
         return [c.raw for c in cells]
 
-    def verify_cell_kzg_proof_batch(self, commitments, cell_indices, cells, proofs):
+    def verify_cell_kzg_proof_batch(self, commitments, cell_indices, cells, proofs, leaf_transcript=False):
+        """leaf_transcript=True: eth_kzg_amd_verify_cell_kzg_proof_batch_ex with ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT -- the challenge is
+        hashed per cell on the GPU instead of over the whole batch on a host core (same verdicts and errors; include/c_eth_kzg.h)."""
         if any(len(c) != 48 for c in commitments) or any(len(p) != 48 for p in proofs) \
                 or any(len(c) != BYTES_PER_CELL for c in cells):
             raise KzgError("InvalidLength")
@@ -477,6 +492,11 @@ class DASContext:
         pa, _k3 = _flat_ptrs(proofs, 48)
         idx = np.array(cell_indices, dtype=np.uint64) if len(cell_indices) else np.zeros(1, np.uint64)
         ok = C.c_bool(False)
+        if leaf_transcript:
+            self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_ex(
+                self._ctx, len(commitments), _vp(ca), len(cell_indices), _vp(idx), len(cells), _vp(cla), len(proofs), _vp(pa),
+                VERIFY_LEAF_TRANSCRIPT, C.byref(ok)))
+            return bool(ok.value)
         self._check(self._lib.eth_kzg_verify_cell_kzg_proof_batch(
             self._ctx, len(commitments), _vp(ca), len(cell_indices), _vp(idx), len(cells), _vp(cla), len(proofs), _vp(pa),
             C.byref(ok)))
@@ -755,10 +775,16 @@ class DASContext:
             ctxs, len(contexts), n, _vp(ba), _vp(bufs["cpp"]), _vp(bufs["ppp"]), bufs["status"]))
         return list(bufs["status"])[:n]
 
-    def verify_cell_kzg_proof_batch_device(self, n, d_commitments, d_cell_indices, d_cells, d_proofs, stream=None):
+    def verify_cell_kzg_proof_batch_device(self, n, d_commitments, d_cell_indices, d_cells, d_proofs, stream=None, leaf_transcript=False):
         """Device-resident verification: integer device addresses of n*48 commitment bytes (one per cell), n uint64 indices,
-        n*2048 cell bytes, n*48 proof bytes."""
+        n*2048 cell bytes, n*48 proof bytes.  leaf_transcript=True: eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex with
+        ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT -- cells and proofs are hashed where they lie and never copied to the host."""
         ok = C.c_bool(False)
+        if leaf_transcript:
+            self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(
+                self._ctx, int(n), C.c_void_p(d_commitments), C.c_void_p(d_cell_indices), C.c_void_p(d_cells), C.c_void_p(d_proofs),
+                VERIFY_LEAF_TRANSCRIPT, C.byref(ok), C.c_void_p(stream) if stream else None))
+            return bool(ok.value)
         self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_device(
             self._ctx, int(n), C.c_void_p(d_commitments), C.c_void_p(d_cell_indices), C.c_void_p(d_cells), C.c_void_p(d_proofs),
             C.byref(ok), C.c_void_p(stream) if stream else None))

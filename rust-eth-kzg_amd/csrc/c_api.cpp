@@ -345,6 +345,50 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device(const DASContext* ctx, ui
     return ok();
 }
 
+// The two calls above with a flags word (c_eth_kzg.h: the leaf-hashed challenge).  The flagged host form is a single-problem call on a
+// serial lane: it never joins the combiner, whose passes keep the reference's transcript.
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_ex(const DASContext* ctx, uint64_t commitments_length, const uint8_t* const* commitments,
+                                                   uint64_t cell_indices_length, const uint64_t* cell_indices, uint64_t cells_length,
+                                                   const uint8_t* const* cells, uint64_t proofs_length, const uint8_t* const* proofs,
+                                                   uint32_t flags, bool* verified) {
+    if (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) return err("InvalidInput: unknown verification flags");  // (before the context is looked at)
+    if (cells_length > kzg::MAX_CELLS_PER_VERIFICATION) return err("InvalidInput");
+    if (!flags)
+        return eth_kzg_verify_cell_kzg_proof_batch(ctx, commitments_length, commitments, cell_indices_length, cell_indices, cells_length, cells,
+                                                   proofs_length, proofs, verified);
+    Picked p = pick(ctx, cells_length / 8 + 1);
+    auto lane = p.e->lease_serial();
+    kzg::Engine* e = lane.e;
+    kzg::CellChallengeMode mode;
+    mode.leaf = true;
+    int ver = 0;
+    int st = e->verify_cell_kzg_proof_batch_host(commitments_length, commitments, cell_indices_length, cell_indices, cells_length, cells,
+                                                 proofs_length, proofs, &ver, &mode);
+    if (st == kzg::ERR_DEVICE) return device_err(e);
+    if (st) return err(status_text(st));
+    *verified = ver != 0;
+    return ok();
+}
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(const DASContext* ctx, uint64_t n, const uint8_t* d_commitments,
+                                                          const uint64_t* d_cell_indices, const uint8_t* d_cells, const uint8_t* d_proofs,
+                                                          uint32_t flags, bool* verified, void* hip_stream) {
+    if (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) return err("InvalidInput: unknown verification flags");
+    if (n > kzg::MAX_CELLS_PER_VERIFICATION) return err("InvalidInput");
+    if (!flags) return eth_kzg_amd_verify_cell_kzg_proof_batch_device(ctx, n, d_commitments, d_cell_indices, d_cells, d_proofs, verified, hip_stream);
+    kzg::Engine* owner = engine_of_pointer(ctx, d_cells);
+    if (!owner) return err("InvalidInput: the buffers are on no device of this context");
+    auto lane = owner->lease_serial();
+    kzg::Engine* e = lane.e;
+    kzg::CellChallengeMode mode;
+    mode.leaf = true;
+    int ver = 0;
+    int st = e->verify_cell_kzg_proof_batch_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, &ver, (hipStream_t)hip_stream, &mode);
+    if (st == kzg::ERR_DEVICE) return device_err(e);
+    if (st) return err(status_text(st));
+    *verified = ver != 0;
+    return ok();
+}
+
 CResult eth_kzg_amd_recover_cells_and_proofs_device(const DASContext* ctx, uint64_t n, const uint8_t* d_cells,
                                                     const uint64_t* present_masks, uint8_t* d_out_cells, uint8_t* d_out_proofs,
                                                     int32_t* status, void* hip_stream) {

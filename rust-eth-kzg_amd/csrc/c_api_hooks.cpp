@@ -84,6 +84,16 @@ int eth_kzg_amd_test_verify_blob_batch_inputs(const DASContext* ctx, uint64_t n,
     *verified = v;
     return rc;
 }
+int eth_kzg_amd_test_cell_leaf_digests(const DASContext* ctx, uint64_t n, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells,
+                                       const uint8_t* proofs, uint8_t* out_digests) {
+    if (!commitments || !cell_indices || !cells || !proofs || !out_digests) return kzg::ERR_INPUT;
+    return eng(ctx)->test_cell_leaf_digests(n, commitments, cell_indices, cells, proofs, out_digests);
+}
+int eth_kzg_amd_test_verify_cells_inputs_ex(const DASContext* ctx, uint64_t n, int on_device, const void* commitments, const void* cell_indices,
+                                            const void* cells, const void* proofs, uint32_t flags, uint8_t* root32, uint8_t* out96) {
+    if (!commitments || !cell_indices || !cells || !proofs || !root32 || !out96 || (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT)) return kzg::ERR_INPUT;
+    return eng(ctx)->test_verify_cells_inputs_ex(n, on_device, commitments, cell_indices, cells, proofs, flags, root32, out96);
+}
 int eth_kzg_amd_test_verify_many_sums(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths,
                                       const uint8_t* const* const* commitments, const uint64_t* cell_indices_lengths,
                                       const uint64_t* const* cell_indices, const uint64_t* cells_lengths, const uint8_t* const* const* cells,

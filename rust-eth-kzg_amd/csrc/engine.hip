@@ -266,6 +266,9 @@ void Engine::construct() {
     if (v_two_streams_) HIPCK(hipStreamCreateWithFlags(&v_side_, hipStreamNonBlocking));
     HIPCK(hipEventCreateWithFlags(&v_decoded_, hipEventDisableTiming));
     HIPCK(hipEventCreateWithFlags(&v_checked_, hipEventDisableTiming));
+    HIPCK(hipEventCreateWithFlags(&v_leaves_, hipEventDisableTiming));
+    HIPCK(hipEventCreateWithFlags(&v_uploaded_, hipEventDisableTiming));
+    HIPCK(hipStreamCreateWithFlags(&v_leaf_stream_, hipStreamNonBlocking));
     for (Work& w : work_) {
         HIPCK(hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
         HIPCK(hipEventCreateWithFlags(&w.ev_in, hipEventDisableTiming));
@@ -405,6 +408,9 @@ void Engine::teardown() noexcept {
     if (v_side_) hipStreamDestroy(v_side_);
     if (v_decoded_) hipEventDestroy(v_decoded_);
     if (v_checked_) hipEventDestroy(v_checked_);
+    if (v_leaves_) hipEventDestroy(v_leaves_);
+    if (v_uploaded_) hipEventDestroy(v_uploaded_);
+    if (v_leaf_stream_) hipStreamDestroy(v_leaf_stream_);
     if (stream_) hipStreamDestroy(stream_);
 }
 

@@ -48,6 +48,16 @@ struct VerifyManyTap {
     std::vector<uint8_t> probe_sums;                 // [probe][2] JacQ
 };
 
+// How a single cell verification takes its Fiat-Shamir challenge (verify.hip).  Null or `leaf` false: the reference's transcript, one
+// SHA-256 over the whole batch on a host core.  leaf: the leaf-hashed challenge (verify_host.hpp: CellLeafTranscript) -- one SHA-256
+// per cell on the GPU, out of the arena the inputs are staged into anyway, and one short SHA-256 over the digests on the host.
+// The two taps are null in every product call (the stage hooks set them).
+struct CellChallengeMode {
+    bool leaf = false;
+    uint8_t* digest_out = nullptr;  // the 32 bytes r was reduced from
+    uint8_t* leaves_out = nullptr;  // (leaf) the n x 32 leaf digests as they came down; the call then returns OK behind them, before any verdict is read
+};
+
 enum Status : int {
     OK = 0,
     ERR_SCALAR = 1,    // a field element >= r   (SerializationError::CouldNotDeserializeScalar)
@@ -164,11 +174,13 @@ public:
     // verify_cell_kzg_proof_batch (eip7594/src/verifier.rs:72-112): returns a Status; *verified set on OK.
     int verify_cell_kzg_proof_batch_host(uint64_t n_commitments, const uint8_t* const* commitments, uint64_t n_indices,
                                          const uint64_t* cell_indices, uint64_t n_cells, const uint8_t* const* cells,
-                                         uint64_t n_proofs, const uint8_t* const* proofs, int* verified);
+                                         uint64_t n_proofs, const uint8_t* const* proofs, int* verified, const CellChallengeMode* mode = nullptr);
     // the same check on flat arrays in this GPU's HBM: n * 48 commitment bytes (one per cell, not deduplicated), n u64 indices,
-    // n * 2048 cell bytes, n * 48 proof bytes
+    // n * 2048 cell bytes, n * 48 proof bytes.  With the leaf-hashed challenge neither cells nor proofs come down: only the
+    // commitments and the indices (validation, de-duplication) and the n * 32 leaf digests do
     int verify_cell_kzg_proof_batch_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices,
-                                           const uint8_t* d_cells, const uint8_t* d_proofs, int* verified, hipStream_t stream);
+                                           const uint8_t* d_cells, const uint8_t* d_proofs, int* verified, hipStream_t stream,
+                                           const CellChallengeMode* mode = nullptr);
     // MANY independent verifications in one call (verify_many.hip): problem b has n_*[b] entries in commitments[b] / cell_indices[b]
     // / cells[b] / proofs[b]; status[b] = a Status (OK, ERR_INPUT, ERR_G1, ERR_SCALAR), verified[b] set when OK.  Returns
     // ERR_DEVICE on a HIP failure, OK otherwise.  Does not take mu_: runs next to the other entry points.
@@ -263,6 +275,13 @@ public:
     // verify_cell_kzg_proof_batch_device (verify_cells_partial_device: the pinned mirror in chunks, the device source)
     int test_verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
                                          const uint8_t* d_proofs, uint64_t lo, uint64_t hi, uint8_t* out96);
+    // the leaf digests of a batch given as flat host arrays, by the staging and the launch the leaf-hashed verification makes (verify.hip)
+    int test_cell_leaf_digests(uint64_t n, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs,
+                               uint8_t* out_digests);
+    // the whole batch's challenge digest and two pairing inputs under either transcript (flags: ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT or 0);
+    // on_device: the flat arrays of the device-resident form, else the host form's pointer arrays
+    int test_verify_cells_inputs_ex(uint64_t n, int on_device, const void* commitments, const void* cell_indices, const void* cells,
+                                    const void* proofs, uint32_t flags, uint8_t* root32, uint8_t* out96);
     // the two sums verify_blob_kzg_proof_batch pairs (rhs | lhs, compressed) and its verdict; on_device: flat arrays in HBM, else host pointers
     int test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs, uint8_t* out96,
                                       int* verified);
@@ -374,16 +393,18 @@ private:
     struct VerifyDeviceSource {
         const uint8_t *d_cells, *d_proofs;  // flat [n][2048] / [n][48] in this GPU's memory
         hipEvent_t* chunk_events;           // chunk j = cells [j * chunk_cells, (j + 1) * chunk_cells) of the mirror
-        int chunk_cells, n_chunks;
+        int chunk_cells, n_chunks;          // (leaf-hashed challenge: no mirror, no chunks: null, 0, 0)
     };
     int verify_cells_partial(uint64_t n_commitments, const uint8_t* const* commitments, uint64_t n_indices,
                              const uint64_t* cell_indices, uint64_t n_cells, const uint8_t* const* cells, uint64_t n_proofs,
                              const uint8_t* const* proofs, uint64_t lo, uint64_t hi, G1Affine* out2, bool* empty,
-                             const VerifyDeviceSource* dsrc = nullptr, VerifyScratch* vs = nullptr);
+                             const VerifyDeviceSource* dsrc = nullptr, VerifyScratch* vs = nullptr, const CellChallengeMode* mode = nullptr);
     // the device-resident form's set-up in front of verify_cells_partial: commitments, indices and proofs down into the pinned mirror,
     // the cells behind them in chunks with an event each, the pointer arrays over the mirror, the device source.  The CALLER holds mu_ (the mirror is the context's).
+    // Leaf-hashed challenge: commitments and indices only, no mirror of cells or proofs and no chunk events.
     int verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
-                                    const uint8_t* d_proofs, uint64_t lo, uint64_t hi, G1Affine* out2, bool* empty, hipStream_t user_stream);
+                                    const uint8_t* d_proofs, uint64_t lo, uint64_t hi, G1Affine* out2, bool* empty, hipStream_t user_stream,
+                                    const CellChallengeMode* mode = nullptr);
     bool verify_cells_pairing(const G1Affine* pts2) const;
     // the same check with the second pair's Miller loop on a thread of the staging pool (the latency path of a single verification)
     bool verify_cells_pairing_split(const G1Affine* pts2);
@@ -500,6 +521,10 @@ private:
     hipStream_t v_side_ = nullptr;  // verification, round 3's form: the subgroup tests run here next to the point shifts on stream_
     bool v_two_streams_ = false;    // (both chains run in ONE launch on stream_, k_pip_shift_subgroup; the two-stream form of round 3 shared hardware queues)
     hipEvent_t v_decoded_ = nullptr, v_checked_ = nullptr;
+    // leaf-hashed challenge (under mu_): the leaf kernel and the read-back of its digests run on a stream of their own, behind the upload
+    // (v_uploaded_) and next to the decoding kernels on stream_; v_leaves_: the digests are in the pinned slab
+    hipStream_t v_leaf_stream_ = nullptr;
+    hipEvent_t v_uploaded_ = nullptr, v_leaves_ = nullptr;
 
     // serial-path lanes (lease_serial)
     const Engine* primary_ = nullptr;   // set in an auxiliary lane

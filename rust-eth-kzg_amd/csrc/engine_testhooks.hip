@@ -433,6 +433,53 @@ int Engine::test_verify_cells_partial_device(uint64_t n, const uint8_t* d_commit
     g1_compress(out96 + 48, pts[1]);
     return OK;
 }
+// The leaf-hashed challenge (verify.hip).  The leaf digests: the flagged verification's own pass over flat host arrays, with the tap
+// that hands the digests out and ends the call behind them.
+int Engine::test_cell_leaf_digests(uint64_t n, const uint8_t* commitments, const uint64_t* cell_indices, const uint8_t* cells, const uint8_t* proofs,
+                                   uint8_t* out_digests) {
+    if (n < 1 || n > MAX_CELLS_PER_VERIFICATION) return ERR_INPUT;
+    std::vector<const uint8_t*> cp, lp, pp;
+    try {
+        cp.resize(n); lp.resize(n); pp.resize(n);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    for (uint64_t k = 0; k < n; k++) {
+        cp[k] = commitments + k * 48;
+        lp[k] = cells + k * (size_t)BYTES_PER_CELL;
+        pp[k] = proofs + k * 48;
+    }
+    CellChallengeMode mode;
+    mode.leaf = true;
+    mode.leaves_out = out_digests;
+    G1Affine pts[2];
+    bool empty = false;
+    return verify_cells_partial(n, cp.data(), n, cell_indices, n, lp.data(), n, pp.data(), 0, n, pts, &empty, nullptr, nullptr, &mode);
+}
+// The whole batch's challenge digest and pairing inputs under either transcript, host or device-resident form.
+int Engine::test_verify_cells_inputs_ex(uint64_t n, int on_device, const void* commitments, const void* cell_indices, const void* cells,
+                                        const void* proofs, uint32_t flags, uint8_t* root32, uint8_t* out96) {
+    if (n < 1 || n > MAX_CELLS_PER_VERIFICATION) return ERR_INPUT;
+    CellChallengeMode mode;
+    mode.leaf = flags != 0;
+    mode.digest_out = root32;
+    G1Affine pts[2];
+    bool empty = false;
+    int rc;
+    if (on_device) {
+        std::lock_guard<std::recursive_mutex> lk(mu_);
+        rc = verify_cells_partial_device(n, (const uint8_t*)commitments, (const uint64_t*)cell_indices, (const uint8_t*)cells, (const uint8_t*)proofs, 0, n,
+                                         pts, &empty, nullptr, &mode);
+    } else {
+        rc = verify_cells_partial(n, (const uint8_t* const*)commitments, n, (const uint64_t*)cell_indices, n, (const uint8_t* const*)cells, n,
+                                  (const uint8_t* const*)proofs, 0, n, pts, &empty, nullptr, nullptr, &mode);
+    }
+    if (rc) return rc;
+    g1_compress(out96, pts[0]);
+    g1_compress(out96 + 48, pts[1]);
+    return OK;
+}
 // The blob batch verifier, host or device-resident form: the product's call with the out-pointer of pairing_check_4844 set.
 int Engine::test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs,
                                           uint8_t* out96, int* verified) {

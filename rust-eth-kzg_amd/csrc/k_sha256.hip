@@ -27,7 +27,11 @@
 //
 // Plain C++: rotates as the compiler lowers them (v_alignbit_b32), no inline assembly, ordinary vector stores; one scheduling
 // builtin keeps the prefetch in front of the rounds (checked in the ISA: wait, swap, four loads, then the 64 rounds).
+//
+// Second kernel, behind the first: k_sha256_cell_leaves, the per-cell leaves of the cell verifier's leaf-hashed challenge.
 #include "launch.hpp"
+
+#include <stdexcept>
 
 namespace kzg {
 namespace {
@@ -149,6 +153,93 @@ __global__ __launch_bounds__(64) void k_sha256_many(int n, const uint8_t* __rest
     }
 }
 
+// ---- The leaves of the cell verifier's leaf-hashed challenge (verify_host.hpp: CellLeafTranscript), straight out of the verifier's
+// arena as stage_and_decode (verify.hip) leaves it:
+//   leaf k = SHA-256("RCKZGCBATCHLEAF1" | be64(k) | be64(idx[k]) | uniq[row[k]] (48 B) | proofs[k] (48 B) | cells[k] (2048 B))
+// 2176 bytes = 34 blocks of the message and a 35th of constant padding.  One lane per cell, blocks of one whole wave, the lanes
+// behind the last cell repeat its work and store nothing: the launch shape of k_sha256_many and its reasons.
+// The uniform layout takes the place of k_sha256_many's general gather: the header is exactly two blocks, built in registers
+// from the position, the index and six 16-byte loads (a commitment and a proof are 48 bytes at 48-byte strides from 256-byte-
+// aligned offsets of the arena); every 64-byte row of the cell is one block and takes the wide loads, one block ahead of the
+// compression, as above -- lane l walks its own 2 KiB row, so the argument of this file's header about lines and latency holds
+// with rows 2 KiB apart instead of 128 KiB; the padding block is three constants.  A batch of 8192 cells is 128 waves on a chip
+// with 1024 SIMDs: while every wave has a SIMD to itself the launch lasts what ONE lane's 35 dependent compressions last
+// (about 0.2 ms with the read-back and the root), and it leaves the chip to the decoding kernels next to it.
+// The launcher refuses pointers that do not have the alignments the wide loads and stores assume.
+constexpr uint32_t be32_of(const char* s) {
+    return ((uint32_t)(uint8_t)s[0] << 24) | ((uint32_t)(uint8_t)s[1] << 16) | ((uint32_t)(uint8_t)s[2] << 8) | (uint32_t)(uint8_t)s[3];
+}
+// "RCKZGCBATCHLEAF1" as four big-endian words
+constexpr uint32_t LEAF_DOMAIN_0 = be32_of("RCKZ"), LEAF_DOMAIN_1 = be32_of("GCBA"), LEAF_DOMAIN_2 = be32_of("TCHL"), LEAF_DOMAIN_3 = be32_of("EAF1");
+constexpr uint32_t LEAF_MESSAGE_BITS = (16 + 8 + 8 + 48 + 48 + 2048) * 8;
+static_assert(LEAF_MESSAGE_BITS == 17408 && LEAF_MESSAGE_BITS % 512 == 0, "34 whole blocks: the padding is a block of its own");
+
+// 16 aligned bytes as four big-endian words
+__device__ __forceinline__ void load16_be(const uint8_t* p, uint32_t* w) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    w[0] = __builtin_bswap32(v.x); w[1] = __builtin_bswap32(v.y); w[2] = __builtin_bswap32(v.z); w[3] = __builtin_bswap32(v.w);
+}
+// the blocks that are not rows of the cell: 0 and 1 = the header, 2 = the padding
+__device__ __forceinline__ void leaf_edge_block(int which, uint32_t k, uint32_t index, const uint8_t* commitment, const uint8_t* proof,
+                                                uint32_t (&w)[16]) {
+    if (which == 0) {
+        w[0] = LEAF_DOMAIN_0; w[1] = LEAF_DOMAIN_1; w[2] = LEAF_DOMAIN_2; w[3] = LEAF_DOMAIN_3;
+        w[4] = 0; w[5] = k;      // be64(k): positions are 32-bit on the device (engine.hpp: MAX_CELLS_PER_VERIFICATION)
+        w[6] = 0; w[7] = index;  // be64(index)
+        load16_be(commitment, w + 8);
+        load16_be(commitment + 16, w + 12);
+    } else if (which == 1) {
+        load16_be(commitment + 32, w);
+        load16_be(proof, w + 4);
+        load16_be(proof + 16, w + 8);
+        load16_be(proof + 32, w + 12);
+    } else {
+        w[0] = 0x80000000u;
+#pragma unroll
+        for (int j = 1; j < 15; j++) w[j] = 0;
+        w[15] = LEAF_MESSAGE_BITS;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_sha256_cell_leaves(int n, const uint8_t* __restrict__ uniq, const int* __restrict__ row,
+                                                           const int* __restrict__ idx, const uint8_t* __restrict__ proofs,
+                                                           const uint8_t* __restrict__ cells, uint8_t* __restrict__ out) {
+    const int lane_cell = blockIdx.x * 64 + threadIdx.x;
+    const int i = lane_cell < n ? lane_cell : n - 1;
+    const uint8_t* commitment = uniq + (size_t)row[i] * 48;
+    const uint8_t* proof = proofs + (size_t)i * 48;
+    const uint8_t* cell = cells + (size_t)i * 2048;
+    const uint32_t index = (uint32_t)idx[i];
+    uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+    uint32_t w[16];
+    // two passes of the edge blocks around the wide loop (one inlined copy of the rounds each): the header, then the padding
+#pragma unroll 1
+    for (int pass = 0; pass < 2; pass++) {
+#pragma unroll 1
+        for (int e = pass ? 2 : 0; e < (pass ? 3 : 2); e++) {
+            leaf_edge_block(e, (uint32_t)i, index, commitment, proof, w);
+            sha256_compress(h, w);
+        }
+        if (pass == 0) {
+            uint32_t raw[16];
+            load_block_wide(cell, raw);
+#pragma unroll 1
+            for (int k = 0; k < 32; k++) {
+#pragma unroll
+                for (int j = 0; j < 16; j++) w[j] = __builtin_bswap32(raw[j]);
+                // the next row's loads are in flight under the 64 rounds below (the last iteration reloads its own row: no branch)
+                load_block_wide(cell + (size_t)(k + 1 < 32 ? k + 1 : k) * 64, raw);
+                __builtin_amdgcn_sched_barrier(0);  // (as in k_sha256_many: the loads stay in front of the rounds)
+                sha256_compress(h, w);
+            }
+        }
+    }
+    if (lane_cell >= n) return;
+    uint4* q = reinterpret_cast<uint4*>(out + (size_t)i * 32);
+    q[0] = make_uint4(__builtin_bswap32(h[0]), __builtin_bswap32(h[1]), __builtin_bswap32(h[2]), __builtin_bswap32(h[3]));
+    q[1] = make_uint4(__builtin_bswap32(h[4]), __builtin_bswap32(h[5]), __builtin_bswap32(h[6]), __builtin_bswap32(h[7]));
+}
+
 }  // namespace
 
 namespace launch {
@@ -156,6 +247,15 @@ namespace launch {
 void preload_k_sha256() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_sha256_many));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_sha256_cell_leaves));
+}
+void sha256_cell_leaves(int n, const uint8_t* uniq, const int* row, const int* idx, const uint8_t* proofs, const uint8_t* cells, uint8_t* out,
+                        hipStream_t st) {
+    if (n <= 0) return;
+    const uintptr_t loads = reinterpret_cast<uintptr_t>(uniq) | reinterpret_cast<uintptr_t>(proofs) | reinterpret_cast<uintptr_t>(cells);
+    if ((loads & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 31) != 0 || ((reinterpret_cast<uintptr_t>(row) | reinterpret_cast<uintptr_t>(idx)) & 3) != 0)
+        throw std::invalid_argument("sha256_cell_leaves: commitments, proofs and cells must be 16-byte aligned, the digests 32-byte aligned");
+    k_sha256_cell_leaves<<<(n + 63) / 64, 64, 0, st>>>(n, uniq, row, idx, proofs, cells, out);
 }
 void sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* body, size_t body_stride, uint32_t body_len,
                  const uint8_t* tail, size_t tail_stride, uint32_t tail_len, uint8_t* out, hipStream_t st) {

@@ -202,6 +202,11 @@ void status_4844(int n, const int* blob_bad, const int* z_bad, const int* g1_bad
 // (tail + i * tail_stride)[tail_len], all device pointers (a part of length 0 may be null); digest i -> out + 32 i
 void sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* body, size_t body_stride, uint32_t body_len,
                  const uint8_t* tail, size_t tail_stride, uint32_t tail_len, uint8_t* out, hipStream_t st);
+// the n leaves of the cell verifier's leaf-hashed challenge (verify_host.hpp: CellLeafTranscript), one lane each, from the verifier's
+// arena: leaf k hashes k, idx[k], uniq + 48 row[k], proofs + 48 k and cells + 2048 k; digest k -> out + 32 k.  uniq, proofs and cells
+// 16-byte aligned, out 32-byte aligned (anything else throws before the launch)
+void sha256_cell_leaves(int n, const uint8_t* uniq, const int* row, const int* idx, const uint8_t* proofs, const uint8_t* cells, uint8_t* out,
+                        hipStream_t st);
 
 constexpr size_t SIZEOF_FR = 32, SIZEOF_G1AFFINE = 96, SIZEOF_G1JAC = 144;
 constexpr size_t SIZEOF_JACS = 156;  // signed 13 x 30-bit Jacobian point (curve30.hpp)

@@ -4,6 +4,8 @@
 // compute_fiat_shamir_challenge (:269-328).
 // Work split: all G1 / Fr batch arithmetic on the GPU; the sequential SHA-256 transcript (verify_host.hpp) and the
 // constant-size 2-pairing check on the host.  Recovery: recover.hip.
+// With ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT (CellChallengeMode::leaf) the challenge is the leaf-hashed one instead (verify_host.hpp:
+// CellLeafTranscript): one SHA-256 per cell on the GPU (k_sha256.hip), the root over the digests on the host.
 #include "engine_internal.hpp"
 #include "curve29.hpp"
 #include "host_pairing.hpp"
@@ -60,21 +62,24 @@ namespace {
 struct Layout {
     const int n, m;
     const bool shifted;  // the byte-shifted lincombs (k_verify.hip): point copies and per-cell interpolation polynomials are built behind the hash
+    const bool leaf;     // the leaf-hashed challenge: n x 32 digest bytes on the device and, read back, in the pinned slab
     const size_t npts = (size_t)n + m + 64;  // one point array [proofs n | commitments m | 64 SRS points] so that the second lincomb is a single MSM
     const int ib = n < 256 ? n : 256;
     const size_t sz_c = (size_t)m * 48, sz_p = (size_t)n * 48, sz_cells = (size_t)n * BYTES_PER_CELL, sz_i = (size_t)n * sizeof(int);
     Carve d;  // (members are initialised in the order they stand here)
     const size_t off_c = d.take(sz_c), off_p = d.take(sz_p), off_cells = d.take(sz_cells), off_idx = d.take(sz_i), off_row = d.take(sz_i), in_bytes = d.end;
     Carve h = d;  // pinned read-back area behind the inputs: statuses (m + n + 1 ints) and room for the two result points
-    const size_t n_status = (size_t)m + n + 1, off_hst = h.take(n_status * sizeof(int)), pin_bytes = (h.take(256), h.end);
+    const size_t n_status = (size_t)m + n + 1, off_hst = h.take(n_status * sizeof(int)), off_hleaf = h.take(leaf ? (size_t)n * 32 : 0),
+                 pin_bytes = (h.take(256), h.end);
     const size_t off_pts = d.take(npts * sizeof(G1Affine)), off_evals = d.take((size_t)n * CELL_LEN * sizeof(Fr)), off_stc = d.take((size_t)m * sizeof(int)),
                  off_stp = d.take(sz_i), off_ste = d.take(sizeof(int)), off_rp = d.take((size_t)n * sizeof(Fr)), off_s1 = d.take((size_t)n * sizeof(Fr)),
                  off_sB = d.take(npts * sizeof(Fr)), off_part = d.take((size_t)ib * 64 * sizeof(Fr)),
                  off_ws = d.take(shifted ? launch::pip_shift_workspace_bytes((int)npts) : launch::pip_workspace_bytes((int)npts)),
                  off_coef = d.take(shifted ? (size_t)n * CELL_LEN * sizeof(Fr) : 0),
                  off_out = d.take(512),  // two affine points, or two Jacobian sums (shifted form)
+                 off_leaf = d.take(leaf ? (size_t)n * 32 : 0),
                  dev_bytes = d.end;
-    Layout(int n_, int m_, bool shifted_) : n(n_), m(m_), shifted(shifted_) {}
+    Layout(int n_, int m_, bool shifted_, bool leaf_ = false) : n(n_), m(m_), shifted(shifted_), leaf(leaf_) {}
 };
 
 // the end of a staging task, seen from the frame whose locals the task uses
@@ -111,6 +116,10 @@ struct CellPass {
     Fr8 inv64;
     hipStream_t side = nullptr;  // round 3's form (ETH_KZG_AMD_VERIFY_SIDE_STREAM=1): the subgroup tests on this second stream; null: one stream
     hipEvent_t decoded = nullptr, checked = nullptr;
+    // leaf-hashed challenge (L.leaf): the leaves are hashed on leaf_st behind `uploaded`, next to the decoding on st; `leaves` is
+    // recorded behind the read-back of their digests
+    hipStream_t leaf_st = nullptr;
+    hipEvent_t uploaded = nullptr, leaves = nullptr;
 
     int* h_status() const { return (int*)(hb + L.off_hst); }  // pinned: [commitments m | proofs n | cells 1]; the read-backs do not block
     G1Affine* d_proofs_aff() const { return (G1Affine*)(db + L.off_pts); }
@@ -148,6 +157,18 @@ struct CellPass {
             HIPCK(hipMemcpyAsync(db + L.off_cells, src_cells + (size_t)k0 * BYTES_PER_CELL, L.sz_cells, hipMemcpyDeviceToDevice, st));
         }
         HIPCK(hipMemsetAsync(d_ste, 0, sizeof(int), st));
+        if (L.leaf) {
+            // the leaves straight out of the arena (every offset of it is a multiple of 256: the kernel's 16-byte loads), on a stream of
+            // their own: a wave per 64 cells for 35 dependent compressions leaves the chip to the decoding below, and the digests are
+            // down and the root hashed while that runs.  (A call that goes on to use r has waited for `leaves` on the host: its work on
+            // leaf_st is over before the arena is touched again.)
+            uint8_t* d_leaf = db + L.off_leaf;
+            HIPCK(hipEventRecord(uploaded, st));
+            HIPCK(hipStreamWaitEvent(leaf_st, uploaded, 0));
+            launch::sha256_cell_leaves(n, db + L.off_c, (const int*)(db + L.off_row), (const int*)(db + L.off_idx), db + L.off_p, db + L.off_cells, d_leaf, leaf_st);
+            HIPCK(hipMemcpyAsync(hb + L.off_hleaf, d_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, leaf_st));
+            HIPCK(hipEventRecord(leaves, leaf_st));
+        }
         // deserialisation with on-curve + subgroup checks (serialization/src/lib.rs:69-99), on the GPU
         const uint8_t *d_cb = db + L.off_c, *d_pb = db + L.off_p, *d_cellb = db + L.off_cells;
         G1Affine *d_prf_p = d_proofs_aff(), *d_comm_p = d_commitments_aff();
@@ -184,14 +205,27 @@ struct CellPass {
 
     // ---- the Fiat-Shamir challenge, hashed straight from the caller's buffers while the GPU decompresses.  The transcript always
     // covers the whole batch (n_all cells), whatever the shard.
-    Fr challenge(int n_all) const {
+    Fr challenge(int n_all, uint8_t* digest_out) const {
         CellBatchTranscript t(L.m, n_all, uniq);
         int chunks_in = 0;  // (device-resident form) chunks of the cells' host mirror that have arrived
         for (int k = 0; k < n_all; k++) {
             while (chunks_in < n_chunks && k >= chunks_in * chunk_cells) HIPCK(hipEventSynchronize(chunk_events[chunks_in++]));
             t.absorb(row[k], cell_indices[k], cells[k], proofs[k]);
         }
-        return t.finish();
+        const Fr r = t.finish();
+        if (digest_out) memcpy(digest_out, t.digest(), 32);
+        return r;
+    }
+    // ---- the leaf-hashed challenge (the whole batch is this pass: L.n cells): the root over the leaf digests the GPU hashed.  Called
+    // once stage_and_decode has returned (the event is recorded); the decoding kernels are still running.
+    Fr challenge_leaf(uint8_t* digest_out, uint8_t* leaves_out) const {
+        HIPCK(hipEventSynchronize(leaves));
+        const uint8_t* dig = hb + L.off_hleaf;
+        CellLeafTranscript t;
+        const Fr r = t.root((uint64_t)L.n, dig);
+        if (digest_out) memcpy(digest_out, t.digest(), 32);
+        if (leaves_out) memcpy(leaves_out, dig, (size_t)L.n * 32);
+        return r;
     }
 
     // ---- what the decoding found, in the order of the reference: commitments, proofs, cells
@@ -247,11 +281,13 @@ struct CellPass {
 int Engine::verify_cells_partial(uint64_t n_commitments, const uint8_t* const* commitments, uint64_t n_indices,
                                  const uint64_t* cell_indices, uint64_t n_cells, const uint8_t* const* cells,
                                  uint64_t n_proofs, const uint8_t* const* proofs, uint64_t lo, uint64_t hi,
-                                 G1Affine* out, bool* empty, const VerifyDeviceSource* dsrc, VerifyScratch* vs) {
+                                 G1Affine* out, bool* empty, const VerifyDeviceSource* dsrc, VerifyScratch* vs, const CellChallengeMode* mode) {
+    const bool leaf = mode && mode->leaf;
     *empty = false;
     out[0] = out[1] = aff_inf();
     if (validate_cell_batch(n_commitments, n_indices, n_cells, n_proofs, cell_indices) != OK) return ERR_INPUT;
     if (lo > hi || hi > n_cells) return ERR_INPUT;
+    if (leaf && (lo != 0 || hi != n_cells || vs)) return ERR_INPUT;  // the leaf-hashed challenge is for whole batches under mu_ (the sharded forms keep the reference's)
     const int n_all = (int)n_cells;
     if (n_all == 0) { *empty = true; return OK; }  // verifier.rs:90-93
     if (lo == hi) return OK;                       // an empty shard contributes the identity twice
@@ -265,7 +301,7 @@ int Engine::verify_cells_partial(uint64_t n_commitments, const uint8_t* const* c
         HIPCK(hipSetDevice(dev_));
         hipStream_t st = vs ? vs->stream : stream_;
         const int n = (int)(hi - lo);
-        const Layout L(n, (int)uniq.size(), n >= pip_shift_min_);
+        const Layout L(n, (int)uniq.size(), n >= pip_shift_min_, leaf);
         grow_device(vs ? vs->dev : v_dev_, vs ? vs->dev_cap : v_dev_cap_, L.dev_bytes, st);  // (no per-call hipMalloc)
         grow_pinned(vs ? vs->pin : v_pin_, vs ? vs->pin_cap : v_pin_cap_, L.pin_bytes);
         CellPass pass(L);
@@ -278,7 +314,8 @@ int Engine::verify_cells_partial(uint64_t n_commitments, const uint8_t* const* c
         }
         pass.d_srs = d_srs_; pass.d_w8192 = d_w8192_; pass.beta = beta_; pass.inv64 = inv64_;
         if (v_two_streams_ && !vs) pass.side = v_side_;
-        pass.decoded = v_decoded_; pass.checked = v_checked_;
+        pass.decoded = v_decoded_; pass.checked = v_checked_; pass.leaves = v_leaves_;
+        pass.leaf_st = v_leaf_stream_; pass.uploaded = v_uploaded_;
         // (a worker of the engine's small persistent pool: starting and joining a fresh thread per call was 50-100 us of a 3.3 ms call)
         std::call_once(stage_pool_once_, [this] { stage_pool_.reset(new HostPool(primary_ ? 1 : 4, [d = dev_] { (void)hipSetDevice(d); })); });
         StageDone staged;
@@ -291,12 +328,22 @@ int Engine::verify_cells_partial(uint64_t n_commitments, const uint8_t* const* c
             }
         });
         struct Joiner { StageDone& s; ~Joiner() { s.wait(); } } joiner{staged};  // whatever happens below, the task has left this frame first
-        const Fr r = pass.challenge(n_all);
-        lap("sha256 transcript (host)");
-        staged.wait();
-        if (staged.error) std::rethrow_exception(staged.error);
+        Fr r;
+        if (leaf) {
+            staged.wait();
+            if (staged.error) std::rethrow_exception(staged.error);
+            lap("stage + enqueue (host)");
+            r = pass.challenge_leaf(mode->digest_out, mode->leaves_out);
+            lap("leaf hashes (GPU) + root (host)");
+        } else {
+            r = pass.challenge(n_all, mode ? mode->digest_out : nullptr);
+            lap("sha256 transcript (host)");
+            staged.wait();
+            if (staged.error) std::rethrow_exception(staged.error);
+        }
         SYNC_CHECKED(st);
         lap("wait decompress/deserialise");
+        if (leaf && mode->leaves_out) return OK;  // (the stage hook of the leaf kernel: the digests are what it asked for)
         if (const int verdict = pass.read_verdicts()) return verdict;
         pass.scalars_and_lincombs(r, out);
         lap("scalars+interp+lincombs (GPU)");
@@ -348,15 +395,18 @@ bool Engine::verify_cells_pairing_split(const G1Affine* pts) {
 // config 3's 17.6 MB, the floor of this call): commitments, indices and proofs first (0.9 MB; the host de-duplicates the
 // commitments), then the cells in eight chunks that the hash consumes as they land (PCIe delivers 20x faster than it reads).
 // Round 3 copied everything down, gathered it on the host and uploaded it again.
+// With the leaf-hashed challenge (mode->leaf) that floor is gone: the leaves are hashed in HBM and neither cells nor proofs come down
+// (verify_cells_partial_device: its first branch).
 int Engine::verify_cell_kzg_proof_batch_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices,
-                                               const uint8_t* d_cells, const uint8_t* d_proofs, int* verified, hipStream_t user_stream) {
+                                               const uint8_t* d_cells, const uint8_t* d_proofs, int* verified, hipStream_t user_stream,
+                                               const CellChallengeMode* mode) {
     *verified = 0;
     if (n == 0) { *verified = 1; return OK; }  // verifier.rs:90-93
     if (n > MAX_CELLS_PER_VERIFICATION) return ERR_INPUT;
     std::lock_guard<std::recursive_mutex> lk(mu_);  // the pinned mirror is the context's (grow-only, reused by every call)
     G1Affine pts[2];
     bool empty = false;
-    const int rc = verify_cells_partial_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, 0, n, pts, &empty, user_stream);
+    const int rc = verify_cells_partial_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, 0, n, pts, &empty, user_stream, mode);
     if (rc) return rc;
     *verified = (empty || verify_cells_pairing_split(pts)) ? 1 : 0;
     return OK;
@@ -365,8 +415,34 @@ int Engine::verify_cell_kzg_proof_batch_device(uint64_t n, const uint8_t* d_comm
 // 1 <= n <= MAX_CELLS_PER_VERIFICATION; the two partial points of the cells [lo, hi) as verify_cells_partial leaves them.
 // The caller holds mu_ (the product call above through its pairing check; the test hook for the call).
 int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
-                                        const uint8_t* d_proofs, uint64_t lo, uint64_t hi, G1Affine* pts, bool* empty, hipStream_t user_stream) {
+                                        const uint8_t* d_proofs, uint64_t lo, uint64_t hi, G1Affine* pts, bool* empty, hipStream_t user_stream,
+                                        const CellChallengeMode* mode) {
     int rc = OK;
+    if (mode && mode->leaf) {
+        // Leaf-hashed challenge: nothing the hash reads has to come down.  Commitments and indices do (0.5 MB for 8192 cells), for
+        // validation and de-duplication; the proofs and the cells are hashed, cell by cell, where the device-to-device copy puts them.
+        try {
+            std::vector<const uint8_t*> cp(n);
+            HIPCK(hipSetDevice(dev_));
+            const size_t sz_c = n * 48, sz_i = n * sizeof(uint64_t);
+            grow_pinned(vd_pin_, vd_pin_cap_, sz_c + sz_i);
+            uint8_t *pin_c = vd_pin_, *pin_i = vd_pin_ + sz_c;
+            hipStream_t st = stream_;
+            if (user_stream != st) {
+                HIPCK(hipEventRecord(v_decoded_, user_stream));
+                HIPCK(hipStreamWaitEvent(st, v_decoded_, 0));
+            }
+            HIPCK(hipMemcpyAsync(pin_c, d_commitments, sz_c, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(pin_i, d_cell_indices, sz_i, hipMemcpyDeviceToHost, st));
+            HIPCK(hipStreamSynchronize(st));
+            for (uint64_t k = 0; k < n; k++) cp[k] = pin_c + k * 48;
+            const VerifyDeviceSource src{d_cells, d_proofs, nullptr, 0, 0};
+            return verify_cells_partial(n, cp.data(), n, reinterpret_cast<const uint64_t*>(pin_i), n, nullptr, n, nullptr, lo, hi, pts, empty, &src, nullptr, mode);
+        } catch (const std::exception& e) {
+            set_error(e);
+            return ERR_DEVICE;
+        }
+    }
     try {
         std::vector<const uint8_t*> cp(n), lp(n), pp(n);  // inside the try: a bogus n must not unwind through the C ABI
         HIPCK(hipSetDevice(dev_));
@@ -399,7 +475,7 @@ int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments
             pp[k] = pin_p + k * 48;
         }
         const VerifyDeviceSource src{d_cells, d_proofs, vd_events_, chunk_cells, n_chunks};
-        rc = verify_cells_partial(n, cp.data(), n, reinterpret_cast<const uint64_t*>(pin_i), n, lp.data(), n, pp.data(), lo, hi, pts, empty, &src);
+        rc = verify_cells_partial(n, cp.data(), n, reinterpret_cast<const uint64_t*>(pin_i), n, lp.data(), n, pp.data(), lo, hi, pts, empty, &src, nullptr, mode);
         if (rc != OK || lo == hi) (void)hipStreamSynchronize(st);  // (an early return, error or empty range: the copies into the mirror must not outlive the call)
     } catch (const std::exception& e) {
         set_error(e);
@@ -410,12 +486,12 @@ int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments
 
 int Engine::verify_cell_kzg_proof_batch_host(uint64_t n_commitments, const uint8_t* const* commitments, uint64_t n_indices,
                                              const uint64_t* cell_indices, uint64_t n_cells, const uint8_t* const* cells,
-                                             uint64_t n_proofs, const uint8_t* const* proofs, int* verified) {
+                                             uint64_t n_proofs, const uint8_t* const* proofs, int* verified, const CellChallengeMode* mode) {
     *verified = 0;
     G1Affine pts[2];
     bool empty = false;
     int st = verify_cells_partial(n_commitments, commitments, n_indices, cell_indices, n_cells, cells, n_proofs, proofs, 0,
-                                  n_cells, pts, &empty);
+                                  n_cells, pts, &empty, nullptr, nullptr, mode);
     if (st) return st;
     TraceLap lap{knobs_.trace, "verify"};
     *verified = (empty || verify_cells_pairing_split(pts)) ? 1 : 0;

@@ -1,6 +1,7 @@
 // The host's share of verification and recovery that is pure computation over bytes: input validation, de-duplication, the scalar
-// codecs and the four Fiat-Shamir transcripts, each stated ONCE for verify.hip, verify_many.hip, eip4844.hip and recover.hip.
-// No HIP call in here, everything inline: tests/c/test_verify_host.cpp runs it on the CPU against hashlib.
+// codecs and the Fiat-Shamir transcripts (the reference's four and the leaf-hashed challenge of the cell verifier), each stated ONCE
+// for verify.hip, verify_many.hip, eip4844.hip and recover.hip.
+// No HIP call in here, everything inline: tests/c/test_verify_host.cpp and test_leaf_transcript.cpp run it on the CPU against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -114,6 +115,54 @@ private:
     Sha256 sh_;
     uint8_t digest_[32];
 };
+
+// ---- the leaf-hashed challenge of the cell verifier (ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT; the reference has nothing like it).
+// The transcript above is ONE SHA-256 over every byte of the batch: serial by construction, 7.2 ms of a host core for 8192 cells.
+// Only the verdict crosses the ABI, never r, so a challenge that binds the same bytes through a two-level hash serves as well:
+//   LEAF_k = SHA-256("RCKZGCBATCHLEAF1" | be64(k) | be64(cell_indices[k]) | commitments[k] | proofs[k] | cells[k])      2176 bytes
+//   ROOT   = SHA-256("RCKZGCBATCHROOT1" | be64(4096) | be64(64) | be64(n) | LEAF_0 | .. | LEAF_{n-1})
+//   r      = fr_from_digest(ROOT)
+// k is the position in the caller's list and commitments[k] the caller's 48 bytes of entry k (no de-duplication).  A leaf is 34
+// blocks: the header is exactly two, every 64-byte row of the cell is one, and the 35th compression is constant padding (0x80,
+// zeroes, the bit length 17408).  The leaves are independent, one lane each on the GPU (k_sha256.hip: k_sha256_cell_leaves); this
+// class is the host's statement of them and of the root, which the host hashes from the n x 32 digest bytes that come down.
+// Soundness.  r is a hash of every input byte: the leaves bind the contents, the root binds their order and number, and two
+// batches with one r are a SHA-256 collision (in a leaf, or in the root).  The batch equation is the reference's: a batch that
+// holds a wrong proof passes only if r is a root of a non-zero polynomial of degree below n over Fr -- the argument of the
+// reference's own challenge, which asks of the hash nothing else.  Valid batches verify under any r, and whether a call is Err or
+// Ok(false) is decided by validation and decoding, before r is used.
+// Out of scope: _partial / _combine, _many and the combiner of concurrent single calls keep the reference's transcript; no
+// environment knob moves the reference's own symbol onto this one; the Node binding does not pass the flag.
+class CellLeafTranscript {
+public:
+    static constexpr size_t LEAF_BYTES = 16 + 8 + 8 + 48 + 48 + BYTES_PER_CELL;  // 2176 = 34 blocks
+    static void leaf(uint64_t k, uint64_t index, const uint8_t* commitment, const uint8_t* proof, const uint8_t* cell, uint8_t out[32]) {
+        uint8_t hdr[128];
+        memcpy(hdr, "RCKZGCBATCHLEAF1", 16);
+        be64(k, hdr + 16); be64(index, hdr + 24);
+        memcpy(hdr + 32, commitment, 48);
+        memcpy(hdr + 80, proof, 48);
+        Sha256 sh;
+        sh.update(hdr, sizeof hdr);
+        sh.update(cell, BYTES_PER_CELL);
+        sh.finish(out);
+    }
+    // leaves: the n digests in the caller's order, 32 bytes each -> the challenge r, Montgomery
+    Fr root(uint64_t n, const uint8_t* leaves) {
+        uint8_t hdr[16 + 24];
+        memcpy(hdr, "RCKZGCBATCHROOT1", 16);
+        be64(N_BLOB, hdr + 16); be64(CELL_LEN, hdr + 24); be64(n, hdr + 32);
+        Sha256 sh;
+        sh.update(hdr, sizeof hdr);
+        sh.update(leaves, (size_t)n * 32);
+        sh.finish(digest_);
+        return fr_from_digest(digest_);
+    }
+    const uint8_t* digest() const { return digest_; }  // after root(): the 32 bytes r was reduced from
+private:
+    uint8_t digest_[32];
+};
+static_assert(CellLeafTranscript::LEAF_BYTES == 34 * 64, "the header is two blocks and the cell thirty-two");
 
 // ---- compute_fiat_shamir_challenge of EIP-4844 (eip4844/src/verifier.rs:155-196): H(header | blob | commitment) mod r
 inline void blob_challenge_header(uint8_t hdr[32]) {
