@@ -348,9 +348,9 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device(const DASContext *ctx, ui
  *                                                de-duplication), and the n * 32 digest bytes
  *   any other bit                                Err("InvalidInput..."), returned with the count checks, before the context is touched
  * On a device-list context the host form routes like any single-problem call, the device form by the owner of the pointers.
- * Not covered: eth_kzg_amd_verify_cell_kzg_proof_batch_partial / _combine, _many and the combining of concurrent calls of
+ * Not covered: eth_kzg_amd_verify_cell_kzg_proof_batch_partial / _combine and the combining of concurrent calls of
  * eth_kzg_verify_cell_kzg_proof_batch keep the reference's transcript; no environment setting moves the reference's own symbol
- * onto this challenge.  When the flag pays: INTEGRATION.md. */
+ * onto this challenge.  The many-verification takes the flag through its own _ex calls, below.  When the flag pays: INTEGRATION.md. */
 #define ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT 1u
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_ex(const DASContext *ctx, uint64_t commitments_length,
                                                    const uint8_t *const *commitments, uint64_t cell_indices_length,
@@ -361,6 +361,51 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(const DASContext *ctx,
                                                           const uint64_t *d_cell_indices, const uint8_t *d_cells,
                                                           const uint8_t *d_proofs, uint32_t flags, bool *verified,
                                                           void *hip_stream);
+
+/* ---- the many-verification with a flags word, and on flat arrays in HBM ----
+ * eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex: eth_kzg_amd_verify_cell_kzg_proof_batch_many with a flags word: 0 = exactly that
+ * call; ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT = every problem's challenge is the leaf-hashed one.
+ * eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex: the same on flat arrays in this GPU's HBM.  cell_starts: HOST,
+ * n_batches + 1 entries, cell_starts[0] = 0, non-decreasing; problem b is the entries [cell_starts[b], cell_starts[b+1]) of the four
+ * arrays; N = cell_starts[n_batches].  d_commitments N*48 (one per cell, NOT de-duplicated, as in the single device form),
+ * d_cell_indices N uint64, d_cells N*2048, d_proofs N*48.  Any byte address for the byte arrays.  verified / status: HOST, n_batches
+ * entries (status may be NULL).  Synchronous; work already queued on hip_stream (NULL: the default stream) that produces the inputs is
+ * waited for.
+ * The challenge of a problem under the flag is exactly what eth_kzg_amd_verify_cell_kzg_proof_batch_ex would take for that problem
+ * alone: k in LEAF_k is the position INSIDE the problem (it restarts at 0 in each one), ROOT carries the problem's own n,
+ * commitments[k] are the caller's 48 bytes; there are no new domain strings.  All the leaves of a pass are hashed in one launch, one
+ * lane per cell; the host hashes one ROOT per problem.  The folding weights that let one pairing check stand for a whole pass keep
+ * their form (SHA-256 under "RCKZGCBATCHFOLD1" over the problems' digests, then per problem); under the flag the digests are the
+ * problems' ROOTs in the place of the reference transcript's digests, and a problem that is empty or refused at validation contributes
+ * 32 zero bytes, as before.  The soundness paragraph above carries over: every ROOT is a hash of every input byte of its problem, so
+ * the weights still hang on every input byte of the pass and are fixed only after all of them.
+ * Verdicts and statuses: per problem status 0 / 1 / 2 / 3 in the reference's error order (commitments, proofs, cells) and verified,
+ * exactly as _many; whether a problem is refused, false or true does not depend on the flag; an empty problem verifies.  In the device
+ * form the four lengths of a problem are one by construction, so status 3 is left for an index >= 128 or more than 2^24 - 1 cells.
+ * Err("InvalidInput...") for the call, checked before the context is touched: a bit other than the leaf flag; n_batches > 2^24; a
+ * malformed cell_starts (NULL with n_batches > 0, a first entry that is not 0, a decreasing entry).  n_batches = 0 is Ok.
+ *   device form, flags = 0      the reference's challenges: the pass copies its proofs and cells down into pinned memory and hashes them
+ *                               on the host threads as the host form does.  Correct, and the slow way: it is there so that the flag
+ *                               means the same in every _ex call and so that the resident pass can be compared with the host pass
+ *                               byte for byte, not for speed.
+ *   device form, leaf flag      neither cells nor proofs cross the link: the commitments and indices come down for validation and
+ *                               de-duplication (56 bytes per cell), then the n * 32 leaf digests, the status words and the sums.
+ * Device lists: the host form is cut by problem over the listed devices, exactly as _many; the device form runs on the device that owns
+ * the buffers, and all four device pointers are resolved: Err("InvalidInput...") unless they are device memory of one listed device.
+ * Out of scope: _partial / _combine keep the reference's transcript; so does the combiner of concurrent
+ * eth_kzg_verify_cell_kzg_proof_batch callers; the Node binding is not extended; no environment setting moves the unflagged calls;
+ * the caller's cells are not read in place -- the pass copies them device-to-device into its arena, as the single resident form does
+ * (2 KB per cell at HBM speed, against milliseconds of pass).  Measured figures: INTEGRATION.md. */
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex(const DASContext *ctx, uint64_t n_batches,
+                                                        const uint64_t *commitments_lengths, const uint8_t *const *const *commitments,
+                                                        const uint64_t *cell_indices_lengths, const uint64_t *const *cell_indices,
+                                                        const uint64_t *cells_lengths, const uint8_t *const *const *cells,
+                                                        const uint64_t *proofs_lengths, const uint8_t *const *const *proofs,
+                                                        uint32_t flags, bool *verified, int32_t *status);
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext *ctx, uint64_t n_batches, const uint64_t *cell_starts,
+                                                               const uint8_t *d_commitments, const uint64_t *d_cell_indices,
+                                                               const uint8_t *d_cells, const uint8_t *d_proofs, uint32_t flags,
+                                                               bool *verified, int32_t *status, void *hip_stream);
 
 /* Introspection used by bench.py / DESIGN.md: bytes of both window tables resident in HBM; nominal window width w of the FK20
  * table in use (a GLV table: ceil(128 / w) windows over the two 128-bit halves of each scalar, packed 96-byte entries: 16

@@ -130,6 +130,28 @@ int eth_kzg_amd_test_verify_many_sums(const DASContext *ctx, uint64_t n_batches,
                                       int32_t *form4, uint8_t *sums96, uint32_t *rho, uint8_t *fold96, int32_t *probe_ranges,
                                       uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes);
 
+/* The same pass over either source and with either challenge (c_eth_kzg.h: eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex /
+ * _many_device_ex; tests/test_gpu_many_leaf.py, the statement is tests/many_leaf.py).  _ex: the pointer lists of the public call;
+ * _device: flat arrays in device memory plus cell_starts (host, n_batches + 1 entries), as the public device form takes them, on the
+ * context's first device.  flags: 0 or ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT.  Every output of eth_kzg_amd_test_verify_many_sums, and
+ *   digests32[B][32]: the 32 bytes each problem's challenge was reduced from -- the reference transcript's digest, or the problem's
+ *     ROOT under the flag; zero for a problem that was not hashed (empty, or refused at validation).  These are what the fold seed hashes.
+ *   leaves32[N][32] (may be NULL; written under the flag only): LEAF_k of every cell in the caller's order, N = all cells of the call;
+ *     zero for the cells of a problem that was refused at validation.
+ * The same rules: one pass only (3 before any launch if the call would be cut, for a NULL buffer, an unknown flag or a malformed
+ * cell_starts), and nothing is added on the device: the tap copies the read-backs the pass makes anyway. */
+int eth_kzg_amd_test_verify_many_sums_ex(const DASContext *ctx, uint64_t n_batches, const uint64_t *commitments_lengths,
+                                         const uint8_t *const *const *commitments, const uint64_t *cell_indices_lengths,
+                                         const uint64_t *const *cell_indices, const uint64_t *cells_lengths, const uint8_t *const *const *cells,
+                                         const uint64_t *proofs_lengths, const uint8_t *const *const *proofs, uint32_t flags, int32_t *verified,
+                                         int32_t *status, int32_t *form4, uint8_t *sums96, uint32_t *rho, uint8_t *fold96, int32_t *probe_ranges,
+                                         uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes, uint8_t *digests32, uint8_t *leaves32);
+int eth_kzg_amd_test_verify_many_sums_device(const DASContext *ctx, uint64_t n_batches, const uint64_t *cell_starts, const uint8_t *d_commitments,
+                                             const uint64_t *d_cell_indices, const uint8_t *d_cells, const uint8_t *d_proofs, uint32_t flags,
+                                             int32_t *verified, int32_t *status, int32_t *form4, uint8_t *sums96, uint32_t *rho, uint8_t *fold96,
+                                             int32_t *probe_ranges, uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes,
+                                             uint8_t *digests32, uint8_t *leaves32);
+
 /* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode in recover.hip, exactly the launches recovery runs).  R >= 1 blobs; blob r has
  * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
  * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat

@@ -45,7 +45,7 @@ SETUP_NO_SUBGROUP_CHECK = 1
 SETUP_CHECK_POWERS = 2
 SETUP_G1_POINTS = 4096
 SETUP_G2_POINTS = 65
-# flags of eth_kzg_amd_verify_cell_kzg_proof_batch_ex / _device_ex
+# flags of eth_kzg_amd_verify_cell_kzg_proof_batch_ex / _device_ex / _many_ex / _many_device_ex
 VERIFY_LEAF_TRANSCRIPT = 1
 
 EXPORTED_SYMBOLS = [
@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_compute_cells_and_kzg_proofs_device", "eth_kzg_amd_blob_to_kzg_commitment_device",
     "eth_kzg_amd_verify_cell_kzg_proof_batch_device", "eth_kzg_amd_verify_cell_kzg_proof_batch_many",
     "eth_kzg_amd_verify_cell_kzg_proof_batch_ex", "eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex",
+    "eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex", "eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex",
     "eth_kzg_amd_compute_blob_kzg_proof_batch", "eth_kzg_amd_compute_kzg_proof_batch",
     "eth_kzg_amd_compute_blob_kzg_proof_device", "eth_kzg_amd_compute_kzg_proof_device",
     "eth_kzg_amd_verify_blob_kzg_proof_batch_device",
@@ -84,6 +85,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_prover_scalars", "eth_kzg_amd_test_verify_many_sums",
     "eth_kzg_amd_test_proofs_from_sums", "eth_kzg_amd_test_linmap_program",
     "eth_kzg_amd_test_cell_leaf_digests", "eth_kzg_amd_test_verify_cells_inputs_ex",
+    "eth_kzg_amd_test_verify_many_sums_ex", "eth_kzg_amd_test_verify_many_sums_device",
 ]
 
 _lib = None
@@ -180,6 +182,8 @@ def load_library():
     for name, args in {
         "eth_kzg_amd_verify_cell_kzg_proof_batch_ex": [P, U64, P, U64, P, U64, P, U64, P, C.c_uint32, P],
         "eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex": [P, U64, P, P, P, P, C.c_uint32, P, P],
+        "eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex": [P, U64, P, P, P, P, P, P, P, P, C.c_uint32, P, P],
+        "eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P],
     }.items():
         if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
             getattr(lib, name).restype = CResult
@@ -212,6 +216,8 @@ def load_library():
         "eth_kzg_amd_test_linmap_program": [P, C.c_int, P, U64, P, P, U64, P, P, P, U64, P],
         "eth_kzg_amd_test_cell_leaf_digests": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_test_verify_cells_inputs_ex": [P, U64, C.c_int, P, P, P, P, C.c_uint32, P, P],
+        "eth_kzg_amd_test_verify_many_sums_ex": [P, U64, P, P, P, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
+        "eth_kzg_amd_test_verify_many_sums_device": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -521,19 +527,25 @@ class DASContext:
             return bool(ok.value)
         return run
 
-    def prepare_verify_cell_kzg_proof_batch_many(self, problems):
+    def prepare_verify_cell_kzg_proof_batch_many(self, problems, leaf_transcript=False):
         """problems = [(commitments, cell_indices, cells, proofs), ...]: marshal them into the pointer tables of
         eth_kzg_amd_verify_cell_kzg_proof_batch_many ONCE and return a zero-argument callable that runs the call and
         returns (verified list[bool], status list[int]) -- status 0 ok, 1 bad field element, 2 bad G1 point, 3 invalid
-        lengths / indices: what the single form raises as KzgError."""
+        lengths / indices: what the single form raises as KzgError.  leaf_transcript=True: eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex
+        with ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT -- every problem's challenge is hashed per cell on the GPU (same verdicts and statuses)."""
         nb, lens, tabs, keep = self._marshal_many(problems)
         ver = (C.c_bool * max(1, nb))()
         st = (C.c_int32 * max(1, nb))()
 
         def run(_keep=keep):
-            self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_many(
-                self._ctx, nb, _vp(lens[0]), _vp(tabs[0]), _vp(lens[1]), _vp(tabs[1]), _vp(lens[2]), _vp(tabs[2]), _vp(lens[3]), _vp(tabs[3]),
-                ver, st))
+            if leaf_transcript:
+                self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex(
+                    self._ctx, nb, _vp(lens[0]), _vp(tabs[0]), _vp(lens[1]), _vp(tabs[1]), _vp(lens[2]), _vp(tabs[2]), _vp(lens[3]), _vp(tabs[3]),
+                    VERIFY_LEAF_TRANSCRIPT, ver, st))
+            else:
+                self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_many(
+                    self._ctx, nb, _vp(lens[0]), _vp(tabs[0]), _vp(lens[1]), _vp(tabs[1]), _vp(lens[2]), _vp(tabs[2]), _vp(lens[3]), _vp(tabs[3]),
+                    ver, st))
             return [bool(v) for v in ver][:nb], list(st)[:nb]
         return run
 
@@ -559,9 +571,25 @@ class DASContext:
             tabs[0][b], tabs[1][b], tabs[2][b], tabs[3][b] = ca.ctypes.data, idx.ctypes.data, cla.ctypes.data, pa.ctypes.data
         return nb, np.ascontiguousarray(lens), tabs, keep
 
-    def verify_cell_kzg_proof_batch_many(self, problems):
+    def verify_cell_kzg_proof_batch_many(self, problems, leaf_transcript=False):
         """Many independent verify_cell_kzg_proof_batch problems in one call (see prepare_verify_cell_kzg_proof_batch_many)."""
-        return self.prepare_verify_cell_kzg_proof_batch_many(problems)()
+        return self.prepare_verify_cell_kzg_proof_batch_many(problems, leaf_transcript)()
+
+    def verify_cell_kzg_proof_batch_many_device(self, cell_starts, d_commitments, d_cell_indices, d_cells, d_proofs, stream=None,
+                                                leaf_transcript=False):
+        """The many-verification on flat arrays in device memory (eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex): cell_starts is a
+        host sequence of n_batches + 1 non-decreasing entries starting at 0, problem b the entries [cell_starts[b], cell_starts[b + 1]) of
+        the four arrays (integer device addresses: N*48 commitment bytes, one per cell; N uint64 indices; N*2048 cell bytes; N*48 proof
+        bytes).  -> (verified list[bool], status list[int]).  leaf_transcript=True: neither cells nor proofs are copied to the host;
+        False: the reference's challenges, for which they are (the slow way)."""
+        cs = np.ascontiguousarray(np.array(cell_starts, dtype=np.uint64))
+        nb = max(0, len(cs) - 1)
+        ver = (C.c_bool * max(1, nb))()
+        st = (C.c_int32 * max(1, nb))()
+        self._check(self._lib.eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(
+            self._ctx, nb, _vp(cs) if len(cs) else None, C.c_void_p(d_commitments), C.c_void_p(d_cell_indices), C.c_void_p(d_cells),
+            C.c_void_p(d_proofs), VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st, C.c_void_p(stream) if stream else None))
+        return [bool(v) for v in ver][:nb], list(st)[:nb]
 
     def verify_cell_kzg_proof_batch_partial(self, commitments, cell_indices, cells, proofs, shard_begin, shard_end):
         """This rank's share of a sharded verification: the whole batch goes in (the challenge hashes all of it), the

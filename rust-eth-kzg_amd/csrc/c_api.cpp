@@ -8,6 +8,7 @@
 // -- and a one-device context takes none of these paths.
 #include "../../include/c_eth_kzg.h"
 #include "c_ctx.hpp"
+#include "verify_host.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -73,6 +74,20 @@ kzg::Engine* engine_of_pointer(const DASContext* ctx, const void* p) {
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     for (kzg::Engine* e : ctx->engines)
         if (e->device() == a.device) return e;
+    return nullptr;
+}
+// the engine on whose GPU all of the pointers lie as device memory; NULL: they do not, or not on a device of this context
+kzg::Engine* engine_of_device_pointers(const DASContext* ctx, const void* const* ptrs, int n_ptrs) {
+    int dev = -1;
+    for (int i = 0; i < n_ptrs; i++) {
+        hipPointerAttribute_t a;
+        if (!ptrs[i] || hipPointerGetAttributes(&a, ptrs[i]) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        if (a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged) return nullptr;
+        if (i && a.device != dev) return nullptr;
+        dev = a.device;
+    }
+    for (kzg::Engine* e : ctx->engines)
+        if (e->device() == dev) return e;
     return nullptr;
 }
 CResult slices_result(const DASContext* ctx, const std::pair<int, std::string>& r) {
@@ -387,6 +402,76 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(const DASContext* ctx,
     if (st) return err(status_text(st));
     *verified = ver != 0;
     return ok();
+}
+
+// The many-verification with a flags word, on pointer lists and on flat arrays in HBM (c_eth_kzg.h).  Flags, counts and cell_starts are
+// checked before the context is looked at.  The host form is cut by problem over the device list, as _many; the device form runs on the
+// device that owns the buffers, and for it ALL FOUR pointers are resolved: a pointer that is not device memory of one listed device is
+// InvalidInput, never a fault (none of them is dereferenced on the host).
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths,
+                                                        const uint8_t* const* const* commitments, const uint64_t* cell_indices_lengths,
+                                                        const uint64_t* const* cell_indices, const uint64_t* cells_lengths,
+                                                        const uint8_t* const* const* cells, const uint64_t* proofs_lengths,
+                                                        const uint8_t* const* const* proofs, uint32_t flags, bool* verified, int32_t* status) {
+    if (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) return err("InvalidInput: unknown verification flags");
+    if (n_batches > MAX_BATCH) return err("InvalidInput");
+    if (!flags)
+        return eth_kzg_amd_verify_cell_kzg_proof_batch_many(ctx, n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices,
+                                                            cells_lengths, cells, proofs_lengths, proofs, verified, status);
+    live(ctx);
+    if (n_batches == 0) return ok();
+    try {
+        std::vector<int> ver(n_batches), st(n_batches);
+        kzg::VerifyManyInput in;
+        in.n_commitments = commitments_lengths; in.n_indices = cell_indices_lengths; in.n_cells = cells_lengths; in.n_proofs = proofs_lengths;
+        in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
+        in.leaf = true;
+        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n_batches, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
+            kzg::Engine* e = ctx->engines[(size_t)d];
+            const int rc = e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver.data() + lo, st.data() + lo);
+            return rc == kzg::ERR_DEVICE ? device_text(e) : std::string();
+        });
+        if (r.first >= 0) return slices_result(ctx, r);
+        for (uint64_t b = 0; b < n_batches; b++) {
+            verified[b] = st[b] == 0 && ver[b] != 0;
+            if (status) status[b] = st[b];
+        }
+        return ok();
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext* ctx, uint64_t n_batches, const uint64_t* cell_starts,
+                                                               const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
+                                                               const uint8_t* d_proofs, uint32_t flags, bool* verified, int32_t* status,
+                                                               void* hip_stream) {
+    if (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) return err("InvalidInput: unknown verification flags");
+    if (n_batches > MAX_BATCH) return err("InvalidInput");
+    if (kzg::validate_cell_starts(n_batches, cell_starts) != kzg::INPUT_VALID)
+        return err("InvalidInput: cell_starts holds n_batches + 1 non-decreasing entries, the first of them 0");
+    live(ctx);
+    if (n_batches == 0) return ok();
+    kzg::Engine* e = ctx->engine;
+    if (cell_starts[n_batches]) {  // (a call of empty problems only reads none of the arrays)
+        const void* const ptrs[4] = {d_commitments, d_cell_indices, d_cells, d_proofs};
+        e = engine_of_device_pointers(ctx, ptrs, 4);
+        if (!e) return err("InvalidInput: the four buffers are not device memory of one device of this context");
+    }
+    try {
+        std::vector<int> ver(n_batches), st(n_batches);
+        kzg::VerifyManyInput in;
+        in.cell_starts = cell_starts; in.d_commitments = d_commitments; in.d_cell_indices = d_cell_indices; in.d_cells = d_cells; in.d_proofs = d_proofs;
+        in.user_stream = (hipStream_t)hip_stream;
+        in.leaf = flags != 0;
+        if (e->verify_cell_kzg_proof_batch_many(n_batches, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
+        for (uint64_t b = 0; b < n_batches; b++) {
+            verified[b] = st[b] == 0 && ver[b] != 0;
+            if (status) status[b] = st[b];
+        }
+        return ok();
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
 }
 
 CResult eth_kzg_amd_recover_cells_and_proofs_device(const DASContext* ctx, uint64_t n, const uint8_t* d_cells,

@@ -3,6 +3,7 @@
 #include "../../include/c_eth_kzg_test_hooks.h"
 #include "c_ctx.hpp"
 #include "launch.hpp"
+#include "verify_host.hpp"
 
 #include <algorithm>
 #include <array>
@@ -106,6 +107,40 @@ int eth_kzg_amd_test_verify_many_sums(const DASContext* ctx, uint64_t n_batches,
     return eng(ctx)->test_verify_many_sums(n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells,
                                            proofs_lengths, proofs, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes,
                                            n_probes);
+}
+// the same pass over either source and with either challenge
+int eth_kzg_amd_test_verify_many_sums_ex(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths,
+                                         const uint8_t* const* const* commitments, const uint64_t* cell_indices_lengths,
+                                         const uint64_t* const* cell_indices, const uint64_t* cells_lengths, const uint8_t* const* const* cells,
+                                         const uint64_t* proofs_lengths, const uint8_t* const* const* proofs, uint32_t flags, int32_t* verified,
+                                         int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges,
+                                         uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes, uint8_t* digests32, uint8_t* leaves32) {
+    if (!commitments_lengths || !commitments || !cell_indices_lengths || !cell_indices || !cells_lengths || !cells || !proofs_lengths || !proofs ||
+        !verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || !digests32 || (max_probes && (!probe_ranges || !probe_sums96)) ||
+        (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT))
+        return kzg::ERR_INPUT;
+    kzg::VerifyManyInput in;
+    in.n_commitments = commitments_lengths; in.n_indices = cell_indices_lengths; in.n_cells = cells_lengths; in.n_proofs = proofs_lengths;
+    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
+    in.leaf = flags != 0;
+    return eng(ctx)->test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
+                                              digests32, leaves32);
+}
+int eth_kzg_amd_test_verify_many_sums_device(const DASContext* ctx, uint64_t n_batches, const uint64_t* cell_starts, const uint8_t* d_commitments,
+                                             const uint64_t* d_cell_indices, const uint8_t* d_cells, const uint8_t* d_proofs, uint32_t flags,
+                                             int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho, uint8_t* fold96,
+                                             int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes, uint8_t* digests32,
+                                             uint8_t* leaves32) {
+    if (!verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || !digests32 || (max_probes && (!probe_ranges || !probe_sums96)) ||
+        (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) || n_batches < 1 || n_batches > (1u << 20) ||
+        kzg::validate_cell_starts(n_batches, cell_starts) != kzg::INPUT_VALID)
+        return kzg::ERR_INPUT;
+    if (cell_starts[n_batches] && (!d_commitments || !d_cell_indices || !d_cells || !d_proofs)) return kzg::ERR_INPUT;
+    kzg::VerifyManyInput in;
+    in.cell_starts = cell_starts; in.d_commitments = d_commitments; in.d_cell_indices = d_cell_indices; in.d_cells = d_cells; in.d_proofs = d_proofs;
+    in.leaf = flags != 0;
+    return eng(ctx)->test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
+                                              digests32, leaves32);
 }
 int eth_kzg_amd_test_rs_decode(const DASContext* ctx, int R, const uint64_t* n_cells, const uint64_t* const* cell_indices,
                                const uint8_t* const* const* cells, int flat_source, int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval,

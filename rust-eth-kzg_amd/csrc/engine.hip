@@ -401,6 +401,9 @@ void Engine::teardown() noexcept {
         if (v.pin) hipHostFree(v.pin);
         if (v.vs.dev) hipFree(v.vs.dev);
         if (v.vs.pin) hipHostFree(v.vs.pin);
+        if (v.src_pin) hipHostFree(v.src_pin);
+        if (v.ordered) hipEventDestroy(v.ordered);
+        if (v.hash_inputs_down) hipEventDestroy(v.hash_inputs_down);
     }
     if (vd_pin_) hipHostFree(vd_pin_);
     for (hipEvent_t e : vd_events_)

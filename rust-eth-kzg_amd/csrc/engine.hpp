@@ -46,6 +46,37 @@ struct VerifyManyTap {
     std::vector<uint8_t> fold;                       // [2] JacQ: the folded pair
     std::vector<int> probes;                         // the search's probes in order: lo, hi, passed
     std::vector<uint8_t> probe_sums;                 // [probe][2] JacQ
+    std::vector<uint8_t> digests;                    // [Bc][32]: the digest each problem's challenge was reduced from (zero: not hashed)
+    std::vector<uint8_t> leaves;                     // (leaf-hashed challenges) [n][32]: the leaf digests of the pass's cells as they came down
+};
+// Where the problems of a many-verification call come from (verify_many.hip), and how they take their challenges.
+//   pointer lists (cell_starts null): problem b has n_*[b] entries in commitments[b] / cell_indices[b] / cells[b] / proofs[b], all on the host
+//   flat arrays in this GPU's HBM (cell_starts set, on the host, n_batches + 1 non-decreasing entries): problem b is the entries
+//     [cell_starts[b], cell_starts[b + 1]) of d_commitments (48 B each, one per cell), d_cell_indices, d_cells (2048 B), d_proofs (48 B);
+//     what user_stream has queued produces them
+// leaf: every problem's challenge is the leaf-hashed one of the problem alone (verify_host.hpp: CellLeafTranscript, cell_leaf_root),
+// the leaves hashed on the GPU out of the pass's arena; else the reference's transcript on the host threads.
+struct VerifyManyInput {
+    const uint64_t *n_commitments = nullptr, *n_indices = nullptr, *n_cells = nullptr, *n_proofs = nullptr;
+    const uint8_t* const* const* commitments = nullptr;
+    const uint64_t* const* cell_indices = nullptr;
+    const uint8_t* const* const* cells = nullptr;
+    const uint8_t* const* const* proofs = nullptr;
+    const uint64_t* cell_starts = nullptr;
+    const uint8_t* d_commitments = nullptr;
+    const uint64_t* d_cell_indices = nullptr;
+    const uint8_t *d_cells = nullptr, *d_proofs = nullptr;
+    hipStream_t user_stream = nullptr;
+    bool leaf = false;
+    bool on_device() const { return cell_starts != nullptr; }
+    uint64_t cells_of(uint64_t b) const { return on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b]; }
+    VerifyManyInput from(uint64_t lo) const {  // the problems from lo on (the flat arrays stay: cell_starts holds absolute entries)
+        VerifyManyInput s = *this;
+        if (on_device()) { s.cell_starts += lo; return s; }
+        s.n_commitments += lo; s.n_indices += lo; s.n_cells += lo; s.n_proofs += lo;
+        s.commitments += lo; s.cell_indices += lo; s.cells += lo; s.proofs += lo;
+        return s;
+    }
 };
 
 // How a single cell verification takes its Fiat-Shamir challenge (verify.hip).  Null or `leaf` false: the reference's transcript, one
@@ -188,6 +219,11 @@ public:
                                               const uint64_t* n_indices, const uint64_t* const* cell_indices, const uint64_t* n_cells,
                                               const uint8_t* const* const* cells, const uint64_t* n_proofs,
                                               const uint8_t* const* const* proofs, int* verified, int* status, VerifyManyTap* tap = nullptr);
+    // the same pass over either source and with either challenge (VerifyManyInput above); the call above is its pointer-list form with
+    // the reference's challenges.  Flat device arrays: the pass copies its proofs and cells device-to-device into its arena; commitments
+    // and indices come down for validation and de-duplication; with the leaf-hashed challenges nothing else does but the n x 32 leaf
+    // digests, without them the proofs and cells come down into the pinned slab for the host threads' hashes (correct, and the slow way)
+    int verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap = nullptr);
     // verify_cell_kzg_proof_batch as the reference's users call it -- one problem per call, from many threads on one context
     // (bindings/node/src/lib.rs:92-299) -- WITHOUT asking them to batch: the first callers take the latency-optimised path
     // (verify_cell_kzg_proof_batch_host, one per engine lane); callers that arrive while every lane is verifying
@@ -292,6 +328,12 @@ public:
                               const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells, const uint64_t* n_proofs,
                               const uint8_t* const* const* proofs, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho,
                               uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes);
+    // the same over either source and with either challenge, plus digests32[B][32] (the digest each problem's challenge was reduced
+    // from; zero for a problem that was not hashed) and, may be null, leaves32[N][32] (leaf-hashed challenges: the leaf digests in the
+    // caller's cell order; zero for the cells of a problem that was not hashed)
+    int test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
+                                 uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
+                                 uint8_t* digests32, uint8_t* leaves32);
     // the Reed-Solomon decoder of recovery on its own: rs_decode (verify.hip) with its tap set, behind the staging of recover_batch_to_coeffs
     // (flat_source = 0) or of recover_cells_and_kzg_proofs_device (1); outputs canonical big-endian on the host, each may be null
     int test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,
@@ -551,6 +593,14 @@ private:
         size_t dev_cap = 0;
         uint8_t* pin = nullptr;
         size_t pin_cap = 0;
+        // flat device source: the pinned mirror of the commitments and indices of the call's problems (those within the size bound, back
+        // to back); `ordered` puts the caller's stream in front of the pass's
+        uint8_t* src_pin = nullptr;
+        size_t src_pin_cap = 0;
+        hipEvent_t ordered = nullptr;
+        // what the host threads hash is in the pinned slab: the leaf digests (leaf-hashed challenges), or the proofs and cells the flat
+        // device source brings down for the reference's transcript
+        hipEvent_t hash_inputs_down = nullptr;
     };
     VmSlot vm_slot_[VM_SLOTS];
     SlotSet<VM_SLOTS> vm_slots_;  // leases of the pass slots (host_sync.hpp)

@@ -503,19 +503,28 @@ int Engine::test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitme
                                   const uint64_t* n_proofs, const uint8_t* const* const* proofs, int32_t* verified, int32_t* status, int32_t* form4,
                                   uint8_t* sums96, uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes,
                                   uint64_t* n_probes) {
+    VerifyManyInput in;
+    in.n_commitments = n_commitments; in.n_indices = n_indices; in.n_cells = n_cells; in.n_proofs = n_proofs;
+    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
+    return test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes, nullptr,
+                                    nullptr);
+}
+// The same over either source and with either challenge (the hooks _ex and _device): the taps of the digests and of the leaves besides.
+int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
+                                     uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
+                                     uint8_t* digests32, uint8_t* leaves32) {
     if (n_batches < 1 || n_batches > (1u << 20)) return ERR_INPUT;
     uint64_t total_cells = 0;
     for (uint64_t b = 0; b < n_batches; b++) {
-        if (n_cells[b] > (uint64_t)VM_CHUNK_CELLS) return ERR_INPUT;
-        total_cells += n_cells[b];
+        if (in.cells_of(b) > (uint64_t)VM_CHUNK_CELLS) return ERR_INPUT;
+        total_cells += in.cells_of(b);
     }
     if (total_cells > (uint64_t)VM_CHUNK_CELLS) return ERR_INPUT;                                                        // chunks
     if (n_batches >= (uint64_t)VM_SPLIT_MIN_PROBLEMS && total_cells >= (uint64_t)VM_SPLIT_MIN_CELLS) return ERR_INPUT;  // parts
     const int B = (int)n_batches;
     std::vector<int> ver(B), st(B);
     VerifyManyTap tap;
-    const int rc = verify_cell_kzg_proof_batch_many_host(n_batches, n_commitments, commitments, n_indices, cell_indices, n_cells, cells, n_proofs, proofs,
-                                                         ver.data(), st.data(), &tap);
+    const int rc = verify_cell_kzg_proof_batch_many(n_batches, in, ver.data(), st.data(), &tap);
     if (rc) return rc;
     if (tap.passes > 1) return ERR_INPUT;  // (cannot happen behind the checks above)
     static_assert(sizeof(JacQ) == launch::SIZEOF_JACQ, "the tap holds JacQ words");
@@ -536,9 +545,20 @@ int Engine::test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitme
     form4[0] = tap.small; form4[1] = tap.folded; form4[2] = tap.searched; form4[3] = tap.fold_verdict;
     memset(fold96, 0, 96);
     *n_probes = tap.probes.size() / 3;
+    if (digests32) memset(digests32, 0, (size_t)B * 32);
+    if (leaves32 && in.leaf) memset(leaves32, 0, (size_t)total_cells * 32);
     if (tap.passes == 0) return OK;  // no cell in the whole call: nothing was launched
+    if (digests32) memcpy(digests32, tap.digests.data(), (size_t)B * 32);
+    if (leaves32 && in.leaf) {  // the pass holds the cells of the problems that passed validation, back to back: into the caller's order
+        size_t at = 0, flat = 0;
+        for (int b = 0; b < B; b++) {
+            const size_t nb = (size_t)in.cells_of((uint64_t)b);
+            if (st[b] != ERR_INPUT && nb) { memcpy(leaves32 + flat * 32, tap.leaves.data() + at * 32, nb * 32); at += nb; }
+            flat += nb;
+        }
+    }
     for (int b = 0; b < B; b++) {
-        if (st[b] == OK && n_cells[b] > 0) compress2(sums96 + 96 * (size_t)b, tap.sums.data() + (size_t)2 * b * sizeof(JacQ));
+        if (st[b] == OK && in.cells_of((uint64_t)b) > 0) compress2(sums96 + 96 * (size_t)b, tap.sums.data() + (size_t)2 * b * sizeof(JacQ));
         for (int j = 0; j < 4; j++) rho[4 * b + j] = tap.rho[4 * (size_t)b + j];
     }
     if (tap.folded) compress2(fold96, tap.fold.data());

@@ -166,6 +166,9 @@ __global__ __launch_bounds__(64) void k_sha256_many(int n, const uint8_t* __rest
 // with 1024 SIMDs: while every wave has a SIMD to itself the launch lasts what ONE lane's 35 dependent compressions last
 // (about 0.2 ms with the read-back and the root), and it leaves the chip to the decoding kernels next to it.
 // The launcher refuses pointers that do not have the alignments the wide loads and stores assume.
+// Two instantiations.  POSITIONS = false is the single verification's kernel: the hashed position of cell i is i.  POSITIONS = true is
+// the many-verification's (verify_many.hip): its arena holds the cells of all the problems of a pass back to back, uniq / row / idx /
+// proofs / cells are pass-wide, and the hashed position is pos[i], the cell's place INSIDE its problem (it restarts at 0 in each one).
 constexpr uint32_t be32_of(const char* s) {
     return ((uint32_t)(uint8_t)s[0] << 24) | ((uint32_t)(uint8_t)s[1] << 16) | ((uint32_t)(uint8_t)s[2] << 8) | (uint32_t)(uint8_t)s[3];
 }
@@ -201,15 +204,18 @@ __device__ __forceinline__ void leaf_edge_block(int which, uint32_t k, uint32_t 
     }
 }
 
+template <bool POSITIONS>
 __global__ __launch_bounds__(64) void k_sha256_cell_leaves(int n, const uint8_t* __restrict__ uniq, const int* __restrict__ row,
-                                                           const int* __restrict__ idx, const uint8_t* __restrict__ proofs,
-                                                           const uint8_t* __restrict__ cells, uint8_t* __restrict__ out) {
+                                                           const int* __restrict__ idx, const int* __restrict__ pos,
+                                                           const uint8_t* __restrict__ proofs, const uint8_t* __restrict__ cells,
+                                                           uint8_t* __restrict__ out) {
     const int lane_cell = blockIdx.x * 64 + threadIdx.x;
     const int i = lane_cell < n ? lane_cell : n - 1;
     const uint8_t* commitment = uniq + (size_t)row[i] * 48;
     const uint8_t* proof = proofs + (size_t)i * 48;
     const uint8_t* cell = cells + (size_t)i * 2048;
     const uint32_t index = (uint32_t)idx[i];
+    const uint32_t position = POSITIONS ? (uint32_t)pos[i] : (uint32_t)i;
     uint32_t h[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a, 0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
     uint32_t w[16];
     // two passes of the edge blocks around the wide loop (one inlined copy of the rounds each): the header, then the padding
@@ -217,7 +223,7 @@ __global__ __launch_bounds__(64) void k_sha256_cell_leaves(int n, const uint8_t*
     for (int pass = 0; pass < 2; pass++) {
 #pragma unroll 1
         for (int e = pass ? 2 : 0; e < (pass ? 3 : 2); e++) {
-            leaf_edge_block(e, (uint32_t)i, index, commitment, proof, w);
+            leaf_edge_block(e, position, index, commitment, proof, w);
             sha256_compress(h, w);
         }
         if (pass == 0) {
@@ -247,15 +253,18 @@ namespace launch {
 void preload_k_sha256() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_sha256_many));
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_sha256_cell_leaves));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_sha256_cell_leaves<false>));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_sha256_cell_leaves<true>));
 }
 void sha256_cell_leaves(int n, const uint8_t* uniq, const int* row, const int* idx, const uint8_t* proofs, const uint8_t* cells, uint8_t* out,
-                        hipStream_t st) {
+                        hipStream_t st, const int* pos) {
     if (n <= 0) return;
     const uintptr_t loads = reinterpret_cast<uintptr_t>(uniq) | reinterpret_cast<uintptr_t>(proofs) | reinterpret_cast<uintptr_t>(cells);
-    if ((loads & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 31) != 0 || ((reinterpret_cast<uintptr_t>(row) | reinterpret_cast<uintptr_t>(idx)) & 3) != 0)
+    const uintptr_t ints = reinterpret_cast<uintptr_t>(row) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(pos);
+    if ((loads & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 31) != 0 || (ints & 3) != 0)
         throw std::invalid_argument("sha256_cell_leaves: commitments, proofs and cells must be 16-byte aligned, the digests 32-byte aligned");
-    k_sha256_cell_leaves<<<(n + 63) / 64, 64, 0, st>>>(n, uniq, row, idx, proofs, cells, out);
+    if (pos) k_sha256_cell_leaves<true><<<(n + 63) / 64, 64, 0, st>>>(n, uniq, row, idx, pos, proofs, cells, out);
+    else k_sha256_cell_leaves<false><<<(n + 63) / 64, 64, 0, st>>>(n, uniq, row, idx, nullptr, proofs, cells, out);
 }
 void sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_t* body, size_t body_stride, uint32_t body_len,
                  const uint8_t* tail, size_t tail_stride, uint32_t tail_len, uint8_t* out, hipStream_t st) {

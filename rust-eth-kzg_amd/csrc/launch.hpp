@@ -204,9 +204,11 @@ void sha256_many(int n, const uint8_t* prefix, uint32_t prefix_len, const uint8_
                  const uint8_t* tail, size_t tail_stride, uint32_t tail_len, uint8_t* out, hipStream_t st);
 // the n leaves of the cell verifier's leaf-hashed challenge (verify_host.hpp: CellLeafTranscript), one lane each, from the verifier's
 // arena: leaf k hashes k, idx[k], uniq + 48 row[k], proofs + 48 k and cells + 2048 k; digest k -> out + 32 k.  uniq, proofs and cells
-// 16-byte aligned, out 32-byte aligned (anything else throws before the launch)
+// 16-byte aligned, out 32-byte aligned (anything else throws before the launch).  pos (the many-verification's arena: the cells of
+// several problems back to back): leaf k hashes pos[k], its position inside its problem, in the place of k -- a second instantiation
+// of the kernel; null: the single verification's
 void sha256_cell_leaves(int n, const uint8_t* uniq, const int* row, const int* idx, const uint8_t* proofs, const uint8_t* cells, uint8_t* out,
-                        hipStream_t st);
+                        hipStream_t st, const int* pos = nullptr);
 
 constexpr size_t SIZEOF_FR = 32, SIZEOF_G1AFFINE = 96, SIZEOF_G1JAC = 144;
 constexpr size_t SIZEOF_JACS = 156;  // signed 13 x 30-bit Jacobian point (curve30.hpp)

@@ -1,7 +1,8 @@
 // The host's share of verification and recovery that is pure computation over bytes: input validation, de-duplication, the scalar
 // codecs and the Fiat-Shamir transcripts (the reference's four and the leaf-hashed challenge of the cell verifier), each stated ONCE
 // for verify.hip, verify_many.hip, eip4844.hip and recover.hip.
-// No HIP call in here, everything inline: tests/c/test_verify_host.cpp and test_leaf_transcript.cpp run it on the CPU against hashlib.
+// No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp and test_many_leaf.cpp run it on the CPU
+// against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -65,17 +66,36 @@ inline int validate_cell_batch(uint64_t n_commitments, uint64_t n_indices, uint6
         if (cell_indices[i] >= (uint64_t)N_CELLS) return INPUT_INVALID;
     return INPUT_VALID;
 }
-// deduplicate_with_indices (verifier.rs:49-65): byte equality, first-occurrence order -> the unique commitments, the row of every entry
-inline void dedup_commitments(uint64_t n, const uint8_t* const* commitments, std::vector<const uint8_t*>& uniq, std::vector<int>& row) {
+// deduplicate_with_indices (verifier.rs:49-65): byte equality, first-occurrence order -> the unique commitments, the row of every entry.
+// at(i) = the 48 bytes of entry i: a pointer list, or flat bytes (the device-resident many-verification's mirror)
+template <class At>
+inline void dedup_commitments_at(uint64_t n, At at, std::vector<const uint8_t*>& uniq, std::vector<int>& row) {
     uniq.clear();
     row.resize(n);
     std::map<std::string, int> seen;
     for (uint64_t i = 0; i < n; i++) {
-        std::string key((const char*)commitments[i], 48);
+        const uint8_t* c = at(i);
+        std::string key((const char*)c, 48);
         auto it = seen.find(key);
-        if (it == seen.end()) { it = seen.emplace(key, (int)uniq.size()).first; uniq.push_back(commitments[i]); }
+        if (it == seen.end()) { it = seen.emplace(key, (int)uniq.size()).first; uniq.push_back(c); }
         row[i] = it->second;
     }
+}
+inline void dedup_commitments(uint64_t n, const uint8_t* const* commitments, std::vector<const uint8_t*>& uniq, std::vector<int>& row) {
+    dedup_commitments_at(n, [commitments](uint64_t i) { return commitments[i]; }, uniq, row);
+}
+inline void dedup_commitments_flat(uint64_t n, const uint8_t* flat48, std::vector<const uint8_t*>& uniq, std::vector<int>& row) {
+    dedup_commitments_at(n, [flat48](uint64_t i) { return flat48 + i * 48; }, uniq, row);
+}
+// cell_starts of the device-resident many-verification (c_eth_kzg.h): n_batches + 1 entries, the first 0, non-decreasing; problem b is
+// the entries [cell_starts[b], cell_starts[b + 1]) of the flat arrays.  How long a problem may be is the problem's own validation
+// (validate_cell_batch: status 3 for that problem), not the array's.
+inline int validate_cell_starts(uint64_t n_batches, const uint64_t* cell_starts) {
+    if (n_batches == 0) return INPUT_VALID;
+    if (!cell_starts || cell_starts[0] != 0) return INPUT_INVALID;
+    for (uint64_t b = 0; b < n_batches; b++)
+        if (cell_starts[b + 1] < cell_starts[b]) return INPUT_INVALID;
+    return INPUT_VALID;
 }
 // validate_recovery_inputs (recovery.rs:90-146)
 inline int validate_recovery(uint64_t n_cells, uint64_t n_indices, const uint64_t* cell_indices) {
@@ -131,8 +151,13 @@ private:
 // holds a wrong proof passes only if r is a root of a non-zero polynomial of degree below n over Fr -- the argument of the
 // reference's own challenge, which asks of the hash nothing else.  Valid batches verify under any r, and whether a call is Err or
 // Ok(false) is decided by validation and decoding, before r is used.
-// Out of scope: _partial / _combine, _many and the combiner of concurrent single calls keep the reference's transcript; no
-// environment knob moves the reference's own symbol onto this one; the Node binding does not pass the flag.
+// The many-verification (verify_many.hip; eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex / _many_device_ex with the flag) takes, for
+// every problem of a call, exactly this challenge of the problem alone: k restarts at 0 in each problem, ROOT carries the problem's own
+// n (cell_leaf_root below).  Its folding weights (fold_seed, fold_weight) then hash the problems' ROOTs where they hash the reference
+// transcript's digests otherwise: every ROOT is a hash of every input byte of its problem, so the weights still hang on every input
+// byte of the pass and cannot be predicted before all of them are fixed -- the argument of the fold is unchanged.
+// Out of scope: _partial / _combine and the combiner of concurrent single calls keep the reference's transcript; no environment knob
+// moves an unflagged symbol onto this one; the Node binding does not pass the flag.
 class CellLeafTranscript {
 public:
     static constexpr size_t LEAF_BYTES = 16 + 8 + 8 + 48 + 48 + BYTES_PER_CELL;  // 2176 = 34 blocks
@@ -163,6 +188,15 @@ private:
     uint8_t digest_[32];
 };
 static_assert(CellLeafTranscript::LEAF_BYTES == 34 * 64, "the header is two blocks and the cell thirty-two");
+// the challenge of problem b of a many-verification pass: leaves = the digests of the pass's cells back to back, 32 bytes each, entry 0
+// the cell starts[0]; problem b holds the cells [starts[b], starts[b + 1]).  digest_out: the problem's ROOT.
+template <class Int>
+inline Fr cell_leaf_root(const uint8_t* leaves, const Int* starts, size_t b, uint8_t digest_out[32]) {
+    CellLeafTranscript t;
+    const Fr r = t.root((uint64_t)(starts[b + 1] - starts[b]), leaves + (size_t)(starts[b] - starts[0]) * 32);
+    memcpy(digest_out, t.digest(), 32);
+    return r;
+}
 
 // ---- compute_fiat_shamir_challenge of EIP-4844 (eip4844/src/verifier.rs:155-196): H(header | blob | commitment) mod r
 inline void blob_challenge_header(uint8_t hdr[32]) {

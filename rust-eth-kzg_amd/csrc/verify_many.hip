@@ -16,6 +16,14 @@
 // Three pass slots, each with its own lock, device arena and pinned slab, on the streams of the prover's three work sets (HIP maps
 // a process's streams onto four hardware queues): passes run side by side, a large call is cut into three concurrent parts, and a
 // "pass" of one problem is the single path on the slot.  Nothing here takes the context's big lock.
+// One pass, two sources, two challenge modes (engine.hpp: VerifyManyInput).  Sources: the caller's pointer lists, gathered into the
+// pinned slab and uploaded; or flat arrays in HBM plus cell_starts, whose proofs and cells go device-to-device into the arena while
+// commitments and indices come down for validation and de-duplication.  Challenges: the reference's transcript on the host threads; or
+// the leaf-hashed challenge of each problem alone (verify_host.hpp: CellLeafTranscript) -- the leaves of ALL the pass's cells in one
+// launch of k_sha256_cell_leaves out of the arena, in order on the pass's stream behind the upload, the n x 32 digests down behind an
+// event, one ROOT per problem on the host threads while the decoding kernels run.  The roots stay on the host on purpose: a lane per
+// problem would serialise n / 2 compressions of a large problem (8192 cells: ~4 k dependent compressions), and the wait for the
+// status words is there anyway.  Everything behind the challenge is the same for all four combinations.
 #include "engine_internal.hpp"
 #include "curve29.hpp"
 #include "host_pairing.hpp"
@@ -34,6 +42,7 @@ struct Problem {  // one verification of the call, after validation
     std::vector<const uint8_t*> uniq;  // de-duplicated commitments, first-occurrence order (verifier.rs:49-65)
     std::vector<int> row;              // per cell: index into uniq
     int n = 0, m = 0;                  // cells, unique commitments (0, 0 when the problem is skipped)
+    uint64_t src0 = 0, mir0 = 0;       // (flat device source) its first entry in the caller's arrays / in the pinned mirror
 };
 
 // Where a pass's arrays lie: n cells and m unique commitments of Bc problems.  Device arena: [inputs, uploaded in one copy |
@@ -41,6 +50,7 @@ struct Problem {  // one verification of the call, after validation
 struct PassLayout {
     const int n, m, Bc;
     const bool small;
+    const bool leaf;  // leaf-hashed challenges: n x 32 digest bytes on the device and, read back, in the pinned slab
     const int max_ranges = std::min(Bc, 2048);  // probes per level of the search for wrong proofs
     static constexpr size_t JACQ = launch::SIZEOF_JACQ;
     Carve d;  // (members are initialised in the order they stand here)
@@ -52,7 +62,8 @@ struct PassLayout {
                  in2_bytes = d.end;
     Carve h = d;  // pinned read-backs behind the inputs
     const size_t poff_st = h.take((size_t)(n + m + Bc) * 4), poff_out = h.take((size_t)2 * Bc * JACQ), poff_fold = h.take((size_t)2 * JACQ),
-                 poff_rng = h.take((size_t)max_ranges * 8), poff_rsum = h.take((size_t)2 * max_ranges * JACQ), pin_bytes = h.end;
+                 poff_rng = h.take((size_t)max_ranges * 8), poff_rsum = h.take((size_t)2 * max_ranges * JACQ), poff_leaf = h.take(leaf ? (size_t)n * 32 : 0),
+                 pin_bytes = h.end;
     // device only
     const size_t off_pts = d.take((size_t)(n + m) * sizeof(G1Affine)), off_evals = d.take((size_t)n * CELL_LEN * sizeof(Fr)),
                  off_coef = d.take((size_t)n * CELL_LEN * sizeof(Fr)),
@@ -61,8 +72,9 @@ struct PassLayout {
                  off_s2 = d.take((size_t)n * sizeof(Fr)), off_w = d.take((size_t)m * sizeof(Fr)), off_isc = d.take((size_t)Bc * 64 * sizeof(Fr)),
                  off_icm = d.take((size_t)Bc * JACQ), off_prod = d.take((size_t)(2 * n + m + (small ? 64 * Bc : 0)) * JACQ),
                  off_out = d.take((size_t)2 * Bc * JACQ), off_fprod = d.take((size_t)2 * Bc * JACQ), off_fold = d.take((size_t)2 * JACQ),
-                 off_rng = d.take((size_t)max_ranges * 8), off_rsum = d.take((size_t)2 * max_ranges * JACQ), dev_bytes = d.end;
-    PassLayout(int n_, int m_, int Bc_, bool small_) : n(n_), m(m_), Bc(Bc_), small(small_) {}
+                 off_rng = d.take((size_t)max_ranges * 8), off_rsum = d.take((size_t)2 * max_ranges * JACQ),
+                 off_leaf = d.take(leaf ? (size_t)n * 32 : 0), dev_bytes = d.end;
+    PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_) {}
 };
 
 // the pairing check of two sums read back (verifier.rs:242-259; vk = [tau^64]_2, -[1]_2): 1 / 0, or -1 where the poison of the result
@@ -77,14 +89,13 @@ int check_pair(const JacQ* two, const pairing::G2Prepared* const* vk) {
     return pairing::product_is_one(pts, vk, 2) ? 1 : 0;
 }
 
-// The host's side of one pass: problems b0 .. b0 + Bc of the call (the inputs are the call's arrays from b0 on), n cells and m unique
+// The host's side of one pass: problems b0 .. b0 + Bc of the call (`in` is the call's input from b0 on), n cells and m unique
 // commitments in all, staged into the pinned slab hb as L lays it out.  Nothing in here touches the GPU.
 struct PassHost {
     const PassLayout& L;
     const Problem* pr;
-    const uint64_t* const* cell_indices;
-    const uint8_t* const* const* cells;
-    const uint8_t* const* const* proofs;
+    const VerifyManyInput in;
+    const uint64_t* mirror_i;  // (flat device source) the pinned mirror of the call's indices: a problem's begin at its mir0
     uint8_t* hb;
     int T;
     HostPool* pool;
@@ -97,8 +108,10 @@ struct PassHost {
     VerifyManyTap* tap = nullptr;            // (null in the product) receives copies of the read-backs
     const JacQ* sums() const { return (const JacQ*)(hb + L.poff_out); }  // the problems' two sums read back
     int* h_status() const { return (int*)(hb + L.poff_st); }  // read-backs: [proofs n | commitments m | cells, per problem]
+    const uint64_t* indices_of(int i) const { return in.on_device() ? mirror_i + pr[i].mir0 : in.cell_indices[i]; }
 
-    // gather the problems into the slab; stale contents of the persistent slab must fail closed: status words and result slots are poisoned
+    // gather the problems into the slab (flat device source: what the host made of them; proofs and cells move inside HBM); stale
+    // contents of the persistent slab must fail closed: status words and result slots are poisoned
     void stage() {
         cell_start.assign(L.Bc + 1, 0); row_start.assign(L.Bc + 1, 0);
         for (int i = 0; i < L.Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[i].n; row_start[i + 1] = row_start[i] + pr[i].m; }
@@ -106,14 +119,18 @@ struct PassHost {
         memcpy(hb + L.off_rs, row_start.data(), (size_t)(L.Bc + 1) * 4);
         int *h_idx = (int*)(hb + L.off_idx), *h_row = (int*)(hb + L.off_row), *h_bat = (int*)(hb + L.off_bat), *h_pos = (int*)(hb + L.off_pos),
             *h_rowb = (int*)(hb + L.off_rowb);
+        const bool gather = !in.on_device();
         parallel_for(L.Bc, T, pool, [&](int i) {
             const Problem& p = pr[i];
             const int c0 = cell_start[i], r0 = row_start[i];
             for (int j = 0; j < p.m; j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
+            const uint64_t* ix = p.n ? indices_of(i) : nullptr;
             for (int k = 0; k < p.n; k++) {
-                memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, proofs[i][k], 48);
-                memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, cells[i][k], BYTES_PER_CELL);
-                h_idx[c0 + k] = (int)cell_indices[i][k];
+                if (gather) {
+                    memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, in.proofs[i][k], 48);
+                    memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, in.cells[i][k], BYTES_PER_CELL);
+                }
+                h_idx[c0 + k] = (int)ix[k];
                 h_row[c0 + k] = r0 + p.row[k];
                 h_bat[c0 + k] = i;
                 h_pos[c0 + k] = k;
@@ -123,7 +140,9 @@ struct PassHost {
         memset(hb + L.poff_out, 0xff, (size_t)2 * L.Bc * launch::SIZEOF_JACQ);
         memset(hb + L.poff_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ);
     }
-    // the Fiat-Shamir challenges on the host threads (verify_host.hpp: CellBatchTranscript), then the table r^(2^i) per problem
+    // the Fiat-Shamir challenges on the host threads, then the table r^(2^i) per problem.  The reference's transcript
+    // (verify_host.hpp: CellBatchTranscript) over the caller's buffers, or, for the flat device source, over the proofs and cells that
+    // came down into the slab; leaf-hashed: one ROOT per problem over the leaf digests that came down (cell_leaf_root)
     void hash_challenges() {
         Fr* h_pow = (Fr*)(hb + L.off_pow);
         digests.assign((size_t)L.Bc * 32, 0);
@@ -131,10 +150,21 @@ struct PassHost {
             const Problem& p = pr[i];
             Fr* tab = h_pow + (size_t)i * 24;
             if (p.n == 0) { for (int j = 0; j < 24; j++) tab[j] = one<FrParams>(); return; }
-            CellBatchTranscript t(p.m, p.n, p.uniq.data());
-            for (int k = 0; k < p.n; k++) t.absorb(p.row[k], cell_indices[i][k], cells[i][k], proofs[i][k]);
-            Fr cur = t.finish();
-            memcpy(&digests[(size_t)i * 32], t.digest(), 32);
+            Fr cur;
+            if (L.leaf) {
+                cur = cell_leaf_root(hb + L.poff_leaf, cell_start.data(), (size_t)i, &digests[(size_t)i * 32]);
+            } else {
+                CellBatchTranscript t(p.m, p.n, p.uniq.data());
+                const uint64_t* ix = indices_of(i);
+                if (in.on_device()) {
+                    const uint8_t *sc = hb + L.off_cells + (size_t)cell_start[i] * BYTES_PER_CELL, *sp = hb + L.off_p + (size_t)cell_start[i] * 48;
+                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], ix[k], sc + (size_t)k * BYTES_PER_CELL, sp + (size_t)k * 48);
+                } else {
+                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], ix[k], in.cells[i][k], in.proofs[i][k]);
+                }
+                cur = t.finish();
+                memcpy(&digests[(size_t)i * 32], t.digest(), 32);
+            }
             for (int j = 0; j < 24; j++) { tab[j] = cur; cur = sqr(cur); }
         });
     }
@@ -255,6 +285,13 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
                                                   const uint64_t* const* cell_indices, const uint64_t* n_cells,
                                                   const uint8_t* const* const* cells, const uint64_t* n_proofs,
                                                   const uint8_t* const* const* proofs, int* verified, int* status, VerifyManyTap* tap) {
+    VerifyManyInput in;
+    in.n_commitments = n_commitments; in.n_indices = n_indices; in.n_cells = n_cells; in.n_proofs = n_proofs;
+    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
+    return verify_cell_kzg_proof_batch_many(n_batches, in, verified, status, tap);
+}
+
+int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
     const int B = (int)n_batches;
     for (int b = 0; b < B; b++) { verified[b] = 0; status[b] = OK; }
     if (B == 0) return OK;
@@ -266,13 +303,13 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
     constexpr int max_parts = VM_SLOTS < 3 ? (int)VM_SLOTS : 3;
     if (!in_part && max_parts > 1 && B >= VM_SPLIT_MIN_PROBLEMS) {
         uint64_t total_cells = 0;
-        for (int b = 0; b < B; b++) total_cells += n_cells[b];
+        for (int b = 0; b < B; b++) total_cells += in.cells_of((uint64_t)b);
         if (total_cells >= (uint64_t)VM_SPLIT_MIN_CELLS) {
             const int parts = max_parts;
             std::vector<int> cut{0};
             uint64_t acc = 0;
             for (int b = 0; b < B; b++) {  // equal shares of the cells
-                acc += n_cells[b];
+                acc += in.cells_of((uint64_t)b);
                 if ((int)cut.size() < parts && acc * parts >= total_cells * cut.size() && b + 1 < B) cut.push_back(b + 1);
             }
             cut.push_back(B);
@@ -281,8 +318,7 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             auto run_part = [&](int p) {
                 const int lo = cut[p], n = cut[p + 1] - lo;
                 in_part = true;
-                rcs[p] = verify_cell_kzg_proof_batch_many_host((uint64_t)n, n_commitments + lo, commitments + lo, n_indices + lo, cell_indices + lo, n_cells + lo,
-                                                               cells + lo, n_proofs + lo, proofs + lo, verified + lo, status + lo);
+                rcs[p] = verify_cell_kzg_proof_batch_many((uint64_t)n, in.from((uint64_t)lo), verified + lo, status + lo);
                 if (rcs[p] == ERR_DEVICE) errs[p] = last_error();
                 in_part = false;
             };
@@ -312,17 +348,64 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
         // concurrent callers).  A prover call that happens to hold that work set shares the (in-order) stream with the pass.
         const int slot_index = (int)(slot - vm_slot_);
         hipStream_t st = work_[1 + slot_index % (NW - 1)].stream ? work_[1 + slot_index % (NW - 1)].stream : stream_;
-        // ---- per problem: validation (verifier.rs:123-164) and de-duplication
+        TraceLap lap{knobs_.trace, "verify_many"};
+        // ---- flat device source: commitments and indices of the call's cells come down (56 bytes per cell) behind whatever the
+        // caller's stream has queued; the host validates and de-duplicates from this pinned mirror, and the unique commitments of a
+        // pass are gathered out of it
+        // A problem beyond the size bound is refused by its validation below (status 3) and has no place in the mirror: nothing of it is
+        // read, and the mirror is sized by problems of at most MAX_CELLS_PER_VERIFICATION cells only.
+        const uint8_t* mirror_c = nullptr;
+        const uint64_t* mirror_i = nullptr;
         std::vector<Problem> pr(B);
+        if (in.on_device()) {
+            uint64_t N = 0;
+            for (int b = 0; b < B; b++) {
+                pr[b].src0 = in.cell_starts[b];
+                pr[b].mir0 = N;
+                if (in.cells_of((uint64_t)b) <= MAX_CELLS_PER_VERIFICATION) N += in.cells_of((uint64_t)b);
+            }
+            if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
+            if (in.user_stream != st) {
+                HIPCK(hipEventRecord(slot->ordered, in.user_stream));
+                HIPCK(hipStreamWaitEvent(st, slot->ordered, 0));
+            }
+            if (N) {
+                grow_pinned(slot->src_pin, slot->src_pin_cap, (size_t)N * 56);
+                uint8_t* const pin_c = slot->src_pin;
+                uint64_t* const pin_i = reinterpret_cast<uint64_t*>(slot->src_pin + (size_t)N * 48);
+                for (int b = 0; b < B;) {  // one pair of copies per run of problems within the bound (they follow each other in both)
+                    uint64_t run = 0;
+                    int e = b;
+                    while (e < B && in.cells_of((uint64_t)e) <= MAX_CELLS_PER_VERIFICATION) run += in.cells_of((uint64_t)e++);
+                    if (run) {
+                        HIPCK(hipMemcpyAsync(pin_c + (size_t)pr[b].mir0 * 48, in.d_commitments + (size_t)pr[b].src0 * 48, (size_t)run * 48, hipMemcpyDeviceToHost, st));
+                        HIPCK(hipMemcpyAsync(pin_i + pr[b].mir0, in.d_cell_indices + pr[b].src0, (size_t)run * 8, hipMemcpyDeviceToHost, st));
+                    }
+                    b = e < B ? e + 1 : e;  // (e is the problem beyond the bound that ended the run)
+                }
+                SYNC_CHECKED(st);
+                mirror_c = pin_c;
+                mirror_i = pin_i;
+            }
+            lap("commitments + indices down");
+        }
+        // ---- per problem: validation (verifier.rs:123-164) and de-duplication
         parallel_for(B, T, pool, [&](int b) {
-            status[b] = validate_cell_batch(n_commitments[b], n_indices[b], n_cells[b], n_proofs[b], cell_indices[b]);
-            if (status[b] != OK) return;
-            if (n_cells[b] == 0) { verified[b] = 1; return; }  // verifier.rs:90-93
+            const uint64_t nb = in.cells_of((uint64_t)b);
             Problem& p = pr[b];
-            dedup_commitments(n_commitments[b], commitments[b], p.uniq, p.row);
-            p.n = (int)n_cells[b];
+            if (in.on_device()) {  // (the four lengths are one by construction: what is left is the bound, checked before an index is read, and the indices)
+                status[b] = validate_cell_batch(nb, nb, nb, nb, mirror_i + p.mir0);
+            } else {
+                status[b] = validate_cell_batch(in.n_commitments[b], in.n_indices[b], nb, in.n_proofs[b], in.cell_indices[b]);
+            }
+            if (status[b] != OK) return;
+            if (nb == 0) { verified[b] = 1; return; }  // verifier.rs:90-93
+            if (in.on_device()) dedup_commitments_flat(nb, mirror_c + (size_t)p.mir0 * 48, p.uniq, p.row);
+            else dedup_commitments(nb, in.commitments[b], p.uniq, p.row);
+            p.n = (int)nb;
             p.m = (int)p.uniq.size();
         });
+        lap("validation + de-duplication");
         // ---- chunks of problems: at most CHUNK_CELLS cells per pass (the pinned slab and the arena stay bounded)
         constexpr int CHUNK_CELLS = VM_CHUNK_CELLS;
         bool fold = true;  // one folded pairing check per pass instead of one per problem (falls back to per-problem checks when it fails)
@@ -337,19 +420,59 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             // (k_vm_mul_small), no fold (its 128-bit multiplication per problem is a 1.4 ms chain; <= 2 T pairing checks are one or
             // two rounds of the host threads) -- decode 0.45 + products 1.7 + sums 0.2 ms of GPU instead of ~6
             const bool small = vm_small_max_ != 0 && Bc <= (vm_small_max_ > 0 ? vm_small_max_ : 2 * T);
-            const PassLayout L(n, m, Bc, small);
+            const PassLayout L(n, m, Bc, small, in.leaf);
             grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
             grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
             uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
-            PassHost H{L, pr.data() + b0, cell_indices + b0, cells + b0, proofs + b0, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, verified + b0};
+            PassHost H{L, pr.data() + b0, in.from((uint64_t)b0), mirror_i, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, verified + b0};
             H.tap = tap;
             H.stage();
+            lap("stage (host)");
             int* h_st = H.h_status();
             HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)(n + m) * 4, st));
             HIPCK(hipMemsetAsync(db + L.off_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ, st));
             HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ, st));
             HIPCK(hipMemsetAsync(db + L.off_ste, 0, (size_t)Bc * 4, st));
-            HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
+            if (!in.on_device()) {
+                HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
+            } else {
+                // only the host-made parts go up; proofs and cells move inside HBM, from any byte address, one copy per run of
+                // problems that follow each other in the caller's arrays (a problem refused at validation leaves a gap)
+                HIPCK(hipMemcpyAsync(db + L.off_c, hb + L.off_c, (size_t)m * 48, hipMemcpyHostToDevice, st));
+                HIPCK(hipMemcpyAsync(db + L.off_idx, hb + L.off_idx, L.in_bytes - L.off_idx, hipMemcpyHostToDevice, st));
+                uint64_t run0 = 0, run = 0, at = 0;
+                auto flush = [&] {
+                    if (!run) return;
+                    HIPCK(hipMemcpyAsync(db + L.off_p + (size_t)at * 48, in.d_proofs + (size_t)run0 * 48, (size_t)run * 48, hipMemcpyDeviceToDevice, st));
+                    HIPCK(hipMemcpyAsync(db + L.off_cells + (size_t)at * BYTES_PER_CELL, in.d_cells + (size_t)run0 * BYTES_PER_CELL,
+                                         (size_t)run * BYTES_PER_CELL, hipMemcpyDeviceToDevice, st));
+                    at += run;
+                    run = 0;
+                };
+                for (int i = 0; i < Bc; i++) {
+                    const Problem& p = pr[b0 + i];
+                    if (p.n == 0) continue;
+                    if (run && p.src0 != run0 + run) flush();
+                    if (!run) run0 = p.src0;
+                    run += (uint64_t)p.n;
+                }
+                flush();
+                if (!in.leaf) {  // the reference's transcript hashes every byte on the host: the pass's proofs and cells come down, compacted
+                    HIPCK(hipMemcpyAsync(hb + L.off_p, db + L.off_p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+                    HIPCK(hipMemcpyAsync(hb + L.off_cells, db + L.off_cells, (size_t)n * BYTES_PER_CELL, hipMemcpyDeviceToHost, st));
+                }
+            }
+            const bool hash_waits = in.leaf || in.on_device();  // the host's hashes read what a copy on st brings down
+            if (hash_waits && !slot->hash_inputs_down) HIPCK(hipEventCreateWithFlags(&slot->hash_inputs_down, hipEventDisableTiming));
+            if (in.leaf) {
+                // the leaves of all the pass's cells straight out of the arena (its offsets are multiples of 256: the kernel's 16-byte
+                // loads), in order on the pass's stream: a stream of its own would be a fifth one (see above), and a wave per 64 cells
+                // for 35 dependent compressions is short against the decoding behind it
+                launch::sha256_cell_leaves(n, db + L.off_c, (const int*)(db + L.off_row), (const int*)(db + L.off_idx), db + L.off_p, db + L.off_cells,
+                                           db + L.off_leaf, st, (const int*)(db + L.off_pos));
+                HIPCK(hipMemcpyAsync(hb + L.poff_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+            }
+            if (hash_waits) HIPCK(hipEventRecord(slot->hash_inputs_down, st));
             // ---- challenge-free GPU work: decode (on curve) + subgroup tests of [proofs | commitments], cells, interpolation
             G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
             int* d_stp = (int*)(db + L.off_stp);
@@ -360,8 +483,12 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
             HIPCK(hipMemcpyAsync(h_st + n + m, db + L.off_ste, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
             HIPCK(hipGetLastError());
+            lap("enqueue (host)");
+            if (hash_waits) HIPCK(hipEventSynchronize(slot->hash_inputs_down));
             H.hash_challenges();  // meanwhile, on the host threads
+            lap(in.leaf ? "leaf hashes (GPU) + roots (host)" : "sha256 transcripts (host)");
             SYNC_CHECKED(st);     // (the challenge-free GPU work has long finished under the hashes: a short wait)
+            lap("wait decode");
             int n_live = H.judge(status + b0);  // (a small pass judges again once its subgroup tests are in)
             const bool folded = fold && n_live >= 2 && !small;
             if (folded) H.fold_weights();
@@ -388,8 +515,11 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
             }
             HIPCK(hipMemcpyAsync(hb + L.poff_out, db + L.off_out, (size_t)2 * Bc * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
             SYNC_CHECKED(st);
+            lap("scalars + products + sums (GPU)");
             if (small) n_live = H.judge(status + b0);
             if (tap) {
+                tap->digests = H.digests;
+                if (in.leaf) tap->leaves.assign(hb + L.poff_leaf, hb + L.poff_leaf + (size_t)n * 32);
                 tap->passes++;
                 tap->small = small; tap->folded = folded;
                 tap->sums.assign(hb + L.poff_out, hb + L.poff_out + (size_t)2 * Bc * launch::SIZEOF_JACQ);
@@ -418,6 +548,7 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
                 });
             }
             if (H.device_fault.load()) throw std::runtime_error("many-verification pass left no result");
+            lap("pairing checks (host)");
             b0 = b1;
         }
     } catch (const std::exception& e) {
