@@ -320,6 +320,35 @@ CResult eth_kzg_amd_verify_blob_kzg_proof_batch_device(const DASContext *ctx, ui
                                                        const uint8_t *d_commitments, const uint8_t *d_proofs, bool *verified,
                                                        void *hip_stream);
 
+/* MANY eth_kzg_verify_kzg_proof items in one call, A VERDICT FOR EACH: the throughput form of the check behind the point-evaluation
+ * precompile, for callers that hold (commitment, z, y, proof) tuples and need to know WHICH of them is wrong (the batch call above
+ * computes z and y from blobs and gives one verdict for all).  Item i: commitments[i] / proofs[i] -> 48 bytes, zs[i] / ys[i] -> 32
+ * bytes big-endian.  Per item the result is exactly what eth_kzg_verify_kzg_proof says of that item alone, in its order of checks
+ * (crates/eip4844/src/verifier.rs:19-44):
+ *   status[i] = 2  the commitment or the proof is not a canonical point of the subgroup (also when z or y is bad as well),
+ *   else      = 1  z or y is >= r,
+ *   else      = 0  and verified[i] is the verdict.  verified[i] is false whenever status[i] != 0.  status may be NULL.
+ * The call: n = 0 is Ok; n > 2^24, or a NULL array with n > 0, is Err("InvalidInput...") before the context is touched; otherwise Err
+ * only for a device failure.  How: csrc/verify_host.hpp (PointProofTranscript) states the check once -- the items of a pass (at most
+ * 16384; not part of the contract) are hashed into leaves, the leaves into a seed, the seed into a 127-bit weight rho_i per item, and
+ * ONE pairing check of  ( sum rho_i pi_i , sum rho_i (C_i + z_i pi_i - y_i G) )  over the pass's valid items passes only if every
+ * one of them is valid (error 2^-127: no weight is known before every input byte is fixed); if it fails the wrong items are searched
+ * by checking the pairs of sub-ranges down to single items, and a single item whose own pair fails is wrong exactly.  The scalar
+ * multiplications run one lane each on the GPU (csrc/k_point_many.hip), the pass on a pass slot of the many-verification: the call
+ * does not take the context's big lock and runs next to every other entry point.  The identity is a valid commitment and a valid proof.
+ * Host form: cut into contiguous slices by item over the context's device list; the host threads hash the leaves.
+ * Device form: flat arrays in this GPU's HBM -- the 48-byte arrays from any byte address, d_zs / d_ys 4-byte aligned (as
+ * eth_kzg_amd_compute_kzg_proof_device) -- verified / status HOST memory.  Synchronous; work already queued on `hip_stream` (NULL: the
+ * default stream) is waited for.  The GPU hashes the leaves: nothing but the status words, the n x 32 leaf digests and the sums come
+ * down, and only the weights go up.  Runs on the device that owns the buffers: all four pointers are resolved, and anything but device
+ * memory of ONE device of the context is Err("InvalidInput...").  When it pays: INTEGRATION.md. */
+CResult eth_kzg_amd_verify_kzg_proof_many(const DASContext *ctx, uint64_t n, const uint8_t *const *commitments,
+                                          const uint8_t *const *zs, const uint8_t *const *ys, const uint8_t *const *proofs,
+                                          bool *verified, int32_t *status);
+CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext *ctx, uint64_t n, const uint8_t *d_commitments, const uint8_t *d_zs,
+                                                 const uint8_t *d_ys, const uint8_t *d_proofs, bool *verified, int32_t *status,
+                                                 void *hip_stream);
+
 /* verify_cell_kzg_proof_batch on flat arrays in this GPU's HBM: n * 48 commitment bytes (one per cell, NOT deduplicated, as in
  * the host form), n indices, n * 2048 cell bytes, n * 48 proof bytes.  The GPU's part reads cells and proofs where they are;
  * the transcript hash runs on a host core, so its bytes come down (in chunks, under the hash) and the call is synchronous;

@@ -152,6 +152,25 @@ int eth_kzg_amd_test_verify_many_sums_device(const DASContext *ctx, uint64_t n_b
                                              int32_t *probe_ranges, uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes,
                                              uint8_t *digests32, uint8_t *leaves32);
 
+/* eth_kzg_amd_verify_kzg_proof_many / _many_device with a tap (csrc/point_many.hip; the statement is tests/point_many.py): exactly the
+ * public call's launches, on the context's first device.  on_device = 0: commitments / zs / ys / proofs are the host form's pointer
+ * lists; 1: the device form's flat arrays in device memory.  1 <= n <= 2^20.  forced_pass: 0 = the product's pass size, else the call is
+ * cut into passes of that many items.  Outputs (host; the passes run one after the other so that they come in order):
+ *   verified[n], status[n]: as the public call gives them.
+ *   pass_starts[*n_passes + 1]: the first item of every pass, then n; returns 3 before any launch if there would be more than
+ *     max_passes passes.
+ *   leaves32[n][32], seeds32[passes][32], rho[n][4] (little-endian words as uploaded): LEAF_i, SEED and rho_i of every item / pass.
+ *   fold96[passes]: compress(first sum) | compress(second sum) of the full-range pair of every pass; fold_verdicts[passes]: whether it
+ *     passed the pairing check.
+ *   probes4[i] = (pass, lo, hi, passed), lo <= position in the pass < hi, and probe_sums96[i] = that range's pair: the probes of the
+ *     searches in the order they were made, the first max_probes of them; *n_probes = how many were made.
+ * Synchronous; returns 0 on success, the library's status codes otherwise. */
+int eth_kzg_amd_test_verify_kzg_proof_many_sums(const DASContext *ctx, uint64_t n, int on_device, const void *commitments, const void *zs,
+                                                const void *ys, const void *proofs, uint64_t forced_pass, int32_t *verified, int32_t *status,
+                                                uint64_t *pass_starts, uint64_t max_passes, uint64_t *n_passes, uint8_t *leaves32,
+                                                uint8_t *seeds32, uint32_t *rho, uint8_t *fold96, int32_t *fold_verdicts, int32_t *probes4,
+                                                uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes);
+
 /* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode in recover.hip, exactly the launches recovery runs).  R >= 1 blobs; blob r has
  * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
  * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_compute_blob_kzg_proof_batch", "eth_kzg_amd_compute_kzg_proof_batch",
     "eth_kzg_amd_compute_blob_kzg_proof_device", "eth_kzg_amd_compute_kzg_proof_device",
     "eth_kzg_amd_verify_blob_kzg_proof_batch_device",
+    "eth_kzg_amd_verify_kzg_proof_many", "eth_kzg_amd_verify_kzg_proof_many_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
     "eth_kzg_amd_set_profiling", "eth_kzg_amd_get_stage_times",
     "eth_kzg_amd_comm_probe", "eth_kzg_amd_comm_unique_id", "eth_kzg_amd_comm_init", "eth_kzg_amd_comm_info",
@@ -86,6 +87,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_proofs_from_sums", "eth_kzg_amd_test_linmap_program",
     "eth_kzg_amd_test_cell_leaf_digests", "eth_kzg_amd_test_verify_cells_inputs_ex",
     "eth_kzg_amd_test_verify_many_sums_ex", "eth_kzg_amd_test_verify_many_sums_device",
+    "eth_kzg_amd_test_verify_kzg_proof_many_sums",
 ]
 
 _lib = None
@@ -184,6 +186,8 @@ def load_library():
         "eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex": [P, U64, P, P, P, P, C.c_uint32, P, P],
         "eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex": [P, U64, P, P, P, P, P, P, P, P, C.c_uint32, P, P],
         "eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P],
+        "eth_kzg_amd_verify_kzg_proof_many": [P, U64, P, P, P, P, P, P],
+        "eth_kzg_amd_verify_kzg_proof_many_device": [P, U64, P, P, P, P, P, P, P],
     }.items():
         if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
             getattr(lib, name).restype = CResult
@@ -218,6 +222,7 @@ def load_library():
         "eth_kzg_amd_test_verify_cells_inputs_ex": [P, U64, C.c_int, P, P, P, P, C.c_uint32, P, P],
         "eth_kzg_amd_test_verify_many_sums_ex": [P, U64, P, P, P, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
         "eth_kzg_amd_test_verify_many_sums_device": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
+        "eth_kzg_amd_test_verify_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -651,6 +656,41 @@ class DASContext:
         ok = C.c_bool(False)
         self._check(self._lib.eth_kzg_verify_kzg_proof(self._ctx, bytes(commitment), bytes(z), bytes(y), bytes(proof), C.byref(ok)))
         return bool(ok.value)
+
+    def prepare_verify_kzg_proof_many(self, items):
+        """items = [(commitment, z, y, proof), ...]: marshal them into the pointer tables of eth_kzg_amd_verify_kzg_proof_many ONCE and
+        return a zero-argument callable that runs the call and returns (verified list[bool], status list[int]) -- per item what
+        verify_kzg_proof says of it alone: status 2 a bad G1 point, else 1 z or y >= r (what the single form raises as KzgError), else 0
+        and the verdict.  A wrong byte length cannot cross the C ABI and raises InvalidLength here."""
+        n = len(items)
+        if any(len(c) != 48 or len(z) != 32 or len(y) != 32 or len(p) != 48 for c, z, y, p in items):
+            raise KzgError("InvalidLength")
+        ca, k1 = _flat_ptrs([it[0] for it in items], 48)
+        za, k2 = _flat_ptrs([it[1] for it in items], 32)
+        ya, k3 = _flat_ptrs([it[2] for it in items], 32)
+        pa, k4 = _flat_ptrs([it[3] for it in items], 48)
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+
+        def run(_keep=(k1, k2, k3, k4)):
+            self._check(self._lib.eth_kzg_amd_verify_kzg_proof_many(self._ctx, n, _vp(ca), _vp(za), _vp(ya), _vp(pa), ver, st))
+            return [bool(v) for v in ver][:n], list(st)[:n]
+        return run
+
+    def verify_kzg_proof_many(self, items):
+        """Many verify_kzg_proof items in one call, a verdict for each (see prepare_verify_kzg_proof_many)."""
+        return self.prepare_verify_kzg_proof_many(items)()
+
+    def verify_kzg_proof_many_device(self, n, d_commitments, d_zs, d_ys, d_proofs, stream=None):
+        """The same on flat arrays in device memory (eth_kzg_amd_verify_kzg_proof_many_device): integer device addresses of n*48
+        commitment bytes, n*32 z and y bytes (big-endian, 4-byte aligned) and n*48 proof bytes.  -> (verified list[bool], status
+        list[int]).  Synchronous; waits for what `stream` (None: the default stream) has queued.  The leaves are hashed on the GPU."""
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_verify_kzg_proof_many_device(
+            self._ctx, n, C.c_void_p(d_commitments), C.c_void_p(d_zs), C.c_void_p(d_ys), C.c_void_p(d_proofs), ver, st,
+            C.c_void_p(stream) if stream else None))
+        return [bool(v) for v in ver][:n], list(st)[:n]
 
     def verify_blob_kzg_proof(self, blob, commitment, proof):
         if len(blob) != BYTES_PER_BLOB or len(commitment) != 48 or len(proof) != 48:

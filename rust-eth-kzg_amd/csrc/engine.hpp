@@ -79,6 +79,36 @@ struct VerifyManyInput {
     }
 };
 
+// Many verify_kzg_proof items in one call (point_many.hip; the statement: verify_host.hpp, PointProofTranscript).  Two sources:
+//   pointer lists on the host: commitments[i] / proofs[i] -> 48 bytes, zs[i] / ys[i] -> 32 bytes big-endian
+//   flat arrays in this GPU's HBM (on_device): n x 48 / n x 32 bytes; the 48-byte arrays from any byte address, zs and ys 4-byte
+//     aligned; what user_stream has queued produces them
+struct PointManyInput {
+    const uint8_t *const *commitments = nullptr, *const *zs = nullptr, *const *ys = nullptr, *const *proofs = nullptr;
+    const uint8_t *d_commitments = nullptr, *d_zs = nullptr, *d_ys = nullptr, *d_proofs = nullptr;
+    bool on_device = false;
+    hipStream_t user_stream = nullptr;
+    PointManyInput from(uint64_t lo) const {
+        PointManyInput s = *this;
+        if (on_device) { s.d_commitments += lo * 48; s.d_zs += lo * 32; s.d_ys += lo * 32; s.d_proofs += lo * 48; }
+        else { s.commitments += lo; s.zs += lo; s.ys += lo; s.proofs += lo; }
+        return s;
+    }
+};
+// Tap of such a call (null in every product call; the stage hook test_verify_kzg_proof_many_sums sets it): copies of what the passes'
+// pinned read-backs held after the syncs they make anyway.  pass_size: 0 = the product's (POINT_MANY_PASS), else a forced one.
+struct PointManyTap {
+    int pass_size = 0;
+    std::vector<uint64_t> pass_starts;   // the first item of every pass, then n
+    std::vector<uint8_t> leaves;         // [n][32]
+    std::vector<uint8_t> seeds;          // [passes][32]
+    std::vector<uint32_t> rho;           // [n][4], as uploaded
+    std::vector<uint8_t> fold;           // [passes][2] JacQ: the full-range pair
+    std::vector<int> fold_verdict;       // [passes]
+    std::vector<int> probes;             // the searches' probes in order: pass, lo, hi (positions in the pass), passed
+    std::vector<uint8_t> probe_sums;     // [probe][2] JacQ
+};
+
 // How a single cell verification takes its Fiat-Shamir challenge (verify.hip).  Null or `leaf` false: the reference's transcript, one
 // SHA-256 over the whole batch on a host core.  leaf: the leaf-hashed challenge (verify_host.hpp: CellLeafTranscript) -- one SHA-256
 // per cell on the GPU, out of the arena the inputs are staged into anyway, and one short SHA-256 over the digests on the host.
@@ -253,6 +283,10 @@ public:
     int verify_blob_kzg_proof_batch_host(uint64_t n_blobs, const uint8_t* const* blobs, uint64_t n_commitments,
                                          const uint8_t* const* commitments, uint64_t n_proofs, const uint8_t* const* proofs,
                                          int* verified, G1Affine* sums2 = nullptr);
+    // MANY verify_kzg_proof items in one call, a verdict each (point_many.hip): status[i] = ERR_G1 / ERR_SCALAR / OK in the single
+    // call's order of checks, verified[i] set when OK.  Returns ERR_DEVICE on a HIP failure, OK otherwise.  Runs on a pass slot of the
+    // many-verification: does not take mu_.
+    int verify_kzg_proof_many(uint64_t n, const PointManyInput& in, int* verified, int* status, PointManyTap* tap = nullptr);
     // ---- EIP-4844 proofs for MANY blobs (eip4844.hip; crates/eip4844/src/prover.rs:37-92 per blob) ----
     // Device-resident: d_blobs n * 131072 B, d_commitments / d_out_proofs n * 48 B, d_z / d_out_y n * 32 B big-endian (4-byte aligned);
     // h_status: n ints on the host or null.  status per blob in the single call's order: 1 the blob holds a non-canonical element,
@@ -334,6 +368,13 @@ public:
     int test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
                                  uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
                                  uint8_t* digests32, uint8_t* leaves32);
+    // verify_kzg_proof_many with its tap set and, if forced_pass > 0, passes of that many items: verdicts and statuses as the call gives
+    // them, the pass bounds (pass_starts: up to max_passes + 1 entries), leaves32[n][32], seeds32 / fold96 / fold_verdicts per pass,
+    // rho[n][4], the probes (probes4[i] = pass, lo, hi, passed; probe_sums96[i]) up to max_probes of them; pairs compressed on the host
+    int test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in, uint64_t forced_pass, int32_t* verified, int32_t* status,
+                                        uint64_t* pass_starts, uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho,
+                                        uint8_t* fold96, int32_t* fold_verdicts, int32_t* probes4, uint8_t* probe_sums96, uint64_t max_probes,
+                                        uint64_t* n_probes);
     // the Reed-Solomon decoder of recovery on its own: rs_decode (verify.hip) with its tap set, behind the staging of recover_batch_to_coeffs
     // (flat_source = 0) or of recover_cells_and_kzg_proofs_device (1); outputs canonical big-endian on the host, each may be null
     int test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,

@@ -1,5 +1,5 @@
 // Shared by the translation units of the engine (engine.hip: context life cycle and constants; engine_tables.hip: window tables,
-// their registry and builder; engine_prover.hip: the prover paths; verify.hip, verify_many.hip, recover.hip, eip4844.hip: the other entry points;
+// their registry and builder; engine_prover.hip: the prover paths; verify.hip, verify_many.hip, point_many.hip, recover.hip, eip4844.hip: the other entry points;
 // engine_testhooks.hip: stage-level test hooks).  Not installed, and not for the kernel files (k_*.hip keep to kcommon.hpp).
 #pragma once
 #include "engine.hpp"

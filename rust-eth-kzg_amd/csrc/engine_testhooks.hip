@@ -569,6 +569,46 @@ int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& 
     return OK;
 }
 
+// The public call's passes with their tap set (point_many.hip), optionally cut at a forced pass size.
+int Engine::test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in, uint64_t forced_pass, int32_t* verified, int32_t* status,
+                                            uint64_t* pass_starts, uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho,
+                                            uint8_t* fold96, int32_t* fold_verdicts, int32_t* probes4, uint8_t* probe_sums96, uint64_t max_probes,
+                                            uint64_t* n_probes) {
+    if (n < 1 || n > (1u << 20) || forced_pass > (1u << 20)) return ERR_INPUT;
+    const uint64_t pass = forced_pass ? forced_pass : (uint64_t)POINT_MANY_PASS;
+    if ((n + pass - 1) / pass > max_passes) return ERR_INPUT;
+    std::vector<int> ver(n), st(n);
+    PointManyTap tap;
+    tap.pass_size = (int)forced_pass;
+    const int rc = verify_kzg_proof_many(n, in, ver.data(), st.data(), &tap);
+    if (rc) return rc;
+    auto compress2 = [](uint8_t* out96, const uint8_t* two) {  // a slot that still holds its poison comes out as 0xff bytes
+        for (int j = 0; j < 2; j++) {
+            JacQ s;
+            memcpy(&s, two + (size_t)j * sizeof(JacQ), sizeof(JacQ));
+            if (s.x.v[0] == 0xffffffffu && s.z.v[0] == 0xffffffffu) memset(out96 + 48 * j, 0xff, 48);
+            else g1_compress(out96 + 48 * j, to_affine(jac_from_jacq(s)));
+        }
+    };
+    for (uint64_t i = 0; i < n; i++) { verified[i] = st[i] == OK && ver[i] != 0; status[i] = st[i]; }
+    const uint64_t np = tap.pass_starts.size() - 1;
+    *n_passes = np;
+    for (uint64_t p = 0; p <= np; p++) pass_starts[p] = tap.pass_starts[p];
+    memcpy(leaves32, tap.leaves.data(), (size_t)n * 32);
+    memcpy(rho, tap.rho.data(), (size_t)n * 16);
+    memcpy(seeds32, tap.seeds.data(), (size_t)np * 32);
+    for (uint64_t p = 0; p < np; p++) {
+        compress2(fold96 + 96 * p, tap.fold.data() + (size_t)2 * p * sizeof(JacQ));
+        fold_verdicts[p] = tap.fold_verdict[p];
+    }
+    *n_probes = tap.probes.size() / 4;
+    for (uint64_t q = 0; q < *n_probes && q < max_probes; q++) {
+        for (int j = 0; j < 4; j++) probes4[4 * q + j] = tap.probes[4 * q + j];
+        compress2(probe_sums96 + 96 * q, tap.probe_sums.data() + (size_t)2 * q * sizeof(JacQ));
+    }
+    return OK;
+}
+
 // The Reed-Solomon decoder of recovery on its own: the masks, slots and cell bytes staged as recover_batch_to_coeffs (list form) or
 // recover_cells_and_kzg_proofs_device (flat form) stage them, then rs_decode with its tap.  The caller (c_api_hooks.cpp) has validated
 // the counts and indices.  Outputs canonical big-endian.

@@ -36,10 +36,10 @@ void glv_split(void* scalars, size_t n, hipStream_t st) {
 GLV_DECL(8) GLV_DECL(12) GLV_DECL(14) GLV_DECL(15) GLV_DECL(16)
 #undef GLV_DECL
 void preload_k_ntt(); void preload_k_g1fft(); void preload_k_g1circ(); void preload_k_g1misc(); void preload_k_verify();
-void preload_k_verify_many(); void preload_k_4844(); void preload_k_sha256(); void preload_k_g1slp(); void preload_k_table();
+void preload_k_verify_many(); void preload_k_point_many(); void preload_k_4844(); void preload_k_sha256(); void preload_k_g1slp(); void preload_k_table();
 void preload_code_objects() {
     preload_k_msm(); preload_k_msm_glv8(); preload_k_msm_glv12(); preload_k_msm_glv14(); preload_k_msm_glv15(); preload_k_msm_glv16();
-    preload_k_ntt(); preload_k_g1fft(); preload_k_g1circ(); preload_k_g1misc(); preload_k_verify(); preload_k_verify_many();
+    preload_k_ntt(); preload_k_g1fft(); preload_k_g1circ(); preload_k_g1misc(); preload_k_verify(); preload_k_verify_many(); preload_k_point_many();
     preload_k_4844(); preload_k_sha256(); preload_k_g1slp(); preload_k_table();
 }
 bool glv_width_supported(int c) {

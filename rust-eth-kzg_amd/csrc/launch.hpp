@@ -189,6 +189,18 @@ void vm_fold(const void* sums, const uint32_t* rho, void* prod, void* out2, int 
 // out[r][2] = the weighted pairs summed over problems ranges[r][0] .. ranges[r][1] - 1 (prod as vm_fold left it)
 void vm_fold_ranges(const void* prod, const int* ranges /*[n_ranges][2], device*/, void* out /*[n_ranges][2] JacQ*/, int n_ranges, hipStream_t st);
 
+// k_point_many.hip: many verify_kzg_proof items in one pass (point_many.hip), one lane per scalar multiplication
+// bodies[n][176] = "RCKZGPROOFLEAF_1" | commitment | z | y | proof per item, for sha256_many; all five arrays 4-byte aligned
+void pm_leaf_bodies(const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys, const uint8_t* proofs, uint8_t* bodies, int n, hipStream_t st);
+// status[i] = 2 if point_status[n + i] (commitment) or point_status[i] (proof), else 1 if z_bad[i] or y_bad[i], else 0
+void pm_status(const int* point_status /*[proofs n | commitments n]*/, const int* z_bad, const int* y_bad, int* status, int n, hipStream_t st);
+// pts = [proofs n | commitments n] (G1Affine), gen = G (G1Affine), z / y Montgomery Fr, rho[n][4].  pairs[2 i] = rho_i pi_i;
+// terms[3][n] = rho C | (rho z) pi | (rho y) G; an item whose status is not 0 gets the identity everywhere (JacQ)
+void pm_mul(const void* pts, const void* gen, const void* z_mont, const void* y_mont, const uint32_t* rho, const int* status, void* pairs, void* terms,
+            int n, const Fp12w& beta, hipStream_t st);
+// pairs[2 i + 1] = terms[0][i] + terms[1][i] - terms[2][i], exact
+void pm_pairs(const void* terms, void* pairs, int n, hipStream_t st);
+
 // k_4844.hip
 void quotient_by_linear(int n, const void* coeffs, const void* z_mont, void* quotient, void* y_out, hipStream_t st);
 // n x 32 big-endian bytes -> Montgomery Fr.  reduce: the value mod r (a digest becomes a challenge; bad is not touched); otherwise a

@@ -1,0 +1,242 @@
+// eth_kzg_amd_verify_kzg_proof_many / _many_device: MANY independent verify_kzg_proof items (commitment, z, y, proof) in one call, a
+// verdict and a status for each -- per item exactly what Verifier::verify_kzg_proof says of it alone (crates/eip4844/src/verifier.rs:
+// 19-44; eip4844.hip: verify_kzg_proof_host is the single call and is not touched).  The statement of the check -- leaves, seed, weights,
+// the pair of a range, why a passing full-range pair means valid items only -- is verify_host.hpp (PointProofTranscript).
+// A call is cut into passes of at most POINT_MANY_PASS items; a pass runs on a PASS SLOT of the many-verification (verify_many.hip: the
+// slot's own lock, arena, pinned slab and stream; nothing here takes the context's big lock), and a call of several passes runs them on
+// up to three slots side by side: one pass's staging, hashing and pairings on the host threads under another's products on the GPU.
+//   host threads : host form: gather the items into the pinned slab, one SHA-256 leaf per item (behind the GPU's decoding); both forms:
+//                  the seed and the weights, ONE 2-pairing check of the full-range pair per pass, and only if that fails the SEARCH of
+//                  vm_search.hpp over sub-ranges of the resident pairs, down to single items (single items are probes like the others:
+//                  the per-item pairs never come down)
+//   GPU          : device form: the four arrays device-to-device into the arena (from any byte address), the leaves' bodies gathered
+//                  and hashed (k_pm_leaf_bodies, k_sha256_many); both: g1_decompress2 of [proofs | commitments], fr_from_be32 of z and
+//                  y, the status words, then the four scalar multiplications per item, one lane each (k_point_many.hip: k_pm_mul), the
+//                  per-item pairs (k_pm_pairs), and the full-range fold in TWO LEVELS of k_vm_fold_ranges: ranges of 128 items, one
+//                  block each, then one block over those sums.  (k_vm_fold_sum's single block would add 128 points per lane one
+//                  after the other at 16384 items, a serial tail of ~130 dependent additions behind products that fill the chip; the
+//                  two levels are 1 + 7 and 1 + 7 dependent additions.)
+// Down the link go the status words, the n x 32 leaf digests (device form) and the sums; up go the weights (and the host form's items).
+#include "vm_search.hpp"
+
+namespace kzg {
+
+namespace {
+constexpr int FOLD_SPAN = 128;  // items per first-level range of the full-range fold: one per lane of k_vm_fold_ranges' trees
+
+struct PointPassLayout {
+    const int n;
+    const int n_l1 = (n + FOLD_SPAN - 1) / FOLD_SPAN;  // first-level ranges of the full-range fold
+    const int max_ranges = std::min(n, 2048);          // probes per level of the search
+    static constexpr size_t JACQ = launch::SIZEOF_JACQ;
+    Carve d;  // (members are initialised in the order they stand here)
+    // inputs: one upload in the host form, device-to-device copies in the device form; then the fold's ranges and the weights
+    const size_t off_p = d.take((size_t)n * 48), off_c = d.take((size_t)n * 48), off_z = d.take((size_t)n * 32), off_y = d.take((size_t)n * 32),
+                 in_bytes = d.end, off_frng = d.take((size_t)(n_l1 + 1) * 8), off_rho = d.take((size_t)n * 16), in2_bytes = d.end;
+    Carve h = d;  // pinned read-backs behind the inputs
+    const size_t poff_st = h.take((size_t)n * 4), poff_fold = h.take(2 * JACQ), poff_rng = h.take((size_t)max_ranges * 8),
+                 poff_rsum = h.take((size_t)2 * max_ranges * JACQ), poff_leaf = h.take((size_t)n * 32), pin_bytes = h.end;
+    // device only
+    const size_t off_pts = d.take((size_t)2 * n * sizeof(G1Affine)), off_stp = d.take((size_t)2 * n * 4), off_zbad = d.take((size_t)n * 4),
+                 off_ybad = d.take((size_t)n * 4), off_st = d.take((size_t)n * 4), off_zm = d.take((size_t)n * sizeof(Fr)),
+                 off_ym = d.take((size_t)n * sizeof(Fr)), off_pairs = d.take((size_t)2 * n * JACQ), off_terms = d.take((size_t)3 * n * JACQ),
+                 off_l1 = d.take((size_t)2 * n_l1 * JACQ), off_fold = d.take(2 * JACQ), off_rng = d.take((size_t)max_ranges * 8),
+                 off_rsum = d.take((size_t)2 * max_ranges * JACQ), off_bodies = d.take((size_t)n * PointProofTranscript::LEAF_BYTES),
+                 off_leaf = d.take((size_t)n * 32), dev_bytes = d.end;
+    explicit PointPassLayout(int n_) : n(n_) {}
+};
+}  // namespace
+
+int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* verified, int* status, PointManyTap* tap) {
+    const int n_all = (int)n64;
+    for (int i = 0; i < n_all; i++) { verified[i] = 0; status[i] = OK; }
+    if (n_all == 0) return OK;
+    const int P = tap && tap->pass_size > 0 ? tap->pass_size : POINT_MANY_PASS;
+    std::vector<uint64_t> starts;
+    for (uint64_t lo = 0; lo < n64; lo = point_pass_end(n64, lo, (uint64_t)P)) starts.push_back(lo);
+    starts.push_back(n64);
+    const int n_passes = (int)starts.size() - 1;
+    if (tap) {
+        tap->pass_starts = starts;
+        tap->leaves.assign((size_t)n_all * 32, 0);
+        tap->rho.assign((size_t)n_all * 4, 0);
+        tap->seeds.assign((size_t)n_passes * 32, 0);
+        tap->fold.assign((size_t)n_passes * 2 * launch::SIZEOF_JACQ, 0xff);
+        tap->fold_verdict.assign(n_passes, -1);
+    }
+    const int T = vm::host_threads(knobs_);
+    std::call_once(vm_pool_once_, [&] { vm_pool_.reset(new HostPool(T > 1 ? T - 1 : 1, [d = dev_] { (void)hipSetDevice(d); })); });
+    HostPool* const pool = vm_pool_.get();
+    const pairing::G2Prepared* const vk[2] = {g2_tau1_.get(), g2_neg_gen_.get()};  // [tau]_2, -[1]_2: the single call's (eip4844.hip)
+
+    // one pass: items [lo, hi) of the call on a pass slot
+    auto run_pass = [&](int pass) {
+        const uint64_t lo = starts[pass];
+        const int n = (int)(starts[pass + 1] - lo);
+        const PointManyInput src = in.from(lo);
+        int* const ver = verified + lo;
+        int* const stat = status + lo;
+        auto slot_lease = vm_slots_.acquire([&](int k) { return mutex_is_free(work_[1 + k % (NW - 1)].mu); });
+        VmSlot* slot = &vm_slot_[slot_lease.index];
+        HIPCK(hipSetDevice(dev_));
+        const int slot_index = (int)(slot - vm_slot_);
+        hipStream_t st = work_[1 + slot_index % (NW - 1)].stream ? work_[1 + slot_index % (NW - 1)].stream : stream_;  // (verify_many.hip: why no stream of its own)
+        TraceLap lap{knobs_.trace, "verify_kzg_proof_many"};
+        const PointPassLayout L(n);
+        grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
+        grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
+        uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
+        int* const h_st = (int*)(hb + L.poff_st);
+        uint8_t* const h_leaf = hb + L.poff_leaf;
+        // stale contents of the persistent slab must fail closed: status words and result slots are poisoned
+        memset(h_st, 0xff, (size_t)n * 4);
+        memset(hb + L.poff_fold, 0xff, 2 * launch::SIZEOF_JACQ);
+        memset(h_leaf, 0xff, (size_t)n * 32);
+        HIPCK(hipMemsetAsync(db + L.off_st, 0xff, (size_t)n * 4, st));
+        HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)2 * n * 4, st));
+        HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, 2 * launch::SIZEOF_JACQ, st));
+        // ---- the items into the arena
+        if (src.on_device) {
+            if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
+            if (src.user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
+                HIPCK(hipEventRecord(slot->ordered, src.user_stream));
+                HIPCK(hipStreamWaitEvent(st, slot->ordered, 0));
+            }
+            HIPCK(hipMemcpyAsync(db + L.off_p, src.d_proofs, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_c, src.d_commitments, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_z, src.d_zs, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_y, src.d_ys, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
+            launch::pm_leaf_bodies(db + L.off_c, db + L.off_z, db + L.off_y, db + L.off_p, db + L.off_bodies, n, st);
+            launch::sha256_many(n, nullptr, 0, db + L.off_bodies, PointProofTranscript::LEAF_BYTES, (uint32_t)PointProofTranscript::LEAF_BYTES, nullptr, 0, 0,
+                                db + L.off_leaf, st);
+            HIPCK(hipMemcpyAsync(h_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        } else {
+            parallel_for(n, T, pool, [&](int i) {
+                memcpy(hb + L.off_p + (size_t)i * 48, src.proofs[i], 48);
+                memcpy(hb + L.off_c + (size_t)i * 48, src.commitments[i], 48);
+                memcpy(hb + L.off_z + (size_t)i * 32, src.zs[i], 32);
+                memcpy(hb + L.off_y + (size_t)i * 32, src.ys[i], 32);
+            });
+            lap("stage (host)");
+            HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
+        }
+        // ---- GPU work that needs no weight: decoding + subgroup tests of [proofs | commitments], z and y, the status words
+        G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
+        int* d_stp = (int*)(db + L.off_stp);
+        launch::g1_decompress2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, n, beta_, st);
+        launch::fr_from_be32(n, db + L.off_z, db + L.off_zm, (int*)(db + L.off_zbad), /*reduce=*/false, st);
+        launch::fr_from_be32(n, db + L.off_y, db + L.off_ym, (int*)(db + L.off_ybad), /*reduce=*/false, st);
+        launch::pm_status(d_stp, (const int*)(db + L.off_zbad), (const int*)(db + L.off_ybad), (int*)(db + L.off_st), n, st);
+        HIPCK(hipMemcpyAsync(h_st, db + L.off_st, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipGetLastError());
+        lap("enqueue (host)");
+        if (!src.on_device) {  // meanwhile, on the host threads: the leaves, from the caller's bytes as they lie in the slab
+            parallel_for(n, T, pool, [&](int i) {
+                PointProofTranscript::leaf(hb + L.off_c + (size_t)i * 48, hb + L.off_z + (size_t)i * 32, hb + L.off_y + (size_t)i * 32,
+                                           hb + L.off_p + (size_t)i * 48, h_leaf + (size_t)i * 32);
+            });
+            lap("leaf hashes (host)");
+        }
+        SYNC_CHECKED(st);
+        lap(src.on_device ? "decode + leaf hashes (GPU)" : "wait decode");
+        // ---- statuses; the seed and the weights of ALL the items of the pass
+        std::vector<char> live(n, 0);
+        int n_live = 0;
+        for (int i = 0; i < n; i++) {
+            if (h_st[i] != OK && h_st[i] != ERR_SCALAR && h_st[i] != ERR_G1) throw std::runtime_error("point verification pass left no status");
+            stat[i] = h_st[i];
+            if (h_st[i] == OK) { live[i] = 1; n_live++; }
+        }
+        uint8_t seed[32];
+        PointProofTranscript::seed((uint64_t)n, h_leaf, seed);
+        uint32_t* const h_rho = (uint32_t*)(hb + L.off_rho);
+        parallel_for(n, T, pool, [&](int i) { fold_weight(seed, (uint64_t)i, h_rho + 4 * (size_t)i); });
+        int* const h_frng = (int*)(hb + L.off_frng);
+        for (int r = 0; r < L.n_l1; r++) { h_frng[2 * r] = r * FOLD_SPAN; h_frng[2 * r + 1] = std::min(n, (r + 1) * FOLD_SPAN); }
+        h_frng[2 * L.n_l1] = 0; h_frng[2 * L.n_l1 + 1] = L.n_l1;
+        lap("seed + weights (host)");
+        if (tap) {
+            memcpy(tap->leaves.data() + lo * 32, h_leaf, (size_t)n * 32);
+            memcpy(tap->seeds.data() + (size_t)pass * 32, seed, 32);
+            memcpy(tap->rho.data() + lo * 4, h_rho, (size_t)n * 16);
+        }
+        // ---- the products, the per-item pairs, the full-range pair (also when no item is live: the pair is then the identity twice)
+        HIPCK(hipMemcpyAsync(db + L.off_frng, hb + L.off_frng, L.in2_bytes - L.off_frng, hipMemcpyHostToDevice, st));
+        launch::pm_mul(d_pts, d_srs_, db + L.off_zm, db + L.off_ym, (const uint32_t*)(db + L.off_rho), (const int*)(db + L.off_st), db + L.off_pairs,
+                       db + L.off_terms, n, beta_, st);
+        launch::pm_pairs(db + L.off_terms, db + L.off_pairs, n, st);
+        const int* d_frng = (const int*)(db + L.off_frng);
+        if (L.n_l1 == 1) {
+            launch::vm_fold_ranges(db + L.off_pairs, d_frng, db + L.off_fold, 1, st);
+        } else {
+            launch::vm_fold_ranges(db + L.off_pairs, d_frng, db + L.off_l1, L.n_l1, st);
+            launch::vm_fold_ranges(db + L.off_l1, d_frng + 2 * L.n_l1, db + L.off_fold, 1, st);
+        }
+        HIPCK(hipMemcpyAsync(hb + L.poff_fold, db + L.off_fold, 2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
+        HIPCK(hipGetLastError());
+        SYNC_CHECKED(st);
+        lap("products + pairs + fold (GPU)");
+        // ---- verdicts: ONE pairing check of the full-range pair; only if that fails the search
+        const int v = vm::check_pair((const JacQ*)(hb + L.poff_fold), vk);
+        if (v < 0) throw std::runtime_error("point verification pass left no folded result");
+        if (tap) {
+            memcpy(tap->fold.data() + (size_t)pass * 2 * launch::SIZEOF_JACQ, hb + L.poff_fold, 2 * launch::SIZEOF_JACQ);
+            tap->fold_verdict[pass] = v;
+        }
+        if (v == 1) {
+            for (int i = 0; i < n; i++) ver[i] = live[i];
+        } else {
+            std::atomic<int> device_fault{0};
+            std::vector<int> probes;
+            vm::SearchView S;
+            S.n = n; S.max_ranges = L.max_ranges; S.T = T; S.pool = pool; S.hb = hb;
+            S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.off_rng = L.off_rng; S.off_pairs = L.off_pairs; S.off_rsum = L.off_rsum;
+            S.vk = vk; S.live = live.data(); S.verified = ver; S.device_fault = &device_fault;
+            if (tap) { S.tap_probes = &probes; S.tap_probe_sums = &tap->probe_sums; }
+            vm::search_wrong_proofs(S, n_live, db, st);
+            if (device_fault.load()) throw std::runtime_error("point verification pass left no result");
+            for (size_t q = 0; tap && q + 2 < probes.size(); q += 3) {
+                const int rec[4] = {pass, probes[q], probes[q + 1], probes[q + 2]};
+                tap->probes.insert(tap->probes.end(), rec, rec + 4);
+            }
+        }
+        lap("pairing checks (host)");
+    };
+
+    // passes side by side on the pass slots (the tap's arrays are filled in order: a tapped call runs its passes one after the other)
+    const int lanes = tap ? 1 : std::min(n_passes, (int)VM_SLOTS);
+    std::vector<std::string> errs(lanes);
+    auto run_lane = [&](int lane) {
+        try {
+            for (int p = lane; p < n_passes; p += lanes) run_pass(p);
+        } catch (const std::exception& e) {
+            errs[lane] = e.what();
+            if (errs[lane].empty()) errs[lane] = "unknown failure";
+        } catch (...) {
+            errs[lane] = "unknown failure";
+        }
+    };
+    {
+        std::vector<std::thread> th;
+        std::vector<int> here{0};
+        th.reserve(lanes);
+        for (int l = 1; l < lanes; l++) {
+            try {
+                th.emplace_back(run_lane, l);
+            } catch (const std::exception&) {  // no thread to be had: that lane's passes run on this thread
+                here.push_back(l);
+            }
+        }
+        for (int l : here) run_lane(l);
+        for (auto& t : th) t.join();
+    }
+    for (int l = 0; l < lanes; l++)
+        if (!errs[l].empty()) {
+            for (int i = 0; i < n_all; i++) verified[i] = 0;
+            set_error(std::runtime_error(errs[l]));
+            return ERR_DEVICE;
+        }
+    return OK;
+}
+
+}  // namespace kzg

@@ -1,8 +1,8 @@
 // The host's share of verification and recovery that is pure computation over bytes: input validation, de-duplication, the scalar
-// codecs and the Fiat-Shamir transcripts (the reference's four and the leaf-hashed challenge of the cell verifier), each stated ONCE
-// for verify.hip, verify_many.hip, eip4844.hip and recover.hip.
-// No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp and test_many_leaf.cpp run it on the CPU
-// against hashlib.
+// codecs and the Fiat-Shamir transcripts (the reference's four, the leaf-hashed challenge of the cell verifier and the leaves, seed and
+// weights of the point many-verification), each stated ONCE for verify.hip, verify_many.hip, point_many.hip, eip4844.hip and recover.hip.
+// No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp, test_many_leaf.cpp and
+// test_point_many.cpp run it on the CPU against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -252,6 +252,63 @@ inline void fold_weight(const uint8_t seed[32], uint64_t i, uint32_t out4[4]) {
     memcpy(out4, dg, 16);
     out4[3] &= 0x7fffffffu;
     if ((out4[0] | out4[1] | out4[2] | out4[3]) == 0) out4[0] = 1;  // a weight of zero would drop its problem from the check
+}
+
+// ---- eth_kzg_amd_verify_kzg_proof_many / _many_device (point_many.hip): MANY items (commitment, z, y, proof), a verdict for each --
+// exactly what Verifier::verify_kzg_proof (crates/eip4844/src/verifier.rs:19-44) says of the item alone.  The reference has nothing
+// like it.  Item equation, as the single call evaluates it (eip4844.hip: verify_kzg_proof_host):
+//     e(pi_i, [tau]_2) e(C_i + z_i pi_i - y_i G, -[1]_2) = 1
+// A call is cut into passes of at most POINT_MANY_PASS items, in the caller's order (point_pass_end).  Within a pass of n_p items:
+//   LEAF_i = SHA-256("RCKZGPROOFLEAF_1" | commitment_i | z_i | y_i | proof_i)           the caller's 160 bytes behind the domain
+//   SEED   = SHA-256("RCKZGPROOFFOLD_1" | be64(n_p) | LEAF_0 | .. | LEAF_{n_p - 1})
+//   rho_i  = fold_weight(SEED, i)                                                      127 bits, never zero; i = position in the pass
+// An item refused at validation (point_item_status != 0) is hashed like any other and takes no part in any sum.  The pair of a range R:
+//     ( sum_{i in R, status 0} rho_i pi_i ,  sum_{i in R, status 0} rho_i (C_i + z_i pi_i - y_i G) )
+// Soundness.  SEED is a hash of every input byte of the pass: the leaves bind the contents of the items, SEED binds their order and
+// number, and two passes with one SEED are a SHA-256 collision (in a leaf, or in the seed).  So no weight can be predicted before every
+// byte of every item is fixed.  Write E_i for the item's own pairing value e(pi_i, [tau]_2) e(C_i + z_i pi_i - y_i G, -[1]_2), an
+// element of the pairing group of prime order r; the pair of R passes the check iff prod_{i in R} E_i^(rho_i) = 1.  If every item of
+// R is valid that holds for any weights.  If some E_j != 1, then for fixed other weights at most one residue of rho_j mod r makes the
+// product 1, and rho_j is one of 2^127 - 1 values the prover could not choose: a range that holds a wrong item passes with probability
+// 2^-127 (the argument of the cell verifier's fold above, and of the powers of r in the reference's own batch check,
+// kzg_single_open/src/verifier.rs:76-107).  A pass whose full-range pair passes therefore holds valid items only; otherwise the wrong
+// items are SEARCHED by checking the pairs of sub-ranges down to single items, and a single item whose pair fails is wrong EXACTLY:
+// E_i^(rho_i) != 1 with 0 < rho_i < r means E_i != 1.  Whether an item's status is 0, 1 or 2 is decided before any weight is used.
+// The host form hashes the leaves on the host threads, the device form on the GPU (k_point_many.hip: k_pm_leaf_bodies + k_sha256_many);
+// both compute the same leaves, seed and weights.
+constexpr uint64_t POINT_MANY_MAX_ITEMS = 1u << 24;
+constexpr int POINT_MANY_PASS = 16384;  // the product's P; not part of the contract
+struct PointProofTranscript {
+    static constexpr size_t LEAF_BYTES = 16 + 48 + 32 + 32 + 48;  // 176: two blocks and 48 bytes
+    static void leaf(const uint8_t* commitment, const uint8_t* z, const uint8_t* y, const uint8_t* proof, uint8_t out[32]) {
+        uint8_t m[LEAF_BYTES];
+        memcpy(m, "RCKZGPROOFLEAF_1", 16);
+        memcpy(m + 16, commitment, 48);
+        memcpy(m + 64, z, 32);
+        memcpy(m + 96, y, 32);
+        memcpy(m + 128, proof, 48);
+        Sha256 sh;
+        sh.update(m, sizeof m);
+        sh.finish(out);
+    }
+    // leaves: the n_p digests of the pass in the caller's order, 32 bytes each
+    static void seed(uint64_t n_p, const uint8_t* leaves, uint8_t out[32]) {
+        uint8_t hdr[24];
+        memcpy(hdr, "RCKZGPROOFFOLD_1", 16);
+        be64(n_p, hdr + 16);
+        Sha256 sh;
+        sh.update(hdr, sizeof hdr);
+        sh.update(leaves, (size_t)n_p * 32);
+        sh.finish(out);
+    }
+};
+// the passes of a call of n items cut at `pass` items: the pass that begins at item lo ends in front of the item returned
+inline uint64_t point_pass_end(uint64_t n, uint64_t lo, uint64_t pass) { return n - lo > pass ? lo + pass : n; }
+// the status of an item in the single call's order of checks: the points first (commitment, then proof), then z, then y
+inline int point_item_status(bool commitment_bad, bool proof_bad, const uint8_t* z, const uint8_t* y) {
+    if (commitment_bad || proof_bad) return 2;
+    if (geq_mod<FrParams>(fr_words_from_be(z).v) || geq_mod<FrParams>(fr_words_from_be(y).v)) return 1;
+    return 0;
 }
 
 }  // namespace kzg

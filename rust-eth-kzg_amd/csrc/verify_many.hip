@@ -24,20 +24,12 @@
 // event, one ROOT per problem on the host threads while the decoding kernels run.  The roots stay on the host on purpose: a lane per
 // problem would serialise n / 2 compressions of a large problem (8192 cells: ~4 k dependent compressions), and the wait for the
 // status words is there anyway.  Everything behind the challenge is the same for all four combinations.
-#include "engine_internal.hpp"
-#include "curve29.hpp"
-#include "host_pairing.hpp"
+#include "vm_search.hpp"
 
 namespace kzg {
 
 namespace {
-int host_threads(const Knobs& k) {
-    int t = 16;
-    const unsigned hw = std::thread::hardware_concurrency();
-    if (hw && (int)hw < t) t = (int)hw;
-    if (k.host_threads) t = k.host_threads;
-    return t;
-}
+using vm::host_threads; using vm::poisoned; using vm::check_pair;  // vm_search.hpp
 struct Problem {  // one verification of the call, after validation
     std::vector<const uint8_t*> uniq;  // de-duplicated commitments, first-occurrence order (verifier.rs:49-65)
     std::vector<int> row;              // per cell: index into uniq
@@ -76,18 +68,6 @@ struct PassLayout {
                  off_leaf = d.take(leaf ? (size_t)n * 32 : 0), dev_bytes = d.end;
     PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_) {}
 };
-
-// the pairing check of two sums read back (verifier.rs:242-259; vk = [tau^64]_2, -[1]_2): 1 / 0, or -1 where the poison of the result
-// slots is still there (a device failure)
-bool poisoned(const JacQ& s) { return s.x.v[0] == 0xffffffffu && s.z.v[0] == 0xffffffffu; }
-int check_pair(const JacQ* two, const pairing::G2Prepared* const* vk) {
-    G1Affine pts[2];
-    for (int j = 0; j < 2; j++) {
-        if (poisoned(two[j])) return -1;
-        pts[j] = to_affine(jac_from_jacq(two[j]));
-    }
-    return pairing::product_is_one(pts, vk, 2) ? 1 : 0;
-}
 
 // The host's side of one pass: problems b0 .. b0 + Bc of the call (`in` is the call's input from b0 on), n cells and m unique
 // commitments in all, staged into the pinned slab hb as L lays it out.  Nothing in here touches the GPU.
@@ -204,79 +184,18 @@ struct PassHost {
     }
 };
 
-// Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM (off_fprod): SEARCH for the wrong ones by
-// folding sub-ranges (k_vm_fold_ranges: one small launch per level) and checking each with one pairing on a host
-// thread -- a range whose fold passes holds only valid proofs (the same 2^-127 argument, the weights were fixed
-// after every input byte), a single problem whose weighted pair fails is wrong EXACTLY (rho_b != 0 and the
-// pairing group has prime order).  Ranges are split K ways with K chosen so that a level's probes fill the
-// host threads once: one wrong proof among 1024 costs ~36 pairings in 3 rounds instead of 1024 in 64 (round 3:
-// 85 ms per call against 29.6 ms for an all-valid one).  When wrong proofs are many the search stops paying:
-// from a quarter of the live problems suspect, the rest is checked one by one as before.
+// Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM (off_fprod): the search of vm_search.hpp over them;
+// where it ends in single problems, each is checked on the host against its own sums, which the pass has read back anyway.
 void search_wrong_proofs(PassHost& V, int n_live, uint8_t* db, hipStream_t st) {
     const PassLayout& L = V.L;
-    const int Bc = L.Bc, T = V.T;
-    HostPool* const pool = V.pool;
-    uint8_t* const hb = V.hb;
-    std::vector<std::pair<int, int>> suspects{{0, Bc}};
-    int* h_rng = (int*)(hb + L.poff_rng);
-    const JacQ* h_rsum = (const JacQ*)(hb + L.poff_rsum);
-    while (!suspects.empty()) {
-        long suspect_problems = 0;
-        for (auto& sr : suspects) suspect_problems += sr.second - sr.first;
-        if ((long)suspects.size() * 4 >= n_live || suspect_problems <= 2 * T) {  // few problems left, or wrong proofs everywhere
-            std::vector<int> todo;
-            for (auto& sr : suspects)
-                for (int i = sr.first; i < sr.second; i++)
-                    if (V.live[i]) todo.push_back(i);
-            parallel_for((int)todo.size(), T, pool, [&](int q) { V.check_single(todo[q]); });
-            break;
-        }
-        int K = T / (int)suspects.size();
-        K = K < 2 ? 2 : K > 16 ? 16 : K;
-        std::vector<std::pair<int, int>> probes;
-        for (auto& sr : suspects) {
-            const int len = sr.second - sr.first, parts = std::min(K, len);
-            for (int q = 0; q < parts; q++) probes.emplace_back(sr.first + (int)((long)len * q / parts), sr.first + (int)((long)len * (q + 1) / parts));
-        }
-        // a level may need more probes than the range buffers hold (max_ranges = min(Bc, 2048): e.g. > 4096 small problems
-        // with > 1024 scattered wrong proofs): it then runs in batches over the same buffers -- never an error, the
-        // valid problems of the pass keep their verdicts
-        std::vector<char> fails(probes.size(), 0);
-        for (size_t q0 = 0; q0 < probes.size() && !V.device_fault.load(); q0 += (size_t)L.max_ranges) {
-            const size_t cnt = std::min(probes.size() - q0, (size_t)L.max_ranges);
-            for (size_t q = 0; q < cnt; q++) { h_rng[2 * q] = probes[q0 + q].first; h_rng[2 * q + 1] = probes[q0 + q].second; }
-            memset(hb + L.poff_rsum, 0xff, cnt * 2 * launch::SIZEOF_JACQ);
-            HIPCK(hipMemcpyAsync(db + L.off_rng, h_rng, cnt * 8, hipMemcpyHostToDevice, st));
-            launch::vm_fold_ranges(db + L.off_fprod, (const int*)(db + L.off_rng), db + L.off_rsum, (int)cnt, st);
-            HIPCK(hipMemcpyAsync(hb + L.poff_rsum, db + L.off_rsum, cnt * 2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
-            SYNC_CHECKED(st);
-            parallel_for((int)cnt, T, pool, [&](int q) {
-                const int v = check_pair(h_rsum + 2 * (size_t)q, V.vk);
-                if (v < 0) V.device_fault.store(1);
-                else fails[q0 + q] = v ? 0 : 1;
-            });
-            if (V.tap && !V.device_fault.load()) {
-                V.tap->searched = 1;
-                for (size_t q = 0; q < cnt; q++) {
-                    const int rec[3] = {probes[q0 + q].first, probes[q0 + q].second, fails[q0 + q] ? 0 : 1};
-                    V.tap->probes.insert(V.tap->probes.end(), rec, rec + 3);
-                }
-                V.tap->probe_sums.insert(V.tap->probe_sums.end(), hb + L.poff_rsum, hb + L.poff_rsum + cnt * 2 * launch::SIZEOF_JACQ);
-            }
-        }
-        if (V.device_fault.load()) break;
-        suspects.clear();
-        for (size_t q = 0; q < probes.size(); q++) {
-            const int lo = probes[q].first, hi = probes[q].second;
-            if (!fails[q]) {
-                for (int i = lo; i < hi; i++) if (V.live[i]) V.verified[i] = 1;
-            } else if (hi - lo == 1) {
-                V.verified[lo] = 0;  // exact: its own weighted pair fails the check
-            } else {
-                suspects.emplace_back(lo, hi);
-            }
-        }
-    }
+    vm::SearchView S;
+    S.n = L.Bc; S.max_ranges = L.max_ranges; S.T = V.T; S.pool = V.pool; S.hb = V.hb;
+    S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.off_rng = L.off_rng; S.off_pairs = L.off_fprod; S.off_rsum = L.off_rsum;
+    S.vk = V.vk; S.live = V.live.data(); S.verified = V.verified; S.device_fault = &V.device_fault;
+    S.check_single = [&V](int i) { V.check_single(i); };
+    if (V.tap) { S.tap_probes = &V.tap->probes; S.tap_probe_sums = &V.tap->probe_sums; }
+    vm::search_wrong_proofs(S, n_live, db, st);
+    if (V.tap && !V.tap->probes.empty()) V.tap->searched = 1;
 }
 }  // namespace
 
