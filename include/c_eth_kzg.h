@@ -349,6 +349,41 @@ CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext *ctx, uint64_t
                                                  const uint8_t *d_ys, const uint8_t *d_proofs, bool *verified, int32_t *status,
                                                  void *hip_stream);
 
+/* MANY eth_kzg_verify_blob_kzg_proof items in one call, A VERDICT FOR EACH: the throughput form of the blob check for callers that need
+ * to know WHICH blob of a batch is wrong (eth_kzg_verify_blob_kzg_proof_batch / _batch_device give one verdict for all, and a node whose
+ * batch fails would otherwise fall back to one single call per blob).  Item i: blobs[i] -> 131072 bytes, commitments[i] / proofs[i] -> 48
+ * bytes.  Per item the result is exactly what eth_kzg_verify_blob_kzg_proof says of that item alone, in its order of checks
+ * (crates/eip4844/src/verifier.rs:49-74):
+ *   status[i] = 1  the blob holds a field element >= r (also when a point is bad as well),
+ *   else      = 2  the commitment or the proof is not a canonical point of the subgroup,
+ *   else      = 0  and verified[i] is the verdict.  verified[i] is false whenever status[i] != 0.  status may be NULL.
+ * The identity is a valid commitment and a valid proof: the all-zero blob with two identities verifies.
+ * The call: n = 0 is Ok; n > 2^24, or a NULL array with n > 0, is Err("InvalidInput...") before the context is touched; otherwise Err
+ * only for a device failure, and then every verified[i] is false.
+ * How: there is no new transcript.  Item i becomes the point item (C_i, z_i, y_i, pi_i) of eth_kzg_amd_verify_kzg_proof_many above, with
+ * z_i = H("FSBLOBVERIFY_V1_" | 4096 | blob_i | commitment_i) mod r hashed from the caller's bytes as they stand and y_i = p_i(z_i)
+ * evaluated on the GPU without leaving the CU (csrc/k_ntt.hip: k_blob_eval_at -- one block per blob: the inverse transform in LDS, then
+ * the 4096 coefficients are summed against powers of z where they lie; no coefficient and no quotient is written to HBM); y_i is 32 zero
+ * bytes for a refused blob.  Leaves, seed, weights, the one pairing check per pass and the search are that call's, unchanged, and so is
+ * the soundness argument (csrc/verify_host.hpp): the per-item equation is over exactly (C, z, y, pi), all of which the leaves bind, and
+ * z and y are computed by the verifier, not supplied.  The leaves are hashed on the GPU in both forms (y exists only there).  A pass
+ * holds at most 256 items (not part of the contract) and runs on a pass slot: the call does not take the context's big lock, needs
+ * none of the prover's workspace and runs next to every other entry point; a call of several passes uses up to three slots.
+ * Host form: cut into contiguous slices by item over the context's device list; the helper threads gather a pass's blobs into pinned
+ * memory and hash the challenges while the bytes are in their cache; one upload per pass.
+ * Device form: flat arrays in one GPU's HBM -- d_blobs n * 131072, d_commitments / d_proofs n * 48 bytes, with the alignment
+ * eth_kzg_amd_verify_blob_kzg_proof_batch_device asks for (the 48-byte arrays from any byte address) -- verified / status HOST memory.
+ * The blobs are read where they lie and never copied; the challenges are hashed on the GPU, one lane per blob, which takes a few
+ * milliseconds whatever n is.  Synchronous; work already queued on `hip_stream` (NULL: the default stream) is waited for.  Runs on the
+ * device that owns the buffers: all three pointers are resolved, and anything but device memory of ONE device of the context is
+ * Err("InvalidInput...").  The Node binding is not extended.  When it pays: INTEGRATION.md. */
+CResult eth_kzg_amd_verify_blob_kzg_proof_many(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs,
+                                               const uint8_t *const *commitments, const uint8_t *const *proofs, bool *verified,
+                                               int32_t *status);
+CResult eth_kzg_amd_verify_blob_kzg_proof_many_device(const DASContext *ctx, uint64_t n, const uint8_t *d_blobs,
+                                                      const uint8_t *d_commitments, const uint8_t *d_proofs, bool *verified,
+                                                      int32_t *status, void *hip_stream);
+
 /* verify_cell_kzg_proof_batch on flat arrays in this GPU's HBM: n * 48 commitment bytes (one per cell, NOT deduplicated, as in
  * the host form), n indices, n * 2048 cell bytes, n * 48 proof bytes.  The GPU's part reads cells and proofs where they are;
  * the transcript hash runs on a host core, so its bytes come down (in chunks, under the hash) and the call is synchronous;

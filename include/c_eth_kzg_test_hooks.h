@@ -171,6 +171,23 @@ int eth_kzg_amd_test_verify_kzg_proof_many_sums(const DASContext *ctx, uint64_t 
                                                 uint8_t *seeds32, uint32_t *rho, uint8_t *fold96, int32_t *fold_verdicts, int32_t *probes4,
                                                 uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes);
 
+/* k_blob_eval_at alone (csrc/k_ntt.hip): y_b = p_b(z_b) for n blobs, 1 <= n <= 4096, on the context's first device.  blobs[b] -> 131072
+ * bytes and zs_be32[n][32] (big-endian; a value >= r is reduced) on the host.  Outputs, host: out_ys_be32[n][32] canonical big-endian,
+ * out_bad[n] = 1 for a blob that holds an element >= r (its y is 32 zero bytes).  Synchronous; 0 on success. */
+int eth_kzg_amd_test_blob_eval_at(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs, const uint8_t *zs_be32,
+                                  uint8_t *out_ys_be32, int32_t *out_bad);
+
+/* eth_kzg_amd_test_verify_kzg_proof_many_sums for the blob source (eth_kzg_amd_verify_blob_kzg_proof_many / _many_device): on_device = 0:
+ * blobs / commitments / proofs are the host form's pointer lists; 1: the device form's flat arrays.  forced_pass: 0 = the product's pass
+ * size of the blob source.  Every output as there, and zs32[n][32], ys32[n][32]: the z_i and y_i the passes computed, as their leaves
+ * hash them (y_i = zero bytes for a refused blob). */
+int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext *ctx, uint64_t n, int on_device, const void *blobs,
+                                                     const void *commitments, const void *proofs, uint64_t forced_pass, int32_t *verified,
+                                                     int32_t *status, uint64_t *pass_starts, uint64_t max_passes, uint64_t *n_passes,
+                                                     uint8_t *leaves32, uint8_t *seeds32, uint32_t *rho, uint8_t *fold96,
+                                                     int32_t *fold_verdicts, int32_t *probes4, uint8_t *probe_sums96, uint64_t max_probes,
+                                                     uint64_t *n_probes, uint8_t *zs32, uint8_t *ys32);
+
 /* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode in recover.hip, exactly the launches recovery runs).  R >= 1 blobs; blob r has
  * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
  * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat

@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_compute_blob_kzg_proof_device", "eth_kzg_amd_compute_kzg_proof_device",
     "eth_kzg_amd_verify_blob_kzg_proof_batch_device",
     "eth_kzg_amd_verify_kzg_proof_many", "eth_kzg_amd_verify_kzg_proof_many_device",
+    "eth_kzg_amd_verify_blob_kzg_proof_many", "eth_kzg_amd_verify_blob_kzg_proof_many_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
     "eth_kzg_amd_set_profiling", "eth_kzg_amd_get_stage_times",
     "eth_kzg_amd_comm_probe", "eth_kzg_amd_comm_unique_id", "eth_kzg_amd_comm_init", "eth_kzg_amd_comm_info",
@@ -88,6 +89,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_cell_leaf_digests", "eth_kzg_amd_test_verify_cells_inputs_ex",
     "eth_kzg_amd_test_verify_many_sums_ex", "eth_kzg_amd_test_verify_many_sums_device",
     "eth_kzg_amd_test_verify_kzg_proof_many_sums",
+    "eth_kzg_amd_test_blob_eval_at", "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums",
 ]
 
 _lib = None
@@ -188,6 +190,8 @@ def load_library():
         "eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P],
         "eth_kzg_amd_verify_kzg_proof_many": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_verify_kzg_proof_many_device": [P, U64, P, P, P, P, P, P, P],
+        "eth_kzg_amd_verify_blob_kzg_proof_many": [P, U64, P, P, P, P, P],
+        "eth_kzg_amd_verify_blob_kzg_proof_many_device": [P, U64, P, P, P, P, P, P],
     }.items():
         if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
             getattr(lib, name).restype = CResult
@@ -223,6 +227,8 @@ def load_library():
         "eth_kzg_amd_test_verify_many_sums_ex": [P, U64, P, P, P, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
         "eth_kzg_amd_test_verify_many_sums_device": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
         "eth_kzg_amd_test_verify_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P],
+        "eth_kzg_amd_test_blob_eval_at": [P, U64, P, P, P, P],
+        "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -305,6 +311,19 @@ def _flat_ptrs(items, size):
     flat = np.frombuffer(b"".join(bytes(x) if not isinstance(x, bytes) else x for x in items), dtype=np.uint8) if n else np.zeros(1, np.uint8)
     ptrs = np.uint64(flat.ctypes.data) + np.arange(max(1, n), dtype=np.uint64) * np.uint64(size)
     return ptrs, flat
+
+
+def _alias_ptrs(items):
+    """(uint64 pointer table, keep-alive) over byte strings WITHOUT copying them together: equal objects share one buffer, so a list
+    that names a few 128 KB blobs many times costs those few."""
+    bufs, ptrs = {}, np.zeros(max(1, len(items)), dtype=np.uint64)
+    for i, x in enumerate(items):
+        key = id(x)
+        if key not in bufs:
+            a = np.frombuffer(x if isinstance(x, bytes) else bytes(x), dtype=np.uint8)
+            bufs[key] = (a, x)  # (the object stays alive with its id)
+        ptrs[i] = bufs[key][0].ctypes.data
+    return ptrs, bufs
 
 
 def _out_ptrs(n_outer, n_inner, size):
@@ -689,6 +708,41 @@ class DASContext:
         st = (C.c_int32 * max(1, n))()
         self._check(self._lib.eth_kzg_amd_verify_kzg_proof_many_device(
             self._ctx, n, C.c_void_p(d_commitments), C.c_void_p(d_zs), C.c_void_p(d_ys), C.c_void_p(d_proofs), ver, st,
+            C.c_void_p(stream) if stream else None))
+        return [bool(v) for v in ver][:n], list(st)[:n]
+
+    def prepare_verify_blob_kzg_proof_many(self, items):
+        """items = [(blob, commitment, proof), ...]: marshal them into the pointer tables of eth_kzg_amd_verify_blob_kzg_proof_many ONCE
+        (a blob object named several times is not copied) and return a zero-argument callable that runs the call and returns (verified
+        list[bool], status list[int]) -- per item what verify_blob_kzg_proof says of it alone: status 1 the blob holds an element >= r,
+        else 2 a bad G1 point (what the single form raises as KzgError), else 0 and the verdict.  A wrong byte length cannot cross the C
+        ABI and raises InvalidLength here."""
+        n = len(items)
+        if any(len(b) != BYTES_PER_BLOB or len(c) != 48 or len(p) != 48 for b, c, p in items):
+            raise KzgError("InvalidLength")
+        ba, k1 = _alias_ptrs([it[0] for it in items])
+        ca, k2 = _flat_ptrs([it[1] for it in items], 48)
+        pa, k3 = _flat_ptrs([it[2] for it in items], 48)
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+
+        def run(_keep=(k1, k2, k3)):
+            self._check(self._lib.eth_kzg_amd_verify_blob_kzg_proof_many(self._ctx, n, _vp(ba), _vp(ca), _vp(pa), ver, st))
+            return [bool(v) for v in ver][:n], list(st)[:n]
+        return run
+
+    def verify_blob_kzg_proof_many(self, items):
+        """Many verify_blob_kzg_proof items in one call, a verdict for each (see prepare_verify_blob_kzg_proof_many)."""
+        return self.prepare_verify_blob_kzg_proof_many(items)()
+
+    def verify_blob_kzg_proof_many_device(self, n, d_blobs, d_commitments, d_proofs, stream=None):
+        """The same on flat arrays in device memory (eth_kzg_amd_verify_blob_kzg_proof_many_device): integer device addresses of
+        n*131072 blob bytes (read where they lie), n*48 commitment and n*48 proof bytes.  -> (verified list[bool], status list[int]).
+        Synchronous; waits for what `stream` (None: the default stream) has queued."""
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_verify_blob_kzg_proof_many_device(
+            self._ctx, n, C.c_void_p(d_blobs), C.c_void_p(d_commitments), C.c_void_p(d_proofs), ver, st,
             C.c_void_p(stream) if stream else None))
         return [bool(v) for v in ver][:n], list(st)[:n]
 

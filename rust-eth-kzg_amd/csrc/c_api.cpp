@@ -817,6 +817,57 @@ CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext* ctx, uint64_t
         return err(std::string("DeviceError(") + ex.what() + ")");
     }
 }
+// Many verify_blob_kzg_proof items, a verdict each: the blob source of the same pass.  Count and arrays first, then the device list
+// (host form: contiguous slices by item) or the owner of ALL THREE buffers (device form).
+CResult eth_kzg_amd_verify_blob_kzg_proof_many(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* commitments,
+                                               const uint8_t* const* proofs, bool* verified, int32_t* status) {
+    if (n > kzg::BLOB_MANY_MAX_ITEMS) return err("InvalidInput");
+    if (n && (!blobs || !commitments || !proofs || !verified)) return err("InvalidInput");
+    live(ctx);
+    if (n == 0) return ok();
+    try {
+        for (uint64_t i = 0; i < n; i++) {
+            verified[i] = false;
+            if (!blobs[i] || !commitments[i] || !proofs[i]) return err("InvalidInput");
+        }
+        std::vector<int> ver(n), st(n);
+        kzg::PointManyInput in;
+        in.from_blobs = true;
+        in.blobs = blobs; in.commitments = commitments; in.proofs = proofs;
+        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
+            kzg::Engine* e = ctx->engines[(size_t)d];
+            const int rc = e->verify_kzg_proof_many(hi - lo, in.from(lo), ver.data() + lo, st.data() + lo);
+            return rc == kzg::ERR_DEVICE ? device_text(e) : std::string();
+        });
+        if (r.first >= 0) return slices_result(ctx, r);
+        return point_many_results(n, ver, st, verified, status);
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+CResult eth_kzg_amd_verify_blob_kzg_proof_many_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments,
+                                                      const uint8_t* d_proofs, bool* verified, int32_t* status, void* hip_stream) {
+    if (n > kzg::BLOB_MANY_MAX_ITEMS) return err("InvalidInput");
+    if (n && (!d_blobs || !d_commitments || !d_proofs || !verified)) return err("InvalidInput");
+    live(ctx);
+    if (n == 0) return ok();
+    for (uint64_t i = 0; i < n; i++) verified[i] = false;
+    const void* const ptrs[3] = {d_blobs, d_commitments, d_proofs};
+    kzg::Engine* e = engine_of_device_pointers(ctx, ptrs, 3);
+    if (!e) return err("InvalidInput: the three buffers are not device memory of one device of this context");
+    try {
+        std::vector<int> ver(n), st(n);
+        kzg::PointManyInput in;
+        in.on_device = true;
+        in.from_blobs = true;
+        in.d_blobs = d_blobs; in.d_commitments = d_commitments; in.d_proofs = d_proofs;
+        in.user_stream = (hipStream_t)hip_stream;
+        if (e->verify_kzg_proof_many(n, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
+        return point_many_results(n, ver, st, verified, status);
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
 void eth_kzg_amd_set_profiling(const DASContext* ctx, int on) { eng(ctx)->set_profiling(on != 0); }
 int eth_kzg_amd_get_stage_times(const DASContext* ctx, double* ms, uint64_t* launches, int n) {
     double m[kzg::Engine::ST_COUNT];

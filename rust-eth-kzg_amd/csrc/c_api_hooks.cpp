@@ -160,6 +160,32 @@ int eth_kzg_amd_test_verify_kzg_proof_many_sums(const DASContext* ctx, uint64_t 
     return eng(ctx)->test_verify_kzg_proof_many_sums(n, in, forced_pass, verified, status, pass_starts, max_passes, n_passes, leaves32, seeds32, rho, fold96,
                                                      fold_verdicts, probes4, probe_sums96, max_probes, n_probes);
 }
+int eth_kzg_amd_test_blob_eval_at(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* zs_be32, uint8_t* out_ys_be32,
+                                  int32_t* out_bad) {
+    if (n < 1 || n > 4096 || !blobs || !zs_be32 || !out_ys_be32 || !out_bad) return kzg::ERR_INPUT;
+    for (uint64_t b = 0; b < n; b++)
+        if (!blobs[b]) return kzg::ERR_INPUT;
+    return eng(ctx)->test_blob_eval_at((int)n, blobs, zs_be32, out_ys_be32, out_bad);
+}
+int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext* ctx, uint64_t n, int on_device, const void* blobs, const void* commitments,
+                                                     const void* proofs, uint64_t forced_pass, int32_t* verified, int32_t* status, uint64_t* pass_starts,
+                                                     uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho,
+                                                     uint8_t* fold96, int32_t* fold_verdicts, int32_t* probes4, uint8_t* probe_sums96, uint64_t max_probes,
+                                                     uint64_t* n_probes, uint8_t* zs32, uint8_t* ys32) {
+    if (!blobs || !commitments || !proofs || !verified || !status || !pass_starts || !n_passes || !leaves32 || !seeds32 || !rho || !fold96 ||
+        !fold_verdicts || !n_probes || !zs32 || !ys32 || (max_probes && (!probes4 || !probe_sums96)) || (on_device != 0 && on_device != 1))
+        return kzg::ERR_INPUT;
+    kzg::PointManyInput in;
+    in.from_blobs = true;
+    in.on_device = on_device != 0;
+    if (on_device) {
+        in.d_blobs = (const uint8_t*)blobs; in.d_commitments = (const uint8_t*)commitments; in.d_proofs = (const uint8_t*)proofs;
+    } else {
+        in.blobs = (const uint8_t* const*)blobs; in.commitments = (const uint8_t* const*)commitments; in.proofs = (const uint8_t* const*)proofs;
+    }
+    return eng(ctx)->test_verify_kzg_proof_many_sums(n, in, forced_pass, verified, status, pass_starts, max_passes, n_passes, leaves32, seeds32, rho, fold96,
+                                                     fold_verdicts, probes4, probe_sums96, max_probes, n_probes, zs32, ys32);
+}
 int eth_kzg_amd_test_rs_decode(const DASContext* ctx, int R, const uint64_t* n_cells, const uint64_t* const* cell_indices,
                                const uint8_t* const* const* cells, int flat_source, int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval,
                                uint8_t* zcinv, uint8_t* coeffs) {

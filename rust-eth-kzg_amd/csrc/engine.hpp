@@ -83,22 +83,36 @@ struct VerifyManyInput {
 //   pointer lists on the host: commitments[i] / proofs[i] -> 48 bytes, zs[i] / ys[i] -> 32 bytes big-endian
 //   flat arrays in this GPU's HBM (on_device): n x 48 / n x 32 bytes; the 48-byte arrays from any byte address, zs and ys 4-byte
 //     aligned; what user_stream has queued produces them
+// A third source, BLOBS (from_blobs; eth_kzg_amd_verify_blob_kzg_proof_many / _many_device): the item is (blob, commitment, proof) and the
+// pass computes z = blob_challenge(blob, commitment) and y = p(z) itself (verify_host.hpp); zs / ys are not given.  blobs[i] -> 131072
+// bytes on the host, or d_blobs: n x 131072 bytes in HBM, 4-byte aligned, read where they lie.
 struct PointManyInput {
     const uint8_t *const *commitments = nullptr, *const *zs = nullptr, *const *ys = nullptr, *const *proofs = nullptr;
     const uint8_t *d_commitments = nullptr, *d_zs = nullptr, *d_ys = nullptr, *d_proofs = nullptr;
-    bool on_device = false;
+    const uint8_t* const* blobs = nullptr;
+    const uint8_t* d_blobs = nullptr;
+    bool on_device = false, from_blobs = false;
     hipStream_t user_stream = nullptr;
     PointManyInput from(uint64_t lo) const {
         PointManyInput s = *this;
-        if (on_device) { s.d_commitments += lo * 48; s.d_zs += lo * 32; s.d_ys += lo * 32; s.d_proofs += lo * 48; }
-        else { s.commitments += lo; s.zs += lo; s.ys += lo; s.proofs += lo; }
+        if (on_device) {
+            s.d_commitments += lo * 48; s.d_proofs += lo * 48;
+            if (from_blobs) s.d_blobs += lo * 131072;
+            else { s.d_zs += lo * 32; s.d_ys += lo * 32; }
+        } else {
+            s.commitments += lo; s.proofs += lo;
+            if (from_blobs) s.blobs += lo;
+            else { s.zs += lo; s.ys += lo; }
+        }
         return s;
     }
 };
 // Tap of such a call (null in every product call; the stage hook test_verify_kzg_proof_many_sums sets it): copies of what the passes'
-// pinned read-backs held after the syncs they make anyway.  pass_size: 0 = the product's (POINT_MANY_PASS), else a forced one.
+// pinned read-backs held after the syncs they make anyway.  pass_size: 0 = the product's (POINT_MANY_PASS; BLOB_MANY_PASS for the blob
+// source), else a forced one.
 struct PointManyTap {
     int pass_size = 0;
+    std::vector<uint8_t> zs, ys;         // [n][32] each, the blob source only: the z and y the pass computed, as its leaves hash them
     std::vector<uint64_t> pass_starts;   // the first item of every pass, then n
     std::vector<uint8_t> leaves;         // [n][32]
     std::vector<uint8_t> seeds;          // [passes][32]
@@ -286,6 +300,7 @@ public:
     // MANY verify_kzg_proof items in one call, a verdict each (point_many.hip): status[i] = ERR_G1 / ERR_SCALAR / OK in the single
     // call's order of checks, verified[i] set when OK.  Returns ERR_DEVICE on a HIP failure, OK otherwise.  Runs on a pass slot of the
     // many-verification: does not take mu_.
+    // in.from_blobs: MANY verify_blob_kzg_proof items, status[i] = ERR_SCALAR (the blob) / ERR_G1 / OK in that call's order.
     int verify_kzg_proof_many(uint64_t n, const PointManyInput& in, int* verified, int* status, PointManyTap* tap = nullptr);
     // ---- EIP-4844 proofs for MANY blobs (eip4844.hip; crates/eip4844/src/prover.rs:37-92 per blob) ----
     // Device-resident: d_blobs n * 131072 B, d_commitments / d_out_proofs n * 48 B, d_z / d_out_y n * 32 B big-endian (4-byte aligned);
@@ -374,7 +389,9 @@ public:
     int test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in, uint64_t forced_pass, int32_t* verified, int32_t* status,
                                         uint64_t* pass_starts, uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho,
                                         uint8_t* fold96, int32_t* fold_verdicts, int32_t* probes4, uint8_t* probe_sums96, uint64_t max_probes,
-                                        uint64_t* n_probes);
+                                        uint64_t* n_probes, uint8_t* zs32 = nullptr, uint8_t* ys32 = nullptr /* the blob source: [n][32] each */);
+    // k_blob_eval_at alone: n blobs and n points (32 big-endian bytes, reduced mod r) from the host -> ys32[n][32], bad[n]
+    int test_blob_eval_at(int n, const uint8_t* const* blobs, const uint8_t* zs_be32, uint8_t* out_ys_be32, int32_t* out_bad);
     // the Reed-Solomon decoder of recovery on its own: rs_decode (verify.hip) with its tap set, behind the staging of recover_batch_to_coeffs
     // (flat_source = 0) or of recover_cells_and_kzg_proofs_device (1); outputs canonical big-endian on the host, each may be null
     int test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,

@@ -573,9 +573,10 @@ int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& 
 int Engine::test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in, uint64_t forced_pass, int32_t* verified, int32_t* status,
                                             uint64_t* pass_starts, uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho,
                                             uint8_t* fold96, int32_t* fold_verdicts, int32_t* probes4, uint8_t* probe_sums96, uint64_t max_probes,
-                                            uint64_t* n_probes) {
+                                            uint64_t* n_probes, uint8_t* zs32, uint8_t* ys32) {
     if (n < 1 || n > (1u << 20) || forced_pass > (1u << 20)) return ERR_INPUT;
-    const uint64_t pass = forced_pass ? forced_pass : (uint64_t)POINT_MANY_PASS;
+    if (in.from_blobs && (!zs32 || !ys32)) return ERR_INPUT;
+    const uint64_t pass = forced_pass ? forced_pass : (uint64_t)(in.from_blobs ? BLOB_MANY_PASS : POINT_MANY_PASS);
     if ((n + pass - 1) / pass > max_passes) return ERR_INPUT;
     std::vector<int> ver(n), st(n);
     PointManyTap tap;
@@ -595,6 +596,10 @@ int Engine::test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in
     *n_passes = np;
     for (uint64_t p = 0; p <= np; p++) pass_starts[p] = tap.pass_starts[p];
     memcpy(leaves32, tap.leaves.data(), (size_t)n * 32);
+    if (in.from_blobs) {
+        memcpy(zs32, tap.zs.data(), (size_t)n * 32);
+        memcpy(ys32, tap.ys.data(), (size_t)n * 32);
+    }
     memcpy(rho, tap.rho.data(), (size_t)n * 16);
     memcpy(seeds32, tap.seeds.data(), (size_t)np * 32);
     for (uint64_t p = 0; p < np; p++) {
@@ -605,6 +610,37 @@ int Engine::test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in
     for (uint64_t q = 0; q < *n_probes && q < max_probes; q++) {
         for (int j = 0; j < 4; j++) probes4[4 * q + j] = tap.probes[4 * q + j];
         compress2(probe_sums96 + 96 * q, tap.probe_sums.data() + (size_t)2 * q * sizeof(JacQ));
+    }
+    return OK;
+}
+
+// k_blob_eval_at on its own: blobs and points up, one launch, y and the refusal flags down.
+int Engine::test_blob_eval_at(int n, const uint8_t* const* blobs, const uint8_t* zs_be32, uint8_t* out_ys_be32, int32_t* out_bad) {
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        hipStream_t st = stream_;
+        PoolBuf d_blobs(*this, (size_t)n * BYTES_PER_BLOB), d_z(*this, (size_t)n * 32), d_zm(*this, (size_t)n * sizeof(Fr)), d_y(*this, (size_t)n * 32),
+            d_ym(*this, (size_t)n * sizeof(Fr)), d_bad(*this, (size_t)n * sizeof(int));
+        for (int b = 0; b < n; b++)
+            HIPCK(hipMemcpyAsync((uint8_t*)d_blobs.p + (size_t)b * BYTES_PER_BLOB, blobs[b], BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(d_z.p, zs_be32, (size_t)n * 32, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemsetAsync(d_y.p, 0xff, (size_t)n * 32, st));  // what the kernel does not write shows
+        HIPCK(hipMemsetAsync(d_bad.p, 0xff, (size_t)n * sizeof(int), st));
+        launch::fr_from_be32(n, (const uint8_t*)d_z.p, d_zm.p, nullptr, /*reduce=*/true, st);
+        launch::blob_eval_at(n, (const uint8_t*)d_blobs.p, d_zm.p, (uint8_t*)d_y.p, d_ym.p, (int*)d_bad.p, d_w29_, n_inv4096_, st);
+        HIPCK(hipGetLastError());
+        // the Montgomery copy must say the same: it comes down through the existing codec
+        launch::fr_mont_to_be32(n, d_ym.p, (uint8_t*)d_z.p, st);
+        std::vector<uint8_t> y2((size_t)n * 32);
+        HIPCK(hipMemcpyAsync(out_ys_be32, d_y.p, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(y2.data(), d_z.p, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(out_bad, d_bad.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        SYNC_CHECKED(st);
+        if (memcmp(y2.data(), out_ys_be32, (size_t)n * 32) != 0) throw std::runtime_error("k_blob_eval_at: the two forms of y differ");
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
     }
     return OK;
 }

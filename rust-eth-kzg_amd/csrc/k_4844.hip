@@ -87,6 +87,11 @@ __global__ __launch_bounds__(64) void k_fr_to_be32(const Fr* __restrict__ canon,
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i < n) store_fr_be(out + (size_t)i * 32, canon[i]);
 }
+// Montgomery Fr -> 32 big-endian canonical bytes (a challenge reduced on the device, as the point many-verification's leaves hash it)
+__global__ __launch_bounds__(64) void k_fr_mont_to_be32(const Fr* __restrict__ mont, uint8_t* __restrict__ out, int n) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < n) store_fr_be(out + (size_t)i * 32, from_mont(mont[i]));
+}
 // per-blob status of a batched opening in the single call's order (eip4844/src/prover.rs:37-92): 1 the blob holds a non-canonical
 // element, else 1 the evaluation point is not canonical (z_bad; null: a hashed challenge), else 2 the commitment is not a valid
 // subgroup point (g1_bad; null: none given), else 0
@@ -107,6 +112,9 @@ void fr_from_be32(int n, const uint8_t* in, void* out_mont, int* bad, bool reduc
 }
 void fr_to_be32(int n, const void* canon, uint8_t* out, hipStream_t st) {
     if (n > 0) k_fr_to_be32<<<(n + 63) / 64, 64, 0, st>>>((const Fr*)canon, out, n);
+}
+void fr_mont_to_be32(int n, const void* mont, uint8_t* out, hipStream_t st) {
+    if (n > 0) k_fr_mont_to_be32<<<(n + 63) / 64, 64, 0, st>>>((const Fr*)mont, out, n);
 }
 void status_4844(int n, const int* blob_bad, const int* z_bad, const int* g1_bad, int* out, hipStream_t st) {
     if (n > 0) k_4844_status<<<(n + 63) / 64, 64, 0, st>>>(blob_bad, z_bad, g1_bad, out, n);

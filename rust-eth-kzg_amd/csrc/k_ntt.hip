@@ -150,6 +150,112 @@ __global__ __launch_bounds__(1024) void k_blob_to_coeffs(const uint8_t* __restri
     }
 }
 
+// y = p(z) of a blob at one point WITHOUT LEAVING THE CU (the blob source of the point many-verification, point_many.hip): the input
+// stage and the inverse transform of k_blob_to_coeffs, then the evaluation of the 4096 coefficients where they lie -- no coefficient and
+// no quotient goes to HBM (the verifiers' other road, k_blob_to_coeffs + k_quotient_by_linear, writes 128 KB of each per blob and needs
+// the engine's workspace; this kernel owns none).  grid = n_blobs, block = 1024, dynamic LDS = 144 KiB; plus 2.8 KB static.
+//   z_mont[b]   the point in the saturated Montgomery form (what k_fr_from_be32 writes)
+//   y_be32[b]   y as 32 big-endian canonical bytes;  y_mont[b]  y in the saturated Montgomery form (what k_pm_mul reads)
+//   bad[b]      1 if the blob holds an element >= r: then y is zero in both forms and nothing is transformed
+// After the transform thread j holds the UNSCALED coefficients c_(j + 1024 k) = n a_(j + 1024 k), k < 4, as plain integers (its own unit's
+// results), and  n p(z) = sum_j z^j (c_j + z^1024 (c_(j+1024) + z^1024 (c_(j+2048) + z^1024 c_(j+3072)))).
+// Powers (Montgomery form, x 2^261, every one a fresh product: < 2r, limbs normalised): wave 0 builds the tables z^a (lanes 0..31) and
+// z^(32 b) (lanes 32..63) with one branch-free square-and-multiply, 5 + 10 products a lane; then per thread z^1024 = z^(32 31) z^32 and
+// z^j = z^(j mod 32) z^(32 (j / 32)): 2 products, 3 for the Horner steps, 1 for z^j: at most 21 products on any thread, 6 on most.
+// A plain value times a Montgomery-form power is plain again, so the block sum S = n p(z) (plain) leaves through ONE product per output
+// form with the constants k_blob_to_coeffs applies per coefficient: S ninv_plain = y, S ninv_to_sat = y 2^256.
+__device__ __forceinline__ Fr29 fr29_shfl_xor(const Fr29& a, int mask) {
+    Fr29 r;
+#pragma unroll
+    for (int l = 0; l < RL; l++) r.v[l] = __shfl_xor(a.v[l], mask);
+    return r;
+}
+// sum over the 8 lanes that differ in the bits `first`, 2 first, 4 first: in < 2r with limbs < 2^29 -> < 4r (limbs < 2^30), < 8r (< 2^31),
+// < 16r (8 (2^29 - 1) < 2^32: no limb wraps) -> swept and brought back below 2r (16r < 2^261: fr29_partial_reduce's range)
+__device__ __forceinline__ Fr29 fr29_sum8_lanes(Fr29 a, int first) {
+    a = fr29_add<false>(a, fr29_shfl_xor(a, first));      // < 4r
+    a = fr29_add<false>(a, fr29_shfl_xor(a, 2 * first));  // < 8r
+    a = fr29_add<false>(a, fr29_shfl_xor(a, 4 * first));  // < 16r: the headroom of the limbs ends here
+    return fr29_partial_reduce(a);                        // < 2r, limbs normalised
+}
+__global__ __launch_bounds__(1024) void k_blob_eval_at(const uint8_t* __restrict__ blobs, const Fr* __restrict__ z_mont,
+                                                      uint8_t* __restrict__ y_be32, Fr* __restrict__ y_mont, int* __restrict__ bad_out,
+                                                      const Fr29* __restrict__ w29, NttConsts K) {
+    extern __shared__ uint32_t s[];
+    __shared__ uint32_t pw[2][RL][32];  // [0]: z^a, [1]: z^(32 b); limb-major like s
+    __shared__ uint32_t wave_sum[RL][16];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const uint8_t* blob = blobs + (size_t)b * BYTES_PER_BLOB;
+    bool bad = false;
+    for (int e = tid; e < N_BLOB; e += 1024) {
+        const Fr x = load_fr_be(blob + 32 * e);
+        bad |= geq_mod<FrParams>(x.v);
+        lds_store(s, e, fr29_from_plain(x));  // the integer itself: < 2^256 < 3r, normalised limbs
+    }
+    if (tid < 64) {  // wave 0, no divergence: lanes 0..31 raise z, lanes 32..63 raise z^32, to the power tid mod 32
+        const bool hi = tid >= 32;
+        Fr29 base = fr29_partial_reduce(fr29_from_fr_mont(z_mont[b]));  // z 2^261: < 32r -> < 2r
+#pragma unroll 1
+        for (int i = 0; i < 5; i++) {
+            const Fr29 sq = fr29_mul(base, base);
+#pragma unroll
+            for (int l = 0; l < RL; l++) base.v[l] = hi ? sq.v[l] : base.v[l];
+        }
+        Fr29 acc = K.one;  // 2^261 mod r: the Montgomery form of 1
+#pragma unroll 1
+        for (int bit = 4; bit >= 0; bit--) {
+            acc = fr29_mul(acc, acc);
+            const Fr29 m = fr29_mul(acc, base);
+            const bool take = ((tid & 31) >> bit) & 1;
+#pragma unroll
+            for (int l = 0; l < RL; l++) acc.v[l] = take ? m.v[l] : acc.v[l];
+        }
+#pragma unroll
+        for (int l = 0; l < RL; l++) pw[hi ? 1 : 0][l][tid & 31] = acc.v[l];
+    }
+    const bool refused = __syncthreads_or(bad) != 0;  // the barrier between the input stage (and the tables) and what reads them
+    if (refused) {                                    // uniform over the block
+        if (tid < 8) {
+            reinterpret_cast<uint32_t*>(y_be32 + (size_t)b * 32)[tid] = 0;
+            y_mont[b].v[tid] = 0;
+        }
+        if (tid == 0) bad_out[b] = 1;
+        return;
+    }
+    ntt4096_dit_inverse(s, w29);  // < 27 r; thread tid's own unit left tid + 1024 k
+    auto power = [&](int t, int e) {
+        Fr29 r;
+#pragma unroll
+        for (int l = 0; l < RL; l++) r.v[l] = pw[t][l][e];
+        return r;
+    };
+    const Fr29 z1024 = fr29_mul(power(1, 31), power(1, 1));
+    Fr29 acc = lds_load(s, tid + 3072);                                         // < 27r
+    acc = fr29_add<false>(fr29_mul(acc, z1024), lds_load(s, tid + 2048));       // 27 x 2 <= 64: < 2r, + < 27r: < 29r, limbs < 2^30
+    acc = fr29_add<false>(fr29_mul(acc, z1024), lds_load(s, tid + 1024));       // 29 x 2 <= 64: < 29r again
+    acc = fr29_add<false>(fr29_mul(acc, z1024), lds_load(s, tid));              // < 29r
+    Fr29 t = fr29_mul(acc, fr29_mul(power(0, tid & 31), power(1, tid >> 5)));   // 29 x 2 <= 64: this thread's share of n p(z), < 2r
+    // the block sum: 1024 values < 2r are 2048r, far beyond 2^261 ~ 70r: reduced after every three levels (fr29_sum8_lanes)
+    t = fr29_sum8_lanes(t, 1);
+    t = fr29_sum8_lanes(t, 8);  // the wave's 64: < 2r
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int l = 0; l < RL; l++) wave_sum[l][tid >> 6] = t.v[l];
+    }
+    __syncthreads();
+    if (tid >= 64) return;
+    const int w = tid & 15;  // wave 0: every lane takes part in the shuffles, lanes 16.. hold copies
+#pragma unroll
+    for (int l = 0; l < RL; l++) t.v[l] = wave_sum[l][w];
+    t = fr29_sum8_lanes(t, 1);                       // 8 waves: < 2r
+    t = fr29_add<false>(t, fr29_shfl_xor(t, 8));     // all 16: S = n p(z) mod r, < 4r, limbs < 2^30
+    if (tid == 0) {
+        store_fr_be(y_be32 + (size_t)b * 32, fr_words_of(fr29_reduce_once(fr29_mul(t, K.ninv_plain))));  // 4 x 1 <= 64
+        y_mont[b] = fr_words_of(fr29_reduce_once(fr29_mul(t, K.ninv_to_sat)));
+        bad_out[b] = 0;
+    }
+}
+
 // Stage H+I: cells = bit_reverse(NTT_8192(coeffs || 0)) serialised big-endian
 // (prover.rs:158-165, serialization/src/lib.rs:132-156).  X[2k+h] = NTT_4096(a_i * w8192^(i*h))[k];
 // the forward network leaves half h bit-reversed in place, which is exactly cells[h*4096 ...].
@@ -333,6 +439,7 @@ static Fr as_fr(const Fr8& x) { Fr r; for (int i = 0; i < 8; i++) r.v[i] = x.v[i
 constexpr size_t LDS_NTT29 = (size_t)N_BLOB * RL * 4;  // 144 KiB: one 4096-point transform of 9-limb elements resident in LDS
 void init_attributes() {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_coeffs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_eval_at), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
 #ifdef KZG_TEST_HOOKS
@@ -367,6 +474,10 @@ void ntt_twiddles29(const void* w8192_mont_host /*Fr[8192]*/, void* out_host /*8
 }
 void blob_to_coeffs(int n, const uint8_t* blobs, void* coeffs, void* canon, int* status, const void* w29, const Fr8& n_inv, hipStream_t st) {
     k_blob_to_coeffs<<<n, 1024, LDS_NTT29, st>>>(blobs, (Fr*)coeffs, (Fr*)canon, status, (const Fr29*)w29, ntt_consts(n_inv));
+}
+void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be32, void* y_mont, int* bad, const void* w29, const Fr8& n_inv,
+                  hipStream_t st) {
+    if (n > 0) k_blob_eval_at<<<n, 1024, LDS_NTT29, st>>>(blobs, (const Fr*)z_mont, y_be32, (Fr*)y_mont, bad, (const Fr29*)w29, ntt_consts(n_inv));
 }
 void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st) {
     k_coeffs_to_cells<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, cells, (const Fr29*)w29);

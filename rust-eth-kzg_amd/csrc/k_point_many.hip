@@ -8,6 +8,7 @@
 // pairs this file leaves in HBM.  This file adds:
 //   k_pm_leaf_bodies  the 176 bytes "RCKZGPROOFLEAF_1" | C_i | z_i | y_i | pi_i of every leaf, gathered for k_sha256_many (device form)
 //   k_pm_status       the item's status in the single call's order: 2 a point is no canonical subgroup point, else 1 z or y >= r, else 0
+//   k_pm_blob_status  the same for an item that came as a blob: 1 the blob holds an element >= r, else 2 a point is bad, else 0
 //   k_pm_mul          ONE LANE PER SCALAR MULTIPLICATION, four per item, with the per-lane GLV multiplication of vm_lane_mul.hpp:
 //                     rho pi and rho C (127 bits: k1 only), (rho z mod r) pi and (rho y mod r) G (255 bits, balanced halves).  The G
 //                     term is taken PER ITEM, so that the pair of every range is a plain sum of resident pairs.  The lanes of a wave
@@ -53,6 +54,16 @@ __global__ __launch_bounds__(256) void k_pm_status(const int* __restrict__ point
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     status[i] = (point_status[n + i] || point_status[i]) ? ERR_G1 : (z_bad[i] || y_bad[i]) ? ERR_SCALAR : OK;
+}
+
+// The blob source: z and y are the verifier's own, so only the blob and the points can refuse an item, the blob first (verify_host.hpp:
+// blob_item_status; crates/eip4844/src/verifier.rs:49-74).  One lane per item; a lane behind the last item repeats it and stores nothing.
+__global__ __launch_bounds__(256) void k_pm_blob_status(const int* __restrict__ point_status, const int* __restrict__ blob_bad,
+                                                        int* __restrict__ status, int n) {
+    const int lane = blockIdx.x * 256 + threadIdx.x;
+    const int i = lane < n ? lane : n - 1;
+    const int s = blob_bad[i] ? ERR_SCALAR : (point_status[n + i] || point_status[i]) ? ERR_G1 : OK;
+    if (lane < n) status[i] = s;
 }
 
 // products e < n: rho_e pi_e -> pairs[2 e];  then into terms: n <= e < 2n: rho C;  2n <= e < 3n: (rho z) pi;  3n <= e < 4n: (rho y) G.
@@ -101,6 +112,9 @@ void pm_leaf_bodies(const uint8_t* commitments, const uint8_t* zs, const uint8_t
 }
 void pm_status(const int* point_status, const int* z_bad, const int* y_bad, int* status, int n, hipStream_t st) {
     if (n > 0) k_pm_status<<<(n + 255) / 256, 256, 0, st>>>(point_status, z_bad, y_bad, status, n);
+}
+void pm_blob_status(const int* point_status, const int* blob_bad, int* status, int n, hipStream_t st) {
+    if (n > 0) k_pm_blob_status<<<(n + 255) / 256, 256, 0, st>>>(point_status, blob_bad, status, n);
 }
 void pm_mul(const void* pts, const void* gen, const void* z_mont, const void* y_mont, const uint32_t* rho, const int* status, void* pairs, void* terms,
             int n, const Fp12w& beta, hipStream_t st) {

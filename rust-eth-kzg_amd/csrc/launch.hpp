@@ -25,6 +25,11 @@ constexpr size_t SIZEOF_FR29 = 36;
 void ntt_twiddles29(const void* w8192_mont_host /*Fr[8192]*/, void* out_host /*8192 x 36 B*/);
 void blob_to_coeffs(int n, const uint8_t* blobs, void* coeffs /*Fr*/, void* canon /*Fr or null*/, int* status,
                     const void* w29, const Fr8& n_inv, hipStream_t st);
+// y_b = p_b(z_b) for n blobs, inside the CU (k_blob_eval_at): blobs 4-byte aligned, z_mont[n] Montgomery Fr (fr_from_be32's output);
+// y_be32[n][32] canonical big-endian bytes (4-byte aligned), y_mont[n] Montgomery Fr, bad[n] = 1 for a blob with an element >= r (its
+// y is zero in both forms).  Writes nothing else and needs no workspace.
+void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be32, void* y_mont, int* bad, const void* w29, const Fr8& n_inv,
+                  hipStream_t st);
 void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st);
 // every scalar leaves as its balanced GLV halves (what launch::glv_split would make of it)
 void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, const Fr8& inv128, int segs, const Fr8* seg_shifts,
@@ -194,6 +199,8 @@ void vm_fold_ranges(const void* prod, const int* ranges /*[n_ranges][2], device*
 void pm_leaf_bodies(const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys, const uint8_t* proofs, uint8_t* bodies, int n, hipStream_t st);
 // status[i] = 2 if point_status[n + i] (commitment) or point_status[i] (proof), else 1 if z_bad[i] or y_bad[i], else 0
 void pm_status(const int* point_status /*[proofs n | commitments n]*/, const int* z_bad, const int* y_bad, int* status, int n, hipStream_t st);
+// the blob source (verify_host.hpp: blob_item_status): status[i] = 1 if blob_bad[i], else 2 if point_status[n + i] or point_status[i], else 0
+void pm_blob_status(const int* point_status /*[proofs n | commitments n]*/, const int* blob_bad, int* status, int n, hipStream_t st);
 // pts = [proofs n | commitments n] (G1Affine), gen = G (G1Affine), z / y Montgomery Fr, rho[n][4].  pairs[2 i] = rho_i pi_i;
 // terms[3][n] = rho C | (rho z) pi | (rho y) G; an item whose status is not 0 gets the identity everywhere (JacQ)
 void pm_mul(const void* pts, const void* gen, const void* z_mont, const void* y_mont, const uint32_t* rho, const int* status, void* pairs, void* terms,
@@ -207,6 +214,7 @@ void quotient_by_linear(int n, const void* coeffs, const void* z_mont, void* quo
 // value >= r gives bad[i] = 1 and the point 0
 void fr_from_be32(int n, const uint8_t* in, void* out_mont, int* bad, bool reduce, hipStream_t st);
 void fr_to_be32(int n, const void* canon /*Fr*/, uint8_t* out, hipStream_t st);
+void fr_mont_to_be32(int n, const void* mont /*Fr*/, uint8_t* out, hipStream_t st);  // the same from the Montgomery form
 // out[i] = 1 if blob_bad[i], else 1 if z_bad[i], else 2 if g1_bad[i], else 0 (z_bad / g1_bad may be null)
 void status_4844(int n, const int* blob_bad, const int* z_bad, const int* g1_bad, int* out, hipStream_t st);
 

@@ -17,6 +17,15 @@
 //                  after the other at 16384 items, a serial tail of ~130 dependent additions behind products that fill the chip; the
 //                  two levels are 1 + 7 and 1 + 7 dependent additions.)
 // Down the link go the status words, the n x 32 leaf digests (device form) and the sums; up go the weights (and the host form's items).
+// THE BLOB SOURCE (eth_kzg_amd_verify_blob_kzg_proof_many / _many_device; the statement: verify_host.hpp): the item comes as (blob,
+// commitment, proof) and the pass makes z and y itself, then is the pass above from "decoding" on.
+//   host threads : host form: gather the blobs (128 KB each) into the pinned slab and, the bytes being in their cache, hash blob_challenge
+//                  (eip4844.hip: proofs_batch_host says why the host hashes what it holds); ONE upload of blobs, proofs, commitments, z
+//   GPU          : device form: proofs and commitments device-to-device into the arena, z = k_sha256_many over the caller's blobs WHERE
+//                  THEY LIE plus the arena's commitments, behind a header the slot owns, reduced by fr_from_be32; both: y = p(z) by
+//                  k_blob_eval_at (k_ntt.hip: inside the CU, no workspace), the leaves' bodies gathered and hashed on the GPU -- y exists
+//                  only there --, the merged status (k_pm_blob_status), then the products as above
+// Nothing of it takes mu_, calls ensure_workspace or touches the engine's coefficient arrays: d_w29_ and n_inv4096_ are constants.
 #include "vm_search.hpp"
 
 namespace kzg {
@@ -26,10 +35,13 @@ constexpr int FOLD_SPAN = 128;  // items per first-level range of the full-range
 
 struct PointPassLayout {
     const int n;
+    const int blobs;  // 0: the items bring z and y; 1: blobs staged through the slab (host form); 2: blobs read where they lie (device form)
     const int n_l1 = (n + FOLD_SPAN - 1) / FOLD_SPAN;  // first-level ranges of the full-range fold
     const int max_ranges = std::min(n, 2048);          // probes per level of the search
     static constexpr size_t JACQ = launch::SIZEOF_JACQ;
     Carve d;  // (members are initialised in the order they stand here)
+    // the blob source's own arrays take no room otherwise (Carve: an array of no bytes): the other sources' layout is what it was
+    const size_t off_blob = d.take(blobs == 1 ? (size_t)n * BYTES_PER_BLOB : 0), off_hdr = d.take(blobs == 2 ? 32 : 0);
     // inputs: one upload in the host form, device-to-device copies in the device form; then the fold's ranges and the weights
     const size_t off_p = d.take((size_t)n * 48), off_c = d.take((size_t)n * 48), off_z = d.take((size_t)n * 32), off_y = d.take((size_t)n * 32),
                  in_bytes = d.end, off_frng = d.take((size_t)(n_l1 + 1) * 8), off_rho = d.take((size_t)n * 16), in2_bytes = d.end;
@@ -42,8 +54,9 @@ struct PointPassLayout {
                  off_ym = d.take((size_t)n * sizeof(Fr)), off_pairs = d.take((size_t)2 * n * JACQ), off_terms = d.take((size_t)3 * n * JACQ),
                  off_l1 = d.take((size_t)2 * n_l1 * JACQ), off_fold = d.take(2 * JACQ), off_rng = d.take((size_t)max_ranges * 8),
                  off_rsum = d.take((size_t)2 * max_ranges * JACQ), off_bodies = d.take((size_t)n * PointProofTranscript::LEAF_BYTES),
-                 off_leaf = d.take((size_t)n * 32), dev_bytes = d.end;
-    explicit PointPassLayout(int n_) : n(n_) {}
+                 off_leaf = d.take((size_t)n * 32), off_dig = d.take(blobs == 2 ? (size_t)n * 32 : 0), off_bbad = d.take(blobs ? (size_t)n * 4 : 0),
+                 dev_bytes = d.end;
+    explicit PointPassLayout(int n_, int blobs_) : n(n_), blobs(blobs_) {}
 };
 }  // namespace
 
@@ -51,7 +64,7 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
     const int n_all = (int)n64;
     for (int i = 0; i < n_all; i++) { verified[i] = 0; status[i] = OK; }
     if (n_all == 0) return OK;
-    const int P = tap && tap->pass_size > 0 ? tap->pass_size : POINT_MANY_PASS;
+    const int P = tap && tap->pass_size > 0 ? tap->pass_size : in.from_blobs ? BLOB_MANY_PASS : POINT_MANY_PASS;
     std::vector<uint64_t> starts;
     for (uint64_t lo = 0; lo < n64; lo = point_pass_end(n64, lo, (uint64_t)P)) starts.push_back(lo);
     starts.push_back(n64);
@@ -59,6 +72,7 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
     if (tap) {
         tap->pass_starts = starts;
         tap->leaves.assign((size_t)n_all * 32, 0);
+        if (in.from_blobs) { tap->zs.assign((size_t)n_all * 32, 0); tap->ys.assign((size_t)n_all * 32, 0); }
         tap->rho.assign((size_t)n_all * 4, 0);
         tap->seeds.assign((size_t)n_passes * 32, 0);
         tap->fold.assign((size_t)n_passes * 2 * launch::SIZEOF_JACQ, 0xff);
@@ -81,8 +95,8 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         HIPCK(hipSetDevice(dev_));
         const int slot_index = (int)(slot - vm_slot_);
         hipStream_t st = work_[1 + slot_index % (NW - 1)].stream ? work_[1 + slot_index % (NW - 1)].stream : stream_;  // (verify_many.hip: why no stream of its own)
-        TraceLap lap{knobs_.trace, "verify_kzg_proof_many"};
-        const PointPassLayout L(n);
+        TraceLap lap{knobs_.trace, src.from_blobs ? "verify_blob_kzg_proof_many" : "verify_kzg_proof_many"};
+        const PointPassLayout L(n, !src.from_blobs ? 0 : src.on_device ? 2 : 1);
         grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
         grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
         uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
@@ -96,7 +110,45 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)2 * n * 4, st));
         HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, 2 * launch::SIZEOF_JACQ, st));
         // ---- the items into the arena
-        if (src.on_device) {
+        const uint8_t* d_blobs = nullptr;
+        if (src.from_blobs) {
+            if (src.on_device) {
+                if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
+                if (src.user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
+                    HIPCK(hipEventRecord(slot->ordered, src.user_stream));
+                    HIPCK(hipStreamWaitEvent(st, slot->ordered, 0));
+                }
+                blob_challenge_header(hb + L.off_hdr);  // the slot's own copy of the 32 bytes (the engine's lives under mu_)
+                HIPCK(hipMemcpyAsync(db + L.off_hdr, hb + L.off_hdr, 32, hipMemcpyHostToDevice, st));
+                HIPCK(hipMemcpyAsync(db + L.off_p, src.d_proofs, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+                HIPCK(hipMemcpyAsync(db + L.off_c, src.d_commitments, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+                d_blobs = src.d_blobs;
+                launch::sha256_many(n, db + L.off_hdr, 32, d_blobs, BYTES_PER_BLOB, BYTES_PER_BLOB, db + L.off_c, 48, 48, db + L.off_dig, st);
+                launch::fr_from_be32(n, db + L.off_dig, db + L.off_zm, nullptr, /*reduce=*/true, st);
+                launch::fr_mont_to_be32(n, db + L.off_zm, db + L.off_z, st);
+            } else {
+                parallel_for(n, T, pool, [&](int i) {
+                    uint8_t* const blob = hb + L.off_blob + (size_t)i * BYTES_PER_BLOB;
+                    memcpy(blob, src.blobs[i], BYTES_PER_BLOB);
+                    memcpy(hb + L.off_p + (size_t)i * 48, src.proofs[i], 48);
+                    memcpy(hb + L.off_c + (size_t)i * 48, src.commitments[i], 48);
+                    fr_to_be(hb + L.off_z + (size_t)i * 32, from_mont(blob_challenge(blob, hb + L.off_c + (size_t)i * 48)));
+                });
+                lap("stage + challenges (host)");
+                HIPCK(hipMemcpyAsync(db, hb, L.off_y, hipMemcpyHostToDevice, st));  // blobs | proofs | commitments | z
+                d_blobs = db + L.off_blob;
+                launch::fr_from_be32(n, db + L.off_z, db + L.off_zm, (int*)(db + L.off_zbad), /*reduce=*/false, st);  // (a reduced digest: never refused)
+            }
+            launch::blob_eval_at(n, d_blobs, db + L.off_zm, db + L.off_y, db + L.off_ym, (int*)(db + L.off_bbad), d_w29_, n_inv4096_, st);
+            launch::pm_leaf_bodies(db + L.off_c, db + L.off_z, db + L.off_y, db + L.off_p, db + L.off_bodies, n, st);
+            launch::sha256_many(n, nullptr, 0, db + L.off_bodies, PointProofTranscript::LEAF_BYTES, (uint32_t)PointProofTranscript::LEAF_BYTES, nullptr, 0, 0,
+                                db + L.off_leaf, st);
+            HIPCK(hipMemcpyAsync(h_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+            if (tap) {  // the pinned staging rows of z and y are free behind the upload
+                HIPCK(hipMemcpyAsync(hb + L.off_z, db + L.off_z, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+                HIPCK(hipMemcpyAsync(hb + L.off_y, db + L.off_y, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+            }
+        } else if (src.on_device) {
             if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
             if (src.user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
                 HIPCK(hipEventRecord(slot->ordered, src.user_stream));
@@ -124,13 +176,17 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
         int* d_stp = (int*)(db + L.off_stp);
         launch::g1_decompress2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, n, beta_, st);
-        launch::fr_from_be32(n, db + L.off_z, db + L.off_zm, (int*)(db + L.off_zbad), /*reduce=*/false, st);
-        launch::fr_from_be32(n, db + L.off_y, db + L.off_ym, (int*)(db + L.off_ybad), /*reduce=*/false, st);
-        launch::pm_status(d_stp, (const int*)(db + L.off_zbad), (const int*)(db + L.off_ybad), (int*)(db + L.off_st), n, st);
+        if (src.from_blobs) {
+            launch::pm_blob_status(d_stp, (const int*)(db + L.off_bbad), (int*)(db + L.off_st), n, st);
+        } else {
+            launch::fr_from_be32(n, db + L.off_z, db + L.off_zm, (int*)(db + L.off_zbad), /*reduce=*/false, st);
+            launch::fr_from_be32(n, db + L.off_y, db + L.off_ym, (int*)(db + L.off_ybad), /*reduce=*/false, st);
+            launch::pm_status(d_stp, (const int*)(db + L.off_zbad), (const int*)(db + L.off_ybad), (int*)(db + L.off_st), n, st);
+        }
         HIPCK(hipMemcpyAsync(h_st, db + L.off_st, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         HIPCK(hipGetLastError());
         lap("enqueue (host)");
-        if (!src.on_device) {  // meanwhile, on the host threads: the leaves, from the caller's bytes as they lie in the slab
+        if (!src.on_device && !src.from_blobs) {  // meanwhile, on the host threads: the leaves, from the caller's bytes as they lie in the slab
             parallel_for(n, T, pool, [&](int i) {
                 PointProofTranscript::leaf(hb + L.off_c + (size_t)i * 48, hb + L.off_z + (size_t)i * 32, hb + L.off_y + (size_t)i * 32,
                                            hb + L.off_p + (size_t)i * 48, h_leaf + (size_t)i * 32);
@@ -138,7 +194,7 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
             lap("leaf hashes (host)");
         }
         SYNC_CHECKED(st);
-        lap(src.on_device ? "decode + leaf hashes (GPU)" : "wait decode");
+        lap(src.from_blobs ? "challenges + evaluations + decode + leaf hashes (GPU)" : src.on_device ? "decode + leaf hashes (GPU)" : "wait decode");
         // ---- statuses; the seed and the weights of ALL the items of the pass
         std::vector<char> live(n, 0);
         int n_live = 0;
@@ -157,6 +213,10 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         lap("seed + weights (host)");
         if (tap) {
             memcpy(tap->leaves.data() + lo * 32, h_leaf, (size_t)n * 32);
+            if (src.from_blobs) {
+                memcpy(tap->zs.data() + lo * 32, hb + L.off_z, (size_t)n * 32);
+                memcpy(tap->ys.data() + lo * 32, hb + L.off_y, (size_t)n * 32);
+            }
             memcpy(tap->seeds.data() + (size_t)pass * 32, seed, 32);
             memcpy(tap->rho.data() + lo * 4, h_rho, (size_t)n * 16);
         }

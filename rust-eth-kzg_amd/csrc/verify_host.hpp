@@ -1,8 +1,8 @@
 // The host's share of verification and recovery that is pure computation over bytes: input validation, de-duplication, the scalar
 // codecs and the Fiat-Shamir transcripts (the reference's four, the leaf-hashed challenge of the cell verifier and the leaves, seed and
 // weights of the point many-verification), each stated ONCE for verify.hip, verify_many.hip, point_many.hip, eip4844.hip and recover.hip.
-// No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp, test_many_leaf.cpp and
-// test_point_many.cpp run it on the CPU against hashlib.
+// No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp, test_many_leaf.cpp,
+// test_point_many.cpp and test_blob_many.cpp run it on the CPU against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -310,5 +310,36 @@ inline int point_item_status(bool commitment_bad, bool proof_bad, const uint8_t*
     if (geq_mod<FrParams>(fr_words_from_be(z).v) || geq_mod<FrParams>(fr_words_from_be(y).v)) return 1;
     return 0;
 }
+
+// ---- eth_kzg_amd_verify_blob_kzg_proof_many / _many_device (point_many.hip, the blob source): MANY items (blob, commitment, proof), a
+// verdict for each -- exactly what Verifier::verify_blob_kzg_proof (crates/eip4844/src/verifier.rs:49-74) says of the item alone.
+// There is NO new transcript: item i of a pass becomes the point item (C_i, z_i, y_i, pi_i) of PointProofTranscript above with
+//     z_i = blob_challenge(blob_i, commitment_i)   hashed from the caller's bytes as they stand, also when they are invalid; the leaf
+//                                                  takes its 32 canonical big-endian bytes
+//     y_i = p_i(z_i)                               32 canonical big-endian bytes (k_ntt.hip: k_blob_eval_at); 32 zero bytes if the blob
+//                                                  is refused
+// and leaves, seed, weights, pairs, the full-range check and the search are the point path's, unchanged; a call is cut into passes of at
+// most BLOB_MANY_PASS items (the host form stages 128 KB per item in the pass slot's pinned slab).
+// Soundness is the point path's.  The equation checked per item is over exactly (C, z, y, pi), and the leaves bind all four, so the
+// argument above holds word for word: no weight is known before every byte of (C_i, z_i, y_i, pi_i) of every item of the pass is fixed.
+// That z and y are not the caller's takes nothing from it -- the prover of a wrong item still has to fix C_i and pi_i (and with them,
+// through the blob, z_i and y_i) before rho_i exists -- and it is what makes the item's equation the statement about the BLOB: z and y
+// are computed by the verifier from the blob's and the commitment's bytes, never supplied, exactly as in the single call.
+// The one new statement is the status of an item, in the single call's order of checks (Engine::verify_blob_kzg_proof_host: the blob is
+// opened first, then verify_kzg_proof_host decodes the commitment, then the proof; z is a reduced digest and y an evaluation, so neither
+// can be out of range): 1 if the blob holds an element >= r -- also when a point is bad as well --, else 2 if the commitment or the proof
+// is not a canonical point of the subgroup, else 0.  Only items of status 0 are live: they alone enter the sums, and only they can be
+// verified.  commitment_status / proof_status: what the decoding left, 0 = a canonical point of the subgroup (k_point_many.hip:
+// k_pm_blob_status is the kernel's copy).
+constexpr uint64_t BLOB_MANY_MAX_ITEMS = 1u << 24;
+constexpr int BLOB_MANY_PASS = 256;  // the product's pass size for the blob source (32 MB of slab); not part of the contract
+inline int blob_item_status(bool blob_bad, int commitment_status, int proof_status) {
+    if (blob_bad) return 1;
+    if (commitment_status != 0 || proof_status != 0) return 2;
+    return 0;
+}
+inline bool blob_item_live(int status) { return status == 0; }
+// what the call hands out for an item: its status, and the pass's verdict on it only if it is live
+inline bool blob_item_verified(int status, bool pair_passed) { return blob_item_live(status) && pair_passed; }
 
 }  // namespace kzg
