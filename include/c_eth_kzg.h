@@ -247,7 +247,8 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_combine(const DASContext *ctx, u
  * threads in parallel, and the pairing checks of a pass are folded into one with 127-bit weights derived from all the
  * challenges (error 2^-127, the argument of the powers of r inside one batch); in a pass that contains wrong proofs they are
  * found by folding sub-ranges of the resident weighted sums (a handful of pairings per wrong proof instead of one per problem)
- * down to single problems, so a false verdict is always exact and per problem.  A problem may hold at most 2^24 - 1 cells.  Per problem: status[b] = 0 and verified[b] = the verdict, or
+ * down to single problems, so a false verdict is always exact and per problem.  Where a level of that search holds many probes their
+ * pairings run on the GPU, one per lane (ETH_KZG_AMD_GPU_PAIRING_MIN; neither verdicts nor statuses depend on it).  A problem may hold at most 2^24 - 1 cells.  Per problem: status[b] = 0 and verified[b] = the verdict, or
  * status[b] = 1 (a cell holds a non-canonical field element), 2 (bad G1 encoding / not in the subgroup), 3 (invalid lengths
  * or indices) and verified[b] = false -- what the single form reports as Err (status may be NULL).  The CResult is Err only
  * for a call-level (device) failure.  An empty problem verifies (verifier.rs:90-93). */
@@ -333,7 +334,9 @@ CResult eth_kzg_amd_verify_blob_kzg_proof_batch_device(const DASContext *ctx, ui
  * 16384; not part of the contract) are hashed into leaves, the leaves into a seed, the seed into a 127-bit weight rho_i per item, and
  * ONE pairing check of  ( sum rho_i pi_i , sum rho_i (C_i + z_i pi_i - y_i G) )  over the pass's valid items passes only if every
  * one of them is valid (error 2^-127: no weight is known before every input byte is fixed); if it fails the wrong items are searched
- * by checking the pairs of sub-ranges down to single items, and a single item whose own pair fails is wrong exactly.  The scalar
+ * by checking the pairs of sub-ranges down to single items, and a single item whose own pair fails is wrong exactly.  Where a level of
+ * that search holds many probes their pairings run on the GPU, one per lane (ETH_KZG_AMD_GPU_PAIRING_MIN; neither
+ * verdicts nor statuses depend on it).  The scalar
  * multiplications run one lane each on the GPU (csrc/k_point_many.hip), the pass on a pass slot of the many-verification: the call
  * does not take the context's big lock and runs next to every other entry point.  The identity is a valid commitment and a valid proof.
  * Host form: cut into contiguous slices by item over the context's device list; the host threads hash the leaves.
@@ -364,7 +367,8 @@ CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext *ctx, uint64_t
  * z_i = H("FSBLOBVERIFY_V1_" | 4096 | blob_i | commitment_i) mod r hashed from the caller's bytes as they stand and y_i = p_i(z_i)
  * evaluated on the GPU without leaving the CU (csrc/k_ntt.hip: k_blob_eval_at -- one block per blob: the inverse transform in LDS, then
  * the 4096 coefficients are summed against powers of z where they lie; no coefficient and no quotient is written to HBM); y_i is 32 zero
- * bytes for a refused blob.  Leaves, seed, weights, the one pairing check per pass and the search are that call's, unchanged, and so is
+ * bytes for a refused blob.  Leaves, seed, weights, the one pairing check per pass and the search are that call's, unchanged (the
+ * search's pairings on the GPU from ETH_KZG_AMD_GPU_PAIRING_MIN probes per level included), and so is
  * the soundness argument (csrc/verify_host.hpp): the per-item equation is over exactly (C, z, y, pi), all of which the leaves bind, and
  * z and y are computed by the verifier, not supplied.  The leaves are hashed on the GPU in both forms (y exists only there).  A pass
  * holds at most 256 items (not part of the contract) and runs on a pass slot: the call does not take the context's big lock, needs

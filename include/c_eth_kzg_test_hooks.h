@@ -188,6 +188,23 @@ int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext *ctx, uint
                                                      int32_t *fold_verdicts, int32_t *probes4, uint8_t *probe_sums96, uint64_t max_probes,
                                                      uint64_t *n_probes, uint8_t *zs32, uint8_t *ys32);
 
+/* k_pairing_check alone (csrc/k_pairing.hip), next to the host's checks of the same pairs.  key: 0 = ([tau^64]_2, -[1]_2), the cell
+ * verifier's pair of keys; 1 = ([tau]_2, -[1]_2), the point verifier's.  pairs: n x 2 x 48 bytes, compressed G1 (on the curve; no subgroup
+ * test), 1 <= n <= 65536.  They are decompressed on the host and become the passes' Jacobian form.  rescale, a word of flags: bit 0 = every
+ * point is multiplied through by a Z != 1 of its own (non-normalised inputs); bit 1 = the second slot of entry (rescale >> 8) is left at
+ * the 0xff poison of the passes' result slots.  Outputs, host: out_gpu[n] the kernel's verdicts, out_host[n] the host threads' (1 / 0;
+ * -1 for a poisoned entry); out_miller_gpu / out_miller_host (each may be NULL): n x 576 bytes, the Miller values before the final
+ * exponentiation, as the words of the tower's Fp12 (the host's: the product of the two single Miller loops; 1 for a poisoned entry).
+ * Synchronous; 0 on success, 3 where the context has no device route (a key at infinity). */
+int eth_kzg_amd_test_pairing_check_many(const DASContext *ctx, int key, uint64_t n, const uint8_t *pairs, int rescale, int8_t *out_gpu,
+                                        int8_t *out_host, uint8_t *out_miller_gpu, uint8_t *out_miller_host);
+
+/* out4[0] = the probes of the last call through one of the *_many_sums hooks whose pairing ran on the GPU (counting the single-entry probes
+ * at the end of a search, which the probe lists of the cell form do not hold), out4[1] = the probes in that call's list; out4[2], out4[3] =
+ * nanoseconds the last eth_kzg_amd_test_pairing_check_many spent on the GPU route (launch, verdict bytes down, wait) and on the host
+ * threads' checks.  Returns 0. */
+int eth_kzg_amd_test_search_stats(const DASContext *ctx, uint64_t *out4);
+
 /* The Reed-Solomon decoder of recovery on its own (Engine::rs_decode in recover.hip, exactly the launches recovery runs).  R >= 1 blobs; blob r has
  * n_cells[r] cells with ascending indices cell_indices[r][..] < 128, 64 <= n_cells[r] <= 128 (anything else: return 3, nothing is
  * launched).  flat_source = 0: cells[r][k] -> 2048 bytes (the list form of recover_cells_and_proofs_batch); 1: cells[r][0] -> the flat

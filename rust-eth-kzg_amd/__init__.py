@@ -90,6 +90,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_verify_many_sums_ex", "eth_kzg_amd_test_verify_many_sums_device",
     "eth_kzg_amd_test_verify_kzg_proof_many_sums",
     "eth_kzg_amd_test_blob_eval_at", "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums",
+    "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats",
 ]
 
 _lib = None
@@ -228,6 +229,8 @@ def load_library():
         "eth_kzg_amd_test_verify_many_sums_device": [P, U64, P, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P],
         "eth_kzg_amd_test_verify_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P],
         "eth_kzg_amd_test_blob_eval_at": [P, U64, P, P, P, P],
+        "eth_kzg_amd_test_pairing_check_many": [P, C.c_int, U64, P, C.c_int, P, P, P, P],
+        "eth_kzg_amd_test_search_stats": [P, P],
         "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P, P, P],
     }.items():
         if hasattr(lib, name):

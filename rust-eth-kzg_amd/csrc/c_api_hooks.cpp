@@ -186,6 +186,16 @@ int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext* ctx, uint
     return eng(ctx)->test_verify_kzg_proof_many_sums(n, in, forced_pass, verified, status, pass_starts, max_passes, n_passes, leaves32, seeds32, rho, fold96,
                                                      fold_verdicts, probes4, probe_sums96, max_probes, n_probes, zs32, ys32);
 }
+int eth_kzg_amd_test_pairing_check_many(const DASContext* ctx, int key, uint64_t n, const uint8_t* pairs, int rescale, int8_t* out_gpu, int8_t* out_host,
+                                        uint8_t* out_miller_gpu, uint8_t* out_miller_host) {
+    if ((key != 0 && key != 1) || n < 1 || n > (1u << 16) || !pairs || !out_gpu || !out_host || rescale < 0) return kzg::ERR_INPUT;
+    return eng(ctx)->test_pairing_check_many(key, n, pairs, rescale, out_gpu, out_host, out_miller_gpu, out_miller_host);
+}
+int eth_kzg_amd_test_search_stats(const DASContext* ctx, uint64_t* out4) {
+    if (!out4) return kzg::ERR_INPUT;
+    eng(ctx)->test_search_stats(out4);
+    return 0;
+}
 int eth_kzg_amd_test_rs_decode(const DASContext* ctx, int R, const uint64_t* n_cells, const uint64_t* const* cell_indices,
                                const uint8_t* const* const* cells, int flat_source, int32_t* status, int32_t* deg, uint8_t* zp, uint8_t* zeval,
                                uint8_t* zcinv, uint8_t* coeffs) {

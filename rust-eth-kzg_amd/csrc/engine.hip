@@ -373,7 +373,7 @@ void Engine::teardown() noexcept {
     host_pool_.reset();  // joins the helper threads before anything they might touch goes away
     vm_pool_.reset();
     stage_pool_.reset();
-    void* ptrs[] = {d_w8192_, d_w29_, d_tapk_, d_naf_, d_srs_, d_fk_bases_, d_in_, d_cells_, d_proofs_, d_coset_, d_coset_inv_, d_circ_terms_, d_4844_};
+    void* ptrs[] = {d_w8192_, d_w29_, d_tapk_, d_naf_, d_srs_, d_fk_bases_, d_in_, d_cells_, d_proofs_, d_coset_, d_coset_inv_, d_circ_terms_, d_4844_, d_pairing_};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (SlpProgram& P : slp_prog_) {

@@ -46,6 +46,7 @@ struct VerifyManyTap {
     std::vector<uint8_t> fold;                       // [2] JacQ: the folded pair
     std::vector<int> probes;                         // the search's probes in order: lo, hi, passed
     std::vector<uint8_t> probe_sums;                 // [probe][2] JacQ
+    int device_probes = 0;                           // probes whose pairing ran on the GPU (k_pairing_check); the others ran on the host threads
     std::vector<uint8_t> digests;                    // [Bc][32]: the digest each problem's challenge was reduced from (zero: not hashed)
     std::vector<uint8_t> leaves;                     // (leaf-hashed challenges) [n][32]: the leaf digests of the pass's cells as they came down
 };
@@ -121,6 +122,7 @@ struct PointManyTap {
     std::vector<int> fold_verdict;       // [passes]
     std::vector<int> probes;             // the searches' probes in order: pass, lo, hi (positions in the pass), passed
     std::vector<uint8_t> probe_sums;     // [probe][2] JacQ
+    int device_probes = 0;               // probes whose pairing ran on the GPU (k_pairing_check); the others ran on the host threads
 };
 
 // How a single cell verification takes its Fiat-Shamir challenge (verify.hip).  Null or `leaf` false: the reference's transcript, one
@@ -392,6 +394,14 @@ public:
                                         uint64_t* n_probes, uint8_t* zs32 = nullptr, uint8_t* ys32 = nullptr /* the blob source: [n][32] each */);
     // k_blob_eval_at alone: n blobs and n points (32 big-endian bytes, reduced mod r) from the host -> ys32[n][32], bad[n]
     int test_blob_eval_at(int n, const uint8_t* const* blobs, const uint8_t* zs_be32, uint8_t* out_ys_be32, int32_t* out_bad);
+    // k_pairing_check and the host's checks on the same n pairs (compressed G1, n x 2 x 48 bytes) against key pair `key` (0: [tau^64]_2, -[1]_2;
+    // 1: [tau]_2, -[1]_2); flags: see include/c_eth_kzg_test_hooks.h.  The Miller values (may be null): n x 576 bytes each
+    int test_pairing_check_many(int key, uint64_t n, const uint8_t* pairs, int flags, int8_t* out_gpu, int8_t* out_host, uint8_t* out_miller_gpu,
+                                uint8_t* out_miller_host);
+    // out4: probes the last tapped many-verification checked on the GPU, all its probes; nanoseconds of the last test_pairing_check_many on
+    // the GPU (launch + verdict copy) and on the host threads
+    void test_search_stats(uint64_t* out4) const { for (int i = 0; i < 4; i++) out4[i] = test_search_stats_[i]; }
+    uint64_t test_search_stats_[4] = {0, 0, 0, 0};
     // the Reed-Solomon decoder of recovery on its own: rs_decode (verify.hip) with its tap set, behind the staging of recover_batch_to_coeffs
     // (flat_source = 0) or of recover_cells_and_kzg_proofs_device (1); outputs canonical big-endian on the host, each may be null
     int test_rs_decode(int R, const uint64_t* n_cells, const uint64_t* const* cell_indices, const uint8_t* const* const* cells, int flat_source,
@@ -612,6 +622,13 @@ private:
     Fr8 inv64_, n_inv8192_;
     std::shared_ptr<pairing::G2Prepared> g2_tau_, g2_neg_gen_;  // [tau^64]_2 and -[1]_2 (verifier.rs:88-90)
     std::shared_ptr<pairing::G2Prepared> g2_tau1_;             // [tau]_2 (EIP-4844 verification key)
+    // the same three keys' prepared lines and the Frobenius constants in HBM, for k_pairing_check (the many-verifications' search for
+    // wrong entries, vm_search.hpp): [tau^64]_2 | -[1]_2 | [tau]_2, 68 lines each, then the constants.  Null where a key is the point
+    // at infinity (a caller's degenerate setup): such a context checks every probe on the host
+    void* d_pairing_ = nullptr;
+    const void* d_pairing_key(int k) const { return (const uint8_t*)d_pairing_ + (size_t)k * 68 * 192; }
+    const void* d_pairing_frob() const { return d_pairing_key(3); }
+    int gpu_pairing_min_ = 0;  // smallest batch of probes whose pairings run on the GPU (ETH_KZG_AMD_GPU_PAIRING_MIN); 0: never
 
     // verify workspace: one device arena + one pinned host staging buffer, grown on demand (guarded by mu_)
     void* v_dev_ = nullptr;

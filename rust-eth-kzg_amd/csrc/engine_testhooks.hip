@@ -1,6 +1,8 @@
 // Stage-level test hooks of the engine (include/c_eth_kzg_test_hooks.h): single stages against the oracle.
 #include "engine_internal.hpp"
 #include "curve29.hpp"
+#include "vm_search.hpp"
+#include <chrono>
 
 #include <array>
 
@@ -527,6 +529,8 @@ int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& 
     const int rc = verify_cell_kzg_proof_batch_many(n_batches, in, ver.data(), st.data(), &tap);
     if (rc) return rc;
     if (tap.passes > 1) return ERR_INPUT;  // (cannot happen behind the checks above)
+    test_search_stats_[0] = (uint64_t)tap.device_probes;
+    test_search_stats_[1] = tap.probes.size() / 3;
     static_assert(sizeof(JacQ) == launch::SIZEOF_JACQ, "the tap holds JacQ words");
     auto compress2 = [](uint8_t* out96, const uint8_t* two) {  // a slot that still holds its poison comes out as 0xff bytes
         for (int j = 0; j < 2; j++) {
@@ -583,6 +587,8 @@ int Engine::test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in
     tap.pass_size = (int)forced_pass;
     const int rc = verify_kzg_proof_many(n, in, ver.data(), st.data(), &tap);
     if (rc) return rc;
+    test_search_stats_[0] = (uint64_t)tap.device_probes;
+    test_search_stats_[1] = tap.probes.size() / 4;
     auto compress2 = [](uint8_t* out96, const uint8_t* two) {  // a slot that still holds its poison comes out as 0xff bytes
         for (int j = 0; j < 2; j++) {
             JacQ s;
@@ -610,6 +616,68 @@ int Engine::test_verify_kzg_proof_many_sums(uint64_t n, const PointManyInput& in
     for (uint64_t q = 0; q < *n_probes && q < max_probes; q++) {
         for (int j = 0; j < 4; j++) probes4[4 * q + j] = tap.probes[4 * q + j];
         compress2(probe_sums96 + 96 * q, tap.probe_sums.data() + (size_t)2 * q * sizeof(JacQ));
+    }
+    return OK;
+}
+
+// k_pairing_check on its own, next to the host's checks of the same pairs.  The pairs are decompressed here, on the host (on the curve;
+// no subgroup test: the pairing of the test's points is what it is either way), and become JacQ as the passes' folds are.
+int Engine::test_pairing_check_many(int key, uint64_t n64, const uint8_t* pairs48, int flags, int8_t* out_gpu, int8_t* out_host, uint8_t* out_miller_gpu,
+                                    uint8_t* out_miller_host) {
+    if (!d_pairing_) return ERR_INPUT;  // (a setup with a key at infinity: no device route)
+    const int n = (int)n64;
+    std::vector<JacQ> pq((size_t)2 * n);
+    for (int i = 0; i < 2 * n; i++) {
+        G1Affine a;
+        if (g1_decompress(a, pairs48 + (size_t)i * 48) != 0) return ERR_G1;
+        G1Jac j = to_jac(a);
+        if ((flags & 1) && !is_inf(a)) {  // the same point with Z = i + 2
+            Fp z = zero<FpParams>();
+            z.v[0] = (uint32_t)i + 2;
+            z = to_mont(z);
+            const Fp z2 = sqr(z);
+            j.x = mul(a.x, z2); j.y = mul(a.y, mul(z2, z)); j.z = z;
+        }
+        pq[(size_t)i] = jacq_from_jac(j);
+    }
+    if (flags & 2) {
+        const size_t e = (size_t)((unsigned)flags >> 8);
+        if (e >= (size_t)n) return ERR_INPUT;
+        memset(&pq[2 * e + 1], 0xff, sizeof(JacQ));
+    }
+    const pairing::G2Prepared* const vk[2] = {key ? g2_tau1_.get() : g2_tau_.get(), g2_neg_gen_.get()};
+    const int T = vm::host_threads(knobs_);
+    std::call_once(vm_pool_once_, [&] { vm_pool_.reset(new HostPool(T > 1 ? T - 1 : 1, [d = dev_] { (void)hipSetDevice(d); })); });
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        hipStream_t st = stream_;
+        PoolBuf d_pairs(*this, pq.size() * sizeof(JacQ)), d_verd(*this, (size_t)n), d_mil(*this, out_miller_gpu ? (size_t)n * sizeof(pairing::Fp12) : 256);
+        HIPCK(hipMemcpyAsync(d_pairs.p, pq.data(), pq.size() * sizeof(JacQ), hipMemcpyHostToDevice, st));
+        HIPCK(hipMemsetAsync(d_verd.p, 0x7f, (size_t)n, st));  // what the kernel does not write shows
+        SYNC_CHECKED(st);
+        const auto t0 = std::chrono::steady_clock::now();
+        launch::pairing_check(d_pairs.p, d_pairing_key(key ? 2 : 0), d_pairing_key(1), d_pairing_frob(), (int8_t*)d_verd.p, n, st,
+                              out_miller_gpu ? d_mil.p : nullptr);
+        HIPCK(hipMemcpyAsync(out_gpu, d_verd.p, (size_t)n, hipMemcpyDeviceToHost, st));
+        SYNC_CHECKED(st);
+        const auto t1 = std::chrono::steady_clock::now();
+        if (out_miller_gpu) HIPCK(hipMemcpy(out_miller_gpu, d_mil.p, (size_t)n * sizeof(pairing::Fp12), hipMemcpyDeviceToHost));
+        parallel_for(n, T, vm_pool_.get(), [&](int i) { out_host[i] = (int8_t)vm::check_pair(&pq[2 * (size_t)i], vk); });
+        const auto t2 = std::chrono::steady_clock::now();
+        test_search_stats_[2] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
+        test_search_stats_[3] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(t2 - t1).count();
+        if (out_miller_host)
+            parallel_for(n, T, vm_pool_.get(), [&](int i) {
+                pairing::Fp12 f = pairing::one12();
+                if (!vm::poisoned(pq[2 * (size_t)i]) && !vm::poisoned(pq[2 * (size_t)i + 1]))
+                    f = pairing::fp12_mul(pairing::miller_loop(to_affine(jac_from_jacq(pq[2 * (size_t)i])), *vk[0]),
+                                          pairing::miller_loop(to_affine(jac_from_jacq(pq[2 * (size_t)i + 1])), *vk[1]));
+                memcpy(out_miller_host + (size_t)i * sizeof(f), &f, sizeof(f));
+            });
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
     }
     return OK;
 }

@@ -7,19 +7,17 @@
 #pragma once
 #include <cstdint>
 #include <vector>
-#include "curve.hpp"
+#include "pairing_tower.hpp"
 
 namespace kzg {
 namespace pairing {
 
-struct Fp2 { Fp c0, c1; };                 // c0 + c1 u, u^2 = -1
-struct Fp6 { Fp2 c0, c1, c2; };            // over Fp2, v^3 = 1 + u
-struct Fp12 { Fp6 c0, c1; };               // over Fp6, w^2 = v
+// Fp2 / Fp6 / Fp12, Line and the arithmetic: pairing_tower.hpp, which the device compiles too
 struct G2Affine { Fp2 x, y; bool inf; };
-struct Line { Fp2 a, b; };                 // l(P) * w^3 = a + (b * xP) v + yP (v w)
 struct G2Prepared { std::vector<Line> lines; bool inf = true; };
 
 void init();                                               // Frobenius constants (idempotent)
+const FrobConsts& frob_consts();                           // (after init) what k_pairing_check gets a copy of
 bool g2_decompress(G2Affine& out, const uint8_t in[96]);   // ZCash encoding, on-curve check only
 G2Affine g2_neg(const G2Affine& q);
 // A caller-supplied setup (trusted_setup.hpp): membership of the order-r subgroup by the psi-endomorphism test (infinity passes,

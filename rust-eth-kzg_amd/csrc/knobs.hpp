@@ -1,7 +1,7 @@
 // EVERY environment variable the library reads, in one place.  They are read ONCE per context (Knobs::from_env in the
 // constructor of the context's engine; the auxiliary engines a context creates copy its values): no getenv on any call path.
 // The reference gets by with one runtime knob (UsePrecomp::Yes{width}, crates/cryptography/bls12_381/src/fixed_base_msm.rs:41-49);
-// here eight are for the host application and the rest are hooks the parity tests use to force a schedule.
+// here nine are for the host application and the rest are hooks the parity tests use to force a schedule.
 //
 //   for the host application
 //   ETH_KZG_AMD_DEVICE=<n>          GPU ordinal of eth_kzg_das_context_new (default 0)
@@ -14,6 +14,9 @@
 //   ETH_KZG_AMD_HOST_THREADS=<n>    helper threads of the host-pointer paths (gather / scatter, hashing, pairings)
 //   ETH_KZG_AMD_SERIAL_LANES=<n>    engine lanes for concurrent recovery / commitment / EIP-4844 calls (default 4)
 //   ETH_KZG_AMD_TRACE=1             timings of context creation and of the verification steps on stderr
+//   ETH_KZG_AMD_GPU_PAIRING_MIN=<n> the "many" verifications' search for wrong entries: the smallest batch of probes whose pairing checks
+//                                   run on the GPU (k_pairing_check) instead of the host threads; 0: never.  Verdicts and statuses do not
+//                                   depend on it (default: vm_search.hpp, GPU_PAIRING_MIN_DEFAULT, from the measured crossover)
 //
 //   test hooks (tests/test_gpu_*.py force every schedule against the oracle)
 //   ETH_KZG_AMD_MSM_CHUNKS=0|4      0: the windowed MSM kernel at every batch size, 4: four chunks per MSM
@@ -51,6 +54,7 @@ struct Knobs {
     bool vm_search = true, vm_fold = true, verify_combine = true, msm_split = true;
     std::string fault;  // ETH_KZG_AMD_FAULT (a copy: the environment may change under a long-lived context)
     int device_batch_max = 0;
+    int gpu_pairing_min = -1;  // -1: the default
 
     static Knobs from_env() {
         Knobs k;
@@ -92,6 +96,7 @@ struct Knobs {
         num("ETH_KZG_AMD_FUSED_SCALARS", 0, 1, k.fused_scalars);
         if (const char* s = getenv("ETH_KZG_AMD_FAULT")) k.fault = s;
         num("ETH_KZG_AMD_DEVICE_BATCH_MAX", 64, 1 << 20, k.device_batch_max);
+        num("ETH_KZG_AMD_GPU_PAIRING_MIN", 0, 1 << 24, k.gpu_pairing_min);
         return k;
     }
 };

@@ -194,6 +194,12 @@ void vm_fold(const void* sums, const uint32_t* rho, void* prod, void* out2, int 
 // out[r][2] = the weighted pairs summed over problems ranges[r][0] .. ranges[r][1] - 1 (prod as vm_fold left it)
 void vm_fold_ranges(const void* prod, const int* ranges /*[n_ranges][2], device*/, void* out /*[n_ranges][2] JacQ*/, int n_ranges, hipStream_t st);
 
+// k_pairing.hip: verdict[i] = e(pairs[i][0], key0) e(pairs[i][1], key1) == 1 ? 1 : 0, or -1 where a pair still holds the 0xff poison of
+// the result slots; pairs [n][2] JacQ, key0 / key1 68 prepared lines each (192 B), frob the three Frobenius constants (288 B), all in
+// HBM.  miller (test hook; null in the product): [n] x 576 B, the Miller values before the final exponentiation
+void pairing_check(const void* pairs, const void* key0, const void* key1, const void* frob, int8_t* verdict, int n, hipStream_t st,
+                   void* miller = nullptr);
+
 // k_point_many.hip: many verify_kzg_proof items in one pass (point_many.hip), one lane per scalar multiplication
 // bodies[n][176] = "RCKZGPROOFLEAF_1" | commitment | z | y | proof per item, for sha256_many; all five arrays 4-byte aligned
 void pm_leaf_bodies(const uint8_t* commitments, const uint8_t* zs, const uint8_t* ys, const uint8_t* proofs, uint8_t* bodies, int n, hipStream_t st);

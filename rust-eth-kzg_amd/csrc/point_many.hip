@@ -37,7 +37,9 @@ struct PointPassLayout {
     const int n;
     const int blobs;  // 0: the items bring z and y; 1: blobs staged through the slab (host form); 2: blobs read where they lie (device form)
     const int n_l1 = (n + FOLD_SPAN - 1) / FOLD_SPAN;  // first-level ranges of the full-range fold
-    const int max_ranges = std::min(n, 2048);          // probes per level of the search
+    // probes per batch of the search: a pass's worth, so that "every live suspect on its own" is ONE launch of k_pairing_check (a wave of
+    // it takes as long as a thousand; 5.5 MB of range sums on either side at 16384)
+    const int max_ranges = n;
     static constexpr size_t JACQ = launch::SIZEOF_JACQ;
     Carve d;  // (members are initialised in the order they stand here)
     // the blob source's own arrays take no room otherwise (Carve: an array of no bytes): the other sources' layout is what it was
@@ -47,7 +49,7 @@ struct PointPassLayout {
                  in_bytes = d.end, off_frng = d.take((size_t)(n_l1 + 1) * 8), off_rho = d.take((size_t)n * 16), in2_bytes = d.end;
     Carve h = d;  // pinned read-backs behind the inputs
     const size_t poff_st = h.take((size_t)n * 4), poff_fold = h.take(2 * JACQ), poff_rng = h.take((size_t)max_ranges * 8),
-                 poff_rsum = h.take((size_t)2 * max_ranges * JACQ), poff_leaf = h.take((size_t)n * 32), pin_bytes = h.end;
+                 poff_rsum = h.take((size_t)2 * max_ranges * JACQ), poff_leaf = h.take((size_t)n * 32), poff_verd = h.take((size_t)max_ranges), pin_bytes = h.end;
     // device only
     const size_t off_pts = d.take((size_t)2 * n * sizeof(G1Affine)), off_stp = d.take((size_t)2 * n * 4), off_zbad = d.take((size_t)n * 4),
                  off_ybad = d.take((size_t)n * 4), off_st = d.take((size_t)n * 4), off_zm = d.take((size_t)n * sizeof(Fr)),
@@ -55,6 +57,7 @@ struct PointPassLayout {
                  off_l1 = d.take((size_t)2 * n_l1 * JACQ), off_fold = d.take(2 * JACQ), off_rng = d.take((size_t)max_ranges * 8),
                  off_rsum = d.take((size_t)2 * max_ranges * JACQ), off_bodies = d.take((size_t)n * PointProofTranscript::LEAF_BYTES),
                  off_leaf = d.take((size_t)n * 32), off_dig = d.take(blobs == 2 ? (size_t)n * 32 : 0), off_bbad = d.take(blobs ? (size_t)n * 4 : 0),
+                 off_verd = d.take((size_t)max_ranges),  // the verdict bytes of k_pairing_check
                  dev_bytes = d.end;
     explicit PointPassLayout(int n_, int blobs_) : n(n_), blobs(blobs_) {}
 };
@@ -252,7 +255,9 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
             S.n = n; S.max_ranges = L.max_ranges; S.T = T; S.pool = pool; S.hb = hb;
             S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.off_rng = L.off_rng; S.off_pairs = L.off_pairs; S.off_rsum = L.off_rsum;
             S.vk = vk; S.live = live.data(); S.verified = ver; S.device_fault = &device_fault;
-            if (tap) { S.tap_probes = &probes; S.tap_probe_sums = &tap->probe_sums; }
+            if (gpu_pairing_min_ > 0) S.gpu = {d_pairing_key(2), d_pairing_key(1), d_pairing_frob(), gpu_pairing_min_};
+            S.off_verd = L.off_verd; S.poff_verd = L.poff_verd;
+            if (tap) { S.tap_probes = &probes; S.tap_probe_sums = &tap->probe_sums; S.tap_device_probes = &tap->device_probes; }
             vm::search_wrong_proofs(S, n_live, db, st);
             if (device_fault.load()) throw std::runtime_error("point verification pass left no result");
             for (size_t q = 0; tap && q + 2 < probes.size(); q += 3) {

@@ -9,6 +9,7 @@
 #include "engine_internal.hpp"
 #include "curve29.hpp"
 #include "host_pairing.hpp"
+#include "vm_search.hpp"
 
 namespace kzg {
 
@@ -41,6 +42,22 @@ void Engine::init_verifier() {
         if (pairing::product_is_one(P, minus, 2) || pairing::product_is_one(P, plus, 2))
             throw std::runtime_error("degenerate trusted setup: tau is a root of unity of the evaluation domain (tau^8192 = 1), so a derived "
                                      "verification base [tau^64 - h^64]_2 is the point at infinity");
+    }
+    // the prepared keys and the Frobenius constants in HBM: from the SAME objects the host's checks use (vm_search.hpp)
+    {
+        const pairing::G2Prepared* keys[3] = {g2_tau_.get(), g2_neg_gen_.get(), g2_tau1_.get()};
+        bool all = true;
+        for (const pairing::G2Prepared* k : keys) all = all && !k->inf && (int)k->lines.size() == pairing::MILLER_LINES;
+        gpu_pairing_min_ = knobs_.gpu_pairing_min >= 0 ? knobs_.gpu_pairing_min : vm::GPU_PAIRING_MIN_DEFAULT;
+        if (!all) gpu_pairing_min_ = 0;
+        if (all) {
+            constexpr size_t KEY = (size_t)pairing::MILLER_LINES * sizeof(pairing::Line);
+            std::vector<uint8_t> img(3 * KEY + sizeof(pairing::FrobConsts));
+            for (int k = 0; k < 3; k++) memcpy(img.data() + (size_t)k * KEY, keys[k]->lines.data(), KEY);
+            memcpy(img.data() + 3 * KEY, &pairing::frob_consts(), sizeof(pairing::FrobConsts));
+            HIPCK(hipMalloc(&d_pairing_, img.size()));
+            HIPCK(hipMemcpy(d_pairing_, img.data(), img.size(), hipMemcpyHostToDevice));
+        }
     }
     // coset shift tables 7^i, 7^-i
     std::vector<Fr> c(N_EXT), ci(N_EXT);

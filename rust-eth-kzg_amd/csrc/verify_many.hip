@@ -55,6 +55,7 @@ struct PassLayout {
     Carve h = d;  // pinned read-backs behind the inputs
     const size_t poff_st = h.take((size_t)(n + m + Bc) * 4), poff_out = h.take((size_t)2 * Bc * JACQ), poff_fold = h.take((size_t)2 * JACQ),
                  poff_rng = h.take((size_t)max_ranges * 8), poff_rsum = h.take((size_t)2 * max_ranges * JACQ), poff_leaf = h.take(leaf ? (size_t)n * 32 : 0),
+                 poff_verd = h.take((size_t)max_ranges),  // the verdict bytes of k_pairing_check
                  pin_bytes = h.end;
     // device only
     const size_t off_pts = d.take((size_t)(n + m) * sizeof(G1Affine)), off_evals = d.take((size_t)n * CELL_LEN * sizeof(Fr)),
@@ -65,7 +66,7 @@ struct PassLayout {
                  off_icm = d.take((size_t)Bc * JACQ), off_prod = d.take((size_t)(2 * n + m + (small ? 64 * Bc : 0)) * JACQ),
                  off_out = d.take((size_t)2 * Bc * JACQ), off_fprod = d.take((size_t)2 * Bc * JACQ), off_fold = d.take((size_t)2 * JACQ),
                  off_rng = d.take((size_t)max_ranges * 8), off_rsum = d.take((size_t)2 * max_ranges * JACQ),
-                 off_leaf = d.take(leaf ? (size_t)n * 32 : 0), dev_bytes = d.end;
+                 off_leaf = d.take(leaf ? (size_t)n * 32 : 0), off_verd = d.take((size_t)max_ranges), dev_bytes = d.end;
     PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_) {}
 };
 
@@ -80,6 +81,7 @@ struct PassHost {
     int T;
     HostPool* pool;
     const pairing::G2Prepared* vk[2];        // [tau^64]_2, -[1]_2
+    vm::DevicePairing gpu;                   // the same keys for k_pairing_check (the search's larger batches of probes)
     int* verified;                           // verified[i] belongs to problem i of the pass
     std::atomic<int> device_fault{0};
     std::vector<int> cell_start, row_start;  // first cell / first unique commitment of each problem
@@ -193,7 +195,8 @@ void search_wrong_proofs(PassHost& V, int n_live, uint8_t* db, hipStream_t st) {
     S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.off_rng = L.off_rng; S.off_pairs = L.off_fprod; S.off_rsum = L.off_rsum;
     S.vk = V.vk; S.live = V.live.data(); S.verified = V.verified; S.device_fault = &V.device_fault;
     S.check_single = [&V](int i) { V.check_single(i); };
-    if (V.tap) { S.tap_probes = &V.tap->probes; S.tap_probe_sums = &V.tap->probe_sums; }
+    S.gpu = V.gpu; S.off_verd = L.off_verd; S.poff_verd = L.poff_verd;
+    if (V.tap) { S.tap_probes = &V.tap->probes; S.tap_probe_sums = &V.tap->probe_sums; S.tap_device_probes = &V.tap->device_probes; }
     vm::search_wrong_proofs(S, n_live, db, st);
     if (V.tap && !V.tap->probes.empty()) V.tap->searched = 1;
 }
@@ -343,7 +346,8 @@ int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyMan
             grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
             grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
             uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
-            PassHost H{L, pr.data() + b0, in.from((uint64_t)b0), mirror_i, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, verified + b0};
+            PassHost H{L, pr.data() + b0, in.from((uint64_t)b0), mirror_i, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, {}, verified + b0};
+            if (gpu_pairing_min_ > 0) H.gpu = {d_pairing_key(0), d_pairing_key(1), d_pairing_frob(), gpu_pairing_min_};
             H.tap = tap;
             H.stage();
             lap("stage (host)");
