@@ -16,6 +16,24 @@ int eth_kzg_amd_test_g1_decompress(const DASContext *ctx, const uint8_t *in, int
 int eth_kzg_amd_test_field_mul(const DASContext *ctx, const uint8_t *a, const uint8_t *b, uint8_t *out, int n,
                                int is_fp);
 
+/* The decoded coordinates themselves (eth_kzg_amd_test_g1_decompress re-compresses on the device with the decoder's own sign predicate,
+ * so a predicate that is wrong both ways still returns the input bytes).  in: n0 + n1 compressed points (host), two segments as the
+ * verifiers pass proofs and commitments (n0 >= 1, n1 >= 0; forms 0 and 1 take one segment: n1 = 0).  The status words start at the
+ * verifiers' 0xff poison.  Exactly the product's launch calls, nothing new on the device; with N = n0 + n1 and M = the limit of the
+ * four-lanes-per-point kernels (launch::coop_points_max: 8192, ETH_KZG_AMD_COOP_POINTS moves it) the kernels of a form are:
+ *   0  launch::g1_decompress, check 0: k_g1_decompress (one lane per point, no subgroup test) at every N
+ *   1  launch::g1_decompress, check 1: k_g1_decompress_coop for N <= M, k_g1_decompress above
+ *   2  launch::g1_decompress2:         k_g1_decompress_coop for N <= M, k_g1_decompress above
+ *   3  launch::g1_decode2, then launch::g1_subgroup2: k_g1_subgroup_coop for N <= M, k_g1_subgroup above
+ *   4  launch::g1_decode2, then launch::pip_shift_prepare_and_subgroup over all N points with the workspace of
+ *      eth_kzg_amd_test_verify_msm: its quad branch for 2 N <= M (it counts the shifted points and the tested ones), its one-lane branch above
+ * status[n0 + n1]: 0 good, 1 bad encoding or off the curve, 2 outside the subgroup (form 0: never 2).
+ * out_xy[n0 + n1][96]: the affine x | y the point array holds behind the launches, canonical big-endian; 96 zero bytes for the identity.
+ * The decoders (forms 0 .. 2, and the decode of 3 and 4) write the identity over a point they refuse; the subgroup-only kernels of forms 3
+ * and 4 write the status word alone, so a point they refuse with 2 keeps its decoded coordinates.  A slot no kernel wrote reads 0xff.
+ * Synchronous; returns 0, or the library's status codes (counts or form out of range: 3). */
+int eth_kzg_amd_test_g1_decode(const DASContext *ctx, int form, const uint8_t *in, int n0, int n1, int32_t *status, uint8_t *out_xy);
+
 /* One stated schedule of the fixed-base MSM (csrc/k_msm_glv.inc) on either window table.  table_kind: 0 = the FK20 table (128 groups of 64
  * bases), 1 = the commitment table (64 groups; the output is then the 64 group sums of a slice, before the commitment's fold).  mode: -1 =
  * what the engine picks for n_slices (launch_msm_range; its two-launch overflow form included), 0 = a block per MSM (flat), 1 = a lane per

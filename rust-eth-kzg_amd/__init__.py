@@ -90,7 +90,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_verify_many_sums_ex", "eth_kzg_amd_test_verify_many_sums_device",
     "eth_kzg_amd_test_verify_kzg_proof_many_sums",
     "eth_kzg_amd_test_blob_eval_at", "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums",
-    "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats",
+    "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats", "eth_kzg_amd_test_g1_decode",
 ]
 
 _lib = None
@@ -207,6 +207,7 @@ def load_library():
         "eth_kzg_amd_test_fixed_msm": [P, U8P, C.c_int, P],
         "eth_kzg_amd_test_fixed_msm_ex": [P, C.c_int, C.c_int, C.c_int, P, C.c_int, P, P],
         "eth_kzg_amd_test_g1_decompress": [P, U8P, C.c_int, C.c_int, P, P],
+        "eth_kzg_amd_test_g1_decode": [P, C.c_int, U8P, C.c_int, C.c_int, P, P],
         "eth_kzg_amd_test_field_mul": [P, U8P, U8P, P, C.c_int, C.c_int],
         "eth_kzg_amd_test_op_info": [C.c_int, P, P, P, C.POINTER(C.c_char_p)],
         "eth_kzg_amd_test_op": [P, C.c_int, C.c_int, P, P, C.c_int],

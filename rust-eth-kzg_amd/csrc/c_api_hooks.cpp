@@ -57,6 +57,10 @@ int eth_kzg_amd_test_g1_decompress(const DASContext* ctx, const uint8_t* in, int
                                    uint8_t* out) {
     return eng(ctx)->test_g1_decompress(in, n, subgroup_check, status, out);
 }
+int eth_kzg_amd_test_g1_decode(const DASContext* ctx, int form, const uint8_t* in, int n0, int n1, int32_t* status, uint8_t* out_xy) {
+    if (!in || !status || !out_xy) return kzg::ERR_INPUT;
+    return eng(ctx)->test_g1_decode(form, in, n0, n1, status, out_xy);
+}
 int eth_kzg_amd_test_field_mul(const DASContext* ctx, const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp) {
     return eng(ctx)->test_field_mul(a, b, out, n, is_fp);
 }

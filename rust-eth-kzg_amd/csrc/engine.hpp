@@ -349,6 +349,8 @@ public:
     int test_linmap_program(int program, uint32_t* words, uint64_t max_words, uint64_t* n_words, int32_t* launches3, uint64_t max_launches,
                             uint64_t* n_launches, int32_t* n_slots, uint8_t* consts_be, uint64_t max_consts, uint64_t* n_consts);
     int test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int* h_status, uint8_t* out_recompressed);
+    // the decoded affine coordinates behind each decode / subgroup launch call (form 0 .. 4: engine_testhooks.hip), segments [n0 | n1]
+    int test_g1_decode(int form, const uint8_t* in, int n0, int n1, int32_t* h_status, uint8_t* out_xy);
     int test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp);
     int test_op(int op, int n, const int32_t* in, int32_t* out);
     // launch::sha256_many on its own: prefix on the host, every other buffer in HBM

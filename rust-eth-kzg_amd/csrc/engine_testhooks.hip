@@ -298,6 +298,74 @@ int Engine::test_g1_decompress(const uint8_t* in, int n, int subgroup_check, int
     return OK;
 }
 
+// The decoded coordinates themselves, through each of the product's decode / subgroup launch calls (test_g1_decompress re-compresses
+// on the device with the decoder's own sign predicate, which hides an error that is wrong both ways).  Two segments [n0 | n1] as a
+// verification passes its proofs and commitments; the status words start at the arena's 0xff poison.  Which kernel a form runs is
+// the launcher's rule, with N = n0 + n1 and M = launch::coop_points_max():
+//   0  g1_decompress, check 0      k_g1_decompress (one lane per point) at every N: no subgroup test
+//   1  g1_decompress, check 1      k_g1_decompress_coop for N <= M, k_g1_decompress above (one segment: n1 must be 0)
+//   2  g1_decompress2              k_g1_decompress_coop for N <= M, k_g1_decompress above
+//   3  g1_decode2 + g1_subgroup2   k_g1_decompress (check 0), then k_g1_subgroup_coop for N <= M, k_g1_subgroup above
+//   4  g1_decode2 + pip_shift_prepare_and_subgroup over all N points: the quad branch (k_pip_shift_subgroup_coop) for 2 N <= M, the
+//      one-lane branch (k_pip_shift_subgroup) above
+// out_xy: what the point array holds behind the launches, x | y canonical big-endian; the identity (0, 0) is 96 zero bytes.  The
+// decoders write the identity over a point they refuse; the subgroup-only kernels of forms 3 and 4 read the points and write the status
+// word alone, so there a point refused with 2 keeps its decoded coordinates.
+int Engine::test_g1_decode(int form, const uint8_t* in, int n0, int n1, int32_t* h_status, uint8_t* out_xy) {
+    if (form < 0 || form > 4 || n0 < 1 || n1 < 0 || (form <= 1 && n1 != 0) || (long)n0 + n1 > (1 << 20)) return ERR_INPUT;
+    const int n = n0 + n1;
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    struct DevBuf {  // (freed on every way out)
+        void* p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } d_in, d_pts, d_st, d_ws;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        HIPCK(hipMalloc(&d_in.p, (size_t)n * 48));
+        HIPCK(hipMalloc(&d_pts.p, (size_t)n * sizeof(G1Affine)));
+        HIPCK(hipMalloc(&d_st.p, (size_t)n * sizeof(int)));
+        if (form == 4) HIPCK(hipMalloc(&d_ws.p, launch::pip_shift_workspace_bytes(n)));
+        hipStream_t st = stream_;
+        HIPCK(hipMemcpyAsync(d_in.p, in, (size_t)n * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemsetAsync(d_st.p, 0xff, (size_t)n * sizeof(int), st));
+        HIPCK(hipMemsetAsync(d_pts.p, 0xff, (size_t)n * sizeof(G1Affine), st));
+        const uint8_t* in0 = (const uint8_t*)d_in.p;
+        G1Affine* p0 = (G1Affine*)d_pts.p;
+        int* st0 = (int*)d_st.p;
+        if (form <= 1) launch::g1_decompress(in0, p0, st0, n, form, beta_, st);
+        else if (form == 2) launch::g1_decompress2(in0, p0, st0, n0, in0 + (size_t)n0 * 48, p0 + n0, st0 + n0, n1, beta_, st);
+        else {
+            launch::g1_decode2(in0, p0, st0, n0, in0 + (size_t)n0 * 48, p0 + n0, st0 + n0, n1, beta_, st);
+            if (form == 3) launch::g1_subgroup2(p0, st0, n0, p0 + n0, st0 + n0, n1, beta_, st);
+            else launch::pip_shift_prepare_and_subgroup(p0, n, n, d_ws.p, p0, st0, n0, p0 + n0, st0 + n0, n1, beta_, st);
+        }
+        HIPCK(hipGetLastError());
+        std::vector<G1Affine> pts(n);
+        HIPCK(hipMemcpyAsync(h_status, d_st.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(pts.data(), d_pts.p, (size_t)n * sizeof(G1Affine), hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        for (int i = 0; i < n; i++) {
+            for (int c = 0; c < 2; c++) {
+                const Fp& m = c ? pts[i].y : pts[i].x;
+                uint8_t* o = out_xy + (size_t)i * 96 + 48 * c;
+                if (geq_mod<FpParams>(m.v)) {  // not a reduced coordinate (the 0xff the array started at): nothing was written
+                    memset(o, 0xff, 48);
+                    continue;
+                }
+                const Fp v = from_mont(m);
+                for (int k = 0; k < 12; k++) {
+                    const uint32_t w = v.v[11 - k];
+                    o[4 * k] = (uint8_t)(w >> 24); o[4 * k + 1] = (uint8_t)(w >> 16); o[4 * k + 2] = (uint8_t)(w >> 8); o[4 * k + 3] = (uint8_t)w;
+                }
+            }
+        }
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 int Engine::test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp) {
     std::lock_guard<std::recursive_mutex> lk(mu_);
     try {

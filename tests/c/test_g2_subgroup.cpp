@@ -4,8 +4,9 @@
 //   curve points over small abscissas x = c + u, which lie in E'(Fp2) but (the cofactor is ~2^508) not in the subgroup, fail both;
 //   the point at infinity passes (the reference's checked parser accepts it);
 //   the sum of 128-bit multiples (g2_lincomb128, the structure check's G2 side) equals the sum of the single multiples.
-// argv[1]: rust-eth-kzg_amd/data/trusted_setup_4096.bin; argv[2] (optional): 96 bytes of a compressed point that must decode to a
-// curve point and FAIL the subgroup test (the point tests/setup_material.py constructs in Python).
+// argv[1]: rust-eth-kzg_amd/data/trusted_setup_4096.bin; argv[2] (optional): a file of any multiple of 96 bytes, compressed points that
+// must each decode to a curve point and FAIL both tests (the point tests/setup_material.py constructs in Python, and the points of
+// small order and [k][1]_2 + small order of tests/small_order.py, which psi(Q) == [x]Q has to tell from the subgroup).
 #include "host_pairing.cpp"
 #include <cstdio>
 #include <cstring>
@@ -57,13 +58,21 @@ int main(int argc, char** argv) {
     if (off_subgroup < 6) { printf("found only %d curve points\n", off_subgroup); bad++; }
     if (argc > 2) {
         FILE* f = fopen(argv[2], "rb");
-        uint8_t b[96];
-        G2Affine q;
-        if (!f || fread(b, 1, 96, f) != 96) { printf("cannot read %s\n", argv[2]); bad++; }
-        else if (!g2_decompress(q, b)) { printf("the constructed point does not decode to a curve point\n"); bad++; }
-        else if (g2_in_subgroup(q) || g2_killed_by_r(q)) { printf("the constructed point passes a subgroup test\n"); bad++; }
-        else off_subgroup++;
-        if (f) fclose(f);
+        std::vector<uint8_t> b;
+        if (f) {
+            uint8_t buf[4096];
+            size_t n;
+            while ((n = fread(buf, 1, sizeof buf, f)) > 0) b.insert(b.end(), buf, buf + n);
+            fclose(f);
+        }
+        if (!f || b.empty() || b.size() % 96) { printf("cannot read %s as 96-byte points\n", argv[2]); bad++; }
+        for (size_t i = 0; f && i + 96 <= b.size() && b.size() % 96 == 0; i += 96) {
+            G2Affine q;
+            if (!g2_decompress(q, b.data() + i)) { printf("constructed point %zu does not decode to a curve point\n", i / 96); bad++; continue; }
+            const bool fast = g2_in_subgroup(q), slow = g2_killed_by_r(q);
+            if (fast || slow) { printf("constructed point %zu: psi test %d, [r]Q test %d\n", i / 96, fast, slow); bad++; }
+            else off_subgroup++;
+        }
     }
     {
         const G2Affine inf = {Fp2{zero<FpParams>(), zero<FpParams>()}, Fp2{zero<FpParams>(), zero<FpParams>()}, true};

@@ -79,6 +79,11 @@ def test_bad_g2_points_are_rejected_on_the_host():
     bad = g2[:96 * 37] + off + g2[96 * 38:]
     with pytest.raises(kzg.KzgError, match=r"InvalidSetup: g2_monomial\[37\] is not in the prime-order subgroup"):
         kzg.DASContext.from_trusted_setup(g1, bad, use_precomp=False, table_budget_gb=3)
+    # [tau^21]_2 plus a point of order 13 (tests/small_order.py): on the curve, and psi(Q) == [x]Q has to tell it from the subgroup
+    import small_order
+    plus13 = sm.g2_compress(sm.g2_add(small_order.g2_decode(g2[96 * 21:96 * 22]), small_order.g2_small_order_points()[13]))
+    with pytest.raises(kzg.KzgError, match=r"InvalidSetup: g2_monomial\[21\] is not in the prime-order subgroup"):
+        kzg.DASContext.from_trusted_setup(g1, g2[:96 * 21] + plus13 + g2[96 * 22:], use_precomp=False, table_budget_gb=3)
     junk = g2[:96 * 5] + bytes([g2[96 * 5] & 0x7f]) + g2[96 * 5 + 1:]  # compression flag cleared
     with pytest.raises(kzg.KzgError, match=r"g2_monomial\[5\] is not the encoding of a curve point"):
         kzg.DASContext.from_trusted_setup(g1, junk, use_precomp=False, table_budget_gb=3)
@@ -144,7 +149,17 @@ def test_host_g2_subgroup_test_against_the_definition(tmp_path):
     subprocess.check_call([hipcc, "-O2", "-std=c++17", "-x", "hip", "--cuda-host-only", "-I", CSRC,
                            os.path.join(ROOT, "tests", "c", "test_g2_subgroup.cpp"), "-o", exe])
     off = tmp_path / "off_subgroup.bin"
-    off.write_bytes(sm.g2_compress(sm.g2_off_subgroup_point()))
+    import small_order
+    planned = small_order.g2_encodings()  # points of order 13, 23, 2713 and [k][1]_2 + each of them
+    assert len(planned) == 96 * small_order.N_G2_POINTS
+    off.write_bytes(sm.g2_compress(sm.g2_off_subgroup_point()) + planned)
     out = subprocess.run([exe, sm.MAINNET_BIN, str(off)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr
-    assert "7 off it, 0 mismatches" in out.stdout, out.stdout
+    assert "%d off it, 0 mismatches" % (7 + small_order.N_G2_POINTS) in out.stdout, out.stdout
+    # the single-point use stays valid
+    off.write_bytes(sm.g2_compress(sm.g2_off_subgroup_point()))
+    out = subprocess.run([exe, sm.MAINNET_BIN, str(off)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "7 off it, 0 mismatches" in out.stdout, out.stdout + out.stderr
+    off.write_bytes(planned[:95])  # and a file that is no multiple of 96 bytes is an error, not an empty list
+    out = subprocess.run([exe, sm.MAINNET_BIN, str(off)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 1 and "cannot read" in out.stdout, out.stdout + out.stderr

@@ -263,7 +263,14 @@ def test_bad_setups_are_rejected_without_abort_or_leak(custom_points, tmp_path):
     inf1 = bytes([0xc0]) + bytes(47)
     mat = tmp_path / "material"
     mat.mkdir()
-    files = {"g1": g1, "g2": g2, "other_g2": other_g2, "tau1_g1": tau1_g1, "tau1_g2": tau1_g2, "off1": off1, "off2": off2, "inf1": inf1}
+    # g1_monomial[513] plus a point of order 11 (tests/small_order.py): what an attacker sends, where off1 is a hash-made curve point
+    import small_order
+    st, p513 = small_order.decode(g1[48 * 513:48 * 514])
+    assert st == 0
+    plus11 = small_order.encode(small_order.d.g_add(p513, small_order.small_order_points()[11]))
+    assert oracle_lib.g1_validate(plus11, False) == 0 and oracle_lib.g1_validate(plus11, True) != 0
+    files = {"g1": g1, "g2": g2, "other_g2": other_g2, "tau1_g1": tau1_g1, "tau1_g2": tau1_g2, "off1": off1, "off2": off2, "inf1": inf1,
+             "plus11": plus11}
     for k, v in files.items():
         (mat / k).write_bytes(v)
     code = (
@@ -288,6 +295,7 @@ def test_bad_setups_are_rejected_without_abort_or_leak(custom_points, tmp_path):
         "    for i in (0, 2077, 4095):\n"
         "        rejected(r'g1_monomial\\[%%d\\] is not in the prime-order subgroup' %% i, sw(g1, 48, i, M['off1']), g2)\n"
         "    rejected(r'g1_monomial\\[1\\] is not in the prime-order subgroup', sw(g1, 48, 1, M['off1']), g2)\n"
+        "    rejected(r'g1_monomial\\[513\\] is not in the prime-order subgroup', sw(g1, 48, 513, M['plus11']), g2)\n"
         "    rejected(r'g1_monomial\\[9\\] is not the encoding', sw(g1, 48, 9, bytes([g1[48 * 9] & 0x7f]) + g1[48 * 9 + 1:48 * 10]), g2)\n"
         "    rejected(r'g1_monomial\\[9\\] is not the encoding', sw(g1, 48, 9, bytes([0xe0]) + bytes(47)), g2)\n"
         "    rejected(r'g1_monomial\\[300\\] is the point at infinity', sw(g1, 48, 300, M['inf1']), g2)\n"

@@ -111,6 +111,12 @@ def test_g1_decompress_matches_oracle(ctx):
         cand[0] |= 0x80 | (0x20 if k & 1 else 0)
         if oracle_lib.g1_validate(bytes(cand), False) == 0:
             bad.append(bytes(cand))
+    # the planned points of tests/small_order.py: small order, subgroup point + small order, boundary y, encoding edges -- their status
+    # comes from exact integers, and every mode must give exactly it
+    import small_order
+    planned = small_order.g1_cases()
+    first_planned = len(pts) + len(bad)
+    bad += [c.enc for c in planned]
     allp = pts + bad
     n = len(allp)
     # modes: 0 = no subgroup test, 1 = production (unsaturated field, endomorphism test), 2 = definitional [r]P == O and
@@ -124,6 +130,8 @@ def test_g1_decompress_matches_oracle(ctx):
             assert (st[i] != 0) == (exp != 0), (i, p.hex(), st[i], exp)
             if exp == 0:
                 assert out.raw[48 * i:48 * i + 48] == p  # decompress -> compress round trip is the identity
+        for j, c in enumerate(planned):
+            assert st[first_planned + j] == (c.status1 if check else c.status0), (check, c.name, st[first_planned + j])
     # Up to 8192 points the production test runs with FOUR lanes per point that share its doublings (g1_coop.hpp), above with
     # one lane per point: the list above took the first form, the same points repeated past the limit take the second
     reps = 8192 // n + 2
