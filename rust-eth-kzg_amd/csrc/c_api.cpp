@@ -17,7 +17,6 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <thread>
 #include <vector>
 
 namespace {
@@ -95,6 +94,62 @@ CResult slices_result(const DASContext* ctx, const std::pair<int, std::string>& 
     if (ctx->engines.size() == 1) return err(r.second);
     return err("device " + std::to_string(ctx->engines[(size_t)r.first]->device()) + ": " + r.second);
 }
+// how a call that returns a Status ends; a verification also hands out its verdict when the status is OK
+CResult finish(kzg::Engine* e, int st) {
+    if (st == kzg::ERR_DEVICE) return device_err(e);
+    return st ? err(status_text(st)) : ok();
+}
+CResult finish_verdict(kzg::Engine* e, int st, int ver, bool* verified) {
+    if (!st) *verified = ver != 0;
+    return finish(e, st);
+}
+// the verdicts and statuses of a many-verification into the caller's arrays
+CResult verdicts_out(uint64_t n, const int* ver, const int* st, bool* verified, int32_t* status) {
+    for (uint64_t i = 0; i < n; i++) {
+        verified[i] = st[i] == 0 && ver[i] != 0;
+        if (status) status[i] = st[i];
+    }
+    return ok();
+}
+std::string many_failure(kzg::Engine* e, int rc) { return rc == kzg::ERR_DEVICE ? device_text(e) : std::string(); }
+std::string batch_failure(kzg::Engine* e, int rc) { return rc ? device_text(e) : std::string(); }
+// A host-pointer batch of n items over the device list.  The count is checked before the context is looked at, args_ok() (null
+// pointers) behind the empty call.  run(engine, lo, hi, st, ver) runs items [lo, hi) on a device's engine, fills their entries of
+// the status (and verdict) words and returns "" or the slice's error text.  `verified` set: a many-verification, whose verdicts go out
+// with the statuses; else a prover batch, whose statuses go out alone.
+template <class ArgsOk, class Run>
+CResult sliced_call(const DASContext* ctx, uint64_t n, uint64_t max_n, bool* verified, int32_t* status, ArgsOk args_ok, Run run) {
+    if (n > max_n) return err("InvalidInput");
+    live(ctx);
+    if (n == 0) return ok();
+    if (!args_ok()) return err("InvalidInput");
+    try {
+        std::vector<int> st(n), ver(verified ? n : 0);
+        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
+            return run(ctx->engines[(size_t)d], lo, hi, st.data(), ver.data());
+        });
+        if (r.first >= 0) return slices_result(ctx, r);
+        if (verified) return verdicts_out(n, ver.data(), st.data(), verified, status);
+        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
+        return ok();
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+// verify_cell_kzg_proof_batch_many on pointer lists, with either challenge: by PROBLEM over the device list -- problems are independent
+// (each has its own Fiat-Shamir transcript); own lock, stream and scratch inside (verify_many.hip): no lane needed
+CResult cell_many(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths, const uint8_t* const* const* commitments,
+                  const uint64_t* cell_indices_lengths, const uint64_t* const* cell_indices, const uint64_t* cells_lengths,
+                  const uint8_t* const* const* cells, const uint64_t* proofs_lengths, const uint8_t* const* const* proofs, bool leaf,
+                  bool* verified, int32_t* status) {
+    kzg::VerifyManyInput in;
+    in.n_commitments = commitments_lengths; in.n_indices = cell_indices_lengths; in.n_cells = cells_lengths; in.n_proofs = proofs_lengths;
+    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
+    in.leaf = leaf;
+    return sliced_call(ctx, n_batches, MAX_BATCH, verified, status, [] { return true; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+        return many_failure(e, e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver + lo, st + lo));
+    });
+}
 
 void free_ctx(DASContext* c) {
     if (!c) return;
@@ -112,36 +167,26 @@ DASContext* try_make_ctx(bool use_precomp, const std::vector<int>& devices, doub
         const size_t D = devices.size();
         c->engines.assign(D, nullptr);
         std::vector<std::string> errs(D);
-        auto make = [&](size_t d) {
-            try {
-                c->engines[d] = new kzg::Engine(use_precomp, devices[d], nullptr, table_budget_gb, setup);
-            } catch (const std::exception& e) {
-                errs[d] = e.what();
-                if (errs[d].empty()) errs[d] = "unknown failure";
-            } catch (...) {  // (nothing may leave a helper thread)
-                errs[d] = "unknown failure";
-            }
-        };
         // Engines on DIFFERENT GPUs are built side by side (they share nothing but the mutex-guarded registries); entries that repeat
         // an ordinal -- the form the one-GPU tests use -- are built one after the other: the later one finds the tables the earlier
         // one has published.  (Same-GPU constructors side by side work as well -- the table registry is made for concurrent
         // constructors, tools/probe_concurrent_ctors.py -- but a list 0,0 built that way kept 1.4 GB of HBM after injected constructor
         // faults on two of the test boxes, which is not understood; the sequential order is the one the soaks have run on.)
-        std::vector<std::thread> th;
-        std::vector<char> deferred(D, 0);
-        for (size_t d = 1; d < D; d++) {
-            for (size_t k = 0; k < d; k++) deferred[d] |= devices[k] == devices[d];
-            if (deferred[d]) continue;
-            try {
-                th.emplace_back(make, d);
-            } catch (const std::exception&) {  // no thread to be had: built on this one, below
-                deferred[d] = 1;
-            }
+        std::vector<size_t> first, again;  // entries that name a GPU for the first time / once more
+        for (size_t d = 0; d < D; d++) {
+            bool repeat = false;
+            for (size_t k = 0; k < d; k++) repeat |= devices[k] == devices[d];
+            (repeat ? again : first).push_back(d);
         }
-        make(0);
-        for (auto& t : th) t.join();
-        for (size_t d = 1; d < D; d++)
-            if (deferred[d]) make(d);
+        auto make = [&](const std::vector<size_t>& ds) {  // side by side
+            const auto thrown = kzg::run_side_by_side((int)ds.size(), [&](int i) {
+                c->engines[ds[(size_t)i]] = new kzg::Engine(use_precomp, devices[ds[(size_t)i]], nullptr, table_budget_gb, setup);
+            });
+            for (size_t i = 0; i < ds.size(); i++)
+                if (thrown[i]) errs[ds[i]] = kzg::what_was_thrown(thrown[i], "", "unknown failure");
+        };
+        make(first);
+        for (size_t d : again) make({d});
         for (size_t d = 0; d < D; d++)
             if (!c->engines[d]) throw std::runtime_error(D == 1 ? errs[d] : "device " + std::to_string(devices[d]) + ": " + errs[d]);
         c->engine = c->engines[0];
@@ -310,10 +355,7 @@ CResult eth_kzg_verify_cell_kzg_proof_batch(const DASContext* ctx, uint64_t comm
     int ver = 0;
     int st = e->verify_cell_kzg_proof_batch_combined(commitments_length, commitments, cell_indices_length, cell_indices,
                                                      cells_length, cells, proofs_length, proofs, &ver);
-    if (st == kzg::ERR_DEVICE) return device_err(e);
-    if (st) return err(status_text(st));
-    *verified = ver != 0;
-    return ok();
+    return finish_verdict(e, st, ver, verified);
 }
 
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths,
@@ -321,28 +363,8 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many(const DASContext* ctx, uint
                                                      const uint64_t* const* cell_indices, const uint64_t* cells_lengths,
                                                      const uint8_t* const* const* cells, const uint64_t* proofs_lengths,
                                                      const uint8_t* const* const* proofs, bool* verified, int32_t* status) {
-    if (n_batches > MAX_BATCH) return err("InvalidInput");  // (before the context is looked at: a corrupted count is rejected whatever else is wrong)
-    live(ctx);  // own lock, stream and scratch inside (verify_many.hip): no lane needed
-    if (n_batches == 0) return ok();
-    try {
-        std::vector<int> ver(n_batches), st(n_batches);
-        // by PROBLEM over the device list: problems are independent (each has its own Fiat-Shamir transcript)
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n_batches, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            kzg::Engine* e = ctx->engines[(size_t)d];
-            const int rc = e->verify_cell_kzg_proof_batch_many_host(hi - lo, commitments_lengths + lo, commitments + lo, cell_indices_lengths + lo,
-                                                                    cell_indices + lo, cells_lengths + lo, cells + lo, proofs_lengths + lo, proofs + lo,
-                                                                    ver.data() + lo, st.data() + lo);
-            return rc == kzg::ERR_DEVICE ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        for (uint64_t b = 0; b < n_batches; b++) {
-            verified[b] = st[b] == 0 && ver[b] != 0;
-            if (status) status[b] = st[b];
-        }
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return cell_many(ctx, n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells, proofs_lengths, proofs,
+                     /*leaf=*/false, verified, status);  // (the count is checked before the context is looked at: sliced_call)
 }
 
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device(const DASContext* ctx, uint64_t n, const uint8_t* d_commitments,
@@ -354,10 +376,7 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device(const DASContext* ctx, ui
     kzg::Engine* e = lane.e;
     int ver = 0;
     int st = e->verify_cell_kzg_proof_batch_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, &ver, (hipStream_t)hip_stream);
-    if (st == kzg::ERR_DEVICE) return device_err(e);
-    if (st) return err(status_text(st));
-    *verified = ver != 0;
-    return ok();
+    return finish_verdict(e, st, ver, verified);
 }
 
 // The two calls above with a flags word (c_eth_kzg.h: the leaf-hashed challenge).  The flagged host form is a single-problem call on a
@@ -379,10 +398,7 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_ex(const DASContext* ctx, uint64
     int ver = 0;
     int st = e->verify_cell_kzg_proof_batch_host(commitments_length, commitments, cell_indices_length, cell_indices, cells_length, cells,
                                                  proofs_length, proofs, &ver, &mode);
-    if (st == kzg::ERR_DEVICE) return device_err(e);
-    if (st) return err(status_text(st));
-    *verified = ver != 0;
-    return ok();
+    return finish_verdict(e, st, ver, verified);
 }
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(const DASContext* ctx, uint64_t n, const uint8_t* d_commitments,
                                                           const uint64_t* d_cell_indices, const uint8_t* d_cells, const uint8_t* d_proofs,
@@ -398,10 +414,7 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device_ex(const DASContext* ctx,
     mode.leaf = true;
     int ver = 0;
     int st = e->verify_cell_kzg_proof_batch_device(n, d_commitments, d_cell_indices, d_cells, d_proofs, &ver, (hipStream_t)hip_stream, &mode);
-    if (st == kzg::ERR_DEVICE) return device_err(e);
-    if (st) return err(status_text(st));
-    *verified = ver != 0;
-    return ok();
+    return finish_verdict(e, st, ver, verified);
 }
 
 // The many-verification with a flags word, on pointer lists and on flat arrays in HBM (c_eth_kzg.h).  Flags, counts and cell_starts are
@@ -414,32 +427,8 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex(const DASContext* ctx, u
                                                         const uint8_t* const* const* cells, const uint64_t* proofs_lengths,
                                                         const uint8_t* const* const* proofs, uint32_t flags, bool* verified, int32_t* status) {
     if (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) return err("InvalidInput: unknown verification flags");
-    if (n_batches > MAX_BATCH) return err("InvalidInput");
-    if (!flags)
-        return eth_kzg_amd_verify_cell_kzg_proof_batch_many(ctx, n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices,
-                                                            cells_lengths, cells, proofs_lengths, proofs, verified, status);
-    live(ctx);
-    if (n_batches == 0) return ok();
-    try {
-        std::vector<int> ver(n_batches), st(n_batches);
-        kzg::VerifyManyInput in;
-        in.n_commitments = commitments_lengths; in.n_indices = cell_indices_lengths; in.n_cells = cells_lengths; in.n_proofs = proofs_lengths;
-        in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
-        in.leaf = true;
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n_batches, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            kzg::Engine* e = ctx->engines[(size_t)d];
-            const int rc = e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver.data() + lo, st.data() + lo);
-            return rc == kzg::ERR_DEVICE ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        for (uint64_t b = 0; b < n_batches; b++) {
-            verified[b] = st[b] == 0 && ver[b] != 0;
-            if (status) status[b] = st[b];
-        }
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return cell_many(ctx, n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells, proofs_lengths, proofs,
+                     /*leaf=*/flags != 0, verified, status);
 }
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext* ctx, uint64_t n_batches, const uint64_t* cell_starts,
                                                                const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
@@ -464,11 +453,7 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext*
         in.user_stream = (hipStream_t)hip_stream;
         in.leaf = flags != 0;
         if (e->verify_cell_kzg_proof_batch_many(n_batches, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
-        for (uint64_t b = 0; b < n_batches; b++) {
-            verified[b] = st[b] == 0 && ver[b] != 0;
-            if (status) status[b] = st[b];
-        }
-        return ok();
+        return verdicts_out(n_batches, ver.data(), st.data(), verified, status);
     } catch (const std::exception& ex) {
         return err(std::string("DeviceError(") + ex.what() + ")");
     }
@@ -535,10 +520,6 @@ uint64_t eth_kzg_constant_bytes_per_proof(void) { return 48; }
 uint64_t eth_kzg_constant_cells_per_ext_blob(void) { return CELLS; }
 
 // EIP-4844 single-point operations (bindings/c/src/lib.rs:423-566)
-static CResult finish(kzg::Engine* e, int st) {
-    if (st == kzg::ERR_DEVICE) return device_err(e);
-    return st ? err(status_text(st)) : ok();
-}
 CResult eth_kzg_compute_kzg_proof(const DASContext* ctx, const uint8_t* blob, const uint8_t* z, uint8_t* out_proof, uint8_t* out_y) {
     Picked p = pick(ctx, CELLS);
     auto lane = p.e->lease_serial();
@@ -558,8 +539,7 @@ CResult eth_kzg_verify_kzg_proof(const DASContext* ctx, const uint8_t* commitmen
     kzg::Engine* e = lane.e;
     int ver = 0;
     int st = e->verify_kzg_proof_host(commitment, z, y, proof, &ver);
-    if (!st) *verified = ver != 0;
-    return finish(e, st);
+    return finish_verdict(e, st, ver, verified);
 }
 CResult eth_kzg_verify_blob_kzg_proof(const DASContext* ctx, const uint8_t* blob, const uint8_t* commitment, const uint8_t* proof,
                                       bool* verified) {
@@ -568,8 +548,7 @@ CResult eth_kzg_verify_blob_kzg_proof(const DASContext* ctx, const uint8_t* blob
     kzg::Engine* e = lane.e;
     int ver = 0;
     int st = e->verify_blob_kzg_proof_host(blob, commitment, proof, &ver);
-    if (!st) *verified = ver != 0;
-    return finish(e, st);
+    return finish_verdict(e, st, ver, verified);
 }
 CResult eth_kzg_verify_blob_kzg_proof_batch(const DASContext* ctx, uint64_t blobs_length, const uint8_t* const* blobs,
                                             uint64_t commitments_length, const uint8_t* const* commitments, uint64_t proofs_length,
@@ -580,8 +559,7 @@ CResult eth_kzg_verify_blob_kzg_proof_batch(const DASContext* ctx, uint64_t blob
     kzg::Engine* e = lane.e;
     int ver = 0;
     int st = e->verify_blob_kzg_proof_batch_host(blobs_length, blobs, commitments_length, commitments, proofs_length, proofs, &ver);
-    if (!st) *verified = ver != 0;
-    return finish(e, st);
+    return finish_verdict(e, st, ver, verified);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -590,69 +568,31 @@ CResult eth_kzg_verify_blob_kzg_proof_batch(const DASContext* ctx, uint64_t blob
 CResult eth_kzg_amd_compute_cells_and_kzg_proofs_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs,
                                                        uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs,
                                                        int32_t* status) {
-    if (n > MAX_BATCH) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    if (!blobs) return err("InvalidInput");
-    try {
-        std::vector<int> st(n);
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            kzg::Engine* e = ctx->engines[(size_t)d];
-            return e->compute_cells_and_kzg_proofs_host((int)(hi - lo), blobs + lo, out_cells ? out_cells + lo : nullptr,
-                                                        out_proofs ? out_proofs + lo : nullptr, st.data() + lo)
-                       ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return sliced_call(ctx, n, MAX_BATCH, nullptr, status, [&] { return blobs != nullptr; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int*) {
+        return batch_failure(e, e->compute_cells_and_kzg_proofs_host((int)(hi - lo), blobs + lo, out_cells ? out_cells + lo : nullptr,
+                                                                     out_proofs ? out_proofs + lo : nullptr, st + lo));
+    });
 }
 CResult eth_kzg_amd_blob_to_kzg_commitment_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs,
                                                  uint8_t* const* out, int32_t* status) {
-    if (n > MAX_BATCH) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    if (!blobs || !out) return err("InvalidInput");
-    try {
-        std::vector<int> st(n);
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            auto lane = ctx->engines[(size_t)d]->lease_serial();
-            kzg::Engine* e = lane.e;
-            return e->blob_to_kzg_commitment_host((int)(hi - lo), blobs + lo, out + lo, st.data() + lo) ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return sliced_call(ctx, n, MAX_BATCH, nullptr, status, [&] { return blobs && out; }, [&](kzg::Engine* dev, uint64_t lo, uint64_t hi, int* st, int*) {
+        auto lane = dev->lease_serial();
+        kzg::Engine* e = lane.e;
+        return batch_failure(e, e->blob_to_kzg_commitment_host((int)(hi - lo), blobs + lo, out + lo, st + lo));
+    });
 }
 CResult eth_kzg_amd_recover_cells_and_proofs_batch(const DASContext* ctx, uint64_t n, const uint64_t* cells_lengths,
                                                    const uint8_t* const* const* cells, const uint64_t* cell_indices_lengths,
                                                    const uint64_t* const* cell_indices, uint8_t* const* const* out_cells,
                                                    uint8_t* const* const* out_proofs, int32_t* status) {
-    if (n > MAX_BATCH) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    if (!cells_lengths || !cells || !cell_indices_lengths || !cell_indices) return err("InvalidInput");
-    try {
-        std::vector<int> st(n);
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            auto lane = ctx->engines[(size_t)d]->lease_serial();
-            kzg::Engine* e = lane.e;
-            return e->recover_cells_and_kzg_proofs_batch_host((int)(hi - lo), cells_lengths + lo, cells + lo, cell_indices_lengths + lo,
-                                                              cell_indices + lo, out_cells ? out_cells + lo : nullptr,
-                                                              out_proofs ? out_proofs + lo : nullptr, st.data() + lo)
-                       ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return sliced_call(ctx, n, MAX_BATCH, nullptr, status, [&] { return cells_lengths && cells && cell_indices_lengths && cell_indices; },
+                       [&](kzg::Engine* dev, uint64_t lo, uint64_t hi, int* st, int*) {
+        auto lane = dev->lease_serial();
+        kzg::Engine* e = lane.e;
+        return batch_failure(e, e->recover_cells_and_kzg_proofs_batch_host((int)(hi - lo), cells_lengths + lo, cells + lo, cell_indices_lengths + lo,
+                                                                           cell_indices + lo, out_cells ? out_cells + lo : nullptr,
+                                                                           out_proofs ? out_proofs + lo : nullptr, st + lo));
+    });
 }
 CResult eth_kzg_amd_compute_cells_and_kzg_proofs_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs,
                                                         uint8_t* d_out_cells, uint8_t* d_out_proofs, int32_t* status,
@@ -683,45 +623,19 @@ CResult eth_kzg_amd_blob_to_kzg_commitment_device(const DASContext* ctx, uint64_
 // the engine that owns d_blobs; the device verifier is ONE random combination over the whole batch and is never cut.
 CResult eth_kzg_amd_compute_blob_kzg_proof_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* commitments,
                                                  uint8_t* const* out_proofs, int32_t* status) {
-    if (n > MAX_BATCH) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    if (!blobs || !commitments || !out_proofs) return err("InvalidInput");
-    try {
-        std::vector<int> st(n);
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            auto lane = ctx->engines[(size_t)d]->lease_serial();
-            kzg::Engine* e = lane.e;
-            return e->compute_blob_kzg_proof_batch_host((int)(hi - lo), blobs + lo, commitments + lo, out_proofs + lo, st.data() + lo) ? device_text(e)
-                                                                                                                                     : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return sliced_call(ctx, n, MAX_BATCH, nullptr, status, [&] { return blobs && commitments && out_proofs; }, [&](kzg::Engine* dev, uint64_t lo, uint64_t hi, int* st, int*) {
+        auto lane = dev->lease_serial();
+        kzg::Engine* e = lane.e;
+        return batch_failure(e, e->compute_blob_kzg_proof_batch_host((int)(hi - lo), blobs + lo, commitments + lo, out_proofs + lo, st + lo));
+    });
 }
 CResult eth_kzg_amd_compute_kzg_proof_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* zs,
                                             uint8_t* const* out_proofs, uint8_t* const* out_ys, int32_t* status) {
-    if (n > MAX_BATCH) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    if (!blobs || !zs || !out_proofs || !out_ys) return err("InvalidInput");
-    try {
-        std::vector<int> st(n);
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            auto lane = ctx->engines[(size_t)d]->lease_serial();
-            kzg::Engine* e = lane.e;
-            return e->compute_kzg_proof_batch_host((int)(hi - lo), blobs + lo, zs + lo, out_proofs + lo, out_ys + lo, st.data() + lo) ? device_text(e)
-                                                                                                                                      : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        if (status) for (uint64_t i = 0; i < n; i++) status[i] = st[i];
-        return ok();
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return sliced_call(ctx, n, MAX_BATCH, nullptr, status, [&] { return blobs && zs && out_proofs && out_ys; }, [&](kzg::Engine* dev, uint64_t lo, uint64_t hi, int* st, int*) {
+        auto lane = dev->lease_serial();
+        kzg::Engine* e = lane.e;
+        return batch_failure(e, e->compute_kzg_proof_batch_host((int)(hi - lo), blobs + lo, zs + lo, out_proofs + lo, out_ys + lo, st + lo));
+    });
 }
 CResult eth_kzg_amd_compute_blob_kzg_proof_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments,
                                                   uint8_t* d_out_proofs, int32_t* status, void* hip_stream) {
@@ -761,40 +675,23 @@ CResult eth_kzg_amd_verify_blob_kzg_proof_batch_device(const DASContext* ctx, ui
     kzg::Engine* e = lane.e;
     int ver = 0;
     const int st = e->verify_blob_kzg_proof_batch_device(n, d_blobs, d_commitments, d_proofs, &ver, (hipStream_t)hip_stream);
-    if (!st) *verified = ver != 0;
-    return finish(e, st);
+    return finish_verdict(e, st, ver, verified);
 }
 // Many verify_kzg_proof items, a verdict each (point_many.hip).  The count and the arrays are checked before the context is looked at.
 // Host form: contiguous slices by item over the device list; device form: the device that owns ALL FOUR buffers.
-static CResult point_many_results(uint64_t n, const std::vector<int>& ver, const std::vector<int>& st, bool* verified, int32_t* status) {
-    for (uint64_t i = 0; i < n; i++) {
-        verified[i] = st[i] == 0 && ver[i] != 0;
-        if (status) status[i] = st[i];
-    }
-    return ok();
-}
 CResult eth_kzg_amd_verify_kzg_proof_many(const DASContext* ctx, uint64_t n, const uint8_t* const* commitments, const uint8_t* const* zs,
                                           const uint8_t* const* ys, const uint8_t* const* proofs, bool* verified, int32_t* status) {
-    if (n > kzg::POINT_MANY_MAX_ITEMS) return err("InvalidInput");
-    if (n && (!commitments || !zs || !ys || !proofs || !verified)) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    try {
+    if (n && (!commitments || !zs || !ys || !proofs || !verified)) return err("InvalidInput");  // (with the count, before the context is looked at)
+    kzg::PointManyInput in;
+    in.commitments = commitments; in.zs = zs; in.ys = ys; in.proofs = proofs;
+    auto items_ok = [&] {
         for (uint64_t i = 0; i < n; i++)
-            if (!commitments[i] || !zs[i] || !ys[i] || !proofs[i]) return err("InvalidInput");
-        std::vector<int> ver(n), st(n);
-        kzg::PointManyInput in;
-        in.commitments = commitments; in.zs = zs; in.ys = ys; in.proofs = proofs;
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            kzg::Engine* e = ctx->engines[(size_t)d];
-            const int rc = e->verify_kzg_proof_many(hi - lo, in.from(lo), ver.data() + lo, st.data() + lo);
-            return rc == kzg::ERR_DEVICE ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        return point_many_results(n, ver, st, verified, status);
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+            if (!commitments[i] || !zs[i] || !ys[i] || !proofs[i]) return false;
+        return true;
+    };
+    return sliced_call(ctx, n, kzg::POINT_MANY_MAX_ITEMS, verified, status, items_ok, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+        return many_failure(e, e->verify_kzg_proof_many(hi - lo, in.from(lo), ver + lo, st + lo));
+    });
 }
 CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext* ctx, uint64_t n, const uint8_t* d_commitments, const uint8_t* d_zs,
                                                  const uint8_t* d_ys, const uint8_t* d_proofs, bool* verified, int32_t* status, void* hip_stream) {
@@ -812,7 +709,7 @@ CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext* ctx, uint64_t
         in.d_commitments = d_commitments; in.d_zs = d_zs; in.d_ys = d_ys; in.d_proofs = d_proofs;
         in.user_stream = (hipStream_t)hip_stream;
         if (e->verify_kzg_proof_many(n, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
-        return point_many_results(n, ver, st, verified, status);
+        return verdicts_out(n, ver.data(), st.data(), verified, status);
     } catch (const std::exception& ex) {
         return err(std::string("DeviceError(") + ex.what() + ")");
     }
@@ -821,29 +718,20 @@ CResult eth_kzg_amd_verify_kzg_proof_many_device(const DASContext* ctx, uint64_t
 // (host form: contiguous slices by item) or the owner of ALL THREE buffers (device form).
 CResult eth_kzg_amd_verify_blob_kzg_proof_many(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* commitments,
                                                const uint8_t* const* proofs, bool* verified, int32_t* status) {
-    if (n > kzg::BLOB_MANY_MAX_ITEMS) return err("InvalidInput");
-    if (n && (!blobs || !commitments || !proofs || !verified)) return err("InvalidInput");
-    live(ctx);
-    if (n == 0) return ok();
-    try {
+    if (n && (!blobs || !commitments || !proofs || !verified)) return err("InvalidInput");  // (with the count, before the context is looked at)
+    kzg::PointManyInput in;
+    in.from_blobs = true;
+    in.blobs = blobs; in.commitments = commitments; in.proofs = proofs;
+    auto items_ok = [&] {
         for (uint64_t i = 0; i < n; i++) {
             verified[i] = false;
-            if (!blobs[i] || !commitments[i] || !proofs[i]) return err("InvalidInput");
+            if (!blobs[i] || !commitments[i] || !proofs[i]) return false;
         }
-        std::vector<int> ver(n), st(n);
-        kzg::PointManyInput in;
-        in.from_blobs = true;
-        in.blobs = blobs; in.commitments = commitments; in.proofs = proofs;
-        const auto r = kzg::fan_out_slices((int)ctx->engines.size(), n, [&](int d, uint64_t lo, uint64_t hi) -> std::string {
-            kzg::Engine* e = ctx->engines[(size_t)d];
-            const int rc = e->verify_kzg_proof_many(hi - lo, in.from(lo), ver.data() + lo, st.data() + lo);
-            return rc == kzg::ERR_DEVICE ? device_text(e) : std::string();
-        });
-        if (r.first >= 0) return slices_result(ctx, r);
-        return point_many_results(n, ver, st, verified, status);
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+        return true;
+    };
+    return sliced_call(ctx, n, kzg::BLOB_MANY_MAX_ITEMS, verified, status, items_ok, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+        return many_failure(e, e->verify_kzg_proof_many(hi - lo, in.from(lo), ver + lo, st + lo));
+    });
 }
 CResult eth_kzg_amd_verify_blob_kzg_proof_many_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments,
                                                       const uint8_t* d_proofs, bool* verified, int32_t* status, void* hip_stream) {
@@ -863,7 +751,7 @@ CResult eth_kzg_amd_verify_blob_kzg_proof_many_device(const DASContext* ctx, uin
         in.d_blobs = d_blobs; in.d_commitments = d_commitments; in.d_proofs = d_proofs;
         in.user_stream = (hipStream_t)hip_stream;
         if (e->verify_kzg_proof_many(n, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
-        return point_many_results(n, ver, st, verified, status);
+        return verdicts_out(n, ver.data(), st.data(), verified, status);
     } catch (const std::exception& ex) {
         return err(std::string("DeviceError(") + ex.what() + ")");
     }

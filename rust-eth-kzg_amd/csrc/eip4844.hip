@@ -494,10 +494,7 @@ int Engine::verify_blob_kzg_proof_batch_device(uint64_t n64, const uint8_t* d_bl
         std::vector<const uint8_t*> cp(n), pp(n);
         HIPCK(hipSetDevice(dev_));
         hipStream_t st = stream_;
-        if (user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
-            HIPCK(hipEventRecord(v_decoded_, user_stream));
-            HIPCK(hipStreamWaitEvent(st, v_decoded_, 0));
-        }
+        order_behind(st, user_stream, v_decoded_);
         const int sub = std::min(n, device_batch_max_);
         ensure_workspace(sub);
         const Scratch4844 s = scratch_4844(n);

@@ -22,6 +22,7 @@
 namespace kzg {
 
 namespace pairing { struct G2Prepared; }
+namespace vm { struct DevicePairing; }  // vm_search.hpp
 struct Comm;  // multi_gpu.cpp
 struct G1Affine;  // curve.hpp
 struct Fr8 { uint32_t v[8]; };
@@ -631,6 +632,7 @@ private:
     const void* d_pairing_key(int k) const { return (const uint8_t*)d_pairing_ + (size_t)k * 68 * 192; }
     const void* d_pairing_frob() const { return d_pairing_key(3); }
     int gpu_pairing_min_ = 0;  // smallest batch of probes whose pairings run on the GPU (ETH_KZG_AMD_GPU_PAIRING_MIN); 0: never
+    vm::DevicePairing device_pairing(int key) const;  // key (0, 2) next to -[1]_2 for k_pairing_check; the empty one where probes never go to the GPU
 
     // verify workspace: one device arena + one pinned host staging buffer, grown on demand (guarded by mu_)
     void* v_dev_ = nullptr;
@@ -681,10 +683,25 @@ private:
     };
     VmSlot vm_slot_[VM_SLOTS];
     SlotSet<VM_SLOTS> vm_slots_;  // leases of the pass slots (host_sync.hpp)
+    // a pass slot taken for one pass (verify_many.hip): the slot, its lock, and the stream the slot runs on
+    struct PassSlot {
+        VmSlot* slot;
+        std::unique_lock<std::mutex> lock;
+        hipStream_t stream;
+    };
+    PassSlot lease_pass_slot(bool prefer_idle_work_set);
+    struct PointPass;  // one pass of verify_kzg_proof_many on such a slot (point_many.hip)
+    // the part of a many-verification call that runs as passes of its own on one slot: the whole call, or one of its concurrent parts
+    int verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap);
     std::unique_ptr<HostPool> stage_pool_;  // staging of single verifications (a few threads: the lane + the pass slots run side by side)
     std::once_flag stage_pool_once_;
     std::unique_ptr<HostPool> vm_pool_;  // the host threads of the many-verification passes (hashes, staging, pairing checks)
     std::once_flag vm_pool_once_;
+    struct VmHost {
+        int T;           // threads a pass spreads its host work over, the caller's among them
+        HostPool* pool;  // the T - 1 others (made on first use)
+    };
+    VmHost vm_host();
     bool vm_search_ = true;  // ETH_KZG_AMD_VM_SEARCH=0: a pass whose folded check fails is re-checked problem by problem (round 3's form)
     int vm_small_max_ = -1;  // passes of at most this many problems take the short-chain form (verify_many.hip); -1: 2 x host threads
     uint8_t* vd_pin_ = nullptr;  // device-resident verification: the host mirror the transcript hash reads (grow-only, guarded by mu_)

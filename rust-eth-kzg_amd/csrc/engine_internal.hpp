@@ -62,6 +62,14 @@ inline void grow_pinned(uint8_t*& p, size_t& cap, size_t bytes) {
     HIPCK(hipHostMalloc((void**)&p, bytes + (bytes >> 2), hipHostMallocDefault));
     cap = bytes + (bytes >> 2);
 }
+// What the caller has queued on its stream (NULL: the default stream) produces the inputs of a device-resident call: the stream `st`
+// the call runs on waits for it, through `ev` (created on first use).  The same stream is in order already.
+inline void order_behind(hipStream_t st, hipStream_t user_stream, hipEvent_t& ev) {
+    if (user_stream == st) return;
+    if (!ev) HIPCK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    HIPCK(hipEventRecord(ev, user_stream));
+    HIPCK(hipStreamWaitEvent(st, ev, 0));
+}
 // the layout of such a block: take `bytes`, get their offset, stay 256-byte aligned
 struct Carve {
     size_t end = 0;

@@ -714,8 +714,7 @@ int Engine::test_pairing_check_many(int key, uint64_t n64, const uint8_t* pairs4
         memset(&pq[2 * e + 1], 0xff, sizeof(JacQ));
     }
     const pairing::G2Prepared* const vk[2] = {key ? g2_tau1_.get() : g2_tau_.get(), g2_neg_gen_.get()};
-    const int T = vm::host_threads(knobs_);
-    std::call_once(vm_pool_once_, [&] { vm_pool_.reset(new HostPool(T > 1 ? T - 1 : 1, [d = dev_] { (void)hipSetDevice(d); })); });
+    const int T = vm_host().T;
     std::lock_guard<std::recursive_mutex> lk(mu_);
     try {
         HIPCK(hipSetDevice(dev_));

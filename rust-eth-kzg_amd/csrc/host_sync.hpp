@@ -1,6 +1,7 @@
 // The host-side concurrency protocols of a context, free of HIP: one context is shared by many host threads (the reference's
 // usage: bindings/node/src/lib.rs:35,92-299, bindings/java/.../LibEthKZGTest.java:28-37), and what makes that work --
 //   HostPool       a persistent pool of helper threads (hashing, staging, pairings)
+//   run_side_by_side  the shares of one call on a thread each (passes, parts, device slices, engine constructors), errors per share
 //   Combiner       concurrent single verifications combined into passes: leader election, follower wake-up, failure fan-out
 //   SlotSet        pass slots: take a free one, prefer one whose partner resource is idle, else queue round-robin
 //   LanePool       engine lanes: the primary when idle, an idle auxiliary, a new one built OUTSIDE the lock, else queue
@@ -112,6 +113,48 @@ inline void parallel_for(int n, int threads, HostPool* pool, F fn) {
         if (sh->state.fetch_or(CLOSED) != 0) sh->cv.wait(lk, [&] { return sh->state.load() == CLOSED; });
     }
     if (sh->err) std::rethrow_exception(sh->err);
+}
+
+// k shares of a call SIDE BY SIDE: fn(0) .. fn(k - 1), each on a fresh thread but index 0, which runs on the caller once the helpers
+// have been started; an index whose thread cannot be had runs on the caller as well.  Every index runs to its end whatever the others
+// do, nothing fn throws leaves a thread, every thread is joined before the return.  Returns, per index, what fn threw (null: nothing).
+template <class F>
+inline std::vector<std::exception_ptr> run_side_by_side(int k, F fn) {
+    if (k < 0) k = 0;
+    std::vector<std::exception_ptr> thrown((size_t)k);
+    auto guarded = [&](int i) {
+        try {
+            fn(i);
+        } catch (...) {
+            thrown[i] = std::current_exception();
+        }
+    };
+    std::vector<std::thread> th;
+    std::vector<int> here;  // the caller's indices
+    if (k > 0) here.push_back(0);
+    th.reserve((size_t)k);  // (before the first thread: a joinable thread must never be unwound)
+    here.reserve((size_t)k);
+    for (int i = 1; i < k; i++) {
+        try {
+            th.emplace_back(guarded, i);
+        } catch (...) {
+            here.push_back(i);
+        }
+    }
+    for (int i : here) guarded(i);
+    for (auto& t : th) t.join();
+    return thrown;
+}
+// the text of such a report: prefix + what() of a std::exception, `unknown` for anything else (and where that text would be empty)
+inline std::string what_was_thrown(const std::exception_ptr& e, const char* prefix, const char* unknown) {
+    std::string s;
+    try {
+        std::rethrow_exception(e);
+    } catch (const std::exception& ex) {
+        s = std::string(prefix) + ex.what();
+    } catch (...) {
+    }
+    return s.empty() ? std::string(unknown) : s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -367,38 +410,21 @@ private:
 inline uint64_t slice_begin(uint64_t n, int n_devices, int d) { return (uint64_t)((unsigned __int128)n * (unsigned)d / (unsigned)n_devices); }
 
 // run(device, lo, hi) -> "" on success, else the error text.  Returns {-1, ""} or {lowest failing device, its text}.
-// An exception out of run() is that slice's error (never out of a thread).
+// An exception out of run() is that slice's error.  Empty slices start no thread; the first non-empty slice is the caller's.
 template <class F>
 inline std::pair<int, std::string> fan_out_slices(int n_devices, uint64_t n, F run) {
     if (n_devices < 1) n_devices = 1;
-    std::vector<std::string> why((size_t)n_devices);
-    std::vector<char> failed((size_t)n_devices, 0);
-    auto guarded = [&](int d, uint64_t lo, uint64_t hi) {
-        try {
-            why[d] = run(d, lo, hi);
-        } catch (const std::exception& e) {
-            why[d] = std::string("exception: ") + e.what();
-        } catch (...) {
-            why[d] = "unknown exception";
-        }
-        failed[d] = !why[d].empty();
-    };
-    std::vector<std::thread> th;
-    int first = -1;
-    for (int d = 0; d < n_devices; d++) {
-        const uint64_t lo = slice_begin(n, n_devices, d), hi = slice_begin(n, n_devices, d + 1);
-        if (lo == hi) continue;
-        if (first < 0) { first = d; continue; }  // the caller's own slice: run last, after the helpers have been started
-        try {
-            th.emplace_back(guarded, d, lo, hi);
-        } catch (const std::exception& e) {  // no thread to be had: the slice runs on the caller
-            guarded(d, lo, hi);
-        }
-    }
-    if (first >= 0) guarded(first, slice_begin(n, n_devices, first), slice_begin(n, n_devices, first + 1));
-    for (auto& t : th) t.join();
+    std::vector<int> dev;  // the devices whose slice is not empty
     for (int d = 0; d < n_devices; d++)
-        if (failed[d]) return {d, why[d]};
+        if (slice_begin(n, n_devices, d) != slice_begin(n, n_devices, d + 1)) dev.push_back(d);
+    std::vector<std::string> why(dev.size());
+    const auto thrown = run_side_by_side((int)dev.size(), [&](int i) {
+        why[i] = run(dev[i], slice_begin(n, n_devices, dev[i]), slice_begin(n, n_devices, dev[i] + 1));
+    });
+    for (size_t i = 0; i < dev.size(); i++) {
+        if (thrown[i]) why[i] = what_was_thrown(thrown[i], "exception: ", "unknown exception");
+        if (!why[i].empty()) return {dev[i], why[i]};
+    }
     return {-1, std::string()};
 }
 

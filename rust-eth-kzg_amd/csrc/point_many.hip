@@ -63,64 +63,63 @@ struct PointPassLayout {
 };
 }  // namespace
 
-int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* verified, int* status, PointManyTap* tap) {
-    const int n_all = (int)n64;
-    for (int i = 0; i < n_all; i++) { verified[i] = 0; status[i] = OK; }
-    if (n_all == 0) return OK;
-    const int P = tap && tap->pass_size > 0 ? tap->pass_size : in.from_blobs ? BLOB_MANY_PASS : POINT_MANY_PASS;
-    std::vector<uint64_t> starts;
-    for (uint64_t lo = 0; lo < n64; lo = point_pass_end(n64, lo, (uint64_t)P)) starts.push_back(lo);
-    starts.push_back(n64);
-    const int n_passes = (int)starts.size() - 1;
-    if (tap) {
-        tap->pass_starts = starts;
-        tap->leaves.assign((size_t)n_all * 32, 0);
-        if (in.from_blobs) { tap->zs.assign((size_t)n_all * 32, 0); tap->ys.assign((size_t)n_all * 32, 0); }
-        tap->rho.assign((size_t)n_all * 4, 0);
-        tap->seeds.assign((size_t)n_passes * 32, 0);
-        tap->fold.assign((size_t)n_passes * 2 * launch::SIZEOF_JACQ, 0xff);
-        tap->fold_verdict.assign(n_passes, -1);
-    }
-    const int T = vm::host_threads(knobs_);
-    std::call_once(vm_pool_once_, [&] { vm_pool_.reset(new HostPool(T > 1 ? T - 1 : 1, [d = dev_] { (void)hipSetDevice(d); })); });
-    HostPool* const pool = vm_pool_.get();
-    const pairing::G2Prepared* const vk[2] = {g2_tau1_.get(), g2_neg_gen_.get()};  // [tau]_2, -[1]_2: the single call's (eip4844.hip)
+// One pass: items [lo, lo + n) of the call on a pass slot, its steps in the order run() takes them.  Everything goes onto the slot's
+// stream st; the tap (null in the product) is the call's.
+struct Engine::PointPass {
+    Engine& e;
+    const PointManyInput src;  // the call's input from lo on
+    const uint64_t lo;
+    const int n, pass;
+    int *const ver, *const stat;  // the pass's verdicts and statuses in the caller's arrays
+    PointManyTap* const tap;
+    const int T;
+    HostPool* const pool;
+    PassSlot slot = e.lease_pass_slot(/*prefer_idle_work_set=*/true);
+    const hipStream_t st = slot.stream;
+    TraceLap lap{e.knobs_.trace, src.from_blobs ? "verify_blob_kzg_proof_many" : "verify_kzg_proof_many"};
+    const PointPassLayout L{n, !src.from_blobs ? 0 : src.on_device ? 2 : 1};
+    const pairing::G2Prepared* const vk[2] = {e.g2_tau1_.get(), e.g2_neg_gen_.get()};  // [tau]_2, -[1]_2: the single call's (eip4844.hip)
+    uint8_t *hb = nullptr, *db = nullptr;  // the slot's pinned slab and device arena
+    std::vector<char> live;                // items that decoded without an error
+    int n_live = 0;
+    int* h_st() const { return (int*)(hb + L.poff_st); }
+    uint8_t* h_leaf() const { return hb + L.poff_leaf; }
 
-    // one pass: items [lo, hi) of the call on a pass slot
-    auto run_pass = [&](int pass) {
-        const uint64_t lo = starts[pass];
-        const int n = (int)(starts[pass + 1] - lo);
-        const PointManyInput src = in.from(lo);
-        int* const ver = verified + lo;
-        int* const stat = status + lo;
-        auto slot_lease = vm_slots_.acquire([&](int k) { return mutex_is_free(work_[1 + k % (NW - 1)].mu); });
-        VmSlot* slot = &vm_slot_[slot_lease.index];
-        HIPCK(hipSetDevice(dev_));
-        const int slot_index = (int)(slot - vm_slot_);
-        hipStream_t st = work_[1 + slot_index % (NW - 1)].stream ? work_[1 + slot_index % (NW - 1)].stream : stream_;  // (verify_many.hip: why no stream of its own)
-        TraceLap lap{knobs_.trace, src.from_blobs ? "verify_blob_kzg_proof_many" : "verify_kzg_proof_many"};
-        const PointPassLayout L(n, !src.from_blobs ? 0 : src.on_device ? 2 : 1);
-        grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
-        grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
-        uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
-        int* const h_st = (int*)(hb + L.poff_st);
-        uint8_t* const h_leaf = hb + L.poff_leaf;
-        // stale contents of the persistent slab must fail closed: status words and result slots are poisoned
-        memset(h_st, 0xff, (size_t)n * 4);
+    void run() {
+        arena();
+        stage_items();
+        decode_and_status();
+        weights_and_ranges();
+        products_and_fold();
+        verdicts();
+    }
+    // the slot's blocks, large enough; stale contents of the persistent slab must fail closed: status words and result slots are poisoned
+    void arena() {
+        HIPCK(hipSetDevice(e.dev_));
+        grow_device(slot.slot->dev, slot.slot->dev_cap, L.dev_bytes, st);
+        grow_pinned(slot.slot->pin, slot.slot->pin_cap, L.pin_bytes);
+        hb = slot.slot->pin;
+        db = (uint8_t*)slot.slot->dev;
+        memset(h_st(), 0xff, (size_t)n * 4);
         memset(hb + L.poff_fold, 0xff, 2 * launch::SIZEOF_JACQ);
-        memset(h_leaf, 0xff, (size_t)n * 32);
+        memset(h_leaf(), 0xff, (size_t)n * 32);
         HIPCK(hipMemsetAsync(db + L.off_st, 0xff, (size_t)n * 4, st));
         HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)2 * n * 4, st));
         HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, 2 * launch::SIZEOF_JACQ, st));
-        // ---- the items into the arena
-        const uint8_t* d_blobs = nullptr;
+    }
+    // the leaves of items whose z and y are in the arena: bodies gathered and hashed on the GPU, the digests down
+    void leaves_on_gpu() {
+        launch::pm_leaf_bodies(db + L.off_c, db + L.off_z, db + L.off_y, db + L.off_p, db + L.off_bodies, n, st);
+        launch::sha256_many(n, nullptr, 0, db + L.off_bodies, PointProofTranscript::LEAF_BYTES, (uint32_t)PointProofTranscript::LEAF_BYTES, nullptr, 0, 0,
+                            db + L.off_leaf, st);
+        HIPCK(hipMemcpyAsync(h_leaf(), db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+    }
+    // ---- the items into the arena, from one of the three sources
+    void stage_items() {
+        if (src.on_device) order_behind(st, src.user_stream, slot.slot->ordered);
         if (src.from_blobs) {
+            const uint8_t* d_blobs = nullptr;
             if (src.on_device) {
-                if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
-                if (src.user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
-                    HIPCK(hipEventRecord(slot->ordered, src.user_stream));
-                    HIPCK(hipStreamWaitEvent(st, slot->ordered, 0));
-                }
                 blob_challenge_header(hb + L.off_hdr);  // the slot's own copy of the 32 bytes (the engine's lives under mu_)
                 HIPCK(hipMemcpyAsync(db + L.off_hdr, hb + L.off_hdr, 32, hipMemcpyHostToDevice, st));
                 HIPCK(hipMemcpyAsync(db + L.off_p, src.d_proofs, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
@@ -142,29 +141,18 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
                 d_blobs = db + L.off_blob;
                 launch::fr_from_be32(n, db + L.off_z, db + L.off_zm, (int*)(db + L.off_zbad), /*reduce=*/false, st);  // (a reduced digest: never refused)
             }
-            launch::blob_eval_at(n, d_blobs, db + L.off_zm, db + L.off_y, db + L.off_ym, (int*)(db + L.off_bbad), d_w29_, n_inv4096_, st);
-            launch::pm_leaf_bodies(db + L.off_c, db + L.off_z, db + L.off_y, db + L.off_p, db + L.off_bodies, n, st);
-            launch::sha256_many(n, nullptr, 0, db + L.off_bodies, PointProofTranscript::LEAF_BYTES, (uint32_t)PointProofTranscript::LEAF_BYTES, nullptr, 0, 0,
-                                db + L.off_leaf, st);
-            HIPCK(hipMemcpyAsync(h_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+            launch::blob_eval_at(n, d_blobs, db + L.off_zm, db + L.off_y, db + L.off_ym, (int*)(db + L.off_bbad), e.d_w29_, e.n_inv4096_, st);
+            leaves_on_gpu();  // (y exists only there)
             if (tap) {  // the pinned staging rows of z and y are free behind the upload
                 HIPCK(hipMemcpyAsync(hb + L.off_z, db + L.off_z, (size_t)n * 32, hipMemcpyDeviceToHost, st));
                 HIPCK(hipMemcpyAsync(hb + L.off_y, db + L.off_y, (size_t)n * 32, hipMemcpyDeviceToHost, st));
             }
         } else if (src.on_device) {
-            if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
-            if (src.user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
-                HIPCK(hipEventRecord(slot->ordered, src.user_stream));
-                HIPCK(hipStreamWaitEvent(st, slot->ordered, 0));
-            }
             HIPCK(hipMemcpyAsync(db + L.off_p, src.d_proofs, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
             HIPCK(hipMemcpyAsync(db + L.off_c, src.d_commitments, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
             HIPCK(hipMemcpyAsync(db + L.off_z, src.d_zs, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
             HIPCK(hipMemcpyAsync(db + L.off_y, src.d_ys, (size_t)n * 32, hipMemcpyDeviceToDevice, st));
-            launch::pm_leaf_bodies(db + L.off_c, db + L.off_z, db + L.off_y, db + L.off_p, db + L.off_bodies, n, st);
-            launch::sha256_many(n, nullptr, 0, db + L.off_bodies, PointProofTranscript::LEAF_BYTES, (uint32_t)PointProofTranscript::LEAF_BYTES, nullptr, 0, 0,
-                                db + L.off_leaf, st);
-            HIPCK(hipMemcpyAsync(h_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+            leaves_on_gpu();
         } else {
             parallel_for(n, T, pool, [&](int i) {
                 memcpy(hb + L.off_p + (size_t)i * 48, src.proofs[i], 48);
@@ -175,10 +163,13 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
             lap("stage (host)");
             HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
         }
-        // ---- GPU work that needs no weight: decoding + subgroup tests of [proofs | commitments], z and y, the status words
+    }
+    // ---- GPU work that needs no weight: decoding + subgroup tests of [proofs | commitments], z and y, the status words; the host
+    // form's leaves meanwhile; then the statuses and the live items
+    void decode_and_status() {
         G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
         int* d_stp = (int*)(db + L.off_stp);
-        launch::g1_decompress2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, n, beta_, st);
+        launch::g1_decompress2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, n, e.beta_, st);
         if (src.from_blobs) {
             launch::pm_blob_status(d_stp, (const int*)(db + L.off_bbad), (int*)(db + L.off_st), n, st);
         } else {
@@ -186,28 +177,30 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
             launch::fr_from_be32(n, db + L.off_y, db + L.off_ym, (int*)(db + L.off_ybad), /*reduce=*/false, st);
             launch::pm_status(d_stp, (const int*)(db + L.off_zbad), (const int*)(db + L.off_ybad), (int*)(db + L.off_st), n, st);
         }
-        HIPCK(hipMemcpyAsync(h_st, db + L.off_st, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(h_st(), db + L.off_st, (size_t)n * 4, hipMemcpyDeviceToHost, st));
         HIPCK(hipGetLastError());
         lap("enqueue (host)");
         if (!src.on_device && !src.from_blobs) {  // meanwhile, on the host threads: the leaves, from the caller's bytes as they lie in the slab
             parallel_for(n, T, pool, [&](int i) {
                 PointProofTranscript::leaf(hb + L.off_c + (size_t)i * 48, hb + L.off_z + (size_t)i * 32, hb + L.off_y + (size_t)i * 32,
-                                           hb + L.off_p + (size_t)i * 48, h_leaf + (size_t)i * 32);
+                                           hb + L.off_p + (size_t)i * 48, h_leaf() + (size_t)i * 32);
             });
             lap("leaf hashes (host)");
         }
         SYNC_CHECKED(st);
         lap(src.from_blobs ? "challenges + evaluations + decode + leaf hashes (GPU)" : src.on_device ? "decode + leaf hashes (GPU)" : "wait decode");
-        // ---- statuses; the seed and the weights of ALL the items of the pass
-        std::vector<char> live(n, 0);
-        int n_live = 0;
+        live.assign(n, 0);
         for (int i = 0; i < n; i++) {
-            if (h_st[i] != OK && h_st[i] != ERR_SCALAR && h_st[i] != ERR_G1) throw std::runtime_error("point verification pass left no status");
-            stat[i] = h_st[i];
-            if (h_st[i] == OK) { live[i] = 1; n_live++; }
+            const int s = h_st()[i];
+            if (s != OK && s != ERR_SCALAR && s != ERR_G1) throw std::runtime_error("point verification pass left no status");
+            stat[i] = s;
+            if (s == OK) { live[i] = 1; n_live++; }
         }
+    }
+    // ---- the seed and the weights of ALL the items of the pass; the ranges of the two-level fold
+    void weights_and_ranges() {
         uint8_t seed[32];
-        PointProofTranscript::seed((uint64_t)n, h_leaf, seed);
+        PointProofTranscript::seed((uint64_t)n, h_leaf(), seed);
         uint32_t* const h_rho = (uint32_t*)(hb + L.off_rho);
         parallel_for(n, T, pool, [&](int i) { fold_weight(seed, (uint64_t)i, h_rho + 4 * (size_t)i); });
         int* const h_frng = (int*)(hb + L.off_frng);
@@ -215,7 +208,7 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         h_frng[2 * L.n_l1] = 0; h_frng[2 * L.n_l1 + 1] = L.n_l1;
         lap("seed + weights (host)");
         if (tap) {
-            memcpy(tap->leaves.data() + lo * 32, h_leaf, (size_t)n * 32);
+            memcpy(tap->leaves.data() + lo * 32, h_leaf(), (size_t)n * 32);
             if (src.from_blobs) {
                 memcpy(tap->zs.data() + lo * 32, hb + L.off_z, (size_t)n * 32);
                 memcpy(tap->ys.data() + lo * 32, hb + L.off_y, (size_t)n * 32);
@@ -223,10 +216,12 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
             memcpy(tap->seeds.data() + (size_t)pass * 32, seed, 32);
             memcpy(tap->rho.data() + lo * 4, h_rho, (size_t)n * 16);
         }
-        // ---- the products, the per-item pairs, the full-range pair (also when no item is live: the pair is then the identity twice)
+    }
+    // ---- the products, the per-item pairs, the full-range pair (also when no item is live: the pair is then the identity twice)
+    void products_and_fold() {
         HIPCK(hipMemcpyAsync(db + L.off_frng, hb + L.off_frng, L.in2_bytes - L.off_frng, hipMemcpyHostToDevice, st));
-        launch::pm_mul(d_pts, d_srs_, db + L.off_zm, db + L.off_ym, (const uint32_t*)(db + L.off_rho), (const int*)(db + L.off_st), db + L.off_pairs,
-                       db + L.off_terms, n, beta_, st);
+        launch::pm_mul((G1Affine*)(db + L.off_pts), e.d_srs_, db + L.off_zm, db + L.off_ym, (const uint32_t*)(db + L.off_rho), (const int*)(db + L.off_st),
+                       db + L.off_pairs, db + L.off_terms, n, e.beta_, st);
         launch::pm_pairs(db + L.off_terms, db + L.off_pairs, n, st);
         const int* d_frng = (const int*)(db + L.off_frng);
         if (L.n_l1 == 1) {
@@ -239,7 +234,9 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         HIPCK(hipGetLastError());
         SYNC_CHECKED(st);
         lap("products + pairs + fold (GPU)");
-        // ---- verdicts: ONE pairing check of the full-range pair; only if that fails the search
+    }
+    // ---- verdicts: ONE pairing check of the full-range pair; only if that fails the search
+    void verdicts() {
         const int v = vm::check_pair((const JacQ*)(hb + L.poff_fold), vk);
         if (v < 0) throw std::runtime_error("point verification pass left no folded result");
         if (tap) {
@@ -251,12 +248,7 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
         } else {
             std::atomic<int> device_fault{0};
             std::vector<int> probes;
-            vm::SearchView S;
-            S.n = n; S.max_ranges = L.max_ranges; S.T = T; S.pool = pool; S.hb = hb;
-            S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.off_rng = L.off_rng; S.off_pairs = L.off_pairs; S.off_rsum = L.off_rsum;
-            S.vk = vk; S.live = live.data(); S.verified = ver; S.device_fault = &device_fault;
-            if (gpu_pairing_min_ > 0) S.gpu = {d_pairing_key(2), d_pairing_key(1), d_pairing_frob(), gpu_pairing_min_};
-            S.off_verd = L.off_verd; S.poff_verd = L.poff_verd;
+            vm::SearchView S = vm::search_view(L, n, L.off_pairs, T, pool, hb, vk, e.device_pairing(2), live.data(), ver, &device_fault);
             if (tap) { S.tap_probes = &probes; S.tap_probe_sums = &tap->probe_sums; S.tap_device_probes = &tap->device_probes; }
             vm::search_wrong_proofs(S, n_live, db, st);
             if (device_fault.load()) throw std::runtime_error("point verification pass left no result");
@@ -266,39 +258,40 @@ int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* v
             }
         }
         lap("pairing checks (host)");
-    };
+    }
+};
 
+int Engine::verify_kzg_proof_many(uint64_t n64, const PointManyInput& in, int* verified, int* status, PointManyTap* tap) {
+    const int n_all = (int)n64;
+    for (int i = 0; i < n_all; i++) { verified[i] = 0; status[i] = OK; }
+    if (n_all == 0) return OK;
+    const int P = tap && tap->pass_size > 0 ? tap->pass_size : in.from_blobs ? BLOB_MANY_PASS : POINT_MANY_PASS;
+    std::vector<uint64_t> starts;
+    for (uint64_t lo = 0; lo < n64; lo = point_pass_end(n64, lo, (uint64_t)P)) starts.push_back(lo);
+    starts.push_back(n64);
+    const int n_passes = (int)starts.size() - 1;
+    if (tap) {
+        tap->pass_starts = starts;
+        tap->leaves.assign((size_t)n_all * 32, 0);
+        if (in.from_blobs) { tap->zs.assign((size_t)n_all * 32, 0); tap->ys.assign((size_t)n_all * 32, 0); }
+        tap->rho.assign((size_t)n_all * 4, 0);
+        tap->seeds.assign((size_t)n_passes * 32, 0);
+        tap->fold.assign((size_t)n_passes * 2 * launch::SIZEOF_JACQ, 0xff);
+        tap->fold_verdict.assign(n_passes, -1);
+    }
+    const VmHost host = vm_host();
     // passes side by side on the pass slots (the tap's arrays are filled in order: a tapped call runs its passes one after the other)
     const int lanes = tap ? 1 : std::min(n_passes, (int)VM_SLOTS);
-    std::vector<std::string> errs(lanes);
-    auto run_lane = [&](int lane) {
-        try {
-            for (int p = lane; p < n_passes; p += lanes) run_pass(p);
-        } catch (const std::exception& e) {
-            errs[lane] = e.what();
-            if (errs[lane].empty()) errs[lane] = "unknown failure";
-        } catch (...) {
-            errs[lane] = "unknown failure";
+    const auto thrown = run_side_by_side(lanes, [&](int lane) {
+        for (int p = lane; p < n_passes; p += lanes) {
+            const uint64_t lo = starts[p];
+            PointPass{*this, in.from(lo), lo, (int)(starts[p + 1] - lo), p, verified + lo, status + lo, tap, host.T, host.pool}.run();
         }
-    };
-    {
-        std::vector<std::thread> th;
-        std::vector<int> here{0};
-        th.reserve(lanes);
-        for (int l = 1; l < lanes; l++) {
-            try {
-                th.emplace_back(run_lane, l);
-            } catch (const std::exception&) {  // no thread to be had: that lane's passes run on this thread
-                here.push_back(l);
-            }
-        }
-        for (int l : here) run_lane(l);
-        for (auto& t : th) t.join();
-    }
+    });
     for (int l = 0; l < lanes; l++)
-        if (!errs[l].empty()) {
+        if (thrown[l]) {
             for (int i = 0; i < n_all; i++) verified[i] = 0;
-            set_error(std::runtime_error(errs[l]));
+            set_error(std::runtime_error(what_was_thrown(thrown[l], "", "unknown failure")));
             return ERR_DEVICE;
         }
     return OK;

@@ -445,10 +445,7 @@ int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments
             grow_pinned(vd_pin_, vd_pin_cap_, sz_c + sz_i);
             uint8_t *pin_c = vd_pin_, *pin_i = vd_pin_ + sz_c;
             hipStream_t st = stream_;
-            if (user_stream != st) {
-                HIPCK(hipEventRecord(v_decoded_, user_stream));
-                HIPCK(hipStreamWaitEvent(st, v_decoded_, 0));
-            }
+            order_behind(st, user_stream, v_decoded_);
             HIPCK(hipMemcpyAsync(pin_c, d_commitments, sz_c, hipMemcpyDeviceToHost, st));
             HIPCK(hipMemcpyAsync(pin_i, d_cell_indices, sz_i, hipMemcpyDeviceToHost, st));
             HIPCK(hipStreamSynchronize(st));
@@ -471,10 +468,7 @@ int Engine::verify_cells_partial_device(uint64_t n, const uint8_t* d_commitments
         uint8_t* pin = vd_pin_;
         uint8_t *pin_c = pin, *pin_i = pin + sz_c, *pin_p = pin + sz_c + sz_i, *pin_l = pin + sz_c + sz_i + sz_p;
         hipStream_t st = stream_;
-        if (user_stream != st) {  // what the caller has queued on its stream (NULL: the default stream) produces the inputs
-            HIPCK(hipEventRecord(v_decoded_, user_stream));
-            HIPCK(hipStreamWaitEvent(st, v_decoded_, 0));
-        }
+        order_behind(st, user_stream, v_decoded_);
         HIPCK(hipMemcpyAsync(pin_c, d_commitments, sz_c, hipMemcpyDeviceToHost, st));
         HIPCK(hipMemcpyAsync(pin_i, d_cell_indices, sz_i, hipMemcpyDeviceToHost, st));
         HIPCK(hipMemcpyAsync(pin_p, d_proofs, sz_p, hipMemcpyDeviceToHost, st));

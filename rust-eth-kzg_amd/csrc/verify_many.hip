@@ -189,13 +189,8 @@ struct PassHost {
 // Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM (off_fprod): the search of vm_search.hpp over them;
 // where it ends in single problems, each is checked on the host against its own sums, which the pass has read back anyway.
 void search_wrong_proofs(PassHost& V, int n_live, uint8_t* db, hipStream_t st) {
-    const PassLayout& L = V.L;
-    vm::SearchView S;
-    S.n = L.Bc; S.max_ranges = L.max_ranges; S.T = V.T; S.pool = V.pool; S.hb = V.hb;
-    S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.off_rng = L.off_rng; S.off_pairs = L.off_fprod; S.off_rsum = L.off_rsum;
-    S.vk = V.vk; S.live = V.live.data(); S.verified = V.verified; S.device_fault = &V.device_fault;
+    vm::SearchView S = vm::search_view(V.L, V.L.Bc, V.L.off_fprod, V.T, V.pool, V.hb, V.vk, V.gpu, V.live.data(), V.verified, &V.device_fault);
     S.check_single = [&V](int i) { V.check_single(i); };
-    S.gpu = V.gpu; S.off_verd = L.off_verd; S.poff_verd = L.poff_verd;
     if (V.tap) { S.tap_probes = &V.tap->probes; S.tap_probe_sums = &V.tap->probe_sums; S.tap_device_probes = &V.tap->device_probes; }
     vm::search_wrong_proofs(S, n_live, db, st);
     if (V.tap && !V.tap->probes.empty()) V.tap->searched = 1;
@@ -221,55 +216,65 @@ int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyMan
     // products are on the GPU the next one's 100+ MB are still being staged and hashed by the host threads (in one pass the
     // staging of all 275 MB of a 1024-problem call came first, ~10 ms, and the GPU waited for it).  Each part folds its own
     // pairing check (one pass, round 3's form: 28.4-28.9 ms against 24.6-26.2 for 1024 problems).
-    static thread_local bool in_part = false;
     constexpr int max_parts = VM_SLOTS < 3 ? (int)VM_SLOTS : 3;
-    if (!in_part && max_parts > 1 && B >= VM_SPLIT_MIN_PROBLEMS) {
-        uint64_t total_cells = 0;
+    uint64_t total_cells = 0;
+    if (max_parts > 1 && B >= VM_SPLIT_MIN_PROBLEMS)
         for (int b = 0; b < B; b++) total_cells += in.cells_of((uint64_t)b);
-        if (total_cells >= (uint64_t)VM_SPLIT_MIN_CELLS) {
-            const int parts = max_parts;
-            std::vector<int> cut{0};
-            uint64_t acc = 0;
-            for (int b = 0; b < B; b++) {  // equal shares of the cells
-                acc += in.cells_of((uint64_t)b);
-                if ((int)cut.size() < parts && acc * parts >= total_cells * cut.size() && b + 1 < B) cut.push_back(b + 1);
-            }
-            cut.push_back(B);
-            std::vector<int> rcs(cut.size() - 1, OK);
-            std::vector<std::string> errs(cut.size() - 1);
-            auto run_part = [&](int p) {
-                const int lo = cut[p], n = cut[p + 1] - lo;
-                in_part = true;
-                rcs[p] = verify_cell_kzg_proof_batch_many((uint64_t)n, in.from((uint64_t)lo), verified + lo, status + lo);
-                if (rcs[p] == ERR_DEVICE) errs[p] = last_error();
-                in_part = false;
-            };
-            std::vector<std::thread> th;
-            for (int p = 1; p + 1 < (int)cut.size(); p++) th.emplace_back(run_part, p);
-            run_part(0);
-            for (auto& t : th) t.join();
-            for (size_t p = 0; p < rcs.size(); p++)
-                if (rcs[p] != OK) { set_error(std::runtime_error(errs[p])); return rcs[p]; }
-            return OK;
-        }
+    if (total_cells < (uint64_t)VM_SPLIT_MIN_CELLS) return verify_cell_kzg_proof_batch_many_part(B, in, verified, status, tap);
+    std::vector<int> cut{0};
+    uint64_t acc = 0;
+    for (int b = 0; b < B; b++) {  // equal shares of the cells
+        acc += in.cells_of((uint64_t)b);
+        if ((int)cut.size() < max_parts && acc * max_parts >= total_cells * cut.size() && b + 1 < B) cut.push_back(b + 1);
     }
+    cut.push_back(B);
+    const int parts = (int)cut.size() - 1;
+    std::vector<int> rcs(parts, OK);
+    std::vector<std::string> errs(parts);  // (the error text belongs to the thread that ran the part)
+    const auto thrown = run_side_by_side(parts, [&](int p) {
+        const int lo = cut[p];
+        rcs[p] = verify_cell_kzg_proof_batch_many_part(cut[p + 1] - lo, in.from((uint64_t)lo), verified + lo, status + lo, nullptr);
+        if (rcs[p] == ERR_DEVICE) errs[p] = last_error();
+    });
+    for (int p = 0; p < parts; p++) {
+        if (thrown[p]) { rcs[p] = ERR_DEVICE; errs[p] = what_was_thrown(thrown[p], "", "unknown failure"); }
+        if (rcs[p] != OK) { set_error(std::runtime_error(errs[p])); return rcs[p]; }
+    }
+    return OK;
+}
+
+Engine::VmHost Engine::vm_host() {
     const int T = host_threads(knobs_);
     std::call_once(vm_pool_once_, [&] { vm_pool_.reset(new HostPool(T > 1 ? T - 1 : 1, [d = dev_] { (void)hipSetDevice(d); })); });
-    HostPool* pool = vm_pool_.get();
-    // a free pass slot (lock, stream, arena, pinned slab); when all are taken, queue on one of them in turn (host_sync.hpp: SlotSet).
-    // First choice: a free slot whose work set (whose in-order stream the pass runs on, below) is not held by a prover call right
-    // now -- otherwise the pass and that call wait on each other's work and a fault of either surfaces in both; a peek,
-    // not a lease: a prover call that takes the set a moment later shares the stream with the pass, which is correct, only serial
-    auto slot_lease = vm_slots_.acquire([&](int k) { return mutex_is_free(work_[1 + k % (NW - 1)].mu); });
-    VmSlot* slot = &vm_slot_[slot_lease.index];
+    return {T, vm_pool_.get()};
+}
+vm::DevicePairing Engine::device_pairing(int key) const {
+    if (gpu_pairing_min_ <= 0) return {};
+    return {d_pairing_key(key), d_pairing_key(1), d_pairing_frob(), gpu_pairing_min_};
+}
+// A free pass slot (lock, stream, arena, pinned slab); when all are taken, queue on one of them in turn (host_sync.hpp: SlotSet).
+// prefer_idle_work_set: first choice is a free slot whose work set (whose in-order stream the pass runs on) is not held by a prover
+// call right now -- otherwise the pass and that call wait on each other's work and a fault of either surfaces in both; a
+// peek, not a lease: a prover call that takes the set a moment later shares the stream with the pass, which is correct, only serial.
+// A slot runs on the stream of one of the prover's three work sets instead of a stream of its own: HIP maps a process's streams onto
+// FOUR hardware queues per priority, and the context's stream + the three work-set streams are exactly four -- a fifth stream would
+// share a queue with one of them and the two would take turns (seen in the rocprofv3 trace of four concurrent callers).
+Engine::PassSlot Engine::lease_pass_slot(bool prefer_idle_work_set) {
+    auto work_of = [this](int k) -> Work& { return work_[1 + k % (NW - 1)]; };
+    auto lease = prefer_idle_work_set ? vm_slots_.acquire([&](int k) { return mutex_is_free(work_of(k).mu); }) : vm_slots_.acquire();
+    const hipStream_t st = work_of(lease.index).stream;
+    return {&vm_slot_[lease.index], std::move(lease.lock), st ? st : stream_};
+}
+
+int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
+    const VmHost host = vm_host();
+    const int T = host.T;
+    HostPool* const pool = host.pool;
+    PassSlot ps = lease_pass_slot(/*prefer_idle_work_set=*/true);
+    VmSlot* const slot = ps.slot;
     try {
         HIPCK(hipSetDevice(dev_));
-        // A slot runs on the stream of one of the prover's three work sets instead of a stream of its own: HIP maps a process's
-        // streams onto FOUR hardware queues per priority, and the context's stream + the three work-set streams are exactly four --
-        // a fifth stream would share a queue with one of them and the two would take turns (seen in the rocprofv3 trace of four
-        // concurrent callers).  A prover call that happens to hold that work set shares the (in-order) stream with the pass.
-        const int slot_index = (int)(slot - vm_slot_);
-        hipStream_t st = work_[1 + slot_index % (NW - 1)].stream ? work_[1 + slot_index % (NW - 1)].stream : stream_;
+        const hipStream_t st = ps.stream;
         TraceLap lap{knobs_.trace, "verify_many"};
         // ---- flat device source: commitments and indices of the call's cells come down (56 bytes per cell) behind whatever the
         // caller's stream has queued; the host validates and de-duplicates from this pinned mirror, and the unique commitments of a
@@ -286,11 +291,7 @@ int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyMan
                 pr[b].mir0 = N;
                 if (in.cells_of((uint64_t)b) <= MAX_CELLS_PER_VERIFICATION) N += in.cells_of((uint64_t)b);
             }
-            if (!slot->ordered) HIPCK(hipEventCreateWithFlags(&slot->ordered, hipEventDisableTiming));
-            if (in.user_stream != st) {
-                HIPCK(hipEventRecord(slot->ordered, in.user_stream));
-                HIPCK(hipStreamWaitEvent(st, slot->ordered, 0));
-            }
+            order_behind(st, in.user_stream, slot->ordered);
             if (N) {
                 grow_pinned(slot->src_pin, slot->src_pin_cap, (size_t)N * 56);
                 uint8_t* const pin_c = slot->src_pin;
@@ -346,8 +347,7 @@ int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyMan
             grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
             grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
             uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
-            PassHost H{L, pr.data() + b0, in.from((uint64_t)b0), mirror_i, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, {}, verified + b0};
-            if (gpu_pairing_min_ > 0) H.gpu = {d_pairing_key(0), d_pairing_key(1), d_pairing_frob(), gpu_pairing_min_};
+            PassHost H{L, pr.data() + b0, in.from((uint64_t)b0), mirror_i, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, device_pairing(0), verified + b0};
             H.tap = tap;
             H.stage();
             lap("stage (host)");
@@ -389,7 +389,7 @@ int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyMan
             if (hash_waits && !slot->hash_inputs_down) HIPCK(hipEventCreateWithFlags(&slot->hash_inputs_down, hipEventDisableTiming));
             if (in.leaf) {
                 // the leaves of all the pass's cells straight out of the arena (its offsets are multiples of 256: the kernel's 16-byte
-                // loads), in order on the pass's stream: a stream of its own would be a fifth one (see above), and a wave per 64 cells
+                // loads), in order on the pass's stream: a stream of its own would be a fifth one (lease_pass_slot), and a wave per 64 cells
                 // for 35 dependent compressions is short against the decoding behind it
                 launch::sha256_cell_leaves(n, db + L.off_c, (const int*)(db + L.off_row), (const int*)(db + L.off_idx), db + L.off_p, db + L.off_cells,
                                            db + L.off_leaf, st, (const int*)(db + L.off_pos));
@@ -530,10 +530,9 @@ int Engine::verify_cell_kzg_proof_batch_combined(uint64_t n_commitments, const u
         // a "pass" of one problem is the single path itself -- 3.3 ms against the 3.65 of a one-problem pass (its points are
         // shifted before the challenge; a pass multiplies by per-lane scalars after it) -- on a pass slot's stream and arena:
         // the latency lane and three slots make four single verifications side by side, one hardware queue each
-        auto sl = vm_slots_.acquire();
-        VmSlot* slot = &vm_slot_[sl.index];
-        const int slot_index = (int)(slot - vm_slot_);
-        slot->vs.stream = work_[1 + slot_index % (NW - 1)].stream ? work_[1 + slot_index % (NW - 1)].stream : stream_;
+        PassSlot sl = lease_pass_slot(/*prefer_idle_work_set=*/false);
+        VmSlot* slot = sl.slot;
+        slot->vs.stream = sl.stream;
         VerifyRequest* r = batch[0];
         G1Affine pts[2];
         bool empty = false;

@@ -62,6 +62,18 @@ struct SearchView {
     std::vector<uint8_t>* tap_probe_sums = nullptr;
     int* tap_device_probes = nullptr;      // how many probes k_pairing_check judged
 };
+// The view of a pass of n entries laid out by L (PassLayout, PointPassLayout: the search's buffers go by the same names in both), its
+// weighted pairs at off_pairs; check_single and the taps are the caller's to add
+template <class Layout>
+inline SearchView search_view(const Layout& L, int n, size_t off_pairs, int T, HostPool* pool, uint8_t* hb, const pairing::G2Prepared* const* vk,
+                              const DevicePairing& gpu, const char* live, int* verified, std::atomic<int>* device_fault) {
+    SearchView S;
+    S.n = n; S.max_ranges = L.max_ranges; S.T = T; S.pool = pool; S.hb = hb;
+    S.poff_rng = L.poff_rng; S.poff_rsum = L.poff_rsum; S.poff_verd = L.poff_verd;
+    S.off_rng = L.off_rng; S.off_pairs = off_pairs; S.off_rsum = L.off_rsum; S.off_verd = L.off_verd;
+    S.gpu = gpu; S.vk = vk; S.live = live; S.verified = verified; S.device_fault = device_fault;
+    return S;
+}
 
 // Some entry of the pass is wrong.  SEARCH for the wrong ones by folding sub-ranges of the resident weighted pairs (k_vm_fold_ranges: one
 // small launch per level) and checking each with one pairing on a host thread -- a range whose fold passes holds only valid entries

@@ -1,5 +1,5 @@
-// The host-side concurrency protocols of a context (csrc/host_sync.hpp: HostPool + parallel_for, Combiner, SlotSet, LanePool,
-// Published) driven WITHOUT a GPU: 32 threads of mixed operations on shared fake contexts whose "device pass" sleeps, throws, or
+// The host-side concurrency protocols of a context (csrc/host_sync.hpp: HostPool + parallel_for, run_side_by_side, Combiner, SlotSet,
+// LanePool, Published) driven WITHOUT a GPU: 32 threads of mixed operations on shared fake contexts whose "device pass" sleeps, throws, or
 // reports wrong proofs, while a builder thread publishes, fills, abandons and reaps tables and a third party creates and frees
 // contexts.  Built with -fsanitize=thread and again with -fsanitize=address,undefined by tests/test_sanitizers.py: a lock-scope
 // bug of the kind ADVICE r3 found by reading (a lane used by two callers, a follower never woken, a table read before its groups
@@ -141,6 +141,53 @@ static void builder(FakeContext& c, std::atomic<bool>& stop) {
     for (int spin = 0; spin < 4000 && c.view.reap([](const FakeTable&) { return true; }) > 0; spin++) nap(50);
 }
 
+// run_side_by_side: the shares of one call (passes, parts, device slices, engine constructors) on a thread each, with shares that
+// sleep, throw std::runtime_error or throw something that is no std::exception.  Checked: every index ran exactly once, index 0 on the
+// caller's thread, a throwing index stops no other, each index's report carries its own text (or nothing), nothing escapes.
+struct NotStd { int share; };
+static void side_by_side(std::mt19937& rng) {
+    static const int ks[5] = {0, 1, 2, 3, 7};
+    const int k = ks[rng() % 5];
+    const unsigned kinds = rng();  // two bits per index: 0 sleeps, 1 throws std::runtime_error, 2 throws a NotStd, 3 returns at once
+    auto kind = [&](int i) { return (int)((kinds >> (2 * i)) & 3u); };
+    std::vector<std::atomic<int>> ran((size_t)k + 1);
+    for (auto& a : ran) a = 0;
+    const std::thread::id caller = std::this_thread::get_id();
+    std::thread::id where0;
+    std::vector<std::exception_ptr> thrown;
+    bool escaped = false;
+    try {
+        thrown = run_side_by_side(k, [&](int i) {
+            ran[(size_t)i]++;
+            if (i == 0) where0 = std::this_thread::get_id();
+            if (kind(i) == 0) nap(20 + 15 * i);
+            if (kind(i) == 1) throw std::runtime_error("share " + std::to_string(i));
+            if (kind(i) == 2) throw NotStd{i};
+        });
+    } catch (...) {
+        escaped = true;
+    }
+    EXPECT(!escaped, "side by side: an exception escaped the runner");
+    EXPECT((int)thrown.size() == k, "side by side: one report per index");
+    if (k > 0) EXPECT(where0 == caller, "side by side: index 0 did not run on the caller's thread");
+    for (int i = 0; i < k && (int)thrown.size() == k; i++) {
+        EXPECT(ran[(size_t)i].load() == 1, "side by side: an index ran twice or never");
+        const std::string own = "share " + std::to_string(i);
+        if (kind(i) == 1) {
+            EXPECT(thrown[i] && what_was_thrown(thrown[i], "", "unknown failure") == own, "side by side: not the index's own text");
+            EXPECT(thrown[i] && what_was_thrown(thrown[i], "exception: ", "unknown exception") == "exception: " + own, "side by side: prefixed text");
+        } else if (kind(i) == 2) {
+            EXPECT(thrown[i] && what_was_thrown(thrown[i], "exception: ", "unknown exception") == "unknown exception", "side by side: a non-std exception's text");
+            int share = -1;
+            try { if (thrown[i]) std::rethrow_exception(thrown[i]); } catch (const NotStd& e) { share = e.share; } catch (...) {}
+            EXPECT(share == i, "side by side: not the index's own exception");
+        } else {
+            EXPECT(!thrown[i], "side by side: a report for an index that did not throw");
+        }
+    }
+    EXPECT(ran[(size_t)k].load() == 0, "side by side: an index beyond k ran");
+}
+
 // The protocol of a context over a device list (c_api.cpp): single calls take a DevicePicker ticket (least load, returned when the
 // call ends), batched calls fan out as contiguous slices with error fan-in -- many threads at once on one picker, fake devices that
 // sleep / fail / throw.  Checked: the loads return to zero, no device is starved or flooded, every index of every batch is served
@@ -230,7 +277,7 @@ int main(int argc, char** argv) {
                 std::mt19937 rng(1234 + t);
                 for (int i = 0; i < iters; i++) {
                     FakeContext& c = shared[(t + i) & 1];
-                    switch (rng() % 6) {
+                    switch (rng() % 7) {
                         case 0: case 1: verify(c, (long)t * 100000 + i); break;
                         case 2: lane_call(c); break;
                         case 3: msm_stage(c); break;
@@ -239,6 +286,7 @@ int main(int argc, char** argv) {
                             nap(60);
                             break;
                         }
+                        case 5: side_by_side(rng); break;
                         default: {
                             std::atomic<int> sum{0};
                             bool threw = false;

@@ -315,6 +315,30 @@ def test_300_items_over_four_blobs_and_the_first_cut(ctx, pool):
     assert st == [0] * n and [i for i in range(n) if not ver[i]] == wrong
 
 
+def test_257_device_items_in_two_passes_side_by_side_behind_the_callers_stream(ctx, pool):
+    """BM.PASS + 1 items in device memory: the smallest call whose two passes run side by side on two pass slots (no tap), each putting
+    its slot's stream behind the caller's, on which the three arrays are still being written when the call is made"""
+    import torch
+    n, wrong = BM.PASS + 1, [0, BM.PASS - 1, BM.PASS]
+    assert n == 257
+    items = [pool[i % 4] for i in range(n)]
+    for i in wrong:
+        items[i] = wrong_of(pool, i % 4)
+    want = expect_single(ctx, items)  # the single call on the four distinct items and the wrong ones
+    assert want[1] == [0] * n and [i for i in range(n) if not want[0][i]] == wrong
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):  # something in front of the writes, so that they have not happened when the call is made
+        a = torch.randn(4096, 4096, device="cuda")
+        for _ in range(8):
+            a = a @ a
+            a = a / a.abs().max()
+    d = DeviceItems(items, stream=s)
+    ver, st = d.call(ctx, stream=s.cuda_stream)
+    torch.cuda.synchronize()
+    assert st == [0] * n and [i for i in range(n) if not ver[i]] == wrong
+    assert (ver, st) == want
+
+
 @pytest.mark.parametrize("where", ["host", "device"])
 def test_nine_wrong_items(ctx, pool, where):
     items = [wrong_of(pool, i % 4) for i in range(9)]
