@@ -475,6 +475,46 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext 
                                                                const uint8_t *d_cells, const uint8_t *d_proofs, uint32_t flags,
                                                                bool *verified, int32_t *status, void *hip_stream);
 
+/* ---- the data columns of one block, the commitments given once ----
+ * A PeerDAS data column sidecar is one cell index, and for every blob of the block one cell and one proof; the block's n_blobs
+ * commitments are the same for every column.  eth_kzg_amd_verify_data_columns takes them ONCE:
+ *   commitments[i]    48 B, blob i                      column_indices[j]   the cell index of column j
+ *   cells[j][i]       2048 B, the cell of blob i in column j              proofs[j][i]   48 B
+ * eth_kzg_amd_verify_data_columns_device: the same in this GPU's HBM -- d_commitments n_blobs*48, d_cells [n_columns][n_blobs][2048],
+ * d_proofs [n_columns][n_blobs][48], any byte address; column_indices, verified and status on the HOST.  Synchronous; work already
+ * queued on hip_stream (NULL: the default stream) is waited for.
+ * Contract: column j gets exactly the verified[j] and status[j] that eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex gives a problem
+ * with the n_blobs commitments as given (one per cell), n_blobs copies of column_indices[j], cells[j] and proofs[j] -- in the
+ * reference's order of checks: status 3 for an index >= 128 or n_blobs > 2^24 - 1; else 2 for a bad commitment, which therefore marks
+ * EVERY column 2; else 2 for a bad proof of that column; else 1 for a non-canonical cell of that column; else 0 and the verdict.
+ * verified[j] is false whenever status[j] != 0; status may be NULL.  n_columns = 0 is Ok.  n_blobs = 0 makes every column verify
+ * whatever its index (an empty problem is validated without an index being read).  Indices may repeat and come in any order;
+ * commitments may repeat.
+ *   flags = 0                                    the reference's transcript per column
+ *   flags = ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT   the leaf-hashed challenge, exactly as the flagged single call takes it for that column
+ *                                                alone; no new domain strings, no new transcript, the folding weights keep their form
+ * Err("InvalidInput...") for the call, before the context is touched: any other flag bit; n_columns > 2^24; a NULL array with a non-zero
+ * count (commitments, cells or proofs with n_blobs > 0 and n_columns > 0 -- also when n_blobs is beyond the bound; column_indices or
+ * verified with n_columns > 0).  A column refused at validation costs its status word: it is taken out of the call before any pass.  Device form: all three device pointers are resolved -- anything but device memory of one listed device is Err; the
+ * commitments come down once (48 * n_blobs bytes); under the leaf flag neither cells nor proofs cross the link, with flags = 0 they
+ * come down for the host's hashes as in _many_device_ex.  Device lists: the host form is cut by column over the listed devices, the
+ * device form runs on the owner of the buffers.
+ * What the call saves against _many on the expanded input is work, not meaning: the unique commitments are decoded and subgroup-tested
+ * once per pass (not once per column), and the cells of a column share h^64, so the second proof product is one per column
+ * (h^64 * sum_k r^k proof_k) where the expanded pass runs one per cell.  Fewer operations, NOT a faster call at the sizes measured:
+ * that one product is a dependent launch and 128 columns x 64 blobs take 0.8 ms longer than _many_device_ex on the expanded input
+ * (DESIGN.md section 5).  The call is there for its interface; when to take it: INTEGRATION.md.
+ * Out of scope: one inverse transform per column in the place of the per-cell interpolation; cheaper w*C products over the shared
+ * points; reading the caller's cells in place; _partial / _combine; the combiner of concurrent single calls; the Node binding. */
+CResult eth_kzg_amd_verify_data_columns(const DASContext *ctx, uint64_t n_blobs, const uint8_t *const *commitments,
+                                        uint64_t n_columns, const uint64_t *column_indices,
+                                        const uint8_t *const *const *cells, const uint8_t *const *const *proofs,
+                                        uint32_t flags, bool *verified, int32_t *status);
+CResult eth_kzg_amd_verify_data_columns_device(const DASContext *ctx, uint64_t n_blobs, const uint8_t *d_commitments,
+                                               uint64_t n_columns, const uint64_t *column_indices, const uint8_t *d_cells,
+                                               const uint8_t *d_proofs, uint32_t flags, bool *verified, int32_t *status,
+                                               void *hip_stream);
+
 /* Introspection used by bench.py / DESIGN.md: bytes of both window tables resident in HBM; nominal window width w of the FK20
  * table in use (a GLV table: ceil(128 / w) windows over the two 128-bit halves of each scalar, packed 96-byte entries: 16
  * gathered additions per base at w = 16, 32 at w = 8 -- the start tables, and all there is with use_precomp = false). */

@@ -170,6 +170,22 @@ int eth_kzg_amd_test_verify_many_sums_device(const DASContext *ctx, uint64_t n_b
                                              int32_t *probe_ranges, uint8_t *probe_sums96, uint64_t max_probes, uint64_t *n_probes,
                                              uint8_t *digests32, uint8_t *leaves32);
 
+/* The same tap on a pass of eth_kzg_amd_verify_data_columns / _device (c_eth_kzg.h; tests/test_gpu_data_columns.py, the expansion into
+ * problems is tests/data_columns.py): problem b of every output above is column b.  on_device = 0: commitments / cells / proofs are the
+ * host form's pointer lists; 1: the device form's flat arrays in device memory (context's first device).  And
+ *   counts2[0]: the commitment points the pass handed to the decoding and subgroup-test launches (the unique commitments, once per pass)
+ *   counts2[1]: the 255-bit products of decoded points the pass's launchers were given: n_columns * n_blobs proofs, n_columns *
+ *               unique commitments and one h^64 * A per column (the interpolation commitments' fixed-base terms are not counted)
+ *   Both are the HOST's launch arguments, not counters read back from the device: they follow the branch the pass took, so they tell a
+ *   column pass from a forward to _many; that every product ran and ran once is what the byte-for-byte pairs say, not these.
+ * One pass only (3 before any launch if the call would be cut, for a NULL buffer, an unknown flag or a column that validation refuses:
+ * the outputs are indexed by column, and refused columns are taken out of the call before its passes); nothing is added on the device. */
+int eth_kzg_amd_test_verify_data_columns_sums(const DASContext *ctx, uint64_t n_blobs, int on_device, const void *commitments,
+                                              uint64_t n_columns, const uint64_t *column_indices, const void *cells, const void *proofs,
+                                              uint32_t flags, int32_t *verified, int32_t *status, int32_t *form4, uint8_t *sums96, uint32_t *rho,
+                                              uint8_t *fold96, int32_t *probe_ranges, uint8_t *probe_sums96, uint64_t max_probes,
+                                              uint64_t *n_probes, uint8_t *digests32, uint8_t *leaves32, uint64_t *counts2);
+
 /* eth_kzg_amd_verify_kzg_proof_many / _many_device with a tap (csrc/point_many.hip; the statement is tests/point_many.py): exactly the
  * public call's launches, on the context's first device.  on_device = 0: commitments / zs / ys / proofs are the host form's pointer
  * lists; 1: the device form's flat arrays in device memory.  1 <= n <= 2^20.  forced_pass: 0 = the product's pass size, else the call is

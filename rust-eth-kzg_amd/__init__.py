@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_blob_kzg_proof_batch_device",
     "eth_kzg_amd_verify_kzg_proof_many", "eth_kzg_amd_verify_kzg_proof_many_device",
     "eth_kzg_amd_verify_blob_kzg_proof_many", "eth_kzg_amd_verify_blob_kzg_proof_many_device",
+    "eth_kzg_amd_verify_data_columns", "eth_kzg_amd_verify_data_columns_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
     "eth_kzg_amd_set_profiling", "eth_kzg_amd_get_stage_times",
     "eth_kzg_amd_comm_probe", "eth_kzg_amd_comm_unique_id", "eth_kzg_amd_comm_init", "eth_kzg_amd_comm_info",
@@ -91,6 +92,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_verify_kzg_proof_many_sums",
     "eth_kzg_amd_test_blob_eval_at", "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums",
     "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats", "eth_kzg_amd_test_g1_decode",
+    "eth_kzg_amd_test_verify_data_columns_sums",
 ]
 
 _lib = None
@@ -193,6 +195,8 @@ def load_library():
         "eth_kzg_amd_verify_kzg_proof_many_device": [P, U64, P, P, P, P, P, P, P],
         "eth_kzg_amd_verify_blob_kzg_proof_many": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_verify_blob_kzg_proof_many_device": [P, U64, P, P, P, P, P, P],
+        "eth_kzg_amd_verify_data_columns": [P, U64, P, U64, P, P, P, C.c_uint32, P, P],
+        "eth_kzg_amd_verify_data_columns_device": [P, U64, P, U64, P, P, P, C.c_uint32, P, P, P],
     }.items():
         if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
             getattr(lib, name).restype = CResult
@@ -233,6 +237,7 @@ def load_library():
         "eth_kzg_amd_test_pairing_check_many": [P, C.c_int, U64, P, C.c_int, P, P, P, P],
         "eth_kzg_amd_test_search_stats": [P, P],
         "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P, P, P],
+        "eth_kzg_amd_test_verify_data_columns_sums": [P, U64, C.c_int, P, U64, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -618,6 +623,49 @@ class DASContext:
             self._ctx, nb, _vp(cs) if len(cs) else None, C.c_void_p(d_commitments), C.c_void_p(d_cell_indices), C.c_void_p(d_cells),
             C.c_void_p(d_proofs), VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st, C.c_void_p(stream) if stream else None))
         return [bool(v) for v in ver][:nb], list(st)[:nb]
+
+    @staticmethod
+    def _marshal_columns(commitments, column_indices, cells, proofs):
+        """-> (n_blobs, n_columns, commitments**, indices*, cells***, proofs***, keep-alive): the arguments of eth_kzg_amd_verify_data_columns
+        (cells[j][i] / proofs[j][i]: blob i in column j)"""
+        nb, nc = len(commitments), len(column_indices)
+        if len(cells) != nc or len(proofs) != nc or any(len(c) != nb for c in cells) or any(len(p) != nb for p in proofs) \
+                or any(len(c) != 48 for c in commitments) or any(len(p) != 48 for col in proofs for p in col) \
+                or any(len(c) != BYTES_PER_CELL for col in cells for c in col):
+            raise KzgError("InvalidLength")  # (fixed-size buffers carry no length across the C ABI)
+        ca, k1 = _flat_ptrs(commitments, 48)
+        idx = np.array(column_indices, dtype=np.uint64) if nc else np.zeros(1, np.uint64)
+        keep, tabs = [k1], [np.zeros(max(1, nc), dtype=np.uint64) for _ in range(2)]
+        for j in range(nc):
+            cla, k2 = _flat_ptrs(cells[j], BYTES_PER_CELL)
+            pa, k3 = _flat_ptrs(proofs[j], 48)
+            keep += [cla, k2, pa, k3]
+            tabs[0][j], tabs[1][j] = cla.ctypes.data, pa.ctypes.data
+        return nb, nc, ca, idx, tabs[0], tabs[1], keep
+
+    def verify_data_columns(self, commitments, column_indices, cells, proofs, leaf_transcript=False):
+        """The data columns of one block, the block's commitments given once (eth_kzg_amd_verify_data_columns): commitments[i] of blob i,
+        column j = (column_indices[j], cells[j][i], proofs[j][i]).  -> (verified list[bool], status list[int]) per column, exactly what
+        verify_cell_kzg_proof_batch_many gives the column as a problem of its own."""
+        nb, nc, ca, idx, cla, pa, _keep = self._marshal_columns(commitments, column_indices, cells, proofs)
+        ver = (C.c_bool * max(1, nc))()
+        st = (C.c_int32 * max(1, nc))()
+        self._check(self._lib.eth_kzg_amd_verify_data_columns(self._ctx, nb, _vp(ca), nc, _vp(idx), _vp(cla), _vp(pa),
+                                                              VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st))
+        return [bool(v) for v in ver][:nc], list(st)[:nc]
+
+    def verify_data_columns_device(self, n_blobs, d_commitments, column_indices, d_cells, d_proofs, stream=None, leaf_transcript=False):
+        """The same on arrays in device memory (eth_kzg_amd_verify_data_columns_device; integer device addresses): d_commitments
+        n_blobs*48 bytes, d_cells [columns][n_blobs][2048], d_proofs [columns][n_blobs][48]; column_indices a host sequence.
+        leaf_transcript=True: neither cells nor proofs are copied to the host."""
+        idx = np.ascontiguousarray(np.array(column_indices, dtype=np.uint64)) if len(column_indices) else np.zeros(1, np.uint64)
+        nc = len(column_indices)
+        ver = (C.c_bool * max(1, nc))()
+        st = (C.c_int32 * max(1, nc))()
+        self._check(self._lib.eth_kzg_amd_verify_data_columns_device(
+            self._ctx, n_blobs, C.c_void_p(d_commitments), nc, _vp(idx), C.c_void_p(d_cells), C.c_void_p(d_proofs),
+            VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st, C.c_void_p(stream) if stream else None))
+        return [bool(v) for v in ver][:nc], list(st)[:nc]
 
     def verify_cell_kzg_proof_batch_partial(self, commitments, cell_indices, cells, proofs, shard_begin, shard_end):
         """This rank's share of a sharded verification: the whole batch goes in (the challenge hashes all of it), the

@@ -459,6 +459,56 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext*
     }
 }
 
+// The columns of one block over ONE commitment list (c_eth_kzg.h): the many-verification's column source (verify_many.hip).  Flags,
+// counts and null arrays are refused before the context is looked at (verify_host.hpp: validate_data_columns_call).  The host form is
+// cut by COLUMN over the device list, the commitments de-duplicated once, here, for all of its slices; the device form runs on the
+// device that owns the three buffers.
+CResult eth_kzg_amd_verify_data_columns(const DASContext* ctx, uint64_t n_blobs, const uint8_t* const* commitments, uint64_t n_columns,
+                                        const uint64_t* column_indices, const uint8_t* const* const* cells, const uint8_t* const* const* proofs,
+                                        uint32_t flags, bool* verified, int32_t* status) {
+    if (kzg::validate_data_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !commitments, !column_indices, !cells, !proofs,
+                                        !verified) != kzg::INPUT_VALID)
+        return err("InvalidInput: unknown verification flags, more than 2^24 columns, or a null array");
+    kzg::ColumnCommitments cc;
+    kzg::VerifyManyInput in;
+    in.columns = true; in.col_blobs = n_blobs; in.col_commitments = commitments; in.col_indices = column_indices; in.cells = cells; in.proofs = proofs;
+    in.leaf = flags != 0;
+    if (n_columns && n_blobs && n_blobs <= kzg::MAX_CELLS_PER_VERIFICATION) {
+        cc.from_list(n_blobs, commitments);
+        in.col = &cc;
+    }
+    return sliced_call(ctx, n_columns, kzg::DATA_COLUMNS_MAX, verified, status, [] { return true; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+        return many_failure(e, e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver + lo, st + lo));
+    });
+}
+CResult eth_kzg_amd_verify_data_columns_device(const DASContext* ctx, uint64_t n_blobs, const uint8_t* d_commitments, uint64_t n_columns,
+                                               const uint64_t* column_indices, const uint8_t* d_cells, const uint8_t* d_proofs, uint32_t flags,
+                                               bool* verified, int32_t* status, void* hip_stream) {
+    if (kzg::validate_data_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !d_commitments, !column_indices, !d_cells, !d_proofs,
+                                        !verified) != kzg::INPUT_VALID)
+        return err("InvalidInput: unknown verification flags, more than 2^24 columns, or a null array");
+    live(ctx);
+    if (n_columns == 0) return ok();
+    kzg::Engine* e = ctx->engine;
+    if (n_blobs && n_blobs <= kzg::MAX_CELLS_PER_VERIFICATION) {  // (otherwise none of the arrays is read)
+        const void* const ptrs[3] = {d_commitments, d_cells, d_proofs};
+        e = engine_of_device_pointers(ctx, ptrs, 3);
+        if (!e) return err("InvalidInput: the three buffers are not device memory of one device of this context");
+    }
+    try {
+        std::vector<int> ver(n_columns), st(n_columns);
+        kzg::VerifyManyInput in;
+        in.columns = in.col_device = true;
+        in.col_blobs = n_blobs; in.col_indices = column_indices; in.d_commitments = d_commitments; in.d_cells = d_cells; in.d_proofs = d_proofs;
+        in.user_stream = (hipStream_t)hip_stream;
+        in.leaf = flags != 0;
+        if (e->verify_cell_kzg_proof_batch_many(n_columns, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
+        return verdicts_out(n_columns, ver.data(), st.data(), verified, status);
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+
 CResult eth_kzg_amd_recover_cells_and_proofs_device(const DASContext* ctx, uint64_t n, const uint8_t* d_cells,
                                                     const uint64_t* present_masks, uint8_t* d_out_cells, uint8_t* d_out_proofs,
                                                     int32_t* status, void* hip_stream) {

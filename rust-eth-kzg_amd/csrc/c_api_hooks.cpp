@@ -146,6 +146,29 @@ int eth_kzg_amd_test_verify_many_sums_device(const DASContext* ctx, uint64_t n_b
     return eng(ctx)->test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
                                               digests32, leaves32);
 }
+// the tap on a pass of the column source (eth_kzg_amd_verify_data_columns / _device)
+int eth_kzg_amd_test_verify_data_columns_sums(const DASContext* ctx, uint64_t n_blobs, int on_device, const void* commitments, uint64_t n_columns,
+                                              const uint64_t* column_indices, const void* cells, const void* proofs, uint32_t flags, int32_t* verified,
+                                              int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges,
+                                              uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes, uint8_t* digests32, uint8_t* leaves32,
+                                              uint64_t* counts2) {
+    if (!verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || !digests32 || !counts2 || (max_probes && (!probe_ranges || !probe_sums96)) ||
+        (on_device != 0 && on_device != 1) || n_columns < 1 || n_columns > (1u << 20) ||
+        kzg::validate_data_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !commitments, !column_indices, !cells, !proofs, false) !=
+            kzg::INPUT_VALID)
+        return kzg::ERR_INPUT;
+    kzg::VerifyManyInput in;
+    in.columns = true; in.col_device = on_device != 0;
+    in.col_blobs = n_blobs; in.col_indices = column_indices;
+    if (on_device) {
+        in.d_commitments = (const uint8_t*)commitments; in.d_cells = (const uint8_t*)cells; in.d_proofs = (const uint8_t*)proofs;
+    } else {
+        in.col_commitments = (const uint8_t* const*)commitments; in.cells = (const uint8_t* const* const*)cells; in.proofs = (const uint8_t* const* const*)proofs;
+    }
+    in.leaf = flags != 0;
+    return eng(ctx)->test_verify_many_sums_in(n_columns, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
+                                              digests32, leaves32, counts2);
+}
 int eth_kzg_amd_test_verify_kzg_proof_many_sums(const DASContext* ctx, uint64_t n, int on_device, const void* commitments, const void* zs, const void* ys,
                                                 const void* proofs, uint64_t forced_pass, int32_t* verified, int32_t* status, uint64_t* pass_starts,
                                                 uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho, uint8_t* fold96,

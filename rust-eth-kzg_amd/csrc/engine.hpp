@@ -24,6 +24,7 @@ namespace kzg {
 namespace pairing { struct G2Prepared; }
 namespace vm { struct DevicePairing; }  // vm_search.hpp
 struct Comm;  // multi_gpu.cpp
+struct ColumnCommitments;  // verify_host.hpp
 struct G1Affine;  // curve.hpp
 struct Fr8 { uint32_t v[8]; };
 struct Fp12w { uint32_t v[12]; };
@@ -50,12 +51,19 @@ struct VerifyManyTap {
     int device_probes = 0;                           // probes whose pairing ran on the GPU (k_pairing_check); the others ran on the host threads
     std::vector<uint8_t> digests;                    // [Bc][32]: the digest each problem's challenge was reduced from (zero: not hashed)
     std::vector<uint8_t> leaves;                     // (leaf-hashed challenges) [n][32]: the leaf digests of the pass's cells as they came down
+    uint64_t commitments_decoded = 0;                // commitment points handed to the pass's decoding launches (a launch argument, not a device counter)
+    uint64_t scalar_muls = 0;                        // 255-bit products of decoded points its launchers were given (proofs, commitments, h^64 A_b)
 };
 // Where the problems of a many-verification call come from (verify_many.hip), and how they take their challenges.
 //   pointer lists (cell_starts null): problem b has n_*[b] entries in commitments[b] / cell_indices[b] / cells[b] / proofs[b], all on the host
 //   flat arrays in this GPU's HBM (cell_starts set, on the host, n_batches + 1 non-decreasing entries): problem b is the entries
 //     [cell_starts[b], cell_starts[b + 1]) of d_commitments (48 B each, one per cell), d_cell_indices, d_cells (2048 B), d_proofs (48 B);
 //     what user_stream has queued produces them
+//   a column matrix over ONE commitment list (columns set; eth_kzg_amd_verify_data_columns / _device): problem b is column b, col_blobs
+//     cells that all carry the index col_indices[b] (host) and whose commitments are the call's col_blobs commitments, one per cell.
+//     Host form: col_commitments[i], cells[b][i], proofs[b][i].  Device form (col_device): d_commitments 48 col_blobs bytes, d_cells /
+//     d_proofs [columns][col_blobs] entries in this GPU's HBM; col0 = the first column of this input in those arrays.  col: the
+//     commitments de-duplicated once for the whole call (null: the call makes it), which every column's problem refers to
 // leaf: every problem's challenge is the leaf-hashed one of the problem alone (verify_host.hpp: CellLeafTranscript, cell_leaf_root),
 // the leaves hashed on the GPU out of the pass's arena; else the reference's transcript on the host threads.
 struct VerifyManyInput {
@@ -70,10 +78,23 @@ struct VerifyManyInput {
     const uint8_t *d_cells = nullptr, *d_proofs = nullptr;
     hipStream_t user_stream = nullptr;
     bool leaf = false;
-    bool on_device() const { return cell_starts != nullptr; }
-    uint64_t cells_of(uint64_t b) const { return on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b]; }
+    bool columns = false, col_device = false;
+    bool col_ready = false;             // the call has validated its columns and taken the refused ones out (verify_many.hip)
+    uint64_t col_blobs = 0, col0 = 0;
+    const uint64_t* col_src = nullptr;  // (device form, once refused columns are out) the place of column b in d_cells / d_proofs
+    const uint8_t* const* col_commitments = nullptr;
+    const uint64_t* col_indices = nullptr;
+    const ColumnCommitments* col = nullptr;
+    bool on_device() const { return columns ? col_device : cell_starts != nullptr; }
+    uint64_t cells_of(uint64_t b) const { return columns ? col_blobs : on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b]; }
     VerifyManyInput from(uint64_t lo) const {  // the problems from lo on (the flat arrays stay: cell_starts holds absolute entries)
         VerifyManyInput s = *this;
+        if (columns) {
+            s.col_indices += lo;
+            if (col_device) { if (col_src) s.col_src += lo; else s.col0 += lo; }
+            else if (cells && proofs) { s.cells += lo; s.proofs += lo; }  // (both may be null when there are no blobs: nothing is read)
+            return s;
+        }
         if (on_device()) { s.cell_starts += lo; return s; }
         s.n_commitments += lo; s.n_indices += lo; s.n_cells += lo; s.n_proofs += lo;
         s.commitments += lo; s.cell_indices += lo; s.cells += lo; s.proofs += lo;
@@ -387,7 +408,8 @@ public:
     // caller's cell order; zero for the cells of a problem that was not hashed)
     int test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
                                  uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
-                                 uint8_t* digests32, uint8_t* leaves32);
+                                 uint8_t* digests32, uint8_t* leaves32, uint64_t* counts2 = nullptr);
+    // (counts2, may be null: the commitment points the pass decoded and the scalar multiplications it launched, VerifyManyTap)
     // verify_kzg_proof_many with its tap set and, if forced_pass > 0, passes of that many items: verdicts and statuses as the call gives
     // them, the pass bounds (pass_starts: up to max_passes + 1 entries), leaves32[n][32], seeds32 / fold96 / fold_verdicts per pass,
     // rho[n][4], the probes (probes4[i] = pass, lo, hi, passed; probe_sums96[i]) up to max_probes of them; pairs compressed on the host

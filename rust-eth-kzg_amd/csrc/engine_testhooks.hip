@@ -582,7 +582,8 @@ int Engine::test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitme
 // The same over either source and with either challenge (the hooks _ex and _device): the taps of the digests and of the leaves besides.
 int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
                                      uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
-                                     uint8_t* digests32, uint8_t* leaves32) {
+                                     uint8_t* digests32, uint8_t* leaves32, uint64_t* counts2) {
+    if (counts2) counts2[0] = counts2[1] = 0;
     if (n_batches < 1 || n_batches > (1u << 20)) return ERR_INPUT;
     uint64_t total_cells = 0;
     for (uint64_t b = 0; b < n_batches; b++) {
@@ -620,6 +621,7 @@ int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& 
     if (digests32) memset(digests32, 0, (size_t)B * 32);
     if (leaves32 && in.leaf) memset(leaves32, 0, (size_t)total_cells * 32);
     if (tap.passes == 0) return OK;  // no cell in the whole call: nothing was launched
+    if (counts2) { counts2[0] = tap.commitments_decoded; counts2[1] = tap.scalar_muls; }
     if (digests32) memcpy(digests32, tap.digests.data(), (size_t)B * 32);
     if (leaves32 && in.leaf) {  // the pass holds the cells of the problems that passed validation, back to back: into the caller's order
         size_t at = 0, flat = 0;

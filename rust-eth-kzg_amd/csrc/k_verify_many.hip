@@ -25,6 +25,8 @@
 #include "glv.hpp"
 #include "vm_lane_mul.hpp"
 
+#include <stdexcept>
+
 namespace kzg {
 
 struct VmPow { Fr p[24]; };  // r^(2^i), Montgomery
@@ -343,6 +345,129 @@ __global__ __launch_bounds__(256) void k_vm_fold_ranges(const JacQ* __restrict__
     if (l == 0) out[2 * (size_t)blockIdx.x + job] = acc;
 }
 
+// ---- The columns of one block over ONE commitment list (eth_kzg_amd_verify_data_columns; verify_many.hip, the column source).
+// Problem b is column b: all its cells carry the index c_b, so h_k^64 = h_(c_b)^64 is one value per column and
+//     B_b = h_(c_b)^64 A_b + sum_row w_(b,row) C_row - commit(sum_k r_b^k I_k):
+// one product per column behind the reduction of A_b where the expanded pass multiplies every proof a second time.  The n_u unique
+// commitments are decoded once per pass; pts = [proofs n | commitments n_u], row[k] < n_u is pass-wide.
+//   k_vc_scalars    r_b^k per cell (no second proof scalar), h_(c_b)^64 per column, canonical
+//   k_vc_weights    w[b][u] = sum of r_b^k over the cells of column b whose commitment is u (block per (column, commitment))
+//   k_vc_products   lane (or quad) per product: r^k pi_k | w[b][u] C_u | (short-chain form) the interpolation terms and, in further
+//                   blocks, the subgroup tests
+//   k_vc_reduce     per column: A_b, and T_b = sum_u w[b][u] C_u - commit(...)
+//   k_vc_hmul       quad per column: B_b = h^64 A_b + T_b, the only writer of the column's second result slot
+// Padding lanes of the product kernels repeat the last product and write nothing (whole waves).
+__global__ void k_vc_scalars(const VmPow* __restrict__ tabs, const int* __restrict__ batch_of, const int* __restrict__ pos_in_batch,
+                             const int* __restrict__ cell_idx, const int* __restrict__ cell_start, const Fr* __restrict__ w8192,
+                             Fr* __restrict__ rp_mont, Fr* __restrict__ s1, Fr* __restrict__ h64, int n, int n_cols) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n) {
+        const VmPow* tab = tabs + batch_of[k];
+        const int e = pos_in_batch[k];
+        Fr acc = one<FrParams>();
+        for (int i = 0; i < 24; i++)
+            if ((e >> i) & 1) acc = mul(acc, tab->p[i]);
+        rp_mont[k] = acc;
+        s1[k] = from_mont(acc);
+    }
+    if (k < n_cols) {  // h_c^64 = omega_128^brp7(c) = w8192[64 * brp7(c)] (k_vm_scalars); a column without cells (refused): 1
+        const int lo = cell_start[k], hi = cell_start[k + 1];
+        Fr h = one<FrParams>();
+        if (lo < hi) h = w8192[64 * (int)(__brev((unsigned)cell_idx[lo]) >> 25)];
+        h64[k] = from_mont(h);
+    }
+}
+__global__ __launch_bounds__(256) void k_vc_weights(const Fr* __restrict__ rp_mont, const int* __restrict__ row, const int* __restrict__ cell_start,
+                                                    Fr* __restrict__ weights, int n_u) {
+    __shared__ uint32_t part[8][256];
+    const int r = blockIdx.x, t = threadIdx.x, b = r / n_u, u = r - b * n_u;
+    const int lo = cell_start[b], hi = cell_start[b + 1];
+    Fr acc = zero<FrParams>();
+    for (int k = lo + t; k < hi; k += 256)
+        if (row[k] == u) acc = add(acc, rp_mont[k]);
+    acc = vm_block_sum(part, acc, t);
+    if (t == 0) weights[r] = from_mont(acc);
+}
+template <bool COOP> struct VcMul;
+template <> struct VcMul<false> {
+    static constexpr int PER_BLOCK = 64;
+    __device__ static JacQ mul(const AffQ& P, const uint32_t split[8], const Fq<1>& beta, int) { return vm_mul_by_scalar(P, split, beta); }
+    __device__ static bool in_subgroup(const AffQ& P, const Fq<1>& beta, int) { return g1_in_subgroup_q(P, beta); }
+};
+template <> struct VcMul<true> {
+    static constexpr int PER_BLOCK = 16;
+    __device__ static JacQ mul(const AffQ& P, const uint32_t split[8], const Fq<1>& beta, int quad) { return vm_mul_by_scalar_coop(P, split, beta, quad); }
+    __device__ static bool in_subgroup(const AffQ& P, const Fq<1>& beta, int quad) { return g1_in_subgroup_coop(P, beta, quad); }
+};
+// products e < n: s1[e] pi_e | n <= e < n + W: w[e - n] C_((e - n) % n_u), W = columns x n_u | n + W <= e < n + W + 64 n_isc:
+// isc[e - n - W] SRS_((e - n - W) & 63) (short-chain form; n_isc = 0 otherwise).  Blocks from mul_blocks on: the subgroup tests of
+// [proofs n | commitments n_u] (status 0 -> 0 / 2, others kept; short-chain form only)
+template <bool COOP>
+__global__ __launch_bounds__(64, 2) void k_vc_products(const G1Affine* __restrict__ pts, const Fr* __restrict__ s1, const Fr* __restrict__ wts,
+                                                       const Fr* __restrict__ isc, const G1Affine* __restrict__ srs, JacQ* __restrict__ prod, int n,
+                                                       int n_u, int W, int n_isc, int mul_blocks, int* __restrict__ status /*[n + n_u]*/, Fq<1> beta) {
+    using M = VcMul<COOP>;
+    const int quad = threadIdx.x & 3, sub = COOP ? threadIdx.x >> 2 : threadIdx.x;
+    if ((int)blockIdx.x >= mul_blocks) {
+        const int i = ((int)blockIdx.x - mul_blocks) * M::PER_BLOCK + sub;
+        if (i >= n + n_u || status[i] != 0) return;
+        const G1Affine a = pts[i];
+        if (is_inf(a)) return;
+        if (!M::in_subgroup(affq_from_affine(a), beta, quad)) status[i] = 2;
+        return;
+    }
+    const int total = n + W + 64 * n_isc;
+    int e = blockIdx.x * M::PER_BLOCK + sub;
+    const bool real = e < total;
+    if (!real) e = total - 1;
+    G1Affine P;
+    Fr k;
+    if (e < n) { P = pts[e]; k = s1[e]; }
+    else if (e < n + W) { P = pts[n + (e - n) % n_u]; k = wts[e - n]; }
+    else { P = srs[(e - n - W) & 63]; k = isc[e - n - W]; }
+    uint32_t split[8];
+    glv_split_balanced(k, split);
+    const JacQ r = M::mul(affq_from_affine(P), split, beta, quad);
+    if (real) prod[e] = r;
+}
+// per column b: out[2b] = A_b = sum of prod[cells of b];  tsum[b] = sum_u prod[n + b n_u + u] + (icommit ? icommit[b] : the 64
+// interpolation terms prod[n + W + 64 b ..]).  out[2b + 1] is left to k_vc_hmul.
+__global__ __launch_bounds__(256) void k_vc_reduce(const JacQ* __restrict__ prod, const JacQ* __restrict__ icommit, const int* __restrict__ cell_start,
+                                                   JacQ* __restrict__ out, JacQ* __restrict__ tsum, int n, int n_u, int W) {
+    __shared__ JacQ red[256];
+    const int b = blockIdx.x, t = threadIdx.x, job = t >> 7, l = t & 127;
+    JacQ acc = jacq_inf();
+    if (!job) {
+        const int lo = cell_start[b], hi = cell_start[b + 1];
+        for (int k = lo + l; k < hi; k += 128) acc = add(acc, prod[k]);
+    } else {
+        const JacQ* wc = prod + n + (size_t)b * n_u;
+        for (int u = l; u < n_u; u += 128) acc = add(acc, wc[u]);
+        if (icommit) { if (l == 0) acc = add(acc, icommit[b]); }
+        else if (l < 64) acc = add(acc, prod[(size_t)n + W + 64 * (size_t)b + l]);
+    }
+    red[t] = acc;
+    vm_two_trees(red, t);
+    if (l == 0) {
+        if (job) tsum[b] = red[128];
+        else out[2 * (size_t)b] = red[0];
+    }
+}
+// out[2b + 1] = h64[b] * out[2b] + tsum[b]: a full 255-bit product per column, four lanes each (the columns of a pass are a few
+// waves); the identity goes through the product as any point does (Z = 0 stays 0)
+__global__ __launch_bounds__(64, 2) void k_vc_hmul(JacQ* __restrict__ out, const JacQ* __restrict__ tsum, const Fr* __restrict__ h64, int n_cols,
+                                                   Fq<1> beta) {
+    const int quad = threadIdx.x & 3;
+    int b = blockIdx.x * 16 + (threadIdx.x >> 2);
+    const bool real = b < n_cols;
+    if (!real) b = n_cols - 1;
+    uint32_t split[8];
+    glv_split_balanced(h64[b], split);
+    JacQ r = vm_mul_by_scalar_coop(out[2 * (size_t)b], split, beta, quad);
+    r = coop_add(r, tsum[b], false, quad);
+    if (real && quad == 0) out[2 * (size_t)b + 1] = r;
+}
+
 namespace launch {
 // the code object of this translation unit is loaded now (HIP loads a code object on the first launch of one of its kernels, and
 // that load is an allocation: it would wait behind a table piece the builder thread is allocating)
@@ -402,6 +527,51 @@ void vm_fold_ranges(const void* prod, const int* ranges, void* out, int n_ranges
 void vm_reduce(const void* prod, const void* icommit, const int* cell_start, const int* row_start, void* out, int n, int n_batches,
                hipStream_t st) {
     if (n_batches > 0) k_vm_reduce<<<n_batches, 256, 0, st>>>((const JacQ*)prod, (const JacQ*)icommit, cell_start, row_start, (JacQ*)out, n);
+}
+// ---- the column source.  Every column of a pass holds cells (verify_many.hip takes refused columns out of the call), so the
+// n_cols * n_u products of a pass are at most its n cells' worth; a count that does not fit the 32-bit indices throws before any launch
+static int vc_weight_products(int n, int n_cols, int n_u) {
+    const long long W = (long long)n_cols * n_u;
+    if (n < 0 || n_cols < 0 || n_u < 0 || (long long)n + W + 65LL * n_cols > 0x7fffffffLL) throw std::runtime_error("column pass: too many products");
+    return (int)W;
+}
+void vc_scalars(const void* pow_tables, const int* batch_of, const int* pos_in_batch, const int* cell_idx, const int* cell_start, const void* w8192,
+                void* rp_mont, void* s1, void* h64, int n, int n_cols, hipStream_t st) {
+    const int lanes = n > n_cols ? n : n_cols;
+    if (lanes > 0)
+        k_vc_scalars<<<(lanes + 255) / 256, 256, 0, st>>>((const VmPow*)pow_tables, batch_of, pos_in_batch, cell_idx, cell_start, (const Fr*)w8192,
+                                                           (Fr*)rp_mont, (Fr*)s1, (Fr*)h64, n, n_cols);
+}
+void vc_weights(const void* rp_mont, const int* row, const int* cell_start, void* weights, int n_cols, int n_u, hipStream_t st) {
+    if (n_cols > 0 && n_u > 0) k_vc_weights<<<vc_weight_products(0, n_cols, n_u), 256, 0, st>>>((const Fr*)rp_mont, row, cell_start, (Fr*)weights, n_u);
+}
+int vc_products(const void* pts, const void* s1, const void* wts, const void* isc, const void* srs, void* prod, int n, int n_u, int n_cols, bool small,
+                int* status, const Fp12w& beta, hipStream_t st) {
+    Fp b384;
+    for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
+    const int W = vc_weight_products(n, n_cols, n_u), n_isc = small ? n_cols : 0, total = n + W + 64 * n_isc, tests = small ? n + n_u : 0;
+    if (total <= 0) return 0;
+    if (small && total + tests <= 2 * coop_points_max()) {  // (k_vm_mul_small's bound: every wave still has a SIMD to itself)
+        const int mb = (total + 15) / 16;
+        k_vc_products<true><<<mb + (tests + 15) / 16, 64, 0, st>>>((const G1Affine*)pts, (const Fr*)s1, (const Fr*)wts, (const Fr*)isc, (const G1Affine*)srs,
+                                                                   (JacQ*)prod, n, n_u, W, n_isc, mb, status, fq_from_fp(b384));
+    } else {
+        const int mb = (total + 63) / 64;
+        k_vc_products<false><<<mb + (tests + 63) / 64, 64, 0, st>>>((const G1Affine*)pts, (const Fr*)s1, (const Fr*)wts, (const Fr*)isc, (const G1Affine*)srs,
+                                                                    (JacQ*)prod, n, n_u, W, n_isc, mb, status, fq_from_fp(b384));
+    }
+    return n + W;
+}
+int vc_sums(const void* prod, const void* icommit, const int* cell_start, const void* h64, void* out, int n, int n_u, int n_cols, bool small,
+            const Fp12w& beta, hipStream_t st) {
+    if (n_cols <= 0) return 0;
+    Fp b384;
+    for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
+    const int W = vc_weight_products(n, n_cols, n_u);
+    JacQ* tsum = (JacQ*)prod + (size_t)n + W + (small ? 64 * (size_t)n_cols : 0);
+    k_vc_reduce<<<n_cols, 256, 0, st>>>((const JacQ*)prod, (const JacQ*)icommit, cell_start, (JacQ*)out, tsum, n, n_u, W);
+    k_vc_hmul<<<(n_cols + 15) / 16, 64, 0, st>>>((JacQ*)out, tsum, (const Fr*)h64, n_cols, fq_from_fp(b384));
+    return n_cols;
 }
 }  // namespace launch
 }  // namespace kzg

@@ -193,6 +193,18 @@ void vm_reduce(const void* prod, const void* icommit, const int* cell_start, con
 void vm_fold(const void* sums, const uint32_t* rho, void* prod, void* out2, int n_batches, const Fp12w& beta, hipStream_t st);
 // out[r][2] = the weighted pairs summed over problems ranges[r][0] .. ranges[r][1] - 1 (prod as vm_fold left it)
 void vm_fold_ranges(const void* prod, const int* ranges /*[n_ranges][2], device*/, void* out /*[n_ranges][2] JacQ*/, int n_ranges, hipStream_t st);
+// the column source (eth_kzg_amd_verify_data_columns): problem b = column b, pts = [proofs n | commitments n_u], row[k] < n_u pass-wide.
+// rp_mont[k] / s1[k] = r_b^k (Montgomery / canonical), h64[b] = h_(c_b)^64 canonical (1 for a column without cells)
+void vc_scalars(const void* pow_tables, const int* batch_of, const int* pos_in_batch, const int* cell_idx, const int* cell_start, const void* w8192,
+                void* rp_mont, void* s1, void* h64, int n, int n_cols, hipStream_t st);
+void vc_weights(const void* rp_mont, const int* row, const int* cell_start, void* weights /*[n_cols][n_u]*/, int n_cols, int n_u, hipStream_t st);
+// prod[n + n_cols n_u (+ 64 n_cols, small) + n_cols] JacQ: s1[e] pi_e | w[b][u] C_u | (small) isc[b][j] SRS_j | scratch of vc_sums;
+// small: with the subgroup tests of the n + n_u points (status: 0 -> 0 / 2), as vm_mul_small.  -> products of decoded points launched
+int vc_products(const void* pts, const void* s1, const void* wts, const void* isc, const void* srs, void* prod, int n, int n_u, int n_cols, bool small,
+                int* status, const Fp12w& beta, hipStream_t st);
+// out[2b] = A_b, out[2b + 1] = h64[b] A_b + sum_u w[b][u] C_u + (small ? the 64 terms : icommit[b]); two launches.  -> products launched
+int vc_sums(const void* prod, const void* icommit, const int* cell_start, const void* h64, void* out /*[n_cols][2] JacQ*/, int n, int n_u, int n_cols,
+            bool small, const Fp12w& beta, hipStream_t st);
 
 // k_pairing.hip: verdict[i] = e(pairs[i][0], key0) e(pairs[i][1], key1) == 1 ? 1 : 0, or -1 where a pair still holds the 0xff poison of
 // the result slots; pairs [n][2] JacQ, key0 / key1 68 prepared lines each (192 B), frob the three Frobenius constants (288 B), all in

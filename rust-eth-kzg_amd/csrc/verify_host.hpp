@@ -2,7 +2,7 @@
 // codecs and the Fiat-Shamir transcripts (the reference's four, the leaf-hashed challenge of the cell verifier and the leaves, seed and
 // weights of the point many-verification), each stated ONCE for verify.hip, verify_many.hip, point_many.hip, eip4844.hip and recover.hip.
 // No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp, test_many_leaf.cpp,
-// test_point_many.cpp and test_blob_many.cpp run it on the CPU against hashlib.
+// test_point_many.cpp, test_blob_many.cpp and test_data_columns.cpp run it on the CPU against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -97,6 +97,37 @@ inline int validate_cell_starts(uint64_t n_batches, const uint64_t* cell_starts)
         if (cell_starts[b + 1] < cell_starts[b]) return INPUT_INVALID;
     return INPUT_VALID;
 }
+// ---- eth_kzg_amd_verify_data_columns / _device (c_eth_kzg.h): the columns of one block over ONE commitment list.  Column j is the
+// problem (commitments as given, n_blobs copies of column_indices[j], cells[j], proofs[j]) of the many-verification; there is no new
+// transcript.  What the call refuses as a whole, before the context is touched:
+constexpr uint64_t DATA_COLUMNS_MAX = 1u << 24;
+inline int validate_data_columns_call(uint32_t flags, uint32_t known_flags, uint64_t n_blobs, uint64_t n_columns, bool commitments_null,
+                                      bool indices_null, bool cells_null, bool proofs_null, bool verified_null) {
+    if (flags & ~known_flags) return INPUT_INVALID;
+    if (n_columns > DATA_COLUMNS_MAX) return INPUT_INVALID;
+    if (n_columns == 0) return INPUT_VALID;
+    if (verified_null || indices_null) return INPUT_INVALID;
+    // (a NULL array with a non-zero count, also when the count is beyond the bound and every column will be status 3 unread)
+    if (n_blobs != 0 && (commitments_null || cells_null || proofs_null)) return INPUT_INVALID;
+    return INPUT_VALID;
+}
+// the status of one column at validation: validate_cell_batch of the expanded problem (four equal lengths, n_blobs copies of the index;
+// an empty problem is valid without its index being read)
+inline int validate_data_column(uint64_t n_blobs, uint64_t column_index) {
+    if (n_blobs > INPUT_MAX_CELLS) return INPUT_INVALID;
+    if (n_blobs != 0 && column_index >= (uint64_t)N_CELLS) return INPUT_INVALID;
+    return INPUT_VALID;
+}
+// The block's commitments de-duplicated ONCE per call: every column's expanded problem has this same unique list and these same rows
+// (dedup_commitments of n_blobs entries does not look at the column), so every column's transcript and ROOT see exactly it.
+struct ColumnCommitments {
+    std::vector<uint8_t> own;          // (device form) the 48 n_blobs bytes as they came down
+    std::vector<const uint8_t*> uniq;  // first-occurrence order
+    std::vector<int> row;              // per blob: index into uniq
+    void from_list(uint64_t n_blobs, const uint8_t* const* commitments) { dedup_commitments(n_blobs, commitments, uniq, row); }
+    void from_own(uint64_t n_blobs) { dedup_commitments_flat(n_blobs, own.data(), uniq, row); }
+};
+
 // validate_recovery_inputs (recovery.rs:90-146)
 inline int validate_recovery(uint64_t n_cells, uint64_t n_indices, const uint64_t* cell_indices) {
     if (n_indices != n_cells) return INPUT_INVALID;

@@ -24,6 +24,11 @@
 // event, one ROOT per problem on the host threads while the decoding kernels run.  The roots stay on the host on purpose: a lane per
 // problem would serialise n / 2 compressions of a large problem (8192 cells: ~4 k dependent compressions), and the wait for the
 // status words is there anyway.  Everything behind the challenge is the same for all four combinations.
+// A third source, the COLUMNS of one block over one commitment list (eth_kzg_amd_verify_data_columns / _device; engine.hpp:
+// VerifyManyInput::columns): problem b is column b.  The commitments are de-duplicated once per call and decoded once per pass, and
+// because all cells of a column carry one index, the second proof product is one per column, h^64 * A_b, behind the reduction of A_b
+// (k_verify_many.hip: k_vc_*): n + Bc n_u + Bc scalar multiplications where the expanded pass has 2 n + Bc n_u.  Validation, chunks,
+// parts, the short-chain form, the challenges, the fold and the search are the pass's own; the per-column pair is the expanded pass's.
 #include "vm_search.hpp"
 
 namespace kzg {
@@ -31,8 +36,10 @@ namespace kzg {
 namespace {
 using vm::host_threads; using vm::poisoned; using vm::check_pair;  // vm_search.hpp
 struct Problem {  // one verification of the call, after validation
-    std::vector<const uint8_t*> uniq;  // de-duplicated commitments, first-occurrence order (verifier.rs:49-65)
-    std::vector<int> row;              // per cell: index into uniq
+    const uint8_t* const* uniq = nullptr;  // de-duplicated commitments, first-occurrence order (verifier.rs:49-65)
+    const int* row = nullptr;              // per cell: index into uniq
+    std::vector<const uint8_t*> own_uniq;  // where the two live when the problem was de-duplicated alone; the columns of a
+    std::vector<int> own_row;              // column call all refer to the call's one pair (verify_host.hpp: ColumnCommitments)
     int n = 0, m = 0;                  // cells, unique commitments (0, 0 when the problem is skipped)
     uint64_t src0 = 0, mir0 = 0;       // (flat device source) its first entry in the caller's arrays / in the pinned mirror
 };
@@ -43,6 +50,10 @@ struct PassLayout {
     const int n, m, Bc;
     const bool small;
     const bool leaf;  // leaf-hashed challenges: n x 32 digest bytes on the device and, read back, in the pinned slab
+    // the column source: the m unique commitments are the PASS's (every problem's), each problem has its own m weights, there is no
+    // second proof scalar but one h^64 per problem, and the products are n + Bc m, with Bc more slots for the commitment-side sums
+    const bool cols;
+    const size_t wn = cols ? (size_t)Bc * (size_t)m : (size_t)m;  // (every column of a column pass holds cells: Bc m <= n m / n_blobs <= n)
     const int max_ranges = std::min(Bc, 2048);  // probes per level of the search for wrong proofs
     static constexpr size_t JACQ = launch::SIZEOF_JACQ;
     Carve d;  // (members are initialised in the order they stand here)
@@ -62,12 +73,13 @@ struct PassLayout {
                  off_coef = d.take((size_t)n * CELL_LEN * sizeof(Fr)),
                  off_stp = d.take((size_t)(n + m) * 4),  // [proofs n | commitments m]
                  off_ste = d.take((size_t)Bc * 4), off_rp = d.take((size_t)n * sizeof(Fr)), off_s1 = d.take((size_t)n * sizeof(Fr)),
-                 off_s2 = d.take((size_t)n * sizeof(Fr)), off_w = d.take((size_t)m * sizeof(Fr)), off_isc = d.take((size_t)Bc * 64 * sizeof(Fr)),
-                 off_icm = d.take((size_t)Bc * JACQ), off_prod = d.take((size_t)(2 * n + m + (small ? 64 * Bc : 0)) * JACQ),
+                 off_s2 = d.take(cols ? 0 : (size_t)n * sizeof(Fr)), off_h = d.take(cols ? (size_t)Bc * sizeof(Fr) : 0),
+                 off_w = d.take(wn * sizeof(Fr)), off_isc = d.take((size_t)Bc * 64 * sizeof(Fr)), off_icm = d.take((size_t)Bc * JACQ),
+                 off_prod = d.take(((cols ? (size_t)n + wn + (size_t)Bc : 2 * (size_t)n + (size_t)m) + (small ? 64 * (size_t)Bc : 0)) * JACQ),
                  off_out = d.take((size_t)2 * Bc * JACQ), off_fprod = d.take((size_t)2 * Bc * JACQ), off_fold = d.take((size_t)2 * JACQ),
                  off_rng = d.take((size_t)max_ranges * 8), off_rsum = d.take((size_t)2 * max_ranges * JACQ),
                  off_leaf = d.take(leaf ? (size_t)n * 32 : 0), off_verd = d.take((size_t)max_ranges), dev_bytes = d.end;
-    PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_) {}
+    PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_, bool cols_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_), cols(cols_) {}
 };
 
 // The host's side of one pass: problems b0 .. b0 + Bc of the call (`in` is the call's input from b0 on), n cells and m unique
@@ -91,12 +103,15 @@ struct PassHost {
     const JacQ* sums() const { return (const JacQ*)(hb + L.poff_out); }  // the problems' two sums read back
     int* h_status() const { return (int*)(hb + L.poff_st); }  // read-backs: [proofs n | commitments m | cells, per problem]
     const uint64_t* indices_of(int i) const { return in.on_device() ? mirror_i + pr[i].mir0 : in.cell_indices[i]; }
+    uint64_t index_of(int i, int k) const { return in.columns ? in.col_indices[i] : indices_of(i)[k]; }  // of cell k of problem i
 
     // gather the problems into the slab (flat device source: what the host made of them; proofs and cells move inside HBM); stale
     // contents of the persistent slab must fail closed: status words and result slots are poisoned
     void stage() {
         cell_start.assign(L.Bc + 1, 0); row_start.assign(L.Bc + 1, 0);
-        for (int i = 0; i < L.Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[i].n; row_start[i + 1] = row_start[i] + pr[i].m; }
+        for (int i = 0; i < L.Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[i].n; row_start[i + 1] = L.cols ? 0 : row_start[i] + pr[i].m; }
+        if (L.cols)  // the one commitment list of the call, once per pass; rows are pass-wide (row_start is 0 throughout)
+            for (int j = 0; j < L.m; j++) memcpy(hb + L.off_c + (size_t)j * 48, in.col->uniq[j], 48);
         memcpy(hb + L.off_cs, cell_start.data(), (size_t)(L.Bc + 1) * 4);
         memcpy(hb + L.off_rs, row_start.data(), (size_t)(L.Bc + 1) * 4);
         int *h_idx = (int*)(hb + L.off_idx), *h_row = (int*)(hb + L.off_row), *h_bat = (int*)(hb + L.off_bat), *h_pos = (int*)(hb + L.off_pos),
@@ -105,14 +120,13 @@ struct PassHost {
         parallel_for(L.Bc, T, pool, [&](int i) {
             const Problem& p = pr[i];
             const int c0 = cell_start[i], r0 = row_start[i];
-            for (int j = 0; j < p.m; j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
-            const uint64_t* ix = p.n ? indices_of(i) : nullptr;
+            for (int j = 0; j < p.m && !L.cols; j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
             for (int k = 0; k < p.n; k++) {
                 if (gather) {
                     memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, in.proofs[i][k], 48);
                     memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, in.cells[i][k], BYTES_PER_CELL);
                 }
-                h_idx[c0 + k] = (int)ix[k];
+                h_idx[c0 + k] = (int)index_of(i, k);
                 h_row[c0 + k] = r0 + p.row[k];
                 h_bat[c0 + k] = i;
                 h_pos[c0 + k] = k;
@@ -136,13 +150,12 @@ struct PassHost {
             if (L.leaf) {
                 cur = cell_leaf_root(hb + L.poff_leaf, cell_start.data(), (size_t)i, &digests[(size_t)i * 32]);
             } else {
-                CellBatchTranscript t(p.m, p.n, p.uniq.data());
-                const uint64_t* ix = indices_of(i);
+                CellBatchTranscript t(p.m, p.n, p.uniq);
                 if (in.on_device()) {
                     const uint8_t *sc = hb + L.off_cells + (size_t)cell_start[i] * BYTES_PER_CELL, *sp = hb + L.off_p + (size_t)cell_start[i] * 48;
-                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], ix[k], sc + (size_t)k * BYTES_PER_CELL, sp + (size_t)k * 48);
+                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], index_of(i, k), sc + (size_t)k * BYTES_PER_CELL, sp + (size_t)k * 48);
                 } else {
-                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], ix[k], in.cells[i][k], in.proofs[i][k]);
+                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], index_of(i, k), in.cells[i][k], in.proofs[i][k]);
                 }
                 cur = t.finish();
                 memcpy(&digests[(size_t)i * 32], t.digest(), 32);
@@ -155,12 +168,14 @@ struct PassHost {
         const int* h_st = h_status();
         live.assign(L.Bc, 0);
         int n_live = 0;
+        bool shared_bad = false;  // (the column source) a bad commitment of the one list is every column's
+        for (int j = 0; j < L.m && L.cols; j++) shared_bad |= h_st[L.n + j] != 0;
         for (int i = 0; i < L.Bc; i++) {
             const Problem& p = pr[i];
             if (p.n == 0) continue;
             const int c0 = cell_start[i], r0 = row_start[i];
-            int bad = OK;
-            for (int j = 0; j < p.m && !bad; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
+            int bad = shared_bad ? (int)ERR_G1 : (int)OK;
+            for (int j = 0; j < p.m && !bad && !L.cols; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
             for (int k = 0; k < p.n && !bad; k++) if (h_st[c0 + k]) bad = ERR_G1;
             if (!bad && h_st[L.n + L.m + i]) bad = ERR_SCALAR;
             status[i] = bad;
@@ -210,6 +225,61 @@ int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint
 
 int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
     const int B = (int)n_batches;
+    if (in.columns && !in.col_ready) {
+        // ---- the column source, once per call: what no column reads anything for; the ONE de-duplication of the call (the device form
+        // brings the 48 n_blobs commitment bytes down for it, behind what the caller's stream has queued); and the columns refused at
+        // validation taken OUT of the call, so that every column of a pass holds n_blobs cells and the per-(column, commitment) work of
+        // a pass (Bc n_u weights and products) is bounded by its cells -- a refused column costs a status word, as in _many
+        if (in.col_blobs == 0 || in.col_blobs > MAX_CELLS_PER_VERIFICATION) {
+            for (int b = 0; b < B; b++) { status[b] = validate_data_column(in.col_blobs, in.col_indices[b]); verified[b] = status[b] == OK; }
+            return OK;
+        }
+        std::vector<uint64_t> keep;  // the columns that go on, in the caller's order
+        for (int b = 0; b < B; b++) {
+            verified[b] = 0;
+            status[b] = validate_data_column(in.col_blobs, in.col_indices[b]);
+            if (status[b] == OK) keep.push_back((uint64_t)b);
+        }
+        if (keep.empty()) return OK;
+        ColumnCommitments cc;
+        VerifyManyInput go = in;
+        go.col_ready = true;
+        if (!in.col) {
+            if (in.col_device) {
+                try {
+                    HIPCK(hipSetDevice(dev_));
+                    cc.own.resize((size_t)in.col_blobs * 48);
+                    HIPCK(hipStreamSynchronize(in.user_stream));
+                    HIPCK(hipMemcpy(cc.own.data(), in.d_commitments, cc.own.size(), hipMemcpyDeviceToHost));
+                } catch (const std::exception& e) {
+                    set_error(e);
+                    return ERR_DEVICE;
+                }
+                cc.from_own(in.col_blobs);
+            } else {
+                cc.from_list(in.col_blobs, in.col_commitments);
+            }
+            go.col = &cc;
+        }
+        if (keep.size() == (size_t)B) return verify_cell_kzg_proof_batch_many(n_batches, go, verified, status, tap);
+        if (tap) return ERR_INPUT;  // (the hook serves calls whose columns all pass validation: its outputs are indexed by column)
+        const size_t K = keep.size();
+        std::vector<uint64_t> idx(K), src(K);
+        std::vector<const uint8_t* const*> cl(in.col_device ? 0 : K), pf(in.col_device ? 0 : K);
+        for (size_t k = 0; k < K; k++) {
+            idx[k] = in.col_indices[keep[k]];
+            src[k] = in.col_src ? in.col_src[keep[k]] : in.col0 + keep[k];
+            if (!in.col_device) { cl[k] = in.cells[keep[k]]; pf[k] = in.proofs[keep[k]]; }
+        }
+        go.col_indices = idx.data();
+        if (in.col_device) { go.col_src = src.data(); go.col0 = 0; }
+        else { go.cells = cl.data(); go.proofs = pf.data(); }
+        std::vector<int> ver(K), st(K);
+        const int rc = verify_cell_kzg_proof_batch_many((uint64_t)K, go, ver.data(), st.data(), nullptr);
+        if (rc != OK) return rc;
+        for (size_t k = 0; k < K; k++) { verified[keep[k]] = ver[k]; status[keep[k]] = st[k]; }
+        return OK;
+    }
     for (int b = 0; b < B; b++) { verified[b] = 0; status[b] = OK; }
     if (B == 0) return OK;
     // A LARGE call is cut into parts that run as passes of their own on different pass slots at the same time: while one part's
@@ -284,7 +354,10 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
         const uint8_t* mirror_c = nullptr;
         const uint64_t* mirror_i = nullptr;
         std::vector<Problem> pr(B);
-        if (in.on_device()) {
+        if (in.columns) {  // (the commitments came down with the call, the indices are the host's: nothing to mirror)
+            for (int b = 0; b < B; b++) pr[b].src0 = (in.col_src ? in.col_src[b] : in.col0 + (uint64_t)b) * in.col_blobs;
+            if (in.on_device()) order_behind(st, in.user_stream, slot->ordered);
+        } else if (in.on_device()) {
             uint64_t N = 0;
             for (int b = 0; b < B; b++) {
                 pr[b].src0 = in.cell_starts[b];
@@ -316,6 +389,15 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
         parallel_for(B, T, pool, [&](int b) {
             const uint64_t nb = in.cells_of((uint64_t)b);
             Problem& p = pr[b];
+            if (in.columns) {  // (verify_host.hpp: validate_data_column; every column refers to the call's one de-duplication)
+                status[b] = validate_data_column(nb, in.col_indices[b]);
+                if (status[b] != OK) return;
+                if (nb == 0) { verified[b] = 1; return; }
+                p.uniq = in.col->uniq.data(); p.row = in.col->row.data();
+                p.n = (int)nb;
+                p.m = (int)in.col->uniq.size();
+                return;
+            }
             if (in.on_device()) {  // (the four lengths are one by construction: what is left is the bound, checked before an index is read, and the indices)
                 status[b] = validate_cell_batch(nb, nb, nb, nb, mirror_i + p.mir0);
             } else {
@@ -323,10 +405,11 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
             }
             if (status[b] != OK) return;
             if (nb == 0) { verified[b] = 1; return; }  // verifier.rs:90-93
-            if (in.on_device()) dedup_commitments_flat(nb, mirror_c + (size_t)p.mir0 * 48, p.uniq, p.row);
-            else dedup_commitments(nb, in.commitments[b], p.uniq, p.row);
+            if (in.on_device()) dedup_commitments_flat(nb, mirror_c + (size_t)p.mir0 * 48, p.own_uniq, p.own_row);
+            else dedup_commitments(nb, in.commitments[b], p.own_uniq, p.own_row);
+            p.uniq = p.own_uniq.data(); p.row = p.own_row.data();
             p.n = (int)nb;
-            p.m = (int)p.uniq.size();
+            p.m = (int)p.own_uniq.size();
         });
         lap("validation + de-duplication");
         // ---- chunks of problems: at most CHUNK_CELLS cells per pass (the pinned slab and the arena stay bounded)
@@ -336,14 +419,14 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
         for (int b0 = 0; b0 < B;) {
             int b1 = b0, nn = 0, mm = 0;
             while (b1 < B && (b1 == b0 || nn + pr[b1].n <= CHUNK_CELLS)) { nn += pr[b1].n; mm += pr[b1].m; b1++; }
-            const int Bc = b1 - b0, n = nn, m = mm;
+            const int Bc = b1 - b0, n = nn, m = in.columns ? (int)in.col->uniq.size() : mm;  // (columns: the pass's one list)
             if (n == 0) { b0 = b1; continue; }
             // A pass of a few problems (concurrent single calls combined) is a chain of latencies, not work: it takes the SHORT-CHAIN
             // form -- subgroup tests and the interpolation commitments' terms inside the ONE launch of all scalar multiplications
             // (k_vm_mul_small), no fold (its 128-bit multiplication per problem is a 1.4 ms chain; <= 2 T pairing checks are one or
             // two rounds of the host threads) -- decode 0.45 + products 1.7 + sums 0.2 ms of GPU instead of ~6
             const bool small = vm_small_max_ != 0 && Bc <= (vm_small_max_ > 0 ? vm_small_max_ : 2 * T);
-            const PassLayout L(n, m, Bc, small, in.leaf);
+            const PassLayout L(n, m, Bc, small, in.leaf, in.columns);
             grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
             grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
             uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
@@ -418,19 +501,34 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
             HIPCK(hipMemcpyAsync(db + L.off_pow, hb + L.off_pow, L.in2_bytes - L.off_pow, hipMemcpyHostToDevice, st));  // power tables + weights
             // ---- per-problem scalars, weights, interpolation sums; every scalar multiplication; the two sums per problem
             const int *d_cs = (const int*)(db + L.off_cs), *d_rs = (const int*)(db + L.off_rs);
-            launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_w8192_,
-                               db + L.off_rp, db + L.off_s1, db + L.off_s2, n, st);
-            launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), (const int*)(db + L.off_rowb), d_cs, db + L.off_w, m, st);
-            launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
-            if (small) {
-                launch::vm_mul_small(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_isc, d_srs_, db + L.off_prod, n, m, Bc, d_stp, beta_, st);
-                launch::vm_reduce_small(db + L.off_prod, d_cs, d_rs, db + L.off_out, n, m, Bc, st);
-                HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
+            uint64_t muls = 0;
+            if (in.columns) {
+                // the column source: r^k per cell and ONE h^64 per column; n + Bc m products over the one decoded commitment table, then
+                // h^64 A_b as a dependent launch of Bc quads behind the reduction of A_b (k_verify_many.hip: k_vc_*)
+                launch::vc_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_cs, d_w8192_,
+                                   db + L.off_rp, db + L.off_s1, db + L.off_h, n, Bc, st);
+                launch::vc_weights(db + L.off_rp, (const int*)(db + L.off_row), d_cs, db + L.off_w, Bc, m, st);
+                launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
+                muls += (uint64_t)launch::vc_products(d_pts, db + L.off_s1, db + L.off_w, db + L.off_isc, d_srs_, db + L.off_prod, n, m, Bc, small, d_stp, beta_, st);
+                if (!small) launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
+                muls += (uint64_t)launch::vc_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, db + L.off_h, db + L.off_out, n, m, Bc, small, beta_, st);
+                if (small) HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
             } else {
-                launch::vm_mul(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_prod, n, m, beta_, st);
-                // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
-                launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
-                launch::vm_reduce(db + L.off_prod, db + L.off_icm, d_cs, d_rs, db + L.off_out, n, Bc, st);
+                muls = 2 * (uint64_t)n + (uint64_t)m;
+                launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_w8192_,
+                                   db + L.off_rp, db + L.off_s1, db + L.off_s2, n, st);
+                launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), (const int*)(db + L.off_rowb), d_cs, db + L.off_w, m, st);
+                launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
+                if (small) {
+                    launch::vm_mul_small(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_isc, d_srs_, db + L.off_prod, n, m, Bc, d_stp, beta_, st);
+                    launch::vm_reduce_small(db + L.off_prod, d_cs, d_rs, db + L.off_out, n, m, Bc, st);
+                    HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
+                } else {
+                    launch::vm_mul(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_prod, n, m, beta_, st);
+                    // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
+                    launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
+                    launch::vm_reduce(db + L.off_prod, db + L.off_icm, d_cs, d_rs, db + L.off_out, n, Bc, st);
+                }
             }
             if (folded) {
                 launch::vm_fold(db + L.off_out, (const uint32_t*)(db + L.off_rho), db + L.off_fprod, db + L.off_fold, Bc, beta_, st);
@@ -445,6 +543,7 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
                 if (in.leaf) tap->leaves.assign(hb + L.poff_leaf, hb + L.poff_leaf + (size_t)n * 32);
                 tap->passes++;
                 tap->small = small; tap->folded = folded;
+                tap->commitments_decoded = (uint64_t)m; tap->scalar_muls = muls;
                 tap->sums.assign(hb + L.poff_out, hb + L.poff_out + (size_t)2 * Bc * launch::SIZEOF_JACQ);
                 tap->rho.assign((const uint32_t*)(hb + L.off_rho), (const uint32_t*)(hb + L.off_rho) + 4 * (size_t)Bc);
                 if (folded) tap->fold.assign(hb + L.poff_fold, hb + L.poff_fold + (size_t)2 * launch::SIZEOF_JACQ);
