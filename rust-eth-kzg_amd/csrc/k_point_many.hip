@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64, 2) void k_pm_mul(const G1Affine* __restrict__ p
             glv_split_balanced(mul(w, kind == 2 ? z_mont[i] : y_mont[i]), split);
         }
         const G1Affine P = kind == 3 ? *gen : pts[kind == 1 ? n + i : i];
-        r = vm_mul_by_scalar(affq_from_affine(P), split, beta);
+        r = vm_mul_by_scalar(affq_from_affine(P), split, beta, VmLane());
     }
     if (lane >= 4L * n) return;
     if (kind == 0) pairs[2 * (size_t)i] = r;
@@ -119,10 +119,8 @@ void pm_blob_status(const int* point_status, const int* blob_bad, int* status, i
 void pm_mul(const void* pts, const void* gen, const void* z_mont, const void* y_mont, const uint32_t* rho, const int* status, void* pairs, void* terms,
             int n, const Fp12w& beta, hipStream_t st) {
     if (n <= 0) return;
-    Fp b384;
-    for (int i = 0; i < 12; i++) b384.v[i] = beta.v[i];
     k_pm_mul<<<(unsigned)((4L * n + 63) / 64), 64, 0, st>>>((const G1Affine*)pts, (const G1Affine*)gen, (const Fr*)z_mont, (const Fr*)y_mont, rho, status,
-                                                          (JacQ*)pairs, (JacQ*)terms, n, fq_from_fp(b384));
+                                                          (JacQ*)pairs, (JacQ*)terms, n, vm_beta(beta));
 }
 void pm_pairs(const void* terms, void* pairs, int n, hipStream_t st) {
     if (n > 0) k_pm_pairs<<<(n + 63) / 64, 64, 0, st>>>((const JacQ*)terms, (JacQ*)pairs, n);

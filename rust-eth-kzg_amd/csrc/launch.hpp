@@ -175,36 +175,31 @@ void rec_dit_last(int R, const void* T, const void* shift, const Fr8& n_inv, voi
                   const void* w8192, int final_pass, hipStream_t st);
 void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st);
 
-// k_verify_many.hip: many independent verifications in one pass (per-problem scalars, one lane per scalar multiplication)
-void vm_scalars(const void* pow_tables /*[B][24] Fr*/, const int* batch_of, const int* pos_in_batch, const int* cell_idx, const void* w8192,
-                void* rp_mont, void* s1, void* s2, int n, hipStream_t st);
-void vm_weights(const void* rp_mont, const int* row, const int* row_batch, const int* cell_start, void* weights, int m, hipStream_t st);
+// k_verify_many.hip: many independent verifications in one pass (per-problem scalars, one lane or quad per scalar multiplication).
+// pts = [proofs n | commitments m] (G1Affine).  The expanded source has m rows over all problems (row_batch, row_start) and two scalars
+// per proof; the column source (eth_kzg_amd_verify_data_columns: problem b = column b) has ONE list of m commitments, row[k] < m
+// pass-wide, and one h_(c_b)^64 per column.  A launcher tells the column source by the pointer it names as null there.
+// rp_mont[k] / s1[k] = r_b^k (Montgomery / canonical);  s2[k] = r_b^k h_k^64 (null: columns);  h64[b] canonical, 1 for a column
+// without cells (null: expanded)
+void vm_scalars(const void* pow_tables /*[B][24] Fr*/, const int* batch_of, const int* pos_in_batch, const int* cell_idx, const int* cell_start,
+                const void* w8192, void* rp_mont, void* s1, void* s2, void* h64, int n, int n_batches, hipStream_t st);
+// weights[m], or [n_batches][m] for columns (row_batch null)
+void vm_weights(const void* rp_mont, const int* row, const int* row_batch, const int* cell_start, void* weights, int m, int n_batches, hipStream_t st);
 void vm_interp_sum(const void* coef, const void* rp_mont, const int* cell_start, void* out_neg_canon, int n_batches, hipStream_t st);
-// pts = [proofs n | commitments m] (G1Affine); prod[2n + m] JacQ: s1[e] pi_e | s2[e] pi_e | w[j] C_j
-void vm_mul(const void* pts, const void* s1, const void* s2, const void* wts, void* prod, int n, int m, const Fp12w& beta, hipStream_t st);
-// small passes: every scalar multiplication of the pass (incl. the 64 interpolation terms isc[b][j] SRS_j per problem, prod[2n + m + 64 b + j])
-// and the subgroup tests of [proofs n | commitments m] (status: 0 -> 0 / 2) in ONE launch; then the per-problem sums
-void vm_mul_small(const void* pts, const void* s1, const void* s2, const void* wts, const void* isc, const void* srs, void* prod, int n, int m,
-                  int n_batches, int* status, const Fp12w& beta, hipStream_t st);
-void vm_reduce_small(const void* prod, const int* cell_start, const int* row_start, void* out, int n, int m, int n_batches, hipStream_t st);
-void vm_reduce(const void* prod, const void* icommit, const int* cell_start, const int* row_start, void* out /*[B][2] JacQ*/, int n,
-               int n_batches, hipStream_t st);
+// every scalar multiplication of the pass in ONE launch.  prod (JacQ): s1[e] pi_e n | s2[e] pi_e n | w[j] C_j m, or for columns (s2 null)
+// s1[e] pi_e n | w[b][u] C_u n_batches m;  small (short-chain passes): behind them the 64 interpolation terms isc[b][j] SRS_j per
+// problem, and the launch also holds the subgroup tests of the n + m points (status: 0 -> 0 / 2).  -> products of decoded points
+int vm_products(const void* pts, const void* s1, const void* s2, const void* wts, const void* isc, const void* srs, void* prod, int n, int m,
+                int n_batches, bool small, int* status, const Fp12w& beta, hipStream_t st);
+// out[b][2] JacQ: the two sums of problem b's products + (icommit ? icommit[b] : its 64 interpolation terms).  Columns (row_start null):
+// out[2b + 1] = h64[b] out[2b] + the rest, a second launch of n_batches products behind the reduction (prod holds n_batches more
+// JacQ behind the products).  -> products launched
+int vm_sums(const void* prod, const void* icommit, const int* cell_start, const int* row_start, const void* h64, void* out /*[B][2] JacQ*/, int n,
+            int m, int n_batches, const Fp12w& beta, hipStream_t st);
 // out2[j] = sum_b rho_b sums[b][j] (rho: 4 words per problem, 0 excludes it); prod: scratch of 2 B JacQ
 void vm_fold(const void* sums, const uint32_t* rho, void* prod, void* out2, int n_batches, const Fp12w& beta, hipStream_t st);
 // out[r][2] = the weighted pairs summed over problems ranges[r][0] .. ranges[r][1] - 1 (prod as vm_fold left it)
 void vm_fold_ranges(const void* prod, const int* ranges /*[n_ranges][2], device*/, void* out /*[n_ranges][2] JacQ*/, int n_ranges, hipStream_t st);
-// the column source (eth_kzg_amd_verify_data_columns): problem b = column b, pts = [proofs n | commitments n_u], row[k] < n_u pass-wide.
-// rp_mont[k] / s1[k] = r_b^k (Montgomery / canonical), h64[b] = h_(c_b)^64 canonical (1 for a column without cells)
-void vc_scalars(const void* pow_tables, const int* batch_of, const int* pos_in_batch, const int* cell_idx, const int* cell_start, const void* w8192,
-                void* rp_mont, void* s1, void* h64, int n, int n_cols, hipStream_t st);
-void vc_weights(const void* rp_mont, const int* row, const int* cell_start, void* weights /*[n_cols][n_u]*/, int n_cols, int n_u, hipStream_t st);
-// prod[n + n_cols n_u (+ 64 n_cols, small) + n_cols] JacQ: s1[e] pi_e | w[b][u] C_u | (small) isc[b][j] SRS_j | scratch of vc_sums;
-// small: with the subgroup tests of the n + n_u points (status: 0 -> 0 / 2), as vm_mul_small.  -> products of decoded points launched
-int vc_products(const void* pts, const void* s1, const void* wts, const void* isc, const void* srs, void* prod, int n, int n_u, int n_cols, bool small,
-                int* status, const Fp12w& beta, hipStream_t st);
-// out[2b] = A_b, out[2b + 1] = h64[b] A_b + sum_u w[b][u] C_u + (small ? the 64 terms : icommit[b]); two launches.  -> products launched
-int vc_sums(const void* prod, const void* icommit, const int* cell_start, const void* h64, void* out /*[n_cols][2] JacQ*/, int n, int n_u, int n_cols,
-            bool small, const Fp12w& beta, hipStream_t st);
 
 // k_pairing.hip: verdict[i] = e(pairs[i][0], key0) e(pairs[i][1], key1) == 1 ? 1 : 0, or -1 where a pair still holds the 0xff poison of
 // the result slots; pairs [n][2] JacQ, key0 / key1 68 prepared lines each (192 B), frob the three Frobenius constants (288 B), all in

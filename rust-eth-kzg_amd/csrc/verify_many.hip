@@ -423,7 +423,7 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
             if (n == 0) { b0 = b1; continue; }
             // A pass of a few problems (concurrent single calls combined) is a chain of latencies, not work: it takes the SHORT-CHAIN
             // form -- subgroup tests and the interpolation commitments' terms inside the ONE launch of all scalar multiplications
-            // (k_vm_mul_small), no fold (its 128-bit multiplication per problem is a 1.4 ms chain; <= 2 T pairing checks are one or
+            // (k_vm_products), no fold (its 128-bit multiplication per problem is a 1.4 ms chain; <= 2 T pairing checks are one or
             // two rounds of the host threads) -- decode 0.45 + products 1.7 + sums 0.2 ms of GPU instead of ~6
             const bool small = vm_small_max_ != 0 && Bc <= (vm_small_max_ > 0 ? vm_small_max_ : 2 * T);
             const PassLayout L(n, m, Bc, small, in.leaf, in.columns);
@@ -483,7 +483,7 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
             G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
             int* d_stp = (int*)(db + L.off_stp);
             launch::g1_decode2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, m, beta_, st);
-            if (!small) launch::g1_subgroup2(d_pts, d_stp, n, d_pts + n, d_stp + n, m, beta_, st);  // (small: inside k_vm_mul_small)
+            if (!small) launch::g1_subgroup2(d_pts, d_stp, n, d_pts + n, d_stp + n, m, beta_, st);  // (small: inside k_vm_products)
             launch::cells_to_fr(db + L.off_cells, db + L.off_evals, nullptr, (int*)(db + L.off_ste), (const int*)(db + L.off_bat), nullptr, n, st);
             launch::interp_cells(db + L.off_evals, (const int*)(db + L.off_idx), d_w8192_, inv64_, db + L.off_coef, n, st);
             HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
@@ -501,35 +501,21 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
             HIPCK(hipMemcpyAsync(db + L.off_pow, hb + L.off_pow, L.in2_bytes - L.off_pow, hipMemcpyHostToDevice, st));  // power tables + weights
             // ---- per-problem scalars, weights, interpolation sums; every scalar multiplication; the two sums per problem
             const int *d_cs = (const int*)(db + L.off_cs), *d_rs = (const int*)(db + L.off_rs);
-            uint64_t muls = 0;
-            if (in.columns) {
-                // the column source: r^k per cell and ONE h^64 per column; n + Bc m products over the one decoded commitment table, then
-                // h^64 A_b as a dependent launch of Bc quads behind the reduction of A_b (k_verify_many.hip: k_vc_*)
-                launch::vc_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_cs, d_w8192_,
-                                   db + L.off_rp, db + L.off_s1, db + L.off_h, n, Bc, st);
-                launch::vc_weights(db + L.off_rp, (const int*)(db + L.off_row), d_cs, db + L.off_w, Bc, m, st);
-                launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
-                muls += (uint64_t)launch::vc_products(d_pts, db + L.off_s1, db + L.off_w, db + L.off_isc, d_srs_, db + L.off_prod, n, m, Bc, small, d_stp, beta_, st);
-                if (!small) launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
-                muls += (uint64_t)launch::vc_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, db + L.off_h, db + L.off_out, n, m, Bc, small, beta_, st);
-                if (small) HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
-            } else {
-                muls = 2 * (uint64_t)n + (uint64_t)m;
-                launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_w8192_,
-                                   db + L.off_rp, db + L.off_s1, db + L.off_s2, n, st);
-                launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), (const int*)(db + L.off_rowb), d_cs, db + L.off_w, m, st);
-                launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
-                if (small) {
-                    launch::vm_mul_small(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_isc, d_srs_, db + L.off_prod, n, m, Bc, d_stp, beta_, st);
-                    launch::vm_reduce_small(db + L.off_prod, d_cs, d_rs, db + L.off_out, n, m, Bc, st);
-                    HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
-                } else {
-                    launch::vm_mul(d_pts, db + L.off_s1, db + L.off_s2, db + L.off_w, db + L.off_prod, n, m, beta_, st);
-                    // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
-                    launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
-                    launch::vm_reduce(db + L.off_prod, db + L.off_icm, d_cs, d_rs, db + L.off_out, n, Bc, st);
-                }
-            }
+            // one sequence for both sources (launch.hpp: a null pointer tells a launcher which).  The column source has r^k per cell and ONE
+            // h^64 per column: n + Bc m products over the one decoded commitment table, then h^64 A_b as a dependent launch of Bc quads
+            // behind the reduction of A_b, inside vm_sums
+            const bool cols = in.columns;
+            launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_cs, d_w8192_,
+                               db + L.off_rp, db + L.off_s1, cols ? nullptr : db + L.off_s2, cols ? db + L.off_h : nullptr, n, Bc, st);
+            launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), cols ? nullptr : (const int*)(db + L.off_rowb), d_cs, db + L.off_w, m, Bc, st);
+            launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
+            uint64_t muls = (uint64_t)launch::vm_products(d_pts, db + L.off_s1, cols ? nullptr : db + L.off_s2, db + L.off_w, db + L.off_isc, d_srs_,
+                                                          db + L.off_prod, n, m, Bc, small, d_stp, beta_, st);
+            // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
+            if (!small) launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
+            muls += (uint64_t)launch::vm_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, cols ? nullptr : d_rs, db + L.off_h, db + L.off_out,
+                                              n, m, Bc, beta_, st);
+            if (small) HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
             if (folded) {
                 launch::vm_fold(db + L.off_out, (const uint32_t*)(db + L.off_rho), db + L.off_fprod, db + L.off_fold, Bc, beta_, st);
                 HIPCK(hipMemcpyAsync(hb + L.poff_fold, db + L.off_fold, (size_t)2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));

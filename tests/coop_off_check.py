@@ -2,7 +2,7 @@
 the one-lane-per-point forms of the verification kernels -- which small inputs no longer reach by default -- on the
 single path, a small many-verification pass and the EIP-4844 verifier, valid, tampered and with the small-order points of
 tests/small_order.py planted as proof and as commitment, then every off-subgroup case and the identity in ONE short-chain pass
-(k_vm_mul_small's one-lane subgroup blocks; the form is asserted); and the prover's G1 stage with a lane per
+(k_vm_products<VmLane>'s one-lane subgroup blocks; the form is asserted); and the prover's G1 stage with a lane per
 blob where twelve blobs would take four (eth_kzg_amd_test_proofs_from_sums on the planned degenerate lanes of tests/linmap_model.py)."""
 import importlib, os, sys
 import numpy as np
@@ -81,7 +81,7 @@ def main():
                 except kzg.KzgError as e:
                     assert "CouldNotDeserializeG1Point" in str(e), (case.name, role, e)
     assert ctx.verify_cell_kzg_proof_batch(*probs[0]) is True
-    # k_vm_mul_small's one-lane subgroup blocks on EVERY off-subgroup case, the identity and valid controls in one pass
+    # k_vm_products<VmLane>'s one-lane subgroup blocks on EVERY off-subgroup case, the identity and valid controls in one pass
     # (small_order.many_plan): a context with eight helper threads, so that twelve problems are a short-chain pass on any machine
     from many_coop_off_check import many_sums
     os.environ["ETH_KZG_AMD_HOST_THREADS"] = "8"

@@ -1,7 +1,10 @@
 """The hook eth_kzg_amd_test_verify_many_sums from Python (tests/test_verify_inputs.py imports many_sums), and, run as a program in a process
 of its own with ETH_KZG_AMD_COOP_POINTS=0 (the limit is read once per process) and ETH_KZG_AMD_HOST_THREADS=2: the many-verification
-without the four-lane kernels -- k_vm_mul_small with its one-lane subgroup blocks in a short-chain pass, k_vm_fold_mul in a folded one --
-compared with the bytes the parent computed.  stdin: JSON {"seed", "passes": {name: {"sums": [hex or null], "fold": hex or null}}}."""
+without the four-lane kernels -- k_vm_products<VmLane> with its one-lane subgroup blocks in a short-chain pass, k_vm_fold_mul<VmLane> in a
+folded one, from both sources: the expanded problems and the columns of a block (nothing else gives the column source's short-chain
+map to the one-lane instantiation) -- compared with the bytes the parent computed with the four-lane kernels on.
+stdin: JSON {"seed", "passes": {name: {"sums": [hex or null], "fold": hex or null}},
+             "columns": {name: {"picks", "indices", "form": [small, folded], "status", "verified", "sums": [hex], "fold": hex}}}."""
 import ctypes as C
 import importlib
 import json
@@ -61,6 +64,18 @@ def main():
         if p.folded:
             assert got.fold.hex() == exp["fold"] and got.fold_verdict == 1, (name, "the folded pair")
         assert ctx.verify_cell_kzg_proof_batch_many(problems) == (got.verified, got.status), name
+    import data_columns as D
+    from test_gpu_data_columns import column_sums  # the column tap hook, as that file calls it
+    for name, exp in want["columns"].items():
+        call = D.block(comms, cells, proofs, exp["picks"], exp["indices"])
+        rc, got = column_sums(ctx, call, "host", 0)
+        assert rc == 0, (name, rc)
+        assert [got.small, got.folded] == exp["form"] and (not got.folded or got.fold_verdict == 1), (name, got.small, got.folded, got.fold_verdict)
+        assert (got.status, got.verified) == (exp["status"], exp["verified"]), (name, got.status, got.verified)
+        assert [s.hex() for s in got.sums] == exp["sums"] and got.fold.hex() == exp["fold"], (name, "differs from the four-lane kernels")
+        rc, same = many_sums(ctx, D.expand(*call))  # column j IS problem j of the expanded input
+        assert rc == 0 and (same.small, same.folded, same.status, same.verified) == (got.small, got.folded, got.status, got.verified), name
+        assert same.sums == got.sums and same.fold == got.fold, (name, "differs from the expanded pass")
     ctx.close()
     print("many coop-off ok")
 

@@ -14,14 +14,14 @@ eth_kzg_amd_test_g1_decode hands out the status words AND the decoded affine coo
   k_pip_shift_subgroup_coop (quad branch)                form 4, 2 N <= M:      test_every_form_..., test_lane_and_segment_edges;
                                                          verify_cell_kzg_proof_batch in test_public_single_routes
   k_pip_shift_subgroup (one-lane branch)                 form 4, 2 N > M:       test_one_lane_kernels_past_the_limit; tests/coop_off_check.py
-  k_vm_mul_small_coop (subgroup blocks)                  test_many_verification_with_every_off_subgroup_point[small],
+  k_vm_products<VmQuad> (subgroup blocks)                test_many_verification_with_every_off_subgroup_point[small],
                                                          test_many_verification_with_a_planted_point[small]
-  k_vm_mul_small (one-lane subgroup blocks)              tests/coop_off_check.py (ETH_KZG_AMD_COOP_POINTS=0, run by tests/test_gpu_parity.py):
+  k_vm_products<VmLane> (one-lane subgroup blocks)       tests/coop_off_check.py (ETH_KZG_AMD_COOP_POINTS=0, run by tests/test_gpu_parity.py):
                                                          the same pass, asserted to be short-chain
   the decoder without the test (k_g1_decompress, check 0): form 0 and the decode of forms 3 and 4 -- every boundary-y and encoding-edge point
 
 The six forms behind the hook are given all of small_order.g1_cases(): every +-S_l, the composite-order points, [k]G + S_l, the identity,
-the valid controls, every boundary-y point in both sign encodings and every encoding edge.  The two k_vm_mul_small forms take their points
+the valid controls, every boundary-y point in both sign encodings and every encoding edge.  The two k_vm_products forms take their points
 from a many-verification's problems: small_order.many_plan gives one pass every +-S_l, both composite-order points and every [k]G + S_l,
 each as a proof and as a commitment, the identity and valid problems; the boundary-y points and the encoding edges are the decoders' matter (the
 hook's forms) and are not planted in a many-verification.
@@ -293,8 +293,8 @@ def test_many_verification_with_a_planted_point(material, form):
 def test_many_verification_with_every_off_subgroup_point(material, oracle, form):
     """One pass whose proof and commitment slots hold every +-S_l, both composite-order points and every [k]G + S_l (each once as a proof
     and once as a commitment, spread over six problems), the identity (a whole valid problem of it, and in the place of one proof) and
-    valid controls: small_order.many_plan.  In the short-chain form these are the inputs of k_vm_mul_small_coop's subgroup blocks
-    (tests/coop_off_check.py gives the same pass to k_vm_mul_small).  Status and verdict of every problem are the plan's; the
+    valid controls: small_order.many_plan.  In the short-chain form these are the inputs of k_vm_products<VmQuad>'s subgroup blocks
+    (tests/coop_off_check.py gives the same pass to k_vm_products<VmLane>).  Status and verdict of every problem are the plan's; the
     well-formed problems' verdicts are the oracle's; the pairs of sums of the problems next to the refused ones do not change."""
     c = _ctx(ETH_KZG_AMD_HOST_THREADS="8" if form == "small" else "2")
     try:

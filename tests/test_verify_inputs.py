@@ -515,9 +515,13 @@ def test_the_hook_serves_one_pass_only(many_ctx, gpu_material):
 
 
 @pytest.mark.gpu
-def test_many_passes_with_the_four_lane_kernels_switched_off(gpu_material):
-    """ETH_KZG_AMD_COOP_POINTS is read once per process: a child process runs the first short-chain pass (k_vm_mul_small, the one-lane
-    subgroup blocks) and a folded pass of ten problems (k_vm_fold_mul) and compares the same bytes (tests/many_coop_off_check.py)."""
+def test_many_passes_with_the_four_lane_kernels_switched_off(many_ctx, gpu_material):
+    """ETH_KZG_AMD_COOP_POINTS is read once per process: a child process runs the first short-chain pass (k_vm_products<VmLane>, the one-lane
+    subgroup blocks) and a folded pass of ten problems (k_vm_fold_mul<VmLane>) and compares the same bytes (tests/many_coop_off_check.py).
+    The same for the column source: a short-chain pass of 3 columns x 2 blobs and a folded one of 6 columns x 2 blobs whose blobs are one
+    blob twice (n_u = 1 < n_blobs), through the column tap hook, against this process's bytes with the four-lane kernels on."""
+    import data_columns as D
+    from test_gpu_data_columns import column_sums
     mat, fp = gpu_material
     want = {"seed": T.SEED, "passes": {}}
     for name in ("short-four-lanes", "folded-ten"):
@@ -525,6 +529,13 @@ def test_many_passes_with_the_four_lane_kernels_switched_off(gpu_material):
         p.check(T.MANY_HOST_THREADS, COOP_POINTS_MAX)
         sums, _, fold = _pass_statement(mat, fp, p)
         want["passes"][name] = {"sums": [s.hex() if s else None for s in sums], "fold": fold.hex() if fold else None}
+    want["columns"] = {}
+    for name, picks, indices, form in (("3x2-short-chain", [0, 1], [127, 64, 1], [True, False]),
+                                       ("6x2-folded-one-blob-twice", [0, 0], [127, 64, 1, 0, 5, 3], [False, True])):
+        rc, got = column_sums(many_ctx, D.block(mat.commitments, mat.cells, mat.proofs, picks, indices), "host", 0)
+        assert rc == 0 and [got.small, got.folded] == form and got.status == [0] * len(indices) and got.verified == [True] * len(indices), (name, rc)
+        want["columns"][name] = {"picks": picks, "indices": indices, "form": form, "status": got.status, "verified": got.verified,
+                                 "sums": [s.hex() for s in got.sums], "fold": got.fold.hex()}
     env = dict(os.environ, ETH_KZG_AMD_COOP_POINTS="0", ETH_KZG_AMD_HOST_THREADS=str(T.MANY_HOST_THREADS), ETH_KZG_AMD_TABLE_GB="3")
     t0 = time.perf_counter()
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "many_coop_off_check.py")], env=env,

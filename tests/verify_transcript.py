@@ -455,7 +455,7 @@ class ManyPass:
         assert self.searched == (self.folded and not all(q.verdict for q in self.problems if q.live)), self.name
         assert self.problems[0].kind not in ("empty", "bad-index"), self.name                 # problem 0 holds cells: later positions are > 0
         e = self.expect
-        if "one_lane" in e:  # k_vm_mul_small_coop up to 2 * coop_points_max() products and subgroup tests, k_vm_mul_small above
+        if "one_lane" in e:  # k_vm_products<VmQuad> up to 2 * coop_points_max() products and subgroup tests, k_vm_products<VmLane> above
             assert self.small and e["one_lane"] == (3 * n + 2 * m + 64 * B > 2 * coop_points_max), (self.name, n, m, B)
         if "kinds" in e:
             assert sorted(q.kind for q in self.problems) == sorted(e["kinds"]), self.name
@@ -505,13 +505,13 @@ LARGE_ORDER = ["len-2", "len-63", "len-1", "len-64", "len-65", "len-255", "len-2
                "all-128-indices", "constant-polynomial", "one-index", "cells-of-r-minus-1", "identity-commitment-only"]
 
 # pass -> kernels of csrc/k_verify_many.hip it reaches (k_vm_scalars, k_vm_weights and k_vm_interp_sum run in every pass)
-#   short-four-lanes    k_vm_mul_small_coop (products, the 64 interpolation terms per problem, subgroup blocks), k_vm_reduce_small
+#   short-four-lanes    k_vm_products<VmQuad> (products, the 64 interpolation terms per problem, subgroup blocks), k_vm_reduce without icommit
 #   short-holes         the same with an empty problem, a refused one and zero cells between exact neighbours
-#   short-one-lane      k_vm_mul_small (3 n + 2 m + 64 B > 2 coop_points_max()), k_vm_reduce_small's 128-stride loops, table entries 0 .. 13
-#   large-folded        k_vm_mul, the commitment window table's MSM, k_vm_reduce, k_vm_fold_mul_coop, k_vm_fold_sum (B < 128)
-#   large-one-live      k_vm_mul, k_vm_reduce; no fold below two live problems
+#   short-one-lane      k_vm_products<VmLane> (3 n + 2 m + 64 B > 2 coop_points_max()), k_vm_reduce's 128-stride loops, table entries 0 .. 13
+#   large-folded        k_vm_products<VmLane>, the commitment window table's MSM, k_vm_reduce, k_vm_fold_mul<VmQuad>, k_vm_fold_sum (B < 128)
+#   large-one-live      k_vm_products<VmLane>, k_vm_reduce; no fold below two live problems
 #   search              k_vm_fold_sum's stride loop (B > 128), k_vm_fold_ranges at widths above and below 128
-#   folded-ten          with the four-lane kernels switched off (a process of its own): k_vm_fold_mul; short-four-lanes there: k_vm_mul_small
+#   folded-ten          with the four-lane kernels switched off (a process of its own): k_vm_fold_mul<VmLane>; short-four-lanes there: k_vm_products<VmLane>
 #                       and the one-lane subgroup blocks
 
 
