@@ -136,19 +136,21 @@ CResult sliced_call(const DASContext* ctx, uint64_t n, uint64_t max_n, bool* ver
         return err(std::string("DeviceError(") + ex.what() + ")");
     }
 }
-// verify_cell_kzg_proof_batch_many on pointer lists, with either challenge: by PROBLEM over the device list -- problems are independent
-// (each has its own Fiat-Shamir transcript); own lock, stream and scratch inside (verify_many.hip): no lane needed
-CResult cell_many(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths, const uint8_t* const* const* commitments,
-                  const uint64_t* cell_indices_lengths, const uint64_t* const* cell_indices, const uint64_t* cells_lengths,
-                  const uint8_t* const* const* cells, const uint64_t* proofs_lengths, const uint8_t* const* const* proofs, bool leaf,
-                  bool* verified, int32_t* status) {
-    kzg::VerifyManyInput in;
-    in.n_commitments = commitments_lengths; in.n_indices = cell_indices_lengths; in.n_cells = cells_lengths; in.n_proofs = proofs_lengths;
-    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
-    in.leaf = leaf;
-    return sliced_call(ctx, n_batches, MAX_BATCH, verified, status, [] { return true; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+// verify_cell_kzg_proof_batch_many on a host source: by PROBLEM over the device list (each has its own transcript); no lane needed
+CResult host_many(const DASContext* ctx, uint64_t n, uint64_t max_n, const kzg::VerifyManyInput& in, bool* verified, int32_t* status) {
+    return sliced_call(ctx, n, max_n, verified, status, [] { return true; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
         return many_failure(e, e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver + lo, st + lo));
     });
+}
+// the same on a device source: on the one engine that owns the caller's buffers
+CResult device_many(kzg::Engine* e, uint64_t n, const kzg::VerifyManyInput& in, bool* verified, int32_t* status) {
+    try {
+        std::vector<int> ver(n), st(n);
+        if (e->verify_cell_kzg_proof_batch_many(n, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
+        return verdicts_out(n, ver.data(), st.data(), verified, status);
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
 }
 
 void free_ctx(DASContext* c) {
@@ -363,8 +365,8 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many(const DASContext* ctx, uint
                                                      const uint64_t* const* cell_indices, const uint64_t* cells_lengths,
                                                      const uint8_t* const* const* cells, const uint64_t* proofs_lengths,
                                                      const uint8_t* const* const* proofs, bool* verified, int32_t* status) {
-    return cell_many(ctx, n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells, proofs_lengths, proofs,
-                     /*leaf=*/false, verified, status);  // (the count is checked before the context is looked at: sliced_call)
+    return host_many(ctx, n_batches, MAX_BATCH, kzg::VerifyManyInput::lists(commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths,
+                     cells, proofs_lengths, proofs, /*leaf=*/false), verified, status);  // (the count is checked before the context is looked at: sliced_call)
 }
 
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_device(const DASContext* ctx, uint64_t n, const uint8_t* d_commitments,
@@ -427,8 +429,8 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex(const DASContext* ctx, u
                                                         const uint8_t* const* const* cells, const uint64_t* proofs_lengths,
                                                         const uint8_t* const* const* proofs, uint32_t flags, bool* verified, int32_t* status) {
     if (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT) return err("InvalidInput: unknown verification flags");
-    return cell_many(ctx, n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells, proofs_lengths, proofs,
-                     /*leaf=*/flags != 0, verified, status);
+    return host_many(ctx, n_batches, MAX_BATCH, kzg::VerifyManyInput::lists(commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths,
+                     cells, proofs_lengths, proofs, /*leaf=*/flags != 0), verified, status);
 }
 CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext* ctx, uint64_t n_batches, const uint64_t* cell_starts,
                                                                const uint8_t* d_commitments, const uint64_t* d_cell_indices, const uint8_t* d_cells,
@@ -446,17 +448,8 @@ CResult eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex(const DASContext*
         e = engine_of_device_pointers(ctx, ptrs, 4);
         if (!e) return err("InvalidInput: the four buffers are not device memory of one device of this context");
     }
-    try {
-        std::vector<int> ver(n_batches), st(n_batches);
-        kzg::VerifyManyInput in;
-        in.cell_starts = cell_starts; in.d_commitments = d_commitments; in.d_cell_indices = d_cell_indices; in.d_cells = d_cells; in.d_proofs = d_proofs;
-        in.user_stream = (hipStream_t)hip_stream;
-        in.leaf = flags != 0;
-        if (e->verify_cell_kzg_proof_batch_many(n_batches, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
-        return verdicts_out(n_batches, ver.data(), st.data(), verified, status);
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return device_many(e, n_batches, kzg::VerifyManyInput::flat_device(cell_starts, d_commitments, d_cell_indices, d_cells, d_proofs, (hipStream_t)hip_stream,
+                                                                       flags != 0), verified, status);
 }
 
 // The columns of one block over ONE commitment list (c_eth_kzg.h): the many-verification's column source (verify_many.hip).  Flags,
@@ -470,16 +463,12 @@ CResult eth_kzg_amd_verify_data_columns(const DASContext* ctx, uint64_t n_blobs,
                                         !verified) != kzg::INPUT_VALID)
         return err("InvalidInput: unknown verification flags, more than 2^24 columns, or a null array");
     kzg::ColumnCommitments cc;
-    kzg::VerifyManyInput in;
-    in.columns = true; in.col_blobs = n_blobs; in.col_commitments = commitments; in.col_indices = column_indices; in.cells = cells; in.proofs = proofs;
-    in.leaf = flags != 0;
+    auto in = kzg::VerifyManyInput::host_columns(n_blobs, commitments, column_indices, cells, proofs, flags != 0);
     if (n_columns && n_blobs && n_blobs <= kzg::MAX_CELLS_PER_VERIFICATION) {
         cc.from_list(n_blobs, commitments);
         in.col = &cc;
     }
-    return sliced_call(ctx, n_columns, kzg::DATA_COLUMNS_MAX, verified, status, [] { return true; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
-        return many_failure(e, e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver + lo, st + lo));
-    });
+    return host_many(ctx, n_columns, kzg::DATA_COLUMNS_MAX, in, verified, status);
 }
 CResult eth_kzg_amd_verify_data_columns_device(const DASContext* ctx, uint64_t n_blobs, const uint8_t* d_commitments, uint64_t n_columns,
                                                const uint64_t* column_indices, const uint8_t* d_cells, const uint8_t* d_proofs, uint32_t flags,
@@ -495,18 +484,8 @@ CResult eth_kzg_amd_verify_data_columns_device(const DASContext* ctx, uint64_t n
         e = engine_of_device_pointers(ctx, ptrs, 3);
         if (!e) return err("InvalidInput: the three buffers are not device memory of one device of this context");
     }
-    try {
-        std::vector<int> ver(n_columns), st(n_columns);
-        kzg::VerifyManyInput in;
-        in.columns = in.col_device = true;
-        in.col_blobs = n_blobs; in.col_indices = column_indices; in.d_commitments = d_commitments; in.d_cells = d_cells; in.d_proofs = d_proofs;
-        in.user_stream = (hipStream_t)hip_stream;
-        in.leaf = flags != 0;
-        if (e->verify_cell_kzg_proof_batch_many(n_columns, in, ver.data(), st.data()) == kzg::ERR_DEVICE) return device_err(e);
-        return verdicts_out(n_columns, ver.data(), st.data(), verified, status);
-    } catch (const std::exception& ex) {
-        return err(std::string("DeviceError(") + ex.what() + ")");
-    }
+    return device_many(e, n_columns, kzg::VerifyManyInput::device_columns(n_blobs, d_commitments, column_indices, d_cells, d_proofs, (hipStream_t)hip_stream,
+                                                                          flags != 0), verified, status);
 }
 
 CResult eth_kzg_amd_recover_cells_and_proofs_device(const DASContext* ctx, uint64_t n, const uint8_t* d_cells,

@@ -108,9 +108,10 @@ int eth_kzg_amd_test_verify_many_sums(const DASContext* ctx, uint64_t n_batches,
     if (!commitments_lengths || !commitments || !cell_indices_lengths || !cell_indices || !cells_lengths || !cells || !proofs_lengths || !proofs ||
         !verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || (max_probes && (!probe_ranges || !probe_sums96)))
         return kzg::ERR_INPUT;
-    return eng(ctx)->test_verify_many_sums(n_batches, commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells,
-                                           proofs_lengths, proofs, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes,
-                                           n_probes);
+    const auto in = kzg::VerifyManyInput::lists(commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells, proofs_lengths,
+                                                proofs, /*leaf=*/false);
+    return eng(ctx)->test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
+                                              nullptr, nullptr);
 }
 // the same pass over either source and with either challenge
 int eth_kzg_amd_test_verify_many_sums_ex(const DASContext* ctx, uint64_t n_batches, const uint64_t* commitments_lengths,
@@ -123,10 +124,8 @@ int eth_kzg_amd_test_verify_many_sums_ex(const DASContext* ctx, uint64_t n_batch
         !verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || !digests32 || (max_probes && (!probe_ranges || !probe_sums96)) ||
         (flags & ~ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT))
         return kzg::ERR_INPUT;
-    kzg::VerifyManyInput in;
-    in.n_commitments = commitments_lengths; in.n_indices = cell_indices_lengths; in.n_cells = cells_lengths; in.n_proofs = proofs_lengths;
-    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
-    in.leaf = flags != 0;
+    const auto in = kzg::VerifyManyInput::lists(commitments_lengths, commitments, cell_indices_lengths, cell_indices, cells_lengths, cells, proofs_lengths,
+                                                proofs, flags != 0);
     return eng(ctx)->test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
                                               digests32, leaves32);
 }
@@ -140,9 +139,7 @@ int eth_kzg_amd_test_verify_many_sums_device(const DASContext* ctx, uint64_t n_b
         kzg::validate_cell_starts(n_batches, cell_starts) != kzg::INPUT_VALID)
         return kzg::ERR_INPUT;
     if (cell_starts[n_batches] && (!d_commitments || !d_cell_indices || !d_cells || !d_proofs)) return kzg::ERR_INPUT;
-    kzg::VerifyManyInput in;
-    in.cell_starts = cell_starts; in.d_commitments = d_commitments; in.d_cell_indices = d_cell_indices; in.d_cells = d_cells; in.d_proofs = d_proofs;
-    in.leaf = flags != 0;
+    const auto in = kzg::VerifyManyInput::flat_device(cell_starts, d_commitments, d_cell_indices, d_cells, d_proofs, nullptr, flags != 0);
     return eng(ctx)->test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
                                               digests32, leaves32);
 }
@@ -157,15 +154,10 @@ int eth_kzg_amd_test_verify_data_columns_sums(const DASContext* ctx, uint64_t n_
         kzg::validate_data_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !commitments, !column_indices, !cells, !proofs, false) !=
             kzg::INPUT_VALID)
         return kzg::ERR_INPUT;
-    kzg::VerifyManyInput in;
-    in.columns = true; in.col_device = on_device != 0;
-    in.col_blobs = n_blobs; in.col_indices = column_indices;
-    if (on_device) {
-        in.d_commitments = (const uint8_t*)commitments; in.d_cells = (const uint8_t*)cells; in.d_proofs = (const uint8_t*)proofs;
-    } else {
-        in.col_commitments = (const uint8_t* const*)commitments; in.cells = (const uint8_t* const* const*)cells; in.proofs = (const uint8_t* const* const*)proofs;
-    }
-    in.leaf = flags != 0;
+    const auto in = on_device ? kzg::VerifyManyInput::device_columns(n_blobs, (const uint8_t*)commitments, column_indices, (const uint8_t*)cells,
+                                                                     (const uint8_t*)proofs, nullptr, flags != 0)
+                              : kzg::VerifyManyInput::host_columns(n_blobs, (const uint8_t* const*)commitments, column_indices,
+                                                                   (const uint8_t* const* const*)cells, (const uint8_t* const* const*)proofs, flags != 0);
     return eng(ctx)->test_verify_many_sums_in(n_columns, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
                                               digests32, leaves32, counts2);
 }

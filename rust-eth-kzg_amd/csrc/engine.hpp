@@ -33,7 +33,7 @@ struct Fp12w { uint32_t v[12]; };
 // (k_verify.hip: k_verify_scalars, k_verify_many.hip: k_vm_scalars) and positions are 32-bit on the device.  2^24 cells are 34 GB
 // of input; longer lists are rejected as invalid input by every verification entry point.
 constexpr uint64_t MAX_CELLS_PER_VERIFICATION = (1u << 24) - 1;
-// How verify_cell_kzg_proof_batch_many_host divides a call (verify_many.hip): a call of at least VM_SPLIT_MIN_PROBLEMS problems and
+// How verify_cell_kzg_proof_batch_many divides a call (verify_many.hip; the plans themselves: verify_host.hpp): a call of at least VM_SPLIT_MIN_PROBLEMS problems and
 // VM_SPLIT_MIN_CELLS cells is cut into concurrent parts, and a pass holds at most VM_CHUNK_CELLS cells (1024 verifications of 128
 // cells: 275 MB of pinned staging, ~1 GB of device arena)
 constexpr int VM_SPLIT_MIN_PROBLEMS = 192, VM_SPLIT_MIN_CELLS = 24576, VM_CHUNK_CELLS = 131072;
@@ -60,39 +60,60 @@ struct VerifyManyTap {
 //     [cell_starts[b], cell_starts[b + 1]) of d_commitments (48 B each, one per cell), d_cell_indices, d_cells (2048 B), d_proofs (48 B);
 //     what user_stream has queued produces them
 //   a column matrix over ONE commitment list (columns set; eth_kzg_amd_verify_data_columns / _device): problem b is column b, col_blobs
-//     cells that all carry the index col_indices[b] (host) and whose commitments are the call's col_blobs commitments, one per cell.
-//     Host form: col_commitments[i], cells[b][i], proofs[b][i].  Device form (col_device): d_commitments 48 col_blobs bytes, d_cells /
-//     d_proofs [columns][col_blobs] entries in this GPU's HBM; col0 = the first column of this input in those arrays.  col: the
-//     commitments de-duplicated once for the whole call (null: the call makes it), which every column's problem refers to
+//     cells that all carry the index col_indices[b] (host) and whose commitments are the call's, one per cell: col_commitments[i],
+//     cells[b][i], proofs[b][i] on the host, or (col_device) d_commitments 48 col_blobs bytes, d_cells / d_proofs [columns][col_blobs]
+//     entries in this GPU's HBM.  Once the call has taken its refused columns out (verify_many.hip), problem b is the caller's column
+//     col_place[b] in all of these.  col: the commitments de-duplicated once for the whole call (null: the call makes it)
 // leaf: every problem's challenge is the leaf-hashed one of the problem alone (verify_host.hpp: CellLeafTranscript, cell_leaf_root),
 // the leaves hashed on the GPU out of the pass's arena; else the reference's transcript on the host threads.
 struct VerifyManyInput {
-    const uint64_t *n_commitments = nullptr, *n_indices = nullptr, *n_cells = nullptr, *n_proofs = nullptr;
-    const uint8_t* const* const* commitments = nullptr;
+    const uint64_t *n_commitments = nullptr, *n_indices = nullptr, *n_cells = nullptr, *n_proofs = nullptr, *cell_starts = nullptr;
+    const uint8_t *const *const *commitments = nullptr, *const *const *cells = nullptr, *const *const *proofs = nullptr;
     const uint64_t* const* cell_indices = nullptr;
-    const uint8_t* const* const* cells = nullptr;
-    const uint8_t* const* const* proofs = nullptr;
-    const uint64_t* cell_starts = nullptr;
-    const uint8_t* d_commitments = nullptr;
+    const uint8_t *d_commitments = nullptr, *d_cells = nullptr, *d_proofs = nullptr;
     const uint64_t* d_cell_indices = nullptr;
-    const uint8_t *d_cells = nullptr, *d_proofs = nullptr;
     hipStream_t user_stream = nullptr;
-    bool leaf = false;
-    bool columns = false, col_device = false;
-    bool col_ready = false;             // the call has validated its columns and taken the refused ones out (verify_many.hip)
-    uint64_t col_blobs = 0, col0 = 0;
-    const uint64_t* col_src = nullptr;  // (device form, once refused columns are out) the place of column b in d_cells / d_proofs
+    bool leaf = false, columns = false, col_device = false;
+    uint64_t col_blobs = 0;
+    const uint64_t *col_place = nullptr, *col_indices = nullptr;
     const uint8_t* const* col_commitments = nullptr;
-    const uint64_t* col_indices = nullptr;
     const ColumnCommitments* col = nullptr;
+    static VerifyManyInput lists(const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
+                                 const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells,
+                                 const uint64_t* n_proofs, const uint8_t* const* const* proofs, bool leaf) {
+        VerifyManyInput in;
+        in.n_commitments = n_commitments; in.n_indices = n_indices; in.n_cells = n_cells; in.n_proofs = n_proofs;
+        in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs; in.leaf = leaf;
+        return in;
+    }
+    static VerifyManyInput flat_device(const uint64_t* cell_starts, const uint8_t* d_commitments, const uint64_t* d_cell_indices,
+                                       const uint8_t* d_cells, const uint8_t* d_proofs, hipStream_t user_stream, bool leaf) {
+        VerifyManyInput in;
+        in.cell_starts = cell_starts; in.d_commitments = d_commitments; in.d_cell_indices = d_cell_indices; in.d_cells = d_cells; in.d_proofs = d_proofs;
+        in.user_stream = user_stream; in.leaf = leaf;
+        return in;
+    }
+    static VerifyManyInput host_columns(uint64_t n_blobs, const uint8_t* const* commitments, const uint64_t* column_indices,
+                                        const uint8_t* const* const* cells, const uint8_t* const* const* proofs, bool leaf) {
+        VerifyManyInput in = lists(nullptr, nullptr, nullptr, nullptr, nullptr, cells, nullptr, proofs, leaf);
+        in.columns = true; in.col_blobs = n_blobs; in.col_commitments = commitments; in.col_indices = column_indices;
+        return in;
+    }
+    static VerifyManyInput device_columns(uint64_t n_blobs, const uint8_t* d_commitments, const uint64_t* column_indices, const uint8_t* d_cells,
+                                          const uint8_t* d_proofs, hipStream_t user_stream, bool leaf) {
+        VerifyManyInput in = flat_device(nullptr, d_commitments, nullptr, d_cells, d_proofs, user_stream, leaf);
+        in.columns = in.col_device = true; in.col_blobs = n_blobs; in.col_indices = column_indices;
+        return in;
+    }
     bool on_device() const { return columns ? col_device : cell_starts != nullptr; }
     uint64_t cells_of(uint64_t b) const { return columns ? col_blobs : on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b]; }
     VerifyManyInput from(uint64_t lo) const {  // the problems from lo on (the flat arrays stay: cell_starts holds absolute entries)
         VerifyManyInput s = *this;
         if (columns) {
-            s.col_indices += lo;
-            if (col_device) { if (col_src) s.col_src += lo; else s.col0 += lo; }
-            else if (cells && proofs) { s.cells += lo; s.proofs += lo; }  // (both may be null when there are no blobs: nothing is read)
+            if (col_place) { s.col_place += lo; return s; }
+            // before the places are made ONLY the host form may be cut: nothing here carries an offset into d_cells / d_proofs
+            s.col_indices += lo;  // (cells and proofs may be null when there are no blobs)
+            if (cells && proofs) { s.cells += lo; s.proofs += lo; }
             return s;
         }
         if (on_device()) { s.cell_starts += lo; return s; }
@@ -280,17 +301,9 @@ public:
     int verify_cell_kzg_proof_batch_device(uint64_t n, const uint8_t* d_commitments, const uint64_t* d_cell_indices,
                                            const uint8_t* d_cells, const uint8_t* d_proofs, int* verified, hipStream_t stream,
                                            const CellChallengeMode* mode = nullptr);
-    // MANY independent verifications in one call (verify_many.hip): problem b has n_*[b] entries in commitments[b] / cell_indices[b]
-    // / cells[b] / proofs[b]; status[b] = a Status (OK, ERR_INPUT, ERR_G1, ERR_SCALAR), verified[b] set when OK.  Returns
-    // ERR_DEVICE on a HIP failure, OK otherwise.  Does not take mu_: runs next to the other entry points.
-    int verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint64_t* n_commitments, const uint8_t* const* const* commitments,
-                                              const uint64_t* n_indices, const uint64_t* const* cell_indices, const uint64_t* n_cells,
-                                              const uint8_t* const* const* cells, const uint64_t* n_proofs,
-                                              const uint8_t* const* const* proofs, int* verified, int* status, VerifyManyTap* tap = nullptr);
-    // the same pass over either source and with either challenge (VerifyManyInput above); the call above is its pointer-list form with
-    // the reference's challenges.  Flat device arrays: the pass copies its proofs and cells device-to-device into its arena; commitments
-    // and indices come down for validation and de-duplication; with the leaf-hashed challenges nothing else does but the n x 32 leaf
-    // digests, without them the proofs and cells come down into the pinned slab for the host threads' hashes (correct, and the slow way)
+    // MANY independent verifications in one call (verify_many.hip), from any source and with either challenge (VerifyManyInput above):
+    // status[b] = a Status (OK, ERR_INPUT, ERR_G1, ERR_SCALAR), verified[b] set when OK.  Returns ERR_DEVICE on a HIP failure, OK
+    // otherwise.  Does not take mu_: runs next to the other entry points.
     int verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap = nullptr);
     // verify_cell_kzg_proof_batch as the reference's users call it -- one problem per call, from many threads on one context
     // (bindings/node/src/lib.rs:92-299) -- WITHOUT asking them to batch: the first callers take the latency-optimised path
@@ -396,14 +409,10 @@ public:
     // the two sums verify_blob_kzg_proof_batch pairs (rhs | lhs, compressed) and its verdict; on_device: flat arrays in HBM, else host pointers
     int test_verify_blob_batch_inputs(uint64_t n, int on_device, const void* blobs, const void* commitments, const void* proofs, uint8_t* out96,
                                       int* verified);
-    // one pass of verify_cell_kzg_proof_batch_many_host with its tap set: verdicts and statuses as the call gives them, form = small, folded,
+    // one pass of verify_cell_kzg_proof_batch_many with its tap set: verdicts and statuses as the call gives them, form = small, folded,
     // searched, folded verdict; sums96[B] and fold96 compressed on the host from the sums read back, rho[B][4], the search's probes
     // (probe_ranges[i] = lo, hi, passed; probe_sums96[i]) up to max_probes of them, *n_probes = how many there were
-    int test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
-                              const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells, const uint64_t* n_proofs,
-                              const uint8_t* const* const* proofs, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho,
-                              uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes);
-    // the same over either source and with either challenge, plus digests32[B][32] (the digest each problem's challenge was reduced
+    // over any source and with either challenge (VerifyManyInput), plus digests32[B][32], may be null (the digest each problem's challenge was reduced
     // from; zero for a problem that was not hashed) and, may be null, leaves32[N][32] (leaf-hashed challenges: the leaf digests in the
     // caller's cell order; zero for the cells of a problem that was not hashed)
     int test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
@@ -713,6 +722,10 @@ private:
     };
     PassSlot lease_pass_slot(bool prefer_idle_work_set);
     struct PointPass;  // one pass of verify_kzg_proof_many on such a slot (point_many.hip)
+    struct CellManyPass;  // one pass of verify_cell_kzg_proof_batch_many on such a slot (verify_many.hip)
+    // the column source's once-per-call work; the body every source shares: the call cut into concurrent parts
+    int verify_data_columns_many(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap);
+    int verify_cell_kzg_proof_batch_many_parts(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap);
     // the part of a many-verification call that runs as passes of its own on one slot: the whole call, or one of its concurrent parts
     int verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap);
     std::unique_ptr<HostPool> stage_pool_;  // staging of single verifications (a few threads: the lane + the pass slots run side by side)

@@ -568,18 +568,7 @@ int Engine::test_verify_blob_batch_inputs(uint64_t n, int on_device, const void*
 // One pass of the many-verification with its tap set (verify_many.hip): the launches are the public call's, the tap copies the pinned
 // read-backs after the pass's own syncs, and the points are compressed here, on the host.  The caller (c_api_hooks.cpp) has refused
 // null buffers; a call the engine would cut into parts or chunks is refused before anything is launched.
-int Engine::test_verify_many_sums(uint64_t n_batches, const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
-                                  const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells,
-                                  const uint64_t* n_proofs, const uint8_t* const* const* proofs, int32_t* verified, int32_t* status, int32_t* form4,
-                                  uint8_t* sums96, uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes,
-                                  uint64_t* n_probes) {
-    VerifyManyInput in;
-    in.n_commitments = n_commitments; in.n_indices = n_indices; in.n_cells = n_cells; in.n_proofs = n_proofs;
-    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
-    return test_verify_many_sums_in(n_batches, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes, nullptr,
-                                    nullptr);
-}
-// The same over either source and with either challenge (the hooks _ex and _device): the taps of the digests and of the leaves besides.
+// Over any source and with either challenge (the hooks' makers: c_api_hooks.cpp); digests32 and leaves32 may be null.
 int Engine::test_verify_many_sums_in(uint64_t n_batches, const VerifyManyInput& in, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96,
                                      uint32_t* rho, uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
                                      uint8_t* digests32, uint8_t* leaves32, uint64_t* counts2) {

@@ -285,6 +285,55 @@ inline void fold_weight(const uint8_t seed[32], uint64_t i, uint32_t out4[4]) {
     if ((out4[0] | out4[1] | out4[2] | out4[3]) == 0) out4[0] = 1;  // a weight of zero would drop its problem from the check
 }
 
+// ---- the bookkeeping of the cell many-verification (verify_many.hip; tests/c/test_vm_plan.cpp): integers in, a vector out, no HIP.
+// The PARTS of a call of B problems, cells_of(b) cells each: cut points 0 = c_0 < .. < c_P = B (B = 0: {0}).  A call below min_problems
+// problems or min_cells cells is one part; a larger one is cut into at most max_parts equal shares of its cells: behind the problem
+// with which the running total reaches the next share, never behind the last problem.
+template <class CellsOf>
+inline std::vector<int> vm_call_parts(int B, CellsOf cells_of, int min_problems, uint64_t min_cells, int max_parts) {
+    std::vector<int> cut{0};
+    if (B == 0) return cut;
+    uint64_t total = 0, acc = 0;
+    for (int b = 0; b < B && max_parts > 1 && B >= min_problems; b++) total += cells_of(b);
+    for (int b = 0; b < B && total >= min_cells; b++) {
+        acc += cells_of(b);
+        if ((int)cut.size() < max_parts && acc * max_parts >= total * cut.size() && b + 1 < B) cut.push_back(b + 1);
+    }
+    cut.push_back(B);
+    return cut;
+}
+// The CHUNK that begins at problem b0 ends in front of the problem returned: as many as hold at most chunk_cells cells, and at least one.
+template <class CellsOf>
+inline int vm_chunk_end(int B, int b0, CellsOf cells_of, uint64_t chunk_cells) {
+    int b1 = b0;
+    uint64_t n = 0;
+    while (b1 < B && (b1 == b0 || n + cells_of(b1) <= chunk_cells)) n += cells_of(b1++);
+    return b1;
+}
+// The COPIES that bring the problems that take part, in order, back to back to a destination: one run per stretch of them that
+// follow each other in the source.  (A problem that takes no part and holds entries ends a run: the source goes on behind them.)
+struct CopyRun { uint64_t src, len, dst; };
+template <class SrcOf, class LenOf, class Takes>
+inline std::vector<CopyRun> vm_copy_runs(int B, SrcOf src_of, LenOf len_of, Takes takes) {
+    std::vector<CopyRun> runs;
+    uint64_t at = 0;
+    for (int b = 0; b < B; b++) {
+        const uint64_t len = takes(b) ? (uint64_t)len_of(b) : 0;
+        if (!len) continue;
+        if (!runs.empty() && runs.back().src + runs.back().len == (uint64_t)src_of(b)) runs.back().len += len;
+        else runs.push_back({(uint64_t)src_of(b), len, at});
+        at += len;
+    }
+    return runs;
+}
+// The columns of a column call that go on (validate_data_column accepts them): kept column k is the caller's column keep[k].
+inline std::vector<uint64_t> vm_kept_columns(uint64_t n_blobs, uint64_t n_columns, const uint64_t* column_indices) {
+    std::vector<uint64_t> keep;
+    for (uint64_t b = 0; b < n_columns; b++)
+        if (validate_data_column(n_blobs, column_indices[b]) == INPUT_VALID) keep.push_back(b);
+    return keep;
+}
+
 // ---- eth_kzg_amd_verify_kzg_proof_many / _many_device (point_many.hip): MANY items (commitment, z, y, proof), a verdict for each --
 // exactly what Verifier::verify_kzg_proof (crates/eip4844/src/verifier.rs:19-44) says of the item alone.  The reference has nothing
 // like it.  Item equation, as the single call evaluates it (eip4844.hip: verify_kzg_proof_host):

@@ -2,34 +2,28 @@
 // Reference semantics per problem: DASContext::verify_cell_kzg_proof_batch (crates/eip7594/src/verifier.rs:72-164) ->
 // FK20Verifier::verify_multi_opening (crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:129-260); the reference gets
 // its throughput by verifying from many threads on one context (bindings/node/src/lib.rs:92-299,
-// crates/cryptography/bls12_381/src/lib.rs:45-50).  Here the problems of a call share every GPU launch:
-//   host threads : validation + de-duplication per problem, staging into one pinned slab, one SHA-256 transcript per problem
-//                  (in parallel, behind the GPU's decoding; a persistent pool), then ONE 2-pairing check per pass: the problems' two
-//                  G1 sums are folded on the GPU with 127-bit weights derived from all the challenges; in a pass whose folded check
-//                  fails (some proof is wrong) the wrong problems are SEARCHED by folding sub-ranges of the resident weighted sums,
-//                  one pairing per probe ($ETH_KZG_AMD_VM_SEARCH=0: re-checked one by one; $ETH_KZG_AMD_VM_FOLD=0: never folded)
-//   GPU          : decode + subgroup-check all points, decode all cells, per-cell interpolation (challenge-free: behind the
-//                  hashes), then per-problem scalars / weights / interpolation sums, ONE LANE PER SCALAR MULTIPLICATION
-//                  (k_verify_many.hip), the 64-term interpolation commitments from the commitment window table, per-problem sums;
-//                  small passes (concurrent single calls combined) take a short-chain form: everything after the challenge in
-//                  one launch, no fold
-// Three pass slots, each with its own lock, device arena and pinned slab, on the streams of the prover's three work sets (HIP maps
-// a process's streams onto four hardware queues): passes run side by side, a large call is cut into three concurrent parts, and a
-// "pass" of one problem is the single path on the slot.  Nothing here takes the context's big lock.
-// One pass, two sources, two challenge modes (engine.hpp: VerifyManyInput).  Sources: the caller's pointer lists, gathered into the
-// pinned slab and uploaded; or flat arrays in HBM plus cell_starts, whose proofs and cells go device-to-device into the arena while
-// commitments and indices come down for validation and de-duplication.  Challenges: the reference's transcript on the host threads; or
-// the leaf-hashed challenge of each problem alone (verify_host.hpp: CellLeafTranscript) -- the leaves of ALL the pass's cells in one
-// launch of k_sha256_cell_leaves out of the arena, in order on the pass's stream behind the upload, the n x 32 digests down behind an
-// event, one ROOT per problem on the host threads while the decoding kernels run.  The roots stay on the host on purpose: a lane per
-// problem would serialise n / 2 compressions of a large problem (8192 cells: ~4 k dependent compressions), and the wait for the
-// status words is there anyway.  Everything behind the challenge is the same for all four combinations.
-// A third source, the COLUMNS of one block over one commitment list (eth_kzg_amd_verify_data_columns / _device; engine.hpp:
-// VerifyManyInput::columns): problem b is column b.  The commitments are de-duplicated once per call and decoded once per pass, and
-// because all cells of a column carry one index, the second proof product is one per column, h^64 * A_b, behind the reduction of A_b
-// (k_verify_many.hip: k_vc_*): n + Bc n_u + Bc scalar multiplications where the expanded pass has 2 n + Bc n_u.  Validation, chunks,
-// parts, the short-chain form, the challenges, the fold and the search are the pass's own; the per-column pair is the expanded pass's.
+// crates/cryptography/bls12_381/src/lib.rs:45-50).  Here the problems of a call share every GPU launch.
+// THREE SOURCES (engine.hpp: VerifyManyInput says what each holds), resolved once per part into a CellSource: pointer lists on the
+// host; flat arrays in HBM plus cell_starts; the columns of one block over ONE commitment list, on the host or in HBM (problem b is
+// column b; verify_data_columns_many does the source's once-per-call work).  Two challenges: the reference's transcript per problem,
+// or the leaf-hashed challenge of each problem alone (verify_host.hpp: CellLeafTranscript).  A large CALL is cut into at most three
+// concurrent PARTS, a part into CHUNKS of at most VM_CHUNK_CELLS cells, and every chunk is one PASS (Engine::CellManyPass) on one of three
+// pass slots (lease_pass_slot); the plans are verify_host.hpp's.  Nothing here takes the context's big lock.  The steps of a pass:
+//   arena      the slot's blocks, large enough; the result slots of the slab poisoned
+//   stage      host threads: the problems into the pinned slab (host sources: proofs and cells; all: commitments, indices, rows)
+//   upload     ONE copy up; device sources: the host-made arrays up, proofs and cells device-to-device in copy runs (and down
+//              again, compacted, for the reference's transcript)
+//   leaves     (leaf-hashed) the leaves of ALL the pass's cells in one launch of k_sha256_cell_leaves out of the arena, n x 32 bytes down
+//   decode     decode + subgroup-check all points, decode all cells, per-cell interpolation: challenge-free, behind the hashes
+//   challenges host threads: one SHA-256 transcript, or one ROOT over the leaf digests, per problem (on the host on purpose: a lane per problem
+//              would serialise n / 2 compressions, and the wait for the status words is there anyway); the decoding verdicts; the folding weights
+//   products_and_sums   scalars / weights / interpolation sums, ONE LANE PER SCALAR MULTIPLICATION (k_verify_many.hip), the 64-term
+//              interpolation commitments from the commitment window table, the two sums per problem (small passes: the short chain)
+//   fold_and_sums_down  the problems' sums folded on the GPU with 127-bit weights derived from all the challenges; both down
+//   verdicts   ONE 2-pairing check per pass; where it fails the wrong problems are SEARCHED by folding sub-ranges of the resident weighted sums,
+//              one pairing per probe ($ETH_KZG_AMD_VM_SEARCH=0: one by one; $ETH_KZG_AMD_VM_FOLD=0: no fold)
 #include "vm_search.hpp"
+#include <numeric>
 
 namespace kzg {
 
@@ -41,8 +35,70 @@ struct Problem {  // one verification of the call, after validation
     std::vector<const uint8_t*> own_uniq;  // where the two live when the problem was de-duplicated alone; the columns of a
     std::vector<int> own_row;              // column call all refer to the call's one pair (verify_host.hpp: ColumnCommitments)
     int n = 0, m = 0;                  // cells, unique commitments (0, 0 when the problem is skipped)
-    uint64_t src0 = 0, mir0 = 0;       // (flat device source) its first entry in the caller's arrays / in the pinned mirror
 };
+
+// Where the B problems of a part come from: made once per part, it answers what the part and its passes ask about problem b.
+struct CellSource {
+    const VerifyManyInput in;  // the part's input
+    const int B;
+    const bool device = in.on_device();  // proofs and cells lie in HBM (the host has neither)
+    const bool shared = in.columns;      // the commitments are the pass's: one list, every problem's (the column source)
+    std::vector<uint64_t> src0;          // (device) the problem's first entry in the caller's d_cells / d_proofs
+    std::vector<uint64_t> mir0;          // (flat arrays) its first entry in the pinned mirror of commitments and indices: back to back
+    uint64_t mirror_n = 0;               // entries of the mirror
+    const uint8_t* mirror_c = nullptr;   // set by mirror_down
+    const uint64_t* mirror_i = nullptr;
+    CellSource(const VerifyManyInput& in_, int B_) : in(in_), B(B_) {
+        for (int b = 0; b < B && device; b++) {
+            src0.push_back(shared ? place(b) * in.col_blobs : in.cell_starts[b]);
+            mir0.push_back(mirror_n);
+            if (!shared && in_mirror(b)) mirror_n += cells_of(b);
+        }
+    }
+    uint64_t cells_of(int b) const { return in.cells_of((uint64_t)b); }
+    // a problem beyond the size bound is refused by its validation (status 3) and has no place in the mirror: nothing of it is read
+    bool in_mirror(int b) const { return cells_of(b) <= MAX_CELLS_PER_VERIFICATION; }
+    uint64_t place(int b) const { return shared ? in.col_place[b] : (uint64_t)b; }  // where the caller's arrays hold problem b
+    uint64_t index_of(int b, int k) const { return shared ? in.col_indices[place(b)] : device ? mirror_i[mir0[b] + k] : in.cell_indices[b][k]; }
+    const uint8_t* cell(int b, int k) const { return in.cells[place(b)][k]; }  // (host sources)
+    const uint8_t* proof(int b, int k) const { return in.proofs[place(b)][k]; }
+    int pass_m() const { return shared ? (int)in.col->uniq.size() : 0; }  // the pass-wide commitments
+    const uint8_t* const* pass_uniq() const { return shared ? in.col->uniq.data() : nullptr; }
+    int own_rows(const Problem& p) const { return shared ? 0 : p.m; }     // the commitments a problem brings into a pass itself
+    // validation (verifier.rs:123-164; flat arrays: the bound, checked before an index is read, and the indices) and de-duplication
+    // of problem b -> its status; p is filled only if the problem goes on
+    int admit(int b, Problem& p) const {
+        const uint64_t nb = cells_of(b);
+        const int st = shared   ? validate_data_column(nb, in.col_indices[place(b)])
+                       : device ? validate_cell_batch(nb, nb, nb, nb, mirror_i + mir0[b])
+                                : validate_cell_batch(in.n_commitments[b], in.n_indices[b], nb, in.n_proofs[b], in.cell_indices[b]);
+        if (st != OK || nb == 0) return st;
+        if (shared) {  // every column refers to the call's one de-duplication
+            p.uniq = in.col->uniq.data(); p.row = in.col->row.data();
+            p.m = (int)in.col->uniq.size();
+        } else {
+            if (device) dedup_commitments_flat(nb, mirror_c + (size_t)mir0[b] * 48, p.own_uniq, p.own_row);
+            else dedup_commitments(nb, in.commitments[b], p.own_uniq, p.own_row);
+            p.uniq = p.own_uniq.data(); p.row = p.own_row.data();
+            p.m = (int)p.own_uniq.size();
+        }
+        p.n = (int)nb;
+        return st;
+    }
+};
+// flat arrays: commitments and indices of the part's cells come down (56 bytes per cell) into the pinned mirror (pin, cap: the
+// slot's), one pair of copies per run of problems within the bound
+void mirror_down(CellSource& S, uint8_t*& pin, size_t& cap, hipStream_t st) {
+    if (!S.mirror_n) return;
+    grow_pinned(pin, cap, (size_t)S.mirror_n * 56);
+    uint64_t* const pin_i = reinterpret_cast<uint64_t*>(pin + (size_t)S.mirror_n * 48);
+    for (const CopyRun& r : vm_copy_runs(S.B, [&](int b) { return S.src0[b]; }, [&](int b) { return S.cells_of(b); }, [&](int b) { return S.in_mirror(b); })) {
+        HIPCK(hipMemcpyAsync(pin + (size_t)r.dst * 48, S.in.d_commitments + (size_t)r.src * 48, (size_t)r.len * 48, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(pin_i + r.dst, S.in.d_cell_indices + r.src, (size_t)r.len * 8, hipMemcpyDeviceToHost, st));
+    }
+    SYNC_CHECKED(st);
+    S.mirror_c = pin; S.mirror_i = pin_i;
+}
 
 // Where a pass's arrays lie: n cells and m unique commitments of Bc problems.  Device arena: [inputs, uploaded in one copy |
 // power tables and folding weights, uploaded after the hashes | device only]; the pinned slab holds both uploads and the read-backs.
@@ -81,68 +137,164 @@ struct PassLayout {
                  off_leaf = d.take(leaf ? (size_t)n * 32 : 0), off_verd = d.take((size_t)max_ranges), dev_bytes = d.end;
     PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_, bool cols_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_), cols(cols_) {}
 };
+}  // namespace
 
-// The host's side of one pass: problems b0 .. b0 + Bc of the call (`in` is the call's input from b0 on), n cells and m unique
-// commitments in all, staged into the pinned slab hb as L lays it out.  Nothing in here touches the GPU.
-struct PassHost {
-    const PassLayout& L;
-    const Problem* pr;
-    const VerifyManyInput in;
-    const uint64_t* mirror_i;  // (flat device source) the pinned mirror of the call's indices: a problem's begin at its mir0
-    uint8_t* hb;
-    int T;
-    HostPool* pool;
-    const pairing::G2Prepared* vk[2];        // [tau^64]_2, -[1]_2
-    vm::DevicePairing gpu;                   // the same keys for k_pairing_check (the search's larger batches of probes)
-    int* verified;                           // verified[i] belongs to problem i of the pass
+// One pass: problems [b0, b0 + Bc) of a part (pr: the first of them; problem i is the source's b0 + i) on the part's slot and its stream
+// st, its steps in the order run() takes them; the tap (null in the product) receives copies of the read-backs in the step that has them.
+struct Engine::CellManyPass {
+    Engine& e;
+    const CellSource& S;
+    const Problem* const pr;
+    const int b0, Bc;
+    int *const ver, *const stat;  // the pass's verdicts and statuses in the caller's arrays
+    VerifyManyTap* const tap;
+    const int T;
+    HostPool* const pool;
+    VmSlot* const slot;
+    const hipStream_t st;
+    TraceLap& lap;
+    static int cells(const Problem* pr, int Bc) { return std::accumulate(pr, pr + Bc, 0, [](int a, const Problem& p) { return a + p.n; }); }
+    const int n = cells(pr, Bc);
+    const int m = S.shared ? S.pass_m() : std::accumulate(pr, pr + Bc, 0, [](int a, const Problem& p) { return a + p.m; });  // unique commitments
+    // A pass of a few problems (concurrent single calls combined) is a chain of latencies, not work: it takes the SHORT-CHAIN form --
+    // subgroup tests and the interpolation commitments' terms inside the ONE launch of all scalar multiplications (k_vm_products), no fold
+    // (a 1.4 ms chain; <= 2 T pairing checks are one or two rounds of the host threads) -- 0.45 + 1.7 + 0.2 ms of GPU instead of ~6
+    const bool small = e.vm_small_max_ != 0 && Bc <= (e.vm_small_max_ > 0 ? e.vm_small_max_ : 2 * T);
+    const PassLayout L{n, m, Bc, small, S.in.leaf, S.shared};
+    const pairing::G2Prepared* const vk[2] = {e.g2_tau_.get(), e.g2_neg_gen_.get()};  // [tau^64]_2, -[1]_2
+    const vm::DevicePairing gpu = e.device_pairing(0);  // the same keys for k_pairing_check (the search's larger batches of probes)
+    // the host's hashes read what a copy on st brings down: the leaf digests, or the proofs and cells of a device source
+    const bool hash_waits = L.leaf || S.device;
+    uint8_t *hb = nullptr, *db = nullptr;    // the slot's pinned slab and device arena
     std::atomic<int> device_fault{0};
     std::vector<int> cell_start, row_start;  // first cell / first unique commitment of each problem
     std::vector<uint8_t> digests;            // of the challenges: the fold seed hashes them
     std::vector<char> live;                  // problems that decoded without an error
-    VerifyManyTap* tap = nullptr;            // (null in the product) receives copies of the read-backs
+    int n_live = 0;
+    bool folded = false;  // one folded pairing check for the pass instead of one per problem
     const JacQ* sums() const { return (const JacQ*)(hb + L.poff_out); }  // the problems' two sums read back
     int* h_status() const { return (int*)(hb + L.poff_st); }  // read-backs: [proofs n | commitments m | cells, per problem]
-    const uint64_t* indices_of(int i) const { return in.on_device() ? mirror_i + pr[i].mir0 : in.cell_indices[i]; }
-    uint64_t index_of(int i, int k) const { return in.columns ? in.col_indices[i] : indices_of(i)[k]; }  // of cell k of problem i
 
-    // gather the problems into the slab (flat device source: what the host made of them; proofs and cells move inside HBM); stale
-    // contents of the persistent slab must fail closed: status words and result slots are poisoned
+    void run() {
+        arena();
+        stage();
+        upload();
+        leaves();
+        decode();
+        challenges();
+        products_and_sums();
+        fold_and_sums_down();
+        verdicts();
+    }
+    // the slot's blocks, large enough; stale contents of the persistent slab must fail closed: status words and result slots are poisoned
+    void arena() {
+        grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
+        grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
+        hb = slot->pin, db = (uint8_t*)slot->dev;
+        memset(h_status(), 0xff, (size_t)(L.n + L.m + L.Bc) * 4);
+        memset(hb + L.poff_out, 0xff, (size_t)2 * L.Bc * launch::SIZEOF_JACQ);
+        memset(hb + L.poff_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ);
+        if (tap) { tap->passes++; tap->small = small; tap->commitments_decoded = (uint64_t)m; }
+    }
+    // ---- gather the problems into the slab (device sources: what the host made of them); the commitments: every problem's own
+    // behind each other, or the pass's one list (rows are then pass-wide: row_start is 0 throughout)
     void stage() {
-        cell_start.assign(L.Bc + 1, 0); row_start.assign(L.Bc + 1, 0);
-        for (int i = 0; i < L.Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[i].n; row_start[i + 1] = L.cols ? 0 : row_start[i] + pr[i].m; }
-        if (L.cols)  // the one commitment list of the call, once per pass; rows are pass-wide (row_start is 0 throughout)
-            for (int j = 0; j < L.m; j++) memcpy(hb + L.off_c + (size_t)j * 48, in.col->uniq[j], 48);
-        memcpy(hb + L.off_cs, cell_start.data(), (size_t)(L.Bc + 1) * 4);
-        memcpy(hb + L.off_rs, row_start.data(), (size_t)(L.Bc + 1) * 4);
+        cell_start.assign(Bc + 1, 0); row_start.assign(Bc + 1, 0);
+        for (int i = 0; i < Bc; i++) { cell_start[i + 1] = cell_start[i] + pr[i].n; row_start[i + 1] = row_start[i] + S.own_rows(pr[i]); }
+        for (int j = 0; j < S.pass_m(); j++) memcpy(hb + L.off_c + (size_t)j * 48, S.pass_uniq()[j], 48);
+        memcpy(hb + L.off_cs, cell_start.data(), (size_t)(Bc + 1) * 4);
+        memcpy(hb + L.off_rs, row_start.data(), (size_t)(Bc + 1) * 4);
         int *h_idx = (int*)(hb + L.off_idx), *h_row = (int*)(hb + L.off_row), *h_bat = (int*)(hb + L.off_bat), *h_pos = (int*)(hb + L.off_pos),
             *h_rowb = (int*)(hb + L.off_rowb);
-        const bool gather = !in.on_device();
-        parallel_for(L.Bc, T, pool, [&](int i) {
+        const bool gather = !S.device;
+        parallel_for(Bc, T, pool, [&](int i) {
             const Problem& p = pr[i];
             const int c0 = cell_start[i], r0 = row_start[i];
-            for (int j = 0; j < p.m && !L.cols; j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
+            for (int j = 0; j < S.own_rows(p); j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
             for (int k = 0; k < p.n; k++) {
                 if (gather) {
-                    memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, in.proofs[i][k], 48);
-                    memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, in.cells[i][k], BYTES_PER_CELL);
+                    memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, S.proof(b0 + i, k), 48);
+                    memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, S.cell(b0 + i, k), BYTES_PER_CELL);
                 }
-                h_idx[c0 + k] = (int)index_of(i, k);
+                h_idx[c0 + k] = (int)S.index_of(b0 + i, k);
                 h_row[c0 + k] = r0 + p.row[k];
                 h_bat[c0 + k] = i;
                 h_pos[c0 + k] = k;
             }
         });
-        memset(h_status(), 0xff, (size_t)(L.n + L.m + L.Bc) * 4);
-        memset(hb + L.poff_out, 0xff, (size_t)2 * L.Bc * launch::SIZEOF_JACQ);
-        memset(hb + L.poff_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ);
+        lap("stage (host)");
     }
-    // the Fiat-Shamir challenges on the host threads, then the table r^(2^i) per problem.  The reference's transcript
-    // (verify_host.hpp: CellBatchTranscript) over the caller's buffers, or, for the flat device source, over the proofs and cells that
-    // came down into the slab; leaf-hashed: one ROOT per problem over the leaf digests that came down (cell_leaf_root)
+    // ---- the device's result slots poisoned, then the inputs into the arena
+    void upload() {
+        HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)(n + m) * 4, st));
+        HIPCK(hipMemsetAsync(db + L.off_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ, st));
+        HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ, st));
+        HIPCK(hipMemsetAsync(db + L.off_ste, 0, (size_t)Bc * 4, st));
+        if (!S.device) {
+            HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
+            return;
+        }
+        // only the host-made parts go up; proofs and cells move inside HBM, from any byte address, one copy per run of problems
+        // that follow each other in the caller's arrays (a problem refused at validation leaves a gap)
+        HIPCK(hipMemcpyAsync(db + L.off_c, hb + L.off_c, (size_t)m * 48, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(db + L.off_idx, hb + L.off_idx, L.in_bytes - L.off_idx, hipMemcpyHostToDevice, st));
+        for (const CopyRun& r : vm_copy_runs(Bc, [&](int i) { return S.src0[b0 + i]; }, [&](int i) { return pr[i].n; }, [&](int i) { return pr[i].n != 0; })) {
+            HIPCK(hipMemcpyAsync(db + L.off_p + (size_t)r.dst * 48, S.in.d_proofs + (size_t)r.src * 48, (size_t)r.len * 48, hipMemcpyDeviceToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_cells + (size_t)r.dst * BYTES_PER_CELL, S.in.d_cells + (size_t)r.src * BYTES_PER_CELL,
+                                 (size_t)r.len * BYTES_PER_CELL, hipMemcpyDeviceToDevice, st));
+        }
+        if (!L.leaf) {  // the reference's transcript hashes every byte on the host: the pass's proofs and cells come down, compacted
+            HIPCK(hipMemcpyAsync(hb + L.off_p, db + L.off_p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(hb + L.off_cells, db + L.off_cells, (size_t)n * BYTES_PER_CELL, hipMemcpyDeviceToHost, st));
+        }
+    }
+    // ---- (leaf-hashed) the leaves of all the pass's cells straight out of the arena (its offsets are multiples of 256: the kernel's
+    // 16-byte loads), in order on the pass's stream (a fifth stream: lease_pass_slot).  The event: what the host threads hash is down.
+    void leaves() {
+        if (hash_waits && !slot->hash_inputs_down) HIPCK(hipEventCreateWithFlags(&slot->hash_inputs_down, hipEventDisableTiming));
+        if (L.leaf) {
+            launch::sha256_cell_leaves(n, db + L.off_c, (const int*)(db + L.off_row), (const int*)(db + L.off_idx), db + L.off_p, db + L.off_cells,
+                                       db + L.off_leaf, st, (const int*)(db + L.off_pos));
+            HIPCK(hipMemcpyAsync(hb + L.poff_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
+        }
+        if (hash_waits) HIPCK(hipEventRecord(slot->hash_inputs_down, st));
+    }
+    // ---- challenge-free GPU work: decode (on curve) + subgroup tests of [proofs | commitments], cells, interpolation
+    void decode() {
+        G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
+        int* d_stp = (int*)(db + L.off_stp);
+        launch::g1_decode2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, m, e.beta_, st);
+        if (!small) launch::g1_subgroup2(d_pts, d_stp, n, d_pts + n, d_stp + n, m, e.beta_, st);  // (small: inside k_vm_products)
+        launch::cells_to_fr(db + L.off_cells, db + L.off_evals, nullptr, (int*)(db + L.off_ste), (const int*)(db + L.off_bat), nullptr, n, st);
+        launch::interp_cells(db + L.off_evals, (const int*)(db + L.off_idx), e.d_w8192_, e.inv64_, db + L.off_coef, n, st);
+        HIPCK(hipMemcpyAsync(h_status(), d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(h_status() + n + m, db + L.off_ste, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipGetLastError());
+        lap("enqueue (host)");
+    }
+    // ---- meanwhile, on the host threads: the challenges; then the decoding verdicts, the live problems and their folding weights
+    void challenges() {
+        if (hash_waits) HIPCK(hipEventSynchronize(slot->hash_inputs_down));
+        hash_challenges();
+        lap(L.leaf ? "leaf hashes (GPU) + roots (host)" : "sha256 transcripts (host)");
+        SYNC_CHECKED(st);  // (the challenge-free GPU work has long finished under the hashes: a short wait)
+        lap("wait decode");
+        n_live = judge();  // (a small pass judges again once its subgroup tests are in)
+        folded = e.knobs_.vm_fold && n_live >= 2 && !small;  // (the knob is a test hook: one pairing per problem)
+        if (folded) fold_weights();
+        if (tap) {
+            tap->digests = digests;
+            if (L.leaf) tap->leaves.assign(hb + L.poff_leaf, hb + L.poff_leaf + (size_t)n * 32);
+            tap->folded = folded;
+        }
+    }
+    // the Fiat-Shamir challenges, then the table r^(2^i) per problem: the reference's transcript (verify_host.hpp: CellBatchTranscript) over
+    // the caller's buffers or what a device source brought down into the slab, or one ROOT over the leaf digests (cell_leaf_root)
     void hash_challenges() {
         Fr* h_pow = (Fr*)(hb + L.off_pow);
-        digests.assign((size_t)L.Bc * 32, 0);
-        parallel_for(L.Bc, T, pool, [&](int i) {
+        digests.assign((size_t)Bc * 32, 0);
+        const bool slab = S.device;
+        parallel_for(Bc, T, pool, [&](int i) {
             const Problem& p = pr[i];
             Fr* tab = h_pow + (size_t)i * 24;
             if (p.n == 0) { for (int j = 0; j < 24; j++) tab[j] = one<FrParams>(); return; }
@@ -151,11 +303,11 @@ struct PassHost {
                 cur = cell_leaf_root(hb + L.poff_leaf, cell_start.data(), (size_t)i, &digests[(size_t)i * 32]);
             } else {
                 CellBatchTranscript t(p.m, p.n, p.uniq);
-                if (in.on_device()) {
-                    const uint8_t *sc = hb + L.off_cells + (size_t)cell_start[i] * BYTES_PER_CELL, *sp = hb + L.off_p + (size_t)cell_start[i] * 48;
-                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], index_of(i, k), sc + (size_t)k * BYTES_PER_CELL, sp + (size_t)k * 48);
-                } else {
-                    for (int k = 0; k < p.n; k++) t.absorb(p.row[k], index_of(i, k), in.cells[i][k], in.proofs[i][k]);
+                const uint8_t *sc = hb + L.off_cells + (size_t)cell_start[i] * BYTES_PER_CELL, *sp = hb + L.off_p + (size_t)cell_start[i] * 48;
+                for (int k = 0; k < p.n; k++) {
+                    const uint8_t* const cell = slab ? sc + (size_t)k * BYTES_PER_CELL : S.cell(b0 + i, k);
+                    const uint8_t* const proof = slab ? sp + (size_t)k * 48 : S.proof(b0 + i, k);
+                    t.absorb(p.row[k], S.index_of(b0 + i, k), cell, proof);
                 }
                 cur = t.finish();
                 memcpy(&digests[(size_t)i * 32], t.digest(), 32);
@@ -164,141 +316,165 @@ struct PassHost {
         });
     }
     // decoding verdicts per problem (order of the reference: commitments, proofs, cells) -> live problems; the others take no further part
-    int judge(int* status) {
+    int judge() {
         const int* h_st = h_status();
-        live.assign(L.Bc, 0);
-        int n_live = 0;
-        bool shared_bad = false;  // (the column source) a bad commitment of the one list is every column's
-        for (int j = 0; j < L.m && L.cols; j++) shared_bad |= h_st[L.n + j] != 0;
-        for (int i = 0; i < L.Bc; i++) {
+        live.assign(Bc, 0);
+        int alive = 0;
+        bool shared_bad = false;  // a bad commitment of the pass's one list is every problem's
+        for (int j = 0; j < S.pass_m(); j++) shared_bad |= h_st[L.n + j] != 0;
+        for (int i = 0; i < Bc; i++) {
             const Problem& p = pr[i];
             if (p.n == 0) continue;
             const int c0 = cell_start[i], r0 = row_start[i];
             int bad = shared_bad ? (int)ERR_G1 : (int)OK;
-            for (int j = 0; j < p.m && !bad && !L.cols; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
+            for (int j = 0; j < S.own_rows(p) && !bad; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
             for (int k = 0; k < p.n && !bad; k++) if (h_st[c0 + k]) bad = ERR_G1;
             if (!bad && h_st[L.n + L.m + i]) bad = ERR_SCALAR;
-            status[i] = bad;
-            if (!bad) { live[i] = 1; n_live++; }
+            stat[i] = bad;
+            if (!bad) { live[i] = 1; alive++; }
         }
-        return n_live;
-    }
-    void check_single(int i) {  // one problem's own pairing check
-        const int v = check_pair(sums() + 2 * (size_t)i, vk);
-        if (v < 0) device_fault.store(1);
-        else verified[i] = v;
+        return alive;
     }
     // folding weights (verify_host.hpp: fold_seed, fold_weight); 0 for problems that are out
     void fold_weights() {
         uint32_t* h_rho = (uint32_t*)(hb + L.off_rho);
         uint8_t seed[32];
         fold_seed(digests.data(), digests.size(), seed);
-        parallel_for(L.Bc, T, pool, [&](int i) {
+        parallel_for(Bc, T, pool, [&](int i) {
             uint32_t* r4 = h_rho + 4 * (size_t)i;
             if (live[i]) fold_weight(seed, (uint64_t)i, r4);
             else r4[0] = r4[1] = r4[2] = r4[3] = 0;
         });
     }
+    // ---- per-problem scalars, weights, interpolation sums; every scalar multiplication; the two sums per problem.  Where the column
+    // source's kernels differ a null pointer tells the launcher (launch.hpp), each stated once here: r^k per cell and ONE h^64 per column,
+    // weights per (column, commitment), n + Bc m products, and h^64 A_b as a dependent launch behind the reduction of A_b, inside vm_sums
+    void products_and_sums() {
+        HIPCK(hipMemcpyAsync(db + L.off_pow, hb + L.off_pow, L.in2_bytes - L.off_pow, hipMemcpyHostToDevice, st));  // power tables + weights
+        const int* const d_cs = (const int*)(db + L.off_cs);
+        int* const d_stp = (int*)(db + L.off_stp);
+        uint8_t *const d_s2 = L.cols ? nullptr : db + L.off_s2, *const d_h = L.cols ? db + L.off_h : nullptr;  // vm_scalars, vm_products
+        const int* const d_rowb = L.cols ? nullptr : (const int*)(db + L.off_rowb);                                // vm_weights
+        const int* const d_rs = L.cols ? nullptr : (const int*)(db + L.off_rs);                                    // vm_sums
+        launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_cs, e.d_w8192_,
+                           db + L.off_rp, db + L.off_s1, d_s2, d_h, n, Bc, st);
+        launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), d_rowb, d_cs, db + L.off_w, m, Bc, st);
+        launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
+        uint64_t muls = (uint64_t)launch::vm_products(db + L.off_pts, db + L.off_s1, d_s2, db + L.off_w, db + L.off_isc, e.d_srs_, db + L.off_prod, n, m, Bc,
+                                                      small, d_stp, e.beta_, st);
+        // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
+        if (!small) e.launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
+        muls += (uint64_t)launch::vm_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, d_rs, db + L.off_h, db + L.off_out, n, m, Bc, e.beta_, st);
+        if (small) HIPCK(hipMemcpyAsync(h_status(), d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
+        if (tap) tap->scalar_muls = muls;
+    }
+    // ---- the fold of a folded pass, then both results down
+    void fold_and_sums_down() {
+        if (folded) {
+            launch::vm_fold(db + L.off_out, (const uint32_t*)(db + L.off_rho), db + L.off_fprod, db + L.off_fold, Bc, e.beta_, st);
+            HIPCK(hipMemcpyAsync(hb + L.poff_fold, db + L.off_fold, (size_t)2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
+        }
+        HIPCK(hipMemcpyAsync(hb + L.poff_out, db + L.off_out, (size_t)2 * Bc * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
+        SYNC_CHECKED(st);
+        lap("scalars + products + sums (GPU)");
+        if (small) n_live = judge();
+        if (tap) {
+            tap->sums.assign(hb + L.poff_out, hb + L.poff_out + (size_t)2 * Bc * launch::SIZEOF_JACQ);
+            tap->rho.assign((const uint32_t*)(hb + L.off_rho), (const uint32_t*)(hb + L.off_rho) + 4 * (size_t)Bc);
+            if (folded) tap->fold.assign(hb + L.poff_fold, hb + L.poff_fold + (size_t)2 * launch::SIZEOF_JACQ);
+        }
+    }
+    // ---- verdicts: ONE pairing check of the folded sums; only if that fails (some problem's proof is wrong) one per problem
+    void verdicts() {
+        bool all_true = false;
+        if (folded) {
+            const int v = check_pair((const JacQ*)(hb + L.poff_fold), vk);
+            if (v < 0) throw std::runtime_error("many-verification pass left no folded result");
+            all_true = v == 1;
+            if (tap) tap->fold_verdict = v;
+        }
+        if (all_true) {
+            for (int i = 0; i < Bc; i++)
+                if (live[i]) {
+                    if (poisoned(sums()[2 * (size_t)i]) || poisoned(sums()[2 * (size_t)i + 1])) { device_fault.store(1); break; }
+                    ver[i] = 1;
+                }
+        } else if (folded && e.vm_search_) {
+            search_wrong_proofs();
+        } else {
+            parallel_for(Bc, T, pool, [&](int i) { if (live[i]) check_single(i); });
+        }
+        if (device_fault.load()) throw std::runtime_error("many-verification pass left no result");
+        lap("pairing checks (host)");
+    }
+    void check_single(int i) {  // one problem's own pairing check
+        const int v = check_pair(sums() + 2 * (size_t)i, vk);
+        if (v < 0) device_fault.store(1);
+        else ver[i] = v;
+    }
+    // Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM (off_fprod): the search of vm_search.hpp over
+    // them; where it ends in single problems, each is checked on the host against its own sums, which the pass has read back anyway.
+    void search_wrong_proofs() {
+        vm::SearchView V = vm::search_view(L, Bc, L.off_fprod, T, pool, hb, vk, gpu, live.data(), ver, &device_fault);
+        V.check_single = [this](int i) { check_single(i); };
+        if (tap) { V.tap_probes = &tap->probes; V.tap_probe_sums = &tap->probe_sums; V.tap_device_probes = &tap->device_probes; }
+        vm::search_wrong_proofs(V, n_live, db, st);
+        if (tap && !tap->probes.empty()) tap->searched = 1;
+    }
 };
 
-// Some proof of the pass is wrong.  The weighted pairs rho_b * sum_b are still in HBM (off_fprod): the search of vm_search.hpp over them;
-// where it ends in single problems, each is checked on the host against its own sums, which the pass has read back anyway.
-void search_wrong_proofs(PassHost& V, int n_live, uint8_t* db, hipStream_t st) {
-    vm::SearchView S = vm::search_view(V.L, V.L.Bc, V.L.off_fprod, V.T, V.pool, V.hb, V.vk, V.gpu, V.live.data(), V.verified, &V.device_fault);
-    S.check_single = [&V](int i) { V.check_single(i); };
-    if (V.tap) { S.tap_probes = &V.tap->probes; S.tap_probe_sums = &V.tap->probe_sums; S.tap_device_probes = &V.tap->device_probes; }
-    vm::search_wrong_proofs(S, n_live, db, st);
-    if (V.tap && !V.tap->probes.empty()) V.tap->searched = 1;
-}
-}  // namespace
-
-int Engine::verify_cell_kzg_proof_batch_many_host(uint64_t n_batches, const uint64_t* n_commitments,
-                                                  const uint8_t* const* const* commitments, const uint64_t* n_indices,
-                                                  const uint64_t* const* cell_indices, const uint64_t* n_cells,
-                                                  const uint8_t* const* const* cells, const uint64_t* n_proofs,
-                                                  const uint8_t* const* const* proofs, int* verified, int* status, VerifyManyTap* tap) {
-    VerifyManyInput in;
-    in.n_commitments = n_commitments; in.n_indices = n_indices; in.n_cells = n_cells; in.n_proofs = n_proofs;
-    in.commitments = commitments; in.cell_indices = cell_indices; in.cells = cells; in.proofs = proofs;
-    return verify_cell_kzg_proof_batch_many(n_batches, in, verified, status, tap);
-}
-
 int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
-    const int B = (int)n_batches;
-    if (in.columns && !in.col_ready) {
-        // ---- the column source, once per call: what no column reads anything for; the ONE de-duplication of the call (the device form
-        // brings the 48 n_blobs commitment bytes down for it, behind what the caller's stream has queued); and the columns refused at
-        // validation taken OUT of the call, so that every column of a pass holds n_blobs cells and the per-(column, commitment) work of
-        // a pass (Bc n_u weights and products) is bounded by its cells -- a refused column costs a status word, as in _many
-        if (in.col_blobs == 0 || in.col_blobs > MAX_CELLS_PER_VERIFICATION) {
-            for (int b = 0; b < B; b++) { status[b] = validate_data_column(in.col_blobs, in.col_indices[b]); verified[b] = status[b] == OK; }
-            return OK;
+    return in.columns ? verify_data_columns_many((int)n_batches, in, verified, status, tap)
+                      : verify_cell_kzg_proof_batch_many_parts((int)n_batches, in, verified, status, tap);
+}
+
+// The column source, once per call: the ONE de-duplication (the device form brings the 48 n_blobs commitment bytes down for it, behind
+// what the caller's stream has queued; a host-form call sliced over a device list brings in.col, made once for all slices); and the
+// columns refused at validation taken OUT, so that every column of a pass holds n_blobs cells and its Bc n_u weights and products are
+// bounded by its cells.  keep[k]: the caller's column that goes on as problem k (in.col_place); the verdicts are scattered back by it.
+int Engine::verify_data_columns_many(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
+    const std::vector<uint64_t> keep = vm_kept_columns(in.col_blobs, (uint64_t)B, in.col_indices);
+    const size_t K = keep.size();
+    for (int b = 0; b < B; b++) { verified[b] = in.col_blobs == 0; status[b] = ERR_INPUT; }  // (no blobs: empty problems, verifier.rs:90-93)
+    for (size_t k = 0; k < K; k++) status[keep[k]] = OK;
+    if (K == 0 || in.col_blobs == 0) return OK;
+    ColumnCommitments cc;
+    VerifyManyInput go = in;
+    if (!in.col && in.col_device) {
+        try {
+            HIPCK(hipSetDevice(dev_));
+            cc.own.resize((size_t)in.col_blobs * 48);
+            HIPCK(hipStreamSynchronize(in.user_stream));
+            HIPCK(hipMemcpy(cc.own.data(), in.d_commitments, cc.own.size(), hipMemcpyDeviceToHost));
+        } catch (const std::exception& e) {
+            set_error(e);
+            return ERR_DEVICE;
         }
-        std::vector<uint64_t> keep;  // the columns that go on, in the caller's order
-        for (int b = 0; b < B; b++) {
-            verified[b] = 0;
-            status[b] = validate_data_column(in.col_blobs, in.col_indices[b]);
-            if (status[b] == OK) keep.push_back((uint64_t)b);
-        }
-        if (keep.empty()) return OK;
-        ColumnCommitments cc;
-        VerifyManyInput go = in;
-        go.col_ready = true;
-        if (!in.col) {
-            if (in.col_device) {
-                try {
-                    HIPCK(hipSetDevice(dev_));
-                    cc.own.resize((size_t)in.col_blobs * 48);
-                    HIPCK(hipStreamSynchronize(in.user_stream));
-                    HIPCK(hipMemcpy(cc.own.data(), in.d_commitments, cc.own.size(), hipMemcpyDeviceToHost));
-                } catch (const std::exception& e) {
-                    set_error(e);
-                    return ERR_DEVICE;
-                }
-                cc.from_own(in.col_blobs);
-            } else {
-                cc.from_list(in.col_blobs, in.col_commitments);
-            }
-            go.col = &cc;
-        }
-        if (keep.size() == (size_t)B) return verify_cell_kzg_proof_batch_many(n_batches, go, verified, status, tap);
-        if (tap) return ERR_INPUT;  // (the hook serves calls whose columns all pass validation: its outputs are indexed by column)
-        const size_t K = keep.size();
-        std::vector<uint64_t> idx(K), src(K);
-        std::vector<const uint8_t* const*> cl(in.col_device ? 0 : K), pf(in.col_device ? 0 : K);
-        for (size_t k = 0; k < K; k++) {
-            idx[k] = in.col_indices[keep[k]];
-            src[k] = in.col_src ? in.col_src[keep[k]] : in.col0 + keep[k];
-            if (!in.col_device) { cl[k] = in.cells[keep[k]]; pf[k] = in.proofs[keep[k]]; }
-        }
-        go.col_indices = idx.data();
-        if (in.col_device) { go.col_src = src.data(); go.col0 = 0; }
-        else { go.cells = cl.data(); go.proofs = pf.data(); }
-        std::vector<int> ver(K), st(K);
-        const int rc = verify_cell_kzg_proof_batch_many((uint64_t)K, go, ver.data(), st.data(), nullptr);
-        if (rc != OK) return rc;
-        for (size_t k = 0; k < K; k++) { verified[keep[k]] = ver[k]; status[keep[k]] = st[k]; }
-        return OK;
+        cc.from_own(in.col_blobs);
+    } else if (!in.col) {
+        cc.from_list(in.col_blobs, in.col_commitments);
     }
+    if (!in.col) go.col = &cc;
+    go.col_place = keep.data();
+    if (K == (size_t)B) return verify_cell_kzg_proof_batch_many_parts(B, go, verified, status, tap);
+    if (tap) return ERR_INPUT;  // (the hook serves calls whose columns all pass validation: its outputs are indexed by column)
+    std::vector<int> ver(K), st(K);
+    const int rc = verify_cell_kzg_proof_batch_many_parts((int)K, go, ver.data(), st.data(), nullptr);
+    if (rc != OK) return rc;
+    for (size_t k = 0; k < K; k++) { verified[keep[k]] = ver[k]; status[keep[k]] = st[k]; }
+    return OK;
+}
+
+// The body every source shares.  A LARGE call is cut into parts that run as passes of their own on different pass slots at the same
+// time: while one part's products are on the GPU the next one's 100+ MB are still being staged and hashed by the host threads (in one
+// pass the staging of a 1024-problem call came first, ~10 ms, and the GPU waited: 28.4-28.9 ms against 24.6-26.2).  Each part folds alone.
+int Engine::verify_cell_kzg_proof_batch_many_parts(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
     for (int b = 0; b < B; b++) { verified[b] = 0; status[b] = OK; }
     if (B == 0) return OK;
-    // A LARGE call is cut into parts that run as passes of their own on different pass slots at the same time: while one part's
-    // products are on the GPU the next one's 100+ MB are still being staged and hashed by the host threads (in one pass the
-    // staging of all 275 MB of a 1024-problem call came first, ~10 ms, and the GPU waited for it).  Each part folds its own
-    // pairing check (one pass, round 3's form: 28.4-28.9 ms against 24.6-26.2 for 1024 problems).
     constexpr int max_parts = VM_SLOTS < 3 ? (int)VM_SLOTS : 3;
-    uint64_t total_cells = 0;
-    if (max_parts > 1 && B >= VM_SPLIT_MIN_PROBLEMS)
-        for (int b = 0; b < B; b++) total_cells += in.cells_of((uint64_t)b);
-    if (total_cells < (uint64_t)VM_SPLIT_MIN_CELLS) return verify_cell_kzg_proof_batch_many_part(B, in, verified, status, tap);
-    std::vector<int> cut{0};
-    uint64_t acc = 0;
-    for (int b = 0; b < B; b++) {  // equal shares of the cells
-        acc += in.cells_of((uint64_t)b);
-        if ((int)cut.size() < max_parts && acc * max_parts >= total_cells * cut.size() && b + 1 < B) cut.push_back(b + 1);
-    }
-    cut.push_back(B);
+    const std::vector<int> cut = vm_call_parts(B, [&](int b) { return in.cells_of((uint64_t)b); }, VM_SPLIT_MIN_PROBLEMS, VM_SPLIT_MIN_CELLS, max_parts);
     const int parts = (int)cut.size() - 1;
+    if (parts == 1) return verify_cell_kzg_proof_batch_many_part(B, in, verified, status, tap);
     std::vector<int> rcs(parts, OK);
     std::vector<std::string> errs(parts);  // (the error text belongs to the thread that ran the part)
     const auto thrown = run_side_by_side(parts, [&](int p) {
@@ -336,228 +512,30 @@ Engine::PassSlot Engine::lease_pass_slot(bool prefer_idle_work_set) {
     return {&vm_slot_[lease.index], std::move(lease.lock), st ? st : stream_};
 }
 
+// One part: the slot, the source (flat arrays: the mirror down), validation and de-duplication per problem, then a pass per chunk of
+// at most VM_CHUNK_CELLS cells that holds a cell (the pinned slab and the arena stay bounded)
 int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
     const VmHost host = vm_host();
-    const int T = host.T;
-    HostPool* const pool = host.pool;
     PassSlot ps = lease_pass_slot(/*prefer_idle_work_set=*/true);
-    VmSlot* const slot = ps.slot;
     try {
         HIPCK(hipSetDevice(dev_));
-        const hipStream_t st = ps.stream;
         TraceLap lap{knobs_.trace, "verify_many"};
-        // ---- flat device source: commitments and indices of the call's cells come down (56 bytes per cell) behind whatever the
-        // caller's stream has queued; the host validates and de-duplicates from this pinned mirror, and the unique commitments of a
-        // pass are gathered out of it
-        // A problem beyond the size bound is refused by its validation below (status 3) and has no place in the mirror: nothing of it is
-        // read, and the mirror is sized by problems of at most MAX_CELLS_PER_VERIFICATION cells only.
-        const uint8_t* mirror_c = nullptr;
-        const uint64_t* mirror_i = nullptr;
-        std::vector<Problem> pr(B);
-        if (in.columns) {  // (the commitments came down with the call, the indices are the host's: nothing to mirror)
-            for (int b = 0; b < B; b++) pr[b].src0 = (in.col_src ? in.col_src[b] : in.col0 + (uint64_t)b) * in.col_blobs;
-            if (in.on_device()) order_behind(st, in.user_stream, slot->ordered);
-        } else if (in.on_device()) {
-            uint64_t N = 0;
-            for (int b = 0; b < B; b++) {
-                pr[b].src0 = in.cell_starts[b];
-                pr[b].mir0 = N;
-                if (in.cells_of((uint64_t)b) <= MAX_CELLS_PER_VERIFICATION) N += in.cells_of((uint64_t)b);
-            }
-            order_behind(st, in.user_stream, slot->ordered);
-            if (N) {
-                grow_pinned(slot->src_pin, slot->src_pin_cap, (size_t)N * 56);
-                uint8_t* const pin_c = slot->src_pin;
-                uint64_t* const pin_i = reinterpret_cast<uint64_t*>(slot->src_pin + (size_t)N * 48);
-                for (int b = 0; b < B;) {  // one pair of copies per run of problems within the bound (they follow each other in both)
-                    uint64_t run = 0;
-                    int e = b;
-                    while (e < B && in.cells_of((uint64_t)e) <= MAX_CELLS_PER_VERIFICATION) run += in.cells_of((uint64_t)e++);
-                    if (run) {
-                        HIPCK(hipMemcpyAsync(pin_c + (size_t)pr[b].mir0 * 48, in.d_commitments + (size_t)pr[b].src0 * 48, (size_t)run * 48, hipMemcpyDeviceToHost, st));
-                        HIPCK(hipMemcpyAsync(pin_i + pr[b].mir0, in.d_cell_indices + pr[b].src0, (size_t)run * 8, hipMemcpyDeviceToHost, st));
-                    }
-                    b = e < B ? e + 1 : e;  // (e is the problem beyond the bound that ended the run)
-                }
-                SYNC_CHECKED(st);
-                mirror_c = pin_c;
-                mirror_i = pin_i;
-            }
+        CellSource S(in, B);
+        if (S.device) order_behind(ps.stream, in.user_stream, ps.slot->ordered);
+        if (S.device && !S.shared) {  // (columns: the commitments came down with the call, the indices are the host's: nothing to mirror)
+            mirror_down(S, ps.slot->src_pin, ps.slot->src_pin_cap, ps.stream);
             lap("commitments + indices down");
         }
-        // ---- per problem: validation (verifier.rs:123-164) and de-duplication
-        parallel_for(B, T, pool, [&](int b) {
-            const uint64_t nb = in.cells_of((uint64_t)b);
-            Problem& p = pr[b];
-            if (in.columns) {  // (verify_host.hpp: validate_data_column; every column refers to the call's one de-duplication)
-                status[b] = validate_data_column(nb, in.col_indices[b]);
-                if (status[b] != OK) return;
-                if (nb == 0) { verified[b] = 1; return; }
-                p.uniq = in.col->uniq.data(); p.row = in.col->row.data();
-                p.n = (int)nb;
-                p.m = (int)in.col->uniq.size();
-                return;
-            }
-            if (in.on_device()) {  // (the four lengths are one by construction: what is left is the bound, checked before an index is read, and the indices)
-                status[b] = validate_cell_batch(nb, nb, nb, nb, mirror_i + p.mir0);
-            } else {
-                status[b] = validate_cell_batch(in.n_commitments[b], in.n_indices[b], nb, in.n_proofs[b], in.cell_indices[b]);
-            }
-            if (status[b] != OK) return;
-            if (nb == 0) { verified[b] = 1; return; }  // verifier.rs:90-93
-            if (in.on_device()) dedup_commitments_flat(nb, mirror_c + (size_t)p.mir0 * 48, p.own_uniq, p.own_row);
-            else dedup_commitments(nb, in.commitments[b], p.own_uniq, p.own_row);
-            p.uniq = p.own_uniq.data(); p.row = p.own_row.data();
-            p.n = (int)nb;
-            p.m = (int)p.own_uniq.size();
+        std::vector<Problem> pr(B);
+        parallel_for(B, host.T, host.pool, [&](int b) {
+            status[b] = S.admit(b, pr[b]);
+            if (status[b] == OK && pr[b].n == 0) verified[b] = 1;  // verifier.rs:90-93
         });
         lap("validation + de-duplication");
-        // ---- chunks of problems: at most CHUNK_CELLS cells per pass (the pinned slab and the arena stay bounded)
-        constexpr int CHUNK_CELLS = VM_CHUNK_CELLS;
-        bool fold = true;  // one folded pairing check per pass instead of one per problem (falls back to per-problem checks when it fails)
-        if (!knobs_.vm_fold) fold = false;  // (test hook: one pairing per problem)
-        for (int b0 = 0; b0 < B;) {
-            int b1 = b0, nn = 0, mm = 0;
-            while (b1 < B && (b1 == b0 || nn + pr[b1].n <= CHUNK_CELLS)) { nn += pr[b1].n; mm += pr[b1].m; b1++; }
-            const int Bc = b1 - b0, n = nn, m = in.columns ? (int)in.col->uniq.size() : mm;  // (columns: the pass's one list)
-            if (n == 0) { b0 = b1; continue; }
-            // A pass of a few problems (concurrent single calls combined) is a chain of latencies, not work: it takes the SHORT-CHAIN
-            // form -- subgroup tests and the interpolation commitments' terms inside the ONE launch of all scalar multiplications
-            // (k_vm_products), no fold (its 128-bit multiplication per problem is a 1.4 ms chain; <= 2 T pairing checks are one or
-            // two rounds of the host threads) -- decode 0.45 + products 1.7 + sums 0.2 ms of GPU instead of ~6
-            const bool small = vm_small_max_ != 0 && Bc <= (vm_small_max_ > 0 ? vm_small_max_ : 2 * T);
-            const PassLayout L(n, m, Bc, small, in.leaf, in.columns);
-            grow_device(slot->dev, slot->dev_cap, L.dev_bytes, st);
-            grow_pinned(slot->pin, slot->pin_cap, L.pin_bytes);
-            uint8_t *hb = slot->pin, *db = (uint8_t*)slot->dev;
-            PassHost H{L, pr.data() + b0, in.from((uint64_t)b0), mirror_i, hb, T, pool, {g2_tau_.get(), g2_neg_gen_.get()}, device_pairing(0), verified + b0};
-            H.tap = tap;
-            H.stage();
-            lap("stage (host)");
-            int* h_st = H.h_status();
-            HIPCK(hipMemsetAsync(db + L.off_stp, 0xff, (size_t)(n + m) * 4, st));
-            HIPCK(hipMemsetAsync(db + L.off_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ, st));
-            HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ, st));
-            HIPCK(hipMemsetAsync(db + L.off_ste, 0, (size_t)Bc * 4, st));
-            if (!in.on_device()) {
-                HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
-            } else {
-                // only the host-made parts go up; proofs and cells move inside HBM, from any byte address, one copy per run of
-                // problems that follow each other in the caller's arrays (a problem refused at validation leaves a gap)
-                HIPCK(hipMemcpyAsync(db + L.off_c, hb + L.off_c, (size_t)m * 48, hipMemcpyHostToDevice, st));
-                HIPCK(hipMemcpyAsync(db + L.off_idx, hb + L.off_idx, L.in_bytes - L.off_idx, hipMemcpyHostToDevice, st));
-                uint64_t run0 = 0, run = 0, at = 0;
-                auto flush = [&] {
-                    if (!run) return;
-                    HIPCK(hipMemcpyAsync(db + L.off_p + (size_t)at * 48, in.d_proofs + (size_t)run0 * 48, (size_t)run * 48, hipMemcpyDeviceToDevice, st));
-                    HIPCK(hipMemcpyAsync(db + L.off_cells + (size_t)at * BYTES_PER_CELL, in.d_cells + (size_t)run0 * BYTES_PER_CELL,
-                                         (size_t)run * BYTES_PER_CELL, hipMemcpyDeviceToDevice, st));
-                    at += run;
-                    run = 0;
-                };
-                for (int i = 0; i < Bc; i++) {
-                    const Problem& p = pr[b0 + i];
-                    if (p.n == 0) continue;
-                    if (run && p.src0 != run0 + run) flush();
-                    if (!run) run0 = p.src0;
-                    run += (uint64_t)p.n;
-                }
-                flush();
-                if (!in.leaf) {  // the reference's transcript hashes every byte on the host: the pass's proofs and cells come down, compacted
-                    HIPCK(hipMemcpyAsync(hb + L.off_p, db + L.off_p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
-                    HIPCK(hipMemcpyAsync(hb + L.off_cells, db + L.off_cells, (size_t)n * BYTES_PER_CELL, hipMemcpyDeviceToHost, st));
-                }
-            }
-            const bool hash_waits = in.leaf || in.on_device();  // the host's hashes read what a copy on st brings down
-            if (hash_waits && !slot->hash_inputs_down) HIPCK(hipEventCreateWithFlags(&slot->hash_inputs_down, hipEventDisableTiming));
-            if (in.leaf) {
-                // the leaves of all the pass's cells straight out of the arena (its offsets are multiples of 256: the kernel's 16-byte
-                // loads), in order on the pass's stream: a stream of its own would be a fifth one (lease_pass_slot), and a wave per 64 cells
-                // for 35 dependent compressions is short against the decoding behind it
-                launch::sha256_cell_leaves(n, db + L.off_c, (const int*)(db + L.off_row), (const int*)(db + L.off_idx), db + L.off_p, db + L.off_cells,
-                                           db + L.off_leaf, st, (const int*)(db + L.off_pos));
-                HIPCK(hipMemcpyAsync(hb + L.poff_leaf, db + L.off_leaf, (size_t)n * 32, hipMemcpyDeviceToHost, st));
-            }
-            if (hash_waits) HIPCK(hipEventRecord(slot->hash_inputs_down, st));
-            // ---- challenge-free GPU work: decode (on curve) + subgroup tests of [proofs | commitments], cells, interpolation
-            G1Affine* d_pts = (G1Affine*)(db + L.off_pts);
-            int* d_stp = (int*)(db + L.off_stp);
-            launch::g1_decode2(db + L.off_p, d_pts, d_stp, n, db + L.off_c, d_pts + n, d_stp + n, m, beta_, st);
-            if (!small) launch::g1_subgroup2(d_pts, d_stp, n, d_pts + n, d_stp + n, m, beta_, st);  // (small: inside k_vm_products)
-            launch::cells_to_fr(db + L.off_cells, db + L.off_evals, nullptr, (int*)(db + L.off_ste), (const int*)(db + L.off_bat), nullptr, n, st);
-            launch::interp_cells(db + L.off_evals, (const int*)(db + L.off_idx), d_w8192_, inv64_, db + L.off_coef, n, st);
-            HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));
-            HIPCK(hipMemcpyAsync(h_st + n + m, db + L.off_ste, (size_t)Bc * 4, hipMemcpyDeviceToHost, st));
-            HIPCK(hipGetLastError());
-            lap("enqueue (host)");
-            if (hash_waits) HIPCK(hipEventSynchronize(slot->hash_inputs_down));
-            H.hash_challenges();  // meanwhile, on the host threads
-            lap(in.leaf ? "leaf hashes (GPU) + roots (host)" : "sha256 transcripts (host)");
-            SYNC_CHECKED(st);     // (the challenge-free GPU work has long finished under the hashes: a short wait)
-            lap("wait decode");
-            int n_live = H.judge(status + b0);  // (a small pass judges again once its subgroup tests are in)
-            const bool folded = fold && n_live >= 2 && !small;
-            if (folded) H.fold_weights();
-            HIPCK(hipMemcpyAsync(db + L.off_pow, hb + L.off_pow, L.in2_bytes - L.off_pow, hipMemcpyHostToDevice, st));  // power tables + weights
-            // ---- per-problem scalars, weights, interpolation sums; every scalar multiplication; the two sums per problem
-            const int *d_cs = (const int*)(db + L.off_cs), *d_rs = (const int*)(db + L.off_rs);
-            // one sequence for both sources (launch.hpp: a null pointer tells a launcher which).  The column source has r^k per cell and ONE
-            // h^64 per column: n + Bc m products over the one decoded commitment table, then h^64 A_b as a dependent launch of Bc quads
-            // behind the reduction of A_b, inside vm_sums
-            const bool cols = in.columns;
-            launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_cs, d_w8192_,
-                               db + L.off_rp, db + L.off_s1, cols ? nullptr : db + L.off_s2, cols ? db + L.off_h : nullptr, n, Bc, st);
-            launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), cols ? nullptr : (const int*)(db + L.off_rowb), d_cs, db + L.off_w, m, Bc, st);
-            launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
-            uint64_t muls = (uint64_t)launch::vm_products(d_pts, db + L.off_s1, cols ? nullptr : db + L.off_s2, db + L.off_w, db + L.off_isc, d_srs_,
-                                                          db + L.off_prod, n, m, Bc, small, d_stp, beta_, st);
-            // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
-            if (!small) launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
-            muls += (uint64_t)launch::vm_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, cols ? nullptr : d_rs, db + L.off_h, db + L.off_out,
-                                              n, m, Bc, beta_, st);
-            if (small) HIPCK(hipMemcpyAsync(h_st, d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
-            if (folded) {
-                launch::vm_fold(db + L.off_out, (const uint32_t*)(db + L.off_rho), db + L.off_fprod, db + L.off_fold, Bc, beta_, st);
-                HIPCK(hipMemcpyAsync(hb + L.poff_fold, db + L.off_fold, (size_t)2 * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
-            }
-            HIPCK(hipMemcpyAsync(hb + L.poff_out, db + L.off_out, (size_t)2 * Bc * launch::SIZEOF_JACQ, hipMemcpyDeviceToHost, st));
-            SYNC_CHECKED(st);
-            lap("scalars + products + sums (GPU)");
-            if (small) n_live = H.judge(status + b0);
-            if (tap) {
-                tap->digests = H.digests;
-                if (in.leaf) tap->leaves.assign(hb + L.poff_leaf, hb + L.poff_leaf + (size_t)n * 32);
-                tap->passes++;
-                tap->small = small; tap->folded = folded;
-                tap->commitments_decoded = (uint64_t)m; tap->scalar_muls = muls;
-                tap->sums.assign(hb + L.poff_out, hb + L.poff_out + (size_t)2 * Bc * launch::SIZEOF_JACQ);
-                tap->rho.assign((const uint32_t*)(hb + L.off_rho), (const uint32_t*)(hb + L.off_rho) + 4 * (size_t)Bc);
-                if (folded) tap->fold.assign(hb + L.poff_fold, hb + L.poff_fold + (size_t)2 * launch::SIZEOF_JACQ);
-            }
-            // ---- verdicts: ONE pairing check of the folded sums; only if that fails (some problem's proof is wrong) one per problem
-            bool all_true = false;
-            if (folded) {
-                const int v = check_pair((const JacQ*)(hb + L.poff_fold), H.vk);
-                if (v < 0) throw std::runtime_error("many-verification pass left no folded result");
-                all_true = v == 1;
-                if (tap) tap->fold_verdict = v;
-            }
-            if (all_true) {
-                for (int i = 0; i < Bc; i++)
-                    if (H.live[i]) {
-                        if (poisoned(H.sums()[2 * (size_t)i]) || poisoned(H.sums()[2 * (size_t)i + 1])) { H.device_fault.store(1); break; }
-                        verified[b0 + i] = 1;
-                    }
-            } else if (folded && vm_search_) {
-                search_wrong_proofs(H, n_live, db, st);
-            } else {
-                parallel_for(Bc, T, pool, [&](int i) {
-                    if (H.live[i]) H.check_single(i);
-                });
-            }
-            if (H.device_fault.load()) throw std::runtime_error("many-verification pass left no result");
-            lap("pairing checks (host)");
-            b0 = b1;
+        for (int b0 = 0, b1 = 0; b0 < B; b0 = b1) {
+            b1 = vm_chunk_end(B, b0, [&](int b) { return (uint64_t)pr[b].n; }, (uint64_t)VM_CHUNK_CELLS);
+            if (CellManyPass::cells(pr.data() + b0, b1 - b0) == 0) continue;
+            CellManyPass{*this, S, pr.data() + b0, b0, b1 - b0, verified + b0, status + b0, tap, host.T, host.pool, ps.slot, ps.stream, lap}.run();
         }
     } catch (const std::exception& e) {
         set_error(e);
@@ -639,8 +617,8 @@ int Engine::verify_cell_kzg_proof_batch_combined(uint64_t n_commitments, const u
             l0[i] = batch[i]->n[0]; l1[i] = batch[i]->n[1]; l2[i] = batch[i]->n[2]; l3[i] = batch[i]->n[3];
             pc[i] = batch[i]->commitments; pi[i] = batch[i]->cell_indices; pl[i] = batch[i]->cells; pp[i] = batch[i]->proofs;
         }
-        rc = verify_cell_kzg_proof_batch_many_host(B, l0.data(), pc.data(), l1.data(), pi.data(), l2.data(), pl.data(), l3.data(),
-                                                   pp.data(), ver.data(), st.data());
+        rc = verify_cell_kzg_proof_batch_many(B, VerifyManyInput::lists(l0.data(), pc.data(), l1.data(), pi.data(), l2.data(), pl.data(), l3.data(), pp.data(),
+                                                                        /*leaf=*/false), ver.data(), st.data());
         if (rc == ERR_DEVICE) why = last_error();
       }
     } catch (const std::exception& e) {

@@ -10,7 +10,8 @@ Contexts as test_verify_inputs.py's many_ctx: small tables, two host threads.
 2. Every form a pass takes (verify_transcript.many_cases(), in process), three ways: host flagged, device flagged, device unflagged
    (the last against the reference-transcript statement test_verify_inputs.py holds the host form to).
 3. The public calls agree on a pass of every ManyProblem kind; the call-level InvalidInput cases with a NULL context.
-4. Byte arrays 8 bytes into their allocations, produced by asynchronous copies on the caller's stream.
+4. Byte arrays 8 bytes into their allocations, produced by asynchronous copies on the caller's stream; a refused problem beside an
+   empty one between two runs of device-to-device copies (3, 0, 2, 65, 1 cells), against the pointer-list form, byte for byte.
 5. Cuts: 192 x 128 cells (three concurrent parts), 1025 x 128 + 3 cells (parts again) and 136 x 1024 cells (two chunks on one slot, with
    refused problems around the chunk boundary), one swapped-proof problem beyond the first cut; a problem of 2^24 cells is refused unread.
 6. The reference's 30 verify_cell_kzg_proof_batch vectors as the problems of one call.
@@ -332,6 +333,49 @@ def test_shifted_addresses_and_inputs_produced_on_the_callers_stream(ctx, materi
     d2 = DeviceArrays(problems, shift=8, stream=stream)
     assert d2.call(ctx, False, stream=stream.cuda_stream) == want
     stream.synchronize()
+
+
+GAP_COUNTS = [3, 0, 2, 65, 1]
+
+
+@pytest.mark.parametrize("wrong", [False, True])
+def test_a_refused_problem_beside_an_empty_one_between_two_copy_runs(ctx, material, wrong):
+    """Flat device arrays whose third problem is refused at validation (an index of 128): its two entries lie between the two runs of
+    device-to-device copies, the empty problem beside it holds none.  Everything equals the pointer-list form of the same problems."""
+    import random
+    rng = random.Random("many-leaf:gap")
+    cases = [T.CellCase("gap-%d" % n, [(rng.choice((0, 1, 2)), rng.randrange(T.N_CELLS)) for _ in range(n)]) for n in GAP_COUNTS]
+    proofs = cases[3].args(material)[3]
+    swap = next((i, j) for i in range(65) for j in range(i + 1, 65) if proofs[i] != proofs[j])
+    qs = [T.ManyProblem(cases[0]), T.ManyProblem(cases[1], "empty"), T.ManyProblem(cases[2], "bad-index"),
+          T.ManyProblem(cases[3], "swapped", swap) if wrong else T.ManyProblem(cases[3]), T.ManyProblem(cases[4])]
+    problems = [q.args(material) for q in qs]
+    assert [len(p[1]) for p in problems] == GAP_COUNTS and problems[2][1] == [problems[2][1][0], 128]
+    accepted, verdicts = [0, 1, 3, 4], [True, True, False, not wrong, True]
+    d = DeviceArrays(problems)
+    assert list(d.starts) == [0, 3, 3, 5, 70, 71]
+    for flags in (0, LEAF):
+        lists = ctx.verify_cell_kzg_proof_batch_many(problems, leaf_transcript=bool(flags))
+        assert lists == (verdicts, [0, 0, 3, 0, 0]), (flags, lists)
+        assert d.call(ctx, bool(flags)) == lists, flags
+        rc, host = many_sums(ctx, problems, "host", flags)
+        assert rc == 0
+        rc, dev = many_sums(ctx, problems, "device", flags)
+        assert rc == 0
+        assert dev.status == [0, 0, 3, 0, 0] and host.status == dev.status, (flags, dev.status)
+        assert dev.verified == host.verified == verdicts, (flags, dev.verified)
+        # five problems under two host threads: the folded form; when the fold fails, the search's plan for four live problems
+        plan = T.search_plan([True, False, False, True, True], verdicts, T.MANY_HOST_THREADS) if wrong else []
+        form = (False, True, bool(plan), 0 if wrong else 1)
+        assert (dev.small, dev.folded, dev.searched, dev.fold_verdict) == form == (host.small, host.folded, host.searched, host.fold_verdict), flags
+        for b in accepted:
+            assert dev.sums[b] == host.sums[b] and dev.rho[b] == host.rho[b] and dev.digests[b] == host.digests[b], (flags, b)
+        assert dev.rho[1] == dev.rho[2] == 0 and all(dev.rho[b] for b in (0, 3, 4))
+        assert dev.fold == host.fold and dev.fold != bytes(96), flags
+        assert dev.n_probes == host.n_probes == len(plan) and dev.probes == host.probes, flags
+        assert [(lo, hi, ok) for lo, hi, _, ok in dev.probes] == plan, flags
+        if flags:
+            assert dev.leaves == host.leaves and dev.leaves[3:5] == [bytes(32)] * 2 and bytes(32) not in dev.leaves[:3] + dev.leaves[5:]
 
 
 # ---- 5. cuts ------------------------------------------------------------------------------------------------------------------------------------
