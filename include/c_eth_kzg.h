@@ -515,6 +515,54 @@ CResult eth_kzg_amd_verify_data_columns_device(const DASContext *ctx, uint64_t n
                                                const uint8_t *d_proofs, uint32_t flags, bool *verified, int32_t *status,
                                                void *hip_stream);
 
+/* ---- a block's data columns computed and recovered in column layout ----
+ * The two neighbours of eth_kzg_amd_verify_data_columns, in its layout: cells and proofs as [column][blob], which is how the 128 data
+ * column sidecars of a block carry them, so that a caller transposes nothing between the three calls.
+ *   out_cells[c][i] / d_out_cells [128][n_blobs][2048]    cell c of blob i        out_proofs[c][i] / d_out_proofs [128][n_blobs][48]
+ *
+ * eth_kzg_amd_compute_data_columns / _device -- the proposer's call: everything the sidecars of a block carry, from its blobs.
+ * Contract: for blob i, status[i], the commitment and the bytes of cell c and proof c are exactly what
+ * eth_kzg_amd_blob_to_kzg_commitment_batch and eth_kzg_amd_compute_cells_and_kzg_proofs_batch (device form: the _device forms of the
+ * two) give for blob i at cell c.  Each of the three outputs may be NULL and is then not computed; status may be NULL.  A blob with
+ * status 1 (an element >= r) leaves its own slots untouched in the host form and unspecified in the device form, and disturbs no other
+ * blob's bytes.  Device form: status on the HOST; stream, ordering behind the caller's queued work, asynchronous return and alignment
+ * as eth_kzg_amd_compute_cells_and_kzg_proofs_device -- with status == NULL and a stream given the call returns without synchronising.
+ * How: the blobs are decoded ONCE per sub-batch -- one launch leaves the coefficients in the form the proofs' stages read and in the
+ * canonical form the commitment's fixed-base MSM reads, where the two separate calls decode every blob twice -- and the kernels that
+ * write cells and proofs store every byte once, at its column address: there is no transposition pass and no [blob][128] copy.
+ *
+ * eth_kzg_amd_recover_data_columns / _device -- the supernode's call: all 128 columns from n_columns >= 64 of them.
+ *   column_indices[j]  HOST, the cell index of the j-th column given, strictly ascending
+ *   cells[j][i] / d_cells [n_columns][n_blobs][2048]      the cell of blob i in that column
+ * Contract: for blob i, status[i] and the bytes are exactly what eth_kzg_amd_recover_cells_and_proofs_batch gives for the list
+ * (cells[0][i] .. cells[n_columns-1][i], column_indices).  A bad index list -- fewer than 64 or more than 128 entries, not strictly
+ * ascending, an index >= 128 -- therefore marks EVERY blob 3, before anything is launched.  A non-canonical element gives status 1 for
+ * its blob only, an inconsistent cell status 4 for its blob only; outputs of such a blob: untouched (host form), unspecified (device
+ * form).  out_cells / out_proofs may be NULL.  Device form: streams and synchronisation as eth_kzg_amd_recover_cells_and_proofs_device:
+ * the decode runs on the library's stream behind what hip_stream has queued and has completed when the call returns.
+ * How: every blob of a block misses the same columns, so ONE vanishing polynomial is built and evaluated per call, not one per blob;
+ * the present cells are read where they lie in the column matrix, and the outputs are written at their column addresses.
+ *
+ * Err("InvalidInput...") for the call, before the context is touched: n_blobs > 2^24; a NULL array with a non-zero count (blobs; cells;
+ * column_indices with n_columns > 0; status in the recover forms).  n_blobs = 0 is Ok.
+ * Device lists: the host forms are cut into contiguous slices by BLOB over the listed devices, the caller's pointers being the gather
+ * target as in the other batched calls; the device forms run on the device that owns the buffers -- all device pointers given are
+ * resolved, and anything but device memory of one listed device is Err("InvalidInput...").
+ * Out of scope: passing present columns through instead of recomputing them; returning only the missing columns; sharding a device
+ * form over GPUs; the Node binding.  When to take the calls, and what was measured: INTEGRATION.md, DESIGN.md section 5. */
+CResult eth_kzg_amd_compute_data_columns(const DASContext *ctx, uint64_t n_blobs, const uint8_t *const *blobs,
+                                         uint8_t *const *out_commitments, uint8_t *const *const *out_cells,
+                                         uint8_t *const *const *out_proofs, int32_t *status);
+CResult eth_kzg_amd_compute_data_columns_device(const DASContext *ctx, uint64_t n_blobs, const uint8_t *d_blobs,
+                                                uint8_t *d_out_commitments, uint8_t *d_out_cells, uint8_t *d_out_proofs,
+                                                int32_t *status, void *hip_stream);
+CResult eth_kzg_amd_recover_data_columns(const DASContext *ctx, uint64_t n_blobs, uint64_t n_columns,
+                                         const uint64_t *column_indices, const uint8_t *const *const *cells,
+                                         uint8_t *const *const *out_cells, uint8_t *const *const *out_proofs, int32_t *status);
+CResult eth_kzg_amd_recover_data_columns_device(const DASContext *ctx, uint64_t n_blobs, uint64_t n_columns,
+                                                const uint64_t *column_indices, const uint8_t *d_cells, uint8_t *d_out_cells,
+                                                uint8_t *d_out_proofs, int32_t *status, void *hip_stream);
+
 /* Introspection used by bench.py / DESIGN.md: bytes of both window tables resident in HBM; nominal window width w of the FK20
  * table in use (a GLV table: ceil(128 / w) windows over the two 128-bit halves of each scalar, packed 96-byte entries: 16
  * gathered additions per base at w = 16, 32 at w = 8 -- the start tables, and all there is with use_precomp = false). */

@@ -72,6 +72,8 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_kzg_proof_many", "eth_kzg_amd_verify_kzg_proof_many_device",
     "eth_kzg_amd_verify_blob_kzg_proof_many", "eth_kzg_amd_verify_blob_kzg_proof_many_device",
     "eth_kzg_amd_verify_data_columns", "eth_kzg_amd_verify_data_columns_device",
+    "eth_kzg_amd_compute_data_columns", "eth_kzg_amd_compute_data_columns_device",
+    "eth_kzg_amd_recover_data_columns", "eth_kzg_amd_recover_data_columns_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
     "eth_kzg_amd_set_profiling", "eth_kzg_amd_get_stage_times",
     "eth_kzg_amd_comm_probe", "eth_kzg_amd_comm_unique_id", "eth_kzg_amd_comm_init", "eth_kzg_amd_comm_info",
@@ -197,6 +199,10 @@ def load_library():
         "eth_kzg_amd_verify_blob_kzg_proof_many_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_verify_data_columns": [P, U64, P, U64, P, P, P, C.c_uint32, P, P],
         "eth_kzg_amd_verify_data_columns_device": [P, U64, P, U64, P, P, P, C.c_uint32, P, P, P],
+        "eth_kzg_amd_compute_data_columns": [P, U64, P, P, P, P, P],
+        "eth_kzg_amd_compute_data_columns_device": [P, U64, P, P, P, P, P, P],
+        "eth_kzg_amd_recover_data_columns": [P, U64, U64, P, P, P, P, P],
+        "eth_kzg_amd_recover_data_columns_device": [P, U64, U64, P, P, P, P, P, P],
     }.items():
         if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
             getattr(lib, name).restype = CResult
@@ -666,6 +672,73 @@ class DASContext:
             self._ctx, n_blobs, C.c_void_p(d_commitments), nc, _vp(idx), C.c_void_p(d_cells), C.c_void_p(d_proofs),
             VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st, C.c_void_p(stream) if stream else None))
         return [bool(v) for v in ver][:nc], list(st)[:nc]
+
+    # ---- a block's data columns computed and recovered in column layout (cells[c][i] / proofs[c][i]: blob i in column c)
+    def compute_data_columns(self, blobs, want_commitments=True, want_cells=True, want_proofs=True, prefill=0):
+        """The proposer's call (eth_kzg_amd_compute_data_columns): blobs -> (status list, commitments[i], cells[c][i], proofs[c][i]) with
+        c over the 128 columns; an output that was not asked for is None.  Byte for byte what blob_to_kzg_commitment_batch and
+        compute_cells_and_kzg_proofs_batch give, transposed; the slots of a blob with status 1 come back as they were: `prefill` bytes."""
+        n = len(blobs)
+        if any(len(b) != BYTES_PER_BLOB for b in blobs):
+            raise KzgError("InvalidLength")
+        ba, _kb = _flat_ptrs(blobs, BYTES_PER_BLOB)
+        comm, ci, _co = _out_ptrs(1, n, 48)
+        cells, _ci, cpp = _out_ptrs(CELLS_PER_EXT_BLOB, n, BYTES_PER_CELL)
+        proofs, _pi, ppp = _out_ptrs(CELLS_PER_EXT_BLOB, n, 48)
+        for out in (comm, cells, proofs):
+            out.fill(prefill)
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_compute_data_columns(
+            self._ctx, n, _vp(ba) if n else None, _vp(ci) if want_commitments else None, _vp(cpp) if want_cells else None,
+            _vp(ppp) if want_proofs else None, st))
+        return (list(st)[:n], _split(comm, 1, n, 48)[0] if want_commitments else None,
+                _split(cells, CELLS_PER_EXT_BLOB, n, BYTES_PER_CELL) if want_cells else None,
+                _split(proofs, CELLS_PER_EXT_BLOB, n, 48) if want_proofs else None)
+
+    def compute_data_columns_device(self, n_blobs, d_blobs, d_commitments, d_cells, d_proofs, want_status=True, stream=None):
+        """The same on flat buffers in device memory (eth_kzg_amd_compute_data_columns_device; integer device addresses): d_commitments
+        n_blobs*48, d_cells [128][n_blobs][2048], d_proofs [128][n_blobs][48], each may be 0 / None.  want_status=False with a stream:
+        returns without synchronising."""
+        st = (C.c_int32 * max(1, n_blobs))() if want_status else None
+        self._check(self._lib.eth_kzg_amd_compute_data_columns_device(
+            self._ctx, n_blobs, C.c_void_p(d_blobs) if d_blobs else None, C.c_void_p(d_commitments) if d_commitments else None,
+            C.c_void_p(d_cells) if d_cells else None, C.c_void_p(d_proofs) if d_proofs else None, st, C.c_void_p(stream) if stream else None))
+        return list(st)[:n_blobs] if want_status else None
+
+    def recover_data_columns(self, column_indices, cells, want_cells=True, want_proofs=True, prefill=0):
+        """The supernode's call (eth_kzg_amd_recover_data_columns): column_indices[j] and cells[j][i] (blob i in the j-th column given)
+        -> (status list per blob, cells[c][i], proofs[c][i]) over all 128 columns; exactly recover_cells_and_kzg_proofs_batch per blob.
+        The slots of a blob whose status is not 0 come back as they were: `prefill` bytes."""
+        nc = len(column_indices)
+        nb = len(cells[0]) if nc else 0
+        if len(cells) != nc or any(len(col) != nb for col in cells) or any(len(c) != BYTES_PER_CELL for col in cells for c in col):
+            raise KzgError("InvalidLength")
+        idx = np.array(column_indices, dtype=np.uint64) if nc else np.zeros(1, np.uint64)
+        keep, tab = [], np.zeros(max(1, nc), dtype=np.uint64)
+        for j in range(nc):
+            cla, k = _flat_ptrs(cells[j], BYTES_PER_CELL)
+            keep += [cla, k]
+            tab[j] = cla.ctypes.data
+        out_cells, _ci, ocp = _out_ptrs(CELLS_PER_EXT_BLOB, nb, BYTES_PER_CELL)
+        out_proofs, _pi, opp = _out_ptrs(CELLS_PER_EXT_BLOB, nb, 48)
+        out_cells.fill(prefill)
+        out_proofs.fill(prefill)
+        st = (C.c_int32 * max(1, nb))()
+        self._check(self._lib.eth_kzg_amd_recover_data_columns(self._ctx, nb, nc, _vp(idx), _vp(tab), _vp(ocp) if want_cells else None,
+                                                               _vp(opp) if want_proofs else None, st))
+        return (list(st)[:nb], _split(out_cells, CELLS_PER_EXT_BLOB, nb, BYTES_PER_CELL) if want_cells else None,
+                _split(out_proofs, CELLS_PER_EXT_BLOB, nb, 48) if want_proofs else None)
+
+    def recover_data_columns_device(self, n_blobs, column_indices, d_cells, d_out_cells, d_out_proofs, stream=None):
+        """The same on device memory (eth_kzg_amd_recover_data_columns_device): d_cells [len(column_indices)][n_blobs][2048],
+        d_out_cells [128][n_blobs][2048], d_out_proofs [128][n_blobs][48] (either may be 0 / None).  -> the per-blob status list."""
+        nc = len(column_indices)
+        idx = np.ascontiguousarray(np.array(column_indices, dtype=np.uint64)) if nc else np.zeros(1, np.uint64)
+        st = (C.c_int32 * max(1, n_blobs))()
+        self._check(self._lib.eth_kzg_amd_recover_data_columns_device(
+            self._ctx, n_blobs, nc, _vp(idx), C.c_void_p(d_cells) if d_cells else None, C.c_void_p(d_out_cells) if d_out_cells else None,
+            C.c_void_p(d_out_proofs) if d_out_proofs else None, st, C.c_void_p(stream) if stream else None))
+        return list(st)[:n_blobs]
 
     def verify_cell_kzg_proof_batch_partial(self, commitments, cell_indices, cells, proofs, shard_begin, shard_end):
         """This rank's share of a sharded verification: the whole batch goes in (the challenge hashes all of it), the

@@ -648,6 +648,68 @@ CResult eth_kzg_amd_blob_to_kzg_commitment_device(const DASContext* ctx, uint64_
     return ok();
 }
 // ---------------------------------------------------------------------------------------------
+// A block's data columns in column layout (data_columns.hip; c_eth_kzg.h).  The count and the NULL arrays are refused before the context
+// is looked at.  Host forms: contiguous slices by BLOB over the device list, every slice writing its blobs' entries of the shared
+// column arrays; device forms: the device that owns every buffer given.
+CResult eth_kzg_amd_compute_data_columns(const DASContext* ctx, uint64_t n_blobs, const uint8_t* const* blobs, uint8_t* const* out_commitments,
+                                         uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int32_t* status) {
+    if (n_blobs > MAX_BATCH || (n_blobs && !blobs)) return err("InvalidInput");
+    if (n_blobs == 0) return ok();  // (an empty call looks at nothing, the context included)
+    return sliced_call(ctx, n_blobs, MAX_BATCH, nullptr, status, [] { return true; }, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int*) {
+        return batch_failure(e, e->compute_data_columns_host((int)lo, (int)(hi - lo), blobs, out_commitments, out_cells, out_proofs, st));
+    });
+}
+CResult eth_kzg_amd_compute_data_columns_device(const DASContext* ctx, uint64_t n_blobs, const uint8_t* d_blobs, uint8_t* d_out_commitments,
+                                                uint8_t* d_out_cells, uint8_t* d_out_proofs, int32_t* status, void* hip_stream) {
+    if (n_blobs > MAX_BATCH) return err("InvalidInput");
+    if (n_blobs && !d_blobs) return err("InvalidInput");
+    if (n_blobs == 0) return ok();
+    live(ctx);
+    const void* ptrs[4] = {d_blobs};
+    int n_ptrs = 1;
+    for (const void* p : {(const void*)d_out_commitments, (const void*)d_out_cells, (const void*)d_out_proofs})
+        if (p) ptrs[n_ptrs++] = p;
+    kzg::Engine* e = engine_of_device_pointers(ctx, ptrs, n_ptrs);
+    if (!e) return err("InvalidInput: the buffers are not device memory of one device of this context");
+    static_assert(sizeof(int32_t) == sizeof(int), "status array");
+    const bool sync = hip_stream == nullptr;
+    if (e->compute_data_columns_device((int)n_blobs, d_blobs, d_out_commitments, d_out_cells, d_out_proofs, (int*)status, (hipStream_t)hip_stream, sync))
+        return device_err(e);
+    if (status) for (uint64_t i = 0; i < n_blobs; i++) status[i] = status[i] ? kzg::ERR_SCALAR : 0;
+    return ok();
+}
+CResult eth_kzg_amd_recover_data_columns(const DASContext* ctx, uint64_t n_blobs, uint64_t n_columns, const uint64_t* column_indices,
+                                         const uint8_t* const* const* cells, uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs,
+                                         int32_t* status) {
+    if (n_blobs > MAX_BATCH || (n_blobs && (!cells || !status || (n_columns && !column_indices)))) return err("InvalidInput");
+    if (n_blobs == 0) return ok();
+    return sliced_call(ctx, n_blobs, MAX_BATCH, nullptr, status, [] { return true; }, [&](kzg::Engine* dev, uint64_t lo, uint64_t hi, int* st, int*) {
+        auto lane = dev->lease_serial();
+        kzg::Engine* e = lane.e;
+        return batch_failure(e, e->recover_data_columns_host((int)lo, (int)(hi - lo), n_columns, column_indices, cells, out_cells, out_proofs, st));
+    });
+}
+CResult eth_kzg_amd_recover_data_columns_device(const DASContext* ctx, uint64_t n_blobs, uint64_t n_columns, const uint64_t* column_indices,
+                                                const uint8_t* d_cells, uint8_t* d_out_cells, uint8_t* d_out_proofs, int32_t* status,
+                                                void* hip_stream) {
+    if (n_blobs > MAX_BATCH) return err("InvalidInput");
+    if (n_blobs && (!d_cells || !status || (n_columns && !column_indices))) return err("InvalidInput");
+    if (n_blobs == 0) return ok();
+    live(ctx);
+    const void* ptrs[3] = {d_cells};
+    int n_ptrs = 1;
+    for (const void* p : {(const void*)d_out_cells, (const void*)d_out_proofs})
+        if (p) ptrs[n_ptrs++] = p;
+    kzg::Engine* owner = engine_of_device_pointers(ctx, ptrs, n_ptrs);
+    if (!owner) return err("InvalidInput: the buffers are not device memory of one device of this context");
+    auto lane = owner->lease_serial();
+    kzg::Engine* e = lane.e;
+    static_assert(sizeof(int32_t) == sizeof(int), "status array");
+    if (e->recover_data_columns_device((int)n_blobs, n_columns, column_indices, d_cells, d_out_cells, d_out_proofs, (int*)status, (hipStream_t)hip_stream))
+        return device_err(e);
+    return ok();
+}
+// ---------------------------------------------------------------------------------------------
 // EIP-4844 proofs for many blobs (eip4844.hip).  Host-pointer forms: contiguous slices over the device list; device-resident forms:
 // the engine that owns d_blobs; the device verifier is ONE random combination over the whole batch and is never cut.
 CResult eth_kzg_amd_compute_blob_kzg_proof_batch(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* commitments,

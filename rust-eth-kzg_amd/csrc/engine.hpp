@@ -26,6 +26,7 @@ namespace vm { struct DevicePairing; }  // vm_search.hpp
 struct Comm;  // multi_gpu.cpp
 struct ColumnCommitments;  // verify_host.hpp
 struct G1Affine;  // curve.hpp
+namespace launch { struct Columns; }  // launch.hpp: the [column][blob] output layout
 struct Fr8 { uint32_t v[8]; };
 struct Fp12w { uint32_t v[12]; };
 
@@ -234,6 +235,12 @@ struct Work {
     hipEvent_t ev_in = nullptr, ev_cells = nullptr, ev_cells_host = nullptr, ev_done = nullptr;
     hipEvent_t ev_coeffs = nullptr, ev_side = nullptr;  // small batches: coefficients ready / cells written on the second stream
     std::vector<hipEvent_t> sub_events;  // per sub-batch of a host-pointer call: [2i] cells computed, [2i+1] cells on the host
+    // the column prover (data_columns.hip), which commits from the same decode as it proves: canonical coefficients (128 KB per blob) and
+    // the commitment MSM's 64 sums per blob, grown on first use; the commitments' staging of its host form
+    int col_cap = 0;
+    void *col_canon = nullptr, *col_sums = nullptr;
+    int comm_cap = 0;
+    uint8_t *d_comm = nullptr, *h_comm = nullptr;
 };
 // (HostPool, the combiner, pass-slot and lane leases: host_sync.hpp -- HIP-free, driven under ThreadSanitizer on the CPU)
 class Engine {
@@ -285,6 +292,23 @@ public:
                                             int* h_status, hipStream_t stream, bool sync);
     int blob_to_kzg_commitment_device(int n, const uint8_t* d_blobs, uint8_t* d_commitments, int* h_status,
                                       hipStream_t stream, bool sync);
+
+    // ---- a block's data columns in column layout (data_columns.hip; c_eth_kzg.h: eth_kzg_amd_compute_data_columns / _recover_data_columns) ----
+    // The prover's call: d_commitments n * 48 B, d_cells [128][n][2048], d_proofs [128][n][48], each may be null.  One decode per
+    // sub-batch feeds the commitment and the proofs; status, stream and sync rules of compute_cells_and_kzg_proofs_device.
+    int compute_data_columns_device(int n, const uint8_t* d_blobs, uint8_t* d_commitments, uint8_t* d_cells, uint8_t* d_proofs, int* h_status,
+                                    hipStream_t stream, bool sync);
+    // host pointers: blobs [lo, lo + n) of the caller's arrays (a slice of the call: the arrays are the WHOLE call's, out_cells[c][i] with
+    // i a blob of the call); h_status: the whole call's as well.  Outputs of a refused blob are left untouched.
+    int compute_data_columns_host(int lo, int n, const uint8_t* const* blobs, uint8_t* const* out_commitments, uint8_t* const* const* out_cells,
+                                  uint8_t* const* const* out_proofs, int* h_status);
+    // The supernode's call: all 128 columns of R blobs from n_columns of them.  d_cells [n_columns][R][2048] in HBM, column_indices on the
+    // host; outputs as above.  ONE vanishing polynomial per call.  A bad list marks every blob ERR_INPUT before anything is launched.
+    int recover_data_columns_device(int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells, uint8_t* d_out_cells,
+                                    uint8_t* d_out_proofs, int* status, hipStream_t stream);
+    // host pointers: cells[j][i], blobs [lo, lo + R) of the call; out_cells / out_proofs [128][blobs of the call], may be null; status: the whole call's
+    int recover_data_columns_host(int lo, int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* const* const* cells,
+                                  uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int* status);
 
     // ---- host-buffer entry points (what the reference's C ABI hands over) ----
     int compute_cells_and_kzg_proofs_host(int n, const uint8_t* const* blobs, uint8_t* const* const* cells,
@@ -555,8 +579,13 @@ private:
     // tap (null in every product call; the stage hook test_rs_decode sets it): host arrays that receive what the decoder's stages left,
     // in the kernels' Montgomery words, before their pool buffers are released -- deg[R], zp[R][65], zeval[R][128], zcinv[R][128]; each may be null
     struct RsDecodeTap { int* deg = nullptr; Fr8 *zp = nullptr, *zeval = nullptr, *zcinv = nullptr; };
+    // src_of (null in every call but the column form): list entry k reads cell (*src_of)[k] of d_cells.  shared_pattern (the column form):
+    // all R blobs miss the same cells -- `present` holds ONE mask and one vanishing polynomial is built for the call.
     int rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
-                  const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap = nullptr);
+                  const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap = nullptr, const std::vector<int>* src_of = nullptr,
+                  bool shared_pattern = false);
+    // the column form's index arrays for blobs [r0, r0 + nr) of n_total, then rs_decode on them (data_columns.hip)
+    int rs_decode_columns(int nr, size_t n_total, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells_r0, int* st_out);
     int recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_t* const* const* cells,
                                 const uint64_t* const* cell_indices, int* st_out);
     void ensure_workspace(int n);  // work_[0]; also makes stream_ wait for the last asynchronous call that used it
@@ -566,10 +595,18 @@ private:
     // msm_cut > 0 (host-pointer path, scalars precomputed): the MSM stage in two launches around the cut -- PROOFS_HEAD issues the
     // arena set-up and the MSMs of blobs [0, msm_cut) and returns, PROOFS_TAIL the MSMs of [msm_cut, n) and everything after
     enum ProofsPhase { PROOFS_ALL = 0, PROOFS_HEAD = 1, PROOFS_TAIL = 2 };
+    // cols (here and below; null: the blob-major layout): d_cells / d_proofs are the whole call's column arrays (launch::Columns)
     void run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream_t st, const TableView* tv_pre = nullptr, ProofsPhase phase = PROOFS_ALL,
-                                int msm_cut = 0);
+                                int msm_cut = 0, const launch::Columns* cols = nullptr);
+    // d_commitments (the column prover only): the blobs' commitments, n * 48 bytes, from the same decode (enqueue_commitments)
     void enqueue_compute(Work& w, int n, const uint8_t* d_blobs, uint8_t* d_cells, uint8_t* d_proofs, hipStream_t st,
-                         hipEvent_t after_cells);
+                         hipEvent_t after_cells, const launch::Columns* cols = nullptr, uint8_t* d_commitments = nullptr);
+    // the commitment stages of n blobs whose canonical coefficients are in w.col_canon: set_inf, MSM on TAB_SRS, fold, compress
+    void enqueue_commitments(Work& w, int n, uint8_t* d_commitments, hipStream_t st);
+    void ensure_commit_scratch(Work& w, int n);
+    // the body of compute_cells_and_kzg_proofs_device and compute_data_columns_device: sub-batches on one leased work set
+    int prover_device(int n, const uint8_t* d_blobs, uint8_t* d_commitments, uint8_t* d_cells, uint8_t* d_proofs, int* h_status, hipStream_t st,
+                      bool sync, bool columns);
     // the G1 stage behind the MSM (engine_prover.hip): its program, lanes and point array; then its launches down to the proof bytes
     struct SlpProgram;
     struct G1Stage {
@@ -578,6 +615,7 @@ private:
         const SlpProgram* prog = nullptr;
         int mulc_coop_lanes = 0;  // > 0: so few blobs that the constant multiplications take several lanes per blob (launch::g1_slp_launch)
         void* X = nullptr;        // where the MSM leaves its sums: the linear map's arena, or the work set's point array
+        const launch::Columns* cols = nullptr;  // the proofs' layout (null: blob-major)
     };
     G1Stage prepare_g1_stage(Work& w, int n, hipStream_t st, int force_program = -1);
     void run_g1_stage(Work& w, const G1Stage& g, int n, uint8_t* d_proofs, hipStream_t st);

@@ -53,7 +53,11 @@ void Engine::ensure_workspace(Work& w, int n, bool release) {
     for (void** p : ptrs)
         if (*p) { HIPCK(hipFree(*p)); *p = nullptr; }
     w.cap = 0;
-    if (release) {  // give the set's memory back (a sub-batch did not fit: the next attempt is half the size)
+    if (release) {
+        void** col[] = {&w.col_canon, &w.col_sums};  // (the column prover's share of a sub-batch that did not fit)
+        for (void** p : col)
+            if (*p) { HIPCK(hipFree(*p)); *p = nullptr; }
+        w.col_cap = 0;  // give the set's memory back (a sub-batch did not fit: the next attempt is half the size)
         if (w.slp_arena) { HIPCK(hipFree(w.slp_arena)); w.slp_arena = nullptr; w.slp_arena_bytes = 0; }
         return;
     }
@@ -226,7 +230,7 @@ void Engine::run_g1_stage(Work& w, const G1Stage& g, int n, uint8_t* d_proofs, h
         n_launches = (int)prog->launches.size();
         mark_end(mk3, n_launches, st);
         const int mk4 = mark_begin(ST_COMPRESS, st);
-        launch::g1_compress((const char*)w.slp_arena + (size_t)128 * bp * pt, d_proofs, 128, bp, n, st, fmt);
+        launch::g1_compress((const char*)w.slp_arena + (size_t)128 * bp * pt, d_proofs, 128, bp, n, st, fmt, g.cols);
         mark_end(mk4, 1, st);
         return;
     }
@@ -237,14 +241,16 @@ void Engine::run_g1_stage(Work& w, const G1Stage& g, int n, uint8_t* d_proofs, h
         mark_end(mk5, 2, st);
     } else throw std::logic_error("run_proofs_from_coeffs: a batch above the circulant form needs the compiled linear map");
     const int mk10 = mark_begin(ST_COMPRESS, st);
-    launch::g1_compress(w.X, d_proofs, 128, bp, n, st, fmt);
+    launch::g1_compress(w.X, d_proofs, 128, bp, n, st, fmt, g.cols);
     mark_end(mk10, 1, st);
 }
 // stages C..G of SURVEY 3.2 from coefficients already in w.coeffs
 // tv_pre: the scalars of all n blobs are in w.scalars already, computed in the form of THIS view (the host-pointer path does it
 // sub-batch by sub-batch under the uploads)
-void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream_t st, const TableView* tv_pre, ProofsPhase phase, int msm_cut) {
-    const G1Stage g1 = prepare_g1_stage(w, n, st);
+void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream_t st, const TableView* tv_pre, ProofsPhase phase, int msm_cut,
+                                    const launch::Columns* cols) {
+    G1Stage g1 = prepare_g1_stage(w, n, st);
+    g1.cols = cols;
     const int bp = g1.bp, segs = g1.segs;
     const Fr8 two_segments[3] = {seg_shift_[1], seg_shift_[1], seg_shift_[1]};  // 2^64
     const bool linmap_mode = g1.linmap_mode;
@@ -283,13 +289,16 @@ void Engine::run_proofs_from_coeffs(Work& w, int n, uint8_t* d_proofs, hipStream
 
 // the kernels of one prover call on `st`, scratch from `w`; optionally records `after_cells` once the cells are written
 void Engine::enqueue_compute(Work& w, int n, const uint8_t* d_blobs, uint8_t* d_cells, uint8_t* d_proofs, hipStream_t st,
-                             hipEvent_t after_cells) {
+                             hipEvent_t after_cells, const launch::Columns* cols, uint8_t* d_commitments) {
     ensure_workspace(w, n);
+    if (d_commitments) ensure_commit_scratch(w, n);
     HIPCK(hipStreamWaitEvent(st, w.done, 0));  // an earlier call may still be using this set on another stream
     HIPCK(hipMemsetAsync(w.status, 0, n * sizeof(int), st));
     const int mk11 = mark_begin(ST_BLOB_TO_COEFFS, st);
-    launch::blob_to_coeffs(n, d_blobs, w.coeffs, nullptr, w.status, d_w29_, n_inv4096_, st);
+    // ONE decode: the Montgomery coefficients for the stages below and, for a caller that wants the commitments too, the canonical ones
+    launch::blob_to_coeffs(n, d_blobs, w.coeffs, d_commitments ? w.col_canon : nullptr, w.status, d_w29_, n_inv4096_, st);
     mark_end(mk11, 1, st);
+    if (d_commitments) enqueue_commitments(w, n, d_commitments, st);
     // a handful of blobs is a chain of latencies: the cells (one 8192-point transform, 0.08 ms) then run on the set's second
     // stream next to the proof stages instead of in front of them
     // ... unless the MSM launch that follows puts a wave on (nearly) every SIMD and no second one: a block of the cells kernel needs a
@@ -313,34 +322,39 @@ void Engine::enqueue_compute(Work& w, int n, const uint8_t* d_blobs, uint8_t* d_
         const int mk = mark_begin(ST_COEFFS_TO_CELLS, st);
         launch::coeffs_to_cells_scalars(n, w.coeffs, d_cells, w.scalars, d_blobs, w.status, d_w29_,
                                         (const char*)d_tapk_ + (linmap_mode ? 0 : (size_t)N_EXT * launch::SIZEOF_FR29), segs,
-                                        segs == 2 ? two_segments : seg_shift_, st);
+                                        segs == 2 ? two_segments : seg_shift_, st, cols);
         mark_end(mk, 1, st);
         fused_launches_.fetch_add(1, std::memory_order_relaxed);
         if (after_cells) HIPCK(hipEventRecord(after_cells, st));
-        run_proofs_from_coeffs(w, n, d_proofs, st, &tv);
+        run_proofs_from_coeffs(w, n, d_proofs, st, &tv, PROOFS_ALL, 0, cols);
         return;
     }
     if (side) {
         HIPCK(hipEventRecord(w.ev_coeffs, st));
         HIPCK(hipStreamWaitEvent(w.copy, w.ev_coeffs, 0));
-        launch::coeffs_to_cells(n, w.coeffs, d_cells, d_w29_, w.copy);
+        launch::coeffs_to_cells(n, w.coeffs, d_cells, d_w29_, w.copy, cols);
         if (after_cells) HIPCK(hipEventRecord(after_cells, w.copy));
         HIPCK(hipEventRecord(w.ev_side, w.copy));
-        run_proofs_from_coeffs(w, n, d_proofs, st);
+        run_proofs_from_coeffs(w, n, d_proofs, st, nullptr, PROOFS_ALL, 0, cols);
         HIPCK(hipStreamWaitEvent(st, w.ev_side, 0));
         return;
     }
     if (d_cells) {
         const int mk12 = mark_begin(ST_COEFFS_TO_CELLS, st);
-        launch::coeffs_to_cells(n, w.coeffs, d_cells, d_w29_, st);
+        launch::coeffs_to_cells(n, w.coeffs, d_cells, d_w29_, st, cols);
         mark_end(mk12, 1, st);
     }
     if (after_cells) HIPCK(hipEventRecord(after_cells, st));
-    if (d_proofs) run_proofs_from_coeffs(w, n, d_proofs, st);
+    if (d_proofs) run_proofs_from_coeffs(w, n, d_proofs, st, nullptr, PROOFS_ALL, 0, cols);
 }
 
 int Engine::compute_cells_and_kzg_proofs_device(int n, const uint8_t* d_blobs, uint8_t* d_cells, uint8_t* d_proofs,
                                                 int* h_status, hipStream_t st, bool sync) {
+    return prover_device(n, d_blobs, nullptr, d_cells, d_proofs, h_status, st, sync, /*columns=*/false);
+}
+// columns: d_cells / d_proofs are [128][n] arrays (sub-batch b0 writes blobs [b0, b0 + nb) of every column) and d_commitments may be set
+int Engine::prover_device(int n, const uint8_t* d_blobs, uint8_t* d_commitments, uint8_t* d_cells, uint8_t* d_proofs, int* h_status, hipStream_t st,
+                          bool sync, bool columns) {
     if (n <= 0) return OK;
     Work* held = nullptr;
     try {
@@ -360,8 +374,13 @@ int Engine::compute_cells_and_kzg_proofs_device(int n, const uint8_t* d_blobs, u
         for (int b0 = 0; b0 < n;) {
             const int nb = std::min(sub, n - b0);
             try {
-                enqueue_compute(w, nb, d_blobs + (size_t)b0 * BYTES_PER_BLOB, d_cells ? d_cells + (size_t)b0 * N_CELLS * BYTES_PER_CELL : nullptr,
-                                d_proofs ? d_proofs + (size_t)b0 * N_CELLS * 48 : nullptr, st, nullptr);
+                const launch::Columns cols{(size_t)n, (size_t)b0};
+                if (columns)
+                    enqueue_compute(w, nb, d_blobs + (size_t)b0 * BYTES_PER_BLOB, d_cells, d_proofs, st, nullptr, &cols,
+                                    d_commitments ? d_commitments + (size_t)b0 * 48 : nullptr);
+                else
+                    enqueue_compute(w, nb, d_blobs + (size_t)b0 * BYTES_PER_BLOB, d_cells ? d_cells + (size_t)b0 * N_CELLS * BYTES_PER_CELL : nullptr,
+                                    d_proofs ? d_proofs + (size_t)b0 * N_CELLS * 48 : nullptr, st, nullptr);
             } catch (const HipError& e) {
                 if (!e.out_of_memory() || sub <= 64) throw;
                 (void)hipGetLastError();

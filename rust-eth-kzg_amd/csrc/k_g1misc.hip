@@ -39,8 +39,20 @@ __device__ __forceinline__ G1Jac jac_of(const JacS& p) {
 // an identity (z = 0) takes part as z = 1 and is encoded as the identity afterwards.  The binary-GCD inversion is ~80 % of a
 // one-point normalisation, so this is ~3x fewer instructions per point; n_pos not a multiple of 4: the tail takes part as ones.
 // (NB = 1 for batches that leave the chip part empty: there the kernel lasts as long as one thread's chain.)
-template <int NB, class Pt>
-__global__ __launch_bounds__(64) void k_g1_compress(const Pt* __restrict__ X, uint8_t* __restrict__ out, int n_pos,
+// Out: where the 48 bytes of (position, slice) go.  G1BySlice: out[(slice * n_pos + pos) * 48], a blob's proofs together.  G1ByPosition:
+// out[(pos * n_total + b0 + slice) * 48], a column's proofs together (launch::Columns) -- a wave's 64 lanes then store 64 consecutive
+// records.  The offsets are size_t: 128 x 2^24 x 48 bytes do not fit 32 bits.
+struct G1BySlice {
+    uint8_t* out;
+    __device__ __forceinline__ uint8_t* at(int slice, int pos, int n_pos) const { return out + ((size_t)slice * n_pos + pos) * 48; }
+};
+struct G1ByPosition {
+    uint8_t* out;
+    size_t n_total, b0;
+    __device__ __forceinline__ uint8_t* at(int slice, int pos, int) const { return out + ((size_t)pos * n_total + b0 + slice) * 48; }
+};
+template <int NB, class Pt, class Out>
+__global__ __launch_bounds__(64) void k_g1_compress(const Pt* __restrict__ X, Out out, int n_pos,
                                                     int stride, int n_slices) {
     const int pos0 = blockIdx.x * NB, slice_of_lane = blockIdx.y * 64 + threadIdx.x;
     // the lanes behind the last blob repeat its work and store nothing (k_g1slp.hip, k_slp_mulc_s: a partly filled wave is the slower one)
@@ -73,7 +85,7 @@ __global__ __launch_bounds__(64) void k_g1_compress(const Pt* __restrict__ X, ui
             }
             uint8_t buf[48];
             g1_compress(buf, a);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(out + ((size_t)slice * n_pos + pos0 + i) * 48);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(out.at(slice, pos0 + i, n_pos));
             const uint32_t* src = reinterpret_cast<const uint32_t*>(buf);
             if (slice_of_lane < n_slices) {
 #pragma unroll
@@ -311,17 +323,22 @@ void g1_set_inf(void* X, size_t n, hipStream_t st, int fmt) {
     if (fmt == FMT_JACS) k_g1_set_inf_s<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((JacS*)X, n);
     else k_g1_set_inf<<<(unsigned)((n + 255) / 256), 256, 0, st>>>((JacQ*)X, n);
 }
-void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slices, hipStream_t st, int fmt) {
+void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slices, hipStream_t st, int fmt, const Columns* cols) {
     // measured (128 positions): 2048 lanes 0.39 -> 0.22 ms with four positions per thread; 512 lanes 0.155 -> 0.21, 64 lanes 0.15 -> 0.21 ms
     // (below two rounds of one-point waves the kernel lasts as long as one thread's chain)
     const bool four = (long)n_pos * stride >= 128L * 2048;
     const dim3 g4((n_pos + 3) / 4, stride / 64), g1(n_pos, stride / 64);
-    if (fmt == FMT_JACS) {  // signed 13 x 30-bit points: what the prover, recovery and the commitments hand over
-        if (four) k_g1_compress<4, JacS><<<g4, 64, 0, st>>>((const JacS*)X, out, n_pos, stride, n_slices);
-        else k_g1_compress<1, JacS><<<g1, 64, 0, st>>>((const JacS*)X, out, n_pos, stride, n_slices);
+    if (cols) {  // the column layout: the prover's and recovery's proofs only, so JacS only
+        if (fmt != FMT_JACS) abort();
+        const G1ByPosition o{out, cols->n_total, cols->b0};
+        if (four) k_g1_compress<4, JacS><<<g4, 64, 0, st>>>((const JacS*)X, o, n_pos, stride, n_slices);
+        else k_g1_compress<1, JacS><<<g1, 64, 0, st>>>((const JacS*)X, o, n_pos, stride, n_slices);
+    } else if (fmt == FMT_JACS) {  // signed 13 x 30-bit points: what the prover, recovery and the commitments hand over
+        if (four) k_g1_compress<4, JacS><<<g4, 64, 0, st>>>((const JacS*)X, G1BySlice{out}, n_pos, stride, n_slices);
+        else k_g1_compress<1, JacS><<<g1, 64, 0, st>>>((const JacS*)X, G1BySlice{out}, n_pos, stride, n_slices);
     } else {
-        if (four) k_g1_compress<4, JacQ><<<g4, 64, 0, st>>>((const JacQ*)X, out, n_pos, stride, n_slices);
-        else k_g1_compress<1, JacQ><<<g1, 64, 0, st>>>((const JacQ*)X, out, n_pos, stride, n_slices);
+        if (four) k_g1_compress<4, JacQ><<<g4, 64, 0, st>>>((const JacQ*)X, G1BySlice{out}, n_pos, stride, n_slices);
+        else k_g1_compress<1, JacQ><<<g1, 64, 0, st>>>((const JacQ*)X, G1BySlice{out}, n_pos, stride, n_slices);
     }
 }
 void g1_sum_positions(void* X, int n_pos, int stride, int n_slices, hipStream_t st) {

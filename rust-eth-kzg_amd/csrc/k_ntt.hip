@@ -260,8 +260,24 @@ __global__ __launch_bounds__(1024) void k_blob_eval_at(const uint8_t* __restrict
 // (prover.rs:158-165, serialization/src/lib.rs:132-156).  X[2k+h] = NTT_4096(a_i * w8192^(i*h))[k];
 // the forward network leaves half h bit-reversed in place, which is exactly cells[h*4096 ...].
 // grid = (n_blobs, 2), block = 1024, dynamic LDS = 144 KiB.
-__global__ __launch_bounds__(1024) void k_coeffs_to_cells(const Fr* __restrict__ coeffs, uint8_t* __restrict__ cells,
-                                                         const Fr29* __restrict__ w29) {
+// Where the two cell writers below put element e of half h of blob b (cell 64 h + e / 64, element e % 64 of it).  Each Fr is stored
+// once, from LDS to its final address, so the layout of the output is this address and nothing else:
+//   CellsByBlob    [blob][128][2048]: the extended blob, what every call but the column forms launches
+//   CellsByColumn  [128][n_total][2048], this launch's blob b being blob b0 + b of the call: the layout of a block's data column
+//                  sidecars (eth_kzg_amd_compute_data_columns / _recover_data_columns).  128 n_total 2048 bytes pass 2^32: size_t throughout.
+struct CellsByBlob {
+    uint8_t* cells;
+    __device__ __forceinline__ uint8_t* fr(int b, int h, int e) const { return cells + ((size_t)b * N_EXT + (size_t)h * N_BLOB + e) * 32; }
+};
+struct CellsByColumn {
+    uint8_t* cells;
+    size_t n_total, b0;
+    __device__ __forceinline__ uint8_t* fr(int b, int h, int e) const {
+        return cells + (((size_t)(h * (N_CELLS / 2) + (e >> 6)) * n_total + b0 + b) * CELL_LEN + (e & (CELL_LEN - 1))) * 32;
+    }
+};
+template <class Dst>
+__global__ __launch_bounds__(1024) void k_coeffs_to_cells(const Fr* __restrict__ coeffs, Dst dst, const Fr29* __restrict__ w29) {
     extern __shared__ uint32_t s[];
     const int b = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
     for (int e = tid; e < N_BLOB; e += 1024) {
@@ -271,10 +287,9 @@ __global__ __launch_bounds__(1024) void k_coeffs_to_cells(const Fr* __restrict__
     }
     __syncthreads();
     ntt4096_ct_forward(s, w29);  // < 56 r
-    uint8_t* out = cells + ((size_t)b * N_EXT + (size_t)h * N_BLOB) * 32;
     const Fr29 one_plain = fr29_const(r29::ONE_PLAIN);
     for (int e = tid; e < N_BLOB; e += 1024)
-        store_fr_be(out + 32 * e, fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), one_plain))));  // X / 2^261 = the value
+        store_fr_be(dst.fr(b, h, e), fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), one_plain))));  // X / 2^261 = the value
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -349,7 +364,8 @@ __global__ __launch_bounds__(256) void k_fk20_scalars(const Fr* __restrict__ coe
 // Cells 0..63 are the blob (the transform of half 0 inverts k_blob_to_coeffs): with `blobs` given and blob b accepted (status 0: every
 // element canonical, so its bytes ARE the canonical encoding), block h = 0 stops after its scalars and copies the 128 KiB across.  A
 // rejected blob, and a caller without the blob's bytes (blobs = null), finish the transform.
-__global__ __launch_bounds__(1024) void k_coeffs_to_cells_scalars(const Fr* __restrict__ coeffs, uint8_t* __restrict__ cells,
+template <class Dst>
+__global__ __launch_bounds__(1024) void k_coeffs_to_cells_scalars(const Fr* __restrict__ coeffs, Dst dst,
                                                                  Fr* __restrict__ scalars, const uint8_t* __restrict__ blobs,
                                                                  const int* __restrict__ status, const Fr29* __restrict__ w29,
                                                                  const Fr29* __restrict__ tapk, int n, int segs, SegShifts sh) {
@@ -372,17 +388,16 @@ __global__ __launch_bounds__(1024) void k_coeffs_to_cells_scalars(const Fr* __re
         for (int sg = 1; sg < segs; sg++)  // plain x times the Montgomery form of the shift: plain (k_fk20_scalars)
             store_split_scalar(&scalars[(size_t)(sg * n + b) * N_EXT + at], fr29_mul(x, sh.p[sg - 1]));
     }
-    uint8_t* out = cells + ((size_t)b * N_EXT + (size_t)h * N_BLOB) * 32;
     if (h == 0 && blobs && status[b] == 0) {  // uniform over the block: no barrier follows
         const uint4* src = reinterpret_cast<const uint4*>(blobs + (size_t)b * BYTES_PER_BLOB);
-        uint4* dst = reinterpret_cast<uint4*>(out);
-        for (int k = tid; k < BYTES_PER_BLOB / 16; k += 1024) dst[k] = src[k];
+        for (int k = tid; k < BYTES_PER_BLOB / 16; k += 1024)  // 16 bytes = half an element: element k / 2 of half 0
+            *reinterpret_cast<uint4*>(dst.fr(b, 0, k >> 1) + 16 * (k & 1)) = src[k];
         return;
     }
     ntt4096_ct_forward_tail(s, w29);  // < 56 r
     const Fr29 one_plain = fr29_const(r29::ONE_PLAIN);
     for (int e = tid; e < N_BLOB; e += 1024)
-        store_fr_be(out + 32 * e, fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), one_plain))));  // X / 2^261 = the value
+        store_fr_be(dst.fr(b, h, e), fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), one_plain))));  // X / 2^261 = the value
 }
 __global__ void k_fk20_tap_consts(const Fr29* __restrict__ w29, Fr29 scale_plain, Fr29* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -440,8 +455,10 @@ constexpr size_t LDS_NTT29 = (size_t)N_BLOB * RL * 4;  // 144 KiB: one 4096-poin
 void init_attributes() {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_coeffs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_eval_at), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByColumn>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars<CellsByColumn>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
 #ifdef KZG_TEST_HOOKS
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_test_ntt4096), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
 #endif
@@ -479,8 +496,9 @@ void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be
                   hipStream_t st) {
     if (n > 0) k_blob_eval_at<<<n, 1024, LDS_NTT29, st>>>(blobs, (const Fr*)z_mont, y_be32, (Fr*)y_mont, bad, (const Fr29*)w29, ntt_consts(n_inv));
 }
-void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st) {
-    k_coeffs_to_cells<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, cells, (const Fr29*)w29);
+void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st, const Columns* cols) {
+    if (cols) k_coeffs_to_cells<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, CellsByColumn{cells, cols->n_total, cols->b0}, (const Fr29*)w29);
+    else k_coeffs_to_cells<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, CellsByBlob{cells}, (const Fr29*)w29);
 }
 void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, const Fr8& inv128, int segs, const Fr8* seg_shifts,
                   hipStream_t st) {
@@ -492,16 +510,22 @@ void fk20_tap_consts(const void* w29, const Fr8& scale, void* out, hipStream_t s
     k_fk20_tap_consts<<<2 * N_BLOB / 256, 256, 0, st>>>((const Fr29*)w29, fr29_from_plain(from_mont(as_fr(scale))), (Fr29*)out);
 }
 void coeffs_to_cells_scalars(int n, const void* coeffs, uint8_t* cells, void* scalars, const uint8_t* blobs, const int* status, const void* w29,
-                             const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st) {
+                             const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st, const Columns* cols) {
     // the 16-byte copy of an accepted blob wants both ends aligned and apart (a caller may hand in any byte address, and cells that
     // overlap the blobs were fine while every blob was read before the first cell was written): otherwise every block transforms
+    // (column layout: `cells` is the whole call's array, n_total blobs wide, and every cell of it starts on a multiple of 2048 from there)
     const uintptr_t pb = (uintptr_t)blobs, pc = (uintptr_t)cells;
-    const bool apart = pb + (size_t)n * BYTES_PER_BLOB <= pc || pc + (size_t)n * N_EXT * 32 <= pb;
+    const size_t cells_bytes = (cols ? cols->n_total : (size_t)n) * N_EXT * 32;
+    const bool apart = pb + (size_t)n * BYTES_PER_BLOB <= pc || pc + cells_bytes <= pb;
     if (!status || ((pb | pc) & 15) || !apart) blobs = nullptr;
     SegShifts sh;
     for (int i = 0; i < 3; i++) sh.p[i] = fr29_mont_of(seg_shifts[i]);
-    k_coeffs_to_cells_scalars<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, cells, (Fr*)scalars, blobs, status, (const Fr29*)w29,
-                                                                   (const Fr29*)tapk, n, segs, sh);
+    if (cols)
+        k_coeffs_to_cells_scalars<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, CellsByColumn{cells, cols->n_total, cols->b0}, (Fr*)scalars, blobs,
+                                                                       status, (const Fr29*)w29, (const Fr29*)tapk, n, segs, sh);
+    else
+        k_coeffs_to_cells_scalars<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, CellsByBlob{cells}, (Fr*)scalars, blobs, status, (const Fr29*)w29,
+                                                                       (const Fr29*)tapk, n, segs, sh);
 }
 #ifdef KZG_TEST_HOOKS
 void test_ntt4096(const uint8_t* in, uint8_t* out, const void* w29, const Fr8& n_inv, int inverse_dit, hipStream_t st) {

@@ -587,14 +587,16 @@ __global__ void k_rec_vanishing(const Fr* __restrict__ zp, const int* __restrict
 //
 // k_rec_dit_half: half h of V (optionally multiplied cell-wise by fac[c]) -> DIT_4096 -> T
 // grid = (R, 2), block = 1024, LDS 128 KiB.
+// fac_stride (here and in k_rec_dif_half): blob r reads fac[r * fac_stride + cell] -- N_CELLS when every blob has factors of its own, 0
+// when all R blobs miss the same cells and share the 128 of ONE vanishing polynomial (the column form of recovery).
 __global__ __launch_bounds__(1024) void k_rec_dit_half(const Fr* __restrict__ V, const Fr* __restrict__ fac, Fr* __restrict__ T,
-                                                      const Fr* __restrict__ w8192) {
+                                                      const Fr* __restrict__ w8192, int fac_stride) {
     extern __shared__ uint32_t s[];
     const int r = blockIdx.x, h = blockIdx.y;
     const Fr* src = V + (size_t)r * N_EXT + (size_t)h * N_BLOB;
     for (int e = threadIdx.x; e < N_BLOB; e += 1024) {
         Fr x = src[e];
-        if (fac) x = mul(x, fac[(size_t)r * N_CELLS + ((h * N_BLOB + e) >> 6)]);
+        if (fac) x = mul(x, fac[(size_t)r * fac_stride + ((h * N_BLOB + e) >> 6)]);
         vl_store(s, e, x);
     }
     __syncthreads();
@@ -623,7 +625,7 @@ __global__ void k_rec_dit_last(const Fr* __restrict__ T, const Fr* __restrict__ 
 }
 // first DIF layer + DIF_4096 on half h, then cell-wise multiply by fac (the inverse vanishing values): U -> V
 __global__ __launch_bounds__(1024) void k_rec_dif_half(const Fr* __restrict__ U, const Fr* __restrict__ fac, Fr* __restrict__ V,
-                                                      const Fr* __restrict__ w8192) {
+                                                      const Fr* __restrict__ w8192, int fac_stride) {
     extern __shared__ uint32_t s[];
     const int r = blockIdx.x, h = blockIdx.y;
     const Fr* src = U + (size_t)r * N_EXT;
@@ -637,7 +639,7 @@ __global__ __launch_bounds__(1024) void k_rec_dif_half(const Fr* __restrict__ U,
     v_dif_forward4096(s, w8192);
     Fr* dst = V + (size_t)r * N_EXT + (size_t)h * N_BLOB;
     for (int e = threadIdx.x; e < N_BLOB; e += 1024)
-        dst[e] = mul(vl_load(s, e), fac[(size_t)r * N_CELLS + ((h * N_BLOB + e) >> 6)]);
+        dst[e] = mul(vl_load(s, e), fac[(size_t)r * fac_stride + ((h * N_BLOB + e) >> 6)]);
 }
 
 namespace launch {
@@ -774,16 +776,16 @@ void rec_vanishing(const void* zp, const int* deg, const void* w8192, const Fr8&
     k_rec_vanishing<<<(R * N_CELLS + 127) / 128, 128, 0, st>>>((const Fr*)zp, deg, (const Fr*)w8192, as_fr2(seven64), (Fr*)zeval,
                                                               (Fr*)zcinv, R);
 }
-void rec_dit_half(int R, const void* V, const void* fac, void* T, const void* w8192, hipStream_t st) {
-    k_rec_dit_half<<<dim3(R, 2), 1024, LDS_NTT, st>>>((const Fr*)V, (const Fr*)fac, (Fr*)T, (const Fr*)w8192);
+void rec_dit_half(int R, const void* V, const void* fac, void* T, const void* w8192, hipStream_t st, int fac_stride) {
+    k_rec_dit_half<<<dim3(R, 2), 1024, LDS_NTT, st>>>((const Fr*)V, (const Fr*)fac, (Fr*)T, (const Fr*)w8192, fac_stride);
 }
 void rec_dit_last(int R, const void* T, const void* shift, const Fr8& n_inv, void* U, void* coeffs, int* status,
                   const void* w8192, int final_pass, hipStream_t st) {
     k_rec_dit_last<<<R * N_BLOB / 256, 256, 0, st>>>((const Fr*)T, (const Fr*)shift, as_fr2(n_inv), (Fr*)U, (Fr*)coeffs, status,
                                                     (const Fr*)w8192, final_pass);
 }
-void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st) {
-    k_rec_dif_half<<<dim3(R, 2), 1024, LDS_NTT, st>>>((const Fr*)U, (const Fr*)fac, (Fr*)V, (const Fr*)w8192);
+void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st, int fac_stride) {
+    k_rec_dif_half<<<dim3(R, 2), 1024, LDS_NTT, st>>>((const Fr*)U, (const Fr*)fac, (Fr*)V, (const Fr*)w8192, fac_stride);
 }
 }  // namespace launch
 }  // namespace kzg

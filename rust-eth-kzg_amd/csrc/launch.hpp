@@ -30,7 +30,14 @@ void blob_to_coeffs(int n, const uint8_t* blobs, void* coeffs /*Fr*/, void* cano
 // y is zero in both forms).  Writes nothing else and needs no workspace.
 void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be32, void* y_mont, int* bad, const void* w29, const Fr8& n_inv,
                   hipStream_t st);
-void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st);
+// The column layout of a block's data columns (eth_kzg_amd_compute_data_columns / _recover_data_columns): a launch over n blobs that are
+// blobs [b0, b0 + n) of a call of n_total writes cell c of its blob b to cells + ((size_t)c * n_total + b0 + b) * 2048 and proof c to
+// proofs + ((size_t)c * n_total + b0 + b) * 48, the output pointers being the WHOLE call's arrays.  Null: the blob-major layout
+// [blob][128] from the pointer on, what every other call launches (its kernels are the instantiations they always were).
+struct Columns {
+    size_t n_total, b0;
+};
+void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st, const Columns* cols = nullptr);
 // every scalar leaves as its balanced GLV halves (what launch::glv_split would make of it)
 void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, const Fr8& inv128, int segs, const Fr8* seg_shifts,
                   hipStream_t st);
@@ -39,7 +46,7 @@ void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, con
 // (both may be null): cells 0..63 of a blob with status 0 are copied from its bytes instead of being transformed back.
 void fk20_tap_consts(const void* w29, const Fr8& scale, void* out /*8192 x 36 B*/, hipStream_t st);
 void coeffs_to_cells_scalars(int n, const void* coeffs, uint8_t* cells, void* scalars, const uint8_t* blobs, const int* status, const void* w29,
-                             const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st);
+                             const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st, const Columns* cols = nullptr);
 void test_ntt4096(const uint8_t* in, uint8_t* out, const void* w29, const Fr8& n_inv, int inverse_dit, hipStream_t st);
 void test_scalars_be(const uint8_t* in, void* out, size_t n, hipStream_t st);
 void test_field_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, int n, int is_fp, hipStream_t st);
@@ -119,7 +126,8 @@ void g1_slp_launch(int kind, void* arena, int stride, const uint32_t* words, int
 void g1_set_inf(void* X, size_t n, hipStream_t st, int fmt);
 int coop_points_max();  // largest launch (points) that takes the four-lanes-per-point kernels (k_g1misc.hip)
 void spin(uint64_t wall_clock_ticks, hipStream_t st);  // one wave, resident for that many ticks of the constant-rate device clock
-void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slices, hipStream_t st, int fmt);
+// cols (JacS only): the record of (position, slice) goes to out + ((size_t)pos * n_total + b0 + slice) * 48 instead of (slice * n_pos + pos) * 48
+void g1_compress(const void* X, uint8_t* out, int n_pos, int stride, int n_slices, hipStream_t st, int fmt, const Columns* cols = nullptr);
 void g1_sum_positions(void* X /*JacS*/, int n_pos, int stride, int n_slices, hipStream_t st);
 // subgroup_check: 0 none, 1 endomorphism test, 2 definitional [r]P == O
 void g1_decompress(const uint8_t* in, void* out /*G1Affine*/, int* status, int n, int subgroup_check, const Fp12w& beta,
@@ -170,10 +178,11 @@ size_t pip_workspace_bytes(int n_max);
 void copy_affine(const void* src, void* dst, int n, hipStream_t st);
 void msm_pippenger2(const void* points, const void* sc0, int n0, const void* sc1, int n1, void* workspace, void* out_affine2,
                     const Fp12w& beta, hipStream_t st);
-void rec_dit_half(int R, const void* V, const void* fac, void* T, const void* w8192, hipStream_t st);
+// fac_stride: factors per blob (128), or 0 when all R blobs share the 128 factors of one vanishing polynomial
+void rec_dit_half(int R, const void* V, const void* fac, void* T, const void* w8192, hipStream_t st, int fac_stride = 128);
 void rec_dit_last(int R, const void* T, const void* shift, const Fr8& n_inv, void* U, void* coeffs, int* status,
                   const void* w8192, int final_pass, hipStream_t st);
-void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st);
+void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st, int fac_stride = 128);
 
 // k_verify_many.hip: many independent verifications in one pass (per-problem scalars, one lane or quad per scalar multiplication).
 // pts = [proofs n | commitments m] (G1Affine).  The expanded source has m rows over all problems (row_batch, row_start) and two scalars

@@ -50,38 +50,41 @@ int Engine::recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_
 // list entry) and `present` (domain-order masks); the cell bytes are read from d_cells at list position k, or at
 // slot[k] when the caller's buffer is the flat [R][128][2048] layout.  Leaves the coefficients in d_coeffs_.
 int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
-                      const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap) {
+                      const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap, const std::vector<int>* src_of, bool shared_pattern) {
     hipStream_t st = stream_;
     const int n = (int)slot.size();
     Fr seven64 = fr_u64(7);
     for (int i = 0; i < 6; i++) seven64 = sqr(seven64);
-    PoolBuf d_slot(*this, (size_t)n * sizeof(int)), d_stof(*this, (size_t)n * sizeof(int));
+    // Rv vanishing polynomials, blob r reading the factors at r * fac_stride: one per blob, or ONE for the call when every blob misses the same cells
+    const int Rv = shared_pattern ? 1 : R, fac_stride = shared_pattern ? 0 : N_CELLS;
+    PoolBuf d_slot(*this, (size_t)n * sizeof(int)), d_stof(*this, (size_t)n * sizeof(int)), d_src(*this, src_of ? (size_t)n * sizeof(int) : 0);
     PoolBuf d_E(*this, (size_t)R * N_EXT * sizeof(Fr)), d_T(*this, (size_t)R * N_EXT * sizeof(Fr)), d_U(*this, (size_t)R * N_EXT * sizeof(Fr));
-    PoolBuf d_zp(*this, (size_t)R * 65 * sizeof(Fr)), d_deg(*this, R * sizeof(int)), d_present(*this, present.size() * 4);
-    PoolBuf d_zeval(*this, (size_t)R * N_CELLS * sizeof(Fr)), d_zcinv(*this, (size_t)R * N_CELLS * sizeof(Fr)), d_st(*this, R * sizeof(int));
+    PoolBuf d_zp(*this, (size_t)Rv * 65 * sizeof(Fr)), d_deg(*this, Rv * sizeof(int)), d_present(*this, present.size() * 4);
+    PoolBuf d_zeval(*this, (size_t)Rv * N_CELLS * sizeof(Fr)), d_zcinv(*this, (size_t)Rv * N_CELLS * sizeof(Fr)), d_st(*this, R * sizeof(int));
     if (n) {
         HIPCK(hipMemcpyAsync(d_slot.p, slot.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
         HIPCK(hipMemcpyAsync(d_stof.p, stof.data(), n * sizeof(int), hipMemcpyHostToDevice, st));
+        if (src_of) HIPCK(hipMemcpyAsync(d_src.p, src_of->data(), n * sizeof(int), hipMemcpyHostToDevice, st));
     }
     HIPCK(hipMemcpyAsync(d_present.p, present.data(), present.size() * 4, hipMemcpyHostToDevice, st));
-    launch::rec_vanishing_poly((const uint32_t*)d_present.p, d_w8192_, d_zp.p, (int*)d_deg.p, R, st);
+    launch::rec_vanishing_poly((const uint32_t*)d_present.p, d_w8192_, d_zp.p, (int*)d_deg.p, Rv, st);
     HIPCK(hipMemsetAsync(d_E.p, 0, (size_t)R * N_EXT * sizeof(Fr), st));
     HIPCK(hipMemsetAsync(d_st.p, 0, R * sizeof(int), st));
     if (n) launch::cells_to_fr(d_cells, d_E.p, (const int*)d_slot.p, (int*)d_st.p, (const int*)d_stof.p,
-                               flat_source ? (const int*)d_slot.p : nullptr, n, st);  // E in cell order
-    launch::rec_vanishing(d_zp.p, (const int*)d_deg.p, d_w8192_, to8(seven64), d_zeval.p, d_zcinv.p, R, st);
-    launch::rec_dit_half(R, d_E.p, d_zeval.p, d_T.p, d_w8192_, st);                                      // (E*Z) -> IFFT ...
+                               src_of ? (const int*)d_src.p : flat_source ? (const int*)d_slot.p : nullptr, n, st);  // E in cell order
+    launch::rec_vanishing(d_zp.p, (const int*)d_deg.p, d_w8192_, to8(seven64), d_zeval.p, d_zcinv.p, Rv, st);
+    launch::rec_dit_half(R, d_E.p, d_zeval.p, d_T.p, d_w8192_, st, fac_stride);                          // (E*Z) -> IFFT ...
     launch::rec_dit_last(R, d_T.p, d_coset_, n_inv8192_, d_U.p, nullptr, nullptr, d_w8192_, 0, st);      // ... * 7^i
-    launch::rec_dif_half(R, d_U.p, d_zcinv.p, d_E.p, d_w8192_, st);                                      // coset FFT, / Z
+    launch::rec_dif_half(R, d_U.p, d_zcinv.p, d_E.p, d_w8192_, st, fac_stride);                          // coset FFT, / Z
     launch::rec_dit_half(R, d_E.p, nullptr, d_T.p, d_w8192_, st);                                        // coset IFFT ...
     launch::rec_dit_last(R, d_T.p, d_coset_inv_, n_inv8192_, nullptr, d_coeffs_, (int*)d_st.p, d_w8192_, 1, st);  // ... * 7^-i
     std::vector<int> hst(R);
     HIPCK(hipMemcpyAsync(hst.data(), d_st.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
     if (tap) {  // the stage hook: what the stages left, while the pool still holds it
-        if (tap->deg) HIPCK(hipMemcpyAsync(tap->deg, d_deg.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
-        if (tap->zp) HIPCK(hipMemcpyAsync(tap->zp, d_zp.p, (size_t)R * 65 * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        if (tap->zeval) HIPCK(hipMemcpyAsync(tap->zeval, d_zeval.p, (size_t)R * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        if (tap->zcinv) HIPCK(hipMemcpyAsync(tap->zcinv, d_zcinv.p, (size_t)R * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (tap->deg) HIPCK(hipMemcpyAsync(tap->deg, d_deg.p, Rv * sizeof(int), hipMemcpyDeviceToHost, st));
+        if (tap->zp) HIPCK(hipMemcpyAsync(tap->zp, d_zp.p, (size_t)Rv * 65 * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (tap->zeval) HIPCK(hipMemcpyAsync(tap->zeval, d_zeval.p, (size_t)Rv * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (tap->zcinv) HIPCK(hipMemcpyAsync(tap->zcinv, d_zcinv.p, (size_t)Rv * N_CELLS * sizeof(Fr), hipMemcpyDeviceToHost, st));
     }
     SYNC_CHECKED(st);
     for (int r = 0; r < R; r++) {
