@@ -388,6 +388,48 @@ CResult eth_kzg_amd_verify_blob_kzg_proof_many_device(const DASContext *ctx, uin
                                                       const uint8_t *d_commitments, const uint8_t *d_proofs, bool *verified,
                                                       int32_t *status, void *hip_stream);
 
+/* MANY blobs against their 128 CELL PROOFS in one call, A VERDICT FOR EACH: the throughput form of the check a blob transaction gets since
+ * PeerDAS (EIP-7594), where the wire carries the blob, its commitment and the blob's 128 cell proofs and the transaction pool checks
+ * cells = compute_cells(blob), then verify_cell_kzg_proof_batch([commitment] * 128, [0..127], cells, proofs).  Item i: blobs[i] -> 131072
+ * bytes, commitments[i] -> 48 bytes, proofs[i][k] -> 48 bytes for k < 128.  Item i gets the verdict that
+ * eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex with ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT gives the problem (128 x commitments[i], indices
+ * 0..127, compute_cells(blobs[i]), proofs[i]); the statuses follow the order of checks of the reference's two calls, compute_cells first:
+ *   status[i] = 1  the blob holds a field element >= r (also when a point of the item is bad as well),
+ *   else      = 2  the commitment or one of the 128 proofs is not a canonical point of the subgroup,
+ *   else      = 0  and verified[i] is the verdict.  verified[i] is false whenever status[i] != 0.  status may be NULL.
+ * There is no status 3: lengths and indices hold by construction.  The identity is a valid commitment and a valid proof: the all-zero
+ * blob with 129 identities verifies.
+ * The call: n = 0 is Ok; n > 2^24, or a NULL array with n > 0, is Err("InvalidInput...") before the context is touched; otherwise Err
+ * only for a device failure, and then every verified[i] is false.
+ * How: there is no flags word and no new transcript.  The blobs are a fourth SOURCE of the many-verification's pass
+ * (csrc/verify_many.hip): blob i's bytes are cells 0..63 of its problem as they stand, and cells 64..127 are computed behind them in the
+ * pass's arena without leaving the CU (csrc/k_ntt.hip: k_blob_to_extension -- one block per blob: the inverse transform, the twist and the
+ * forward transform on one image in LDS; no coefficient is written to HBM and none of the prover's workspace is used); a refused blob
+ * gets zero bytes there.  The challenge of item i is always the leaf-hashed one of that problem alone, exactly as _many_ex takes it under
+ * the flag, the leaves hashed on the GPU out of the arena: they bind the computed cells, the caller's commitment bytes and the caller's
+ * proofs.  The folding weights, the one pairing check per pass and the search (its pairings on the GPU from
+ * ETH_KZG_AMD_GPU_PAIRING_MIN probes per level) keep their form.  A verdict never depends on the challenge, and the caller never sees
+ * it; the soundness paragraph of eth_kzg_amd_verify_cell_kzg_proof_batch_many_device_ex carries over unchanged.
+ * The call runs on pass slots (at most 1024 blobs per pass, three parts side by side from 192 blobs on; not part of the contract): it
+ * does not take the context's big lock, needs none of the prover's work sets and runs next to every other entry point.
+ * Host form: cut into contiguous slices by item over the context's device list; per pass the blobs and proofs are gathered into pinned
+ * memory and uploaded -- 128 KB + 6 KB per blob up, nothing but status words, leaf digests and sums down -- where
+ * compute_cells_and_kzg_proofs_batch + _many_ex move 256 KB of cells down and up again and 56 x 128 bytes of commitments and indices.
+ * Device form: flat arrays in one GPU's HBM -- d_blobs n * 131072 bytes with the alignment
+ * eth_kzg_amd_verify_blob_kzg_proof_many_device asks for, d_commitments n * 48 and d_proofs n * 128 * 48 bytes from any byte address --
+ * verified / status HOST memory.  One device-to-device copy per pass brings the blobs into the arena; only the n * 48 commitment bytes
+ * come down.  Synchronous; work already queued on `hip_stream` (NULL: the default stream) is waited for.  Runs on the device that owns
+ * the buffers: all three pointers are resolved, and anything but device memory of ONE device of the context is Err("InvalidInput...").
+ * Out of scope: interpolation sums taken straight from the coefficients in place of the per-cell interpolation; writing the decoded
+ * evaluations from the new kernel and skipping the cells' decoding; a reference-transcript variant; _partial / _combine; sharding a device
+ * form over GPUs.  The Node binding is not extended.  When it pays: INTEGRATION.md. */
+CResult eth_kzg_amd_verify_blob_cell_proofs_many(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs,
+                                                 const uint8_t *const *commitments, const uint8_t *const *const *proofs, bool *verified,
+                                                 int32_t *status);
+CResult eth_kzg_amd_verify_blob_cell_proofs_many_device(const DASContext *ctx, uint64_t n, const uint8_t *d_blobs,
+                                                        const uint8_t *d_commitments, const uint8_t *d_proofs, bool *verified,
+                                                        int32_t *status, void *hip_stream);
+
 /* verify_cell_kzg_proof_batch on flat arrays in this GPU's HBM: n * 48 commitment bytes (one per cell, NOT deduplicated, as in
  * the host form), n indices, n * 2048 cell bytes, n * 48 proof bytes.  The GPU's part reads cells and proofs where they are;
  * the transcript hash runs on a host core, so its bytes come down (in chunks, under the hash) and the call is synchronous;

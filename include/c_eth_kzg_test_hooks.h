@@ -222,6 +222,22 @@ int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext *ctx, uint
                                                      int32_t *fold_verdicts, int32_t *probes4, uint8_t *probe_sums96, uint64_t max_probes,
                                                      uint64_t *n_probes, uint8_t *zs32, uint8_t *ys32);
 
+/* k_blob_to_extension alone (csrc/k_ntt.hip) behind the copy of cells 0..63: the extended blob of n blobs, 1 <= n <= 1024, on the
+ * context's first device.  blobs[b] -> 131072 bytes on the host.  Outputs, host: out_cells[n][128][2048] -- cells 0..63 the blob's bytes,
+ * cells 64..127 the kernel's (zero bytes for a refused blob) --, out_bad[n] = the problem's cell-status word: 1 for a blob that holds an
+ * element >= r, else 0.  Synchronous; 0 on success. */
+int eth_kzg_amd_test_blob_extension(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs, uint8_t *out_cells, int32_t *out_bad);
+
+/* The tap of eth_kzg_amd_test_verify_many_sums_device on a pass of eth_kzg_amd_verify_blob_cell_proofs_many / _many_device (c_eth_kzg.h;
+ * tests/test_gpu_blob_cells.py, the expansion into problems is tests/blob_cells.py): problem b of every output is item b, 128 cells each
+ * (leaves32: n x 128 x 32 bytes).  on_device = 0: blobs / commitments / proofs are the host form's pointer lists; 1: the device form's
+ * flat arrays in device memory (context's first device).  One pass only (3 before any launch if the call would be cut, or for a NULL
+ * buffer); nothing is added on the device. */
+int eth_kzg_amd_test_verify_blob_cell_proofs_sums(const DASContext *ctx, uint64_t n, int on_device, const void *blobs, const void *commitments,
+                                                  const void *proofs, int32_t *verified, int32_t *status, int32_t *form4, uint8_t *sums96,
+                                                  uint32_t *rho, uint8_t *fold96, int32_t *probe_ranges, uint8_t *probe_sums96,
+                                                  uint64_t max_probes, uint64_t *n_probes, uint8_t *digests32, uint8_t *leaves32);
+
 /* k_pairing_check alone (csrc/k_pairing.hip), next to the host's checks of the same pairs.  key: 0 = ([tau^64]_2, -[1]_2), the cell
  * verifier's pair of keys; 1 = ([tau]_2, -[1]_2), the point verifier's.  pairs: n x 2 x 48 bytes, compressed G1 (on the curve; no subgroup
  * test), 1 <= n <= 65536.  They are decompressed on the host and become the passes' Jacobian form.  rescale, a word of flags: bit 0 = every

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_kzg_proof_many", "eth_kzg_amd_verify_kzg_proof_many_device",
     "eth_kzg_amd_verify_blob_kzg_proof_many", "eth_kzg_amd_verify_blob_kzg_proof_many_device",
     "eth_kzg_amd_verify_data_columns", "eth_kzg_amd_verify_data_columns_device",
+    "eth_kzg_amd_verify_blob_cell_proofs_many", "eth_kzg_amd_verify_blob_cell_proofs_many_device",
     "eth_kzg_amd_compute_data_columns", "eth_kzg_amd_compute_data_columns_device",
     "eth_kzg_amd_recover_data_columns", "eth_kzg_amd_recover_data_columns_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
@@ -95,6 +96,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_blob_eval_at", "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums",
     "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats", "eth_kzg_amd_test_g1_decode",
     "eth_kzg_amd_test_verify_data_columns_sums",
+    "eth_kzg_amd_test_blob_extension", "eth_kzg_amd_test_verify_blob_cell_proofs_sums",
 ]
 
 _lib = None
@@ -198,6 +200,8 @@ def load_library():
         "eth_kzg_amd_verify_blob_kzg_proof_many": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_verify_blob_kzg_proof_many_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_verify_data_columns": [P, U64, P, U64, P, P, P, C.c_uint32, P, P],
+        "eth_kzg_amd_verify_blob_cell_proofs_many": [P, U64, P, P, P, P, P],
+        "eth_kzg_amd_verify_blob_cell_proofs_many_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_verify_data_columns_device": [P, U64, P, U64, P, P, P, C.c_uint32, P, P, P],
         "eth_kzg_amd_compute_data_columns": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_compute_data_columns_device": [P, U64, P, P, P, P, P, P],
@@ -244,6 +248,8 @@ def load_library():
         "eth_kzg_amd_test_search_stats": [P, P],
         "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P, P, P],
         "eth_kzg_amd_test_verify_data_columns_sums": [P, U64, C.c_int, P, U64, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P, P],
+        "eth_kzg_amd_test_blob_extension": [P, U64, P, P, P],
+        "eth_kzg_amd_test_verify_blob_cell_proofs_sums": [P, U64, C.c_int, P, P, P, P, P, P, P, P, P, P, P, U64, P, P, P],
     }.items():
         if hasattr(lib, name):
             getattr(lib, name).argtypes = args
@@ -870,6 +876,67 @@ class DASContext:
             self._ctx, n, C.c_void_p(d_blobs), C.c_void_p(d_commitments), C.c_void_p(d_proofs), ver, st,
             C.c_void_p(stream) if stream else None))
         return [bool(v) for v in ver][:n], list(st)[:n]
+
+    @staticmethod
+    def _marshal_blob_cell_proofs(items):
+        """-> (blobs**, commitments**, proofs***, keep-alive): the pointer tables of eth_kzg_amd_verify_blob_cell_proofs_many; a blob
+        object named several times is not copied"""
+        n = len(items)
+        if any(len(b) != BYTES_PER_BLOB or len(c) != 48 or len(ps) != CELLS_PER_EXT_BLOB or any(len(p) != 48 for p in ps) for b, c, ps in items):
+            raise KzgError("InvalidLength")
+        ba, k1 = _alias_ptrs([it[0] for it in items])
+        ca, k2 = _flat_ptrs([it[1] for it in items], 48)
+        inner, k3 = _flat_ptrs([p for it in items for p in it[2]], 48)
+        outer = np.uint64(inner.ctypes.data) + np.arange(max(1, n), dtype=np.uint64) * np.uint64(CELLS_PER_EXT_BLOB * 8)
+        return ba, ca, outer, (k1, k2, k3, inner)
+
+    def prepare_verify_blob_cell_proofs_many(self, items):
+        """items = [(blob, commitment, [128 cell proofs]), ...]: marshal them into the pointer tables of
+        eth_kzg_amd_verify_blob_cell_proofs_many ONCE and return a zero-argument callable that runs the call and returns (verified
+        list[bool], status list[int]) -- per item what compute_cells + verify_cell_kzg_proof_batch([commitment] * 128, 0..127, cells,
+        proofs) say of it: status 1 the blob holds an element >= r, else 2 a bad G1 point, else 0 and the verdict.  A wrong byte
+        length or proof count cannot cross the C ABI and raises InvalidLength here."""
+        n = len(items)
+        ba, ca, pa, keep = self._marshal_blob_cell_proofs(items)
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+
+        def run(_keep=keep):
+            self._check(self._lib.eth_kzg_amd_verify_blob_cell_proofs_many(self._ctx, n, _vp(ba), _vp(ca), _vp(pa), ver, st))
+            return [bool(v) for v in ver][:n], list(st)[:n]
+        return run
+
+    def verify_blob_cell_proofs_many(self, items):
+        """Many blobs against their 128 cell proofs in one call, a verdict for each (see prepare_verify_blob_cell_proofs_many)."""
+        return self.prepare_verify_blob_cell_proofs_many(items)()
+
+    def verify_blob_cell_proofs_many_device(self, n, d_blobs, d_commitments, d_proofs, stream=None):
+        """The same on flat arrays in device memory (eth_kzg_amd_verify_blob_cell_proofs_many_device): integer device addresses of
+        n*131072 blob bytes (4-byte aligned), n*48 commitment and n*128*48 proof bytes.  -> (verified list[bool], status list[int]).
+        Synchronous; waits for what `stream` (None: the default stream) has queued."""
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_verify_blob_cell_proofs_many_device(
+            self._ctx, n, C.c_void_p(d_blobs), C.c_void_p(d_commitments), C.c_void_p(d_proofs), ver, st,
+            C.c_void_p(stream) if stream else None))
+        return [bool(v) for v in ver][:n], list(st)[:n]
+
+    def test_blob_extension(self, blobs):
+        """eth_kzg_amd_test_blob_extension (hooks library): -> (cells[n][128] as bytes, bad[n])"""
+        n = len(blobs)
+        if any(len(b) != BYTES_PER_BLOB for b in blobs):
+            raise KzgError("InvalidLength")
+        ba, keep = _alias_ptrs(list(blobs))
+        out = np.zeros(max(1, n) * CELLS_PER_EXT_BLOB * BYTES_PER_CELL, dtype=np.uint8)
+        bad = (C.c_int32 * max(1, n))()
+        rc = self._lib.eth_kzg_amd_test_blob_extension(self._ctx, n, _vp(ba), _vp(out), bad)
+        if rc != 0:
+            raise KzgError("test_blob_extension: status %d" % rc)
+        raw = out.tobytes()
+        cells = [[raw[(b * CELLS_PER_EXT_BLOB + k) * BYTES_PER_CELL:(b * CELLS_PER_EXT_BLOB + k + 1) * BYTES_PER_CELL] for k in range(CELLS_PER_EXT_BLOB)]
+                 for b in range(n)]
+        del keep
+        return cells, list(bad)[:n]
 
     def verify_blob_kzg_proof(self, blob, commitment, proof):
         if len(blob) != BYTES_PER_BLOB or len(commitment) != 48 or len(proof) != 48:

@@ -847,6 +847,39 @@ CResult eth_kzg_amd_verify_blob_kzg_proof_many_device(const DASContext* ctx, uin
         return err(std::string("DeviceError(") + ex.what() + ")");
     }
 }
+// Many blobs against their 128 cell proofs, a verdict each: the blob source of the cell many-verification (verify_many.hip).  Count and
+// arrays first (verify_host.hpp: validate_blob_cells_call), then the device list (host form: contiguous slices by item) or the owner of
+// ALL THREE buffers (device form).  Nothing here takes a lane or the context's big lock: the passes run on pass slots.
+CResult eth_kzg_amd_verify_blob_cell_proofs_many(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, const uint8_t* const* commitments,
+                                                 const uint8_t* const* const* proofs, bool* verified, int32_t* status) {
+    if (kzg::validate_blob_cells_call(n, !blobs, !commitments, !proofs, !verified) != kzg::INPUT_VALID)
+        return err("InvalidInput: more than 2^24 items, or a null array");  // (before the context is looked at)
+    const auto in = kzg::VerifyManyInput::host_blobs(blobs, commitments, proofs);
+    auto items_ok = [&] {
+        for (uint64_t i = 0; i < n; i++) verified[i] = false;
+        for (uint64_t i = 0; i < n; i++) {
+            if (!blobs[i] || !commitments[i] || !proofs[i]) return false;
+            for (int k = 0; k < kzg::N_CELLS; k++)
+                if (!proofs[i][k]) return false;
+        }
+        return true;
+    };
+    return sliced_call(ctx, n, kzg::BLOB_CELLS_MAX_ITEMS, verified, status, items_ok, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+        return many_failure(e, e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver + lo, st + lo));
+    });
+}
+CResult eth_kzg_amd_verify_blob_cell_proofs_many_device(const DASContext* ctx, uint64_t n, const uint8_t* d_blobs, const uint8_t* d_commitments,
+                                                        const uint8_t* d_proofs, bool* verified, int32_t* status, void* hip_stream) {
+    if (kzg::validate_blob_cells_call(n, !d_blobs, !d_commitments, !d_proofs, !verified) != kzg::INPUT_VALID)
+        return err("InvalidInput: more than 2^24 items, or a null array");
+    live(ctx);
+    if (n == 0) return ok();
+    for (uint64_t i = 0; i < n; i++) verified[i] = false;
+    const void* const ptrs[3] = {d_blobs, d_commitments, d_proofs};
+    kzg::Engine* e = engine_of_device_pointers(ctx, ptrs, 3);
+    if (!e) return err("InvalidInput: the three buffers are not device memory of one device of this context");
+    return device_many(e, n, kzg::VerifyManyInput::device_blobs(d_blobs, d_commitments, d_proofs, (hipStream_t)hip_stream), verified, status);
+}
 void eth_kzg_amd_set_profiling(const DASContext* ctx, int on) { eng(ctx)->set_profiling(on != 0); }
 int eth_kzg_amd_get_stage_times(const DASContext* ctx, double* ms, uint64_t* launches, int n) {
     double m[kzg::Engine::ST_COUNT];

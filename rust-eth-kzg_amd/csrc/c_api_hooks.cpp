@@ -205,6 +205,26 @@ int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext* ctx, uint
     return eng(ctx)->test_verify_kzg_proof_many_sums(n, in, forced_pass, verified, status, pass_starts, max_passes, n_passes, leaves32, seeds32, rho, fold96,
                                                      fold_verdicts, probes4, probe_sums96, max_probes, n_probes, zs32, ys32);
 }
+int eth_kzg_amd_test_blob_extension(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, uint8_t* out_cells, int32_t* out_bad) {
+    if (n < 1 || n > 1024 || !blobs || !out_cells || !out_bad) return kzg::ERR_INPUT;
+    for (uint64_t b = 0; b < n; b++)
+        if (!blobs[b]) return kzg::ERR_INPUT;
+    return eng(ctx)->test_blob_extension((int)n, blobs, out_cells, out_bad);
+}
+// the tap on a pass of the blob source of the cell many-verification (eth_kzg_amd_verify_blob_cell_proofs_many / _many_device)
+int eth_kzg_amd_test_verify_blob_cell_proofs_sums(const DASContext* ctx, uint64_t n, int on_device, const void* blobs, const void* commitments,
+                                                  const void* proofs, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho,
+                                                  uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
+                                                  uint8_t* digests32, uint8_t* leaves32) {
+    if (!blobs || !commitments || !proofs || !verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || !digests32 ||
+        (max_probes && (!probe_ranges || !probe_sums96)) || (on_device != 0 && on_device != 1) || n < 1 || n > (1u << 20))
+        return kzg::ERR_INPUT;
+    const auto in = on_device ? kzg::VerifyManyInput::device_blobs((const uint8_t*)blobs, (const uint8_t*)commitments, (const uint8_t*)proofs, nullptr)
+                              : kzg::VerifyManyInput::host_blobs((const uint8_t* const*)blobs, (const uint8_t* const*)commitments,
+                                                                 (const uint8_t* const* const*)proofs);
+    return eng(ctx)->test_verify_many_sums_in(n, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
+                                              digests32, leaves32);
+}
 int eth_kzg_amd_test_pairing_check_many(const DASContext* ctx, int key, uint64_t n, const uint8_t* pairs, int rescale, int8_t* out_gpu, int8_t* out_host,
                                         uint8_t* out_miller_gpu, uint8_t* out_miller_host) {
     if ((key != 0 && key != 1) || n < 1 || n > (1u << 16) || !pairs || !out_gpu || !out_host || rescale < 0) return kzg::ERR_INPUT;

@@ -65,6 +65,10 @@ struct VerifyManyTap {
 //     cells[b][i], proofs[b][i] on the host, or (col_device) d_commitments 48 col_blobs bytes, d_cells / d_proofs [columns][col_blobs]
 //     entries in this GPU's HBM.  Once the call has taken its refused columns out (verify_many.hip), problem b is the caller's column
 //     col_place[b] in all of these.  col: the commitments de-duplicated once for the whole call (null: the call makes it)
+//   blobs with their 128 cell proofs (from_blobs; eth_kzg_amd_verify_blob_cell_proofs_many / _many_device): problem b is the blob's 128
+//     cells with the indices 0..127 under ONE commitment; the pass computes the cells itself (k_ntt.hip: k_blob_to_extension) and the
+//     challenge is always the leaf-hashed one.  blobs[b] -> 131072 bytes, blob_commitments[b] -> 48 bytes, proofs[b][k] -> 48 bytes on the
+//     host, or (blobs_device) d_blobs n x 131072 bytes (4-byte aligned), d_commitments n x 48, d_proofs n x 128 x 48 in this GPU's HBM
 // leaf: every problem's challenge is the leaf-hashed one of the problem alone (verify_host.hpp: CellLeafTranscript, cell_leaf_root),
 // the leaves hashed on the GPU out of the pass's arena; else the reference's transcript on the host threads.
 struct VerifyManyInput {
@@ -79,6 +83,9 @@ struct VerifyManyInput {
     const uint64_t *col_place = nullptr, *col_indices = nullptr;
     const uint8_t* const* col_commitments = nullptr;
     const ColumnCommitments* col = nullptr;
+    bool from_blobs = false, blobs_device = false;
+    const uint8_t *const *blobs = nullptr, *const *blob_commitments = nullptr;
+    const uint8_t* d_blobs = nullptr;
     static VerifyManyInput lists(const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
                                  const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells,
                                  const uint64_t* n_proofs, const uint8_t* const* const* proofs, bool leaf) {
@@ -106,10 +113,27 @@ struct VerifyManyInput {
         in.columns = in.col_device = true; in.col_blobs = n_blobs; in.col_indices = column_indices;
         return in;
     }
-    bool on_device() const { return columns ? col_device : cell_starts != nullptr; }
-    uint64_t cells_of(uint64_t b) const { return columns ? col_blobs : on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b]; }
+    static VerifyManyInput host_blobs(const uint8_t* const* blobs, const uint8_t* const* commitments, const uint8_t* const* const* proofs) {
+        VerifyManyInput in = lists(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, /*leaf=*/true);
+        in.from_blobs = true; in.blobs = blobs; in.blob_commitments = commitments;
+        return in;
+    }
+    static VerifyManyInput device_blobs(const uint8_t* d_blobs, const uint8_t* d_commitments, const uint8_t* d_proofs, hipStream_t user_stream) {
+        VerifyManyInput in = flat_device(nullptr, d_commitments, nullptr, nullptr, d_proofs, user_stream, /*leaf=*/true);
+        in.from_blobs = in.blobs_device = true; in.d_blobs = d_blobs;
+        return in;
+    }
+    bool on_device() const { return from_blobs ? blobs_device : columns ? col_device : cell_starts != nullptr; }
+    uint64_t cells_of(uint64_t b) const {
+        return from_blobs ? 128 : columns ? col_blobs : on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b];
+    }
     VerifyManyInput from(uint64_t lo) const {  // the problems from lo on (the flat arrays stay: cell_starts holds absolute entries)
         VerifyManyInput s = *this;
+        if (from_blobs) {  // (one entry per blob in every array: the arrays themselves move)
+            if (blobs_device) { s.d_blobs += lo * 131072; s.d_commitments += lo * 48; s.d_proofs += lo * 128 * 48; }
+            else { s.blobs += lo; s.blob_commitments += lo; s.proofs += lo; }
+            return s;
+        }
         if (columns) {
             if (col_place) { s.col_place += lo; return s; }
             // before the places are made ONLY the host form may be cut: nothing here carries an offset into d_cells / d_proofs
@@ -452,6 +476,8 @@ public:
                                         uint64_t* n_probes, uint8_t* zs32 = nullptr, uint8_t* ys32 = nullptr /* the blob source: [n][32] each */);
     // k_blob_eval_at alone: n blobs and n points (32 big-endian bytes, reduced mod r) from the host -> ys32[n][32], bad[n]
     int test_blob_eval_at(int n, const uint8_t* const* blobs, const uint8_t* zs_be32, uint8_t* out_ys_be32, int32_t* out_bad);
+    // k_blob_to_extension alone behind the copy of cells 0..63: n blobs from the host -> out_cells[n][128][2048], bad[n] (the status word)
+    int test_blob_extension(int n, const uint8_t* const* blobs, uint8_t* out_cells, int32_t* out_bad);
     // k_pairing_check and the host's checks on the same n pairs (compressed G1, n x 2 x 48 bytes) against key pair `key` (0: [tau^64]_2, -[1]_2;
     // 1: [tau]_2, -[1]_2); flags: see include/c_eth_kzg_test_hooks.h.  The Miller values (may be null): n x 576 bytes each
     int test_pairing_check_many(int key, uint64_t n, const uint8_t* pairs, int flags, int8_t* out_gpu, int8_t* out_host, uint8_t* out_miller_gpu,

@@ -771,6 +771,29 @@ int Engine::test_blob_eval_at(int n, const uint8_t* const* blobs, const uint8_t*
     return OK;
 }
 
+// k_blob_to_extension on its own: the blobs up into the first halves of their slices (the copy of cells 0..63), one launch, the slices down.
+int Engine::test_blob_extension(int n, const uint8_t* const* blobs, uint8_t* out_cells, int32_t* out_bad) {
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        hipStream_t st = stream_;
+        PoolBuf d_cells(*this, (size_t)n * 2 * BYTES_PER_BLOB), d_bad(*this, (size_t)n * sizeof(int));
+        HIPCK(hipMemsetAsync(d_cells.p, 0xff, (size_t)n * 2 * BYTES_PER_BLOB, st));  // what the kernel does not write shows
+        HIPCK(hipMemsetAsync(d_bad.p, 0, (size_t)n * sizeof(int), st));              // the status word is OR-ed into, as in a pass
+        for (int b = 0; b < n; b++)
+            HIPCK(hipMemcpyAsync((uint8_t*)d_cells.p + blob_cells_slice((size_t)b).blob_at, blobs[b], BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+        launch::blob_to_extension(n, (uint8_t*)d_cells.p, (int*)d_bad.p, d_w29_, n_inv4096_, st);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(out_cells, d_cells.p, (size_t)n * 2 * BYTES_PER_BLOB, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(out_bad, d_bad.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        SYNC_CHECKED(st);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 // The Reed-Solomon decoder of recovery on its own: the masks, slots and cell bytes staged as recover_batch_to_coeffs (list form) or
 // recover_cells_and_kzg_proofs_device (flat form) stage them, then rs_decode with its tap.  The caller (c_api_hooks.cpp) has validated
 // the counts and indices.  Outputs canonical big-endian.

@@ -256,6 +256,51 @@ __global__ __launch_bounds__(1024) void k_blob_eval_at(const uint8_t* __restrict
     }
 }
 
+// Cells 64..127 of a blob WITHOUT LEAVING THE CU (the blob source of the cell many-verification, verify_many.hip): the input stage and
+// the inverse transform of k_blob_to_coeffs, the twist by w8192^e and the forward transform of half 1 of k_coeffs_to_cells, on one LDS
+// image -- no coefficient goes to HBM and the kernel owns no workspace.  grid = n_blobs, block = 1024, dynamic LDS = 144 KiB (one block
+// per CU, as every transform of this file).
+//   cells     [n][128][2048]: the slice of blob b holds the blob's bytes in its first half (cells 0..63 ARE the blob: copied by the
+//             caller, never transformed back); this kernel writes the second half, each Fr once, big-endian, at its final address
+//   status[b] |= 1 if the blob holds an element >= r (the word k_cells_to_fr sets for the same problem): nothing is transformed then
+//             and the second half is written as zeros, so that whoever hashes or decodes the slice reads nothing stale
+// Values.  The blob's elements are plain integers (< 2^256 < 3r); after the inverse transform (< 27r) thread j holds the UNSCALED
+// coefficients c_e = n a_e, e = j + 1024 k, plain.  x_e = c_e w8192^e is one product against w29 (27 x 1 <= 64: < 2r, plain again, limbs
+// normalised: the forward network's input bound with room to spare); the forward network leaves n X[2 q' + 1] bit-reversed in place
+// (< 2 + 24 = 26r), and the n^-1 the coefficients never got rides on the product every output has anyway: 26 x 1 <= 64, K.ninv_plain
+// where k_coeffs_to_cells multiplies by one.  No premultiplied table: it would save nothing over w29.
+// Barriers.  The inverse network's last pass leaves unit j's results at j + 1024 k, and the forward network's first pass (h = 1024) reads
+// j + 1024 k: both are thread j's own unit (comments at the two networks), so the twist in between, which loads and stores exactly
+// those four elements, needs no barrier of its own: a wave's LDS operations execute in program order.
+__global__ __launch_bounds__(1024) void k_blob_to_extension(uint8_t* __restrict__ cells, int* __restrict__ status,
+                                                           const Fr29* __restrict__ w29, NttConsts K) {
+    extern __shared__ uint32_t s[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const uint8_t* blob = cells + (size_t)b * 2 * BYTES_PER_BLOB;
+    uint8_t* ext = cells + ((size_t)b * 2 + 1) * BYTES_PER_BLOB;
+    bool bad = false;
+    for (int e = tid; e < N_BLOB; e += 1024) {
+        const Fr x = load_fr_be(blob + 32 * e);
+        bad |= geq_mod<FrParams>(x.v);
+        lds_store(s, e, fr29_from_plain(x));  // the integer itself: < 2^256 < 3r, normalised limbs
+    }
+    const bool refused = __syncthreads_or(bad) != 0;  // the barrier between the input stage and the transform
+    if (refused) {                                    // uniform over the block
+        for (int k = tid; k < BYTES_PER_BLOB / 16; k += 1024) reinterpret_cast<uint4*>(ext)[k] = make_uint4(0, 0, 0, 0);
+        if (tid == 0) atomicOr(&status[b], 1);
+        return;
+    }
+    ntt4096_dit_inverse(s, w29);  // < 27 r; thread tid's own unit left tid + 1024 k
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {
+        const int e = tid + 1024 * k;
+        lds_store(s, e, fr29_mul(lds_load(s, e), w29[e]));  // 27 x 1 <= 64: n a_e w8192^e, < 2r
+    }
+    ntt4096_ct_forward(s, w29);  // < 26 r; its first pass reads what this thread has just stored
+    for (int e = tid; e < N_BLOB; e += 1024)
+        store_fr_be(ext + 32 * e, fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), K.ninv_plain))));  // 26 x 1 <= 64: X n / n = the value
+}
+
 // Stage H+I: cells = bit_reverse(NTT_8192(coeffs || 0)) serialised big-endian
 // (prover.rs:158-165, serialization/src/lib.rs:132-156).  X[2k+h] = NTT_4096(a_i * w8192^(i*h))[k];
 // the forward network leaves half h bit-reversed in place, which is exactly cells[h*4096 ...].
@@ -455,6 +500,7 @@ constexpr size_t LDS_NTT29 = (size_t)N_BLOB * RL * 4;  // 144 KiB: one 4096-poin
 void init_attributes() {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_coeffs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_eval_at), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_extension), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByColumn>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
@@ -495,6 +541,9 @@ void blob_to_coeffs(int n, const uint8_t* blobs, void* coeffs, void* canon, int*
 void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be32, void* y_mont, int* bad, const void* w29, const Fr8& n_inv,
                   hipStream_t st) {
     if (n > 0) k_blob_eval_at<<<n, 1024, LDS_NTT29, st>>>(blobs, (const Fr*)z_mont, y_be32, (Fr*)y_mont, bad, (const Fr29*)w29, ntt_consts(n_inv));
+}
+void blob_to_extension(int n, uint8_t* cells, int* status, const void* w29, const Fr8& n_inv, hipStream_t st) {
+    if (n > 0) k_blob_to_extension<<<n, 1024, LDS_NTT29, st>>>(cells, status, (const Fr29*)w29, ntt_consts(n_inv));
 }
 void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st, const Columns* cols) {
     if (cols) k_coeffs_to_cells<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, CellsByColumn{cells, cols->n_total, cols->b0}, (const Fr29*)w29);

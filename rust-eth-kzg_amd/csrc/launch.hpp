@@ -30,6 +30,10 @@ void blob_to_coeffs(int n, const uint8_t* blobs, void* coeffs /*Fr*/, void* cano
 // y is zero in both forms).  Writes nothing else and needs no workspace.
 void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be32, void* y_mont, int* bad, const void* w29, const Fr8& n_inv,
                   hipStream_t st);
+// cells 64..127 of n blobs, inside the CU (k_blob_to_extension): cells = [n][128][2048] bytes, 16-byte aligned, the first half of every
+// slice holding its blob; the second half is written (zeros for a blob with an element >= r, whose status[b] gets bit 0 set; status[n]
+// is not written otherwise).  Writes nothing else and needs no workspace.
+void blob_to_extension(int n, uint8_t* cells, int* status, const void* w29, const Fr8& n_inv, hipStream_t st);
 // The column layout of a block's data columns (eth_kzg_amd_compute_data_columns / _recover_data_columns): a launch over n blobs that are
 // blobs [b0, b0 + n) of a call of n_total writes cell c of its blob b to cells + ((size_t)c * n_total + b0 + b) * 2048 and proof c to
 // proofs + ((size_t)c * n_total + b0 + b) * 48, the output pointers being the WHOLE call's arrays.  Null: the blob-major layout

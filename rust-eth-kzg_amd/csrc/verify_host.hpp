@@ -2,7 +2,7 @@
 // codecs and the Fiat-Shamir transcripts (the reference's four, the leaf-hashed challenge of the cell verifier and the leaves, seed and
 // weights of the point many-verification), each stated ONCE for verify.hip, verify_many.hip, point_many.hip, eip4844.hip and recover.hip.
 // No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp, test_many_leaf.cpp,
-// test_point_many.cpp, test_blob_many.cpp and test_data_columns.cpp run it on the CPU against hashlib.
+// test_point_many.cpp, test_blob_many.cpp, test_data_columns.cpp and test_blob_cells.cpp run it on the CPU against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -421,5 +421,37 @@ inline int blob_item_status(bool blob_bad, int commitment_status, int proof_stat
 inline bool blob_item_live(int status) { return status == 0; }
 // what the call hands out for an item: its status, and the pass's verdict on it only if it is live
 inline bool blob_item_verified(int status, bool pair_passed) { return blob_item_live(status) && pair_passed; }
+
+// ---- eth_kzg_amd_verify_blob_cell_proofs_many / _many_device (verify_many.hip, the blob source of the cell many-verification): MANY items
+// (blob, commitment, 128 cell proofs), a verdict for each.  Item i is the problem (128 x commitment_i, indices 0..127,
+// compute_cells(blob_i), proofs_i) of the many-verification under the leaf-hashed challenge of that problem alone (CellLeafTranscript,
+// cell_leaf_root): there is NO new transcript, and the leaves bind the computed cells, the caller's commitment bytes and the caller's
+// proofs.  Cells 0..63 are the blob's bytes, cells 64..127 come from k_ntt.hip: k_blob_to_extension (zero bytes if the blob is refused).
+// Lengths and indices hold by construction: no item is refused at validation (there is no status 3), every problem has N_CELLS cells
+// and ONE unique commitment with every row 0.  What the call refuses as a whole, before the context is touched:
+constexpr uint64_t BLOB_CELLS_MAX_ITEMS = 1u << 24;
+inline int validate_blob_cells_call(uint64_t n, bool blobs_null, bool commitments_null, bool proofs_null, bool verified_null) {
+    if (n > BLOB_CELLS_MAX_ITEMS) return INPUT_INVALID;
+    if (n != 0 && (blobs_null || commitments_null || proofs_null || verified_null)) return INPUT_INVALID;
+    return INPUT_VALID;
+}
+// The status of an item, in the order of checks of the reference's two calls (compute_cells opens the blob; verify_cell_kzg_proof_batch
+// then decodes the commitment and the proofs; the cells it is handed are compute_cells' own and cannot be out of range): 1 if the blob
+// holds an element >= r -- also when a point is bad as well --, else 2 if the commitment or one of the 128 proofs is not a canonical
+// point of the subgroup, else 0.  Only items of status 0 are live.  (The other sources of the pass decide points first: their cells are
+// the caller's.)
+inline int blob_cells_item_status(bool blob_bad, bool point_bad) {
+    if (blob_bad) return 1;
+    if (point_bad) return 2;
+    return 0;
+}
+// Where item i of a pass lies in the pass's cells (arena and pinned slab alike, from the first cell's byte on): the layout is the
+// other sources' -- cell k of item i is cell 128 i + k -- so the blob's bytes are the first half of the item's slice and the second
+// half is the kernel's to fill.  Only the blob halves are staged and uploaded.
+struct BlobCellsSlice { size_t blob_at, ext_at; };
+inline BlobCellsSlice blob_cells_slice(size_t i) { return {i * 2 * (size_t)BYTES_PER_BLOB, (i * 2 + 1) * (size_t)BYTES_PER_BLOB}; }
+static_assert(2 * BYTES_PER_BLOB == N_CELLS * BYTES_PER_CELL, "a blob is half of its 128 cells");
+// the items of a call as the pass's plans see them: N_CELLS cells each (vm_call_parts, vm_chunk_end: at most chunk_cells / 128 per pass)
+inline uint64_t blob_cells_of(uint64_t) { return (uint64_t)N_CELLS; }
 
 }  // namespace kzg

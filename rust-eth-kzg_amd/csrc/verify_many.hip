@@ -3,16 +3,18 @@
 // FK20Verifier::verify_multi_opening (crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:129-260); the reference gets
 // its throughput by verifying from many threads on one context (bindings/node/src/lib.rs:92-299,
 // crates/cryptography/bls12_381/src/lib.rs:45-50).  Here the problems of a call share every GPU launch.
-// THREE SOURCES (engine.hpp: VerifyManyInput says what each holds), resolved once per part into a CellSource: pointer lists on the
+// FOUR SOURCES (engine.hpp: VerifyManyInput says what each holds), resolved once per part into a CellSource: pointer lists on the
 // host; flat arrays in HBM plus cell_starts; the columns of one block over ONE commitment list, on the host or in HBM (problem b is
-// column b; verify_data_columns_many does the source's once-per-call work).  Two challenges: the reference's transcript per problem,
+// column b; verify_data_columns_many does the source's once-per-call work); blobs with their commitment and 128 cell proofs, on the host
+// or in HBM (problem b is blob b's 128 cells, which the pass computes itself in its arena: the step `extend`).  Two challenges: the reference's transcript per problem,
 // or the leaf-hashed challenge of each problem alone (verify_host.hpp: CellLeafTranscript).  A large CALL is cut into at most three
 // concurrent PARTS, a part into CHUNKS of at most VM_CHUNK_CELLS cells, and every chunk is one PASS (Engine::CellManyPass) on one of three
 // pass slots (lease_pass_slot); the plans are verify_host.hpp's.  Nothing here takes the context's big lock.  The steps of a pass:
 //   arena      the slot's blocks, large enough; the result slots of the slab poisoned
 //   stage      host threads: the problems into the pinned slab (host sources: proofs and cells; all: commitments, indices, rows)
 //   upload     ONE copy up; device sources: the host-made arrays up, proofs and cells device-to-device in copy runs (and down
-//              again, compacted, for the reference's transcript)
+//              again, compacted, for the reference's transcript); the blob source: only the blob halves of the cells
+//   extend     (the blob source) cells 64..127 of every blob into the second half of its slice, in place (k_ntt.hip: k_blob_to_extension)
 //   leaves     (leaf-hashed) the leaves of ALL the pass's cells in one launch of k_sha256_cell_leaves out of the arena, n x 32 bytes down
 //   decode     decode + subgroup-check all points, decode all cells, per-cell interpolation: challenge-free, behind the hashes
 //   challenges host threads: one SHA-256 transcript, or one ROOT over the leaf digests, per problem (on the host on purpose: a lane per problem
@@ -43,6 +45,7 @@ struct CellSource {
     const int B;
     const bool device = in.on_device();  // proofs and cells lie in HBM (the host has neither)
     const bool shared = in.columns;      // the commitments are the pass's: one list, every problem's (the column source)
+    const bool blobs = in.from_blobs;    // a problem is a blob: its cells are computed in the arena, its indices are 0..127, one commitment
     std::vector<uint64_t> src0;          // (device) the problem's first entry in the caller's d_cells / d_proofs
     std::vector<uint64_t> mir0;          // (flat arrays) its first entry in the pinned mirror of commitments and indices: back to back
     uint64_t mirror_n = 0;               // entries of the mirror
@@ -50,17 +53,22 @@ struct CellSource {
     const uint64_t* mirror_i = nullptr;
     CellSource(const VerifyManyInput& in_, int B_) : in(in_), B(B_) {
         for (int b = 0; b < B && device; b++) {
-            src0.push_back(shared ? place(b) * in.col_blobs : in.cell_starts[b]);
+            src0.push_back(blobs ? (uint64_t)b * N_CELLS : shared ? place(b) * in.col_blobs : in.cell_starts[b]);
             mir0.push_back(mirror_n);
-            if (!shared && in_mirror(b)) mirror_n += cells_of(b);
+            if (!shared && !blobs && in_mirror(b)) mirror_n += cells_of(b);
         }
     }
     uint64_t cells_of(int b) const { return in.cells_of((uint64_t)b); }
     // a problem beyond the size bound is refused by its validation (status 3) and has no place in the mirror: nothing of it is read
     bool in_mirror(int b) const { return cells_of(b) <= MAX_CELLS_PER_VERIFICATION; }
     uint64_t place(int b) const { return shared ? in.col_place[b] : (uint64_t)b; }  // where the caller's arrays hold problem b
-    uint64_t index_of(int b, int k) const { return shared ? in.col_indices[place(b)] : device ? mirror_i[mir0[b] + k] : in.cell_indices[b][k]; }
+    uint64_t index_of(int b, int k) const {
+        return blobs ? (uint64_t)k : shared ? in.col_indices[place(b)] : device ? mirror_i[mir0[b] + k] : in.cell_indices[b][k];
+    }
     const uint8_t* cell(int b, int k) const { return in.cells[place(b)][k]; }  // (host sources)
+    const uint8_t* blob(int b) const { return in.blobs[b]; }                   // (the blob source on the host)
+    // (the blob source) the problem's one commitment: the caller's bytes, or what commitments_down brought
+    const uint8_t* blob_commitment(int b) const { return device ? mirror_c + (size_t)b * 48 : in.blob_commitments[b]; }
     const uint8_t* proof(int b, int k) const { return in.proofs[place(b)][k]; }
     int pass_m() const { return shared ? (int)in.col->uniq.size() : 0; }  // the pass-wide commitments
     const uint8_t* const* pass_uniq() const { return shared ? in.col->uniq.data() : nullptr; }
@@ -69,6 +77,13 @@ struct CellSource {
     // of problem b -> its status; p is filled only if the problem goes on
     int admit(int b, Problem& p) const {
         const uint64_t nb = cells_of(b);
+        if (blobs) {  // lengths and indices hold by construction (verify_host.hpp): nothing to validate, one commitment, every row 0
+            static const int row0[N_CELLS] = {};
+            p.own_uniq.assign(1, blob_commitment(b));
+            p.uniq = p.own_uniq.data(); p.row = row0;
+            p.m = 1; p.n = N_CELLS;
+            return OK;
+        }
         const int st = shared   ? validate_data_column(nb, in.col_indices[place(b)])
                        : device ? validate_cell_batch(nb, nb, nb, nb, mirror_i + mir0[b])
                                 : validate_cell_batch(in.n_commitments[b], in.n_indices[b], nb, in.n_proofs[b], in.cell_indices[b]);
@@ -98,6 +113,13 @@ void mirror_down(CellSource& S, uint8_t*& pin, size_t& cap, hipStream_t st) {
     }
     SYNC_CHECKED(st);
     S.mirror_c = pin; S.mirror_i = pin_i;
+}
+// the blob source in HBM: the part's B x 48 commitment bytes come down for the passes' commitment rows (nothing else of the source does)
+void commitments_down(CellSource& S, uint8_t*& pin, size_t& cap, hipStream_t st) {
+    grow_pinned(pin, cap, (size_t)S.B * 48);
+    HIPCK(hipMemcpyAsync(pin, S.in.d_commitments, (size_t)S.B * 48, hipMemcpyDeviceToHost, st));
+    SYNC_CHECKED(st);
+    S.mirror_c = pin;
 }
 
 // Where a pass's arrays lie: n cells and m unique commitments of Bc problems.  Device arena: [inputs, uploaded in one copy |
@@ -179,6 +201,7 @@ struct Engine::CellManyPass {
         arena();
         stage();
         upload();
+        extend();
         leaves();
         decode();
         challenges();
@@ -211,10 +234,11 @@ struct Engine::CellManyPass {
             const Problem& p = pr[i];
             const int c0 = cell_start[i], r0 = row_start[i];
             for (int j = 0; j < S.own_rows(p); j++) { memcpy(hb + L.off_c + (size_t)(r0 + j) * 48, p.uniq[j], 48); h_rowb[r0 + j] = i; }
+            if (gather && S.blobs) memcpy(hb + L.off_cells + blob_cells_slice((size_t)i).blob_at, S.blob(b0 + i), BYTES_PER_BLOB);  // cells 0..63
             for (int k = 0; k < p.n; k++) {
                 if (gather) {
                     memcpy(hb + L.off_p + (size_t)(c0 + k) * 48, S.proof(b0 + i, k), 48);
-                    memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, S.cell(b0 + i, k), BYTES_PER_CELL);
+                    if (!S.blobs) memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, S.cell(b0 + i, k), BYTES_PER_CELL);
                 }
                 h_idx[c0 + k] = (int)S.index_of(b0 + i, k);
                 h_row[c0 + k] = r0 + p.row[k];
@@ -230,6 +254,13 @@ struct Engine::CellManyPass {
         HIPCK(hipMemsetAsync(db + L.off_out, 0xff, (size_t)2 * Bc * launch::SIZEOF_JACQ, st));
         HIPCK(hipMemsetAsync(db + L.off_fold, 0xff, (size_t)2 * launch::SIZEOF_JACQ, st));
         HIPCK(hipMemsetAsync(db + L.off_ste, 0, (size_t)Bc * 4, st));
+        constexpr size_t slice = 2 * (size_t)BYTES_PER_BLOB;  // (the blob source) a blob's 128 cells; its first half is the blob
+        if (!S.device && S.blobs) {  // the empty halves stay where they are: [proofs, commitments], the blob halves (one strided copy), the rest
+            HIPCK(hipMemcpyAsync(db, hb, L.off_cells, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpy2DAsync(db + L.off_cells, slice, hb + L.off_cells, slice, BYTES_PER_BLOB, (size_t)Bc, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpyAsync(db + L.off_idx, hb + L.off_idx, L.in_bytes - L.off_idx, hipMemcpyHostToDevice, st));
+            return;
+        }
         if (!S.device) {
             HIPCK(hipMemcpyAsync(db, hb, L.in_bytes, hipMemcpyHostToDevice, st));
             return;
@@ -240,6 +271,11 @@ struct Engine::CellManyPass {
         HIPCK(hipMemcpyAsync(db + L.off_idx, hb + L.off_idx, L.in_bytes - L.off_idx, hipMemcpyHostToDevice, st));
         for (const CopyRun& r : vm_copy_runs(Bc, [&](int i) { return S.src0[b0 + i]; }, [&](int i) { return pr[i].n; }, [&](int i) { return pr[i].n != 0; })) {
             HIPCK(hipMemcpyAsync(db + L.off_p + (size_t)r.dst * 48, S.in.d_proofs + (size_t)r.src * 48, (size_t)r.len * 48, hipMemcpyDeviceToDevice, st));
+            if (S.blobs) {  // the run's blobs (128 entries each) into the first halves of their slices: one strided copy
+                HIPCK(hipMemcpy2DAsync(db + L.off_cells + (size_t)r.dst * BYTES_PER_CELL, slice, S.in.d_blobs + (size_t)(r.src / N_CELLS) * BYTES_PER_BLOB,
+                                       BYTES_PER_BLOB, BYTES_PER_BLOB, (size_t)(r.len / N_CELLS), hipMemcpyDeviceToDevice, st));
+                continue;
+            }
             HIPCK(hipMemcpyAsync(db + L.off_cells + (size_t)r.dst * BYTES_PER_CELL, S.in.d_cells + (size_t)r.src * BYTES_PER_CELL,
                                  (size_t)r.len * BYTES_PER_CELL, hipMemcpyDeviceToDevice, st));
         }
@@ -247,6 +283,11 @@ struct Engine::CellManyPass {
             HIPCK(hipMemcpyAsync(hb + L.off_p, db + L.off_p, (size_t)n * 48, hipMemcpyDeviceToHost, st));
             HIPCK(hipMemcpyAsync(hb + L.off_cells, db + L.off_cells, (size_t)n * BYTES_PER_CELL, hipMemcpyDeviceToHost, st));
         }
+    }
+    // ---- (the blob source) every blob's cells 64..127 behind its bytes; a refused blob sets its problem's cell-status word (which upload
+    // has zeroed on this stream) and gets zeros, so that the leaves and the decoding read nothing stale
+    void extend() {
+        if (S.blobs) launch::blob_to_extension(Bc, db + L.off_cells, (int*)(db + L.off_ste), e.d_w29_, e.n_inv4096_, st);
     }
     // ---- (leaf-hashed) the leaves of all the pass's cells straight out of the arena (its offsets are multiples of 256: the kernel's
     // 16-byte loads), in order on the pass's stream (a fifth stream: lease_pass_slot).  The event: what the host threads hash is down.
@@ -315,7 +356,8 @@ struct Engine::CellManyPass {
             for (int j = 0; j < 24; j++) { tab[j] = cur; cur = sqr(cur); }
         });
     }
-    // decoding verdicts per problem (order of the reference: commitments, proofs, cells) -> live problems; the others take no further part
+    // decoding verdicts per problem (order of the reference: commitments, proofs, cells; the blob source: the blob first, verify_host.hpp:
+    // blob_cells_item_status) -> live problems; the others take no further part
     int judge() {
         const int* h_st = h_status();
         live.assign(Bc, 0);
@@ -330,6 +372,7 @@ struct Engine::CellManyPass {
             for (int j = 0; j < S.own_rows(p) && !bad; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
             for (int k = 0; k < p.n && !bad; k++) if (h_st[c0 + k]) bad = ERR_G1;
             if (!bad && h_st[L.n + L.m + i]) bad = ERR_SCALAR;
+            if (S.blobs) bad = blob_cells_item_status(h_st[L.n + L.m + i] != 0, bad == ERR_G1);
             stat[i] = bad;
             if (!bad) { live[i] = 1; alive++; }
         }
@@ -522,7 +565,10 @@ int Engine::verify_cell_kzg_proof_batch_many_part(int B, const VerifyManyInput& 
         TraceLap lap{knobs_.trace, "verify_many"};
         CellSource S(in, B);
         if (S.device) order_behind(ps.stream, in.user_stream, ps.slot->ordered);
-        if (S.device && !S.shared) {  // (columns: the commitments came down with the call, the indices are the host's: nothing to mirror)
+        if (S.device && S.blobs) {
+            commitments_down(S, ps.slot->src_pin, ps.slot->src_pin_cap, ps.stream);
+            lap("commitments down");
+        } else if (S.device && !S.shared) {  // (columns: the commitments came down with the call, the indices are the host's: nothing to mirror)
             mirror_down(S, ps.slot->src_pin, ps.slot->src_pin_cap, ps.stream);
             lap("commitments + indices down");
         }
