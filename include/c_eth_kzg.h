@@ -605,6 +605,64 @@ CResult eth_kzg_amd_recover_data_columns_device(const DASContext *ctx, uint64_t 
                                                 const uint64_t *column_indices, const uint8_t *d_cells, uint8_t *d_out_cells,
                                                 uint8_t *d_out_proofs, int32_t *status, void *hip_stream);
 
+/* ---- a block's data columns recovered AND checked against the block's commitments ----
+ * eth_kzg_amd_recover_data_columns / _device cannot tell a right input from a wrong one when exactly 64 columns are given: the decoder's
+ * only consistency test is that the recovered polynomial has no coefficient at 4096 or above (status 4), and ANY 64 columns of
+ * canonical bytes decode to some polynomial of degree below 4096 -- status 0, with 128 cells and 128 proofs that are valid for a
+ * polynomial nobody committed to.  What identifies the right polynomial is the block's commitment, and the recovered coefficients are in
+ * HBM when the decode ends: the checked forms commit to them (one fixed-base MSM per blob, the stages of
+ * eth_kzg_amd_blob_to_kzg_commitment_device) and compare.
+ *   commitments[i] / d_commitments n_blobs*48          the commitment blob i is expected to have; NULL: nothing is compared
+ *   out_blobs[i] / d_out_blobs [n_blobs][131072]       the recovered blob, blob-major: its cells 0..63 concatenated
+ *   out_commitments[i] / d_out_commitments n_blobs*48  the commitment of the recovered polynomial
+ *   column_indices, cells, out_cells, out_proofs, status, hip_stream: as eth_kzg_amd_recover_data_columns / _device
+ * Status of blob i, in this order: 3 a bad index list -- it marks EVERY blob, before anything is launched and before commitments is
+ * read (device form: before any pointer is resolved); else 1 a non-canonical element in the blob's cells; else 4 the cells lie on no
+ * polynomial of degree below 4096; else 6 the recovered polynomial's commitment differs from commitments[i]; else 0.  The statuses 0, 1,
+ * 3 and 4 are exactly what eth_kzg_amd_recover_data_columns gives on the same cells, whatever the commitments are.  6 is a value no
+ * other call returns (5 is taken inside the library).
+ * The comparison is on BYTES: the computed commitment in its canonical 48-byte compressed encoding against the caller's 48 bytes as
+ * they stand.  The caller's commitment is never decoded, so a malformed or non-canonical one -- flag bits wrong, x not below p, a point
+ * off the curve or outside the subgroup -- can never match: it gives 6, NOT 2.  The identity (0xc0 00 ... 00) matches the all-zero blob
+ * and nothing else.  With commitments == NULL status 6 cannot occur.
+ * Outputs.  Blob with status 0: out_cells / out_proofs hold the bytes of eth_kzg_amd_recover_data_columns, out_commitments[i] the bytes
+ * eth_kzg_amd_blob_to_kzg_commitment_batch gives for the recovered blob, out_blobs[i] that blob's own 131072 bytes.  Any other status:
+ * the blob's slots are untouched (host form) or unspecified (device form); no other blob's bytes are disturbed.  Each of the four
+ * outputs may be NULL and is then not computed.  With all four NULL the call is a pure check: the decode, the commitments and the
+ * comparison, no cell kernel and no FK20 stage.  With commitments and out_commitments NULL as well it is the decode and the statuses of
+ * eth_kzg_amd_recover_data_columns and nothing more.
+ * What status 0 says when commitments are given.  The decoder's test passed: the quotient Q it recovered has degree below 4096, so Q Z
+ * (Z the vanishing polynomial of the missing cells, degree at most 4096) has degree below 8192 and agrees with the interpolant of E Z on
+ * the 8192 points of the coset; hence Q Z = E Z on the domain itself, and every GIVEN cell is Q's evaluation.  commit(Q) == C_i then
+ * identifies Q as the committed polynomial under the binding of KZG.  So status 0 says of every given cell what a valid cell proof
+ * says of it -- at least 64 columns of a block checked against the commitments WITHOUT any proofs.  What the call cannot do is name the
+ * wrong column: a blob with 4 or 6 goes through eth_kzg_amd_verify_data_columns, with proofs, for that.
+ * Err("InvalidInput...") for the call, before the context is touched: exactly what eth_kzg_amd_recover_data_columns refuses -- n_blobs >
+ * 2^24, or NULL cells, column_indices (with n_columns > 0) or status with n_blobs > 0.  n_blobs = 0 is Ok.
+ * Device form: every device pointer given is resolved, d_commitments, d_out_blobs and d_out_commitments included; anything but device
+ * memory of one listed device is Err("InvalidInput...").  The byte arrays may start at any byte address; the caller's commitments are
+ * read where they lie.  Streams as eth_kzg_amd_recover_data_columns_device: the decode, the commitments and the comparison run on the
+ * library's stream behind what hip_stream has queued -- the work that wrote d_commitments included -- and have completed when the call
+ * returns, d_out_commitments with them; the kernels that write d_out_blobs, d_out_cells and d_out_proofs go onto hip_stream.
+ * Device lists: the host form is cut into contiguous slices by BLOB (commitments, out_blobs and out_commitments indexed like every other
+ * array of the call); the device form runs on the owner of the buffers.
+ * How: the last pass of the decoder stores the coefficients a second time as canonical integers; the MSM, its fold, the compression
+ * and the comparison are enqueued in front of the decode's one synchronisation, so a sub-batch costs one synchronisation as before and
+ * the status words come down once.  A blob whose decode failed runs through the commitment stages all the same and its result is
+ * ignored.  out_blobs is the cells' transform launched for cells 0..63 alone, written blob-major.
+ * Out of scope: the blob-major recovery calls (their erasure patterns differ per blob); locating the wrong column; decoding or
+ * subgroup-testing the caller's commitments; passing present columns through; returning only the missing columns; sharding a device
+ * form over GPUs; the Node binding.  When to take the call, and what was measured: INTEGRATION.md, DESIGN.md section 5. */
+CResult eth_kzg_amd_recover_data_columns_checked(const DASContext *ctx, uint64_t n_blobs, const uint8_t *const *commitments,
+                                                 uint64_t n_columns, const uint64_t *column_indices,
+                                                 const uint8_t *const *const *cells, uint8_t *const *out_blobs,
+                                                 uint8_t *const *out_commitments, uint8_t *const *const *out_cells,
+                                                 uint8_t *const *const *out_proofs, int32_t *status);
+CResult eth_kzg_amd_recover_data_columns_checked_device(const DASContext *ctx, uint64_t n_blobs, const uint8_t *d_commitments,
+                                                        uint64_t n_columns, const uint64_t *column_indices, const uint8_t *d_cells,
+                                                        uint8_t *d_out_blobs, uint8_t *d_out_commitments, uint8_t *d_out_cells,
+                                                        uint8_t *d_out_proofs, int32_t *status, void *hip_stream);
+
 /* Introspection used by bench.py / DESIGN.md: bytes of both window tables resident in HBM; nominal window width w of the FK20
  * table in use (a GLV table: ceil(128 / w) windows over the two 128-bit halves of each scalar, packed 96-byte entries: 16
  * gathered additions per base at w = 16, 32 at w = 8 -- the start tables, and all there is with use_precomp = false). */

@@ -75,6 +75,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_blob_cell_proofs_many", "eth_kzg_amd_verify_blob_cell_proofs_many_device",
     "eth_kzg_amd_compute_data_columns", "eth_kzg_amd_compute_data_columns_device",
     "eth_kzg_amd_recover_data_columns", "eth_kzg_amd_recover_data_columns_device",
+    "eth_kzg_amd_recover_data_columns_checked", "eth_kzg_amd_recover_data_columns_checked_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
     "eth_kzg_amd_set_profiling", "eth_kzg_amd_get_stage_times",
     "eth_kzg_amd_comm_probe", "eth_kzg_amd_comm_unique_id", "eth_kzg_amd_comm_init", "eth_kzg_amd_comm_info",
@@ -207,6 +208,8 @@ def load_library():
         "eth_kzg_amd_compute_data_columns_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_recover_data_columns": [P, U64, U64, P, P, P, P, P],
         "eth_kzg_amd_recover_data_columns_device": [P, U64, U64, P, P, P, P, P, P],
+        "eth_kzg_amd_recover_data_columns_checked": [P, U64, P, U64, P, P, P, P, P, P, P],
+        "eth_kzg_amd_recover_data_columns_checked_device": [P, U64, P, U64, P, P, P, P, P, P, P, P],
     }.items():
         if hasattr(lib, name):  # (as above: a build from before these symbols still loads)
             getattr(lib, name).restype = CResult
@@ -744,6 +747,54 @@ class DASContext:
         self._check(self._lib.eth_kzg_amd_recover_data_columns_device(
             self._ctx, n_blobs, nc, _vp(idx), C.c_void_p(d_cells) if d_cells else None, C.c_void_p(d_out_cells) if d_out_cells else None,
             C.c_void_p(d_out_proofs) if d_out_proofs else None, st, C.c_void_p(stream) if stream else None))
+        return list(st)[:n_blobs]
+
+    def recover_data_columns_checked(self, column_indices, cells, commitments=None, want_blobs=True, want_commitments=True, want_cells=True,
+                                     want_proofs=True, prefill=0):
+        """The recovery checked against the block's commitments (eth_kzg_amd_recover_data_columns_checked): column_indices[j], cells[j][i]
+        and commitments[i] (None: nothing is compared) -> (status list per blob, blobs[i], commitments[i], cells[c][i], proofs[c][i]); an
+        output that was not asked for is None.  Status 6: the recovered polynomial's commitment differs from commitments[i], compared
+        on bytes.  The slots of a blob whose status is not 0 come back as they were: `prefill` bytes."""
+        nc = len(column_indices)
+        nb = len(cells[0]) if nc else 0
+        if len(cells) != nc or any(len(col) != nb for col in cells) or any(len(c) != BYTES_PER_CELL for col in cells for c in col):
+            raise KzgError("InvalidLength")
+        if commitments is not None and (len(commitments) != nb or any(len(c) != 48 for c in commitments)):
+            raise KzgError("InvalidLength")  # (fixed-size buffers carry no length across the C ABI)
+        idx = np.array(column_indices, dtype=np.uint64) if nc else np.zeros(1, np.uint64)
+        keep, tab = [], np.zeros(max(1, nc), dtype=np.uint64)
+        for j in range(nc):
+            cla, k = _flat_ptrs(cells[j], BYTES_PER_CELL)
+            keep += [cla, k]
+            tab[j] = cla.ctypes.data
+        ca, _kc = _flat_ptrs(commitments, 48) if commitments is not None else (None, None)
+        out_blobs, bi, _bo = _out_ptrs(1, nb, BYTES_PER_BLOB)
+        out_comm, ki, _ko = _out_ptrs(1, nb, 48)
+        out_cells, _ci, ocp = _out_ptrs(CELLS_PER_EXT_BLOB, nb, BYTES_PER_CELL)
+        out_proofs, _pi, opp = _out_ptrs(CELLS_PER_EXT_BLOB, nb, 48)
+        for out in (out_blobs, out_comm, out_cells, out_proofs):
+            out.fill(prefill)
+        st = (C.c_int32 * max(1, nb))()
+        self._check(self._lib.eth_kzg_amd_recover_data_columns_checked(
+            self._ctx, nb, _vp(ca) if ca is not None else None, nc, _vp(idx), _vp(tab), _vp(bi) if want_blobs else None,
+            _vp(ki) if want_commitments else None, _vp(ocp) if want_cells else None, _vp(opp) if want_proofs else None, st))
+        return (list(st)[:nb], _split(out_blobs, 1, nb, BYTES_PER_BLOB)[0] if want_blobs else None,
+                _split(out_comm, 1, nb, 48)[0] if want_commitments else None,
+                _split(out_cells, CELLS_PER_EXT_BLOB, nb, BYTES_PER_CELL) if want_cells else None,
+                _split(out_proofs, CELLS_PER_EXT_BLOB, nb, 48) if want_proofs else None)
+
+    def recover_data_columns_checked_device(self, n_blobs, column_indices, d_cells, d_commitments=None, d_out_blobs=None, d_out_commitments=None,
+                                            d_out_cells=None, d_out_proofs=None, stream=None):
+        """The same on device memory (eth_kzg_amd_recover_data_columns_checked_device; integer device addresses, each of the five behind
+        d_cells may be 0 / None): d_cells [len(column_indices)][n_blobs][2048], d_commitments and d_out_commitments n_blobs*48,
+        d_out_blobs [n_blobs][131072], d_out_cells [128][n_blobs][2048], d_out_proofs [128][n_blobs][48].  -> the per-blob status list."""
+        nc = len(column_indices)
+        idx = np.ascontiguousarray(np.array(column_indices, dtype=np.uint64)) if nc else np.zeros(1, np.uint64)
+        st = (C.c_int32 * max(1, n_blobs))()
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        self._check(self._lib.eth_kzg_amd_recover_data_columns_checked_device(
+            self._ctx, n_blobs, vp(d_commitments), nc, _vp(idx), vp(d_cells), vp(d_out_blobs), vp(d_out_commitments), vp(d_out_cells),
+            vp(d_out_proofs), st, vp(stream)))
         return list(st)[:n_blobs]
 
     def verify_cell_kzg_proof_batch_partial(self, commitments, cell_indices, cells, proofs, shard_begin, shard_end):

@@ -709,6 +709,54 @@ CResult eth_kzg_amd_recover_data_columns_device(const DASContext* ctx, uint64_t 
         return device_err(e);
     return ok();
 }
+// The same recovery checked against the block's commitments.  The refusals of the call are those of the two above; the host form's
+// slices index commitments, out_blobs and out_commitments with their offset like every other array of the call.  The device form
+// settles a bad index list BEFORE it resolves a pointer: every blob is 3 and nothing -- d_commitments included -- is looked at.
+CResult eth_kzg_amd_recover_data_columns_checked(const DASContext* ctx, uint64_t n_blobs, const uint8_t* const* commitments, uint64_t n_columns,
+                                                 const uint64_t* column_indices, const uint8_t* const* const* cells, uint8_t* const* out_blobs,
+                                                 uint8_t* const* out_commitments, uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs,
+                                                 int32_t* status) {
+    if (n_blobs > MAX_BATCH || (n_blobs && (!cells || !status || (n_columns && !column_indices)))) return err("InvalidInput");
+    if (n_blobs == 0) return ok();
+    kzg::Engine::RecoverCheck chk;
+    chk.commitments = commitments;
+    chk.out_blobs = out_blobs;
+    chk.out_commitments = out_commitments;
+    return sliced_call(ctx, n_blobs, MAX_BATCH, nullptr, status, [] { return true; }, [&](kzg::Engine* dev, uint64_t lo, uint64_t hi, int* st, int*) {
+        auto lane = dev->lease_serial();
+        kzg::Engine* e = lane.e;
+        return batch_failure(e, e->recover_data_columns_checked_host((int)lo, (int)(hi - lo), n_columns, column_indices, cells, chk, out_cells, out_proofs, st));
+    });
+}
+CResult eth_kzg_amd_recover_data_columns_checked_device(const DASContext* ctx, uint64_t n_blobs, const uint8_t* d_commitments, uint64_t n_columns,
+                                                        const uint64_t* column_indices, const uint8_t* d_cells, uint8_t* d_out_blobs,
+                                                        uint8_t* d_out_commitments, uint8_t* d_out_cells, uint8_t* d_out_proofs, int32_t* status,
+                                                        void* hip_stream) {
+    if (n_blobs > MAX_BATCH) return err("InvalidInput");
+    if (n_blobs && (!d_cells || !status || (n_columns && !column_indices))) return err("InvalidInput");
+    if (n_blobs == 0) return ok();
+    live(ctx);
+    if (kzg::column_list_status(n_columns, column_indices) != kzg::INPUT_VALID) {
+        for (uint64_t i = 0; i < n_blobs; i++) status[i] = kzg::ERR_INPUT;
+        return ok();
+    }
+    const void* ptrs[6] = {d_cells};
+    int n_ptrs = 1;
+    for (const void* p : {(const void*)d_commitments, (const void*)d_out_blobs, (const void*)d_out_commitments, (const void*)d_out_cells, (const void*)d_out_proofs})
+        if (p) ptrs[n_ptrs++] = p;
+    kzg::Engine* owner = engine_of_device_pointers(ctx, ptrs, n_ptrs);
+    if (!owner) return err("InvalidInput: the buffers are not device memory of one device of this context");
+    auto lane = owner->lease_serial();
+    kzg::Engine* e = lane.e;
+    kzg::Engine::RecoverCheck chk;
+    chk.d_commitments = d_commitments;
+    chk.d_out_blobs = d_out_blobs;
+    chk.d_out_commitments = d_out_commitments;
+    if (e->recover_data_columns_checked_device((int)n_blobs, n_columns, column_indices, d_cells, chk, d_out_cells, d_out_proofs, (int*)status,
+                                               (hipStream_t)hip_stream))
+        return device_err(e);
+    return ok();
+}
 // ---------------------------------------------------------------------------------------------
 // EIP-4844 proofs for many blobs (eip4844.hip).  Host-pointer forms: contiguous slices over the device list; device-resident forms:
 // the engine that owns d_blobs; the device verifier is ONE random combination over the whole batch and is never cut.

@@ -1,6 +1,7 @@
 // A block's data columns in column layout: the proposer's call (commitments, cells and proofs of every blob, cells and proofs laid
 // out [column][blob] as the 128 sidecars carry them) and the supernode's call (all 128 columns from at least 64 of them).
-// c_eth_kzg.h: eth_kzg_amd_compute_data_columns / _device, eth_kzg_amd_recover_data_columns / _device.
+// c_eth_kzg.h: eth_kzg_amd_compute_data_columns / _device, eth_kzg_amd_recover_data_columns / _device, and the recovery checked against
+// the block's commitments, eth_kzg_amd_recover_data_columns_checked / _device.
 //
 // Neither call computes anything new: the prover's stages are enqueue_compute's and the decoder is rs_decode.  What is new is WHERE the
 // kernels that write the outputs put them -- k_coeffs_to_cells / _scalars and k_g1_compress store every byte once, so the layout is
@@ -106,16 +107,12 @@ int Engine::compute_data_columns_host(int lo, int n, const uint8_t* const* blobs
 }
 
 // ---- the supernode's call ------------------------------------------------------------------------------------------------------
-// The status of an index list: validate_recovery of the per-blob list every blob of the call expands into (the count first: a list of
-// more than 128 entries is refused unread).
-static int column_list_status(uint64_t n_columns, const uint64_t* column_indices) {
-    if (n_columns < (uint64_t)N_CELLS / 2 || n_columns > (uint64_t)N_CELLS || !column_indices) return ERR_INPUT;
-    return validate_recovery(n_columns, n_columns, column_indices) == INPUT_VALID ? OK : ERR_INPUT;
-}
+// (the status of an index list: verify_host.hpp, column_list_status -- c_api.cpp asks it too, before it resolves a pointer)
 // The decoder's index arrays for the column source: list entry (column rank j, blob i) lands in slot i * 128 + column_indices[j] of
 // the evaluations, counts towards blob i's status and is read at cell j * n_total + i of d_cells_r0 = the call's cells + r0 cells
 // (k_cells_to_fr's src_of).  ONE presence mask: every blob misses the same columns.  j * n_total + i < 127 * 2^24 + 2^24 <= 2^31 - 1.
-int Engine::rs_decode_columns(int nr, size_t n_total, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells_r0, int* st_out) {
+int Engine::rs_decode_columns(int nr, size_t n_total, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells_r0, int* st_out,
+                              const RsCommit* commit) {
     std::vector<uint32_t> present(4, 0);
     for (uint64_t j = 0; j < n_columns; j++) {
         const int i = brp7((int)column_indices[j]);  // domain-order index of a cell = its bit-reversed index (cosets.rs:186-195)
@@ -131,11 +128,24 @@ int Engine::rs_decode_columns(int nr, size_t n_total, uint64_t n_columns, const 
             stof.push_back(i);
             src.push_back((int)(j * n_total + (size_t)i));
         }
-    return rs_decode(nr, d_cells_r0, false, slot, stof, present, st_out, nullptr, &src, /*shared_pattern=*/true);
+    return rs_decode(nr, d_cells_r0, false, slot, stof, present, st_out, nullptr, &src, /*shared_pattern=*/true, commit);
 }
 
 int Engine::recover_data_columns_device(int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells, uint8_t* d_out_cells,
                                         uint8_t* d_out_proofs, int* status, hipStream_t user_stream) {
+    return recover_data_columns_checked_device(R, n_columns, column_indices, d_cells, RecoverCheck{}, d_out_cells, d_out_proofs, status, user_stream);
+}
+int Engine::recover_data_columns_host(int lo, int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* const* const* cells,
+                                      uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int* status) {
+    return recover_data_columns_checked_host(lo, R, n_columns, column_indices, cells, RecoverCheck{}, out_cells, out_proofs, status);
+}
+
+// The checked forms are the two calls above with three things more, all of them behind the decode they share: the commitment of every
+// recovered polynomial from the coefficients the decoder has just left (rs_decode's `commit`: in front of its one synchronisation, so a
+// sub-batch still costs one and the status words come down once), the comparison with the caller's bytes, and cells 0..63 once more in
+// blob-major order -- the recovered blobs.  An empty RecoverCheck launches what the unchecked calls always launched.
+int Engine::recover_data_columns_checked_device(int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells, const RecoverCheck& chk,
+                                                uint8_t* d_out_cells, uint8_t* d_out_proofs, int* status, hipStream_t user_stream) {
     if (R <= 0) return OK;
     const int list = column_list_status(n_columns, column_indices);
     for (int r = 0; r < R; r++) status[r] = list;
@@ -149,10 +159,17 @@ int Engine::recover_data_columns_device(int R, uint64_t n_columns, const uint64_
             ensure_workspace(nr);  // also orders stream_ behind the previous asynchronous user of the workspace (the sub-batch before this one)
             HIPCK(hipEventRecord(work_[0].ev_in, user_stream));  // the decode runs on the library's stream, behind what the caller's wrote into d_cells
             HIPCK(hipStreamWaitEvent(stream_, work_[0].ev_in, 0));
-            const int rc = rs_decode_columns(nr, (size_t)R, n_columns, column_indices, d_cells + (size_t)r0 * BYTES_PER_CELL, status + r0);
+            PoolBuf d_calc(*this, chk.commits() ? (size_t)nr * 48 : 0);
+            RsCommit commit;
+            commit.d_calc = (uint8_t*)d_calc.p;
+            commit.d_expected = chk.d_commitments ? chk.d_commitments + (size_t)r0 * 48 : nullptr;
+            commit.d_out = chk.d_out_commitments ? chk.d_out_commitments + (size_t)r0 * 48 : nullptr;
+            const int rc = rs_decode_columns(nr, (size_t)R, n_columns, column_indices, d_cells + (size_t)r0 * BYTES_PER_CELL, status + r0,
+                                             chk.commits() ? &commit : nullptr);
             if (rc) return rc;
             hipStream_t st = user_stream ? user_stream : stream_;
             const launch::Columns cols{(size_t)R, (size_t)r0};
+            if (chk.d_out_blobs) launch::coeffs_to_blobs(nr, d_coeffs_, chk.d_out_blobs + (size_t)r0 * BYTES_PER_BLOB, d_w29_, st);
             if (d_out_cells) launch::coeffs_to_cells(nr, d_coeffs_, d_out_cells, d_w29_, st, &cols);
             if (d_out_proofs) run_proofs_from_coeffs(work_[0], nr, d_out_proofs, st, nullptr, PROOFS_ALL, 0, &cols);
             HIPCK(hipEventRecord(work_[0].done, st));
@@ -166,8 +183,8 @@ int Engine::recover_data_columns_device(int R, uint64_t n_columns, const uint64_
     return OK;
 }
 
-int Engine::recover_data_columns_host(int lo, int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* const* const* cells,
-                                      uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int* status) {
+int Engine::recover_data_columns_checked_host(int lo, int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* const* const* cells,
+                                              const RecoverCheck& chk, uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int* status) {
     if (R <= 0) return OK;
     const int list = column_list_status(n_columns, column_indices);
     for (int r = 0; r < R; r++) status[lo + r] = list;
@@ -179,18 +196,34 @@ int Engine::recover_data_columns_host(int lo, int R, uint64_t n_columns, const u
         for (int r0 = 0; r0 < R; r0 += device_batch_max_) {
             const int nr = std::min(device_batch_max_, R - r0), first = lo + r0;
             ensure_workspace(nr);
-            // the present columns of these blobs as a [n_columns][nr] matrix, through pinned memory
-            const size_t in_bytes = (size_t)n_columns * nr * BYTES_PER_CELL;
-            PoolBuf h_in(*this, in_bytes, true), d_in(*this, in_bytes);
+            // the present columns of these blobs as a [n_columns][nr] matrix, through pinned memory; the expected commitments go up with them
+            const size_t in_bytes = (size_t)n_columns * nr * BYTES_PER_CELL, e_bytes = chk.commitments ? (size_t)nr * 48 : 0;
+            const size_t k_bytes = chk.commits() ? (size_t)nr * 48 : 0;
+            PoolBuf h_in(*this, in_bytes, true), d_in(*this, in_bytes), h_exp(*this, e_bytes, true), d_exp(*this, e_bytes);
+            PoolBuf d_calc(*this, k_bytes), h_calc(*this, chk.out_commitments ? k_bytes : 0, true);
             for (uint64_t j = 0; j < n_columns; j++)
                 for (int i = 0; i < nr; i++) memcpy((uint8_t*)h_in.p + (j * nr + i) * BYTES_PER_CELL, cells[j][first + i], BYTES_PER_CELL);
             HIPCK(hipMemcpyAsync(d_in.p, h_in.p, in_bytes, hipMemcpyHostToDevice, stream_));
-            const int rc = rs_decode_columns(nr, (size_t)nr, n_columns, column_indices, (const uint8_t*)d_in.p, status + first);
+            if (chk.commitments) {
+                for (int i = 0; i < nr; i++) memcpy((uint8_t*)h_exp.p + (size_t)i * 48, chk.commitments[first + i], 48);
+                HIPCK(hipMemcpyAsync(d_exp.p, h_exp.p, e_bytes, hipMemcpyHostToDevice, stream_));
+            }
+            RsCommit commit;
+            commit.d_calc = (uint8_t*)d_calc.p;
+            commit.d_expected = chk.commitments ? (const uint8_t*)d_exp.p : nullptr;
+            commit.h_out = chk.out_commitments ? (uint8_t*)h_calc.p : nullptr;
+            const int rc = rs_decode_columns(nr, (size_t)nr, n_columns, column_indices, (const uint8_t*)d_in.p, status + first, chk.commits() ? &commit : nullptr);
             if (rc) return rc;
             lap("stage in + RS decode");
             const size_t c_bytes = out_cells ? (size_t)nr * N_CELLS * BYTES_PER_CELL : 0, p_bytes = out_proofs ? (size_t)nr * N_CELLS * 48 : 0;
+            const size_t b_bytes = chk.out_blobs ? (size_t)nr * BYTES_PER_BLOB : 0;
             PoolBuf d_c(*this, c_bytes), d_p(*this, p_bytes), h_c(*this, c_bytes, true), h_p(*this, p_bytes, true);
+            PoolBuf d_b(*this, b_bytes), h_b(*this, b_bytes, true);
             const launch::Columns cols{(size_t)nr, 0};
+            if (chk.out_blobs) {
+                launch::coeffs_to_blobs(nr, d_coeffs_, (uint8_t*)d_b.p, d_w29_, stream_);
+                HIPCK(hipMemcpyAsync(h_b.p, d_b.p, b_bytes, hipMemcpyDeviceToHost, stream_));
+            }
             if (out_cells) {
                 launch::coeffs_to_cells(nr, d_coeffs_, (uint8_t*)d_c.p, d_w29_, stream_, &cols);
                 HIPCK(hipMemcpyAsync(h_c.p, d_c.p, c_bytes, hipMemcpyDeviceToHost, stream_));
@@ -201,7 +234,12 @@ int Engine::recover_data_columns_host(int lo, int R, uint64_t n_columns, const u
             }
             SYNC_CHECKED(stream_);
             lap("cells + proofs + D2H");
-            for (int c = 0; c < N_CELLS; c++)
+            for (int i = 0; i < nr; i++) {
+                if (status[first + i] != OK) continue;  // a refused blob: its slots stay as the caller left them
+                if (chk.out_commitments) memcpy(chk.out_commitments[first + i], (const uint8_t*)h_calc.p + (size_t)i * 48, 48);
+                if (chk.out_blobs) memcpy(chk.out_blobs[first + i], (const uint8_t*)h_b.p + (size_t)i * BYTES_PER_BLOB, BYTES_PER_BLOB);
+            }
+            for (int c = 0; c < N_CELLS && (out_cells || out_proofs); c++)
                 for (int i = 0; i < nr; i++) {
                     if (status[first + i] != OK) continue;
                     if (out_cells) memcpy(out_cells[c][first + i], (const uint8_t*)h_c.p + ((size_t)c * nr + i) * BYTES_PER_CELL, BYTES_PER_CELL);

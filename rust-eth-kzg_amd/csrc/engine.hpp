@@ -210,6 +210,7 @@ enum Status : int {
     ERR_INPUT = 3,     // length / index validation failed
     ERR_RECOVERY = 4,  // recovered polynomial has non-zero high coefficients
     ERR_DEVICE = 5,    // HIP failure
+    ERR_COMMITMENT = 6,  // checked recovery: the recovered polynomial's commitment differs from the one given (public; 5 is internal)
 };
 
 // Scoped scratch buffers of the host-pointer entry points come from per-context pools instead of hipMalloc / hipFree
@@ -333,6 +334,22 @@ public:
     // host pointers: cells[j][i], blobs [lo, lo + R) of the call; out_cells / out_proofs [128][blobs of the call], may be null; status: the whole call's
     int recover_data_columns_host(int lo, int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* const* const* cells,
                                   uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int* status);
+    // The same recovery checked against the block's commitments (c_eth_kzg.h: eth_kzg_amd_recover_data_columns_checked): what the checked
+    // forms add to the two calls above, which are these with an empty RecoverCheck.  Device form: d_* in HBM at any byte address,
+    // d_commitments / d_out_commitments R * 48, d_out_blobs [R][131072]; host form: the whole call's pointer arrays, indexed lo + r.
+    // Each may be null.  A blob whose commitment differs gets ERR_COMMITMENT behind ERR_SCALAR and ERR_RECOVERY.
+    struct RecoverCheck {
+        const uint8_t* d_commitments = nullptr;
+        uint8_t *d_out_blobs = nullptr, *d_out_commitments = nullptr;
+        const uint8_t* const* commitments = nullptr;
+        uint8_t* const* out_blobs = nullptr;
+        uint8_t* const* out_commitments = nullptr;
+        bool commits() const { return d_commitments || d_out_commitments || commitments || out_commitments; }
+    };
+    int recover_data_columns_checked_device(int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells, const RecoverCheck& chk,
+                                            uint8_t* d_out_cells, uint8_t* d_out_proofs, int* status, hipStream_t stream);
+    int recover_data_columns_checked_host(int lo, int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* const* const* cells,
+                                          const RecoverCheck& chk, uint8_t* const* const* out_cells, uint8_t* const* const* out_proofs, int* status);
 
     // ---- host-buffer entry points (what the reference's C ABI hands over) ----
     int compute_cells_and_kzg_proofs_host(int n, const uint8_t* const* blobs, uint8_t* const* const* cells,
@@ -607,11 +624,19 @@ private:
     struct RsDecodeTap { int* deg = nullptr; Fr8 *zp = nullptr, *zeval = nullptr, *zcinv = nullptr; };
     // src_of (null in every call but the column form): list entry k reads cell (*src_of)[k] of d_cells.  shared_pattern (the column form):
     // all R blobs miss the same cells -- `present` holds ONE mask and one vanishing polynomial is built for the call.
+    // commit (null in every call but the checked column recovery): behind the decode and in front of its one synchronisation, the
+    // commitments of the R recovered polynomials -- the stages of blob_to_kzg_commitment_device on the canonical coefficients the last
+    // pass leaves in work_[0].canon, the sums in work_[0].X -- into d_calc (R * 48 bytes of the engine's, 4-byte aligned);
+    // d_expected (device, any byte address, or null: nothing is compared): a blob whose 48 bytes differ gets ERR_COMMITMENT unless it
+    // has ERR_SCALAR or ERR_RECOVERY already; d_out (device, any address) / h_out (host), each R * 48 bytes or null: copies of d_calc,
+    // complete when rs_decode returns.  Every blob runs through the stages, a failed one on whatever its coefficients are.
+    struct RsCommit { uint8_t* d_calc = nullptr; const uint8_t* d_expected = nullptr; uint8_t* d_out = nullptr; uint8_t* h_out = nullptr; };
     int rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
                   const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap = nullptr, const std::vector<int>* src_of = nullptr,
-                  bool shared_pattern = false);
+                  bool shared_pattern = false, const RsCommit* commit = nullptr);
     // the column form's index arrays for blobs [r0, r0 + nr) of n_total, then rs_decode on them (data_columns.hip)
-    int rs_decode_columns(int nr, size_t n_total, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells_r0, int* st_out);
+    int rs_decode_columns(int nr, size_t n_total, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells_r0, int* st_out,
+                          const RsCommit* commit = nullptr);
     int recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_t* const* const* cells,
                                 const uint64_t* const* cell_indices, int* st_out);
     void ensure_workspace(int n);  // work_[0]; also makes stream_ wait for the last asynchronous call that used it

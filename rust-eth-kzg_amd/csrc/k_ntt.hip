@@ -310,6 +310,8 @@ __global__ __launch_bounds__(1024) void k_blob_to_extension(uint8_t* __restrict_
 //   CellsByBlob    [blob][128][2048]: the extended blob, what every call but the column forms launches
 //   CellsByColumn  [128][n_total][2048], this launch's blob b being blob b0 + b of the call: the layout of a block's data column
 //                  sidecars (eth_kzg_amd_compute_data_columns / _recover_data_columns).  128 n_total 2048 bytes pass 2^32: size_t throughout.
+//   BlobsOnly      [blob][131072]: cells 0..63 and nothing else, which are the blob's own bytes (eth_kzg_amd_recover_data_columns_checked's
+//                  out_blobs).  Launched with ONE block per blob (grid (n, 1)): half 1, the cells 64..127, is not computed at all.
 struct CellsByBlob {
     uint8_t* cells;
     __device__ __forceinline__ uint8_t* fr(int b, int h, int e) const { return cells + ((size_t)b * N_EXT + (size_t)h * N_BLOB + e) * 32; }
@@ -320,6 +322,10 @@ struct CellsByColumn {
     __device__ __forceinline__ uint8_t* fr(int b, int h, int e) const {
         return cells + (((size_t)(h * (N_CELLS / 2) + (e >> 6)) * n_total + b0 + b) * CELL_LEN + (e & (CELL_LEN - 1))) * 32;
     }
+};
+struct BlobsOnly {
+    uint8_t* blobs;
+    __device__ __forceinline__ uint8_t* fr(int b, int, int e) const { return blobs + ((size_t)b * N_BLOB + e) * 32; }
 };
 template <class Dst>
 __global__ __launch_bounds__(1024) void k_coeffs_to_cells(const Fr* __restrict__ coeffs, Dst dst, const Fr29* __restrict__ w29) {
@@ -503,6 +509,7 @@ void init_attributes() {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_extension), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByColumn>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<BlobsOnly>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells_scalars<CellsByColumn>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
 #ifdef KZG_TEST_HOOKS
@@ -557,6 +564,9 @@ void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, con
 }
 void fk20_tap_consts(const void* w29, const Fr8& scale, void* out, hipStream_t st) {
     k_fk20_tap_consts<<<2 * N_BLOB / 256, 256, 0, st>>>((const Fr29*)w29, fr29_from_plain(from_mont(as_fr(scale))), (Fr29*)out);
+}
+void coeffs_to_blobs(int n, const void* coeffs, uint8_t* blobs, const void* w29, hipStream_t st) {
+    k_coeffs_to_cells<<<dim3(n, 1), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, BlobsOnly{blobs}, (const Fr29*)w29);  // blockIdx.y = 0: half 0 alone
 }
 void coeffs_to_cells_scalars(int n, const void* coeffs, uint8_t* cells, void* scalars, const uint8_t* blobs, const int* status, const void* w29,
                              const void* tapk, int segs, const Fr8* seg_shifts, hipStream_t st, const Columns* cols) {

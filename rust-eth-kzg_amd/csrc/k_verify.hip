@@ -605,9 +605,11 @@ __global__ __launch_bounds__(1024) void k_rec_dit_half(const Fr* __restrict__ V,
     for (int e = threadIdx.x; e < N_BLOB; e += 1024) dst[e] = vl_load(s, e);
 }
 // last DIT layer of the 8192-point inverse transform + 1/8192 + coset (un)shift by shift[i]  (domain.rs:129-142,214-223).
-// final_pass: also check that coefficients 4096.. are zero (reed_solomon.rs:373-380) and emit only the low half to `coeffs`.
+// final_pass: also check that coefficients 4096.. are zero (reed_solomon.rs:373-380) and emit only the low half to `coeffs`; canon (may
+// be null): the same low half as canonical integers, the form the commitment's fixed-base MSM reads (checked recovery, data_columns.hip).
 __global__ void k_rec_dit_last(const Fr* __restrict__ T, const Fr* __restrict__ shift, Fr n_inv, Fr* __restrict__ U,
-                               Fr* __restrict__ coeffs, int* __restrict__ status, const Fr* __restrict__ w8192, int final_pass) {
+                               Fr* __restrict__ coeffs, int* __restrict__ status, const Fr* __restrict__ w8192, int final_pass,
+                               Fr* __restrict__ canon) {
     int idx = blockIdx.x * blockDim.x + threadIdx.x;  // r * 4096 + i
     int r = idx >> 12, i = idx & (N_BLOB - 1);
     const Fr* t = T + (size_t)r * N_EXT;
@@ -618,10 +620,22 @@ __global__ void k_rec_dit_last(const Fr* __restrict__ T, const Fr* __restrict__ 
     if (final_pass) {
         if (!is_zero(hi)) atomicOr(&status[r], 4);
         coeffs[(size_t)r * N_BLOB + i] = lo;
+        if (canon) canon[(size_t)r * N_BLOB + i] = from_mont(lo);
     } else {
         U[(size_t)r * N_EXT + i] = lo;
         U[(size_t)r * N_EXT + i + N_BLOB] = hi;
     }
+}
+// Checked recovery: one thread per blob compares the 48 bytes the commitment stages computed for the recovered polynomial (calc, a
+// work array of the engine) with the 48 bytes the caller expects -- read byte by byte where they lie, at any address, and never
+// decoded -- and ORs REC_COMMITMENT_BIT into the decoder's status word of the blob on a difference.  The bits 1 and 4 stay: the host
+// maps 1 first, then 4, then this one.
+__global__ void k_commitment_check(const uint8_t* __restrict__ calc, const uint8_t* __restrict__ expected, int* __restrict__ status, int n) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n) return;
+    uint32_t diff = 0;
+    for (int k = 0; k < 48; k++) diff |= (uint32_t)(calc[(size_t)b * 48 + k] ^ expected[(size_t)b * 48 + k]);
+    if (diff) atomicOr(&status[b], launch::REC_COMMITMENT_BIT);
 }
 // first DIF layer + DIF_4096 on half h, then cell-wise multiply by fac (the inverse vanishing values): U -> V
 __global__ __launch_bounds__(1024) void k_rec_dif_half(const Fr* __restrict__ U, const Fr* __restrict__ fac, Fr* __restrict__ V,
@@ -780,9 +794,12 @@ void rec_dit_half(int R, const void* V, const void* fac, void* T, const void* w8
     k_rec_dit_half<<<dim3(R, 2), 1024, LDS_NTT, st>>>((const Fr*)V, (const Fr*)fac, (Fr*)T, (const Fr*)w8192, fac_stride);
 }
 void rec_dit_last(int R, const void* T, const void* shift, const Fr8& n_inv, void* U, void* coeffs, int* status,
-                  const void* w8192, int final_pass, hipStream_t st) {
+                  const void* w8192, int final_pass, hipStream_t st, void* canon) {
     k_rec_dit_last<<<R * N_BLOB / 256, 256, 0, st>>>((const Fr*)T, (const Fr*)shift, as_fr2(n_inv), (Fr*)U, (Fr*)coeffs, status,
-                                                    (const Fr*)w8192, final_pass);
+                                                    (const Fr*)w8192, final_pass, (Fr*)canon);
+}
+void commitment_check(const uint8_t* calc, const uint8_t* expected, int* status, int n, hipStream_t st) {
+    k_commitment_check<<<(n + 63) / 64, 64, 0, st>>>(calc, expected, status, n);
 }
 void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st, int fac_stride) {
     k_rec_dif_half<<<dim3(R, 2), 1024, LDS_NTT, st>>>((const Fr*)U, (const Fr*)fac, (Fr*)V, (const Fr*)w8192, fac_stride);

@@ -42,6 +42,8 @@ struct Columns {
     size_t n_total, b0;
 };
 void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st, const Columns* cols = nullptr);
+// cells 0..63 only, blob-major: blobs = [n][131072], the bytes of the n blobs the coefficients belong to (checked recovery's out_blobs)
+void coeffs_to_blobs(int n, const void* coeffs, uint8_t* blobs, const void* w29, hipStream_t st);
 // every scalar leaves as its balanced GLV halves (what launch::glv_split would make of it)
 void fk20_scalars(int n, const void* coeffs, void* scalars, const void* w29, const Fr8& inv128, int segs, const Fr8* seg_shifts,
                   hipStream_t st);
@@ -184,8 +186,12 @@ void msm_pippenger2(const void* points, const void* sc0, int n0, const void* sc1
                     const Fp12w& beta, hipStream_t st);
 // fac_stride: factors per blob (128), or 0 when all R blobs share the 128 factors of one vanishing polynomial
 void rec_dit_half(int R, const void* V, const void* fac, void* T, const void* w8192, hipStream_t st, int fac_stride = 128);
+// canon (final pass only, may be null): the coefficients once more as canonical integers, what the commitment MSM reads
 void rec_dit_last(int R, const void* T, const void* shift, const Fr8& n_inv, void* U, void* coeffs, int* status,
-                  const void* w8192, int final_pass, hipStream_t st);
+                  const void* w8192, int final_pass, hipStream_t st, void* canon = nullptr);
+// checked recovery: status[b] |= REC_COMMITMENT_BIT where calc[48 b ..] differs from expected[48 b ..] (expected: any byte address)
+constexpr int REC_COMMITMENT_BIT = 8;
+void commitment_check(const uint8_t* calc, const uint8_t* expected, int* status, int n, hipStream_t st);
 void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8192, hipStream_t st, int fac_stride = 128);
 
 // k_verify_many.hip: many independent verifications in one pass (per-problem scalars, one lane or quad per scalar multiplication).

@@ -50,7 +50,8 @@ int Engine::recover_batch_to_coeffs(int R, const uint64_t* n_cells, const uint8_
 // list entry) and `present` (domain-order masks); the cell bytes are read from d_cells at list position k, or at
 // slot[k] when the caller's buffer is the flat [R][128][2048] layout.  Leaves the coefficients in d_coeffs_.
 int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std::vector<int>& slot, const std::vector<int>& stof,
-                      const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap, const std::vector<int>* src_of, bool shared_pattern) {
+                      const std::vector<uint32_t>& present, int* st_out, const RsDecodeTap* tap, const std::vector<int>* src_of, bool shared_pattern,
+                      const RsCommit* commit) {
     hipStream_t st = stream_;
     const int n = (int)slot.size();
     Fr seven64 = fr_u64(7);
@@ -77,7 +78,24 @@ int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std
     launch::rec_dit_last(R, d_T.p, d_coset_, n_inv8192_, d_U.p, nullptr, nullptr, d_w8192_, 0, st);      // ... * 7^i
     launch::rec_dif_half(R, d_U.p, d_zcinv.p, d_E.p, d_w8192_, st, fac_stride);                          // coset FFT, / Z
     launch::rec_dit_half(R, d_E.p, nullptr, d_T.p, d_w8192_, st);                                        // coset IFFT ...
-    launch::rec_dit_last(R, d_T.p, d_coset_inv_, n_inv8192_, nullptr, d_coeffs_, (int*)d_st.p, d_w8192_, 1, st);  // ... * 7^-i
+    launch::rec_dit_last(R, d_T.p, d_coset_inv_, n_inv8192_, nullptr, d_coeffs_, (int*)d_st.p, d_w8192_, 1, st,
+                         commit ? d_canon_ : nullptr);                                                  // ... * 7^-i
+    if (commit) {
+        // commit = MSM_4096(coefficients, monomial SRS), the stages of blob_to_kzg_commitment_device (engine_prover.hip) on the workspace
+        // this call holds: 64 groups of 64 bases into d_X_, folded over the groups, compressed -- for every blob, whatever its status
+        const int bp = ((R + 63) / 64) * 64;
+        const int mk = mark_begin(ST_MSM_FIXED, st);
+        launch::g1_set_inf(d_X_, (size_t)64 * bp, st, launch::FMT_JACS);
+        launch_msm(d_canon_, TAB_SRS, d_X_, 64, R, bp, 0, st, launch::FMT_JACS);
+        launch::g1_sum_positions(d_X_, 64, bp, R, st);
+        mark_end(mk, 2, st);
+        const int mk2 = mark_begin(ST_COMPRESS, st);
+        launch::g1_compress(d_X_, commit->d_calc, 1, bp, R, st, launch::FMT_JACS);
+        mark_end(mk2, 1, st);
+        if (commit->d_expected) launch::commitment_check(commit->d_calc, commit->d_expected, (int*)d_st.p, R, st);
+        if (commit->d_out) HIPCK(hipMemcpyAsync(commit->d_out, commit->d_calc, (size_t)R * 48, hipMemcpyDeviceToDevice, st));
+        if (commit->h_out) HIPCK(hipMemcpyAsync(commit->h_out, commit->d_calc, (size_t)R * 48, hipMemcpyDeviceToHost, st));
+    }
     std::vector<int> hst(R);
     HIPCK(hipMemcpyAsync(hst.data(), d_st.p, R * sizeof(int), hipMemcpyDeviceToHost, st));
     if (tap) {  // the stage hook: what the stages left, while the pool still holds it
@@ -91,6 +109,7 @@ int Engine::rs_decode(int R, const uint8_t* d_cells, bool flat_source, const std
         if (st_out[r] != OK) continue;
         if (hst[r] & 1) st_out[r] = ERR_SCALAR;
         else if (hst[r] & 4) st_out[r] = ERR_RECOVERY;
+        else if (hst[r] & launch::REC_COMMITMENT_BIT) st_out[r] = ERR_COMMITMENT;
     }
     return OK;
 }

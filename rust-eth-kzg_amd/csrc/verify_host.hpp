@@ -138,6 +138,12 @@ inline int validate_recovery(uint64_t n_cells, uint64_t n_indices, const uint64_
     if (n_indices < (uint64_t)N_CELLS / 2 || n_indices > (uint64_t)N_CELLS) return INPUT_INVALID;
     return INPUT_VALID;
 }
+// The status of the index list of a column recovery (eth_kzg_amd_recover_data_columns and its checked form): validate_recovery of the
+// per-blob list every blob of the call expands into (the count first: a list of more than 128 entries is refused unread).
+inline int column_list_status(uint64_t n_columns, const uint64_t* column_indices) {
+    if (n_columns < (uint64_t)N_CELLS / 2 || n_columns > (uint64_t)N_CELLS || !column_indices) return INPUT_INVALID;
+    return validate_recovery(n_columns, n_columns, column_indices);
+}
 
 // ---- compute_fiat_shamir_challenge of the cell verifier (fk20/verifier.rs:269-328), cell by cell: valid inputs are canonical
 // encodings, so the transcript is the input bytes themselves.  It always covers the WHOLE batch (n_all cells, m unique commitments).
