@@ -557,6 +557,47 @@ CResult eth_kzg_amd_verify_data_columns_device(const DASContext *ctx, uint64_t n
                                                const uint8_t *d_proofs, uint32_t flags, bool *verified, int32_t *status,
                                                void *hip_stream);
 
+/* ---- partial data columns: a bitmap of the blobs present per column ----
+ * Cell-level dissemination does not send whole sidecars: a partial data column sidecar carries a column index, a bitmap of the blobs
+ * present, and cells and proofs for those blobs only.  eth_kzg_amd_verify_partial_data_columns checks many such messages of one block
+ * over the block's commitment list, given ONCE:
+ *   commitments[i]   48 B, blob i (all n_blobs of the block)      column_indices[j]   the cell index of column j
+ *   present[j]       W = ceil(n_blobs / 64) words; bit i % 64 of word i / 64 is set when column j carries blob i (the convention of
+ *                    present_masks in eth_kzg_amd_recover_cells_and_proofs_device).  m_j = the set bits among the first n_blobs
+ *   cells[j][k] / proofs[j][k], k < m_j: of the k-th set bit in ascending blob order
+ * eth_kzg_amd_verify_partial_data_columns_device: d_commitments n_blobs*48, d_cells [N][2048] and d_proofs [N][48] PACKED in this GPU's
+ * HBM, any byte address: column after column, within a column ascending blob order.  A column occupies as many entries as ALL W of its
+ * words have set bits, stray bits included (so a refused column is skipped without being read); N is the sum of these counts.
+ * column_indices, present (flat, [n_columns][W]), verified and status are on the HOST.  Synchronous; work already queued on hip_stream
+ * (NULL: the default stream) is waited for.
+ * Contract: column j gets exactly the verified[j] and status[j] that eth_kzg_amd_verify_cell_kzg_proof_batch_many_ex gives the problem
+ * (commitments[i] for the set bits i in ascending order; m_j copies of column_indices[j]; cells[j]; proofs[j]), under either flag value:
+ * no new transcript, no new domain string, the folding weights keep their form.  Order of checks per column: status 3 for n_blobs >
+ * 2^24 - 1 (every column, nothing read), a set bit at or beyond n_blobs, or m_j > 0 and an index >= 128; else 2 when a commitment OF A
+ * PRESENT BLOB is bad -- a bad commitment marks the columns that hold a cell of that blob and no others, one that no column holds marks
+ * nothing --; else 2 for a bad proof of the column; else 1 for a non-canonical cell of the column; else 0 and the verdict.
+ * verified[j] is false whenever status[j] != 0; status may be NULL.  A column with no bit set verifies whatever its index (an empty
+ * problem).  Indices may repeat: two messages for one column with disjoint bitmaps are two problems.  Commitments may repeat.
+ * n_columns = 0 is Ok.  flags: 0 = the reference's transcript per column, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT as in the dense call.
+ * Err("InvalidInput...") for the call, before the context is touched: any other flag bit; n_columns > 2^24; column_indices or verified
+ * NULL with n_columns > 0; present NULL with n_columns > 0 and n_blobs > 0; commitments, cells or proofs NULL with both counts non-zero.
+ * A column refused at validation costs its status word: it is taken out of the call before any pass.  Device lists: the host form is cut
+ * by column over the listed devices; the device form runs on the owner of the buffers, and all three device pointers are resolved.
+ * The call de-duplicates the block's commitments once, a pass decodes each unique commitment once, every proof is multiplied once
+ * (the column shares h^64), and weights and w*C products exist only for the (column, commitment) pairs that hold a cell.
+ * Reconstruction from partial columns needs nothing new: per-blob erasure patterns are what
+ * eth_kzg_amd_recover_cells_and_proofs_batch takes.
+ * Out of scope: recovery in a masked column layout; merging partial columns; _partial / _combine; the combiner of concurrent single
+ * calls; sharding a device form over GPUs; the Node binding. */
+CResult eth_kzg_amd_verify_partial_data_columns(const DASContext *ctx, uint64_t n_blobs, const uint8_t *const *commitments,
+                                                uint64_t n_columns, const uint64_t *column_indices, const uint64_t *const *present,
+                                                const uint8_t *const *const *cells, const uint8_t *const *const *proofs,
+                                                uint32_t flags, bool *verified, int32_t *status);
+CResult eth_kzg_amd_verify_partial_data_columns_device(const DASContext *ctx, uint64_t n_blobs, const uint8_t *d_commitments,
+                                                       uint64_t n_columns, const uint64_t *column_indices, const uint64_t *present,
+                                                       const uint8_t *d_cells, const uint8_t *d_proofs,
+                                                       uint32_t flags, bool *verified, int32_t *status, void *hip_stream);
+
 /* ---- a block's data columns computed and recovered in column layout ----
  * The two neighbours of eth_kzg_amd_verify_data_columns, in its layout: cells and proofs as [column][blob], which is how the 128 data
  * column sidecars of a block carry them, so that a caller transposes nothing between the three calls.

@@ -186,6 +186,19 @@ int eth_kzg_amd_test_verify_data_columns_sums(const DASContext *ctx, uint64_t n_
                                               uint8_t *fold96, int32_t *probe_ranges, uint8_t *probe_sums96, uint64_t max_probes,
                                               uint64_t *n_probes, uint8_t *digests32, uint8_t *leaves32, uint64_t *counts2);
 
+/* The same tap on a pass of eth_kzg_amd_verify_partial_data_columns / _device (tests/test_gpu_partial_columns.py; the expansion into
+ * problems is tests/partial_columns.py): the arguments of eth_kzg_amd_test_verify_data_columns_sums plus the bitmaps -- on_device = 0:
+ * present is the host form's list of n_columns pointers, cells / proofs its pointer lists; 1: present is the flat [n_columns][W] array
+ * (host), cells / proofs the packed device arrays.  Problem b of every output is column b, leaves32 holds the leaves of the present
+ * cells column after column.  counts2[0]: the unique commitments of the call, decoded once per pass; counts2[1]: n proofs, one
+ * product per (column, commitment) PAIR and one h^64 * A per column.  One pass only, and 3 for a column that validation refuses. */
+int eth_kzg_amd_test_verify_partial_data_columns_sums(const DASContext *ctx, uint64_t n_blobs, int on_device, const void *commitments,
+                                                      uint64_t n_columns, const uint64_t *column_indices, const void *present,
+                                                      const void *cells, const void *proofs, uint32_t flags, int32_t *verified,
+                                                      int32_t *status, int32_t *form4, uint8_t *sums96, uint32_t *rho, uint8_t *fold96,
+                                                      int32_t *probe_ranges, uint8_t *probe_sums96, uint64_t max_probes,
+                                                      uint64_t *n_probes, uint8_t *digests32, uint8_t *leaves32, uint64_t *counts2);
+
 /* eth_kzg_amd_verify_kzg_proof_many / _many_device with a tap (csrc/point_many.hip; the statement is tests/point_many.py): exactly the
  * public call's launches, on the context's first device.  on_device = 0: commitments / zs / ys / proofs are the host form's pointer
  * lists; 1: the device form's flat arrays in device memory.  1 <= n <= 2^20.  forced_pass: 0 = the product's pass size, else the call is

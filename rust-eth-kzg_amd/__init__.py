@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_kzg_proof_many", "eth_kzg_amd_verify_kzg_proof_many_device",
     "eth_kzg_amd_verify_blob_kzg_proof_many", "eth_kzg_amd_verify_blob_kzg_proof_many_device",
     "eth_kzg_amd_verify_data_columns", "eth_kzg_amd_verify_data_columns_device",
+    "eth_kzg_amd_verify_partial_data_columns", "eth_kzg_amd_verify_partial_data_columns_device",
     "eth_kzg_amd_verify_blob_cell_proofs_many", "eth_kzg_amd_verify_blob_cell_proofs_many_device",
     "eth_kzg_amd_compute_data_columns", "eth_kzg_amd_compute_data_columns_device",
     "eth_kzg_amd_recover_data_columns", "eth_kzg_amd_recover_data_columns_device",
@@ -96,7 +97,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_verify_kzg_proof_many_sums",
     "eth_kzg_amd_test_blob_eval_at", "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums",
     "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats", "eth_kzg_amd_test_g1_decode",
-    "eth_kzg_amd_test_verify_data_columns_sums",
+    "eth_kzg_amd_test_verify_data_columns_sums", "eth_kzg_amd_test_verify_partial_data_columns_sums",
     "eth_kzg_amd_test_blob_extension", "eth_kzg_amd_test_verify_blob_cell_proofs_sums",
 ]
 
@@ -204,6 +205,8 @@ def load_library():
         "eth_kzg_amd_verify_blob_cell_proofs_many": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_verify_blob_cell_proofs_many_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_verify_data_columns_device": [P, U64, P, U64, P, P, P, C.c_uint32, P, P, P],
+        "eth_kzg_amd_verify_partial_data_columns": [P, U64, P, U64, P, P, P, P, C.c_uint32, P, P],
+        "eth_kzg_amd_verify_partial_data_columns_device": [P, U64, P, U64, P, P, P, P, C.c_uint32, P, P, P],
         "eth_kzg_amd_compute_data_columns": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_compute_data_columns_device": [P, U64, P, P, P, P, P, P],
         "eth_kzg_amd_recover_data_columns": [P, U64, U64, P, P, P, P, P],
@@ -251,6 +254,7 @@ def load_library():
         "eth_kzg_amd_test_search_stats": [P, P],
         "eth_kzg_amd_test_verify_blob_kzg_proof_many_sums": [P, U64, C.c_int, P, P, P, U64, P, P, P, U64, P, P, P, P, P, P, P, P, U64, P, P, P],
         "eth_kzg_amd_test_verify_data_columns_sums": [P, U64, C.c_int, P, U64, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P, P],
+        "eth_kzg_amd_test_verify_partial_data_columns_sums": [P, U64, C.c_int, P, U64, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P, P],
         "eth_kzg_amd_test_blob_extension": [P, U64, P, P, P],
         "eth_kzg_amd_test_verify_blob_cell_proofs_sums": [P, U64, C.c_int, P, P, P, P, P, P, P, P, P, P, P, U64, P, P, P],
     }.items():
@@ -679,6 +683,70 @@ class DASContext:
         st = (C.c_int32 * max(1, nc))()
         self._check(self._lib.eth_kzg_amd_verify_data_columns_device(
             self._ctx, n_blobs, C.c_void_p(d_commitments), nc, _vp(idx), C.c_void_p(d_cells), C.c_void_p(d_proofs),
+            VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st, C.c_void_p(stream) if stream else None))
+        return [bool(v) for v in ver][:nc], list(st)[:nc]
+
+    # ---- partial data columns: present[j] is a Python int, bit i = blob i (so that stray bits can be expressed)
+    @staticmethod
+    def _present_words(n_blobs, present):
+        """-> uint64 [n_columns][W], W = ceil(n_blobs / 64): the bitmaps as the C ABI takes them; bits beyond 64 W cannot cross it"""
+        words = (n_blobs + 63) // 64
+        if any(p < 0 or p >> (64 * words) for p in present):
+            raise KzgError("InvalidLength")
+        out = np.zeros((max(1, len(present)), max(1, words)), dtype=np.uint64)
+        for j, p in enumerate(present):
+            for w in range(words):
+                out[j, w] = (p >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+        return out, words
+
+    @classmethod
+    def _marshal_partial_columns(cls, commitments, column_indices, present, cells, proofs):
+        """-> (n_blobs, n_columns, commitments**, indices*, present**, cells***, proofs***, keep-alive): the arguments of
+        eth_kzg_amd_verify_partial_data_columns (cells[j][k] / proofs[j][k]: the k-th set bit of present[j])"""
+        nb, nc = len(commitments), len(column_indices)
+        if len(present) != nc or len(cells) != nc or len(proofs) != nc or any(len(c) != 48 for c in commitments) \
+                or any(len(cells[j]) != len(proofs[j]) for j in range(nc)) or any(len(p) != 48 for col in proofs for p in col) \
+                or any(len(c) != BYTES_PER_CELL for col in cells for c in col):
+            raise KzgError("InvalidLength")  # (fixed-size buffers carry no length across the C ABI)
+        bits, _words = cls._present_words(nb, present)
+        if any(len(cells[j]) != bin(present[j] & ((1 << nb) - 1)).count("1") for j in range(nc)):
+            raise KzgError("InvalidLength")  # (a column's lists are as long as its bitmap says: m_j, the set bits below n_blobs)
+        ca, k1 = _flat_ptrs(commitments, 48)
+        idx = np.array(column_indices, dtype=np.uint64) if nc else np.zeros(1, np.uint64)
+        keep, tabs = [k1, bits], [np.zeros(max(1, nc), dtype=np.uint64) for _ in range(3)]
+        for j in range(nc):
+            cla, k2 = _flat_ptrs(cells[j], BYTES_PER_CELL)
+            pa, k3 = _flat_ptrs(proofs[j], 48)
+            keep += [cla, k2, pa, k3]
+            tabs[0][j], tabs[1][j], tabs[2][j] = bits[j].ctypes.data, cla.ctypes.data, pa.ctypes.data
+        return nb, nc, ca, idx, tabs[0], tabs[1], tabs[2], keep
+
+    def verify_partial_data_columns(self, commitments, column_indices, present, cells, proofs, leaf_transcript=False):
+        """Partial data columns of one block (eth_kzg_amd_verify_partial_data_columns): commitments[i] of every blob i of the block,
+        column j = (column_indices[j], present[j], cells[j][k], proofs[j][k]) with k over the set bits of present[j] in ascending blob
+        order.  -> (verified list[bool], status list[int]) per column, exactly what verify_cell_kzg_proof_batch_many gives the column's
+        present cells as a problem of its own."""
+        nb, nc, ca, idx, ba, cla, pa, _keep = self._marshal_partial_columns(commitments, column_indices, present, cells, proofs)
+        ver = (C.c_bool * max(1, nc))()
+        st = (C.c_int32 * max(1, nc))()
+        self._check(self._lib.eth_kzg_amd_verify_partial_data_columns(self._ctx, nb, _vp(ca), nc, _vp(idx), _vp(ba), _vp(cla), _vp(pa),
+                                                                      VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st))
+        return [bool(v) for v in ver][:nc], list(st)[:nc]
+
+    def verify_partial_data_columns_device(self, n_blobs, d_commitments, column_indices, present, d_cells, d_proofs, stream=None,
+                                           leaf_transcript=False):
+        """The same on arrays in device memory (eth_kzg_amd_verify_partial_data_columns_device; integer device addresses): d_commitments
+        n_blobs*48 bytes; d_cells [N][2048] and d_proofs [N][48] packed column after column, within a column in ascending blob order, a
+        column taking as many entries as its bitmap has set bits; column_indices and present host sequences."""
+        nc = len(column_indices)
+        if len(present) != nc:
+            raise KzgError("InvalidLength")
+        idx = np.ascontiguousarray(np.array(column_indices, dtype=np.uint64)) if nc else np.zeros(1, np.uint64)
+        bits, _words = self._present_words(n_blobs, present)
+        ver = (C.c_bool * max(1, nc))()
+        st = (C.c_int32 * max(1, nc))()
+        self._check(self._lib.eth_kzg_amd_verify_partial_data_columns_device(
+            self._ctx, n_blobs, C.c_void_p(d_commitments), nc, _vp(idx), _vp(bits), C.c_void_p(d_cells), C.c_void_p(d_proofs),
             VERIFY_LEAF_TRANSCRIPT if leaf_transcript else 0, ver, st, C.c_void_p(stream) if stream else None))
         return [bool(v) for v in ver][:nc], list(st)[:nc]
 

@@ -488,6 +488,53 @@ CResult eth_kzg_amd_verify_data_columns_device(const DASContext* ctx, uint64_t n
                                                                           flags != 0), verified, status);
 }
 
+// Partial data columns (c_eth_kzg.h): the column source's fifth spelling.  The call-level refusals come before the context is looked at
+// (verify_host.hpp: validate_partial_columns_call); the bitmaps are validated and counted ONCE, here (PartialColumns), and the host
+// form's commitments de-duplicated once for all slices of a device list.
+CResult eth_kzg_amd_verify_partial_data_columns(const DASContext* ctx, uint64_t n_blobs, const uint8_t* const* commitments, uint64_t n_columns,
+                                                const uint64_t* column_indices, const uint64_t* const* present, const uint8_t* const* const* cells,
+                                                const uint8_t* const* const* proofs, uint32_t flags, bool* verified, int32_t* status) {
+    if (kzg::validate_partial_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !commitments, !column_indices, !present, !cells,
+                                           !proofs, !verified) != kzg::INPUT_VALID)
+        return err("InvalidInput: unknown verification flags, more than 2^24 columns, or a null array");
+    try {  // (the column plan and the de-duplication allocate: nothing may be thrown across the C ABI)
+        kzg::PartialColumns pc;
+        kzg::ColumnCommitments cc;
+        pc.from_list(n_blobs, n_columns, column_indices, present);
+        auto in = kzg::VerifyManyInput::host_partial_columns(pc, commitments, column_indices, cells, proofs, flags != 0);
+        if (pc.total_cells()) {
+            cc.from_list(n_blobs, commitments);
+            in.col = &cc;
+        }
+        return host_many(ctx, n_columns, kzg::DATA_COLUMNS_MAX, in, verified, status);
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+CResult eth_kzg_amd_verify_partial_data_columns_device(const DASContext* ctx, uint64_t n_blobs, const uint8_t* d_commitments, uint64_t n_columns,
+                                                       const uint64_t* column_indices, const uint64_t* present, const uint8_t* d_cells,
+                                                       const uint8_t* d_proofs, uint32_t flags, bool* verified, int32_t* status, void* hip_stream) {
+    if (kzg::validate_partial_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !d_commitments, !column_indices, !present, !d_cells,
+                                           !d_proofs, !verified) != kzg::INPUT_VALID)
+        return err("InvalidInput: unknown verification flags, more than 2^24 columns, or a null array");
+    live(ctx);
+    if (n_columns == 0) return ok();
+    try {  // (the column plan allocates: nothing may be thrown across the C ABI)
+        kzg::PartialColumns pc;
+        pc.from_flat(n_blobs, n_columns, column_indices, present);
+        kzg::Engine* e = ctx->engine;
+        if (n_blobs && n_blobs <= kzg::MAX_CELLS_PER_VERIFICATION) {  // (otherwise none of the arrays is read)
+            const void* const ptrs[3] = {d_commitments, d_cells, d_proofs};
+            e = engine_of_device_pointers(ctx, ptrs, 3);
+            if (!e) return err("InvalidInput: the three buffers are not device memory of one device of this context");
+        }
+        return device_many(e, n_columns, kzg::VerifyManyInput::device_partial_columns(pc, d_commitments, column_indices, d_cells, d_proofs,
+                                                                                      (hipStream_t)hip_stream, flags != 0), verified, status);
+    } catch (const std::exception& ex) {
+        return err(std::string("DeviceError(") + ex.what() + ")");
+    }
+}
+
 CResult eth_kzg_amd_recover_cells_and_proofs_device(const DASContext* ctx, uint64_t n, const uint8_t* d_cells,
                                                     const uint64_t* present_masks, uint8_t* d_out_cells, uint8_t* d_out_proofs,
                                                     int32_t* status, void* hip_stream) {

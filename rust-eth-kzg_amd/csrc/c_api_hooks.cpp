@@ -161,6 +161,32 @@ int eth_kzg_amd_test_verify_data_columns_sums(const DASContext* ctx, uint64_t n_
     return eng(ctx)->test_verify_many_sums_in(n_columns, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
                                               digests32, leaves32, counts2);
 }
+// the tap on a pass of the partial spelling (eth_kzg_amd_verify_partial_data_columns / _device)
+int eth_kzg_amd_test_verify_partial_data_columns_sums(const DASContext* ctx, uint64_t n_blobs, int on_device, const void* commitments, uint64_t n_columns,
+                                                      const uint64_t* column_indices, const void* present, const void* cells, const void* proofs,
+                                                      uint32_t flags, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho,
+                                                      uint8_t* fold96, int32_t* probe_ranges, uint8_t* probe_sums96, uint64_t max_probes, uint64_t* n_probes,
+                                                      uint8_t* digests32, uint8_t* leaves32, uint64_t* counts2) {
+    if (!verified || !status || !form4 || !sums96 || !rho || !fold96 || !n_probes || !digests32 || !counts2 || (max_probes && (!probe_ranges || !probe_sums96)) ||
+        (on_device != 0 && on_device != 1) || n_columns < 1 || n_columns > (1u << 20) ||
+        kzg::validate_partial_columns_call(flags, ETH_KZG_AMD_VERIFY_LEAF_TRANSCRIPT, n_blobs, n_columns, !commitments, !column_indices, !present, !cells,
+                                           !proofs, false) != kzg::INPUT_VALID)
+        return kzg::ERR_INPUT;
+    try {
+    kzg::PartialColumns pc;
+    if (on_device) pc.from_flat(n_blobs, n_columns, column_indices, (const uint64_t*)present);
+    else pc.from_list(n_blobs, n_columns, column_indices, (const uint64_t* const*)present);
+    const auto in = on_device ? kzg::VerifyManyInput::device_partial_columns(pc, (const uint8_t*)commitments, column_indices, (const uint8_t*)cells,
+                                                                             (const uint8_t*)proofs, nullptr, flags != 0)
+                              : kzg::VerifyManyInput::host_partial_columns(pc, (const uint8_t* const*)commitments, column_indices,
+                                                                           (const uint8_t* const* const*)cells, (const uint8_t* const* const*)proofs,
+                                                                           flags != 0);
+    return eng(ctx)->test_verify_many_sums_in(n_columns, in, verified, status, form4, sums96, rho, fold96, probe_ranges, probe_sums96, max_probes, n_probes,
+                                              digests32, leaves32, counts2);
+    } catch (const std::exception&) {  // (the column plan allocates)
+        return kzg::ERR_DEVICE;
+    }
+}
 int eth_kzg_amd_test_verify_kzg_proof_many_sums(const DASContext* ctx, uint64_t n, int on_device, const void* commitments, const void* zs, const void* ys,
                                                 const void* proofs, uint64_t forced_pass, int32_t* verified, int32_t* status, uint64_t* pass_starts,
                                                 uint64_t max_passes, uint64_t* n_passes, uint8_t* leaves32, uint8_t* seeds32, uint32_t* rho, uint8_t* fold96,

@@ -25,6 +25,7 @@ namespace pairing { struct G2Prepared; }
 namespace vm { struct DevicePairing; }  // vm_search.hpp
 struct Comm;  // multi_gpu.cpp
 struct ColumnCommitments;  // verify_host.hpp
+struct PartialColumns;
 struct G1Affine;  // curve.hpp
 namespace launch { struct Columns; }  // launch.hpp: the [column][blob] output layout
 struct Fr8 { uint32_t v[8]; };
@@ -65,6 +66,8 @@ struct VerifyManyTap {
 //     cells[b][i], proofs[b][i] on the host, or (col_device) d_commitments 48 col_blobs bytes, d_cells / d_proofs [columns][col_blobs]
 //     entries in this GPU's HBM.  Once the call has taken its refused columns out (verify_many.hip), problem b is the caller's column
 //     col_place[b] in all of these.  col: the commitments de-duplicated once for the whole call (null: the call makes it)
+//     Partial columns (part set; eth_kzg_amd_verify_partial_data_columns / _device): column b holds cells and proofs for the blobs of its
+//     bitmap only, part->count[b] of them, and in HBM the columns lie packed from entry part->start[b] on.
 //   blobs with their 128 cell proofs (from_blobs; eth_kzg_amd_verify_blob_cell_proofs_many / _many_device): problem b is the blob's 128
 //     cells with the indices 0..127 under ONE commitment; the pass computes the cells itself (k_ntt.hip: k_blob_to_extension) and the
 //     challenge is always the leaf-hashed one.  blobs[b] -> 131072 bytes, blob_commitments[b] -> 48 bytes, proofs[b][k] -> 48 bytes on the
@@ -82,6 +85,9 @@ struct VerifyManyInput {
     uint64_t col_blobs = 0;
     const uint64_t *col_place = nullptr, *col_indices = nullptr;
     const uint8_t* const* col_commitments = nullptr;
+    const PartialColumns* part = nullptr;  // (partial columns) the call's columns; problem b is its column part_base + (col_place ? col_place[b] : b)
+    const uint64_t* part_count = nullptr;  // part->count: m of every column of the call
+    uint64_t part_base = 0;
     const ColumnCommitments* col = nullptr;
     bool from_blobs = false, blobs_device = false;
     const uint8_t *const *blobs = nullptr, *const *blob_commitments = nullptr;
@@ -113,6 +119,13 @@ struct VerifyManyInput {
         in.columns = in.col_device = true; in.col_blobs = n_blobs; in.col_indices = column_indices;
         return in;
     }
+    // partial columns: a bitmap of the blobs present per column (verify_host.hpp: PartialColumns, made by the caller once per call);
+    // cells[b][k] / proofs[b][k] on the host, or d_cells / d_proofs packed column after column from part.start[b] on.  Defined in
+    // verify_many.hip, where PartialColumns is complete: n_blobs and the counts are taken from `part` there and nowhere else
+    static VerifyManyInput host_partial_columns(const PartialColumns& part, const uint8_t* const* commitments, const uint64_t* column_indices,
+                                                const uint8_t* const* const* cells, const uint8_t* const* const* proofs, bool leaf);
+    static VerifyManyInput device_partial_columns(const PartialColumns& part, const uint8_t* d_commitments, const uint64_t* column_indices,
+                                                  const uint8_t* d_cells, const uint8_t* d_proofs, hipStream_t user_stream, bool leaf);
     static VerifyManyInput host_blobs(const uint8_t* const* blobs, const uint8_t* const* commitments, const uint8_t* const* const* proofs) {
         VerifyManyInput in = lists(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, proofs, /*leaf=*/true);
         in.from_blobs = true; in.blobs = blobs; in.blob_commitments = commitments;
@@ -125,6 +138,7 @@ struct VerifyManyInput {
     }
     bool on_device() const { return from_blobs ? blobs_device : columns ? col_device : cell_starts != nullptr; }
     uint64_t cells_of(uint64_t b) const {
+        if (part) return part_count[part_base + (col_place ? col_place[b] : b)];  // m_b
         return from_blobs ? 128 : columns ? col_blobs : on_device() ? cell_starts[b + 1] - cell_starts[b] : n_cells[b];
     }
     VerifyManyInput from(uint64_t lo) const {  // the problems from lo on (the flat arrays stay: cell_starts holds absolute entries)
@@ -138,6 +152,7 @@ struct VerifyManyInput {
             if (col_place) { s.col_place += lo; return s; }
             // before the places are made ONLY the host form may be cut: nothing here carries an offset into d_cells / d_proofs
             s.col_indices += lo;  // (cells and proofs may be null when there are no blobs)
+            s.part_base += lo;
             if (cells && proofs) { s.cells += lo; s.proofs += lo; }
             return s;
         }

@@ -71,12 +71,25 @@ __device__ __forceinline__ Fr vm_block_sum(uint32_t (*part)[256], Fr acc, int t)
 }
 // weights[r] = sum of r_b^k over the cells k of problem b whose commitment is u (verifier.rs:216-219), canonical, block per weight.
 // Expanded source: r = u is a global row (problem's first row + local row) and b = row_batch[r];  column source (row_batch null):
-// r = b n_u + u over the pass's one commitment list.  [cell_start[b], cell_start[b + 1]) = that problem's cells
+// r = b n_u + u over the pass's one commitment list;  partial columns (pair_start set): r is a pair, b the column whose pairs
+// [pair_start[b], pair_start[b + 1]) hold it (a search over the n_cols + 1 starts, the same for the whole block) and u = pair_u[r].
+// [cell_start[b], cell_start[b + 1]) = that problem's cells
+__device__ __forceinline__ int vm_pair_column(const int* __restrict__ pair_start, int n_cols, int r) {
+    int lo = 0, hi = n_cols;  // the last b with pair_start[b] <= r: columns without pairs repeat a start and are passed over
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pair_start[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 __global__ __launch_bounds__(256) void k_vm_weights(const Fr* __restrict__ rp_mont, const int* __restrict__ row,
                                                     const int* __restrict__ row_batch, const int* __restrict__ cell_start,
-                                                    Fr* __restrict__ weights, int n_u) {
+                                                    Fr* __restrict__ weights, int n_u, const int* __restrict__ pair_start,
+                                                    const int* __restrict__ pair_u, int n_cols) {
     __shared__ uint32_t part[8][256];
-    const int r = blockIdx.x, t = threadIdx.x, b = row_batch ? row_batch[r] : r / n_u, u = row_batch ? r : r - b * n_u;
+    const int r = blockIdx.x, t = threadIdx.x;
+    const int b = pair_start ? vm_pair_column(pair_start, n_cols, r) : row_batch ? row_batch[r] : r / n_u;
+    const int u = pair_start ? pair_u[r] : row_batch ? r : r - b * n_u;
     const int lo = cell_start[b], hi = cell_start[b + 1];
     Fr acc = zero<FrParams>();
     for (int k = lo + t; k < hi; k += 256)
@@ -108,9 +121,9 @@ __global__ __launch_bounds__(256) void k_vm_interp_sum(const Fr* __restrict__ co
 
 // The product k P itself, by a lane or by a quad: vm_lane_mul.hpp (vm_mul_by_scalar; k_point_many.hip takes it from there too).
 // The products of a pass: at most four consecutive segments of the product index e, segment j = [seg[j - 1].end, seg[j].end):
-// its i-th product is scalars[i] (canonical) times points[wrap ? i % wrap : i] (affine Montgomery-384, decoded); an empty segment
-// repeats the end before it.  The two sources differ in the map alone (launch::vm_products).
-struct VmSeg { int end, wrap; const Fr* scalars; const G1Affine* points; };
+// its i-th product is scalars[i] (canonical) times points[idx ? idx[i] : wrap ? i % wrap : i] (affine Montgomery-384, decoded); an
+// empty segment repeats the end before it.  The sources differ in the map alone (launch::vm_products).
+struct VmSeg { int end, wrap; const Fr* scalars; const G1Affine* points; const int* idx; };
 struct VmProductMap { VmSeg seg[4]; };
 // prod[e] for every e < seg[3].end, PER_BLOCK products per block; a lane behind the last product repeats it and stores nothing
 // (whole waves).  SHORT-CHAIN passes (a handful of problems: concurrent single calls combined, verify_many.hip)
@@ -142,7 +155,7 @@ __global__ __launch_bounds__(64, 2) void k_vm_products(VmProductMap map, JacQ* _
         if (e >= map.seg[j - 1].end) { s = map.seg[j]; i = e - map.seg[j - 1].end; }
     uint32_t split[8];
     glv_split_balanced(s.scalars[i], split);
-    const JacQ r = vm_mul_by_scalar(affq_from_affine(s.points[s.wrap ? i % s.wrap : i]), split, beta, ops);
+    const JacQ r = vm_mul_by_scalar(affq_from_affine(s.points[s.idx ? s.idx[i] : s.wrap ? i % s.wrap : i]), split, beta, ops);
     if (real) prod[e] = r;
 }
 // two trees of 128 partial sums side by side (job 0 in red[0..128), job 1 in red[128..256)), each folded by its half of the
@@ -242,6 +255,8 @@ __global__ __launch_bounds__(256) void k_vm_fold_ranges(const JacQ* __restrict__
 //   k_vm_products   the map r^k pi_k | w[b][u] C_u | (short-chain form) the interpolation terms
 //   k_vc_reduce     per column: A_b, and T_b = sum_u w[b][u] C_u - commit(...)
 //   k_vc_hmul       quad per column: B_b = h^64 A_b + T_b, the only writer of the column's second result slot
+// PARTIAL columns (eth_kzg_amd_verify_partial_data_columns) hold the blobs of their bitmap only: the (column, commitment) pairs that
+// exist are a list (pair_start per column, pair_u per pair), one weight and one product per pair; nothing else differs.
 __global__ void k_vc_scalars(const VmPow* __restrict__ tabs, const int* __restrict__ batch_of, const int* __restrict__ pos_in_batch,
                              const int* __restrict__ cell_idx, const int* __restrict__ cell_start, const Fr* __restrict__ w8192,
                              Fr* __restrict__ rp_mont, Fr* __restrict__ s1, Fr* __restrict__ h64, int n, int n_cols) {
@@ -259,9 +274,11 @@ __global__ void k_vc_scalars(const VmPow* __restrict__ tabs, const int* __restri
     }
 }
 // per column b: out[2b] = A_b = sum of prod[cells of b];  tsum[b] = sum_u prod[n + b n_u + u] + (icommit ? icommit[b] : the 64
-// interpolation terms prod[n + W + 64 b ..]), W = columns x n_u.  out[2b + 1] is left to k_vc_hmul.
+// interpolation terms prod[n + W + 64 b ..]), W = columns x n_u.  out[2b + 1] is left to k_vc_hmul.  Partial columns (pair_start
+// set): the column's w C products are prod[n + pair_start[b] .. n + pair_start[b + 1]) and W is the pass's pairs.
 __global__ __launch_bounds__(256) void k_vc_reduce(const JacQ* __restrict__ prod, const JacQ* __restrict__ icommit, const int* __restrict__ cell_start,
-                                                   JacQ* __restrict__ out, JacQ* __restrict__ tsum, int n, int n_u, int W) {
+                                                   JacQ* __restrict__ out, JacQ* __restrict__ tsum, int n, int n_u, int W,
+                                                   const int* __restrict__ pair_start) {
     __shared__ JacQ red[256];
     const int b = blockIdx.x, t = threadIdx.x, job = t >> 7, l = t & 127;
     JacQ acc = jacq_inf();
@@ -269,8 +286,9 @@ __global__ __launch_bounds__(256) void k_vc_reduce(const JacQ* __restrict__ prod
         const int lo = cell_start[b], hi = cell_start[b + 1];
         for (int k = lo + l; k < hi; k += 128) acc = add(acc, prod[k]);
     } else {
-        const JacQ* wc = prod + n + (size_t)b * n_u;
-        for (int u = l; u < n_u; u += 128) acc = add(acc, wc[u]);
+        const JacQ* wc = prod + n + (pair_start ? (size_t)pair_start[b] : (size_t)b * n_u);
+        const int n_w = pair_start ? pair_start[b + 1] - pair_start[b] : n_u;
+        for (int u = l; u < n_w; u += 128) acc = add(acc, wc[u]);
         if (icommit) { if (l == 0) acc = add(acc, icommit[b]); }
         else if (l < 64) acc = add(acc, prod[(size_t)n + W + 64 * (size_t)b + l]);
     }
@@ -321,22 +339,24 @@ void vm_scalars(const void* pow_tables /*[B][24] Fr, device*/, const int* batch_
         k_vm_scalars<<<(lanes + 255) / 256, 256, 0, st>>>((const VmPow*)pow_tables, batch_of, pos_in_batch, cell_idx, (const Fr*)w8192, (Fr*)rp_mont,
                                                            (Fr*)s1, (Fr*)s2, n);
 }
-void vm_weights(const void* rp_mont, const int* row, const int* row_batch, const int* cell_start, void* weights, int m, int n_batches, hipStream_t st) {
-    const int blocks = row_batch ? m : vm_count((long long)n_batches * m, n_batches);
-    if (blocks > 0) k_vm_weights<<<blocks, 256, 0, st>>>((const Fr*)rp_mont, row, row_batch, cell_start, (Fr*)weights, m);
+void vm_weights(const void* rp_mont, const int* row, const int* row_batch, const int* cell_start, void* weights, int m, int n_batches, hipStream_t st,
+                const VmPairs& pairs) {
+    const int blocks = pairs.start ? vm_count(pairs.count, n_batches) : row_batch ? m : vm_count((long long)n_batches * m, n_batches);
+    if (blocks > 0)
+        k_vm_weights<<<blocks, 256, 0, st>>>((const Fr*)rp_mont, row, row_batch, cell_start, (Fr*)weights, m, pairs.start, pairs.u, n_batches);
 }
 void vm_interp_sum(const void* coef, const void* rp_mont, const int* cell_start, void* out_neg_canon, int n_batches, hipStream_t st) {
     if (n_batches > 0) k_vm_interp_sum<<<n_batches, 256, 0, st>>>((const Fr*)coef, (const Fr*)rp_mont, cell_start, (Fr*)out_neg_canon);
 }
 int vm_products(const void* pts, const void* s1, const void* s2, const void* wts, const void* isc, const void* srs, void* prod, int n, int m,
-                int n_batches, bool small, int* status, const Fp12w& beta, hipStream_t st) {
+                int n_batches, bool small, int* status, const Fp12w& beta, hipStream_t st, const VmPairs& pairs) {
     const G1Affine* p = (const G1Affine*)pts;
-    const long long W = s2 ? m : (long long)n_batches * m, both = s2 ? 2LL * n : n;
+    const long long W = pairs.start ? pairs.count : s2 ? m : (long long)n_batches * m, both = s2 ? 2LL * n : n;
     const int decoded = vm_count(n < 0 || m < 0 ? -1 : both + W, n_batches), proofs = (int)both;
     const int total = decoded + (small ? 64 * n_batches : 0), tests = small ? n + m : 0;
     if (total <= 0) return 0;
-    const VmProductMap map = {{{n, 0, (const Fr*)s1, p}, {proofs, 0, (const Fr*)s2, p}, {decoded, s2 ? 0 : m, (const Fr*)wts, p + n},
-                               {total, 64, (const Fr*)isc, (const G1Affine*)srs}}};
+    const VmProductMap map = {{{n, 0, (const Fr*)s1, p, nullptr}, {proofs, 0, (const Fr*)s2, p, nullptr},
+                               {decoded, s2 ? 0 : m, (const Fr*)wts, p + n, pairs.u}, {total, 64, (const Fr*)isc, (const G1Affine*)srs, nullptr}}};
     // quads up to 1,024 waves of 16 (products and tests): every wave still has a SIMD to itself
     const bool quads = small && total + tests <= 2 * coop_points_max();
     const int per = quads ? VmQuad::PER_BLOCK : VmLane::PER_BLOCK, mb = (total + per - 1) / per;
@@ -345,15 +365,15 @@ int vm_products(const void* pts, const void* s1, const void* s2, const void* wts
     return decoded;
 }
 int vm_sums(const void* prod, const void* icommit, const int* cell_start, const int* row_start, const void* h64, void* out, int n, int m, int n_batches,
-            const Fp12w& beta, hipStream_t st) {
+            const Fp12w& beta, hipStream_t st, const VmPairs& pairs) {
     if (n_batches <= 0) return 0;
     if (row_start) {
         k_vm_reduce<<<n_batches, 256, 0, st>>>((const JacQ*)prod, (const JacQ*)icommit, cell_start, row_start, (JacQ*)out, n, m);
         return 0;
     }
-    const int W = vm_count((long long)n_batches * m, n_batches);
+    const int W = pairs.start ? vm_count(pairs.count, n_batches) : vm_count((long long)n_batches * m, n_batches);
     JacQ* tsum = (JacQ*)prod + (size_t)n + W + (icommit ? 0 : 64 * (size_t)n_batches);
-    k_vc_reduce<<<n_batches, 256, 0, st>>>((const JacQ*)prod, (const JacQ*)icommit, cell_start, (JacQ*)out, tsum, n, m, W);
+    k_vc_reduce<<<n_batches, 256, 0, st>>>((const JacQ*)prod, (const JacQ*)icommit, cell_start, (JacQ*)out, tsum, n, m, W, pairs.start);
     k_vc_hmul<<<(n_batches + 15) / 16, 64, 0, st>>>((JacQ*)out, tsum, (const Fr*)h64, n_batches, vm_beta(beta));
     return n_batches;
 }

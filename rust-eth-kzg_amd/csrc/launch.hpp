@@ -200,21 +200,26 @@ void rec_dif_half(int R, const void* U, const void* fac, void* V, const void* w8
 // pass-wide, and one h_(c_b)^64 per column.  A launcher tells the column source by the pointer it names as null there.
 // rp_mont[k] / s1[k] = r_b^k (Montgomery / canonical);  s2[k] = r_b^k h_k^64 (null: columns);  h64[b] canonical, 1 for a column
 // without cells (null: expanded)
+// Partial columns (eth_kzg_amd_verify_partial_data_columns): a column holds the blobs of its bitmap only, so its weights and w C products
+// go by a sparse pair list where the dense column pass addresses (b, u) at b m + u: column b's pairs are start[b] .. start[b + 1], pair r
+// is the commitment u[r] of the pass's list; count = start[n_batches] <= n.  start null: no pair list (every other source).
+struct VmPairs { const int* start = nullptr; const int* u = nullptr; int count = 0; };
 void vm_scalars(const void* pow_tables /*[B][24] Fr*/, const int* batch_of, const int* pos_in_batch, const int* cell_idx, const int* cell_start,
                 const void* w8192, void* rp_mont, void* s1, void* s2, void* h64, int n, int n_batches, hipStream_t st);
-// weights[m], or [n_batches][m] for columns (row_batch null)
-void vm_weights(const void* rp_mont, const int* row, const int* row_batch, const int* cell_start, void* weights, int m, int n_batches, hipStream_t st);
+// weights[m], or [n_batches][m] for columns (row_batch null), or one per pair
+void vm_weights(const void* rp_mont, const int* row, const int* row_batch, const int* cell_start, void* weights, int m, int n_batches, hipStream_t st,
+                const VmPairs& pairs = {});
 void vm_interp_sum(const void* coef, const void* rp_mont, const int* cell_start, void* out_neg_canon, int n_batches, hipStream_t st);
 // every scalar multiplication of the pass in ONE launch.  prod (JacQ): s1[e] pi_e n | s2[e] pi_e n | w[j] C_j m, or for columns (s2 null)
-// s1[e] pi_e n | w[b][u] C_u n_batches m;  small (short-chain passes): behind them the 64 interpolation terms isc[b][j] SRS_j per
+// s1[e] pi_e n | w[b][u] C_u n_batches m (pairs: w[r] C_(u[r]), count of them);  small (short-chain passes): behind them the 64 interpolation terms isc[b][j] SRS_j per
 // problem, and the launch also holds the subgroup tests of the n + m points (status: 0 -> 0 / 2).  -> products of decoded points
 int vm_products(const void* pts, const void* s1, const void* s2, const void* wts, const void* isc, const void* srs, void* prod, int n, int m,
-                int n_batches, bool small, int* status, const Fp12w& beta, hipStream_t st);
+                int n_batches, bool small, int* status, const Fp12w& beta, hipStream_t st, const VmPairs& pairs = {});
 // out[b][2] JacQ: the two sums of problem b's products + (icommit ? icommit[b] : its 64 interpolation terms).  Columns (row_start null):
 // out[2b + 1] = h64[b] out[2b] + the rest, a second launch of n_batches products behind the reduction (prod holds n_batches more
 // JacQ behind the products).  -> products launched
 int vm_sums(const void* prod, const void* icommit, const int* cell_start, const int* row_start, const void* h64, void* out /*[B][2] JacQ*/, int n,
-            int m, int n_batches, const Fp12w& beta, hipStream_t st);
+            int m, int n_batches, const Fp12w& beta, hipStream_t st, const VmPairs& pairs = {});
 // out2[j] = sum_b rho_b sums[b][j] (rho: 4 words per problem, 0 excludes it); prod: scratch of 2 B JacQ
 void vm_fold(const void* sums, const uint32_t* rho, void* prod, void* out2, int n_batches, const Fp12w& beta, hipStream_t st);
 // out[r][2] = the weighted pairs summed over problems ranges[r][0] .. ranges[r][1] - 1 (prod as vm_fold left it)

@@ -2,7 +2,8 @@
 // codecs and the Fiat-Shamir transcripts (the reference's four, the leaf-hashed challenge of the cell verifier and the leaves, seed and
 // weights of the point many-verification), each stated ONCE for verify.hip, verify_many.hip, point_many.hip, eip4844.hip and recover.hip.
 // No HIP call in here, everything inline: tests/c/test_verify_host.cpp, test_leaf_transcript.cpp, test_many_leaf.cpp,
-// test_point_many.cpp, test_blob_many.cpp, test_data_columns.cpp and test_blob_cells.cpp run it on the CPU against hashlib.
+// test_point_many.cpp, test_blob_many.cpp, test_data_columns.cpp, test_partial_columns.cpp and test_blob_cells.cpp run it on the CPU
+// against hashlib.
 // Reference: crates/eip7594/src/verifier.rs:49-164, crates/cryptography/kzg_multi_open/src/fk20/verifier.rs:269-328,
 // crates/eip4844/src/verifier.rs:155-262, crates/eip7594/src/recovery.rs:90-146, crates/cryptography/bls12_381/src/lib.rs:128-140.
 #pragma once
@@ -127,6 +128,111 @@ struct ColumnCommitments {
     void from_list(uint64_t n_blobs, const uint8_t* const* commitments) { dedup_commitments(n_blobs, commitments, uniq, row); }
     void from_own(uint64_t n_blobs) { dedup_commitments_flat(n_blobs, own.data(), uniq, row); }
 };
+
+// ---- eth_kzg_amd_verify_partial_data_columns / _device (c_eth_kzg.h): columns that carry a BITMAP of the blobs present and cells and
+// proofs for those blobs only (the partial data column sidecar of cell-level dissemination).  present[j]: W = ceil(n_blobs / 64) words,
+// bit i % 64 of word i / 64 = blob i (the convention of present_masks in eth_kzg_amd_recover_cells_and_proofs_device).  Column j is the
+// problem (commitments[i] for its set bits i in ascending order, m_j copies of column_indices[j], cells[j], proofs[j]) of the
+// many-verification; there is no new transcript.  A fifth spelling of the column source, not a new verifier.
+inline uint64_t partial_words(uint64_t n_blobs) { return (n_blobs + 63) / 64; }
+// what the call refuses as a whole, before the context is touched
+inline int validate_partial_columns_call(uint32_t flags, uint32_t known_flags, uint64_t n_blobs, uint64_t n_columns, bool commitments_null,
+                                         bool indices_null, bool present_null, bool cells_null, bool proofs_null, bool verified_null) {
+    if (flags & ~known_flags) return INPUT_INVALID;
+    if (n_columns > DATA_COLUMNS_MAX) return INPUT_INVALID;
+    if (n_columns == 0) return INPUT_VALID;
+    if (verified_null || indices_null) return INPUT_INVALID;
+    if (n_blobs != 0 && (present_null || commitments_null || cells_null || proofs_null)) return INPUT_INVALID;
+    return INPUT_VALID;
+}
+inline uint64_t popcount64(uint64_t w) { uint64_t c = 0; for (; w; w &= w - 1) c++; return c; }
+// The entries a column occupies in the packed device arrays: the set bits of ALL its W words, stray bits included, so that a refused
+// column is skipped without being read.
+inline uint64_t partial_column_entries(uint64_t n_blobs, const uint64_t* words) {
+    uint64_t c = 0;
+    for (uint64_t w = 0; w < partial_words(n_blobs); w++) c += popcount64(words[w]);
+    return c;
+}
+// THE STRAY-BIT RULE and the status of one column at validation: 3 for a set bit at or beyond n_blobs (only the last word can hold
+// one) or, where the column holds a cell, an index >= 128 (validate_cell_batch of the expanded problem: an empty problem is valid
+// without its index being read).  n_blobs beyond the bound: every column, nothing read.  *count = m_j, the set bits below n_blobs.
+inline int validate_partial_column(uint64_t n_blobs, uint64_t column_index, const uint64_t* words, uint64_t* count) {
+    *count = 0;
+    if (n_blobs > INPUT_MAX_CELLS) return INPUT_INVALID;
+    const uint64_t W = partial_words(n_blobs);
+    if (n_blobs % 64 != 0 && (words[W - 1] >> (n_blobs % 64)) != 0) return INPUT_INVALID;
+    uint64_t m = 0;
+    for (uint64_t w = 0; w < W; w++) m += popcount64(words[w]);
+    if (m != 0 && column_index >= (uint64_t)N_CELLS) return INPUT_INVALID;
+    *count = m;
+    return INPUT_VALID;
+}
+// The columns of a call, made ONCE (c_api.cpp, before the call is cut over a device list): per column its status at validation, m_j
+// (0 for a refused column), its first entry in the packed device arrays (start, n_columns + 1 entries: a refused column keeps its
+// place there) and the blobs it holds in ascending order (blob[blob_start[j] .. blob_start[j + 1]); nothing for a refused column).
+// words_of(j) -> the W words of column j (a pointer list, or the flat array of the device form).
+struct PartialColumns {
+    uint64_t n_blobs = 0, W = 0;
+    std::vector<int> status;
+    std::vector<uint64_t> count, start, blob_start;
+    std::vector<uint32_t> blob;
+    template <class WordsOf>
+    void build(uint64_t n_blobs_, uint64_t n_columns, const uint64_t* column_indices, WordsOf words_of) {
+        n_blobs = n_blobs_; W = partial_words(n_blobs);
+        const bool unread = n_blobs > INPUT_MAX_CELLS;  // nothing of the bitmaps is read
+        status.assign(n_columns, INPUT_INVALID); count.assign(n_columns, 0); start.assign(n_columns + 1, 0); blob_start.assign(n_columns + 1, 0);
+        blob.clear();
+        for (uint64_t j = 0; j < n_columns; j++) {
+            const uint64_t* const words = unread || W == 0 ? nullptr : words_of(j);
+            if (!unread) status[j] = validate_partial_column(n_blobs, column_indices[j], words, &count[j]);
+            start[j + 1] = start[j] + (unread || W == 0 ? 0 : partial_column_entries(n_blobs, words));
+            if (status[j] == INPUT_VALID)
+                for (uint64_t w = 0; w < W; w++)
+                    for (uint64_t bits = words[w]; bits; bits &= bits - 1) blob.push_back((uint32_t)(w * 64 + (uint64_t)__builtin_ctzll(bits)));
+            blob_start[j + 1] = blob.size();
+        }
+    }
+    void from_list(uint64_t n_blobs_, uint64_t n_columns, const uint64_t* column_indices, const uint64_t* const* present) {
+        build(n_blobs_, n_columns, column_indices, [present](uint64_t j) { return present[j]; });
+    }
+    void from_flat(uint64_t n_blobs_, uint64_t n_columns, const uint64_t* column_indices, const uint64_t* present) {
+        const uint64_t w = partial_words(n_blobs_);
+        build(n_blobs_, n_columns, column_indices, [present, w](uint64_t j) { return present + j * w; });
+    }
+    uint64_t total_cells() const { return blob.size(); }
+};
+// What differs per column, stated once.  (1) THE TRANSCRIPT'S ROWS.  The expanded problem is de-duplicated alone
+// (dedup_commitments over the commitments of its present blobs): its unique list holds the call's unique commitments that its present
+// blobs refer to, in the order in which the column's OWN blobs first name them -- with repeated commitments that need not be the order
+// of the call's list (blobs X Y X with blobs 1 and 2 present: Y X) -- and its rows are ranks inside that list.  Under flags = 0 the
+// reference transcript carries that list, its length and those rows (uniq, row); the kernels go on reading the pass-wide row of every
+// cell (pass_row).  (2) THE PAIR LIST.  The column's (column, commitment) pairs are that same list as indices into the call's unique
+// list (pair_u): one weight and one product each, never more than the column has cells.
+struct PartialColumnView {
+    std::vector<const uint8_t*> uniq;  // the column's own unique list
+    std::vector<int> row;              // per cell: rank in uniq
+    std::vector<int> pass_row;         // per cell: index into the call's unique list
+    std::vector<int> pair_u;           // per entry of uniq: its index in the call's unique list
+};
+inline void partial_column_view(const ColumnCommitments& cc, const uint32_t* blobs, uint64_t m, PartialColumnView& v) {
+    v.uniq.clear(); v.pair_u.clear();
+    v.row.resize(m); v.pass_row.resize(m);
+    std::map<int, int> rank;  // call-wide row -> rank in the column's list
+    for (uint64_t k = 0; k < m; k++) {
+        const int u = cc.row[blobs[k]];
+        auto it = rank.find(u);
+        if (it == rank.end()) { it = rank.emplace(u, (int)v.uniq.size()).first; v.uniq.push_back(cc.uniq[(size_t)u]); v.pair_u.push_back(u); }
+        v.row[k] = it->second;
+        v.pass_row[k] = u;
+    }
+}
+// The columns of a partial call that go on: kept column k is the caller's column keep[k].
+inline std::vector<uint64_t> vm_kept_partial_columns(const PartialColumns& pc, uint64_t base, uint64_t n_columns) {
+    std::vector<uint64_t> keep;
+    for (uint64_t b = 0; b < n_columns; b++)
+        if (pc.status[base + b] == INPUT_VALID) keep.push_back(b);
+    return keep;
+}
 
 // validate_recovery_inputs (recovery.rs:90-146)
 inline int validate_recovery(uint64_t n_cells, uint64_t n_indices, const uint64_t* cell_indices) {

@@ -5,7 +5,8 @@
 // crates/cryptography/bls12_381/src/lib.rs:45-50).  Here the problems of a call share every GPU launch.
 // FOUR SOURCES (engine.hpp: VerifyManyInput says what each holds), resolved once per part into a CellSource: pointer lists on the
 // host; flat arrays in HBM plus cell_starts; the columns of one block over ONE commitment list, on the host or in HBM (problem b is
-// column b; verify_data_columns_many does the source's once-per-call work); blobs with their commitment and 128 cell proofs, on the host
+// column b; verify_data_columns_many does the source's once-per-call work; its PARTIAL spelling: a column holds the blobs of its bitmap
+// only, and its weights and products go by a sparse (column, commitment) pair list); blobs with their commitment and 128 cell proofs, on the host
 // or in HBM (problem b is blob b's 128 cells, which the pass computes itself in its arena: the step `extend`).  Two challenges: the reference's transcript per problem,
 // or the leaf-hashed challenge of each problem alone (verify_host.hpp: CellLeafTranscript).  A large CALL is cut into at most three
 // concurrent PARTS, a part into CHUNKS of at most VM_CHUNK_CELLS cells, and every chunk is one PASS (Engine::CellManyPass) on one of three
@@ -25,6 +26,7 @@
 //   verdicts   ONE 2-pairing check per pass; where it fails the wrong problems are SEARCHED by folding sub-ranges of the resident weighted sums,
 //              one pairing per probe ($ETH_KZG_AMD_VM_SEARCH=0: one by one; $ETH_KZG_AMD_VM_FOLD=0: no fold)
 #include "vm_search.hpp"
+#include <memory>
 #include <numeric>
 
 namespace kzg {
@@ -37,6 +39,11 @@ struct Problem {  // one verification of the call, after validation
     std::vector<const uint8_t*> own_uniq;  // where the two live when the problem was de-duplicated alone; the columns of a
     std::vector<int> own_row;              // column call all refer to the call's one pair (verify_host.hpp: ColumnCommitments)
     int n = 0, m = 0;                  // cells, unique commitments (0, 0 when the problem is skipped)
+    // (partial columns, verify_host.hpp: PartialColumnView) uniq / row / m above are the TRANSCRIPT's view, the column's own list and the
+    // rows re-ranked inside it; the kernels read the pass-wide row of every cell, and the column's pairs are its list in pass-wide rows
+    std::unique_ptr<PartialColumnView> pv;  // (null for every other source: they pay a pointer)
+    const int* pass_row = nullptr;     // per cell: the row the kernels read (null: row)
+    int pairs() const { return pv ? (int)pv->pair_u.size() : 0; }
 };
 
 // Where the B problems of a part come from: made once per part, it answers what the part and its passes ask about problem b.
@@ -45,6 +52,7 @@ struct CellSource {
     const int B;
     const bool device = in.on_device();  // proofs and cells lie in HBM (the host has neither)
     const bool shared = in.columns;      // the commitments are the pass's: one list, every problem's (the column source)
+    const bool partial = in.part != nullptr;  // (the column source) a bitmap of blobs per column: unequal columns, a pair list per pass
     const bool blobs = in.from_blobs;    // a problem is a blob: its cells are computed in the arena, its indices are 0..127, one commitment
     std::vector<uint64_t> src0;          // (device) the problem's first entry in the caller's d_cells / d_proofs
     std::vector<uint64_t> mir0;          // (flat arrays) its first entry in the pinned mirror of commitments and indices: back to back
@@ -53,7 +61,7 @@ struct CellSource {
     const uint64_t* mirror_i = nullptr;
     CellSource(const VerifyManyInput& in_, int B_) : in(in_), B(B_) {
         for (int b = 0; b < B && device; b++) {
-            src0.push_back(blobs ? (uint64_t)b * N_CELLS : shared ? place(b) * in.col_blobs : in.cell_starts[b]);
+            src0.push_back(blobs ? (uint64_t)b * N_CELLS : partial ? in.part->start[part_at(b)] : shared ? place(b) * in.col_blobs : in.cell_starts[b]);
             mir0.push_back(mirror_n);
             if (!shared && !blobs && in_mirror(b)) mirror_n += cells_of(b);
         }
@@ -62,6 +70,7 @@ struct CellSource {
     // a problem beyond the size bound is refused by its validation (status 3) and has no place in the mirror: nothing of it is read
     bool in_mirror(int b) const { return cells_of(b) <= MAX_CELLS_PER_VERIFICATION; }
     uint64_t place(int b) const { return shared ? in.col_place[b] : (uint64_t)b; }  // where the caller's arrays hold problem b
+    uint64_t part_at(int b) const { return in.part_base + place(b); }               // (partial columns) its column in the call's PartialColumns
     uint64_t index_of(int b, int k) const {
         return blobs ? (uint64_t)k : shared ? in.col_indices[place(b)] : device ? mirror_i[mir0[b] + k] : in.cell_indices[b][k];
     }
@@ -82,6 +91,14 @@ struct CellSource {
             p.own_uniq.assign(1, blob_commitment(b));
             p.uniq = p.own_uniq.data(); p.row = row0;
             p.m = 1; p.n = N_CELLS;
+            return OK;
+        }
+        if (partial) {  // validated with the call (only accepted columns come here); the column's own list, rows and pairs
+            if (nb == 0) return OK;
+            p.pv.reset(new PartialColumnView);
+            partial_column_view(*in.col, in.part->blob.data() + in.part->blob_start[part_at(b)], nb, *p.pv);
+            p.uniq = p.pv->uniq.data(); p.row = p.pv->row.data(); p.pass_row = p.pv->pass_row.data();
+            p.m = (int)p.pv->uniq.size(); p.n = (int)nb;
             return OK;
         }
         const int st = shared   ? validate_data_column(nb, in.col_indices[place(b)])
@@ -131,13 +148,17 @@ struct PassLayout {
     // the column source: the m unique commitments are the PASS's (every problem's), each problem has its own m weights, there is no
     // second proof scalar but one h^64 per problem, and the products are n + Bc m, with Bc more slots for the commitment-side sums
     const bool cols;
-    const size_t wn = cols ? (size_t)Bc * (size_t)m : (size_t)m;  // (every column of a column pass holds cells: Bc m <= n m / n_blobs <= n)
+    // partial columns: P (column, commitment) pairs in place of Bc m, P <= n always since every pair has a cell (-1: no pair list)
+    const int P;
+    const size_t wn = P >= 0 ? (size_t)P : cols ? (size_t)Bc * (size_t)m : (size_t)m;  // (every column of a dense pass holds cells: Bc m <= n m / n_blobs <= n)
     const int max_ranges = std::min(Bc, 2048);  // probes per level of the search for wrong proofs
     static constexpr size_t JACQ = launch::SIZEOF_JACQ;
     Carve d;  // (members are initialised in the order they stand here)
     const size_t off_p = d.take((size_t)n * 48), off_c = d.take((size_t)m * 48), off_cells = d.take((size_t)n * BYTES_PER_CELL),
                  off_idx = d.take((size_t)n * 4), off_row = d.take((size_t)n * 4), off_bat = d.take((size_t)n * 4), off_pos = d.take((size_t)n * 4),
-                 off_rowb = d.take((size_t)m * 4), off_cs = d.take((size_t)(Bc + 1) * 4), off_rs = d.take((size_t)(Bc + 1) * 4), in_bytes = d.end;
+                 off_rowb = d.take((size_t)m * 4), off_cs = d.take((size_t)(Bc + 1) * 4), off_rs = d.take((size_t)(Bc + 1) * 4),
+                 off_ps = d.take(P >= 0 ? (size_t)(Bc + 1) * 4 : 0), off_pu = d.take(P >= 0 ? (size_t)P * 4 : 0),  // pair_start, pair_u
+                 in_bytes = d.end;
     const size_t off_pow = d.take((size_t)Bc * 24 * sizeof(Fr)),  // second upload (after the hashes)
                  off_rho = d.take((size_t)Bc * 16),               // folding weights, 128 bits per problem
                  in2_bytes = d.end;
@@ -157,7 +178,8 @@ struct PassLayout {
                  off_out = d.take((size_t)2 * Bc * JACQ), off_fprod = d.take((size_t)2 * Bc * JACQ), off_fold = d.take((size_t)2 * JACQ),
                  off_rng = d.take((size_t)max_ranges * 8), off_rsum = d.take((size_t)2 * max_ranges * JACQ),
                  off_leaf = d.take(leaf ? (size_t)n * 32 : 0), off_verd = d.take((size_t)max_ranges), dev_bytes = d.end;
-    PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_, bool cols_) : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_), cols(cols_) {}
+    PassLayout(int n_, int m_, int Bc_, bool small_, bool leaf_, bool cols_, int P_)
+        : n(n_), m(m_), Bc(Bc_), small(small_), leaf(leaf_), cols(cols_), P(P_) {}
 };
 }  // namespace
 
@@ -182,7 +204,8 @@ struct Engine::CellManyPass {
     // subgroup tests and the interpolation commitments' terms inside the ONE launch of all scalar multiplications (k_vm_products), no fold
     // (a 1.4 ms chain; <= 2 T pairing checks are one or two rounds of the host threads) -- 0.45 + 1.7 + 0.2 ms of GPU instead of ~6
     const bool small = e.vm_small_max_ != 0 && Bc <= (e.vm_small_max_ > 0 ? e.vm_small_max_ : 2 * T);
-    const PassLayout L{n, m, Bc, small, S.in.leaf, S.shared};
+    const int P = S.partial ? std::accumulate(pr, pr + Bc, 0, [](int a, const Problem& p) { return a + p.pairs(); }) : -1;  // the pass's pairs
+    const PassLayout L{n, m, Bc, small, S.in.leaf, S.shared, P};
     const pairing::G2Prepared* const vk[2] = {e.g2_tau_.get(), e.g2_neg_gen_.get()};  // [tau^64]_2, -[1]_2
     const vm::DevicePairing gpu = e.device_pairing(0);  // the same keys for k_pairing_check (the search's larger batches of probes)
     // the host's hashes read what a copy on st brings down: the leaf digests, or the proofs and cells of a device source
@@ -190,6 +213,7 @@ struct Engine::CellManyPass {
     uint8_t *hb = nullptr, *db = nullptr;    // the slot's pinned slab and device arena
     std::atomic<int> device_fault{0};
     std::vector<int> cell_start, row_start;  // first cell / first unique commitment of each problem
+    std::vector<int> pair_start;             // (partial columns) first pair of each column
     std::vector<uint8_t> digests;            // of the challenges: the fold seed hashes them
     std::vector<char> live;                  // problems that decoded without an error
     int n_live = 0;
@@ -227,6 +251,13 @@ struct Engine::CellManyPass {
         for (int j = 0; j < S.pass_m(); j++) memcpy(hb + L.off_c + (size_t)j * 48, S.pass_uniq()[j], 48);
         memcpy(hb + L.off_cs, cell_start.data(), (size_t)(Bc + 1) * 4);
         memcpy(hb + L.off_rs, row_start.data(), (size_t)(Bc + 1) * 4);
+        if (S.partial) {  // the pair list: column i's pairs are its own unique list, as indices into the pass's commitments
+            pair_start.assign(Bc + 1, 0);
+            for (int i = 0; i < Bc; i++) pair_start[i + 1] = pair_start[i] + pr[i].pairs();
+            memcpy(hb + L.off_ps, pair_start.data(), (size_t)(Bc + 1) * 4);
+            int* const h_pu = (int*)(hb + L.off_pu);
+            for (int i = 0; i < Bc; i++) if (pr[i].pv) std::copy(pr[i].pv->pair_u.begin(), pr[i].pv->pair_u.end(), h_pu + pair_start[i]);
+        }
         int *h_idx = (int*)(hb + L.off_idx), *h_row = (int*)(hb + L.off_row), *h_bat = (int*)(hb + L.off_bat), *h_pos = (int*)(hb + L.off_pos),
             *h_rowb = (int*)(hb + L.off_rowb);
         const bool gather = !S.device;
@@ -241,7 +272,7 @@ struct Engine::CellManyPass {
                     if (!S.blobs) memcpy(hb + L.off_cells + (size_t)(c0 + k) * BYTES_PER_CELL, S.cell(b0 + i, k), BYTES_PER_CELL);
                 }
                 h_idx[c0 + k] = (int)S.index_of(b0 + i, k);
-                h_row[c0 + k] = r0 + p.row[k];
+                h_row[c0 + k] = p.pass_row ? p.pass_row[k] : r0 + p.row[k];
                 h_bat[c0 + k] = i;
                 h_pos[c0 + k] = k;
             }
@@ -362,14 +393,15 @@ struct Engine::CellManyPass {
         const int* h_st = h_status();
         live.assign(Bc, 0);
         int alive = 0;
-        bool shared_bad = false;  // a bad commitment of the pass's one list is every problem's
-        for (int j = 0; j < S.pass_m(); j++) shared_bad |= h_st[L.n + j] != 0;
+        bool shared_bad = false;  // a bad commitment of the pass's one list is every problem's; partial columns: of the columns that hold it
+        for (int j = 0; j < S.pass_m() && !S.partial; j++) shared_bad |= h_st[L.n + j] != 0;
         for (int i = 0; i < Bc; i++) {
             const Problem& p = pr[i];
             if (p.n == 0) continue;
             const int c0 = cell_start[i], r0 = row_start[i];
             int bad = shared_bad ? (int)ERR_G1 : (int)OK;
             for (int j = 0; j < S.own_rows(p) && !bad; j++) if (h_st[L.n + r0 + j]) bad = ERR_G1;
+            for (int j = 0; j < p.pairs() && !bad; j++) if (h_st[L.n + p.pv->pair_u[j]]) bad = ERR_G1;
             for (int k = 0; k < p.n && !bad; k++) if (h_st[c0 + k]) bad = ERR_G1;
             if (!bad && h_st[L.n + L.m + i]) bad = ERR_SCALAR;
             if (S.blobs) bad = blob_cells_item_status(h_st[L.n + L.m + i] != 0, bad == ERR_G1);
@@ -399,15 +431,17 @@ struct Engine::CellManyPass {
         uint8_t *const d_s2 = L.cols ? nullptr : db + L.off_s2, *const d_h = L.cols ? db + L.off_h : nullptr;  // vm_scalars, vm_products
         const int* const d_rowb = L.cols ? nullptr : (const int*)(db + L.off_rowb);                                // vm_weights
         const int* const d_rs = L.cols ? nullptr : (const int*)(db + L.off_rs);                                    // vm_sums
+        // (partial columns) the pair list: weights, the w C products and the commitment-side sums go by it
+        const launch::VmPairs pairs = {S.partial ? (const int*)(db + L.off_ps) : nullptr, S.partial ? (const int*)(db + L.off_pu) : nullptr, S.partial ? P : 0};
         launch::vm_scalars(db + L.off_pow, (const int*)(db + L.off_bat), (const int*)(db + L.off_pos), (const int*)(db + L.off_idx), d_cs, e.d_w8192_,
                            db + L.off_rp, db + L.off_s1, d_s2, d_h, n, Bc, st);
-        launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), d_rowb, d_cs, db + L.off_w, m, Bc, st);
+        launch::vm_weights(db + L.off_rp, (const int*)(db + L.off_row), d_rowb, d_cs, db + L.off_w, m, Bc, st, pairs);
         launch::vm_interp_sum(db + L.off_coef, db + L.off_rp, d_cs, db + L.off_isc, Bc, st);
         uint64_t muls = (uint64_t)launch::vm_products(db + L.off_pts, db + L.off_s1, d_s2, db + L.off_w, db + L.off_isc, e.d_srs_, db + L.off_prod, n, m, Bc,
-                                                      small, d_stp, e.beta_, st);
+                                                      small, d_stp, e.beta_, st, pairs);
         // - commit(interpolation polynomial): 64 fixed bases = group 0 of the commitment window table (verification_key.rs:66-70)
         if (!small) e.launch_msm(db + L.off_isc, TAB_SRS, db + L.off_icm, 1, Bc, Bc, 0, st, launch::FMT_JACQ);
-        muls += (uint64_t)launch::vm_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, d_rs, db + L.off_h, db + L.off_out, n, m, Bc, e.beta_, st);
+        muls += (uint64_t)launch::vm_sums(db + L.off_prod, small ? nullptr : db + L.off_icm, d_cs, d_rs, db + L.off_h, db + L.off_out, n, m, Bc, e.beta_, st, pairs);
         if (small) HIPCK(hipMemcpyAsync(h_status(), d_stp, (size_t)(n + m) * 4, hipMemcpyDeviceToHost, st));  // with the subgroup verdicts now
         if (tap) tap->scalar_muls = muls;
     }
@@ -466,6 +500,19 @@ struct Engine::CellManyPass {
     }
 };
 
+VerifyManyInput VerifyManyInput::host_partial_columns(const PartialColumns& part, const uint8_t* const* commitments, const uint64_t* column_indices,
+                                                      const uint8_t* const* const* cells, const uint8_t* const* const* proofs, bool leaf) {
+    VerifyManyInput in = host_columns(part.n_blobs, commitments, column_indices, cells, proofs, leaf);
+    in.part = &part; in.part_count = part.count.data();
+    return in;
+}
+VerifyManyInput VerifyManyInput::device_partial_columns(const PartialColumns& part, const uint8_t* d_commitments, const uint64_t* column_indices,
+                                                        const uint8_t* d_cells, const uint8_t* d_proofs, hipStream_t user_stream, bool leaf) {
+    VerifyManyInput in = device_columns(part.n_blobs, d_commitments, column_indices, d_cells, d_proofs, user_stream, leaf);
+    in.part = &part; in.part_count = part.count.data();
+    return in;
+}
+
 int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
     return in.columns ? verify_data_columns_many((int)n_batches, in, verified, status, tap)
                       : verify_cell_kzg_proof_batch_many_parts((int)n_batches, in, verified, status, tap);
@@ -475,12 +522,20 @@ int Engine::verify_cell_kzg_proof_batch_many(uint64_t n_batches, const VerifyMan
 // what the caller's stream has queued; a host-form call sliced over a device list brings in.col, made once for all slices); and the
 // columns refused at validation taken OUT, so that every column of a pass holds n_blobs cells and its Bc n_u weights and products are
 // bounded by its cells.  keep[k]: the caller's column that goes on as problem k (in.col_place); the verdicts are scattered back by it.
+// Partial columns (in.part: validated and counted by the caller, once): the kept columns hold m_b cells each, a column without a bit is
+// an empty problem, and a call whose kept columns hold no cell reads nothing.
 int Engine::verify_data_columns_many(int B, const VerifyManyInput& in, int* verified, int* status, VerifyManyTap* tap) {
-    const std::vector<uint64_t> keep = vm_kept_columns(in.col_blobs, (uint64_t)B, in.col_indices);
+    const std::vector<uint64_t> keep = in.part ? vm_kept_partial_columns(*in.part, in.part_base, (uint64_t)B) : vm_kept_columns(in.col_blobs, (uint64_t)B, in.col_indices);
     const size_t K = keep.size();
     for (int b = 0; b < B; b++) { verified[b] = in.col_blobs == 0; status[b] = ERR_INPUT; }  // (no blobs: empty problems, verifier.rs:90-93)
     for (size_t k = 0; k < K; k++) status[keep[k]] = OK;
-    if (K == 0 || in.col_blobs == 0) return OK;
+    uint64_t kept_cells = in.part ? 0 : (uint64_t)K * in.col_blobs;
+    for (size_t k = 0; k < K && in.part; k++) {  // (partial columns: a column without a bit is an empty problem)
+        const uint64_t m_k = in.part->count[in.part_base + keep[k]];
+        verified[keep[k]] = m_k == 0;
+        kept_cells += m_k;
+    }
+    if (kept_cells == 0) return OK;  // (nothing to read: neither the commitments nor a cell)
     ColumnCommitments cc;
     VerifyManyInput go = in;
     if (!in.col && in.col_device) {
