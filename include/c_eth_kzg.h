@@ -646,6 +646,51 @@ CResult eth_kzg_amd_recover_data_columns_device(const DASContext *ctx, uint64_t 
                                                 const uint64_t *column_indices, const uint8_t *d_cells, uint8_t *d_out_cells,
                                                 uint8_t *d_out_proofs, int32_t *status, void *hip_stream);
 
+/* ---- a block's data columns from blobs whose cell proofs the caller HOLDS ----
+ * eth_kzg_amd_blobs_to_data_columns / _device -- the call of a proposer, and of every node that fetches blobs from its execution client
+ * (getBlobsV2), the transaction pool or a relay: since PeerDAS a blob arrives with its 128 cell proofs, so the node that builds the 128
+ * sidecars runs no FK20.  It needs cells = compute_cells(blob) as [column][blob], the proofs it was handed re-ordered from [blob][128]
+ * to [128][blob], and usually a check of those proofs before it signs or forwards anything.
+ *   blobs[i] / d_blobs n_blobs * 131072      commitments[i] / d_commitments n_blobs * 48      proofs[i][k] / d_proofs [n_blobs][128][48]
+ *   out_cells[c][i] / d_out_cells [128][n_blobs][2048]      out_proofs[c][i] / d_out_proofs [128][n_blobs][48]
+ * out_cells / out_proofs may each be NULL and are then not produced.  verified and status are HOST memory.
+ * flags = 0: status[i] is what eth_kzg_amd_compute_data_columns gives blob i (1: an element >= r, else 0) and out_cells[c][i] are the
+ * bytes of that call's out_cells[c][i]; out_proofs[c][i] are the 48 bytes of proofs[i][c] as they stand -- never decoded: garbage is
+ * copied as garbage.  commitments is not read and may be NULL; verified is not written and may be NULL; status may be NULL.  Device
+ * form: status, stream, ordering behind the caller's queued work and alignment of d_blobs as eth_kzg_amd_compute_data_columns_device
+ * (d_out_cells 4-byte aligned like d_blobs; d_proofs and d_out_proofs from any byte address); with status == NULL and a stream given
+ * the call returns without synchronising.
+ * flags = ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS: status[i] and verified[i] are exactly what eth_kzg_amd_verify_blob_cell_proofs_many /
+ * _many_device give item i -- that call's order of checks, its leaf-hashed challenge per item, its folding weights, its one pairing
+ * check per pass, its search and its soundness paragraph; there is no new transcript and no new domain string.  Synchronous; runs on
+ * pass slots and does not take the context's big lock.
+ * Outputs.  Host form: blob i's slots are written only when status[i] == 0 and, under the flag, verified[i] is true; otherwise they
+ * stay as the caller left them.  Device form: the slots of such a blob are unspecified.  No other blob's bytes are disturbed.
+ * Err("InvalidInput...") for the call, before the context is touched: any other flag bit; n_blobs > 2^24; blobs NULL with n_blobs > 0;
+ * proofs NULL when the flag is set or out_proofs is given; commitments or verified NULL when the flag is set.  n_blobs = 0 is Ok.
+ * Device lists: the host form is cut into contiguous slices by blob; the device form runs on the owner of the buffers -- every device
+ * pointer given is resolved, and anything but device memory of one listed device is Err("InvalidInput...").
+ * How.  flags = 0: one block per blob computes all 128 cells without leaving the CU (csrc/k_ntt.hip: k_blob_to_columns, the image and
+ * transforms of k_blob_to_extension) and stores every byte once at its column address -- no coefficient goes to HBM, none of the
+ * prover's workspace is used and there is no [blob][128] intermediate -- and one small kernel re-orders the proofs.  Host form: every
+ * blob is uploaded once and only cells 64..127 (128 KB per blob) come down; cells 0..63 ARE the caller's blob bytes and out_proofs the
+ * caller's proof bytes, copied on the host by the helper threads.  Under the flag the columns are an output of the blob source of the
+ * many-verification (csrc/verify_many.hip): the pass keeps its blob-major arena for leaves and decoding, a copy kernel behind the
+ * extension step puts the cells at their column addresses (device form) or the extension halves come down into the pass's pinned slab
+ * (host form), and the proofs are re-ordered from where the pass holds them.  Each blob is uploaded once where the two calls it
+ * replaces upload it twice and extend it twice.
+ * Out of scope: computing missing proofs with FK20 inside this call; computing or checking commitments from the blobs; a
+ * reference-transcript variant; sharding a device form over GPUs.  The Node binding is not extended.  When it pays: INTEGRATION.md. */
+#define ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS 1u
+CResult eth_kzg_amd_blobs_to_data_columns(const DASContext *ctx, uint64_t n_blobs, const uint8_t *const *blobs,
+                                          const uint8_t *const *commitments, const uint8_t *const *const *proofs, uint32_t flags,
+                                          uint8_t *const *const *out_cells, uint8_t *const *const *out_proofs, bool *verified,
+                                          int32_t *status);
+CResult eth_kzg_amd_blobs_to_data_columns_device(const DASContext *ctx, uint64_t n_blobs, const uint8_t *d_blobs,
+                                                 const uint8_t *d_commitments, const uint8_t *d_proofs, uint32_t flags,
+                                                 uint8_t *d_out_cells, uint8_t *d_out_proofs, bool *verified, int32_t *status,
+                                                 void *hip_stream);
+
 /* ---- a block's data columns recovered AND checked against the block's commitments ----
  * eth_kzg_amd_recover_data_columns / _device cannot tell a right input from a wrong one when exactly 64 columns are given: the decoder's
  * only consistency test is that the recovered polynomial has no coefficient at 4096 or above (status 4), and ANY 64 columns of

@@ -241,6 +241,15 @@ int eth_kzg_amd_test_verify_blob_kzg_proof_many_sums(const DASContext *ctx, uint
  * element >= r, else 0.  Synchronous; 0 on success. */
 int eth_kzg_amd_test_blob_extension(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs, uint8_t *out_cells, int32_t *out_bad);
 
+/* k_blob_to_columns alone (csrc/k_ntt.hip; the kernel of eth_kzg_amd_blobs_to_data_columns): ONE launch over n blobs, 1 <= n <= 1024, that
+ * are blobs [b0, b0 + n) of a column matrix of n_total blobs, b0 + n <= n_total <= 4096, on the context's first device.  blobs[b] -> 131072
+ * bytes on the host.  matrix, host, [128][n_total][2048]: goes up as the caller filled it (a guard pattern), is written by the launch and
+ * comes down again -- cell c of blob b at ((c * n_total + b0 + b) * 2048); a refused blob writes nothing.  blob_half = 0: rows 0..63 are
+ * not written (the host form's launch).  out_bad[n] = the status words: 1 for a blob that holds an element >= r, else 0.  Synchronous;
+ * 0 on success, 3 for a bad argument before anything is launched. */
+int eth_kzg_amd_test_blob_to_columns(const DASContext *ctx, uint64_t n, const uint8_t *const *blobs, uint64_t n_total, uint64_t b0, int blob_half,
+                                     uint8_t *matrix, int32_t *out_bad);
+
 /* The tap of eth_kzg_amd_test_verify_many_sums_device on a pass of eth_kzg_amd_verify_blob_cell_proofs_many / _many_device (c_eth_kzg.h;
  * tests/test_gpu_blob_cells.py, the expansion into problems is tests/blob_cells.py): problem b of every output is item b, 128 cells each
  * (leaves32: n x 128 x 32 bytes).  on_device = 0: blobs / commitments / proofs are the host form's pointer lists; 1: the device form's

@@ -47,6 +47,8 @@ SETUP_G1_POINTS = 4096
 SETUP_G2_POINTS = 65
 # flags of eth_kzg_amd_verify_cell_kzg_proof_batch_ex / _device_ex / _many_ex / _many_device_ex
 VERIFY_LEAF_TRANSCRIPT = 1
+# flag of eth_kzg_amd_blobs_to_data_columns / _device
+COLUMNS_VERIFY_PROOFS = 1
 
 EXPORTED_SYMBOLS = [
     "eth_kzg_das_context_new", "eth_kzg_das_context_free", "eth_kzg_free_error_message",
@@ -75,6 +77,7 @@ EXPORTED_SYMBOLS = [
     "eth_kzg_amd_verify_partial_data_columns", "eth_kzg_amd_verify_partial_data_columns_device",
     "eth_kzg_amd_verify_blob_cell_proofs_many", "eth_kzg_amd_verify_blob_cell_proofs_many_device",
     "eth_kzg_amd_compute_data_columns", "eth_kzg_amd_compute_data_columns_device",
+    "eth_kzg_amd_blobs_to_data_columns", "eth_kzg_amd_blobs_to_data_columns_device",
     "eth_kzg_amd_recover_data_columns", "eth_kzg_amd_recover_data_columns_device",
     "eth_kzg_amd_recover_data_columns_checked", "eth_kzg_amd_recover_data_columns_checked_device",
     "eth_kzg_amd_table_bytes", "eth_kzg_amd_window_bits", "eth_kzg_amd_tables_ready", "eth_kzg_amd_table_groups_ready", "eth_kzg_amd_table_build_info", "eth_kzg_amd_linmap_info",
@@ -99,6 +102,7 @@ TEST_HOOK_SYMBOLS = [
     "eth_kzg_amd_test_pairing_check_many", "eth_kzg_amd_test_search_stats", "eth_kzg_amd_test_g1_decode",
     "eth_kzg_amd_test_verify_data_columns_sums", "eth_kzg_amd_test_verify_partial_data_columns_sums",
     "eth_kzg_amd_test_blob_extension", "eth_kzg_amd_test_verify_blob_cell_proofs_sums",
+    "eth_kzg_amd_test_blob_to_columns",
 ]
 
 _lib = None
@@ -209,6 +213,8 @@ def load_library():
         "eth_kzg_amd_verify_partial_data_columns_device": [P, U64, P, U64, P, P, P, P, C.c_uint32, P, P, P],
         "eth_kzg_amd_compute_data_columns": [P, U64, P, P, P, P, P],
         "eth_kzg_amd_compute_data_columns_device": [P, U64, P, P, P, P, P, P],
+        "eth_kzg_amd_blobs_to_data_columns": [P, U64, P, P, P, C.c_uint32, P, P, P, P],
+        "eth_kzg_amd_blobs_to_data_columns_device": [P, U64, P, P, P, C.c_uint32, P, P, P, P, P],
         "eth_kzg_amd_recover_data_columns": [P, U64, U64, P, P, P, P, P],
         "eth_kzg_amd_recover_data_columns_device": [P, U64, U64, P, P, P, P, P, P],
         "eth_kzg_amd_recover_data_columns_checked": [P, U64, P, U64, P, P, P, P, P, P, P],
@@ -256,6 +262,7 @@ def load_library():
         "eth_kzg_amd_test_verify_data_columns_sums": [P, U64, C.c_int, P, U64, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P, P],
         "eth_kzg_amd_test_verify_partial_data_columns_sums": [P, U64, C.c_int, P, U64, P, P, P, P, C.c_uint32, P, P, P, P, P, P, P, P, U64, P, P, P, P],
         "eth_kzg_amd_test_blob_extension": [P, U64, P, P, P],
+        "eth_kzg_amd_test_blob_to_columns": [P, U64, P, U64, U64, C.c_int, P, P],
         "eth_kzg_amd_test_verify_blob_cell_proofs_sums": [P, U64, C.c_int, P, P, P, P, P, P, P, P, P, P, P, U64, P, P, P],
     }.items():
         if hasattr(lib, name):
@@ -781,6 +788,63 @@ class DASContext:
             self._ctx, n_blobs, C.c_void_p(d_blobs) if d_blobs else None, C.c_void_p(d_commitments) if d_commitments else None,
             C.c_void_p(d_cells) if d_cells else None, C.c_void_p(d_proofs) if d_proofs else None, st, C.c_void_p(stream) if stream else None))
         return list(st)[:n_blobs] if want_status else None
+
+    def blobs_to_data_columns(self, items, verify=False, want_cells=True, want_proofs=True, prefill=0):
+        """The call of a node that HOLDS the cell proofs (eth_kzg_amd_blobs_to_data_columns): items = [(blob, commitment, [128 cell
+        proofs]), ...] -> (verified list[bool] or None, status list, cells[c][i], proofs[c][i]) with c over the 128 columns; an output
+        that was not asked for is None.  verify=False: the commitment may be None (it is not read), status is compute_data_columns'
+        and proofs[c][i] is items[i][2][c] byte for byte.  verify=True (ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS): verified and status are
+        verify_blob_cell_proofs_many's.  The slots of an item that is refused or fails come back as they were: `prefill` bytes."""
+        n = len(items)
+        if not verify:
+            items = [(b, c if c is not None else bytes(48), ps) for b, c, ps in items]
+        ba, ca, pa, keep = DASContext._marshal_blob_cell_proofs(items)
+        cells, _ci, cpp = _out_ptrs(CELLS_PER_EXT_BLOB, n, BYTES_PER_CELL) if want_cells else (None, None, None)
+        proofs, _pi, ppp = _out_ptrs(CELLS_PER_EXT_BLOB, n, 48) if want_proofs else (None, None, None)
+        for out in (cells, proofs):
+            if out is not None:
+                out.fill(prefill)
+        ver = (C.c_bool * max(1, n))()
+        st = (C.c_int32 * max(1, n))()
+        self._check(self._lib.eth_kzg_amd_blobs_to_data_columns(
+            self._ctx, n, _vp(ba) if n else None, _vp(ca) if verify else None, _vp(pa) if n else None,
+            COLUMNS_VERIFY_PROOFS if verify else 0, _vp(cpp) if want_cells else None, _vp(ppp) if want_proofs else None,
+            ver if verify else None, st))
+        del keep
+        return ([bool(v) for v in ver][:n] if verify else None, list(st)[:n],
+                _split(cells, CELLS_PER_EXT_BLOB, n, BYTES_PER_CELL) if want_cells else None,
+                _split(proofs, CELLS_PER_EXT_BLOB, n, 48) if want_proofs else None)
+
+    def blobs_to_data_columns_device(self, n_blobs, d_blobs, d_commitments, d_proofs, d_out_cells, d_out_proofs, verify=False, want_status=True,
+                                     stream=None):
+        """The same on flat buffers in device memory (eth_kzg_amd_blobs_to_data_columns_device; integer device addresses): d_blobs
+        n_blobs*131072 (4-byte aligned), d_commitments n_blobs*48, d_proofs [n_blobs][128][48], d_out_cells [128][n_blobs][2048] (4-byte
+        aligned), d_out_proofs [128][n_blobs][48]; the outputs, and without verify the commitments, may be 0 / None.
+        -> (verified list[bool] or None, status list or None).  verify=False, want_status=False and a stream: returns without
+        synchronising."""
+        p = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        ver = (C.c_bool * max(1, n_blobs))() if verify else None
+        st = (C.c_int32 * max(1, n_blobs))() if want_status or verify else None
+        self._check(self._lib.eth_kzg_amd_blobs_to_data_columns_device(
+            self._ctx, n_blobs, p(d_blobs), p(d_commitments), p(d_proofs), COLUMNS_VERIFY_PROOFS if verify else 0, p(d_out_cells), p(d_out_proofs),
+            ver, st, p(stream)))
+        return [bool(v) for v in ver][:n_blobs] if verify else None, list(st)[:n_blobs] if st is not None else None
+
+    def test_blob_to_columns(self, blobs, n_total=None, b0=0, blob_half=True, guard=0xA5):
+        """eth_kzg_amd_test_blob_to_columns (hooks library): the kernel alone over a matrix of n_total blobs filled with `guard`
+        -> (matrix [128][n_total] of cell bytes, bad[n])"""
+        n = len(blobs)
+        n_total = n if n_total is None else n_total
+        if any(len(b) != BYTES_PER_BLOB for b in blobs):
+            raise KzgError("InvalidLength")
+        ba, keep = _alias_ptrs(list(blobs))
+        m = np.full(CELLS_PER_EXT_BLOB * max(1, n_total) * BYTES_PER_CELL, guard, dtype=np.uint8)
+        bad = (C.c_int32 * max(1, n))()
+        rc = self._lib.eth_kzg_amd_test_blob_to_columns(self._ctx, n, _vp(ba), n_total, b0, 1 if blob_half else 0, _vp(m), bad)
+        if rc != 0:
+            raise KzgError("test_blob_to_columns: status %d" % rc)
+        del keep
+        return _split(m, CELLS_PER_EXT_BLOB, n_total, BYTES_PER_CELL), list(bad)[:n]
 
     def recover_data_columns(self, column_indices, cells, want_cells=True, want_proofs=True, prefill=0):
         """The supernode's call (eth_kzg_amd_recover_data_columns): column_indices[j] and cells[j][i] (blob i in the j-th column given)

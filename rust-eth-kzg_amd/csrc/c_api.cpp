@@ -975,6 +975,71 @@ CResult eth_kzg_amd_verify_blob_cell_proofs_many_device(const DASContext* ctx, u
     if (!e) return err("InvalidInput: the three buffers are not device memory of one device of this context");
     return device_many(e, n, kzg::VerifyManyInput::device_blobs(d_blobs, d_commitments, d_proofs, (hipStream_t)hip_stream), verified, status);
 }
+// A block's data columns from blobs whose cell proofs the caller holds (data_columns.hip; under the flag verify_many.hip: the columns are
+// an output of the blob source of the many-verification).  Flags, count and NULL arrays first, before the context is looked at; then the
+// device list (host form: contiguous slices by blob, every slice writing its blobs' entries of the shared column arrays) or the owner of
+// EVERY device buffer given (device form).  Nothing here takes a lane or the context's big lock.
+static bool blobs_to_columns_args_ok(uint64_t n_blobs, bool blobs_null, bool commitments_null, bool proofs_null, uint32_t flags, bool out_proofs_given,
+                                     bool verified_null) {
+    if ((flags & ~(uint32_t)ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS) || n_blobs > MAX_BATCH) return false;
+    if (n_blobs == 0) return true;
+    const bool verify = (flags & ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS) != 0;
+    if (blobs_null || (proofs_null && (verify || out_proofs_given))) return false;
+    return !(verify && (commitments_null || verified_null));
+}
+CResult eth_kzg_amd_blobs_to_data_columns(const DASContext* ctx, uint64_t n_blobs, const uint8_t* const* blobs, const uint8_t* const* commitments,
+                                          const uint8_t* const* const* proofs, uint32_t flags, uint8_t* const* const* out_cells,
+                                          uint8_t* const* const* out_proofs, bool* verified, int32_t* status) {
+    if (!blobs_to_columns_args_ok(n_blobs, !blobs, !commitments, !proofs, flags, out_proofs != nullptr, !verified))
+        return err("InvalidInput: an unknown flag, more than 2^24 blobs, or a null array");
+    if (n_blobs == 0) return ok();  // (an empty call looks at nothing, the context included)
+    const bool verify = (flags & ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS) != 0;
+    auto items_ok = [&] {
+        for (uint64_t i = 0; i < n_blobs; i++) {
+            if (verify) verified[i] = false;
+            if (!blobs[i] || (verify && !commitments[i]) || (proofs && !proofs[i])) return false;
+            for (int k = 0; k < kzg::N_CELLS && proofs; k++)
+                if (!proofs[i][k]) return false;
+        }
+        return true;
+    };
+    if (!verify)
+        return sliced_call(ctx, n_blobs, MAX_BATCH, nullptr, status, items_ok, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int*) {
+            return batch_failure(e, e->blobs_to_data_columns_host((int)lo, (int)(hi - lo), blobs, proofs, out_cells, out_proofs, st));
+        });
+    auto in = kzg::VerifyManyInput::host_blobs(blobs, commitments, proofs);
+    in.out.cells = out_cells; in.out.proofs = out_proofs; in.out.n_total = n_blobs;
+    return sliced_call(ctx, n_blobs, MAX_BATCH, verified, status, items_ok, [&](kzg::Engine* e, uint64_t lo, uint64_t hi, int* st, int* ver) {
+        return many_failure(e, e->verify_cell_kzg_proof_batch_many(hi - lo, in.from(lo), ver + lo, st + lo));
+    });
+}
+CResult eth_kzg_amd_blobs_to_data_columns_device(const DASContext* ctx, uint64_t n_blobs, const uint8_t* d_blobs, const uint8_t* d_commitments,
+                                                 const uint8_t* d_proofs, uint32_t flags, uint8_t* d_out_cells, uint8_t* d_out_proofs, bool* verified,
+                                                 int32_t* status, void* hip_stream) {
+    if (!blobs_to_columns_args_ok(n_blobs, !d_blobs, !d_commitments, !d_proofs, flags, d_out_proofs != nullptr, !verified))
+        return err("InvalidInput: an unknown flag, more than 2^24 blobs, or a null array");
+    if (n_blobs == 0) return ok();
+    live(ctx);
+    const bool verify = (flags & ETH_KZG_AMD_COLUMNS_VERIFY_PROOFS) != 0;
+    for (uint64_t i = 0; i < n_blobs && verify; i++) verified[i] = false;
+    const void* ptrs[5] = {d_blobs};
+    int n_ptrs = 1;
+    for (const void* p : {(const void*)(verify ? d_commitments : nullptr), (const void*)d_proofs, (const void*)d_out_cells, (const void*)d_out_proofs})
+        if (p) ptrs[n_ptrs++] = p;  // (without the flag the commitments are not read: not resolved either)
+    kzg::Engine* e = engine_of_device_pointers(ctx, ptrs, n_ptrs);
+    if (!e) return err("InvalidInput: the buffers are not device memory of one device of this context");
+    if (verify) {
+        auto in = kzg::VerifyManyInput::device_blobs(d_blobs, d_commitments, d_proofs, (hipStream_t)hip_stream);
+        in.out.d_cells = d_out_cells; in.out.d_proofs = d_out_proofs; in.out.n_total = n_blobs;
+        return device_many(e, n_blobs, in, verified, status);
+    }
+    static_assert(sizeof(int32_t) == sizeof(int), "status array");
+    const bool sync = hip_stream == nullptr;
+    if (e->blobs_to_data_columns_device((int)n_blobs, d_blobs, d_proofs, d_out_cells, d_out_proofs, (int*)status, (hipStream_t)hip_stream, sync))
+        return device_err(e);
+    if (status) for (uint64_t i = 0; i < n_blobs; i++) status[i] = status[i] ? kzg::ERR_SCALAR : 0;
+    return ok();
+}
 void eth_kzg_amd_set_profiling(const DASContext* ctx, int on) { eng(ctx)->set_profiling(on != 0); }
 int eth_kzg_amd_get_stage_times(const DASContext* ctx, double* ms, uint64_t* launches, int n) {
     double m[kzg::Engine::ST_COUNT];

@@ -237,6 +237,13 @@ int eth_kzg_amd_test_blob_extension(const DASContext* ctx, uint64_t n, const uin
         if (!blobs[b]) return kzg::ERR_INPUT;
     return eng(ctx)->test_blob_extension((int)n, blobs, out_cells, out_bad);
 }
+int eth_kzg_amd_test_blob_to_columns(const DASContext* ctx, uint64_t n, const uint8_t* const* blobs, uint64_t n_total, uint64_t b0, int blob_half,
+                                     uint8_t* matrix, int32_t* out_bad) {
+    if (n < 1 || n > 1024 || n_total > 4096 || b0 > n_total || n > n_total - b0 || !blobs || !matrix || !out_bad) return kzg::ERR_INPUT;
+    for (uint64_t b = 0; b < n; b++)
+        if (!blobs[b]) return kzg::ERR_INPUT;
+    return eng(ctx)->test_blob_to_columns((int)n, blobs, n_total, b0, blob_half, matrix, out_bad);
+}
 // the tap on a pass of the blob source of the cell many-verification (eth_kzg_amd_verify_blob_cell_proofs_many / _many_device)
 int eth_kzg_amd_test_verify_blob_cell_proofs_sums(const DASContext* ctx, uint64_t n, int on_device, const void* blobs, const void* commitments,
                                                   const void* proofs, int32_t* verified, int32_t* status, int32_t* form4, uint8_t* sums96, uint32_t* rho,

@@ -106,6 +106,109 @@ int Engine::compute_data_columns_host(int lo, int n, const uint8_t* const* blobs
     return OK;
 }
 
+// ---- the call of a node that holds the proofs --------------------------------------------------------------------------------------
+// eth_kzg_amd_blobs_to_data_columns without its flag (with it: verify_many.hip, an output of the blob source).  No FK20, so nothing of
+// the prover's stages: ONE launch of k_blob_to_columns computes every blob's cells inside the CU and stores them at their column
+// addresses, one launch of k_proofs_to_columns re-orders the proofs the caller holds.  Of a work set the call takes the streams, the
+// staging of the host form and the status words below; coefficients, scalars and point arrays are never allocated for it.
+static void ensure_sidecar_status(Work& w, int n) {
+    if (n <= w.sc_cap) return;
+    if (w.sc_status) { HIPCK(hipFree(w.sc_status)); w.sc_status = nullptr; }
+    w.sc_cap = 0;
+    const int cap = ((n + 63) / 64) * 64;
+    HIPCK(hipMalloc(&w.sc_status, (size_t)cap * sizeof(int)));
+    w.sc_cap = cap;
+}
+int Engine::blobs_to_data_columns_device(int n, const uint8_t* d_blobs, const uint8_t* d_proofs, uint8_t* d_cells, uint8_t* d_out_proofs, int* h_status,
+                                         hipStream_t st, bool sync) {
+    if (n <= 0) return OK;
+    Work* held = nullptr;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        Work& w = lease_work(1, NW - 1);
+        held = &w;
+        if (!st) {  // NULL: the library's stream, ordered behind whatever the caller has queued on the default stream so far
+            st = w.stream;
+            HIPCK(hipEventRecord(w.ev_in, nullptr));
+            HIPCK(hipStreamWaitEvent(st, w.ev_in, 0));
+        }
+        const launch::Columns cols{(size_t)n, 0};
+        // the status words are the set's: they are idle whenever the set is free, because a call that asks for them leaves synchronised
+        if (h_status) {
+            ensure_sidecar_status(w, n);
+            HIPCK(hipMemsetAsync(w.sc_status, 0, (size_t)n * sizeof(int), st));
+        }
+        if (d_cells || h_status) launch::blob_to_columns(n, d_blobs, d_cells, cols, /*blob_half=*/true, h_status ? w.sc_status : nullptr, d_w29_, n_inv4096_, st);
+        if (d_out_proofs) launch::proofs_to_columns(n, d_proofs, d_out_proofs, cols, st);
+        if (h_status) HIPCK(hipMemcpyAsync(h_status, w.sc_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCK(hipGetLastError());
+        if (sync || h_status) HIPCK(hipStreamSynchronize(st));
+        release_work(w);
+        held = nullptr;
+    } catch (const std::exception& e) {
+        if (held) {
+            (void)hipStreamSynchronize(st);
+            release_work(*held);
+        }
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
+// Host pointers: chunks of at most CHUNK blobs through the work set's staging.  Every blob goes up ONCE; the kernel writes rows 64..127
+// of the chunk's [128][ns] matrix only, and that half alone comes down (128 KB per blob): cells 0..63 are the caller's own blob bytes,
+// which the helper threads copy across on the host together with the proofs while nothing of them crosses the link.
+int Engine::blobs_to_data_columns_host(int lo, int n, const uint8_t* const* blobs, const uint8_t* const* const* proofs, uint8_t* const* const* out_cells,
+                                       uint8_t* const* const* out_proofs, int* h_status) {
+    if (n <= 0) return OK;
+    constexpr int CHUNK = 256;
+    HostPool* pool = n >= 4 ? ensure_host_pool() : nullptr;  // a couple of blobs: everything on the calling thread
+    const int T = pool ? pool->threads() + 1 : 1;
+    Work* held = nullptr;
+    try {
+        HIPCK(hipSetDevice(dev_));
+        Work& w = lease_work(1, NW - 1);
+        held = &w;
+        for (int s0 = 0; s0 < n; s0 += CHUNK) {
+            const int ns = std::min(CHUNK, n - s0), first = lo + s0;
+            ensure_staging(w, ns);
+            ensure_sidecar_status(w, ns);
+            parallel_for(ns, T, pool, [&](int b) { memcpy(w.h_in + (size_t)b * BYTES_PER_BLOB, blobs[first + b], BYTES_PER_BLOB); });
+            HIPCK(hipStreamWaitEvent(w.stream, w.done, 0));  // (the staging is shared with the prover's host forms)
+            HIPCK(hipMemcpyAsync(w.d_in, w.h_in, (size_t)ns * BYTES_PER_BLOB, hipMemcpyHostToDevice, w.stream));
+            HIPCK(hipMemsetAsync(w.sc_status, 0, (size_t)ns * sizeof(int), w.stream));
+            const launch::Columns cols{(size_t)ns, 0};
+            const size_t half = (size_t)(N_CELLS / 2) * ns * BYTES_PER_CELL;  // rows 0..63 of the chunk's matrix
+            launch::blob_to_columns(ns, w.d_in, out_cells ? w.d_cells : nullptr, cols, /*blob_half=*/false, w.sc_status, d_w29_, n_inv4096_, w.stream);
+            HIPCK(hipMemcpyAsync(w.h_status, w.sc_status, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, w.stream));
+            if (out_cells) HIPCK(hipMemcpyAsync(w.h_cells + half, w.d_cells + half, half, hipMemcpyDeviceToHost, w.stream));
+            HIPCK(hipEventRecord(w.done, w.stream));
+            HIPCK(hipGetLastError());
+            HIPCK(hipStreamSynchronize(w.stream));
+            parallel_for(ns, T, pool, [&](int b) {
+                if (h_status) h_status[first + b] = w.h_status[b] ? ERR_SCALAR : OK;
+                if (w.h_status[b]) return;  // a refused blob: its slots stay as the caller left them
+                for (int c = 0; c < N_CELLS && out_cells; c++) {
+                    const uint8_t* from = c < N_CELLS / 2 ? blobs[first + b] + (size_t)c * BYTES_PER_CELL : w.h_cells + ((size_t)c * ns + b) * BYTES_PER_CELL;
+                    memcpy(out_cells[c][first + b], from, BYTES_PER_CELL);
+                }
+                for (int c = 0; c < N_CELLS && out_proofs; c++) memcpy(out_proofs[c][first + b], proofs[first + b][c], 48);
+            });
+        }
+        release_work(w);
+        held = nullptr;
+    } catch (const std::exception& e) {
+        if (held) {
+            (void)hipStreamSynchronize(held->stream);
+            release_work(*held);
+        }
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 // ---- the supernode's call ------------------------------------------------------------------------------------------------------
 // (the status of an index list: verify_host.hpp, column_list_status -- c_api.cpp asks it too, before it resolves a pointer)
 // The decoder's index arrays for the column source: list entry (column rank j, blob i) lands in slot i * 128 + column_indices[j] of

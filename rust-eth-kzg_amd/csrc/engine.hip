@@ -381,7 +381,7 @@ void Engine::teardown() noexcept {
         if (P.d_naf && P.owns_naf) hipFree(P.d_naf);
     }
     for (Work& w : work_) {
-        void* dev[] = {w.coeffs, w.canon, w.scalars, w.X, w.status, w.circ_table, w.slp_arena, w.d_in, w.d_cells, w.d_proofs, w.col_canon, w.col_sums, w.d_comm};
+        void* dev[] = {w.coeffs, w.canon, w.scalars, w.X, w.status, w.circ_table, w.slp_arena, w.d_in, w.d_cells, w.d_proofs, w.col_canon, w.col_sums, w.d_comm, w.sc_status};
         for (void* p : dev)
             if (p) hipFree(p);
         void* pin[] = {w.h_in, w.h_cells, w.h_proofs, w.h_status, w.h_comm};

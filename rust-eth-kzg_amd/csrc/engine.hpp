@@ -92,6 +92,16 @@ struct VerifyManyInput {
     bool from_blobs = false, blobs_device = false;
     const uint8_t *const *blobs = nullptr, *const *blob_commitments = nullptr;
     const uint8_t* d_blobs = nullptr;
+    // (the blob source; eth_kzg_amd_blobs_to_data_columns under its flag) the call also BUILDS the block's data columns from what the pass
+    // holds anyway: item i's 128 cells and its 128 proofs as the caller gave them, at [c][first + i] of the WHOLE call's arrays of n_total
+    // blobs -- pointer tables on the host (written for the items that pass, behind the verdicts) or matrices in this GPU's HBM
+    // ([128][n_total][2048], 4-byte aligned, and [128][n_total][48]: written for every item of a pass, behind its extension step).
+    // Each may be null.
+    struct BlobColumnsOut {
+        uint8_t *const *const *cells = nullptr, *const *const *proofs = nullptr;
+        uint8_t *d_cells = nullptr, *d_proofs = nullptr;
+        uint64_t n_total = 0, first = 0;
+    } out;
     static VerifyManyInput lists(const uint64_t* n_commitments, const uint8_t* const* const* commitments, const uint64_t* n_indices,
                                  const uint64_t* const* cell_indices, const uint64_t* n_cells, const uint8_t* const* const* cells,
                                  const uint64_t* n_proofs, const uint8_t* const* const* proofs, bool leaf) {
@@ -146,6 +156,7 @@ struct VerifyManyInput {
         if (from_blobs) {  // (one entry per blob in every array: the arrays themselves move)
             if (blobs_device) { s.d_blobs += lo * 131072; s.d_commitments += lo * 48; s.d_proofs += lo * 128 * 48; }
             else { s.blobs += lo; s.blob_commitments += lo; s.proofs += lo; }
+            s.out.first += lo;
             return s;
         }
         if (columns) {
@@ -281,6 +292,9 @@ struct Work {
     void *col_canon = nullptr, *col_sums = nullptr;
     int comm_cap = 0;
     uint8_t *d_comm = nullptr, *h_comm = nullptr;
+    // blobs_to_data_columns (data_columns.hip), which uses nothing of the set but its streams and events: its own status words
+    int sc_cap = 0;
+    int* sc_status = nullptr;
 };
 // (HostPool, the combiner, pass-slot and lane leases: host_sync.hpp -- HIP-free, driven under ThreadSanitizer on the CPU)
 class Engine {
@@ -342,6 +356,15 @@ public:
     // i a blob of the call); h_status: the whole call's as well.  Outputs of a refused blob are left untouched.
     int compute_data_columns_host(int lo, int n, const uint8_t* const* blobs, uint8_t* const* out_commitments, uint8_t* const* const* out_cells,
                                   uint8_t* const* const* out_proofs, int* h_status);
+    // The call of a node that HOLDS the proofs (c_eth_kzg.h: eth_kzg_amd_blobs_to_data_columns without its flag; the flagged forms are an
+    // output of the many-verification's blob source, VerifyManyInput::out): d_cells [128][n][2048] straight from k_blob_to_columns,
+    // d_out_proofs [128][n][48] = d_proofs [n][128][48] re-ordered, each may be null; status, stream and sync rules of
+    // compute_data_columns_device.  Uses none of the prover's workspace.  Host form: the slice [lo, lo + n) of the whole call's arrays;
+    // every blob goes up once, only cells 64..127 come down, the rest is copied on the host from the caller's own bytes.
+    int blobs_to_data_columns_device(int n, const uint8_t* d_blobs, const uint8_t* d_proofs, uint8_t* d_cells, uint8_t* d_out_proofs, int* h_status,
+                                     hipStream_t stream, bool sync);
+    int blobs_to_data_columns_host(int lo, int n, const uint8_t* const* blobs, const uint8_t* const* const* proofs, uint8_t* const* const* out_cells,
+                                   uint8_t* const* const* out_proofs, int* h_status);
     // The supernode's call: all 128 columns of R blobs from n_columns of them.  d_cells [n_columns][R][2048] in HBM, column_indices on the
     // host; outputs as above.  ONE vanishing polynomial per call.  A bad list marks every blob ERR_INPUT before anything is launched.
     int recover_data_columns_device(int R, uint64_t n_columns, const uint64_t* column_indices, const uint8_t* d_cells, uint8_t* d_out_cells,
@@ -510,6 +533,9 @@ public:
     int test_blob_eval_at(int n, const uint8_t* const* blobs, const uint8_t* zs_be32, uint8_t* out_ys_be32, int32_t* out_bad);
     // k_blob_to_extension alone behind the copy of cells 0..63: n blobs from the host -> out_cells[n][128][2048], bad[n] (the status word)
     int test_blob_extension(int n, const uint8_t* const* blobs, uint8_t* out_cells, int32_t* out_bad);
+    // k_blob_to_columns alone: n blobs from the host as blobs [b0, b0 + n) of a matrix of n_total; matrix [128][n_total][2048] on the host goes
+    // up as it is (the caller's guard pattern), one launch, and comes down; bad[n]: the status words
+    int test_blob_to_columns(int n, const uint8_t* const* blobs, uint64_t n_total, uint64_t b0, int blob_half, uint8_t* matrix, int32_t* out_bad);
     // k_pairing_check and the host's checks on the same n pairs (compressed G1, n x 2 x 48 bytes) against key pair `key` (0: [tau^64]_2, -[1]_2;
     // 1: [tau]_2, -[1]_2); flags: see include/c_eth_kzg_test_hooks.h.  The Miller values (may be null): n x 576 bytes each
     int test_pairing_check_many(int key, uint64_t n, const uint8_t* pairs, int flags, int8_t* out_gpu, int8_t* out_host, uint8_t* out_miller_gpu,

@@ -794,6 +794,32 @@ int Engine::test_blob_extension(int n, const uint8_t* const* blobs, uint8_t* out
     return OK;
 }
 
+// k_blob_to_columns on its own: the blobs and the caller's matrix (its guard pattern) up, one launch over blobs [b0, b0 + n) of n_total, the
+// matrix down.  The caller (c_api_hooks.cpp) has checked b0 + n <= n_total: every address the launch forms lies inside the matrix.
+int Engine::test_blob_to_columns(int n, const uint8_t* const* blobs, uint64_t n_total, uint64_t b0, int blob_half, uint8_t* matrix, int32_t* out_bad) {
+    std::lock_guard<std::recursive_mutex> lk(mu_);
+    try {
+        HIPCK(hipSetDevice(dev_));
+        hipStream_t st = stream_;
+        const size_t m_bytes = (size_t)N_CELLS * n_total * BYTES_PER_CELL;
+        PoolBuf d_blobs(*this, (size_t)n * BYTES_PER_BLOB), d_m(*this, m_bytes), d_bad(*this, (size_t)n * sizeof(int));
+        for (int b = 0; b < n; b++)
+            HIPCK(hipMemcpyAsync((uint8_t*)d_blobs.p + (size_t)b * BYTES_PER_BLOB, blobs[b], BYTES_PER_BLOB, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(d_m.p, matrix, m_bytes, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemsetAsync(d_bad.p, 0, (size_t)n * sizeof(int), st));  // the status word is OR-ed into
+        launch::blob_to_columns(n, (const uint8_t*)d_blobs.p, (uint8_t*)d_m.p, launch::Columns{(size_t)n_total, (size_t)b0}, blob_half != 0, (int*)d_bad.p, d_w29_,
+                                n_inv4096_, st);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(matrix, d_m.p, m_bytes, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(out_bad, d_bad.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+        SYNC_CHECKED(st);
+    } catch (const std::exception& e) {
+        set_error(e);
+        return ERR_DEVICE;
+    }
+    return OK;
+}
+
 // The Reed-Solomon decoder of recovery on its own: the masks, slots and cell bytes staged as recover_batch_to_coeffs (list form) or
 // recover_cells_and_kzg_proofs_device (flat form) stage them, then rs_decode with its tap.  The caller (c_api_hooks.cpp) has validated
 // the counts and indices.  Outputs canonical big-endian.

@@ -327,6 +327,77 @@ struct BlobsOnly {
     uint8_t* blobs;
     __device__ __forceinline__ uint8_t* fr(int b, int, int e) const { return blobs + ((size_t)b * N_BLOB + e) * 32; }
 };
+// All 128 cells of a blob at their SIDECAR addresses WITHOUT LEAVING THE CU (eth_kzg_amd_blobs_to_data_columns: the caller holds the
+// proofs already, so nothing of FK20 runs): k_blob_to_extension's image, transforms, barriers and value bounds (comments there), read
+// from the caller's blobs where they lie and written through CellsByColumn -- no coefficient goes to HBM, no workspace, no [blob][128]
+// intermediate.  grid = n_blobs, block = 1024, dynamic LDS = 144 KiB.
+//   kBlobHalf   the input stage also stores cells 0..63, which ARE the four elements a thread has just loaded: they wait in registers for
+//               the verdict on the blob and leave before the transform starts.  false (the host form, whose helper threads copy that
+//               half from the caller's own bytes): rows 0..63 of the matrix are not touched
+//   status      (may be null) status[b] |= 1 if the blob holds an element >= r.  Such a blob writes NOTHING: its slots keep what they held
+// Every output byte is written once: element e of half h at dst.fr(b, h, e), 32 bytes, 4-byte aligned like the blob.
+template <bool kBlobHalf>
+__global__ __launch_bounds__(1024) void k_blob_to_columns(const uint8_t* __restrict__ blobs, CellsByColumn dst, int* __restrict__ status,
+                                                         const Fr29* __restrict__ w29, NttConsts K) {
+    extern __shared__ uint32_t s[];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const uint8_t* blob = blobs + (size_t)b * BYTES_PER_BLOB;
+    Fr own[4];
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int e = tid + 1024 * k;
+        own[k] = load_fr_be(blob + 32 * e);
+        bad |= geq_mod<FrParams>(own[k].v);
+        lds_store(s, e, fr29_from_plain(own[k]));  // the integer itself: < 2^256 < 3r, normalised limbs
+    }
+    const bool refused = __syncthreads_or(bad) != 0;  // the barrier between the input stage and the transform
+    if (refused) {                                    // uniform over the block
+        if (tid == 0 && status) atomicOr(&status[b], 1);
+        return;
+    }
+    if (!dst.cells) return;  // a caller that wants the status words alone (uniform over the grid)
+    if (kBlobHalf) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) store_fr_be(dst.fr(b, 0, tid + 1024 * k), own[k]);  // the bytes as they came: any 256-bit value round-trips
+    }
+    ntt4096_dit_inverse(s, w29);  // < 27 r; thread tid's own unit left tid + 1024 k
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) {
+        const int e = tid + 1024 * k;
+        lds_store(s, e, fr29_mul(lds_load(s, e), w29[e]));  // 27 x 1 <= 64: n a_e w8192^e, < 2r
+    }
+    ntt4096_ct_forward(s, w29);  // < 26 r; its first pass reads what this thread has just stored
+    for (int e = tid; e < N_BLOB; e += 1024)
+        store_fr_be(dst.fr(b, 1, e), fr_words_of(fr29_reduce_once(fr29_mul(lds_load(s, e), K.ninv_plain))));  // 26 x 1 <= 64: X n / n = the value
+}
+// The flagged form of the same call (verify_many.hip): the pass has every blob's 128 cells in its arena, blob-major, for the leaves and
+// the decoding; this copies them to their sidecar addresses behind the extension step.  src [n][128][2048], 16-byte aligned (the
+// arena's); grid = (n, 128), block = 128: a block moves one cell, a thread 16 bytes of it; vec16: the matrix is 16-byte aligned too
+// (it is 4-byte aligned always, like the output of k_blob_to_columns).
+__global__ __launch_bounds__(128) void k_cells_to_columns(const uint8_t* __restrict__ src, CellsByColumn dst, int vec16) {
+    const int b = blockIdx.x, c = blockIdx.y, t = threadIdx.x;
+    const uint4 v = *reinterpret_cast<const uint4*>(src + ((size_t)b * N_CELLS + c) * BYTES_PER_CELL + 16 * t);
+    uint8_t* to = dst.fr(b, c >> 6, (c & 63) << 6) + 16 * t;  // element 0 of cell c
+    if (vec16) {
+        *reinterpret_cast<uint4*>(to) = v;
+    } else {
+        uint32_t* w = reinterpret_cast<uint32_t*>(to);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+}
+// The proofs a caller holds per blob, [n][128][48], to where the sidecars carry them: dst [128][n_total][48], blob b of this launch being
+// blob b0 + b.  A plain re-ordering: the 48 bytes are never decoded.  T = uint32_t where both arrays are 4-byte aligned (a proof is 12
+// words), else uint8_t: any byte address.  A thread moves one unit; units = n * 128 * 48 / sizeof(T).
+template <class T>
+__global__ __launch_bounds__(256) void k_proofs_to_columns(const T* __restrict__ src, T* __restrict__ dst, size_t n_total, size_t b0, size_t units) {
+    constexpr size_t U = 48 / sizeof(T);
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= units) return;
+    const size_t p = i / U, j = i % U, b = p / N_CELLS, k = p % N_CELLS;
+    dst[(k * n_total + b0 + b) * U + j] = src[i];
+}
+
 template <class Dst>
 __global__ __launch_bounds__(1024) void k_coeffs_to_cells(const Fr* __restrict__ coeffs, Dst dst, const Fr29* __restrict__ w29) {
     extern __shared__ uint32_t s[];
@@ -507,6 +578,8 @@ void init_attributes() {
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_coeffs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_eval_at), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_extension), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_columns<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(k_blob_to_columns<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByBlob>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<CellsByColumn>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
     hipFuncSetAttribute(reinterpret_cast<const void*>(k_coeffs_to_cells<BlobsOnly>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_NTT29);
@@ -551,6 +624,26 @@ void blob_eval_at(int n, const uint8_t* blobs, const void* z_mont, uint8_t* y_be
 }
 void blob_to_extension(int n, uint8_t* cells, int* status, const void* w29, const Fr8& n_inv, hipStream_t st) {
     if (n > 0) k_blob_to_extension<<<n, 1024, LDS_NTT29, st>>>(cells, status, (const Fr29*)w29, ntt_consts(n_inv));
+}
+void blob_to_columns(int n, const uint8_t* blobs, uint8_t* cells, const Columns& cols, bool blob_half, int* status, const void* w29, const Fr8& n_inv,
+                     hipStream_t st) {
+    if (n <= 0) return;
+    const CellsByColumn dst{cells, cols.n_total, cols.b0};
+    if (blob_half) k_blob_to_columns<true><<<n, 1024, LDS_NTT29, st>>>(blobs, dst, status, (const Fr29*)w29, ntt_consts(n_inv));
+    else k_blob_to_columns<false><<<n, 1024, LDS_NTT29, st>>>(blobs, dst, status, (const Fr29*)w29, ntt_consts(n_inv));
+}
+void cells_to_columns(int n, const uint8_t* src, uint8_t* cells, const Columns& cols, hipStream_t st) {
+    if (n <= 0) return;
+    const int vec16 = ((uintptr_t)cells & 15) == 0;  // (every cell of the matrix starts a multiple of 2048 from there)
+    k_cells_to_columns<<<dim3(n, N_CELLS), 128, 0, st>>>(src, CellsByColumn{cells, cols.n_total, cols.b0}, vec16);
+}
+void proofs_to_columns(int n, const uint8_t* proofs, uint8_t* out, const Columns& cols, hipStream_t st) {
+    if (n <= 0) return;
+    const size_t bytes = (size_t)n * N_CELLS * 48;
+    if ((((uintptr_t)proofs | (uintptr_t)out) & 3) == 0)
+        k_proofs_to_columns<uint32_t><<<(unsigned)((bytes / 4 + 255) / 256), 256, 0, st>>>((const uint32_t*)proofs, (uint32_t*)out, cols.n_total, cols.b0, bytes / 4);
+    else
+        k_proofs_to_columns<uint8_t><<<(unsigned)((bytes + 255) / 256), 256, 0, st>>>(proofs, out, cols.n_total, cols.b0, bytes);
 }
 void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st, const Columns* cols) {
     if (cols) k_coeffs_to_cells<<<dim3(n, 2), 1024, LDS_NTT29, st>>>((const Fr*)coeffs, CellsByColumn{cells, cols->n_total, cols->b0}, (const Fr29*)w29);

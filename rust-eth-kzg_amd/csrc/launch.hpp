@@ -42,6 +42,15 @@ struct Columns {
     size_t n_total, b0;
 };
 void coeffs_to_cells(int n, const void* coeffs, uint8_t* cells, const void* w29, hipStream_t st, const Columns* cols = nullptr);
+// eth_kzg_amd_blobs_to_data_columns: the three kernels that put what a caller with proofs in hand needs at its sidecar address.
+// blob_to_columns (k_blob_to_columns): all 128 cells of n blobs (4-byte aligned, read where they lie) inside the CU, straight into the
+// column matrix `cells` (4-byte aligned); blob_half = false leaves rows 0..63 alone; status (may be null) gets bit 0 set for a blob with
+// an element >= r, which writes nothing.  cells_to_columns: the same matrix from n extended blobs [n][128][2048] (16-byte aligned).
+// proofs_to_columns: proofs [n][128][48] -> out [128][n_total][48], both from any byte address.
+void blob_to_columns(int n, const uint8_t* blobs, uint8_t* cells, const Columns& cols, bool blob_half, int* status, const void* w29, const Fr8& n_inv,
+                     hipStream_t st);
+void cells_to_columns(int n, const uint8_t* src, uint8_t* cells, const Columns& cols, hipStream_t st);
+void proofs_to_columns(int n, const uint8_t* proofs, uint8_t* out, const Columns& cols, hipStream_t st);
 // cells 0..63 only, blob-major: blobs = [n][131072], the bytes of the n blobs the coefficients belong to (checked recovery's out_blobs)
 void coeffs_to_blobs(int n, const void* coeffs, uint8_t* blobs, const void* w29, hipStream_t st);
 // every scalar leaves as its balanced GLV halves (what launch::glv_split would make of it)

@@ -226,12 +226,14 @@ struct Engine::CellManyPass {
         stage();
         upload();
         extend();
+        columns();
         leaves();
         decode();
         challenges();
         products_and_sums();
         fold_and_sums_down();
         verdicts();
+        columns_out();
     }
     // the slot's blocks, large enough; stale contents of the persistent slab must fail closed: status words and result slots are poisoned
     void arena() {
@@ -319,6 +321,38 @@ struct Engine::CellManyPass {
     // has zeroed on this stream) and gets zeros, so that the leaves and the decoding read nothing stale
     void extend() {
         if (S.blobs) launch::blob_to_extension(Bc, db + L.off_cells, (int*)(db + L.off_ste), e.d_w29_, e.n_inv4096_, st);
+    }
+    // ---- (the blob source of a call that also builds the block's data columns: S.in.out, eth_kzg_amd_blobs_to_data_columns under its flag)
+    // The arena holds every item's 128 cells blob-major, which the leaves and the decoding need as they are; the column matrix is a COPY of
+    // them behind the extension step (a copy kernel, not a second destination of k_blob_to_extension, whose launch stays
+    // what it was), and the proofs are re-ordered from where the pass holds them.  Device source: both into the caller's matrices, for
+    // every item of the pass (the slots of an item that fails are unspecified).  Host source: only the extension halves come down, into the
+    // halves of the pinned slab's slices that the staging left empty; columns_out hands them over once the verdicts are in.
+    void columns() {
+        const VerifyManyInput::BlobColumnsOut& o = S.in.out;
+        if (!S.blobs) return;
+        const launch::Columns cols{(size_t)o.n_total, (size_t)o.first + (size_t)b0};
+        if (o.d_cells) launch::cells_to_columns(Bc, db + L.off_cells, o.d_cells, cols, st);
+        if (o.d_proofs) launch::proofs_to_columns(Bc, db + L.off_p, o.d_proofs, cols, st);
+        constexpr size_t slice = 2 * (size_t)BYTES_PER_BLOB;
+        if (o.cells)
+            HIPCK(hipMemcpy2DAsync(hb + L.off_cells + blob_cells_slice(0).ext_at, slice, db + L.off_cells + blob_cells_slice(0).ext_at, slice, BYTES_PER_BLOB,
+                                   (size_t)Bc, hipMemcpyDeviceToHost, st));
+    }
+    // ---- (the same, host source) behind the verdicts: the slots of the items that PASSED, and of no other.  Cells 0..63 and the proofs are
+    // the caller's own bytes, copied on the host; cells 64..127 are what columns() brought down (fold_and_sums_down has synchronised)
+    void columns_out() {
+        const VerifyManyInput::BlobColumnsOut& o = S.in.out;
+        if (!S.blobs || S.device || (!o.cells && !o.proofs)) return;
+        parallel_for(Bc, T, pool, [&](int i) {
+            if (!ver[i] || stat[i] != OK) return;
+            const size_t at = (size_t)o.first + (size_t)b0 + (size_t)i;
+            const uint8_t *const blob = S.blob(b0 + i), *const ext = hb + L.off_cells + blob_cells_slice((size_t)i).ext_at;
+            for (int c = 0; c < N_CELLS && o.cells; c++)
+                memcpy(o.cells[c][at], c < N_CELLS / 2 ? blob + (size_t)c * BYTES_PER_CELL : ext + (size_t)(c - N_CELLS / 2) * BYTES_PER_CELL, BYTES_PER_CELL);
+            for (int c = 0; c < N_CELLS && o.proofs; c++) memcpy(o.proofs[c][at], S.proof(b0 + i, c), 48);
+        });
+        lap("columns out (host)");
     }
     // ---- (leaf-hashed) the leaves of all the pass's cells straight out of the arena (its offsets are multiples of 256: the kernel's
     // 16-byte loads), in order on the pass's stream (a fifth stream: lease_pass_slot).  The event: what the host threads hash is down.
